@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W                               # BASELINE configs[2], weak scaling
     python bench.py --gpus N --samples 64 --k 10 --ctx edit --samples-per-gpu 8   # BASELINE configs[3], strong scaling
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs bench_outputs   # + the last timed region's (u, s, vT) as bench_outputs/*.npy
 
 A *step* is one power iteration for k directions on one x_t sample: k JVPs + k VJPs through the U-Net prefix up to the
 tap + the k x N re-orthonormalisation (reference src/utils/utils.py:756-808).  A sample's job is one primal (stash) pass
@@ -69,6 +70,9 @@ def parse():
     ap.add_argument("--no-strong-leg", action="store_true", help="skip the BASELINE configs[3] leg (64 samples, k = 10, edit ctx, sharded over the ranks)")
     ap.add_argument("--strong-samples", type=int, default=64)
     ap.add_argument("--profile-run", action="store_true", help="for rocprofv3 runs: headline region only, once (no repeats, no extra legs, no CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the (u, s, vT) of every sample of the last timed region as DIR/{u,s,vT}.npy (float32, "
+                         "samples in id order; a fixed seeded subset of the samples when all of them exceed 60 MiB, i.e. at most 64 MB in all)")
     a = ap.parse_args()
     if a.profile_run:
         a.repeats, a.no_cpu_baseline, a.no_roofline, a.no_unet_forward, a.no_strong_leg, a.no_sd21_leg = 1, True, True, True, True, True
@@ -347,6 +351,37 @@ def sd21_leg(dev):
     return out
 
 
+DUMP_BYTES = 60 << 20                                   # data bytes of a dump: under 64 MB with the .npy headers, in either unit
+
+
+def dump_outputs(out_dir, allres):
+    """The arrays the timed path hands its caller, per sample id: u [N_h, k], s [k], vT [k, N_in] -> DIR/u.npy [n, N_h, k], DIR/s.npy [n, k],
+    DIR/vT.npy [n, k, N_in], float32, n samples in id order.  Above DUMP_BYTES in all, a fixed seeded subset of the samples (the same for the
+    same arguments) and, if one sample alone is larger, a fixed seeded subset of the rows of u / columns of vT.  -> dict for the JSON line."""
+    import numpy as np
+    ids = sorted(allres)
+    u0, s0, v0 = allres[ids[0]]
+    n_h, k, n_in = u0.shape[0], s0.shape[0], v0.shape[1]
+    rng = np.random.default_rng(0)
+    rows, cols = np.arange(n_h), np.arange(n_in)
+    per = 4 * k * (n_h + 1 + n_in)
+    if per > DUMP_BYTES:                                  # one sample alone is too large: keep a seeded share of its u rows and vT columns
+        f = (DUMP_BYTES // (4 * k) - 1) / (n_h + n_in)
+        rows = np.sort(rng.choice(n_h, max(1, int(n_h * f)), replace=False))
+        cols = np.sort(rng.choice(n_in, max(1, int(n_in * f)), replace=False))
+        per = 4 * k * (rows.size + 1 + cols.size)
+    keep = ids if per * len(ids) <= DUMP_BYTES else sorted(int(ids[i]) for i in rng.choice(len(ids), max(1, DUMP_BYTES // per), replace=False))
+    ri, ci = torch.from_numpy(rows), torch.from_numpy(cols)
+    arrs = {"u": np.stack([allres[i][0].float().cpu()[ri].numpy() for i in keep]),
+            "s": np.stack([allres[i][1].float().cpu().numpy() for i in keep]),
+            "vT": np.stack([allres[i][2].float().cpu()[:, ci].numpy() for i in keep])}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, x in arrs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(x, dtype=np.float32))
+    return {"dir": out_dir, "arrays": {n: list(x.shape) for n, x in arrs.items()}, "sample_ids": [int(i) for i in keep],
+            "samples_total": len(ids), "u_rows": "all" if rows.size == n_h else rows.size, "vT_cols": "all" if cols.size == n_in else cols.size}
+
+
 def cpu_info():
     model, phys = "unknown", set()
     try:
@@ -477,6 +512,7 @@ def main():
     assert len(allres) == n_total, (len(allres), n_total)
     s0 = allres[0][1]
     finite = all(bool(torch.isfinite(v[1]).all() and torch.isfinite(v[2]).all()) for v in allres.values())
+    dumped = dump_outputs(a.dump_outputs, allres) if a.dump_outputs and rank == 0 else None     # the last timed region's bases, outside the clock
 
     total_steps = steps if strong else world * steps
     res = {
@@ -496,6 +532,8 @@ def main():
                    "timed_gpu_seconds_total": round(sum(times), 4), "value_is": "steps / median over the repeats of the max-over-ranks time of one `steps`-step region"},
         "finite": finite, "s_top": [round(v, 4) for v in s0.cpu().tolist()[:k]],
     }
+    if dumped:
+        res["dump_outputs"] = dumped
 
 
     if a.workload == "sd15" and not strong and not a.no_strong_leg and tap == ("mid", 0) and not a.flat_spectrum:

@@ -419,14 +419,14 @@ def test_flash_forward_isa_keeps_the_rescale_and_the_row_sum_off_the_hot_path(tm
         assert masked <= 0, (name, "the exchange of l runs under an exec mask")
 
 
-def test_measurement_scripts_compile():
+def test_measurement_scripts_compile(tmp_path):
     """tools/*.py and bench.py are not imported by any test (they need a GPU box): at least their syntax is checked here."""
     import glob, os, py_compile
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     files = sorted(glob.glob(os.path.join(root, "tools", "*.py"))) + [os.path.join(root, "bench.py"), os.path.join(root, "__graft_entry__.py")]
     assert len(files) > 10
     for f in files:
-        py_compile.compile(f, doraise=True, cfile=os.path.join("/tmp", "dpb_pyc_" + os.path.basename(f) + "c"))
+        py_compile.compile(f, doraise=True, cfile=str(tmp_path / (os.path.basename(f) + "c")))
 
 
 def test_p8_isa_keeps_fragment_registers_untouched_until_their_wait(tmp_path):
@@ -495,3 +495,33 @@ def test_p8_isa_keeps_fragment_registers_untouched_until_their_wait(tmp_path):
     assert stores and all(re.search(r"global_store_dwordx4 [^\n]* sc1\s*\n\s*s_nop 1", b) for b in stores), "an asm write-through store without its s_nop 1"
     for m in re.finditer(r"\.private_segment_fixed_size:\s*(\d+)", text):
         assert m.group(1) == "0"
+
+
+def test_bench_dump_outputs_is_bounded_and_seeded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float32 (u, s, vT) stacked in sample-id order; above the budget, the same seeded subset every time and
+    never more than 64 MB on disk."""
+    import importlib.util, os
+    import numpy as np
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))    # bench.py sets it on import: undone after the test
+    spec = importlib.util.spec_from_file_location("dpb_bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+
+    def res(n, n_h, k, n_in):
+        return {i: (torch.randn(k, n_h, generator=g).T, torch.rand(k, generator=g), torch.randn(k, n_in, generator=g)) for i in range(n)}
+    small = res(3, 100, 5, 40)
+    info = bench.dump_outputs(str(tmp_path / "a"), small)
+    assert info["sample_ids"] == [0, 1, 2]
+    u, s, vT = (np.load(tmp_path / "a" / f"{n}.npy") for n in ("u", "s", "vT"))
+    assert u.dtype == s.dtype == vT.dtype == np.float32 and u.shape == (3, 100, 5) and s.shape == (3, 5) and vT.shape == (3, 5, 40)
+    assert np.array_equal(u[1], small[1][0].numpy()) and np.array_equal(s[2], small[2][1].numpy()) and np.array_equal(vT[0], small[0][2].numpy())
+    big = res(40, 81920, 5, 16384)                                    # the headline shapes (mid tap of SD-1.5, k = 5): 1.9 MB per sample
+    a, b = bench.dump_outputs(str(tmp_path / "b"), big), bench.dump_outputs(str(tmp_path / "c"), big)
+    assert a["sample_ids"] == b["sample_ids"] and 1 <= len(a["sample_ids"]) < 40
+    for d in ("b", "c"):
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= 64 * 10 ** 6
+    j = a["sample_ids"][-1]
+    assert np.array_equal(np.load(tmp_path / "b" / "vT.npy")[-1], big[j][2].numpy())
