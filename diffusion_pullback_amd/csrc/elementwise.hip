@@ -194,6 +194,31 @@ int launch_copy_cols(int dtype, const void* src, int lds_, int cs0, void* dst, i
   return 0;
 }
 
+// zero a column window dst[r][cd0 .. cd0+ncols) of a [rows][ldd] tensor (tangent of the inactive operand of a concat: the window may hold a
+// pass of another seed; the rest of the tensor is written by the concat's other copy)
+template <typename T>
+__global__ __launch_bounds__(256) void zero_cols_kernel(T* dst, int ldd, int cd0, long rows, int ncols) {
+  constexpr int CH = TT<T>::CH;
+  const int nch = ncols / CH;
+  const long total = rows * nch;
+  float v[CH];
+#pragma unroll
+  for (int e = 0; e < CH; ++e) v[e] = 0.f;
+  for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+    const long r = idx / nch;
+    const int c = (int)(idx - r * nch) * CH;
+    Vec<T>::store(dst + r * ldd + cd0 + c, v);
+  }
+}
+int launch_zero_cols(int dtype, void* dst, int ldd, int cd0, long rows, int ncols, hipStream_t st) {
+  int CH = dt_chunk(dtype);
+  if (ncols % CH || cd0 % CH || ldd % CH || cd0 + ncols > ldd) { set_error("zero_cols: misaligned window"); return -1; }
+  unsigned g = grid_for(rows * (ncols / CH));
+  DPB_DISPATCH_STMT(dtype, T, hipLaunchKernelGGL((zero_cols_kernel<T>), dim3(g), dim3(256), 0, st, (T*)dst, ldd, cd0, rows, ncols));
+  DPB_CHECK(hipGetLastError());
+  return 0;
+}
+
 // fp32 NCHW -> T NHWC (channel pad to Cpad with zeros).  Small tensors (boundary only): tile transpose through LDS.
 template <typename T>
 __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* src, T* dst, int C, int HW, int Cpad) {

@@ -87,6 +87,16 @@ struct dpb_engine {
   int cur_batch = 0;
   std::vector<int> uses;            // buffer -> number of ops reading it (in0 / in1 / in2 / res)
   int cur_tap = -1;                 // tap buffer of the pass being run
+  // Seed of the tangent / adjoint pass being run: x_buf for the encoder entry points, any buffer for the *_between ones.  A buffer (op) is
+  // ACTIVE for a seed if it is reachable forward from it (an op: one of its differentiated inputs is); only active buffers carry tangents and
+  // cotangents.  For x_buf the flags are exactly !is_const.  One flag vector per seed, computed on first use (set_seed).
+  int src = -1;
+  const char* bact = nullptr;       // [n_buffers] activity of the current seed's buffers
+  const char* oact = nullptr;       // [n_ops]     activity of the current seed's ops
+  std::vector<std::vector<char>> act_cache;   // seed buffer -> [n_buffers + n_ops] flags (empty: not computed yet)
+  int primal_last = -1;             // last op whose primal state (with the tangent / adjoint stash) is resident; -1: none
+  int fwd_seed = -1;                // dpb_forward_from: buffer overwritten by fwd_h after its producer has run
+  const float* fwd_h = nullptr;
   struct { bool on = false; GemmArgs a; } pend;   // a split-K product whose reduction is deferred to the normalisation op that consumes it
   bool fwd_only = false;            // dpb_forward: primal pass that keeps no tangent / adjoint stash (DDIM loop)
   std::vector<char> ginit;
@@ -195,7 +205,7 @@ int conv_fwd(dpb_engine* e, const Op& op, int mode, int n) {
   const int H = d.ip[0], W = d.ip[1], Cin = d.ip[2], Ho = d.ip[3], Wo = d.ip[4], Cout = d.ip[5], KS = d.ip[6];
   const Buf& bi = e->bufs[d.in0];
   const Buf& bo = e->bufs[d.out];
-  if (mode == 1 && bi.is_const) {     // only the residual carries a tangent
+  if (mode == 1 && !e->bact[d.in0]) {   // only the residual carries a tangent
     e->n_launch++;
     return launch_axpy(e->dtype, e->T(d.res), e->T(d.out), (long)n * bo.rows * bo.C, 0, e->stream);
   }
@@ -225,7 +235,7 @@ int conv_fwd(dpb_engine* e, const Op& op, int mode, int n) {
       g.rowbias_div = 1 << 30;
     }
   }
-  if (d.res >= 0 && (mode == 0 || !e->bufs[d.res].is_const)) {
+  if (d.res >= 0 && (mode == 0 || e->bact[d.res])) {
     g.R = mode == 0 ? e->P(d.res) : e->T(d.res);
     g.ldr = e->bufs[d.res].C;
   }
@@ -251,7 +261,7 @@ int conv_fwd(dpb_engine* e, const Op& op, int mode, int n) {
       return gemm(e, f);
     }
   }
-  if (mode == 0 && e->fwd_only && op.geglu_next >= 0 && g_geglu_fwd && !shared_out && d.out != e->cur_tap) {   // (a pass that stops AT h needs h written)
+  if (mode == 0 && e->fwd_only && op.geglu_next >= 0 && g_geglu_fwd && !shared_out && d.out != e->cur_tap && d.out != e->fwd_seed) {   // (a pass that stops AT h needs h written)
     // forward only (dpb_forward): an FF-in product that runs unsplit anyway applies GEGLU in its epilogue -- h [rows][2F] is neither written nor
     // re-read (84 MB per 64x64-level layer at batch 2), one launch less; bitwise the separate product + GEGLU kernel
     const dpb_op_desc& gd = e->ops[op.geglu_next].d;
@@ -276,7 +286,7 @@ int conv_adj(dpb_engine* e, const Op& op, int n) {
   const Buf& bi = e->bufs[d.in0];
   const Buf& bo = e->bufs[d.out];
   const int Cout = bo.C;              // padded channel count of the cotangent (w[1] is [Cin][KS*KS*CoutPadded])
-  if (!bi.is_const) {
+  if (e->bact[d.in0]) {
     if (!d.w[1]) return fail("conv op has no transposed weight (w[1]) but its adjoint is needed");
     GemmArgs g;
     g.A = e->G(d.out);
@@ -289,7 +299,8 @@ int conv_adj(dpb_engine* e, const Op& op, int n) {
     const int gather = d.ip[9];
     // the LayerNorm that wrote this product's input: its adjoint in the epilogue (K <= 1024: beyond -- the FF-in adjoint, K = 8 C -- the
     // row-complete tile's one block per CU loses more in the K loop than the fusion saves: g_ln_fuse bit 1 forces it for A/Bs)
-    if (gather == GATHER_NONE && op.ln_prev >= 0 && g_ln_fuse && e->uses[d.in0] == 1 && (g.K <= g_ln_kmax || (g_ln_fuse & 2))) {
+    // (not when the input is the seed: the LayerNorm / GEGLU that wrote it is upstream of the pass, its cotangent G(seed) is the result)
+    if (gather == GATHER_NONE && op.ln_prev >= 0 && g_ln_fuse && e->uses[d.in0] == 1 && d.in0 != e->src && (g.K <= g_ln_kmax || (g_ln_fuse & 2))) {
       const dpb_op_desc& ld = e->ops[op.ln_prev].d;
       GemmArgs f = g;
       f.M = n * bi.rows;
@@ -303,7 +314,7 @@ int conv_adj(dpb_engine* e, const Op& op, int n) {
         goto residual;
       }
     }
-    if (gather == GATHER_NONE && op.geglu_prev >= 0) {   // FF-out adjoint: GEGLU's adjoint in the epilogue, gy [rows][F] is never written
+    if (gather == GATHER_NONE && op.geglu_prev >= 0 && d.in0 != e->src) {   // FF-out adjoint: GEGLU's adjoint in the epilogue, gy [rows][F] is never written
       const dpb_op_desc& gd = e->ops[op.geglu_prev].d;
       GemmArgs f = g;
       f.M = n * bi.rows;
@@ -316,7 +327,7 @@ int conv_adj(dpb_engine* e, const Op& op, int n) {
         goto residual;
       }
     }
-    const bool lone = e->uses[d.in0] == 1 && d.in0 != e->x_buf;   // the cotangent has this one contribution: its producer's adjoint may add the slabs
+    const bool lone = e->uses[d.in0] == 1 && d.in0 != e->src;     // the cotangent has this one contribution: its producer's adjoint may add the slabs
     if (gather == GATHER_NONE) {
       g.M = n * bi.rows;
       g.C = e->G(d.in0);
@@ -341,7 +352,7 @@ int conv_adj(dpb_engine* e, const Op& op, int n) {
     e->ginit[d.in0] = 1;
   }
 residual:
-  if (d.res >= 0 && !e->bufs[d.res].is_const) {
+  if (d.res >= 0 && e->bact[d.res]) {
     Buf& br = e->bufs[d.res];
     if (!e->ginit[d.res] && br.rows == bo.rows && br.C == bo.C && br.kind == bo.kind) {
       // first cotangent of the residual stream: G(out) is dead once its producer (this op) has run, so hand its storage
@@ -482,17 +493,25 @@ int concat_run(dpb_engine* e, const Op& op, int mode, int n) {
   const long rows = (long)n * bo.rows;
   e->n_launch += 2;
   if (mode == MODE_ADJOINT) {
-    if (!b0.is_const) {
+    if (e->bact[d.in0]) {
       if (int r = launch_copy_cols(e->dtype, e->G(d.out), bo.C, 0, e->G(d.in0), b0.C, 0, rows, b0.C, e->ginit[d.in0], e->stream)) return r;
       e->ginit[d.in0] = 1;
     }
-    if (!b1.is_const) {
+    if (e->bact[d.in1]) {
       if (int r = launch_copy_cols(e->dtype, e->G(d.out), bo.C, b0.C, e->G(d.in1), b1.C, 0, rows, b1.C, e->ginit[d.in1], e->stream)) return r;
       e->ginit[d.in1] = 1;
     }
     return 0;
   }
-  if (mode == MODE_TANGENT && (b0.is_const || b1.is_const)) return fail("concat of x-independent and x-dependent buffers is unsupported");
+  if (mode == MODE_TANGENT && (!e->bact[d.in0] || !e->bact[d.in1])) {
+    // one operand does not depend on the seed (the skip half of an up-block concat when the pass starts at a tap): its window of the tangent
+    // is zero -- written on every pass, since a pass of another seed may have left a tangent in that storage
+    char* o = e->T(d.out);
+    if (int r = e->bact[d.in0] ? launch_copy_cols(e->dtype, e->T(d.in0), b0.C, 0, o, bo.C, 0, rows, b0.C, 0, e->stream)
+                               : launch_zero_cols(e->dtype, o, bo.C, 0, rows, b0.C, e->stream)) return r;
+    return e->bact[d.in1] ? launch_copy_cols(e->dtype, e->T(d.in1), b1.C, 0, o, bo.C, b0.C, rows, b1.C, 0, e->stream)
+                          : launch_zero_cols(e->dtype, o, bo.C, b0.C, rows, b1.C, e->stream);
+  }
   char* o = mode == MODE_PRIMAL ? e->P(d.out) : e->T(d.out);
   const char* i0 = mode == MODE_PRIMAL ? e->P(d.in0) : e->T(d.in0);
   const char* i1 = mode == MODE_PRIMAL ? e->P(d.in1) : e->T(d.in1);
@@ -780,6 +799,60 @@ int check_tap(dpb_engine* e, int tap, int nt) {
   return 0;
 }
 
+// make `src` the seed of the passes that follow: its activity flags (computed once per seed and cached)
+int set_seed(dpb_engine* e, int src) {
+  const int nb = (int)e->bufs.size(), no = (int)e->ops.size();
+  std::vector<char>& a = e->act_cache[src];
+  if (a.empty()) {
+    std::vector<char> f(nb + no, 0);
+    if (src == e->x_buf) {                        // the create-time flags, unchanged
+      for (int b = 0; b < nb; ++b) f[b] = !e->bufs[b].is_const;
+      for (int i = 0; i < no; ++i) f[nb + i] = !e->ops[i].is_const;
+    } else {
+      f[src] = 1;
+      for (int i = e->producer[src] + 1; i < no; ++i) {   // ops up to producer[src] cannot read a buffer written later (SSA tape order)
+        const Op& op = e->ops[i];
+        const dpb_op_desc& d = op.d;
+        bool on = f[d.in0];
+        if (d.kind == DPB_OP_ATTENTION || d.kind == DPB_OP_CONCAT) on = on || f[d.in1];
+        if (d.kind == DPB_OP_ATTENTION) on = on || f[d.in2];
+        if (d.kind == DPB_OP_CONV && d.res >= 0) on = on || f[d.res];
+        if (d.kind == DPB_OP_SILU && on) return fail("op %d (SILU / GELU, primal only) depends on source buffer %d", i, src);
+        if (on && d.kind == DPB_OP_ATTENTION) {   // the attention kernels were planned for x: the query and (k, v) must have the same activity as for x
+          const AttnPlan& p = e->plans[op.attn];
+          if (!f[d.in0] || f[d.in1] != f[d.in2] || (bool)f[d.in1] == p.kv_const)
+            return fail("attention op %d: q, k, v depend on source buffer %d differently than on x (unsupported)", i, src);
+        }
+        f[nb + i] = on;
+        if (on) f[d.out] = 1;
+      }
+    }
+    a.swap(f);
+  }
+  e->src = src;
+  e->bact = a.data();
+  e->oact = a.data() + nb;
+  return 0;
+}
+
+// channels of the seed's fp32 NCHW boundary: the network input's true channels, a tap's valid channels
+int seed_channels(const dpb_engine* e, int src) { return src == e->x_buf ? e->x_channels : e->bufs[src].Cv; }
+
+// the checks of check_tap, plus (src != x_buf) those of a pass between two inner buffers; makes src the seed
+int check_pair(dpb_engine* e, int src, int dst, int nt) {
+  if (int r = check_tap(e, dst, nt)) return r;
+  if (src != e->x_buf) {
+    if (src < 0 || src >= (int)e->bufs.size() || e->producer[src] < 0 || e->bufs[src].kind != DPB_BUF_ACT) return fail("invalid source buffer %d", src);
+    if (e->bufs[src].is_const) return fail("source buffer %d does not depend on x", src);
+    if (e->producer[dst] > e->primal_last)
+      return fail("no primal state up to dst buffer %d (produced by op %d, the primal pass covers ops 0..%d): run dpb_primal with upto_buf = dst or later",
+                  dst, e->producer[dst], e->primal_last);
+  }
+  if (int r = set_seed(e, src)) return r;
+  if (dst == src || !e->bact[dst]) return fail("dst buffer %d is not downstream of source buffer %d", dst, src);
+  return 0;
+}
+
 }  // namespace
 
 // =================================================================== C ABI
@@ -974,6 +1047,8 @@ int dpb_engine_create(const dpb_net_desc* net, dpb_engine** out) {
   e->pbW = take((size_t)e->maxT * nx * sizeof(float));
   e->ws_bytes = off;
   e->ginit.assign(nb, 0);
+  e->act_cache.assign(nb, std::vector<char>());
+  if (set_seed(e, e->x_buf)) { delete e; return -1; }
   *out = e;
   return 0;
 }
@@ -1040,11 +1115,19 @@ static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const 
   e->cur_batch = batch;
   e->cur_tap = upto_buf; e->pend.on = false;
   const int last = e->producer[upto_buf];
+  const int seed_op = e->fwd_seed >= 0 ? e->producer[e->fwd_seed] : -1;
+  e->primal_last = -1;
   std::fill(e->skip.begin(), e->skip.end(), 0);
   for (int i = 0; i <= last; ++i) {
-    if (e->skip[i]) continue;                      // (forward only: a GEGLU applied by the epilogue of the FF-in product)
-    if (int r = run_op(e, e->ops[i], MODE_PRIMAL, batch)) return r;
+    if (!e->skip[i])                               // (forward only: a GEGLU applied by the epilogue of the FF-in product)
+      if (int r = run_op(e, e->ops[i], MODE_PRIMAL, batch)) return r;
+    if (i == seed_op) {                            // dpb_forward_from: the caller's activation replaces the one just computed
+      const Buf& bs = e->bufs[e->fwd_seed];
+      e->n_launch++;
+      if (int r = launch_nchw_to_nhwc(e->dtype, e->fwd_h, e->P(e->fwd_seed), batch, bs.Cv, bs.rows, bs.C, e->stream)) return r;
+    }
   }
+  if (!e->fwd_only) e->primal_last = last;
   return 0;
 }
 
@@ -1063,6 +1146,24 @@ int dpb_forward(dpb_engine* e, const float* x, int batch, float t, const float* 
   return r;
 }
 
+int dpb_forward_from(dpb_engine* e, const float* x, int batch, float t, const float* ctx, int src_buf, const float* h, int dst_buf, int channels,
+                     float* out) {
+  if (!e || !out || !h) return fail("null argument");
+  const int nb = (int)e->bufs.size();
+  if (src_buf < 0 || src_buf >= nb || e->producer[src_buf] < 0 || e->bufs[src_buf].kind != DPB_BUF_ACT || e->bufs[src_buf].is_const)
+    return fail("invalid source buffer %d (an x-dependent activation produced by an op)", src_buf);
+  if (dst_buf < 0 || dst_buf >= nb || e->producer[dst_buf] < 0) return fail("invalid dst buffer %d", dst_buf);
+  const int prev = e->src;
+  if (int r = set_seed(e, src_buf)) return r;
+  const bool down = dst_buf != src_buf && e->bact[dst_buf];
+  set_seed(e, prev);
+  if (!down) return fail("dst buffer %d is not downstream of source buffer %d", dst_buf, src_buf);
+  e->fwd_seed = src_buf; e->fwd_h = h;
+  const int r = dpb_forward(e, x, batch, t, ctx, dst_buf, channels, out);
+  e->fwd_seed = -1; e->fwd_h = nullptr;
+  return r;
+}
+
 int dpb_read_buffer(dpb_engine* e, int buf, int channels, float* out) {
   if (!e || !out) return fail("null argument");
   if (buf < 0 || buf >= (int)e->bufs.size()) return fail("bad buffer %d", buf);
@@ -1074,19 +1175,20 @@ int dpb_read_buffer(dpb_engine* e, int buf, int channels, float* out) {
 }
 
 // U == nullptr (dpb_pullback_iterate, every iteration but the last): the tangent of the tap stays in T(tap); the adjoint pass takes it from there
-static int jvp_pass(dpb_engine* e, int tap, const float* V, int nt, float* U) {
+// src: the seed buffer (x_buf: the encoder Jacobian); ops up to producer[src] and ops whose output does not depend on src do not run
+static int jvp_pass(dpb_engine* e, int src, int tap, const float* V, int nt, float* U) {
   if (!e || !V) return fail("null argument");
-  if (int r = check_tap(e, tap, nt)) return r;
+  if (int r = check_pair(e, src, tap, nt)) return r;
   e->n_launch = 0; e->flops = 0; e->gbytes = 0;
-  const Buf& bx = e->bufs[e->x_buf];
+  const Buf& bx = e->bufs[src];
   e->n_launch++;
-  if (int r = launch_nchw_to_nhwc(e->dtype, V, e->T(e->x_buf), nt, e->x_channels, bx.rows, bx.C, e->stream)) return r;
+  if (int r = launch_nchw_to_nhwc(e->dtype, V, e->T(src), nt, seed_channels(e, src), bx.rows, bx.C, e->stream)) return r;
   if (e->tstats_bytes && !gn_deterministic()) DPB_CHECK(hipMemsetAsync(e->ws + e->tstats_off, 0, e->tstats_bytes, e->stream));   // atomic statistics accumulate
   const int last = e->producer[tap];
   std::fill(e->skip.begin(), e->skip.end(), 0);
   e->cur_tap = tap; e->pend.on = false;
-  for (int i = 0; i <= last; ++i) {
-    if (e->ops[i].is_const || e->skip[i]) continue;
+  for (int i = e->producer[src] + 1; i <= last; ++i) {
+    if (!e->oact[i] || e->skip[i]) continue;
     if (int r = run_op(e, e->ops[i], MODE_TANGENT, nt)) return r;
   }
   if (int r = flush_pending(e)) return r;
@@ -1098,14 +1200,19 @@ static int jvp_pass(dpb_engine* e, int tap, const float* V, int nt, float* U) {
 
 int dpb_jvp(dpb_engine* e, int tap, const float* V, int nt, float* U) {
   if (!U) return fail("null argument");
-  return jvp_pass(e, tap, V, nt, U);
+  return jvp_pass(e, e ? e->x_buf : -1, tap, V, nt, U);
+}
+
+int dpb_jvp_between(dpb_engine* e, int src_buf, int dst_buf, const float* V, int nt, float* U) {
+  if (!e || !U) return fail("null argument");
+  return jvp_pass(e, src_buf, dst_buf, V, nt, U);
 }
 
 // U == nullptr: the cotangent seed IS the tangent the last jvp_pass left in T(tap) -- its storage is handed to G(tap) for this pass (the fp32 NCHW round
 // trip through U is the identity on 16-bit and fp32 values alike, so the results are bitwise those of the two conversion kernels it replaces)
-static int vjp_pass(dpb_engine* e, int tap, const float* U, int nt, float* W) {
+static int vjp_pass(dpb_engine* e, int src, int tap, const float* U, int nt, float* W) {
   if (!e || !W) return fail("null argument");
-  if (int r = check_tap(e, tap, nt)) return r;
+  if (int r = check_pair(e, src, tap, nt)) return r;
   e->n_launch = 0; e->flops = 0; e->gbytes = 0;
   const Buf& bt = e->bufs[tap];
   std::fill(e->ginit.begin(), e->ginit.end(), 0);
@@ -1119,16 +1226,19 @@ static int vjp_pass(dpb_engine* e, int tap, const float* U, int nt, float* W) {
   e->ginit[tap] = 1;
   if (e->tstats_bytes && !gn_deterministic()) DPB_CHECK(hipMemsetAsync(e->ws + e->tstats_off, 0, e->tstats_bytes, e->stream));
   e->cur_tap = tap; e->pend.on = false;
-  for (int i = e->producer[tap]; i >= 0; --i) {
+  for (int i = e->producer[tap]; i > e->producer[src]; --i) {   // (the seed's producer and everything before it: upstream of the pass)
     const Op& op = e->ops[i];
-    if (op.is_const || !e->ginit[op.d.out]) continue;
+    if (!e->oact[i] || !e->ginit[op.d.out]) continue;
     if (int r = run_op(e, op, MODE_ADJOINT, nt)) return r;
   }
   if (int r = flush_pending(e)) return r;
-  if (!e->ginit[e->x_buf]) return fail("tap buffer %d is not connected to x", tap);
-  const Buf& bx = e->bufs[e->x_buf];
+  if (!e->ginit[src]) {
+    for (auto& b : e->bufs) b.g_off = b.g_off0;
+    return src == e->x_buf ? fail("tap buffer %d is not connected to x", tap) : fail("dst buffer %d is not connected to source buffer %d", tap, src);
+  }
+  const Buf& bx = e->bufs[src];
   e->n_launch++;
-  const int r = launch_nhwc_to_nchw(e->dtype, e->G(e->x_buf), W, nt, e->x_channels, bx.rows, bx.C, e->stream);
+  const int r = launch_nhwc_to_nchw(e->dtype, e->G(src), W, nt, seed_channels(e, src), bx.rows, bx.C, e->stream);
   // Invariant of Buf::g_off / t_off: between passes every buffer's cotangent storage is its own (g_off == g_off0).  Inside the pass the residual adjoint
   // swaps g_off between buffers and U == nullptr lends the tap's TANGENT storage to its cotangent; undo both here so that nothing that reads G() or
   // T(tap) after the pass (a debug read, a later feature) sees aliased data.  (The launch above is already enqueued with the pointer it needs.)
@@ -1138,7 +1248,12 @@ static int vjp_pass(dpb_engine* e, int tap, const float* U, int nt, float* W) {
 
 int dpb_vjp(dpb_engine* e, int tap, const float* U, int nt, float* W) {
   if (!U) return fail("null argument");
-  return vjp_pass(e, tap, U, nt, W);
+  return vjp_pass(e, e ? e->x_buf : -1, tap, U, nt, W);
+}
+
+int dpb_vjp_between(dpb_engine* e, int src_buf, int dst_buf, const float* U, int nt, float* W) {
+  if (!e || !U) return fail("null argument");
+  return vjp_pass(e, src_buf, dst_buf, U, nt, W);
 }
 
 int dpb_orth(const float* W, const float* Vprev, float* V, float* s, float* conv, void* scratch, int k, int64_t N, void* stream) {
@@ -1167,36 +1282,35 @@ static int g_iter_alias = getenv("DPB_ITER_ALIAS") ? atoi(getenv("DPB_ITER_ALIAS
 static int g_orth_batch = getenv("DPB_ORTH_BATCH") ? atoi(getenv("DPB_ORTH_BATCH")) : 1;   // A/B switch: 0 = re-orthonormalise the samples of a batch one by one
 static int g_graph_iterate = 0;      // dpb_debug_set("graph_iterate", 1): replay the power iteration as a captured hipGraph (measurement option)
 
-int dpb_pullback_iterate(dpb_engine* e, int tap, float* V, float* U, float* s, float* conv, int k, int n_iters) {
-  if (!e || !V || !U || !s || !conv) return fail("null argument");
-  if (k < 1 || k > ORTH_MAX_RANK) return fail("pca_rank k=%d outside [1,%d]", k, ORTH_MAX_RANK);
-  const int B = e->cur_batch;                       // samples advanced together: one weight stream for all of them
-  if (int r = check_tap(e, tap, k * (B > 0 ? B : 1))) return r;
+// The power iteration between seed `src` and `tap`.  Wm: fp32 [B][k][N] staging of W = J^T J V, orth_scratch: B slots of orth_stride bytes
+// (the encoder entry point: the engine's workspace; the *_between one: the caller's scratch).
+static int iterate_pass(dpb_engine* e, int src, int tap, float* V, float* U, float* s, float* conv, int k, int n_iters, float* Wm, char* orth_scratch,
+                        size_t orth_stride) {
+  const int B = e->cur_batch;
   const int nt = k * B;
-  const long N = (long)e->bufs[e->x_buf].rows * e->x_channels;
-  float* Wm = (float*)(e->ws + e->pbW);
+  const long N = (long)e->bufs[src].rows * seed_channels(e, src);
   long launches = 0; double fl = 0, gb = 0;
   const bool alias_ok = e->bufs[tap].Cv == e->bufs[tap].C && g_iter_alias;   // (padded tap channels: the conversion kernels zero them, an alias would not)
   auto body = [&](bool want_u) -> int {             // one power iteration: k JVPs, k VJPs, re-orthonormalisation, V <- V_new; no host sync
     // U = J V_prev is an OUTPUT of the last iteration only (utils.py:810): before that the tap's tangent goes straight from T(tap) into the adjoint
     // pass -- no nhwc -> fp32 nchw -> nhwc round trip (two launches per iteration, bitwise the same values)
     const bool keep = alias_ok && !want_u;
-    if (int r = jvp_pass(e, tap, V, nt, keep ? nullptr : U)) return r;
+    if (int r = jvp_pass(e, src, tap, V, nt, keep ? nullptr : U)) return r;
     launches += e->n_launch; fl += e->flops; gb += e->gbytes;
-    if (int r = vjp_pass(e, tap, keep ? nullptr : U, nt, Wm)) return r;
+    if (int r = vjp_pass(e, src, tap, keep ? nullptr : U, nt, Wm)) return r;
     launches += e->n_launch; fl += e->flops; gb += e->gbytes;
     {                                               // independent k x N re-orthonormalisation per sample, all samples in one set of four launches
       OrthArgs a;                                   // (in place, V is Vprev: see dpb.h)
-      a.W = Wm; a.Vprev = V; a.V = V; a.s = s; a.conv = conv; a.scratch = (double*)(e->ws + e->orth); a.k = k; a.N = N;
+      a.W = Wm; a.Vprev = V; a.V = V; a.s = s; a.conv = conv; a.scratch = (double*)orth_scratch; a.k = k; a.N = N;
       a.scratch_bytes = orth_scratch_bytes(k, N);
-      a.batch = B; a.stride_w = (long)k * N; a.stride_v = (long)k * N; a.stride_s = k; a.stride_conv = 2; a.scratch_stride = e->orth_stride;
+      a.batch = B; a.stride_w = (long)k * N; a.stride_v = (long)k * N; a.stride_s = k; a.stride_conv = 2; a.scratch_stride = orth_stride;
       if (g_orth_batch) {
         if (int r = launch_orth(a, e->stream)) return r;
       } else {                                      // A/B switch DPB_ORTH_BATCH=0: four launches per sample, as rounds 1-5 (same bits)
         a.batch = 1;
         for (int b = 0; b < B; ++b) {
           if (int r = launch_orth(a, e->stream)) return r;
-          a.W += a.stride_w; a.Vprev += a.stride_v; a.V += a.stride_v; a.s += k; a.conv += 2; a.scratch += e->orth_stride / sizeof(double);
+          a.W += a.stride_w; a.Vprev += a.stride_v; a.V += a.stride_v; a.s += k; a.conv += 2; a.scratch += orth_stride / sizeof(double);
         }
       }
     }
@@ -1204,7 +1318,7 @@ int dpb_pullback_iterate(dpb_engine* e, int tap, float* V, float* U, float* s, f
     return 0;
   };
   int it = 0;
-  if (g_graph_iterate && !e->profiling && e->stream != 0) {
+  if (g_graph_iterate && !e->profiling && e->stream != 0 && src == e->x_buf) {   // (the captured graph is keyed on the tap alone: encoder entry point only)
     // The launch sequence of an iteration is fixed for fixed (tap, k, batch, buffers): capture it once (after one eager iteration, so that
     // every code object is loaded) and replay it.  Measured on MI355X: no gain -- the stream never runs dry.
     const dpb_engine::GraphKey key{tap, k, B, V, U, s, conv};
@@ -1234,6 +1348,39 @@ int dpb_pullback_iterate(dpb_engine* e, int tap, float* V, float* U, float* s, f
     if (int r = body(it == n_iters - 1)) return r;
   e->n_launch = launches; e->flops = fl; e->gbytes = gb;
   return 0;
+}
+
+int dpb_pullback_iterate(dpb_engine* e, int tap, float* V, float* U, float* s, float* conv, int k, int n_iters) {
+  if (!e || !V || !U || !s || !conv) return fail("null argument");
+  if (k < 1 || k > ORTH_MAX_RANK) return fail("pca_rank k=%d outside [1,%d]", k, ORTH_MAX_RANK);
+  const int B = e->cur_batch;                       // samples advanced together: one weight stream for all of them
+  if (int r = check_tap(e, tap, k * (B > 0 ? B : 1))) return r;
+  return iterate_pass(e, e->x_buf, tap, V, U, s, conv, k, n_iters, (float*)(e->ws + e->pbW), e->ws + e->orth, e->orth_stride);
+}
+
+// scratch of the *_between iteration for `batch` samples: W staging, then one re-orthonormalisation slot per sample
+static size_t between_scratch_bytes(const dpb_engine* e, int src, int k, int batch) {
+  const long N = (long)e->bufs[src].rows * seed_channels(e, src);
+  return align_up((size_t)batch * k * N * sizeof(float)) + (size_t)batch * align_up(orth_scratch_bytes(k, N));
+}
+
+size_t dpb_pullback_scratch_bytes(const dpb_engine* e, int src_buf, int k) {
+  if (!e || k < 1 || k > ORTH_MAX_RANK || src_buf < 0 || src_buf >= (int)e->bufs.size() || e->bufs[src_buf].kind != DPB_BUF_ACT) return 0;
+  return between_scratch_bytes(e, src_buf, k, e->maxB);
+}
+
+int dpb_pullback_iterate_between(dpb_engine* e, int src_buf, int dst_buf, float* V, float* U, float* s, float* conv, int k, int n_iters, void* scratch,
+                                 size_t scratch_bytes) {
+  if (!e || !V || !U || !s || !conv || !scratch) return fail("null argument");
+  if (k < 1 || k > ORTH_MAX_RANK) return fail("pca_rank k=%d outside [1,%d]", k, ORTH_MAX_RANK);
+  const int B = e->cur_batch;
+  if (int r = check_pair(e, src_buf, dst_buf, k * (B > 0 ? B : 1))) return r;
+  if ((uintptr_t)scratch % 256) return fail("scratch must be 256-byte aligned");
+  const size_t need = between_scratch_bytes(e, src_buf, k, B);
+  if (scratch_bytes < need) return fail("scratch of %zu bytes, the iteration needs %zu (dpb_pullback_scratch_bytes)", scratch_bytes, need);
+  const long N = (long)e->bufs[src_buf].rows * seed_channels(e, src_buf);
+  const size_t wbytes = align_up((size_t)B * k * N * sizeof(float));      // the layout of between_scratch_bytes
+  return iterate_pass(e, src_buf, dst_buf, V, U, s, conv, k, n_iters, (float*)scratch, (char*)scratch + wbytes, align_up(orth_scratch_bytes(k, N)));
 }
 
 int dpb_ddim_step(const float* x, const float* eps, float* out, float* x0, int64_t n, float a_t, float a_next, void* stream) {

@@ -182,6 +182,8 @@ int launch_axpy(int dtype, const void* x, void* y, long n, int accumulate, hipSt
 // channel concat / split on [rows][C] tensors: copy src[rows][Cs] <-> dst[rows][Cd] column window at c0
 int launch_copy_cols(int dtype, const void* src, int lds, int cs0, void* dst, int ldd, int cd0, long rows, int ncols,
                      int accumulate, hipStream_t st);
+// dst[rows][ldd] column window [cd0, cd0 + ncols) <- 0
+int launch_zero_cols(int dtype, void* dst, int ldd, int cd0, long rows, int ncols, hipStream_t st);
 // fp32 NCHW [n][C][HW]  <->  T NHWC [n][HW][Cpad]
 int launch_nchw_to_nhwc(int dtype, const float* src, void* dst, int n, int C, int HW, int Cpad, hipStream_t st);
 int launch_nhwc_to_nchw(int dtype, const void* src, float* dst, int n, int C, int HW, int Cpad, hipStream_t st);

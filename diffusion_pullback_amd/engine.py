@@ -186,6 +186,64 @@ class Engine:
             L.check(self.lib.dpb_pullback_iterate(self.h, buf, _ptr(V), _ptr(U), _ptr(s), _ptr(conv), k, n_iters))
         return V, U, s, conv
 
+    # ------------------------------------------------------------------ passes seeded at a tap (the decoder Jacobian d dst / d src)
+    def forward_from(self, x: torch.Tensor, t: float, ctx: Optional[torch.Tensor], src, h: torch.Tensor, dst="eps") -> torch.Tensor:
+        """dpb_forward_from: the forward pass with the activation at tap `src` replaced by h [B, C, H, W] (x [B, ...]: the caller repeats
+        one sample), read at `dst`.  Like forward(), keeps no primal state."""
+        sbuf, dbuf = self.tape.taps[src], self.tape.taps[dst]
+        c, hh, ww = self.tape.tap_shape[dbuf]
+        with torch.cuda.device(self.device):
+            self._set_stream()
+            x, b, ctx = self._inputs(x, ctx)
+            h = _f32(h, self.device).reshape(b, -1)
+            if h.shape[1] != self.tap_numel(src):
+                raise L.DpbError(f"input_h has {h.shape[1]} elements per sample, tap {src} has {self.tap_numel(src)}")
+            out = torch.empty(b, c, hh, ww, dtype=torch.float32, device=self.device)
+            L.check(self.lib.dpb_forward_from(self.h, _ptr(x), b, float(t), _ptr(ctx), sbuf, _ptr(h), dbuf, c, _ptr(out)))
+            self.batch = 0
+        return out
+
+    def jvp_between(self, src, dst, V: torch.Tensor) -> torch.Tensor:
+        """V [nt, N_src] (NCHW-flattened tangents of the tap `src`) -> U [nt, N_dst]; the primal must reach `dst`"""
+        with torch.cuda.device(self.device):
+            self._set_stream()
+            V = _f32(V, self.device).reshape(-1, self.tap_numel(src))
+            U = torch.empty(V.shape[0], self.tap_numel(dst), dtype=torch.float32, device=self.device)
+            L.check(self.lib.dpb_jvp_between(self.h, self.tape.taps[src], self.tape.taps[dst], _ptr(V), V.shape[0], _ptr(U)))
+        return U
+
+    def vjp_between(self, src, dst, U: torch.Tensor) -> torch.Tensor:
+        """U [nt, N_dst] -> W = J^T U [nt, N_src]"""
+        with torch.cuda.device(self.device):
+            self._set_stream()
+            U = _f32(U, self.device).reshape(-1, self.tap_numel(dst))
+            W = torch.empty(U.shape[0], self.tap_numel(src), dtype=torch.float32, device=self.device)
+            L.check(self.lib.dpb_vjp_between(self.h, self.tape.taps[src], self.tape.taps[dst], _ptr(U), U.shape[0], _ptr(W)))
+        return W
+
+    def scratch_bytes(self, src, k: int) -> int:
+        """device scratch of iterate_between for k directions per sample (dpb_pullback_scratch_bytes, at max_batch)"""
+        return int(self.lib.dpb_pullback_scratch_bytes(self.h, self.tape.taps[src], int(k)))
+
+    def iterate_between(self, src, dst, V: torch.Tensor, n_iters: int, scratch: Optional[torch.Tensor] = None):
+        """iterate() between two taps: n_iters power iterations in place on V [B*k, N_src]; returns (V, U [B*k, N_dst], s [B*k], conv [B, 2]).
+        scratch: uint8 device tensor of >= scratch_bytes(src, k) + 256 bytes (allocated here when None)."""
+        with torch.cuda.device(self.device):
+            self._set_stream()
+            assert V.is_cuda and V.dtype == torch.float32 and V.is_contiguous() and self.batch > 0 and V.shape[0] % self.batch == 0
+            nt = V.shape[0]
+            k = nt // self.batch
+            need = self.scratch_bytes(src, k)
+            if scratch is None:
+                scratch = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+            off = (-scratch.data_ptr()) % 256
+            U = torch.empty(nt, self.tap_numel(dst), dtype=torch.float32, device=self.device)
+            s = torch.empty(nt, dtype=torch.float32, device=self.device)
+            conv = torch.empty(self.batch, 2, dtype=torch.float32, device=self.device)
+            L.check(self.lib.dpb_pullback_iterate_between(self.h, self.tape.taps[src], self.tape.taps[dst], _ptr(V), _ptr(U), _ptr(s), _ptr(conv), k,
+                                                          n_iters, C.c_void_p(scratch.data_ptr() + off), max(scratch.numel() - off, 0)))
+        return V, U, s, conv
+
     def profile(self, enable: bool):
         L.check(self.lib.dpb_engine_profile(self.h, int(enable)))
 

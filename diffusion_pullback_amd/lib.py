@@ -78,6 +78,12 @@ SYMBOLS = {
     "dpb_engine_profile_dump": (_I, [_P, C.c_char_p]),
     "dpb_engine_profile_read": (_I, [_P, _I, C.POINTER(_L), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "dpb_engine_profile_overhead": (_I, [_P, C.POINTER(C.c_double)]),
+    # the decoder pullback: passes seeded at an inner activation (src_buf -> dst_buf)
+    "dpb_jvp_between": (_I, [_P, _I, _I, _P, _I, _P]),
+    "dpb_vjp_between": (_I, [_P, _I, _I, _P, _I, _P]),
+    "dpb_pullback_scratch_bytes": (C.c_size_t, [_P, _I, _I]),
+    "dpb_pullback_iterate_between": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _P, C.c_size_t]),
+    "dpb_forward_from": (_I, [_P, _P, _I, _F, _P, _I, _P, _I, _I, _P]),
 }
 
 _lib = None

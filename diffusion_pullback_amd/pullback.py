@@ -166,6 +166,121 @@ class PullbackUNet:
         chunks = pca_rank // chunk_size if pca_rank % chunk_size == 0 else pca_rank // chunk_size + 1   # utils.py:178
         return self._pullback(x, t, None, op, block_idx, pca_rank, chunks, min_iter, max_iter, convergence_threshold, V0)
 
+    # ------------------------------------------------------------------ decoder side: h -> eps
+    def _decoder_tap(self, op, block_idx):
+        key = self._tap(op, block_idx)
+        if "eps" not in self.engine.tape.taps:
+            raise ValueError("the decoder pullback needs an engine built up to eps: this one was built with upto=... and stops at "
+                             f"{[k for k in self.engine.tape.taps][-1]}")
+        return key
+
+    def _get_h_to_e(self, sample, timestep, ctx, input_h, op, block_idx, verbose):
+        key = self._decoder_tap(op, block_idx)
+        b = input_h.shape[0]
+        if not (1 <= b <= self.engine.max_batch):
+            raise ValueError(f"input_h.size(0) = {b} outside [1, max_batch = {self.engine.max_batch}] of this engine")
+        if sample.shape[0] != 1:
+            raise ValueError("get_h_to_e expects a single sample (batch 1): its skips are repeated input_h.size(0) times, as the reference does")
+        x = sample.expand(b, *sample.shape[1:])
+        e = self.engine.forward_from(x, _t_float(timestep), ctx, key, input_h, "eps")
+        if verbose:
+            print(f"op : {op}, block_idx : {block_idx}, input_h.shape : {tuple(input_h.shape)}, return eps.shape : {tuple(e.shape)}")
+        return e.to(sample.dtype)
+
+    def get_h_to_e(self, *args, **kwargs):
+        """eps of the U-Net with the activation at (op, block_idx) replaced by input_h [B, C, H, W] and every skip connection held at its
+        value for the single sample given (repeated B times).  SD: get_h_to_e(sample, timestep, encoder_hidden_states, input_h, op,
+        block_idx) (utils.py:529-635); uncond: get_h_to_e(x, t, input_h, op, block_idx) (diffusion.py:273-345).  Every tap of the
+        engine is accepted (the reference's DDPM code asserts op == 'mid', its SD code takes 'mid' and 'down')."""
+        if self.kind == "sd":
+            def sd(sample=None, timestep=None, encoder_hidden_states=None, input_h=None, op=None, block_idx=None, verbose=False):
+                return self._get_h_to_e(sample, timestep, encoder_hidden_states, input_h, op, block_idx, verbose)
+            return sd(*args, **kwargs)
+
+        def ddpm(x=None, t=None, input_h=None, op=None, block_idx=None, verbose=False):
+            return self._get_h_to_e(x, t, None, input_h, op, block_idx, verbose)
+        return ddpm(*args, **kwargs)
+
+    def _decoder_pullback(self, x, t, ctx, op, block_idx, k, chunks, min_iter, max_iter, thr, V0):
+        """Power iteration on J_dec = d eps / d h at one sample: the host-driven loop of _pullback with the passes seeded at the tap.
+        Returns (u = V^T [N_h, k] view, s [k], vT = J_dec V_prev [k, N_eps]) in the reference's decoder convention (diffusion.py:626-631)."""
+        if x.shape[0] != 1:
+            raise ValueError("local_decoder_pullback expects a single sample (batch 1), as the reference does")
+        if not (1 <= k <= min(self.max_rank, RANK_LIMIT)):
+            raise ValueError(f"pca_rank={k} outside [1, {min(self.max_rank, RANK_LIMIT)}] supported by the HIP engine (built for max_rank={self.max_rank} "
+                             f"tangents; the library's limit is {RANK_LIMIT})")
+        key = self._decoder_tap(op, block_idx)
+        eng = self.engine
+        n_h = eng.tap_numel(key)
+        if V0 is None:
+            q, _ = torch.linalg.qr(torch.randn(n_h, k, dtype=torch.float))        # diffusion.py:585-588 (CPU generator, as _pullback)
+            V0 = q.T
+        V = V0.reshape(k, n_h).to(device=self.device, dtype=torch.float32).contiguous()
+        time_s = time.time()
+        eng.primal(x, _t_float(t), ctx, "eps")
+        U = s = None
+        self.last_history = []
+        for i in range(max_iter):
+            V_prev = V
+            U = torch.cat([eng.jvp_between(key, "eps", vi) for vi in V.chunk(chunks)], dim=0)
+            W = torch.cat([eng.vjp_between(key, "eps", ui) for ui in U.chunk(chunks)], dim=0)
+            V, s, conv = eng.orth(W, V_prev)
+            dist, viol = conv.tolist()                                            # the only host sync per iteration
+            self.last_history.append(dist)
+            if self.verbose:
+                print(f"power method : {i}-th step convergence : ", dist)
+            if thr is not None and viol <= thr and i > min_iter:                 # the encoder's sign-aligned allclose rule (module docstring)
+                if self.verbose:
+                    print("reach convergence threshold : ", dist)
+                break
+        self.last_iters, self.last_dist = i + 1, dist
+        if self.verbose:
+            print("power method runtime ==", time.time() - time_s)
+        dt = x.dtype if x.dtype in (torch.float32, torch.float64) else torch.float32
+        return V.to(dt).T, s.to(dt), U.to(dt)
+
+    def local_decoder_pullback_xt(self, x=None, t=None, op="mid", block_idx=0, pca_rank=50, chunk_size=10, min_iter=10, max_iter=100,
+                                  convergence_threshold=1e-3, V0=None):
+        """Reference: PullBackDDPM.local_decoder_pullback_xt, src/models/ddpm/diffusion.py:558-632.  Low-rank SVD of J_dec = d eps / d h at
+        the tap (op, block_idx) with the skips held at their primal values.  Returns u [N_h, k] (h-space directions, V^T), s = sqrt(singular
+        values of J^T J V_prev), vT [k, N_eps] = J_dec V_prev of the last iteration (un-normalised)."""
+        chunks = pca_rank // chunk_size if pca_rank % chunk_size == 0 else pca_rank // chunk_size + 1   # diffusion.py:569
+        return self._decoder_pullback(x, t, None, op, block_idx, pca_rank, chunks, min_iter, max_iter, convergence_threshold, V0)
+
+    def local_x0_decoder_pullback_xt(self, x=None, t=None, at=None, op="mid", block_idx=0, pca_rank=50, chunk_size=10, num_chunk=None,
+                                     min_iter=10, max_iter=100, convergence_threshold=1e-3, V0=None):
+        """Reference: PullBackDDPM.local_x0_decoder_pullback_xt, src/models/ddpm/diffusion.py:634-710: the same SVD for
+        x0 = (x - sqrt(1 - a_t) eps) / sqrt(a_t).  J_x0 = c J_dec with c = -sqrt(1 - a_t) / sqrt(a_t), so J_x0^T J_x0 = c^2 J_dec^T J_dec
+        has the same singular vectors (and the same iterates, stop test included): this is the decoder run with s scaled by |c| and vT by c,
+        exactly.  (`num_chunk` is accepted and unused, as in the reference; chunks = pca_rank // chunk_size, at least 1.)"""
+        a = at.to(torch.float32) if torch.is_tensor(at) else torch.tensor(float(at), dtype=torch.float32)
+        c = float((-(1 - a).sqrt() / a.sqrt()).reshape(-1)[0])
+        chunks = max(1, pca_rank // chunk_size)                                   # diffusion.py:664
+        u, s, vT = self._decoder_pullback(x, t, None, op, block_idx, pca_rank, chunks, min_iter, max_iter, convergence_threshold, V0)
+        return u, s * abs(c), vT * c
+
+    def local_decoder_pullback_zt(self, sample, timestep, encoder_hidden_states=None, op=None, block_idx=None, pca_rank=50, chunk_size=25,
+                                  min_iter=10, max_iter=100, convergence_threshold=None, V0=None):
+        """Reference: utils.local_decoder_pullback_zt, src/utils/utils.py:818-898 (SD).  Conventions of local_decoder_pullback_xt.
+        convergence_threshold=None (the reference's default, on which its own stop test raises: allclose(atol=None) is a TypeError) means
+        no early stop: max_iter iterations."""
+        chunks = max(1, pca_rank // chunk_size)                                   # utils.py:853, clamped as local_encoder_pullback_zt
+        return self._decoder_pullback(sample, timestep, encoder_hidden_states, op, block_idx, pca_rank, chunks, min_iter, max_iter,
+                                      convergence_threshold, V0)
+
+    def decoder_pullback_fixed(self, x, t, ctx, op, block_idx, pca_rank, n_iters, V0):
+        """pullback_fixed for the decoder: n_iters fused iterations (dpb_pullback_iterate_between), no host synchronisation.
+        V0 [b*k, N_h] or [k, N_h] (shared by the b samples); returns (u [N_h, b*k], s, vT [b*k, N_eps], conv [b, 2])."""
+        key = self._decoder_tap(op, block_idx)
+        eng = self.engine
+        eng.primal(x, _t_float(t), ctx, "eps")
+        b = x.shape[0]
+        V = V0.reshape(-1, eng.tap_numel(key)).to(device=self.device, dtype=torch.float32)
+        if V.shape[0] == pca_rank and b > 1:
+            V = V.repeat(b, 1)
+        V, U, s, conv = eng.iterate_between(key, "eps", V.contiguous().clone(), n_iters)
+        return V.T, s, U, conv
+
     def pullback_fixed(self, x, t, ctx, op, block_idx, pca_rank, n_iters, V0):
         """Fixed-iteration variant with no host synchronisation (what bench.py times)."""
         key = self._tap(op, block_idx)
@@ -209,8 +324,12 @@ def bind(unet, kind: str, cfg, dtype=torch.float32, device="cuda:0", **kw) -> Pu
     impl = PullbackUNet(kind, cfg, sd, dtype, device, **kw)
     unet._dpb = impl
     unet.get_h = types.MethodType(lambda self, *a, **k: self._dpb.get_h(*a, **k), unet)
+    unet.get_h_to_e = types.MethodType(lambda self, *a, **k: self._dpb.get_h_to_e(*a, **k), unet)
     if kind == "sd":
         unet.local_encoder_pullback_zt = types.MethodType(lambda self, *a, **k: self._dpb.local_encoder_pullback_zt(*a, **k), unet)
+        unet.local_decoder_pullback_zt = types.MethodType(lambda self, *a, **k: self._dpb.local_decoder_pullback_zt(*a, **k), unet)
     else:
         unet.local_encoder_pullback_xt = types.MethodType(lambda self, *a, **k: self._dpb.local_encoder_pullback_xt(*a, **k), unet)
+        unet.local_decoder_pullback_xt = types.MethodType(lambda self, *a, **k: self._dpb.local_decoder_pullback_xt(*a, **k), unet)
+        unet.local_x0_decoder_pullback_xt = types.MethodType(lambda self, *a, **k: self._dpb.local_x0_decoder_pullback_xt(*a, **k), unet)
     return impl

@@ -138,6 +138,35 @@ int dpb_orth_checked(const float* W, const float* Vprev, float* V, float* s, flo
  * Replaces: the loop body utils.py:756-808 (k <= 128), once per sample of the batch. */
 int dpb_pullback_iterate(dpb_engine* e, int tap_buf, float* V, float* U, float* s, float* conv, int k, int n_iters);
 
+/* ---- the decoder pullback: passes seeded at an inner activation (additive to ABI version 1) -----------------------------
+ * J_dec = d eps / d h of the tap-to-output map, every skip connection held at its primal value (reference: PullBackDDPM.get_h_to_e,
+ * src/models/ddpm/diffusion.py:273-345; utils.get_h_to_e, src/utils/utils.py:529-635).  src_buf is the seed (a tap h), dst_buf a buffer
+ * downstream of it (the eps buffer).  A buffer carries a tangent / cotangent in these passes iff it is reachable forward from src_buf; the
+ * others (skip activations, the time-embedding and text paths, everything upstream of src_buf) are constants.  With src_buf = x_buf the
+ * passes are exactly dpb_jvp / dpb_vjp / dpb_pullback_iterate.  Primal state: dpb_primal(..., upto_buf = dst_buf or later) keeps everything
+ * these passes read (its stash already covers the whole prefix of the tape); a primal that stops before dst_buf is refused, as are a dst_buf
+ * not downstream of src_buf, dpb_forward's missing state and k outside [1, 128]; errors via dpb_last_error.
+ * V fp32 NCHW [nt][channels(src)][rows(src)], U fp32 NCHW [nt][channels(dst)][rows(dst)] (valid channels).
+ * Replace: torch.func.jacfwd of get_h_to_e (diffusion.py:599-602, utils.py:863-866) and autograd.functional.jacobian (diffusion.py:614-616,
+ * utils.py:878-880). */
+int dpb_jvp_between(dpb_engine* e, int src_buf, int dst_buf, const float* V, int nt, float* U);
+int dpb_vjp_between(dpb_engine* e, int src_buf, int dst_buf, const float* U, int nt, float* W);
+/* Device scratch the iteration below needs for k directions per sample, at the engine's max_batch: the fp32 staging of W = J^T J V and one
+ * re-orthonormalisation slot per sample, both sized by N = numel(src_buf) -- the caller provides it, so the engine workspace
+ * (dpb_engine_workspace_bytes) does not grow for engines that never run the decoder.  0 for an invalid src_buf or k outside [1, 128]. */
+size_t dpb_pullback_scratch_bytes(const dpb_engine* e, int src_buf, int k);
+/* dpb_pullback_iterate between src_buf and dst_buf: V [B][k][N_src] in/out, U [B][k][N_dst] out (J V_prev of the last iteration), s [B][k],
+ * conv [B][2]; no host synchronisation.  scratch: 256-byte aligned device memory of scratch_bytes >= what B = the last primal's batch needs
+ * (dpb_pullback_scratch_bytes is enough for any B).  Replaces: the loop body of local_decoder_pullback_xt / _zt (diffusion.py:592-625,
+ * utils.py:856-890), k <= 128. */
+int dpb_pullback_iterate_between(dpb_engine* e, int src_buf, int dst_buf, float* V, float* U, float* s, float* conv, int k, int n_iters,
+                                 void* scratch, size_t scratch_bytes);
+/* Forward from a tap (get_h_to_e): the primal to src_buf at `batch` samples of x (the caller repeats x), P(src_buf) overwritten by h
+ * (fp32 NCHW [batch][channels(src)][rows(src)]), then on to dst_buf, copied out like dpb_forward (whose state rules it shares: no primal
+ * state afterwards).  Replaces: get_h_to_e with input_h.size(0) = batch (utils.py:593-606, diffusion.py:321-325: the skips repeated). */
+int dpb_forward_from(dpb_engine* e, const float* x, int batch, float t, const float* ctx, int src_buf, const float* h, int dst_buf, int channels,
+                     float* out);
+
 /* DDIM update (utils.py:301-306 / :1220-1225, eta = 0) and the x-space-guidance axpy (edit.py:490, :501). */
 int dpb_ddim_step(const float* x, const float* eps, float* out, float* x0, int64_t n, float alpha_t, float alpha_next,
                   void* hip_stream);
