@@ -1278,6 +1278,16 @@ int dpb_orth_checked(const float* W, const float* Vprev, float* V, float* s, flo
 
 size_t dpb_orth_scratch_bytes(int k, int64_t N) { return (k < 1 || k > ORTH_MAX_RANK || N < 1) ? 0 : orth_scratch_bytes(k, N); }
 
+// torch.pca_lowrank(H, q, center=True, niter) for the reference's global_pca_zt (src/utils/utils.py:978-1027; torch._lowrank._svd_lowrank +
+// get_approximate_basis): pca.hip
+size_t dpb_pca_scratch_bytes(int q, int64_t N, int64_t D) { return pca_scratch_bytes(q, N, D); }
+
+int dpb_pca_lowrank(const float* H, int64_t N, int64_t D, const float* R, int q, int niter, float* u, float* s, void* scratch,
+                    size_t scratch_bytes, void* stream) {
+  if (!H || !R || !u || !s || (!scratch && scratch_bytes)) return fail("dpb_pca_lowrank: null argument");   // (no scratch: the size check below fails)
+  return launch_pca_lowrank(H, N, D, R, q, niter, u, s, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
 static int g_iter_alias = getenv("DPB_ITER_ALIAS") ? atoi(getenv("DPB_ITER_ALIAS")) : 1;   // A/B switch: 0 = convert U out and back in every iteration
 static int g_orth_batch = getenv("DPB_ORTH_BATCH") ? atoi(getenv("DPB_ORTH_BATCH")) : 1;   // A/B switch: 0 = re-orthonormalise the samples of a batch one by one
 static int g_graph_iterate = 0;      // dpb_debug_set("graph_iterate", 1): replay the power iteration as a captured hipGraph (measurement option)

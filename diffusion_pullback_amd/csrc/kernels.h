@@ -208,6 +208,13 @@ constexpr int ORTH_MAX_RANK = 128;   // largest pca_rank of the re-orthonormalis
 int launch_orth(const OrthArgs& a, hipStream_t st);
 size_t orth_scratch_bytes(int k, long N);
 
+// ---------------------------------------------------------------- randomized low-rank PCA (pca.hip): torch.pca_lowrank(H, q, center=True, niter)
+// H [N][D] fp32, R [min(N, D)][q] (torch.randn(A.shape[-1], q) of _svd_lowrank's A), u [q][D] (rows: the reference's u^T), s [q]
+const char* pca_invalid(int q, long N, long D);          // nullptr if the shape is supported
+size_t pca_scratch_bytes(int q, long N, long D);         // 0 when invalid
+int launch_pca_lowrank(const float* H, long N, long D, const float* R, int q, int niter, float* u, float* s, void* scratch, size_t scratch_bytes,
+                       hipStream_t st);
+
 // ---------------------------------------------------------------- DDIM
 // x_next = sqrt(a_next) * (x - e*sqrt(1-a_t))/sqrt(a_t) + sqrt(1-a_next) * e      (fp32, elementwise)
 int launch_ddim_step(const float* x, const float* e, float* out, float* x0, long n, float a_t, float a_next, hipStream_t st);

@@ -127,15 +127,21 @@ class Engine:
             L.check(self.lib.dpb_read_buffer(self.h, buf, c, _ptr(out)))
         return out
 
-    def forward(self, x, t, ctx=None, tap="eps") -> torch.Tensor:
+    def forward(self, x, t, ctx=None, tap="eps", out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Forward only (dpb_forward): the U-Net calls of the DDIM / guidance loop and get_h.  Keeps no tangent / adjoint stash,
-        so jvp / vjp / iterate need a primal() first (the engine refuses otherwise)."""
+        so jvp / vjp / iterate need a primal() first (the engine refuses otherwise).  out: a contiguous fp32 device tensor of
+        B * C * H * W elements to write into (a row slice of a feature matrix); returned viewed as [B, C, H, W]."""
         buf = self.tape.taps[tap]
         c, h, w = self.tape.tap_shape[buf]
         with torch.cuda.device(self.device):
             self._set_stream()
             x, b, ctx = self._inputs(x, ctx)
-            out = torch.empty(b, c, h, w, dtype=torch.float32, device=self.device)
+            if out is None:
+                out = torch.empty(b, c, h, w, dtype=torch.float32, device=self.device)
+            else:
+                if not (out.is_cuda and out.device == x.device and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == b * c * h * w):
+                    raise L.DpbError(f"out must be a contiguous fp32 tensor of {b * c * h * w} elements on {x.device}")
+                out = out.view(b, c, h, w)
             L.check(self.lib.dpb_forward(self.h, _ptr(x), b, float(t), _ptr(ctx), buf, c, _ptr(out)))
             self.batch = 0
         return out
@@ -265,3 +271,26 @@ class Engine:
         n = C.c_int64(); f = C.c_double(); b = C.c_double()
         L.check(self.lib.dpb_engine_stats(self.h, C.byref(n), C.byref(f), C.byref(b)))
         return n.value, f.value, b.value
+
+
+def pca_lowrank(H: torch.Tensor, R: torch.Tensor, q: int, niter: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """torch.pca_lowrank(H, q, center=True, niter) on the GPU (dpb_pca_lowrank; engine-independent).  H [N, D] fp32 contiguous on a HIP device,
+    R the Gaussian draw of torch._lowrank.get_approximate_basis ([N, q] if N < D, else [D, q]).  Returns device tensors u [q, D] (rows = the
+    columns of pca_lowrank's V, sign arbitrary) and s [q]; no host sync.  Limits: 1 <= q <= 128, q <= N - 1, q <= D."""
+    lib = L.load()
+    if H.dim() != 2 or not H.is_cuda or H.dtype != torch.float32 or not H.is_contiguous():
+        raise L.DpbError("H must be a contiguous fp32 [N, D] tensor on a HIP device")
+    n, d = H.shape
+    with torch.cuda.device(H.device):
+        st = torch.cuda.current_stream(H.device).cuda_stream
+        need = int(lib.dpb_pca_scratch_bytes(int(q), n, d))
+        R = _f32(R, H.device)
+        u = torch.empty(max(int(q), 1), d, dtype=torch.float32, device=H.device)
+        s = torch.empty(max(int(q), 1), dtype=torch.float32, device=H.device)
+        if need == 0:                                  # unsupported shape: the library states why
+            L.check(lib.dpb_pca_lowrank(_ptr(H), n, d, _ptr(R), int(q), int(niter), _ptr(u), _ptr(s), None, 0, C.c_void_p(st)))
+        if tuple(R.shape) != (min(n, d), q):
+            raise L.DpbError(f"R has shape {tuple(R.shape)}, expected [{min(n, d)}, {q}] (torch.randn(A.shape[-1], q) of _svd_lowrank's A)")
+        scratch = torch.empty(need, dtype=torch.uint8, device=H.device)
+        L.check(lib.dpb_pca_lowrank(_ptr(H), n, d, _ptr(R), int(q), int(niter), _ptr(u), _ptr(s), _ptr(scratch), need, C.c_void_p(st)))
+    return u, s

@@ -30,7 +30,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import lib as L
-from .engine import Engine
+from .engine import Engine, pca_lowrank
 from .tape import build_ddpm, build_sd
 
 MAX_RANK = 56          # default tangent capacity of an engine (workspace sizing)
@@ -311,6 +311,69 @@ class PullbackUNet:
         U, s, V, conv = pdist.k_sharded_power_iteration(jtj, eng.orth, V, n_iters, group)
         return U.T, s, V, conv
 
+    # ------------------------------------------------------------------ global h-space PCA and h -> x directions
+    def global_pca_zt(self, sample=None, timestep=None, encoder_hidden_states=None, op=None, block_idx=None, memory_bound=5, pca_rank=100,
+                      pca_device="cpu", x=None, t=None):
+        """Reference: utils.global_pca_zt, src/utils/utils.py:978-1027.  h = get_h of every sample (one encoder_hidden_states for all of them, as
+        the reference's .repeat), then torch.pca_lowrank(h [N, D], q=pca_rank, center=True, niter=5) -- here dpb_pca_lowrank on the GPU.
+        Returns (u [D, q], s [q]) on pca_device in sample.dtype.  R is drawn with torch.randn on pca_device where pca_lowrank draws it, so a seeded
+        call with the default pca_device='cpu' uses the reference's own R.  uncond: global_pca_zt(x=..., t=..., op, block_idx).
+        Limits: pca_rank <= 128 (RANK_LIMIT), pca_rank <= N - 1, pca_rank <= D."""
+        sample = x if sample is None else sample
+        timestep = t if timestep is None else timestep
+        key = self._tap(op, block_idx)
+        eng = self.engine
+        n, d, q = sample.shape[0], eng.tap_numel(key), int(pca_rank)
+        if eng.lib.dpb_pca_scratch_bytes(q, n, d) == 0:
+            raise ValueError(f"pca_rank={q} is not supported for {n} samples of {d} features: 1 <= pca_rank <= min({RANK_LIMIT}, N - 1, D)")
+        if memory_bound < 1:
+            raise ValueError(f"memory_bound={memory_bound} < 1")
+        time_s = time.time()
+        tt = _t_float(timestep)
+        H = torch.empty(n, d, dtype=torch.float32, device=self.device)
+        step = min(int(memory_bound), eng.max_batch)     # the reference's chunks hold <= memory_bound samples; the engine's batch bounds them too
+        for i0 in range(0, n, step):
+            b = min(step, n - i0)
+            eng.forward(sample[i0:i0 + b], tt, encoder_hidden_states, key, out=H[i0:i0 + b])
+        if self.verbose:
+            torch.cuda.synchronize(self.device)
+            c, hh, ww = eng.tape.tap_shape[eng.tape.taps[key]]
+            print("num_pca_samples ==", n)
+            print("h sampling t ==", time.time() - time_s)
+            print("h shape : ", torch.Size([n, c, hh, ww]))
+        time_s = time.time()
+        R = torch.randn(min(n, d), q, dtype=torch.float32, device=pca_device)    # torch._lowrank.get_approximate_basis: randn(A.shape[-1], q)
+        u, s = pca_lowrank(H, R, q, niter=5)
+        s = s.to(device=pca_device, dtype=sample.dtype)
+        u = u.T.to(device=pca_device, dtype=sample.dtype)
+        if not (torch.isfinite(s).all() and (s > 0).all()):
+            raise L.DpbError(f"global_pca_zt: the centred features have rank < pca_rank={q} (singular values {s.tolist()})")
+        if self.verbose:
+            print("torch.pca_lowrank t ==", time.time() - time_s)
+            print(f"eigenvalue spectrum : {s}")
+        return u, s
+
+    def inv_jac_zt(self, sample=None, timestep=None, encoder_hidden_states=None, op=None, block_idx=None, u=None, perturb_h=1e-1, x=None, t=None):
+        """Reference: utils.inv_jac_zt, src/utils/utils.py:1117-1160: the x-space direction of the h-space direction u at one sample.  The
+        reference differentiates ||h + perturb_h u - get_h(x)|| at x, whose gradient is -J^T u / ||u||; so vT = -J^T u / ||J^T u|| (one primal,
+        one adjoint pass; perturb_h drops out).  u [D] -> vT [1, N_in].  Extension: u [D, k] (the reference raises NotImplementedError, the
+        code after its raise states the result) -> vT [k, N_in], row i from column i, each row normalised; the adjoints run in chunks of max_rank."""
+        sample = x if sample is None else sample
+        timestep = t if timestep is None else timestep
+        key = self._tap(op, block_idx)
+        if sample.shape[0] != 1:
+            raise ValueError("sample size should be 1")                         # utils.py:1146
+        eng = self.engine
+        d = eng.tap_numel(key)
+        if u is None or u.numel() % d != 0 or (u.dim() == 1 and u.numel() != d):
+            raise ValueError(f"u must be [{d}] or [{d}, k] (features of the tap ({op}, {block_idx}))")
+        U = u.reshape(1, d) if u.dim() == 1 else u.reshape(d, -1).T
+        U = U.to(device=self.device, dtype=torch.float32).contiguous()
+        eng.primal(sample, _t_float(timestep), encoder_hidden_states, key)
+        W = torch.cat([eng.vjp(key, ui) for ui in U.split(self.max_rank)], dim=0)
+        vT = -W / W.norm(dim=1, keepdim=True)
+        return vT.to(sample.dtype)
+
 
 def bind(unet, kind: str, cfg, dtype=torch.float32, device="cuda:0", **kw) -> PullbackUNet:
     """Attach the HIP-backed methods onto an existing U-Net module, like the reference's
@@ -328,6 +391,8 @@ def bind(unet, kind: str, cfg, dtype=torch.float32, device="cuda:0", **kw) -> Pu
     if kind == "sd":
         unet.local_encoder_pullback_zt = types.MethodType(lambda self, *a, **k: self._dpb.local_encoder_pullback_zt(*a, **k), unet)
         unet.local_decoder_pullback_zt = types.MethodType(lambda self, *a, **k: self._dpb.local_decoder_pullback_zt(*a, **k), unet)
+        unet.global_pca_zt = types.MethodType(lambda self, *a, **k: self._dpb.global_pca_zt(*a, **k), unet)
+        unet.inv_jac_zt = types.MethodType(lambda self, *a, **k: self._dpb.inv_jac_zt(*a, **k), unet)
     else:
         unet.local_encoder_pullback_xt = types.MethodType(lambda self, *a, **k: self._dpb.local_encoder_pullback_xt(*a, **k), unet)
         unet.local_decoder_pullback_xt = types.MethodType(lambda self, *a, **k: self._dpb.local_decoder_pullback_xt(*a, **k), unet)

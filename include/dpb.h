@@ -132,6 +132,19 @@ size_t dpb_orth_scratch_bytes(int k, int64_t N);   /* 0 for k outside [1, 128] *
 int dpb_orth_checked(const float* W, const float* Vprev, float* V, float* s, float* conv, void* scratch, size_t scratch_bytes, int k, int64_t N,
                      void* hip_stream);
 
+/* ---- randomized low-rank PCA of a feature matrix (additive to ABI version 1; engine-independent) ------------------------------
+ * torch.pca_lowrank(H, q, center=True, niter) -- torch._lowrank._svd_lowrank + get_approximate_basis (Halko et al. 2009, 4.4 / 5.1) -- of
+ * H [N][D] fp32 (N samples of D features), as the reference's global_pca_zt calls it (src/utils/utils.py:978-1027, the pca_lowrank at :1017).
+ * R: the Gaussian draw of get_approximate_basis exactly as torch.randn(A.shape[-1], q) makes it for _svd_lowrank's A: [N][q] if N < D
+ * (A = H^T), else [D][q].  Out: u [q][D] (rows = the columns of the reference's u = _svd_lowrank's V, sign arbitrary), s [q] (its S,
+ * descending).  The QR factorisations and svd(B) are dpb_orth (same spans); products on the f32-input MFMA, every reduction in a fixed
+ * order (bitwise reproducible), 64-bit offsets (H may exceed 4 GiB).  1 <= q <= 128, q <= N - 1, q <= D, niter >= 0; scratch: device
+ * memory of >= dpb_pca_scratch_bytes(q, N, D) bytes (any alignment).  No host synchronisation.  A rank-deficient centred H gives s = 0
+ * in the missing directions (and zero rows of u).  Errors via dpb_last_error. */
+size_t dpb_pca_scratch_bytes(int q, int64_t N, int64_t D);   /* 0 when invalid */
+int dpb_pca_lowrank(const float* H, int64_t N, int64_t D, const float* R, int q, int niter, float* u, float* s, void* scratch,
+                    size_t scratch_bytes, void* hip_stream);
+
 /* n_iters full power iterations with no host synchronisation: V <- orth(J^T J V), U = J V_prev, for all B samples
  * of the last dpb_primal together (independent bases, one shared weight stream; B*k <= max_tangents).
  * V [B][k][N_in] in/out, U [B][k][N_h] out, s [B][k] out, conv [B][2] out (of the last iteration).
