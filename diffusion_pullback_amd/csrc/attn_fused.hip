@@ -753,6 +753,7 @@ __global__ __launch_bounds__((FA<D, W>::NT), (D <= 40 ? 2 : 1)) void attn_adj_kv
   }
   bf16* gKp = a.gK + j * LC + (long)key * a.C + h * D;
   bf16* gVp = a.gV + j * LC + (long)key * a.C + h * D;
+  const bool kv_same = a.gK == a.gV;             // k and v windows of one buffer coincide (the engine then sets accK alone)
 #pragma unroll
   for (int d = 0; d < F::ND; ++d)
 #pragma unroll
@@ -762,18 +763,20 @@ __global__ __launch_bounds__((FA<D, W>::NT), (D <= 40 ? 2 : 1)) void attn_adj_kv
         float vk[4], vv[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) { vk[i] = a.scale * accK[d][g * 4 + i]; vv[i] = accV[d][g * 4 + i]; }
+        if (kv_same)                                    // k and v are one window: one store of gK + gV
+          for (int i = 0; i < 4; ++i) vk[i] += vv[i];
         if (a.accK) {
           uint2 ov = *reinterpret_cast<const uint2*>(gKp + col);
           vk[0] += H16<FL>::lo(ov.x); vk[1] += H16<FL>::hi(ov.x);
           vk[2] += H16<FL>::lo(ov.y); vk[3] += H16<FL>::hi(ov.y);
         }
-        if (a.accV) {
+        if (a.accV && !kv_same) {
           uint2 ov = *reinterpret_cast<const uint2*>(gVp + col);
           vv[0] += H16<FL>::lo(ov.x); vv[1] += H16<FL>::hi(ov.x);
           vv[2] += H16<FL>::lo(ov.y); vv[3] += H16<FL>::hi(ov.y);
         }
         store_out8<DPB_OUT_STORE_ATT>(gKp + col, H16<FL>::pack2(vk[0], vk[1]), H16<FL>::pack2(vk[2], vk[3]));
-        store_out8<DPB_OUT_STORE_ATT>(gVp + col, H16<FL>::pack2(vv[0], vv[1]), H16<FL>::pack2(vv[2], vv[3]));
+        if (!kv_same) store_out8<DPB_OUT_STORE_ATT>(gVp + col, H16<FL>::pack2(vv[0], vv[1]), H16<FL>::pack2(vv[2], vv[3]));
       }
     }
 }
@@ -989,6 +992,7 @@ __global__ __launch_bounds__((SHK<D, TJ>::NT)) void attn_adj_kv_shared_kernel(Fu
   if (t >= nj) return;
   bf16* gKp = a.gK + (long)(j0 + t) * LC + (long)key * a.C + h * D;
   bf16* gVp = a.gV + (long)(j0 + t) * LC + (long)key * a.C + h * D;
+  const bool kv_same = a.gK == a.gV;             // k and v windows of one buffer coincide (the engine then sets accK alone)
 #pragma unroll
   for (int d = 0; d < S::ND; ++d)
 #pragma unroll
@@ -998,18 +1002,20 @@ __global__ __launch_bounds__((SHK<D, TJ>::NT)) void attn_adj_kv_shared_kernel(Fu
         float vk[4], vv[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) { vk[i] = a.scale * accK[d][gg * 4 + i]; vv[i] = accV[d][gg * 4 + i]; }
+        if (kv_same)                                    // k and v are one window: one store of gK + gV
+          for (int i = 0; i < 4; ++i) vk[i] += vv[i];
         if (a.accK) {
           uint2 ov = *reinterpret_cast<const uint2*>(gKp + col);
           vk[0] += H16<FL>::lo(ov.x); vk[1] += H16<FL>::hi(ov.x);
           vk[2] += H16<FL>::lo(ov.y); vk[3] += H16<FL>::hi(ov.y);
         }
-        if (a.accV) {
+        if (a.accV && !kv_same) {
           uint2 ov = *reinterpret_cast<const uint2*>(gVp + col);
           vv[0] += H16<FL>::lo(ov.x); vv[1] += H16<FL>::hi(ov.x);
           vv[2] += H16<FL>::lo(ov.y); vv[3] += H16<FL>::hi(ov.y);
         }
         store_out8<DPB_OUT_STORE_ATT>(gKp + col, H16<FL>::pack2(vk[0], vk[1]), H16<FL>::pack2(vk[2], vk[3]));
-        store_out8<DPB_OUT_STORE_ATT>(gVp + col, H16<FL>::pack2(vv[0], vv[1]), H16<FL>::pack2(vv[2], vv[3]));
+        if (!kv_same) store_out8<DPB_OUT_STORE_ATT>(gVp + col, H16<FL>::pack2(vv[0], vv[1]), H16<FL>::pack2(vv[2], vv[3]));
       }
     }
 }
@@ -1280,6 +1286,8 @@ static int att_block_waves(int d, int L, int pairs) {
   if (force == 4 || force == 8) return force;
   return ((long)(L / 256) * pairs) % 256 == 0 ? 8 : 4;
 }
+
+int attn_jvp_block_waves(int d, int L, int pairs) { return att_block_waves(d, L, pairs); }
 
 int launch_attn_jvp_fused(const FusedAttnArgs& f, int nt, hipStream_t st) {
   FusedArgs a = to_args(f);

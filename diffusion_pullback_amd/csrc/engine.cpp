@@ -157,7 +157,8 @@ int flush_pending(dpb_engine* e) {                 // the designated consumer di
 
 // ---- measurement brackets (dpb_engine_profile): an event pair around one launch (or one fused group of launches) with its algorithmic flops.
 // kind: 0..6 the GEMM kernel kinds (include/dpb.h), 7 flash attention forward, 8 fused attention tangent, 9 fused attention adjoint (query-major +
-// key-major launches together; `gather` holds the route bits of attn_adj_route_bits), 10 one-launch cross-attention tangent / adjoint
+// key-major launches together; `gather` holds the route bits of attn_adj_route_bits; for kind 8 it holds the kernel's waves per block), 10 one-launch
+// cross-attention tangent / adjoint
 int prof_open(dpb_engine* e, double flops, int kind, int M, int N, int K, int Z, int gather) {
   if (!e->profiling) return -1;
   dpb_engine::Prof p;
@@ -629,7 +630,7 @@ int attn_tangent(dpb_engine* e, const Op& op, int nt) {
     f.dQ = t.Q; f.dK = t.K; f.dV = t.V; f.dO = t.O;
     const double fl = 2.0 * p.Lq * (double)p.Lk * p.d * 5 * nt * H;     // dS (2 products), dP V, P dV + the recomputed scores: 5 L x L x d products
     e->flops += fl;
-    const int pi = prof_open(e, fl, 8, p.Lq, p.Lk, p.d, nt * H, 0);
+    const int pi = prof_open(e, fl, 8, p.Lq, p.Lk, p.d, nt * H, attn_jvp_block_waves(p.d, p.Lq, nt * H));
     const int r = launch_attn_jvp_fused(f, nt, e->stream);
     prof_close(e, pi);
     return r;
@@ -686,8 +687,12 @@ int attn_adjoint(dpb_engine* e, const Op& op, int nt) {
   float* Dv = (float*)(ws + e->Dv);
   const AttnPtrs x = attn_ptrs(e, d, p, 0), c = attn_ptrs(e, d, p, 2);
   const char* gO = c.O;
-  // first-write / accumulate flags, read up front: q, k, v may be windows of ONE buffer (fused QKV)
-  const int accQ = e->ginit[d.in0], accK = p.kv_const ? 0 : e->ginit[d.in1], accV = p.kv_const ? 0 : e->ginit[d.in2];
+  // first-write / accumulate flags, read up front: q, k, v may be windows of ONE buffer (fused QKV).  A window that IS an earlier-written one
+  // (q, k and v of one [rows][C] input) accumulates onto it: gQ is written first; gV, then gK on the materialised path; the fused key-major
+  // kernels write gK + gV once when their windows coincide
+  const bool kq = d.in1 == d.in0 && p.ok == p.oq, vq = d.in2 == d.in0 && p.ov == p.oq, vk = d.in2 == d.in1 && p.ov == p.ok;
+  const int accQ = e->ginit[d.in0], accK = p.kv_const ? 0 : e->ginit[d.in1] || kq || (!p.fused && vk),
+            accV = p.kv_const ? 0 : e->ginit[d.in2] || vq;
   if (p.fused) {
     e->n_launch += attn_adj_launches(p.d, p.Lq, kps, nt);
     FusedAttnArgs f;
@@ -908,6 +913,9 @@ int dpb_engine_create(const dpb_net_desc* net, dpb_engine** out) {
       p.d = Cattn / p.heads;
       if (p.oq % 8 || p.ok % 8 || p.ov % 8 || p.oq + Cattn > e->bufs[d.in0].C || p.ok + Cattn > e->bufs[d.in1].C || p.ov + Cattn > e->bufs[d.in2].C)
         return bad("bad q/k/v column window", i);
+      auto part = [&](int b0, int o0, int b1, int o1) { return b0 == b1 && o0 != o1 && o0 < o1 + Cattn && o1 < o0 + Cattn; };
+      if (part(d.in0, p.oq, d.in1, p.ok) || part(d.in0, p.oq, d.in2, p.ov) || part(d.in1, p.ok, d.in2, p.ov))
+        return bad("q/k/v windows of one buffer must coincide or be disjoint", i);
       if (p.d % 8) return bad("head dim must be a multiple of 8", i);
       p.Lq = e->bufs[d.in0].rows; p.Lk = e->bufs[d.in1].rows;
       p.Lqp = round8(p.Lq); p.Lkp = round8(p.Lk);

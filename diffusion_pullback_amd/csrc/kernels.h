@@ -158,6 +158,7 @@ int launch_attn_cross(const CrossAttnArgs& f, int nt, hipStream_t st);
 int launch_row_stats(int fl, const void* S, float* stats, long nrows, int Lk, int ld, hipStream_t st);
 int attn_adj_route_bits(int d, int L, int kps, int nt);   // bit 0: multi-cotangent query-major kernel, bit 1: shared-probability key-major kernel
 int attn_adj_launches(int d, int L, int kps, int nt);   // kernels launch_attn_adj_fused enqueues for such a layer (2 or 3)
+int attn_jvp_block_waves(int d, int L, int pairs);   // waves per block of the fused tangent kernel launch_attn_jvp_fused picks (pairs = nt * heads)
 int launch_attn_fwd_fused(const FusedAttnArgs& f, int batch, void* O, float* stats, hipStream_t st);   // primal O + row statistics
 int launch_attn_jvp_fused(const FusedAttnArgs& f, int nt, hipStream_t st);
 int launch_attn_adj_fused(const FusedAttnArgs& f, int nt, hipStream_t st);
