@@ -4,6 +4,7 @@
     python bench.py --gpus N --steps K --warmup W                               # BASELINE configs[2], weak scaling
     python bench.py --gpus N --samples 64 --k 10 --ctx edit --samples-per-gpu 8   # BASELINE configs[3], strong scaling
     python bench.py --gpus 1 --steps K --warmup W --dump-outputs bench_outputs   # + the last timed region's (u, s, vT) as bench_outputs/*.npy
+    python bench.py --gpus 1 --full                                               # + every leg after the headline (see Output below)
 
 A *step* is one power iteration for k directions on one x_t sample: k JVPs + k VJPs through the U-Net prefix up to the
 tap + the k x N re-orthonormalisation (reference src/utils/utils.py:756-808).  A sample's job is one primal (stash) pass
@@ -18,10 +19,13 @@ all_gather of the final bases (dist.gather_bases) inside the timed region.
   * --samples T (strong): T samples in total (seeds 0..T-1), sample i on rank i mod N (dist.shard_indices), the whole job is
     T * 12 steps -- value = T * 12 / max-over-ranks time, "scaling": "strong" (the north star's 64-sample config).
 
-Output: ONE JSON line on rank 0 with `roofline` (dominant kernel = most GPU time, measured live with HIP events around
-every GEMM launch on the engine's stream in a separate instrumented iteration) and `cpu_baseline` (the CPU oracle, i.e.
-the reference's algorithm with the same autodiff calls, BASELINE.md section 3 protocol: 1 warm-up + 2 timed iterations on
-this host's cores, CPU model stated).
+Output: ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the
+headline; nothing else.  --full adds every other leg after the headline (each can still be dropped with its --no-* flag):
+`strong_scaling` (BASELINE configs[3]), `roofline` (dominant kernel = most GPU time, measured live with HIP events around
+every GEMM launch on the engine's stream in a separate instrumented iteration), `time_to_converged_basis`,
+`batched_throughput`, `two_stream_throughput`, `unet_forward`, `sd21_reference_setting` and `cpu_baseline` (the CPU oracle,
+i.e. the reference's algorithm with the same autodiff calls, BASELINE.md section 3 protocol: 1 warm-up + 2 timed iterations
+on this host's cores, CPU model stated).
 """
 import argparse
 import json
@@ -60,6 +64,9 @@ def parse():
                     help="strong-scaling mode (BASELINE configs[3]): total number of x_t samples sharded over the ranks; steps = samples * 12")
     ap.add_argument("--ctx", default="null", choices=["null", "edit"], help="SD conditioning: seeded null-prompt or edit-prompt embedding")
     ap.add_argument("--flat-spectrum", action="store_true", help="unshaped random-init weights (round-1 workload; the stop rule does not converge)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the other legs (strong scaling, roofline, time to a converged basis, batched and two-stream "
+                         "throughput, U-Net forward, SD-2.1-base setting, CPU baseline); the --no-* flags below drop single legs of a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-k", type=int, default=0, help="directions per CPU iteration (0 = all k)")
@@ -75,7 +82,9 @@ def parse():
                          "samples in id order; a fixed seeded subset of the samples when all of them exceed 60 MiB, i.e. at most 64 MB in all)")
     a = ap.parse_args()
     if a.profile_run:
-        a.repeats, a.no_cpu_baseline, a.no_roofline, a.no_unet_forward, a.no_strong_leg, a.no_sd21_leg = 1, True, True, True, True, True
+        a.repeats = 1
+    if a.profile_run or not a.full:                        # the headline alone: no leg after it
+        a.no_cpu_baseline, a.no_roofline, a.no_unet_forward, a.no_strong_leg, a.no_sd21_leg = True, True, True, True, True
     return a
 
 
@@ -537,7 +546,7 @@ def main():
 
 
     if a.workload == "sd15" and not strong and not a.no_strong_leg and tap == ("mid", 0) and not a.flat_spectrum:
-        # ---- BASELINE configs[3] / north-star ">= 6x strong scaling at 8 GPUs" leg, in EVERY run (so `bench.py --gpus N` alone reports it): 64 seeded
+        # ---- BASELINE configs[3] / north-star ">= 6x strong scaling at 8 GPUs" leg, in every --full run (`bench.py --gpus N --full` reports it): 64 seeded
         # x_t samples in total, edit-prompt ctx, k = 10; sample i on rank i mod N (dist.shard_indices), 8 advanced together, 12 iterations each, one
         # packed all_gather of the bases at the end (reference: one process per sample, src/scripts/main_celeba_hf_local_encoder_pullback.sh:2-9).
         # Not part of `value` (which stays the weak headline so that N = 1 agrees with BENCH).

@@ -525,3 +525,29 @@ def test_bench_dump_outputs_is_bounded_and_seeded(tmp_path, monkeypatch):
         assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= 64 * 10 ** 6
     j = a["sample_ids"][-1]
     assert np.array_equal(np.load(tmp_path / "b" / "vT.npy")[-1], big[j][2].numpy())
+
+
+def test_bench_plain_run_is_the_headline_alone(monkeypatch):
+    """bench.py without --full runs no leg after the headline (same steps, warm-up and repeats); --full runs every leg unless its --no-* flag
+    drops it; --profile-run drops them all even under --full."""
+    import importlib.util, os, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))    # bench.py sets it on import: undone after the test
+    spec = importlib.util.spec_from_file_location("dpb_bench_full", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    # these five flags gate every leg of main() after the headline (time_to_converged_basis, batched_throughput and two_stream_throughput
+    # run under no_roofline): a new leg needs a flag here, or a place under one of them
+    legs = ("no_cpu_baseline", "no_roofline", "no_unet_forward", "no_strong_leg", "no_sd21_leg")
+
+    def parse(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        a = bench.parse()
+        return a, [n for n in legs if getattr(a, n)]
+    a, dropped = parse("--gpus", "1", "--steps", "24", "--warmup", "12")
+    assert not a.full and dropped == list(legs) and (a.steps, a.warmup, a.repeats) == (24, 12, 7)
+    a, dropped = parse("--gpus", "1", "--steps", "24", "--warmup", "12", "--full")
+    assert a.full and dropped == [] and (a.steps, a.warmup, a.repeats) == (24, 12, 7)
+    assert parse("--full", "--no-sd21-leg", "--no-cpu-baseline")[1] == ["no_cpu_baseline", "no_sd21_leg"]
+    a, dropped = parse("--full", "--profile-run")
+    assert dropped == list(legs) and a.repeats == 1

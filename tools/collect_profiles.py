@@ -1,10 +1,11 @@
-"""Copy the evidence of one tools/gpu_final.sh run from gpurun_out/ (scratch) into profiles/ (tracked) under the names the tools expect:
+"""Copy the evidence of one tools/gpu_final.sh run from $OUT (scratch, default runs/, the directory gpu_final.sh wrote) into profiles/ (tracked)
+under the names the tools expect; a missing input is reported on stderr:
 
-    python tools/collect_profiles.py r02e r02        # gpurun_out/r02e_*  ->  profiles/r02_*
+    [OUT=dir] python tools/collect_profiles.py r02e r02        # $OUT/r02e_*  ->  profiles/r02_*
 
   r02_sd15_mid_k5_bf16_kernel_stats.csv      rocprofv3 --kernel-trace --stats of  bench.py --steps 36 --warmup 12 --no-cpu-baseline --no-roofline
-  r02_sd15_gemm_launches_hip_events.csv      per-launch HIP-event durations of the GEMM kernels (bench.py roofline leg, DPB_PROFILE_CSV)
-  r02_bench_sd15_mid_k5_bf16.json            the headline bench line of the same session
+  r02_sd15_gemm_launches_hip_events.csv      per-launch HIP-event durations of the GEMM kernels (bench.py --full roofline leg, DPB_PROFILE_CSV)
+  r02_bench_sd15_mid_k5_bf16.json            the bench.py --full line of the same session
   r02_pmc_sd15_mid_k5_bf16.json              per-kernel PMC summary (MFMA busy, stall shares, FETCH_SIZE / WRITE_SIZE), tools/summarize_pmc.py
   r02_pmc_traffic_sd15_mid_k5_bf16.json      HBM bytes per launch per bench.py kernel label (what bench.py's `roofline.traffic` reads)
   r02_config_sweep.jsonl                     BASELINE configs[1], [3], [4] bench lines (tools/sweep_configs.sh)
@@ -17,7 +18,7 @@ import sys
 
 SRC_TAG = sys.argv[1]
 DST_TAG = sys.argv[2] if len(sys.argv) > 2 else SRC_TAG
-SRC, DST = "gpurun_out", "profiles"
+SRC, DST = os.environ.get("OUT") or "runs", "profiles"
 TRACE_ITERS = 48.0      # tools/gpu_session.sh traces `bench.py --steps 36 --warmup 12 --profile-run`: 48 power iterations (+ 4 primal passes, ~2 % of the product time)
 PMC_ITERS = 12.0        # tools/pmc_mfma.sh profiles `bench.py --steps 12 --warmup 0 --profile-run`: one sample, 12 power iterations
 
@@ -76,7 +77,14 @@ def main():
         p = os.path.join(SRC, s)
         if d and os.path.exists(p) and os.path.getsize(p) > 0:
             shutil.copy(p, os.path.join(DST, d))
+        elif d:
+            print(f"missing or empty, not copied: {p}", file=sys.stderr)
     pj = os.path.join(SRC, f"{SRC_TAG}_pmc_mfma.json")
+    stats = os.path.join(SRC, f"{SRC_TAG}_stats/sd15_kernel_stats.csv")
+    if not os.path.exists(pj):
+        print(f"missing: {pj} -- no pmc_traffic file written", file=sys.stderr)
+    elif not os.path.exists(stats):
+        print(f"missing: {stats} -- the pmc_traffic file gets no _trace block", file=sys.stderr)
     if os.path.exists(pj):
         agg = {}
         src_hash = json.load(open(pj)).get("_src_hash", "")

@@ -2,7 +2,7 @@
 VAR=$1; A=$2; B=$3; shift 3
 for rep in 1 2; do
   for v in $A $B; do
-    env $VAR=$v python bench.py --no-cpu-baseline --no-strong-leg --no-sd21-leg "$@" 2>/dev/null | python -c "
+    env $VAR=$v python bench.py --full --no-cpu-baseline --no-strong-leg --no-sd21-leg "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 u=d.get('unet_forward',{}).get('batches',{})

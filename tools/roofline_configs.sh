@@ -15,7 +15,7 @@ for CFG in $CFGS; do
   esac
   P=gpurun_out/${TAG}_${CFG}
   cd $R
-  DPB_PROFILE_CSV=${P}_gemm_launches_hip_events.csv python bench.py $ARGS --steps $ST --warmup $WU --no-cpu-baseline --no-unet-forward --no-strong-leg --repeats 3 > ${P}_bench.json 2> ${P}_bench.err
+  DPB_PROFILE_CSV=${P}_gemm_launches_hip_events.csv python bench.py $ARGS --steps $ST --warmup $WU --full --no-cpu-baseline --no-unet-forward --no-strong-leg --repeats 3 > ${P}_bench.json 2> ${P}_bench.err
   cd /tmp && export TMPDIR=/tmp
   B="python $R/bench.py $ARGS --profile-run"
   rocprofv3 --kernel-trace --stats --output-format csv -d $R/${P}_stats -o k -- $B --steps $ST --warmup $WU > /dev/null 2>&1

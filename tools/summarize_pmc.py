@@ -1,4 +1,4 @@
-"""Per-kernel PMC summary of tools/pmc_mfma.sh:  python tools/summarize_pmc.py gpurun_out TAG  -> gpurun_out/TAG_pmc_mfma.json + a table.
+"""Per-kernel PMC summary of tools/pmc_mfma.sh:  python tools/summarize_pmc.py [DIR] TAG  -> DIR/TAG_pmc_mfma.json + a table (DIR: $OUT, default runs).
 
 MFMA utilisation = SQ_VALU_MFMA_BUSY_CYCLES / (4 SIMDs x 256 CUs x GRBM_GUI_ACTIVE / 8): the share of SIMD-cycles with the matrix pipe
 busy while the kernel ran.  SQ_VALU_MFMA_BUSY_CYCLES counts cycles, 32 per v_mfma_f32_32x32x16 (checked: = 32 x SQ_INSTS_MFMA in every
@@ -13,7 +13,7 @@ import os
 import re
 import sys
 
-SRC = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out"
+SRC = sys.argv[1] if len(sys.argv) > 1 else os.environ.get("OUT") or "runs"
 TAG = sys.argv[2] if len(sys.argv) > 2 else "pmc"
 
 

@@ -1,8 +1,8 @@
-"""Turn the raw rocprofv3 output of tools/refresh_profiles.sh (under gpurun_out/) into the committed summaries under
+"""Turn the raw rocprofv3 output of tools/refresh_profiles.sh (under $OUT, default runs/) into the committed summaries under
 profiles/:  the --kernel-trace --stats CSV (copied as is), the per-kernel HBM traffic JSON from the two --pmc passes
 (FETCH_SIZE, WRITE_SIZE; separate runs, MI355X_MICROARCH.md HBM section), the per-launch HIP-event CSV and the bench lines.
 
-    python tools/summarize_profiles.py [gpurun_out] [profiles] [round-tag]
+    [OUT=dir] python tools/summarize_profiles.py [dir] [profiles] [round-tag]
 """
 import csv
 import glob
@@ -12,7 +12,7 @@ import re
 import shutil
 import sys
 
-SRC = sys.argv[1] if len(sys.argv) > 1 else "gpurun_out"
+SRC = sys.argv[1] if len(sys.argv) > 1 else os.environ.get("OUT") or "runs"
 DST = sys.argv[2] if len(sys.argv) > 2 else "profiles"
 TAG = sys.argv[3] if len(sys.argv) > 3 else "r01"
 
