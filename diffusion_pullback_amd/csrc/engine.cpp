@@ -1499,6 +1499,7 @@ int dpb_debug_set(const char* key, int value) {
   else if (!strcmp(key, "gemm_dma_auto")) { gemm_debug_dma_auto(value); return 0; }
   else if (!strcmp(key, "gemm_order")) { gemm_debug_order(value); return 0; }
   else if (!strcmp(key, "p8")) { gemm_debug_p8(value); return 0; }
+  else if (!strcmp(key, "halo_loop")) { conv_halo_debug_loop(value); return 0; }
   else if (!strcmp(key, "wres")) { gemm_debug_wres(value); return 0; }
   else if (!strcmp(key, "gn_deterministic")) { gn_debug_deterministic(value); return 0; }
   else if (!strcmp(key, "graph_iterate")) { g_graph_iterate = value; return 0; }

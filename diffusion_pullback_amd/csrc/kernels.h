@@ -63,6 +63,7 @@ bool gemm_p8_fits32(const GemmArgs& a);                                // its 32
 int launch_gemm_p8(const GemmArgs& a, int tile, hipStream_t st);      // 8-phase ping-pong loop (gemm_p8.hip); tile 530 = 256x256x64, 8 waves
 int conv_halo_supported(const GemmArgs& a);                        // 3x3 stride-1 convolution in halo-tile form (gemm_halo.hip)
 int launch_conv_halo(const GemmArgs& a, hipStream_t st);
+void conv_halo_debug_loop(int on);   // 1 (default): the 8-phase main loop of the halo convolution; 0: the ring loop, bitwise A/B
 int gemm_uses_halo(int dtype, const GemmArgs& a);
 int gemm_epi_supported(int dtype, const GemmArgs& a);   // can this launch take GemmArgs::epi != EPI_PLAIN?
 int gemm_uses_dma(int dtype, const GemmArgs& a);   // 0 = register-staged kernel, else the tile code for launch_gemm_dma

@@ -215,7 +215,7 @@ int dpb_engine_profile_overhead(const dpb_engine* e, double* bracket_overhead_ms
 /* Tuning overrides for micro-benchmarks and the bitwise kernel-equivalence tests (0 / -1 = heuristic): "gemm_tile"
  * (64, 128: register-staged; 129, 131, 133, 257, 65, 67: BK=32 rings; 512..518: BK=64 rings, 518 = 256x256 tile for plain-row operands, 530 = the 8-phase 256x256 tile (gemm_p8.hip), 540 = the weights-resident streaming kernel (gemm_wres.hip; products it does not take fall back to 515), 521 / 522 / 523 =
  * half tiles 64x128 (3 / 2 stages) and 128x64 for plain-row operands;
- * 600: halo-tile 3x3 convolution), "gemm_splitk" (n), "gemm_kch", "p8" (1, default: the dispatch may pick the 8-phase tile; 0 = the ring / halo dispatch of round 4), "wres" (1, default: K = 320 / N % 320 == 0 plain products of >= 8192 rows go to the weights-resident kernel; 0 = the round-5 dispatch; bitwise equal), "gemm_dma_auto" (0|1), "gemm_order" (-1 | 0 A-major | 1 B-major block
+ * 600: halo-tile 3x3 convolution), "gemm_splitk" (n), "gemm_kch", "p8" (1, default: the dispatch may pick the 8-phase tile; 0 = the ring / halo dispatch of round 4), "wres" (1, default: K = 320 / N % 320 == 0 plain products of >= 8192 rows go to the weights-resident kernel; 0 = the round-5 dispatch; bitwise equal), "halo_loop" (1, default: the halo-tile convolution runs its 8-phase main loop; 0 = its ring loop, also DPB_HALO_LOOP=0; bitwise equal), "gemm_dma_auto" (0|1), "gemm_order" (-1 | 0 A-major | 1 B-major block
  * order per XCD), "gn_deterministic" (1, default: GroupNorm statistics of the two-pass kernels reduced in a fixed order -> bitwise
  * reproducible runs; 0 = the round-1 atomic statistics, A/B only), "graph_iterate" (0|1: dpb_pullback_iterate replays a captured hipGraph on a non-default stream;
  * measured equal to eager launches, default 0), "attn_shared" (2, default: shared-probability key-major adjoint of the head-dim-40
