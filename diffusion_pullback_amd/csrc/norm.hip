@@ -72,6 +72,15 @@ __device__ inline uint4 slab_chunk(const SlabSrc& s, long row, int c0) {
   return packed;
 }
 
+// Shift of the primal statistics of (sample b, group g): the group's first value (pixel 0, first channel).  Every route accumulates sum (x - c) and
+// sum (x - c)^2 instead of sum x and sum x^2: var = E[(x - c)^2] - (E[x - c])^2 then cancels against (c - mean)^2 / var -- the squared z-score of one
+// sample of the group, O(1) -- instead of mean^2 / var, which for a group whose mean is large against its spread (mean 256, std 0.25) wiped out the
+// fp32 partials (2.6e-2 relative on the output).  Every block of every run reads the same c: the fixed-order reductions stay bitwise reproducible.
+template <typename T>
+__device__ inline float gn_shift(const GNArgs& a, int b, int g) {
+  return TT<T>::ld((const T*)a.x + (long)b * a.HW * a.C + g * (a.C / a.G));
+}
+
 template <typename T, int MODE, bool STATS>
 __global__ __launch_bounds__(256) void gn_kernel(GNArgs a, int ppb) {
   constexpr int CH = TT<T>::CH;
@@ -124,9 +133,10 @@ __global__ __launch_bounds__(256) void gn_kernel(GNArgs a, int ppb) {
     __syncthreads();
     if (MODE == MODE_PRIMAL) {
       for (int g = tid; g < a.G; g += 256) {
-        const double m = lseg[0][2 * g] * inv_n;
-        double v = lseg[0][2 * g + 1] * inv_n - m * m;
+        const double ms = lseg[0][2 * g] * inv_n;                // mean of x - c
+        double v = lseg[0][2 * g + 1] * inv_n - ms * ms;
         if (v < 0) v = 0;
+        const double m = (double)gn_shift<T>(a, j, g) + ms;
         const double rs = 1.0 / sqrt(v + (double)a.eps);
         lsum[2 * g] = (float)m; lsum[2 * g + 1] = (float)rs;
         if (blockIdx.x == 0) { a.pstats[((long)j * a.G + g) * 2] = m; a.pstats[((long)j * a.G + g) * 2 + 1] = rs; }   // kept for the tangent / adjoint passes
@@ -154,6 +164,8 @@ __global__ __launch_bounds__(256) void gn_kernel(GNArgs a, int ppb) {
         } else if (MODE != MODE_PRIMAL || !STATS) {
           me[0] = (float)a.pstats[((long)b * a.G + g0) * 2]; rs[0] = (float)a.pstats[((long)b * a.G + g0) * 2 + 1];
           me[1] = (float)a.pstats[((long)b * a.G + g1) * 2]; rs[1] = (float)a.pstats[((long)b * a.G + g1) * 2 + 1];
+        } else {                                                  // primal statistics: mean[] holds the shift (gn_shift)
+          me[0] = gn_shift<T>(a, b, g0); me[1] = gn_shift<T>(a, b, g1);
         }
         if (MODE != MODE_PRIMAL && !STATS && a.red) {
           t1[0] = lsum[2 * g0]; t2[0] = lsum[2 * g0 + 1]; t1[1] = lsum[2 * g1]; t2[1] = lsum[2 * g1 + 1];
@@ -177,6 +189,8 @@ __global__ __launch_bounds__(256) void gn_kernel(GNArgs a, int ppb) {
           } else if (MODE != MODE_PRIMAL || !STATS) {
             mean[e] = (float)a.pstats[((long)b * a.G + grp[e]) * 2];
             rstd[e] = (float)a.pstats[((long)b * a.G + grp[e]) * 2 + 1];
+          } else {
+            mean[e] = gn_shift<T>(a, b, grp[e]);                 // primal statistics: the shift
           }
           if (MODE != MODE_PRIMAL && !STATS && a.red) {
             m1[e] = lsum[2 * grp[e]]; m2[e] = lsum[2 * grp[e] + 1];
@@ -197,8 +211,9 @@ __global__ __launch_bounds__(256) void gn_kernel(GNArgs a, int ppb) {
         for (int e = 0; e < CH; ++e) {
           if (MODE == MODE_PRIMAL) {
             if (STATS) {
-              s1[e] += x[e];
-              s2[e] += x[e] * x[e];
+              const float xs = x[e] - mean[e];                    // shifted (gn_shift)
+              s1[e] += xs;
+              s2[e] += xs * xs;
             } else {
               float y = (x[e] - mean[e]) * rstd[e] * gam[e] + bet[e];
               o[e] = a.silu ? silu_(y) : y;
@@ -320,10 +335,12 @@ __global__ __launch_bounds__(512) void gn_fused_kernel(GNArgs a, int GC) {
     Vec<float>::load(a.gamma + ch0, gam);
     Vec<float>::load(a.beta + ch0, bet);
     if constexpr (CH == 8) { Vec<float>::load(a.gamma + ch0 + 4, gam + 4); Vec<float>::load(a.beta + ch0 + 4, bet + 4); }
+    const int g1 = min(g0 + 1, a.G - 1);
     if (MODE != MODE_PRIMAL) {
-      const int g1 = min(g0 + 1, a.G - 1);
       mean[0] = (float)a.pstats[((long)b * a.G + g0) * 2]; rstd[0] = (float)a.pstats[((long)b * a.G + g0) * 2 + 1];
       mean[1] = (float)a.pstats[((long)b * a.G + g1) * 2]; rstd[1] = (float)a.pstats[((long)b * a.G + g1) * 2 + 1];
+    } else {                                                    // primal: the shift of the statistics (gn_shift)
+      mean[0] = gn_shift<T>(a, b, g0); mean[1] = gn_shift<T>(a, b, g1);
     }
   }
   uint4 xr[MAXC], dr[MAXC];
@@ -347,8 +364,9 @@ __global__ __launch_bounds__(512) void gn_fused_kernel(GNArgs a, int GC) {
       for (int e = 0; e < CH; ++e) {
         const int hi = e >= split ? 1 : 0;
         if (MODE == MODE_PRIMAL) {
-          s[hi * 2] += x[e];
-          s[hi * 2 + 1] += x[e] * x[e];
+          const float xs = x[e] - mean[hi];
+          s[hi * 2] += xs;
+          s[hi * 2 + 1] += xs * xs;
         } else {
           const float xh = (x[e] - mean[hi]) * rstd[hi];
           const float y = gam[e] * xh + bet[e];
@@ -401,9 +419,10 @@ __global__ __launch_bounds__(512) void gn_fused_kernel(GNArgs a, int GC) {
   __syncthreads();
   if (MODE == MODE_PRIMAL) {
     if (tid < GC) {
-      const double m = gsum[0][tid] * inv_n;
-      double v = gsum[1][tid] * inv_n - m * m;
+      const double ms = gsum[0][tid] * inv_n;                   // mean of x - c
+      double v = gsum[1][tid] * inv_n - ms * ms;
       if (v < 0) v = 0;
+      const double m = (double)gn_shift<T>(a, j, gbase + tid) + ms;
       const double rs = 1.0 / sqrt(v + (double)a.eps);
       a.pstats[((long)j * a.G + gbase + tid) * 2] = m;
       a.pstats[((long)j * a.G + gbase + tid) * 2 + 1] = rs;
@@ -473,7 +492,7 @@ static int gn_fused_groups(int C, int G, int HW, int CH, int es) {
 // Large maps (more than GN_RED_MAX statistics blocks per sample: DDPM 64x64 and up, the image autoencoder): one small launch adds the per-block
 // partials in the same fixed order into the fp64 statistics (and finalises the primal ones), so the apply blocks need not each walk them.
 constexpr int GN_RED_MAX = 256;
-template <int MODE>
+template <typename T, int MODE>
 __global__ __launch_bounds__(1024) void gn_reduce_kernel(GNArgs a, int nblk) {
   // one block per sample / tangent: SEG = 1024 / 2G block-range segments per statistic, each added in block order with 32 clamped loads in flight
   // (a plain loop waits out one L2 round trip per partial: 60 us per launch on the 256 x 256 maps), then the segment sums in segment order
@@ -503,21 +522,24 @@ __global__ __launch_bounds__(1024) void gn_reduce_kernel(GNArgs a, int nblk) {
   } else {
     for (int g = tid; g < a.G; g += 1024) {
       const double s1 = total(2 * g), s2 = total(2 * g + 1);
-      const double m = s1 * inv_n;
-      double v = s2 * inv_n - m * m;
+      const double ms = s1 * inv_n;                            // mean of x - c (gn_shift)
+      double v = s2 * inv_n - ms * ms;
       if (v < 0) v = 0;
+      const double m = (double)gn_shift<T>(a, j, g) + ms;
       dst[((long)j * a.G + g) * 2] = m;
       dst[((long)j * a.G + g) * 2 + 1] = 1.0 / sqrt(v + (double)a.eps);
     }
   }
 }
 
-__global__ void gn_finalize(double* st, int n_groups, double inv_n, double eps) {
+template <typename T>
+__global__ void gn_finalize(GNArgs a, double* st, int n_groups, double inv_n, double eps) {
   int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_groups) return;
-  double m = st[2 * i] * inv_n;
-  double v = st[2 * i + 1] * inv_n - m * m;
+  double ms = st[2 * i] * inv_n;                                // mean of x - c (gn_shift)
+  double v = st[2 * i + 1] * inv_n - ms * ms;
   if (v < 0) v = 0;
+  const double m = (double)gn_shift<T>(a, i / a.G, i % a.G) + ms;
   st[2 * i] = m;
   st[2 * i + 1] = 1.0 / sqrt(v + eps);
 }
@@ -561,10 +583,10 @@ static int gn_launch(const GNArgs& a, hipStream_t st) {
   GNArgs b = a;
   b.red = a.det && (int)grid.x <= GN_RED_MAX;     // the apply blocks add the partials themselves (32 ... 256 L2-resident loads per thread quarter)
   hipLaunchKernelGGL((gn_kernel<T, MODE, true>), grid, dim3(256), lds, st, b, ppb);
-  if (a.det && !b.red) hipLaunchKernelGGL((gn_reduce_kernel<MODE>), dim3(n), dim3(1024), 0, st, b, (int)grid.x);
+  if (a.det && !b.red) hipLaunchKernelGGL((gn_reduce_kernel<T, MODE>), dim3(n), dim3(1024), 0, st, b, (int)grid.x);
   if (MODE == MODE_PRIMAL && !a.det) {
     int ng = a.Bp * a.G;
-    hipLaunchKernelGGL(gn_finalize, dim3((ng + 255) / 256), dim3(256), 0, st, a.pstats, ng, 1.0 / ((double)a.HW * (a.C / a.G)), (double)a.eps);
+    hipLaunchKernelGGL(gn_finalize<T>, dim3((ng + 255) / 256), dim3(256), 0, st, a, a.pstats, ng, 1.0 / ((double)a.HW * (a.C / a.G)), (double)a.eps);
   }
   hipLaunchKernelGGL((gn_kernel<T, MODE, false>), grid, dim3(256), 0, st, b, ppb);
   DPB_CHECK(hipGetLastError());
