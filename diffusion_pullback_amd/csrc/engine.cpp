@@ -99,6 +99,7 @@ struct dpb_engine {
   const float* fwd_h = nullptr;
   struct { bool on = false; GemmArgs a; } pend;   // a split-K product whose reduction is deferred to the normalisation op that consumes it
   bool fwd_only = false;            // dpb_forward: primal pass that keeps no tangent / adjoint stash (DDIM loop)
+  bool temb_keep = false;           // dpb_local_pca_sample, chunks after the first: P(temb_buf) already holds this t's embedding (no upload, no sync)
   std::vector<char> ginit;
   std::vector<char> skip;           // ops whose work a fused epilogue of another op has done in the current pass
   long n_launch = 0;
@@ -1100,7 +1101,7 @@ static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const 
     e->n_launch++;
     if (int r = launch_nchw_to_nhwc(e->dtype, ctx, e->P(e->ctx_buf), batch * bc.rows, bc.Cv, 1, bc.C, e->stream)) return r;
   }
-  if (e->temb_buf >= 0) {
+  if (e->temb_buf >= 0 && !e->temb_keep) {
     // sinusoidal timestep embedding, computed on the host in fp32 exactly as the reference frameworks do
     // (diffusion.py:783-804 / diffusers Timesteps), uploaded through the io staging area.
     const int dim = e->temb_dim, half = dim / 2;
@@ -1294,6 +1295,66 @@ int dpb_pca_lowrank(const float* H, int64_t N, int64_t D, const float* R, int q,
                     size_t scratch_bytes, void* stream) {
   if (!H || !R || !u || !s || (!scratch && scratch_bytes)) return fail("dpb_pca_lowrank: null argument");   // (no scratch: the size check below fails)
   return launch_pca_lowrank(H, N, D, R, q, niter, u, s, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+// The perturbed batch and the sampling loop of the reference's local_pca_zt / local_pca_xt (src/utils/utils.py:916-933;
+// src/models/ddpm/diffusion.py:396-409): noise.hip
+size_t dpb_perturb_scratch_bytes(int B, int64_t n) { return perturb_scratch_bytes(B, n); }
+
+int dpb_perturb_unit(const float* x, const float* noise, uint64_t seed, int64_t first, int B, int64_t n, float norm, float* out, float* noise_out,
+                     void* scratch, size_t scratch_bytes, void* stream) {
+  if (!x || !out || !scratch) return fail("dpb_perturb_unit: null argument");
+  return launch_perturb_unit(x, noise, seed, first, B, n, norm, out, noise_out, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+namespace {
+struct LocalPcaScratch { size_t xb = 0, ctxb = 0, part = 0, total = 0; long n_in = 0, n_ctx = 0; };
+void local_pca_layout(const dpb_engine* e, LocalPcaScratch& l) {
+  l.n_in = (long)e->bufs[e->x_buf].rows * e->x_channels;
+  l.n_ctx = e->ctx_buf >= 0 ? (long)e->bufs[e->ctx_buf].rows * e->bufs[e->ctx_buf].Cv : 0;
+  size_t off = 0;
+  auto take = [&](size_t b) { const size_t o = off; off += (b + 255) / 256 * 256; return o; };
+  l.xb = take((size_t)e->maxB * l.n_in * sizeof(float));
+  l.ctxb = take((size_t)e->maxB * l.n_ctx * sizeof(float));
+  l.part = take(perturb_scratch_bytes(e->maxB, l.n_in));
+  l.total = off;
+}
+}  // namespace
+
+size_t dpb_local_pca_scratch_bytes(const dpb_engine* e) {
+  LocalPcaScratch l;
+  if (e) local_pca_layout(e, l);
+  return l.total;
+}
+
+int dpb_local_pca_sample(dpb_engine* e, const float* x, float t, const float* ctx, int upto_buf, int channels, const float* noise, uint64_t seed,
+                         int64_t first, int64_t count, float* H, void* scratch, size_t scratch_bytes) {
+  if (!e || !x || !H || !scratch) return fail("dpb_local_pca_sample: null argument");
+  e->cur_batch = 0;                                // as dpb_forward: whatever happens below, the primal state is gone
+  if (count < 1 || first < 0 || first > INT64_MAX - count) return fail("dpb_local_pca_sample: first=%lld count=%lld invalid", (long long)first, (long long)count);
+  if (upto_buf < 0 || upto_buf >= (int)e->bufs.size() || e->producer[upto_buf] < 0) return fail("invalid upto buffer %d", upto_buf);
+  if (channels < 1 || channels > e->bufs[upto_buf].C) return fail("bad channel count");
+  if (e->ctx_buf >= 0 && !ctx) return fail("this network needs ctx (encoder_hidden_states)");
+  LocalPcaScratch l;
+  local_pca_layout(e, l);
+  if ((uintptr_t)scratch % 256) return fail("dpb_local_pca_sample: scratch must be 256-byte aligned");
+  if (scratch_bytes < l.total) return fail("dpb_local_pca_sample: scratch of %zu bytes, dpb_local_pca_scratch_bytes = %zu", scratch_bytes, l.total);
+  char* sc = (char*)scratch;
+  float* xb = (float*)(sc + l.xb);
+  float* cb = e->ctx_buf >= 0 ? (float*)(sc + l.ctxb) : nullptr;
+  const int64_t D = (int64_t)channels * e->bufs[upto_buf].rows;
+  for (int b = 0; cb && b < e->maxB; ++b)          // the conditioning of every chunk: max_batch copies, made once
+    DPB_CHECK(hipMemcpyAsync(cb + (size_t)b * l.n_ctx, ctx, (size_t)l.n_ctx * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+  int r = 0;
+  for (int64_t c0 = 0; c0 < count && !r; c0 += e->maxB) {
+    const int B = (int)std::min<int64_t>(e->maxB, count - c0);
+    r = launch_perturb_unit(x, noise ? noise + c0 * l.n_in : nullptr, seed, first + c0, B, l.n_in, 1.f, xb, nullptr, sc + l.part,
+                            l.total - l.part, e->stream);
+    e->temb_keep = c0 > 0;                         // same t as the chunk before: its embedding is still in P(temb_buf)
+    if (!r) r = dpb_forward(e, xb, B, t, cb, upto_buf, channels, H + c0 * D);
+  }
+  e->temb_keep = false;
+  return r;
 }
 
 static int g_iter_alias = getenv("DPB_ITER_ALIAS") ? atoi(getenv("DPB_ITER_ALIAS")) : 1;   // A/B switch: 0 = convert U out and back in every iteration

@@ -217,6 +217,13 @@ size_t pca_scratch_bytes(int q, long N, long D);         // 0 when invalid
 int launch_pca_lowrank(const float* H, long N, long D, const float* R, int q, int niter, float* u, float* s, void* scratch, size_t scratch_bytes,
                        hipStream_t st);
 
+// ---------------------------------------------------------------- the perturbed batch of local PCA (noise.hip)
+// out[b][j] = x[j] + norm * g_b[j] / ||g_b||_2, b < B, j < n (fp32); g_b = noise[b] or Philox4x32-10 normals of (seed, first + b) (dpb.h);
+// noise_out (optional) receives the unnormalised g; scratch: 8-byte aligned, >= perturb_scratch_bytes(B, n) (per-slice fp64 partial sums)
+size_t perturb_scratch_bytes(int B, long n);             // 0 when invalid
+int launch_perturb_unit(const float* x, const float* noise, uint64_t seed, int64_t first, int B, long n, float norm, float* out, float* noise_out,
+                        void* scratch, size_t scratch_bytes, hipStream_t st);
+
 // ---------------------------------------------------------------- DDIM
 // x_next = sqrt(a_next) * (x - e*sqrt(1-a_t))/sqrt(a_t) + sqrt(1-a_next) * e      (fp32, elementwise)
 int launch_ddim_step(const float* x, const float* e, float* out, float* x0, long n, float a_t, float a_next, hipStream_t st);

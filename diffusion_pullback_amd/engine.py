@@ -250,6 +250,41 @@ class Engine:
                                                           n_iters, C.c_void_p(scratch.data_ptr() + off), max(scratch.numel() - off, 0)))
         return V, U, s, conv
 
+    # ------------------------------------------------------------------ local PCA: the sampling loop on the device
+    def local_pca_sample(self, x: torch.Tensor, t: float, ctx: Optional[torch.Tensor], tap, count: int, noise: Optional[torch.Tensor] = None,
+                         seed: int = 0, first: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """dpb_local_pca_sample: `count` feature rows get_h(x + g_i / ||g_i||), i = first .. first + count - 1, of ONE input x [1, C, H, W]
+        (ctx [1, L, D] or None) at `tap`, in chunks of max_batch with no host round trip per chunk.  g_i = noise[i - first] (noise [count, ...]
+        unnormalised Gaussian draws) or, when noise is None, generated on the device from (seed, i).  out: a contiguous fp32 [count, D] device
+        tensor to write into (rows of a larger matrix), allocated here when None.  Like forward(), keeps no primal state."""
+        buf = self.tape.taps[tap]
+        c, h, w = self.tape.tap_shape[buf]
+        d = c * h * w
+        count, first = int(count), int(first)
+        with torch.cuda.device(self.device):
+            self._set_stream()
+            x, b, ctx = self._inputs(x, ctx)
+            if b != 1:
+                raise L.DpbError(f"local_pca_sample perturbs ONE input, got a batch of {b}")
+            if count < 1 or first < 0:
+                raise L.DpbError(f"local_pca_sample: count={count} and first={first} must be >= 1 and >= 0")
+            if noise is not None:
+                if noise.numel() != count * self.n_in:
+                    raise L.DpbError(f"noise has {noise.numel()} elements, expected count * N_in = {count} * {self.n_in}")
+                noise = _f32(noise, self.device)
+            if out is None:
+                out = torch.empty(count, d, dtype=torch.float32, device=self.device)
+            elif not (out.is_cuda and out.device == x.device and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == count * d):
+                raise L.DpbError(f"out must be a contiguous fp32 tensor of {count * d} elements on {x.device}")
+            need = int(self.lib.dpb_local_pca_scratch_bytes(self.h))
+            if getattr(self, "_lp_scratch", None) is None or self._lp_scratch.numel() < need + 256:
+                self._lp_scratch = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+            off = (-self._lp_scratch.data_ptr()) % 256
+            self.batch = 0
+            L.check(self.lib.dpb_local_pca_sample(self.h, _ptr(x), float(t), _ptr(ctx), buf, c, _ptr(noise), C.c_uint64(int(seed) & (2 ** 64 - 1)), first,
+                                                  count, _ptr(out), C.c_void_p(self._lp_scratch.data_ptr() + off), need))
+        return out.view(count, d)
+
     def profile(self, enable: bool):
         L.check(self.lib.dpb_engine_profile(self.h, int(enable)))
 
@@ -294,3 +329,28 @@ def pca_lowrank(H: torch.Tensor, R: torch.Tensor, q: int, niter: int) -> Tuple[t
         scratch = torch.empty(need, dtype=torch.uint8, device=H.device)
         L.check(lib.dpb_pca_lowrank(_ptr(H), n, d, _ptr(R), int(q), int(niter), _ptr(u), _ptr(s), _ptr(scratch), need, C.c_void_p(st)))
     return u, s
+
+
+def perturb_unit(x: torch.Tensor, B: int, noise: Optional[torch.Tensor] = None, seed: int = 0, first: int = 0, norm: float = 1.0,
+                 return_noise: bool = False):
+    """dpb_perturb_unit (engine-independent): out[b] = x + norm * g_b / ||g_b||_2 for b < B, x one fp32 input of any shape on a HIP device,
+    g_b = noise[b] (noise [B, *x.shape]) or the kernel's Philox4x32-10 normals of (seed, first + b) (include/dpb.h states the mapping).
+    Returns out [B, n] (n = x.numel()), and the unnormalised g [B, n] as well when return_noise.  No host sync."""
+    lib = L.load()
+    if not x.is_cuda:
+        raise L.DpbError("x must be on a HIP device")
+    x = _f32(x, x.device).reshape(-1)
+    n, B = x.numel(), int(B)
+    with torch.cuda.device(x.device):
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        if noise is not None:
+            if noise.numel() != B * n:
+                raise L.DpbError(f"noise has {noise.numel()} elements, expected B * n = {B} * {n}")
+            noise = _f32(noise, x.device)
+        out = torch.empty(max(B, 1), n, dtype=torch.float32, device=x.device)
+        g = torch.empty(max(B, 1), n, dtype=torch.float32, device=x.device) if return_noise else None
+        need = int(lib.dpb_perturb_scratch_bytes(B, n))
+        scratch = torch.empty(max(need // 8, 1), dtype=torch.float64, device=x.device)
+        L.check(lib.dpb_perturb_unit(_ptr(x), _ptr(noise), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(first), B, n, float(norm), _ptr(out), _ptr(g),
+                                     _ptr(scratch), need, C.c_void_p(st)))
+    return (out, g) if return_noise else out

@@ -87,6 +87,11 @@ SYMBOLS = {
     # randomized low-rank PCA of a feature matrix (global_pca_zt)
     "dpb_pca_scratch_bytes": (C.c_size_t, [_I, _L, _L]),
     "dpb_pca_lowrank": (_I, [_P, _L, _L, _P, _I, _I, _P, _P, _P, C.c_size_t, _P]),
+    # local h-space PCA (local_pca_zt / local_pca_xt): the perturbed batch and the sampling loop
+    "dpb_perturb_scratch_bytes": (C.c_size_t, [_I, _L]),
+    "dpb_perturb_unit": (_I, [_P, _P, C.c_uint64, _L, _I, _L, _F, _P, _P, _P, C.c_size_t, _P]),
+    "dpb_local_pca_scratch_bytes": (C.c_size_t, [_P]),
+    "dpb_local_pca_sample": (_I, [_P, _P, _F, _P, _I, _I, _P, C.c_uint64, _L, _L, _P, _P, C.c_size_t]),
 }
 
 _lib = None

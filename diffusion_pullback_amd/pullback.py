@@ -374,6 +374,90 @@ class PullbackUNet:
         vT = -W / W.norm(dim=1, keepdim=True)
         return vT.to(sample.dtype)
 
+    # ------------------------------------------------------------------ local h-space PCA: the sampling-based estimate of the local basis
+    def local_pca_zt(self, sample=None, timestep=None, encoder_hidden_states=None, op=None, block_idx=None, memory_bound=5, num_pca_samples=50000,
+                     pca_rank=RANK_LIMIT, pca_device="cpu", return_x_direction=True, perturb_h=1e-1, x=None, t=None, noise=None, seed=None):
+        """Reference: utils.local_pca_zt, src/utils/utils.py:900-975 (uncond: PullBackDDPM.local_pca_xt, src/models/ddpm/diffusion.py:379-436).
+        N = num_pca_samples feature rows h_i = get_h(sample + g_i / ||g_i||) of ONE sample (dpb_local_pca_sample: perturbation and forward pass per
+        chunk on the device, no host round trip), then torch.pca_lowrank(H [N, D], q=pca_rank, center=True, niter=2) -- dpb_pca_lowrank, with R drawn
+        by torch.randn(min(N, D), q) on pca_device where pca_lowrank draws it.  Returns (u [D, q], s [q], vT [q, N_in]) on sample.device in
+        sample.dtype (the reference's local variant; the global one returns on pca_device).  vT holds the x-space directions of the columns of u,
+        vT_i = -J^T u_i / ||J^T u_i||: the reference differentiates ||h + perturb_h u_i - get_h(x)|| at x, whose gradient for a unit u_i is
+        -u_i^T J (perturb_h drops out) -- inv_jac_zt's 2-D path, one primal and the adjoints in chunks of max_rank.
+        (Row i belongs to COLUMN i of u, as in PullBackDDPM.inv_jac_xt's rearrange, diffusion.py:360.  utils.local_pca_zt itself adds
+        u.view(*original_h.shape), utils.py:960 -- the row-major view of u [D, q] as [q, D] -- so for q > 1 its rows are directions of mixtures of
+        all columns; at q = 1 the two agree.  The mixture is not reproduced: it depends on the arbitrary signs of the columns.)
+        Extensions: `noise` [N, C, H, W], the unnormalised Gaussian draws g_i (nothing is drawn from any generator before R then); otherwise the
+        noise is generated in the kernel from (seed, i) -- Philox4x32-10, include/dpb.h -- with seed=None replaced by ONE torch.randint draw from
+        the global CPU generator, so torch.manual_seed governs the call.  The reference's own noise depends on its chunking and on the device
+        generator; here sample i's noise never depends on the chunking: memory_bound is validated and otherwise without effect (the chunks are the
+        engine's max_batch, which sized the workspace), it never changes the results.  uncond: local_pca_zt(x=..., t=..., op, block_idx).
+        Deviations: pca_rank <= 128 (RANK_LIMIT, the default: the reference's defaults of 2000 / 512 exceed the re-orthonormalisation's limit), also
+        <= N - 1 and <= D; num_pca_samples % memory_bound != 0 raises ValueError (the DDPM reference asserts, the SD one fails at its view);
+        sample.shape[0] != 1 raises ValueError; return_x_direction=False returns vT=None (the reference crashes on None.detach()).
+        16-bit engines: the unit-norm perturbation is about 1 / sqrt(N_in) per element -- 0.0078 at the SD latent's 16 384 elements, which is
+        the bf16 spacing at 1.0 -- so in a bf16 engine most of the perturbation is lost when x is rounded to the engine's type and the spectrum
+        is that of the rounding pattern as much as of J; fp16 keeps three more bits.  The method runs there (finite, descending s); use an fp32
+        engine when the basis matters."""
+        sample = x if sample is None else sample
+        timestep = t if timestep is None else timestep
+        key = self._tap(op, block_idx)
+        eng = self.engine
+        if sample.shape[0] != 1:
+            raise ValueError("local_pca expects a single sample (batch 1): every row perturbs the same input")
+        n, d, q, mb = int(num_pca_samples), eng.tap_numel(key), int(pca_rank), int(memory_bound)
+        if mb < 1:
+            raise ValueError(f"memory_bound={memory_bound} < 1")
+        if n < 1 or n % mb != 0:
+            raise ValueError(f"num_pca_samples={n} must be a positive multiple of memory_bound={mb}")   # diffusion.py:391
+        if eng.lib.dpb_pca_scratch_bytes(q, n, d) == 0:
+            raise ValueError(f"pca_rank={q} is not supported for {n} samples of {d} features: 1 <= pca_rank <= min({RANK_LIMIT}, N - 1, D)")
+        if noise is not None:
+            if tuple(noise.shape) != (n, *sample.shape[1:]):
+                raise ValueError(f"noise has shape {tuple(noise.shape)}, expected {(n, *sample.shape[1:])} (num_pca_samples unnormalised Gaussian draws)")
+        elif seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())      # the global CPU generator: torch.manual_seed governs
+        time_s = time.time()
+        H = eng.local_pca_sample(sample, _t_float(timestep), encoder_hidden_states, key, n, noise=noise, seed=0 if seed is None else int(seed))
+        if self.verbose:
+            torch.cuda.synchronize(self.device)
+            print("h sampling t ==", time.time() - time_s)
+        time_s = time.time()
+        R = torch.randn(min(n, d), q, dtype=torch.float32, device=pca_device)    # torch._lowrank.get_approximate_basis: randn(A.shape[-1], q)
+        ud, sd = pca_lowrank(H, R, q, niter=2)                                    # utils.py:939
+        del H
+        s = sd.to(device=sample.device, dtype=sample.dtype)
+        u = ud.T.to(device=sample.device, dtype=sample.dtype)
+        if not (torch.isfinite(s).all() and (s > 0).all()):
+            raise L.DpbError(f"local_pca: the centred features have rank < pca_rank={q} (singular values {s.tolist()})")
+        if self.verbose:
+            print("torch.pca_lowrank t ==", time.time() - time_s)
+            print(f"eigenvalue spectrum : {s}")
+        vT = None
+        if return_x_direction:
+            time_s = time.time()
+            vT = self.inv_jac_zt(sample, timestep, encoder_hidden_states, op=op, block_idx=block_idx, u=ud.T, perturb_h=perturb_h)
+            vT = vT.to(device=sample.device)
+            if self.verbose:
+                print("torch.jac t ==", time.time() - time_s)
+        return u, s, vT
+
+    def local_pca_xt(self, x=None, t=None, op=None, block_idx=None, memory_bound=5, num_pca_samples=50000, pca_rank=RANK_LIMIT, pca_device="cpu",
+                     return_x_direction=True, perturb_h=1e-1, noise=None, seed=None):
+        """Reference: PullBackDDPM.local_pca_xt, src/models/ddpm/diffusion.py:379-436: local_pca_zt without conditioning (see there)."""
+        return self.local_pca_zt(x, t, None, op=op, block_idx=block_idx, memory_bound=memory_bound, num_pca_samples=num_pca_samples, pca_rank=pca_rank,
+                                 pca_device=pca_device, return_x_direction=return_x_direction, perturb_h=perturb_h, noise=noise, seed=seed)
+
+    def global_pca_xt(self, x=None, t=None, op=None, block_idx=None, memory_bound=5, pca_rank=100, pca_device="cpu"):
+        """Reference: PullBackDDPM.global_pca_xt, src/models/ddpm/diffusion.py:438-482: global_pca_zt without conditioning (its limits; the reference's
+        default rank of 512 exceeds them, so the default is global_pca_zt's 100)."""
+        return self.global_pca_zt(x, t, None, op=op, block_idx=block_idx, memory_bound=memory_bound, pca_rank=pca_rank, pca_device=pca_device)
+
+    def inv_jac_xt(self, x=None, t=None, op=None, block_idx=None, u=None, perturb_h=1e-1):
+        """Reference: PullBackDDPM.inv_jac_xt, src/models/ddpm/diffusion.py:347-377: inv_jac_zt without conditioning; u [D] -> vT [1, N_in], u [D, k]
+        -> vT [k, N_in] (the vendored class takes 2-D u)."""
+        return self.inv_jac_zt(x, t, None, op=op, block_idx=block_idx, u=u, perturb_h=perturb_h)
+
 
 def bind(unet, kind: str, cfg, dtype=torch.float32, device="cuda:0", **kw) -> PullbackUNet:
     """Attach the HIP-backed methods onto an existing U-Net module, like the reference's
@@ -393,8 +477,12 @@ def bind(unet, kind: str, cfg, dtype=torch.float32, device="cuda:0", **kw) -> Pu
         unet.local_decoder_pullback_zt = types.MethodType(lambda self, *a, **k: self._dpb.local_decoder_pullback_zt(*a, **k), unet)
         unet.global_pca_zt = types.MethodType(lambda self, *a, **k: self._dpb.global_pca_zt(*a, **k), unet)
         unet.inv_jac_zt = types.MethodType(lambda self, *a, **k: self._dpb.inv_jac_zt(*a, **k), unet)
+        unet.local_pca_zt = types.MethodType(lambda self, *a, **k: self._dpb.local_pca_zt(*a, **k), unet)
     else:
         unet.local_encoder_pullback_xt = types.MethodType(lambda self, *a, **k: self._dpb.local_encoder_pullback_xt(*a, **k), unet)
         unet.local_decoder_pullback_xt = types.MethodType(lambda self, *a, **k: self._dpb.local_decoder_pullback_xt(*a, **k), unet)
         unet.local_x0_decoder_pullback_xt = types.MethodType(lambda self, *a, **k: self._dpb.local_x0_decoder_pullback_xt(*a, **k), unet)
+        unet.local_pca_xt = types.MethodType(lambda self, *a, **k: self._dpb.local_pca_xt(*a, **k), unet)
+        unet.global_pca_xt = types.MethodType(lambda self, *a, **k: self._dpb.global_pca_xt(*a, **k), unet)
+        unet.inv_jac_xt = types.MethodType(lambda self, *a, **k: self._dpb.inv_jac_xt(*a, **k), unet)
     return impl

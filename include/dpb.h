@@ -145,6 +145,42 @@ size_t dpb_pca_scratch_bytes(int q, int64_t N, int64_t D);   /* 0 when invalid *
 int dpb_pca_lowrank(const float* H, int64_t N, int64_t D, const float* R, int q, int niter, float* u, float* s, void* scratch,
                     size_t scratch_bytes, void* hip_stream);
 
+/* ---- local h-space PCA: the perturbed batch and the sampling loop (additive to ABI version 1) ---------------------------------------
+ * out[b][j] = x[j] + norm * g_b[j] / ||g_b||_2 for b < B, j < n, all fp32: B unit-norm (norm = 1) perturbations of ONE input, the
+ * reference's x + normalize_wrt_batch(torch.randn_like(x)) (src/utils/utils.py:918-925; src/models/ddpm/diffusion.py:399-401).  Engine-independent.
+ * g_b is noise[b] when `noise` is given ([B][n], unnormalised Gaussian draws), else it is generated in the kernel, a function of
+ * (seed, first + b) only -- not of B, of the chunking or of the launch:
+ *   Philox4x32-10 (Salmon, Moraes, Dror, Shaw, SC'11; multipliers D2511F53 / CD9E8D57, Weyl constants 9E3779B9 / BB67AE85), key =
+ *   (seed & 0xffffffff, seed >> 32), counter = (i & 0xffffffff, i >> 32, c & 0xffffffff, c >> 32) with i = first + b the 64-bit sample
+ *   index and c = j / 4 the index of the group of four elements; the output words (w0, w1, w2, w3) give the elements 4c .. 4c+3:
+ *     u(w) = ((w >> 9) + 0.5) * 2^-23      an odd multiple of 2^-24 in (0, 1): 24 significant bits, so exact in fp32, never 0, never 1
+ *                                          (the 24-bit variant ((w >> 8) + 0.5) * 2^-24 needs 25 bits and would round)
+ *     g[4c]   = sqrt(-2 ln u(w0)) cos(2 pi u(w1))      g[4c+1] = sqrt(-2 ln u(w0)) sin(2 pi u(w1))
+ *     g[4c+2] = sqrt(-2 ln u(w2)) cos(2 pi u(w3))      g[4c+3] = sqrt(-2 ln u(w2)) sin(2 pi u(w3))        (fp32 arithmetic)
+ * ||g_b||^2 is summed in fp64 in a fixed order (partial sums of slices of 4096 elements, then the slices in index order; no atomics), the
+ * factor norm / ||g_b|| is rounded to fp32 once and applied by one fused multiply-add per element: bitwise reproducible, and sample i's row
+ * does not depend on B or `first`.  noise_out (optional) receives the unnormalised g.  1 <= B <= 65535, n >= 1 (any n; 16-byte accesses
+ * when n % 4 == 0 and the pointers are 16-byte aligned), 0 <= first; scratch: 8-byte aligned device memory of >= dpb_perturb_scratch_bytes(B, n)
+ * bytes.  out must not alias x or noise.  No host synchronisation.  Errors via dpb_last_error. */
+size_t dpb_perturb_scratch_bytes(int B, int64_t n);   /* 0 when invalid */
+int dpb_perturb_unit(const float* x, const float* noise /*[B][n] or NULL*/, uint64_t seed, int64_t first, int B, int64_t n,
+                     float norm, float* out /*[B][n]*/, float* noise_out /*[B][n] or NULL: the unnormalised g*/,
+                     void* scratch, size_t scratch_bytes, void* hip_stream);
+/* The sampling loop of local_pca_zt / local_pca_xt (src/utils/utils.py:916-933; src/models/ddpm/diffusion.py:396-409): rows first .. first + count - 1
+ * of the feature matrix, H[i] = get_h(x + g_i / ||g_i||) at the tap upto_buf (fp32 NCHW-flattened, D = channels * rows(upto_buf)).  `H` points at
+ * the row of sample `first`, `noise` (or NULL: generated from (seed, sample index) as above) at its noise row.  x [1][N_in] is ONE input, ctx
+ * [1][L][Dc] ONE conditioning (or NULL for a network without), both repeated on the device.  The samples go through in chunks of the engine's
+ * max_batch: dpb_perturb_unit into scratch, then the dpb_forward pass with the features written straight into their rows of H.  The engine
+ * workspace does not grow: scratch is 256-byte aligned device memory of >= dpb_local_pca_scratch_bytes(e) bytes (the perturbed chunk, max_batch
+ * copies of ctx, the norm partials).  Host synchronisation: none per chunk; the one upload of the timestep embedding that every dpb_forward makes
+ * happens once per call (the chunks share t).  State rules and error paths of dpb_forward: no primal state afterwards, errors via
+ * dpb_last_error. */
+size_t dpb_local_pca_scratch_bytes(const dpb_engine* e);
+int dpb_local_pca_sample(dpb_engine* e, const float* x /*[1][N_in]*/, float t, const float* ctx /*[1][L][Dc] or NULL*/,
+                         int upto_buf, int channels, const float* noise /*[count][N_in] or NULL*/, uint64_t seed,
+                         int64_t first, int64_t count, float* H /*[count][D] rows first.. of the caller's matrix*/,
+                         void* scratch, size_t scratch_bytes);
+
 /* n_iters full power iterations with no host synchronisation: V <- orth(J^T J V), U = J V_prev, for all B samples
  * of the last dpb_primal together (independent bases, one shared weight stream; B*k <= max_tangents).
  * V [B][k][N_in] in/out, U [B][k][N_h] out, s [B][k] out, conv [B][2] out (of the last iteration).
