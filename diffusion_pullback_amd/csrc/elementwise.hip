@@ -265,6 +265,119 @@ int launch_nhwc_to_nchw(int dtype, const void* src, float* dst, int n, int C, in
   return 0;
 }
 
+// h-space shift of a tap (dpb_forward_shift): P(src)[b] = P(src)[bcast ? 0 : b] + scale[b] * u[dir[b]] for the rows b0 .. b0 + nb - 1 of a batch.
+// h: the tap, NHWC [.][HW][C] in T (C - Cv pad channels, copied); u: fp32 [nu][Cv][HW], the NCHW-flattened layout of every tap at the boundary.
+// One block owns a tile of 32 pixels x 64 channels for ALL rows: every element of h is read and written by one thread only, so the in-place
+// broadcast of row 0 (read once into registers before any row is written) has no hazard.  u goes through LDS (read along pixels, written along
+// channels); the sum is formed in fp32 and rounded once by the store.  VEC: elements per access on the NHWC side (a 16-byte chunk, or 1).
+constexpr int SHIFT_TP = 32, SHIFT_TC = 64;
+template <typename T, int VEC>
+__global__ __launch_bounds__(256) void shift_tap_kernel(T* h, const float* u, ShiftRows rows, int b0, int nb, int bcast, int C, int Cv, long HW) {
+  constexpr int CPP = SHIFT_TC / VEC;                    // accesses per pixel of the tile
+  constexpr int ITER = SHIFT_TP * CPP / 256;
+  __shared__ float tile[SHIFT_TC][SHIFT_TP + 1];
+  const long p0 = (long)blockIdx.x * SHIFT_TP;
+  const int c0 = blockIdx.y * SHIFT_TC;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+  const long img = HW * (long)C;
+  float src[ITER][VEC];
+  auto ld = [&](const T* p, float* o) {
+    if constexpr (VEC == 1) o[0] = TT<T>::ld(p); else Vec<T>::load(p, o);
+  };
+  auto st = [&](T* p, const float* o) {
+    if constexpr (VEC == 1) TT<T>::st(p, o[0]); else Vec<T>::store(p, o);
+  };
+  if (bcast) {
+#pragma unroll
+    for (int it = 0; it < ITER; ++it) {
+      const int q = it * 256 + threadIdx.x, pl = q / CPP, c = c0 + (q % CPP) * VEC;
+      if (p0 + pl < HW && c < C) ld(h + (p0 + pl) * C + c, src[it]);
+    }
+  }
+  for (int r = 0; r < nb; ++r) {
+    const int b = b0 + r, dir = rows.dir[r];
+    const float sc = rows.scale[r];
+    if (dir < 0 && !(bcast && b > 0)) continue;          // unshifted row that is its own source: nothing to write (uniform over the block)
+    if (dir >= 0) {
+      __syncthreads();                                   // the tile of the row before has been read
+      const float* ub = u + (long)dir * Cv * HW;
+      for (int k = ty; k < SHIFT_TC; k += 8) {
+        const int c = c0 + k;
+        tile[k][tx] = (c < Cv && p0 + tx < HW) ? ub[(long)c * HW + p0 + tx] : 0.f;
+      }
+      __syncthreads();
+    }
+    T* hb = h + (long)b * img;
+#pragma unroll
+    for (int it = 0; it < ITER; ++it) {
+      const int q = it * 256 + threadIdx.x, pl = q / CPP, cl = (q % CPP) * VEC, c = c0 + cl;
+      if (p0 + pl >= HW || c >= C) continue;
+      T* p = hb + (p0 + pl) * C + c;
+      float v[VEC];
+      if (bcast) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) v[e] = src[it][e];
+      } else {
+        ld(p, v);
+      }
+      if (dir >= 0) {
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) v[e] += sc * tile[cl + e][pl];
+      }
+      st(p, v);
+    }
+  }
+}
+
+template <typename T>
+static int shift_tap_t(void* h, const float* u, const int* dir, const float* scale, int batch, int bcast, int C, int Cv, long HW, hipStream_t st) {
+  const dim3 grid((unsigned)((HW + SHIFT_TP - 1) / SHIFT_TP), (unsigned)((C + SHIFT_TC - 1) / SHIFT_TC));
+  // rows travel as kernel arguments, SHIFT_MAX_ROWS per launch; the chunk holding row 0 -- the source of a broadcast -- goes last
+  for (int b0 = (batch - 1) / SHIFT_MAX_ROWS * SHIFT_MAX_ROWS; b0 >= 0; b0 -= SHIFT_MAX_ROWS) {
+    ShiftRows rows;
+    const int nb = std::min(SHIFT_MAX_ROWS, batch - b0);
+    for (int r = 0; r < nb; ++r) { rows.dir[r] = dir[b0 + r]; rows.scale[r] = scale[b0 + r]; }
+    if (C % TT<T>::CH == 0) hipLaunchKernelGGL((shift_tap_kernel<T, TT<T>::CH>), grid, dim3(256), 0, st, (T*)h, u, rows, b0, nb, bcast, C, Cv, HW);
+    else hipLaunchKernelGGL((shift_tap_kernel<T, 1>), grid, dim3(256), 0, st, (T*)h, u, rows, b0, nb, bcast, C, Cv, HW);
+    DPB_CHECK(hipGetLastError());
+  }
+  return 0;
+}
+int shift_tap_launches(int batch) { return (batch + SHIFT_MAX_ROWS - 1) / SHIFT_MAX_ROWS; }
+int launch_shift_tap(int dtype, void* h, const float* u, const int* dir, const float* scale, int batch, int bcast, int C, int Cv, long HW,
+                     hipStream_t st) {
+  if (batch < 1 || C < 1 || Cv < 1 || Cv > C || HW < 1) { set_error("shift_tap: empty or inconsistent problem"); return -1; }
+  return DPB_DISPATCH_T(dtype, T, shift_tap_t<T>(h, u, dir, scale, batch, bcast, C, Cv, HW, st));
+}
+
+// sample 0 of every buffer of a descriptor table -> samples 1 .. batch-1, in place, 16-byte copies (blockIdx.y: the buffer)
+__global__ __launch_bounds__(256) void replicate_rows_kernel(ReplTable t, int batch) {
+  uint4* p = (uint4*)t.p[blockIdx.y];
+  const long n = t.chunks[blockIdx.y];
+  for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+    const uint4 v = p[i];
+    for (int b = 1; b < batch; ++b) p[(long)b * n + i] = v;
+  }
+}
+int replicate_rows_launches(int nbufs) { return (nbufs + REPL_MAX_BUFS - 1) / REPL_MAX_BUFS; }
+int launch_replicate_rows(void* const* bufs, const size_t* sample_bytes, int nbufs, int batch, hipStream_t st) {
+  if (batch < 2) return 0;
+  for (int i0 = 0; i0 < nbufs; i0 += REPL_MAX_BUFS) {
+    ReplTable t;
+    const int n = std::min(REPL_MAX_BUFS, nbufs - i0);
+    long most = 1;
+    for (int i = 0; i < n; ++i) {
+      if (sample_bytes[i0 + i] % 16 || (uintptr_t)bufs[i0 + i] % 16) { set_error("replicate_rows: buffer %d is not a whole number of aligned 16-byte chunks per sample", i0 + i); return -1; }
+      t.p[i] = bufs[i0 + i];
+      t.chunks[i] = (long)(sample_bytes[i0 + i] / 16);
+      most = std::max(most, t.chunks[i]);
+    }
+    hipLaunchKernelGGL(replicate_rows_kernel, dim3(std::min(grid_for(most), 2048u), n), dim3(256), 0, st, t, batch);
+    DPB_CHECK(hipGetLastError());
+  }
+  return 0;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void pool2x2_kernel(const T* in, T* out, int n, int H, int W, int C, int accumulate) {
   constexpr int CH = TT<T>::CH;

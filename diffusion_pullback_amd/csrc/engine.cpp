@@ -97,6 +97,10 @@ struct dpb_engine {
   int primal_last = -1;             // last op whose primal state (with the tangent / adjoint stash) is resident; -1: none
   int fwd_seed = -1;                // dpb_forward_from: buffer overwritten by fwd_h after its producer has run
   const float* fwd_h = nullptr;
+  // dpb_forward_shift: after the producer of fwd_seed has run, P(fwd_seed)[b] <- P(fwd_seed)[b or 0] + fwd_scale[b] * fwd_u[fwd_dir[b]] (no overwrite by
+  // fwd_h).  fwd_xb: samples of x / ctx, i.e. the batch of ops 0 .. producer[fwd_seed]; 1 < batch: the shared prefix, the rest of the tape runs on copies
+  const float* fwd_u = nullptr; const int32_t* fwd_dir = nullptr; const float* fwd_scale = nullptr;
+  int fwd_xb = 0;
   struct { bool on = false; GemmArgs a; } pend;   // a split-K product whose reduction is deferred to the normalisation op that consumes it
   bool fwd_only = false;            // dpb_forward: primal pass that keeps no tangent / adjoint stash (DDIM loop)
   bool temb_keep = false;           // dpb_local_pca_sample, chunks after the first: P(temb_buf) already holds this t's embedding (no upload, no sync)
@@ -1085,6 +1089,37 @@ int dpb_engine_set_workspace(dpb_engine* e, void* ws, size_t bytes) {
   return 0;
 }
 
+// dpb_forward_shift, right after op producer[fwd_seed]: the `batch` shifted copies of the tap, then (shared prefix, xb == 1 < batch) sample 0 of every
+// buffer the rest of the pass still reads broadcast to the other samples.  That set comes from the tape: the per-sample inputs (in0 / in1 / in2 / res)
+// of the ops in (producer[fwd_seed], last] that were written at or before producer[fwd_seed] or are network inputs (ctx) -- the skips, the net-wide K/V
+// projection of the context.  SHARED buffers (time-embedding path, row biases) have one copy for any batch; the tap itself is written by shift_tap.
+// Nothing else crosses the seam: a primal normalisation op computes its statistics from its own input, it takes none from that input's producer.
+static int shift_seed(dpb_engine* e, int batch, int xb, int last) {
+  const int src = e->fwd_seed, ps = e->producer[src];
+  const Buf& bs = e->bufs[src];
+  e->n_launch += shift_tap_launches(batch);
+  if (int r = launch_shift_tap(e->dtype, e->P(src), e->fwd_u, e->fwd_dir, e->fwd_scale, batch, xb < batch, bs.C, bs.Cv, bs.rows, e->stream)) return r;
+  if (xb == batch) return 0;
+  std::vector<char> seen(e->bufs.size(), 0);
+  std::vector<void*> ptr;
+  std::vector<size_t> bytes;
+  auto need = [&](int b) {
+    if (b < 0 || b == src || seen[b] || e->bufs[b].kind == DPB_BUF_SHARED || e->producer[b] > ps) return;
+    seen[b] = 1;
+    ptr.push_back(e->P(b));
+    bytes.push_back((size_t)e->bufs[b].rows * e->bufs[b].C * e->es);
+  };
+  for (int i = ps + 1; i <= last; ++i) {
+    const dpb_op_desc& d = e->ops[i].d;
+    need(d.in0);
+    if (d.kind == DPB_OP_ATTENTION || d.kind == DPB_OP_CONCAT) need(d.in1);
+    if (d.kind == DPB_OP_ATTENTION) need(d.in2);
+    if (d.kind == DPB_OP_CONV) need(d.res);
+  }
+  e->n_launch += replicate_rows_launches((int)ptr.size());
+  return launch_replicate_rows(ptr.data(), bytes.data(), (int)ptr.size(), batch, e->stream);
+}
+
 static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const float* ctx, int upto_buf) {
   if (!e || !x) return fail("null argument");
   if (!e->ws) return fail("workspace not set (dpb_engine_set_workspace)");
@@ -1092,14 +1127,15 @@ static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const 
   if (upto_buf < 0 || upto_buf >= (int)e->bufs.size() || e->producer[upto_buf] < 0) return fail("invalid upto buffer %d", upto_buf);
   e->n_launch = 0; e->flops = 0; e->gbytes = 0;
   const Buf& bx = e->bufs[e->x_buf];
+  const int xb = e->fwd_u ? e->fwd_xb : batch;     // samples of x / ctx (dpb_forward_shift with a shared prefix: 1)
   e->n_launch++;
-  if (int r = launch_nchw_to_nhwc(e->dtype, x, e->P(e->x_buf), batch, e->x_channels, bx.rows, bx.C, e->stream)) return r;
+  if (int r = launch_nchw_to_nhwc(e->dtype, x, e->P(e->x_buf), xb, e->x_channels, bx.rows, bx.C, e->stream)) return r;
   if (e->ctx_buf >= 0) {
     if (!ctx) return fail("this network needs ctx (encoder_hidden_states)");
     const Buf& bc = e->bufs[e->ctx_buf];
     // ctx is already [batch][rows][Cv] channel-last (Cv = un-padded width): cast (and zero-pad to C) via the nchw kernel with HW=1
     e->n_launch++;
-    if (int r = launch_nchw_to_nhwc(e->dtype, ctx, e->P(e->ctx_buf), batch * bc.rows, bc.Cv, 1, bc.C, e->stream)) return r;
+    if (int r = launch_nchw_to_nhwc(e->dtype, ctx, e->P(e->ctx_buf), xb * bc.rows, bc.Cv, 1, bc.C, e->stream)) return r;
   }
   if (e->temb_buf >= 0 && !e->temb_keep) {
     // sinusoidal timestep embedding, computed on the host in fp32 exactly as the reference frameworks do
@@ -1129,8 +1165,10 @@ static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const 
   std::fill(e->skip.begin(), e->skip.end(), 0);
   for (int i = 0; i <= last; ++i) {
     if (!e->skip[i])                               // (forward only: a GEGLU applied by the epilogue of the FF-in product)
-      if (int r = run_op(e, e->ops[i], MODE_PRIMAL, batch)) return r;
-    if (i == seed_op) {                            // dpb_forward_from: the caller's activation replaces the one just computed
+      if (int r = run_op(e, e->ops[i], MODE_PRIMAL, i <= seed_op ? xb : batch)) return r;
+    if (i == seed_op && e->fwd_u) {                // dpb_forward_shift: the tap just computed, shifted per row (of sample 0 for every row when xb == 1)
+      if (int r = shift_seed(e, batch, xb, last)) return r;
+    } else if (i == seed_op) {                     // dpb_forward_from: the caller's activation replaces the one just computed
       const Buf& bs = e->bufs[e->fwd_seed];
       e->n_launch++;
       if (int r = launch_nchw_to_nhwc(e->dtype, e->fwd_h, e->P(e->fwd_seed), batch, bs.Cv, bs.rows, bs.C, e->stream)) return r;
@@ -1170,6 +1208,31 @@ int dpb_forward_from(dpb_engine* e, const float* x, int batch, float t, const fl
   e->fwd_seed = src_buf; e->fwd_h = h;
   const int r = dpb_forward(e, x, batch, t, ctx, dst_buf, channels, out);
   e->fwd_seed = -1; e->fwd_h = nullptr;
+  return r;
+}
+
+int dpb_forward_shift(dpb_engine* e, const float* x, int xbatch, int batch, float t, const float* ctx, int src_buf, const float* u, int nu,
+                      const int32_t* dir, const float* scale, int dst_buf, int channels, float* out) {
+  if (!e || !x || !out || !dir || !scale) return fail("null argument");
+  e->cur_batch = 0;                                // as dpb_forward: whatever happens below, the primal state is gone
+  if (batch < 1 || batch > e->maxB) return fail("batch=%d outside [1,%d]", batch, e->maxB);
+  if (xbatch != 1 && xbatch != batch) return fail("xbatch=%d must be 1 (one sample shared by the batch) or batch=%d", xbatch, batch);
+  if (nu < 1) return fail("nu=%d: at least one direction is needed", nu);
+  if (!u) return fail("null argument");
+  for (int b = 0; b < batch; ++b)
+    if (dir[b] < -1 || dir[b] >= nu) return fail("dir[%d]=%d outside [-1,%d) (-1: no shift)", b, dir[b], nu);
+  const int nb = (int)e->bufs.size();
+  if (src_buf < 0 || src_buf >= nb || e->producer[src_buf] < 0 || e->bufs[src_buf].kind != DPB_BUF_ACT || e->bufs[src_buf].is_const)
+    return fail("invalid source buffer %d (an x-dependent activation produced by an op)", src_buf);
+  if (dst_buf < 0 || dst_buf >= nb || e->producer[dst_buf] < 0) return fail("invalid dst buffer %d", dst_buf);
+  const int prev = e->src;
+  if (int r = set_seed(e, src_buf)) return r;
+  const bool down = dst_buf != src_buf && e->bact[dst_buf];
+  set_seed(e, prev);
+  if (!down) return fail("dst buffer %d is not downstream of source buffer %d", dst_buf, src_buf);
+  e->fwd_seed = src_buf; e->fwd_u = u; e->fwd_dir = dir; e->fwd_scale = scale; e->fwd_xb = xbatch;
+  const int r = dpb_forward(e, x, batch, t, ctx, dst_buf, channels, out);
+  e->fwd_seed = -1; e->fwd_u = nullptr; e->fwd_dir = nullptr; e->fwd_scale = nullptr; e->fwd_xb = 0;
   return r;
 }
 

@@ -189,6 +189,21 @@ int launch_zero_cols(int dtype, void* dst, int ldd, int cd0, long rows, int ncol
 // fp32 NCHW [n][C][HW]  <->  T NHWC [n][HW][Cpad]
 int launch_nchw_to_nhwc(int dtype, const float* src, void* dst, int n, int C, int HW, int Cpad, hipStream_t st);
 int launch_nhwc_to_nchw(int dtype, const void* src, float* dst, int n, int C, int HW, int Cpad, hipStream_t st);
+// h-space shift of a tap (dpb_forward_shift): h[b] = h[bcast ? 0 : b] + scale[b] * u[dir[b]] for b < batch, in place.  h: NHWC [batch][HW][C] in
+// the engine dtype (Cv valid channels, the pad channels are copied); u: DEVICE fp32 [nu][Cv][HW] (NCHW-flattened); dir / scale: HOST arrays of
+// `batch` entries (dir[b] in [-1, nu), checked by the caller; -1 = no shift), passed as kernel arguments, SHIFT_MAX_ROWS rows per launch.
+// The sum is formed in fp32 and rounded once; 64-bit offsets; 16-byte accesses on the NHWC side when C is a multiple of the chunk.
+constexpr int SHIFT_MAX_ROWS = 64;
+struct ShiftRows { int dir[SHIFT_MAX_ROWS]; float scale[SHIFT_MAX_ROWS]; };
+int launch_shift_tap(int dtype, void* h, const float* u, const int* dir, const float* scale, int batch, int bcast, int C, int Cv, long HW,
+                     hipStream_t st);
+int shift_tap_launches(int batch);           // kernels launch_shift_tap enqueues
+// sample 0 of each of `nbufs` buffers (sample_bytes[i] bytes per sample, a multiple of 16; 16-byte aligned) copied to samples 1 .. batch-1 in
+// place: one launch per REPL_MAX_BUFS buffers, the descriptor table in the kernel arguments, 16-byte copies
+constexpr int REPL_MAX_BUFS = 32;
+struct ReplTable { void* p[REPL_MAX_BUFS]; long chunks[REPL_MAX_BUFS]; };
+int launch_replicate_rows(void* const* bufs, const size_t* sample_bytes, int nbufs, int batch, hipStream_t st);
+int replicate_rows_launches(int nbufs);      // kernels launch_replicate_rows enqueues (for batch >= 2)
 // 2x2 sum pooling of a cotangent (adjoint of nearest x2 upsampling): in [n][2H*2W][C] -> out [n][H*W][C]
 int launch_pool2x2_sum(int dtype, const void* in, void* out, int n, int H, int W, int C, int accumulate, hipStream_t st);
 

@@ -209,6 +209,29 @@ class Engine:
             self.batch = 0
         return out
 
+    def forward_shift(self, x: torch.Tensor, t: float, ctx: Optional[torch.Tensor], src, u: torch.Tensor, dirs, scales, dst="eps") -> torch.Tensor:
+        """dpb_forward_shift: row b of the result is `dst` of the net with the activation at tap `src` replaced by h(x_b) + scales[b] * u[dirs[b]]
+        (dirs[b] = -1: unshifted).  u [nu, N_src] fp32 directions (NCHW-flattened; a device tensor is used where it lies), dirs / scales: host
+        sequences of B entries.  x [B, ...] (ctx [B or 1, L, D]): one forward pass at B; x [1, ...] with B > 1: the shared prefix -- the part of
+        the net up to the tap runs once, only the part after it at B.  Like forward(), keeps no primal state."""
+        sbuf, dbuf = self.tape.taps[src], self.tape.taps[dst]
+        c, hh, ww = self.tape.tap_shape[dbuf]
+        dirs, scales = [int(d) for d in dirs], [float(s) for s in scales]
+        b = len(dirs)
+        if len(scales) != b:
+            raise L.DpbError(f"dirs has {b} entries, scales {len(scales)}: one of each per output row")
+        with torch.cuda.device(self.device):
+            self._set_stream()
+            x, xb, ctx = self._inputs(x, ctx)
+            if u.numel() % self.tap_numel(src):
+                raise L.DpbError(f"u has {u.numel()} elements, not a whole number of directions of {self.tap_numel(src)} (tap {src})")
+            u = _f32(u, self.device).reshape(-1, self.tap_numel(src))
+            out = torch.empty(max(b, 1), c, hh, ww, dtype=torch.float32, device=self.device)
+            self.batch = 0
+            L.check(self.lib.dpb_forward_shift(self.h, _ptr(x), xb, b, float(t), _ptr(ctx), sbuf, _ptr(u), u.shape[0], (C.c_int32 * max(b, 1))(*dirs),
+                                               (C.c_float * max(b, 1))(*scales), dbuf, c, _ptr(out)))
+        return out
+
     def jvp_between(self, src, dst, V: torch.Tensor) -> torch.Tensor:
         """V [nt, N_src] (NCHW-flattened tangents of the tap `src`) -> U [nt, N_dst]; the primal must reach `dst`"""
         with torch.cuda.device(self.device):

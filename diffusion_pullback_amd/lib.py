@@ -84,6 +84,8 @@ SYMBOLS = {
     "dpb_pullback_scratch_bytes": (C.c_size_t, [_P, _I, _I]),
     "dpb_pullback_iterate_between": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _I, _P, C.c_size_t]),
     "dpb_forward_from": (_I, [_P, _P, _I, _F, _P, _I, _P, _I, _I, _P]),
+    # the h-space shifted forward (forward_dh): per-row shift of a tap, optional shared prefix
+    "dpb_forward_shift": (_I, [_P, _P, _I, _I, _F, _P, _I, _P, _I, _P, _P, _I, _I, _P]),
     # randomized low-rank PCA of a feature matrix (global_pca_zt)
     "dpb_pca_scratch_bytes": (C.c_size_t, [_I, _L, _L]),
     "dpb_pca_lowrank": (_I, [_P, _L, _L, _P, _I, _I, _P, _P, _P, C.c_size_t, _P]),

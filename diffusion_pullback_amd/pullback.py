@@ -91,8 +91,75 @@ class PullbackUNet:
         return h.to(sample.dtype)
 
     def __call__(self, sample, timestep, encoder_hidden_states=None, **kwargs):
+        """The U-Net itself.  uncond: PullBackDDPM.forward(x, t, u=None, op=None, block_idx=None) (diffusion.py:145-200) -- with u, eps of
+        the net with u added to the activation at (op, block_idx); SD: unet(sample, timestep, encoder_hidden_states).sample, whose shifted
+        form is forward_dh (a u= / uk= here raises instead of being dropped).  Without u / op / block_idx: the plain forward pass."""
+        shift = {k: kwargs[k] for k in ("u", "uk", "op", "block_idx") if kwargs.get(k) is not None}
+        if shift:
+            if self.kind == "sd":
+                raise TypeError("the SD U-Net call takes no h-space shift (" + ", ".join(shift) + " given): use "
+                                "forward_dh(sample, timestep, encoder_hidden_states, op=, block_idx=, uk=)")
+            if "uk" in shift:
+                raise TypeError("the DDPM forward takes the shift as u= (uk= is forward_dh's name for it)")
+            return self._forward_shifted(sample, timestep, None, shift.get("u"), shift.get("op"), shift.get("block_idx"))
         eps = self.engine.forward(sample, _t_float(timestep), encoder_hidden_states, "eps").to(sample.dtype)
         return UNetOutput(eps) if self.kind == "sd" else eps
+
+    # ------------------------------------------------------------------ h-space shift: the forward pass with h + u at the tap
+    def _forward_shifted(self, sample, timestep, ctx, u, op, block_idx):
+        """eps with u.view(-1, C, H, W) added at the tap (op, block_idx): one row is broadcast over the batch, B rows give one per sample"""
+        if u is None or op is None or block_idx is None:
+            raise ValueError("an h-space shift needs all of u, op and block_idx")
+        key = self._decoder_tap(op, block_idx)
+        b, d = sample.shape[0], self.engine.tap_numel(key)
+        if u.numel() == 0 or u.numel() % d:
+            raise ValueError(f"u has {u.numel()} elements, the tap ({op}, {block_idx}) has {d}")
+        rows = u.numel() // d
+        if rows not in (1, b):
+            raise ValueError(f"u holds {rows} shifts of the tap for a batch of {b}: 1 (broadcast) or one per sample")
+        dirs = [0] * b if rows == 1 else list(range(b))
+        e = self.engine.forward_shift(sample, _t_float(timestep), ctx, key, u.reshape(rows, d), dirs, [1.0] * b, "eps")
+        return e.to(sample.dtype)
+
+    def forward_dh(self, sample=None, timestep=None, encoder_hidden_states=None, cross_attention_kwargs=None, op=None, block_idx=None, uk=None,
+                   verbose=False):
+        """Reference: utils.forward_dh, src/utils/utils.py:350-436 (SD): the eps TENSOR (not an output object) of the U-Net with
+        uk.view(-1, C, H, W) added to the activation at (op, block_idx) -- 'down' (after the block's downsampler; the last skip of the block is
+        that same tensor and is shifted with it), 'mid', 'up'.  The after_res / after_sa sub-block taps, which the reference names and never
+        defines, do not exist here.  Without op and uk: the plain eps."""
+        if self.kind != "sd":
+            raise TypeError("forward_dh is the SD form; the DDPM net takes unet(x, t, u=, op=, block_idx=)")
+        if op is None and block_idx is None and uk is None:
+            return self.engine.forward(sample, _t_float(timestep), encoder_hidden_states, "eps").to(sample.dtype)
+        e = self._forward_shifted(sample, timestep, encoder_hidden_states, uk, op, block_idx)
+        if verbose:
+            print(f"op : {op}, block_idx : {block_idx}, return eps.shape : {tuple(e.shape)}")
+        return e
+
+    def h_traversal(self, x, t, ctx, u, scales, op, block_idx, pcs=None):
+        """eps [len(pcs), len(scales), C, H, W] of ONE sample x [1, ...] moved along h-space directions: entry (i, j) is the net with
+        scales[j] * u[:, pcs[i]] / ||u[:, pcs[i]]|| added at the tap (op, block_idx).  u [D, k] as the pullbacks and PCAs return it (columns;
+        pcs=None: all of them).  The rows go through shared-prefix calls of at most max_batch: the part of the net up to the tap runs once per
+        call, the directions are uploaded once and addressed per row."""
+        if x.shape[0] != 1:
+            raise ValueError("h_traversal moves a single sample (batch 1)")
+        key = self._decoder_tap(op, block_idx)
+        eng = self.engine
+        d = eng.tap_numel(key)
+        if u.dim() != 2 or u.shape[0] != d:
+            raise ValueError(f"u must be [{d}, k] (columns: directions at the tap ({op}, {block_idx})), got {tuple(u.shape)}")
+        pcs = list(range(u.shape[1])) if pcs is None else [int(i) for i in pcs]
+        scales = [float(a) for a in scales]
+        if not pcs or not scales or min(pcs) < 0 or max(pcs) >= u.shape[1]:
+            raise ValueError(f"pcs must be a non-empty subset of range({u.shape[1]}) and scales non-empty")
+        U = u.detach().to(device=self.device, dtype=torch.float32)
+        U = (U / U.norm(dim=0, keepdim=True)).T.contiguous()                     # [k, D] rows, unit norm (as the edit drivers: edit.py:267)
+        rows = [(i, a) for i in pcs for a in scales]
+        tt = _t_float(t)
+        out = [eng.forward_shift(x, tt, ctx, key, U, [r[0] for r in rows[i0:i0 + eng.max_batch]], [r[1] for r in rows[i0:i0 + eng.max_batch]], "eps")
+               for i0 in range(0, len(rows), eng.max_batch)]
+        c, hh, ww = eng.tape.tap_shape[eng.tape.taps["eps"]]
+        return torch.cat(out).view(len(pcs), len(scales), c, hh, ww).to(x.dtype)
 
     # ------------------------------------------------------------------ power iteration
     def _pullback(self, x, t, ctx, op, block_idx, k, chunks, min_iter, max_iter, thr, V0):
@@ -477,6 +544,7 @@ def bind(unet, kind: str, cfg, dtype=torch.float32, device="cuda:0", **kw) -> Pu
         unet.local_decoder_pullback_zt = types.MethodType(lambda self, *a, **k: self._dpb.local_decoder_pullback_zt(*a, **k), unet)
         unet.global_pca_zt = types.MethodType(lambda self, *a, **k: self._dpb.global_pca_zt(*a, **k), unet)
         unet.inv_jac_zt = types.MethodType(lambda self, *a, **k: self._dpb.inv_jac_zt(*a, **k), unet)
+        unet.forward_dh = types.MethodType(lambda self, *a, **k: self._dpb.forward_dh(*a, **k), unet)
         unet.local_pca_zt = types.MethodType(lambda self, *a, **k: self._dpb.local_pca_zt(*a, **k), unet)
     else:
         unet.local_encoder_pullback_xt = types.MethodType(lambda self, *a, **k: self._dpb.local_encoder_pullback_xt(*a, **k), unet)

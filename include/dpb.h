@@ -215,6 +215,19 @@ int dpb_pullback_iterate_between(dpb_engine* e, int src_buf, int dst_buf, float*
  * state afterwards).  Replaces: get_h_to_e with input_h.size(0) = batch (utils.py:593-606, diffusion.py:321-325: the skips repeated). */
 int dpb_forward_from(dpb_engine* e, const float* x, int batch, float t, const float* ctx, int src_buf, const float* h, int dst_buf, int channels,
                      float* out);
+/* The h-space shifted forward (additive to ABI version 1): row b of `out` is dst_buf of the net with the activation at src_buf replaced by
+ * h(x_b) + scale[b] * u[dir[b]] and every skip taken from x_b.  u: DEVICE fp32 [nu][channels(src)][rows(src)] (NCHW-flattened, valid channels);
+ * dir, scale: HOST arrays of `batch` entries -- they travel as kernel arguments, dir[b] = -1 leaves row b unshifted.  The sum is formed in fp32
+ * and rounded once to the engine dtype.  xbatch = batch: x [batch] and ctx [batch] rows, one ordinary forward pass with the shift applied right
+ * after the producer of src_buf.  xbatch = 1 < batch (shared prefix): x [1], ctx [1]; the ops up to the producer of src_buf run ONCE at batch 1,
+ * the tap is written as `batch` shifted copies, sample 0 of every buffer the rest of the pass still reads (skips, the context's K/V projection;
+ * derived from the tape) is broadcast in one launch, and only the ops after the tap run at `batch`.  No device allocation, no host synchronisation
+ * beyond dpb_forward's one for the timestep embedding; state rules of dpb_forward (no primal state afterwards); dpb_engine_stats reports what was
+ * launched.  Refused (dpb_last_error): batch outside [1, max_batch], xbatch not in {1, batch}, nu < 1, a dir[b] outside [-1, nu), src_buf not an
+ * x-dependent activation produced by an op, dst_buf not strictly downstream of src_buf.
+ * Replaces: PullBackDDPM.forward(x, t, u, op, block_idx) (src/models/ddpm/diffusion.py:145-200) and forward_dh (src/utils/utils.py:350-436). */
+int dpb_forward_shift(dpb_engine* e, const float* x, int xbatch, int batch, float t, const float* ctx, int src_buf, const float* u, int nu,
+                      const int32_t* dir, const float* scale, int dst_buf, int channels, float* out);
 
 /* DDIM update (utils.py:301-306 / :1220-1225, eta = 0) and the x-space-guidance axpy (edit.py:490, :501). */
 int dpb_ddim_step(const float* x, const float* eps, float* out, float* x0, int64_t n, float alpha_t, float alpha_next,
