@@ -192,12 +192,10 @@ int gemm(dpb_engine* e, GemmArgs a, bool can_defer = false) {
   e->flops += 2.0 * a.M * (double)a.N * kk * a.Z1 * a.Z2;
   e->gbytes += ((double)a.M * a.K + (double)a.N * a.K + (double)a.M * a.N) * a.Z1 * a.Z2 * e->es;
   int nl = 1;                                   // kernels enqueued: the product itself (+ splitk_reduce_kernel for split-K launches)
-  if (!e->profiling) { const int r = launch_gemm(e->dtype, a, e->stream, &nl, pend); e->n_launch += nl; e->pend.on = pend && pend->splitk > 1; return r; }
-  int kind;
-  { GemmArgs az = a; az.zeros = e->ws + e->zeros; const int dm = gemm_uses_dma(e->dtype, a); kind = gemm_uses_halo(e->dtype, az) ? 5 : dm == 540 ? 12 : dm == 530 ? 11 : dm == 518 ? 6 : dm >= 512 ? 4 : (dm == 128 || dm == 130 || dm == 132 || dm == 256) ? 2 : dm ? 3 : gemm_uses_big_tile(e->dtype, a); }   // 0: 64x64 register-staged, 2: 128x128 ring, 3: 64x64 ring, 4: BK=64 ring (128x128 tile), 5: halo-tile 3x3 convolution, 6: BK=64 ring, 256x256 tile, 11: 8-phase 256x256 tile (gemm_p8.hip)
-  // the same bracket helpers as the attention launches (an event that cannot be created or recorded costs the bracket, never leaks its partner)
-  const int pi = prof_open(e, 2.0 * a.M * (double)a.N * kk * a.Z1 * a.Z2, kind, a.M, a.N, a.K, a.Z1 * a.Z2, a.gather);
-  int r = launch_gemm(e->dtype, a, e->stream, &nl, pend);
+  const GemmPlan pl = gemm_plan(e->dtype, a);   // the one dispatch of this launch: launch_gemm runs it, the bracket is labelled with its tile's profile kind
+  // (-1 with profiling off) the same bracket helpers as the attention launches (an event that cannot be created or recorded costs the bracket, never leaks its partner)
+  const int pi = prof_open(e, 2.0 * a.M * (double)a.N * kk * a.Z1 * a.Z2, pl.row ? pl.row->kind : 0, a.M, a.N, a.K, a.Z1 * a.Z2, a.gather);
+  const int r = launch_gemm(e->dtype, a, e->stream, &nl, pend, &pl);
   e->n_launch += nl;
   e->pend.on = pend && pend->splitk > 1;
   prof_close(e, pi);
@@ -1653,7 +1651,7 @@ int dpb_debug_gemm_plan(int dtype, int M, int N, int K, int conv_hw, int conv_ci
     a.gather = GATHER_CONV; a.H = a.W = a.Ho = a.Wo = conv_hw; a.Cin = conv_cin; a.KS = 3; a.stride = 1; a.pad = 1; a.lda = conv_cin;
   }
   const GemmPlan pl = gemm_plan(dtype, a);
-  if (pl.kind < 0) return -1;
+  if (!pl.row) return -1;
   *kind = pl.kind; *tile = pl.tile; *splitk = pl.splitk;
   return 0;
 }

@@ -449,19 +449,20 @@ static int g_p8 = 1;
 void gemm_debug_p8(int on) { g_p8 = on; }
 static int g_wres = 1;
 void gemm_debug_wres(int on) { g_wres = on; }
+void gemm_variant_error(const GemmTile& t, const GemmArgs& a) { set_error("gemm: tile %d has no kernel of this family for gather %d with epilogue %d", t.code, a.gather, a.epi); }
 static thread_local int t_reduce_launched = 0;   // set by launch_t when a splitk_reduce_kernel launch followed the product
 static thread_local GemmArgs* t_pending = nullptr;   // launch_gemm(..., pending): where a deferrable reduction is parked instead of launched
 
-int gemm_uses_big_tile(int dtype, const GemmArgs& a) {
+static const GemmTile* pick_reg_tile(int dtype, const GemmArgs& a) {
   // Register-staged kernel, measured on MI355X (tools/gpu_gemm_bench.py, profiles/r01_gemm_microbench.txt):
   // bf16 -- the 64x64 tile (7 blocks/CU in flight) beats the 128x128 tile, which is latency-bound at <= 4 blocks/CU
   //         (large bf16 problems go to the asynchronous ring kernels instead);
   // fp32 -- the slow fp32 MFMA (64 cycles) hides the load latency: with >= 4 tiles per CU the 128x128 tile wins
   //         (119 vs 93 TF/s on the 256x256-resolution DDPM convolutions), below that the 64x64 tile.
-  if (g_force_tile) return g_force_tile == 128;
-  if (dtype != DT_F32 || a.A2) return 0;
-  const long t128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128) * a.Z1 * a.Z2;
-  return t128 >= 1024;
+  const GemmTile *small = &kGemmTiles[T_REG64], *big = &kGemmTiles[T_REG128];
+  if (g_force_tile) return g_force_tile == big->forced ? big : small;
+  if (dtype != DT_F32 || a.A2) return small;
+  return gemm_tile_count(*big, a) >= 1024 ? big : small;
 }
 
 // Per-shape tuning overrides, for in-pipeline kernel selection experiments (tools/gpu_gemm_override.py):
@@ -488,8 +489,17 @@ static const ShapeOverride* find_override(const GemmArgs& a) {
     if (r.M == a.M && r.N == a.N && r.K == a.K && r.gather == a.gather && a.Z1 * a.Z2 == 1) return &r;
   return nullptr;
 }
+// the forced tile code / split count of a product: dpb_debug_set first, then the per-shape override (0 = heuristic)
+static int forced_code(const GemmArgs& a) {
+  const ShapeOverride* ov = g_force_tile ? nullptr : find_override(a);
+  return ov ? ov->code : g_force_tile;
+}
+static long forced_splitk(const GemmArgs& a) {
+  const ShapeOverride* ov = g_force_splitk ? nullptr : find_override(a);
+  return g_force_splitk ? g_force_splitk : ov ? ov->split : 0;
+}
 
-// The weights-resident streaming kernel (gemm_wres.hip, tile code 540): plain products with K = 320 and N a multiple of 320 (the 320-channel linear layers
+// The weights-resident streaming kernel (gemm_wres.hip, row T_WRES): plain products with K = 320 and N a multiple of 320 (the 320-channel linear layers
 // of the 64 x 64 level, tangent / adjoint passes) from the row count at which streaming beats the tile kernels.  Measured against the round-5 dispatch per
 // shape (profiles/r06_wres_shapes.txt, event brackets, same session): N = 320 -- 20480 rows 15.0 vs 11.8 us (the 200 KB weight preload per CU and three
 // serial tiles are not amortised: the rings keep the 5-tangent pass), 40960 rows equal, 81920 rows 30 vs 35 us, 327680 rows 93 vs 156 us (4.5 TB/s of
@@ -523,46 +533,42 @@ static int p8_wants(int dtype, const GemmArgs& a) {
 }
 
 // the halo-tile 3x3 convolution (gemm_halo.hip): every supported shape of the path measured faster than the implicit-GEMM rings
-int gemm_uses_halo(int dtype, const GemmArgs& a) {
+static bool wants_halo(int dtype, const GemmArgs& a) {
   static const int halo_env = getenv("DPB_CONV_HALO") ? atoi(getenv("DPB_CONV_HALO")) : 1;   // tuning switch (0: implicit-GEMM rings)
-  const ShapeOverride* ov = g_force_tile ? nullptr : find_override(a);
-  const int force = ov ? ov->code : g_force_tile;
-  const bool want = force == 600 || (halo_env && force == 0 && g_dma_auto && !p8_wants(dtype, a));
+  const int force = forced_code(a);
+  const bool forced = force == kGemmTiles[T_HALO].forced;
+  const bool want = forced || (halo_env && force == 0 && g_dma_auto && !p8_wants(dtype, a));
   // (8x8 images, four per tile, are supported but measure no better than the split-K ring: forced only)
-  return want && dtype != DT_F32 && conv_halo_supported(a) && (a.H * a.W >= 256 || force == 600);
+  return want && dtype != DT_F32 && conv_halo_supported(a) && (a.H * a.W >= 256 || forced);
 }
 
-// the asynchronous LDS-ring kernel (gemm_dma.hip): bf16, one operand pair, enough 128x128 tiles to fill the chip
-int gemm_uses_dma(int dtype, const GemmArgs& a) {
-  const ShapeOverride* ov = g_force_tile ? nullptr : find_override(a);
-  const int force = ov ? ov->code : g_force_tile;
-  if (dtype == DT_F32 || a.A2 || !a.zeros || force == 64 || force == 128) return 0;
-  if (force == 129) return 128;
-  if (force == 131) return 130;
-  if (force == 133) return 132;
-  if (force == 257) return 256;
-  if (force == 65) return 64;
-  if (force == 67) return 66;
-  if (force >= 512 && force <= 517) return force;
-  if (force == 521 && a.epi == EPI_PLAIN && a.gather != GATHER_UPCONV) return 521;     // (also as an implicit-GEMM convolution)
-  if (force >= 521 && force <= 523) return (a.gather == GATHER_NONE && a.epi == EPI_PLAIN) ? force : 515;
-  if (force == 518) return a.gather == GATHER_NONE ? 518 : 515;
-  if (force == 530) return ((a.epi == EPI_PLAIN || a.gather == GATHER_NONE) && (a.gather == GATHER_NONE || a.Cin % 64 == 0)) ? 530 : 515;
-  if (force == 540) return gemm_wres_supported(dtype, a) ? 540 : 515;
-  const long t128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128) * a.Z1 * a.Z2;
-  const long t64 = (long)((a.M + 63) / 64) * ((a.N + 63) / 64) * a.Z1 * a.Z2;
+// The tile of a product that is not a halo-tile convolution: a row of one of the four asynchronous families (BK = 32 / BK = 64 LDS rings, 8-phase
+// tile, weights-resident kernel) -- 16-bit, one operand pair -- or nullptr for the register-staged kernel (pick_reg_tile).
+static const GemmTile* pick_async_tile(int dtype, const GemmArgs& a) {
+  if (dtype == DT_F32 || a.A2 || !a.zeros) return nullptr;
+  if (const GemmTile* f = gemm_tile_forced(forced_code(a))) {
+    // a forced code: its tile, or that row's substitute for a product the tile does not take.  A code that names no row (and the halo code on a
+    // product the halo kernel does not take) falls through to the heuristic -- with the halo kernel off (wants_halo)
+    if (f->family == FAM_REG) return nullptr;
+    if (f->family != FAM_HALO) {
+      const bool takes = gemm_tile_builds(*f, a.gather, a.epi) && !((f->flags & TILE_CIN64) && a.gather != GATHER_NONE && a.Cin % 64) &&
+                         (f->family != FAM_WRES || gemm_wres_supported(dtype, a));
+      return (takes || f->substitute == T_NONE) ? f : &kGemmTiles[f->substitute];
+    }
+  }
+  const long t128 = gemm_tile_count(kGemmTiles[T_R64_S2], a), t64 = gemm_tile_count(kGemmTiles[T_R32_64], a);
   // measured on the path's layer shapes (profiles/r01_gemm_microbench.txt): the 128x128 ring wins once every CU holds
   // >= ~2 tiles, and for long-K under-filled problems when combined with split-K; short-K mid-size problems go to the
   // 64x64 ring; everything else (tiny problems, fp32, dual-operand products) to the register-staged kernel.
-  if (!g_dma_auto || a.K < 256) return 0;
-  if (wres_wants(dtype, a)) return 540;
-  if (p8_wants(dtype, a)) return 530;
+  if (!g_dma_auto || a.K < 256) return nullptr;
+  if (wres_wants(dtype, a)) return &kGemmTiles[T_WRES];
+  if (p8_wants(dtype, a)) return &kGemmTiles[T_P8];
   // 256x256 8-wave tile (half the L2->LDS bytes per flop): plain-row products that give >= 160 such tiles with < 7 % padding and K >= 640
   // -- 12-26 % ahead of the 128x128 ring there, behind it below (profiles/r02_gemm_big_microbench.txt, r02_gemm_split_microbench.txt)
   static const int big_env = getenv("DPB_TILE256") ? atoi(getenv("DPB_TILE256")) : 1;   // tuning switch
   if (big_env && a.gather == GATHER_NONE && a.K >= 640 && a.Z1 * a.Z2 == 1) {
     const long t256 = (long)((a.M + 255) / 256) * ((a.N + 255) / 256);
-    if (t256 >= 160 && (double)t256 * 65536.0 <= 1.07 * (double)a.M * a.N) return 518;
+    if (t256 >= 160 && (double)t256 * 65536.0 <= 1.07 * (double)a.M * a.N) return &kGemmTiles[T_R64_256];
   }
   // Half tiles for launches that give every CU at most ONE 128x128 block (128 <= tiles < 256: the plain-row products of the 32x32 level at k = 5,
   // 5120x640xK = 200 tiles): a lone 4-wave block has no co-resident partner to cover its barrier / fragment latency (43 us for 5120x640x2560
@@ -571,150 +577,111 @@ int gemm_uses_dma(int dtype, const GemmArgs& a) {
   // (46.5 vs 56.3 us).  128x64 tiles measure the same, the 2-stage 64x128 ring (three blocks per CU) less (profiles/r04_gemm_override_half_tiles.txt).
   static const int half_env = getenv("DPB_HALF_TILE") ? atoi(getenv("DPB_HALF_TILE")) : 3;   // tuning switch (bit 0 / bit 1: the two rules below)
   static const int half_kmin = getenv("DPB_HALF_KMIN") ? atoi(getenv("DPB_HALF_KMIN")) : 256;   // tuning switch (256: the K = 320 products of a batch-2 forward at 64x64 too: forward -0.3 %, iteration neutral)
-  if ((half_env & 1) && a.gather == GATHER_NONE && a.epi == EPI_PLAIN && a.Z1 * a.Z2 == 1 && a.K >= half_kmin && a.K <= 4096 && t128 >= 128 && t128 < 256) return 521;
+  if ((half_env & 1) && a.gather == GATHER_NONE && a.epi == EPI_PLAIN && a.Z1 * a.Z2 == 1 && a.K >= half_kmin && a.K <= 4096 && t128 >= 128 && t128 < 256) return &kGemmTiles[T_R64_HALF];
   // ... and for long-K products whose last 128-row tile is at most half full (M = 320 = 64 k rows of the 8x8 level at k = 5: 2.5 tiles, 17 % padded
   // MFMAs): 64-row tiles cover M exactly, give 50 instead of 30 tiles, and the split-K plan needs 9 instead of 15 fp32 slabs for its ~450 blocks --
   // the consumers (one-launch GroupNorm, LayerNorm) gather 40 % fewer slab bytes: 8.577 -> 8.52 ms per iteration inside the pass on the seventeen
   // 8x8-level convolutions (22.4 -> 21.7 us each; 15 or 6 splits on the same tile: 25-27 us)
-  if ((half_env & 2) && a.epi == EPI_PLAIN && a.gather != GATHER_UPCONV && a.Z1 * a.Z2 == 1 && a.K >= 2048 && t128 < 128 && (a.M % 128) && (a.M % 128) <= 64) return 521;
+  if ((half_env & 2) && a.epi == EPI_PLAIN && a.gather != GATHER_UPCONV && a.Z1 * a.Z2 == 1 && a.K >= 2048 && t128 < 128 && (a.M % 128) && (a.M % 128) <= 64) return &kGemmTiles[T_R64_HALF];
   // BK = 64 ring (gemm_ring64.hip: whole-line DMA + in-wave fragment prefetch, 128x128 tile, 2 stages -> 2 blocks/CU):
   // ahead of the BK = 32 rings by 10-35 % from ~8 stages of K on, with split-K when the tiles leave CUs idle
-  if (a.K >= 512 && (t128 >= 200 || a.K >= 2048)) return 515;
+  if (a.K >= 512 && (t128 >= 200 || a.K >= 2048)) return &kGemmTiles[T_R64_S2];
   // short K (320 on the 64x64 level) with the chip filled by 128x128 tiles: the BK=64 ring again -- 11.5 vs 12.9 us on 20480x320x320,
-  // 27.9 vs 30.4 us at N = 960, equal at N >= 1280 (profiles/r02_gemm_shortk_microbench.txt); the BK=32 ring (130) remains for K % 64 != 0
+  // 27.9 vs 30.4 us at N = 960, equal at N >= 1280 (profiles/r02_gemm_shortk_microbench.txt); the BK=32 ring (T_R32_S3) remains for K % 64 != 0
   // -- up to ~1300 tiles; beyond (several samples advanced together: 81920 rows) the BK=32 ring's three blocks per CU hide the residual /
   // row-bias loads of the epilogue better (43 vs 45 us on 81920x320x320 inside the pass)
-  if (t128 >= 400) return (a.K % 64 == 0 && t128 <= 1280) ? 515 : 130;
-  if (a.K >= 2048 && t128 >= 64) return 256;    // long K, under-filled: 256x128 ring + split-K (fewest operand re-reads)
+  if (t128 >= 400) return &kGemmTiles[(a.K % 64 == 0 && t128 <= 1280) ? T_R64_S2 : T_R32_S3];
+  if (a.K >= 2048 && t128 >= 64) return &kGemmTiles[T_R32_TALL];    // long K, under-filled: 256x128 ring + split-K (fewest operand re-reads)
   // 64x64 ring, unsplit: also for ~100-250 tiles at K >= 1024 -- inside the pass 11.6 vs 13.8 us (320x1280x1280, ten per iteration) and 11.0 vs
   // 17.2 us (1280x640x1280) against the register-staged kernel with split-K 5 + reduce (profiles/r02_gemm_override_in_pipeline.txt)
-  if (t64 >= 256 || (t64 >= 96 && a.K >= 1024)) return 64;
-  return 0;
+  if (t64 >= 256 || (t64 >= 96 && a.K >= 1024)) return &kGemmTiles[T_R32_64];
+  return nullptr;
 }
 
 // fused epilogues (epilogue.h) live in the ring kernels with 128-column tiles and need the whole K range in one block
 int gemm_epi_supported(int dtype, const GemmArgs& a) {
-  if (a.epi == EPI_LN_TAN || a.epi == EPI_LN_ADJ)                // row-complete 128 x 320 tile (gemm_ring64.hip, tile code 520)
-    return dtype != DT_F32 && a.Z1 * a.Z2 == 1 && a.gather == GATHER_NONE && a.N == 320 && a.ldc == 320 && a.M >= 128 && a.K % 64 == 0 && a.zeros &&
+  if (a.epi == EPI_LN_TAN || a.epi == EPI_LN_ADJ) {              // the row-complete tile (T_R64_LN)
+    const GemmTile& ln = kGemmTiles[T_R64_LN];
+    return dtype != DT_F32 && a.Z1 * a.Z2 == 1 && a.gather == GATHER_NONE && a.N == ln.bn && a.ldc == ln.bn && a.M >= ln.bm && a.K % 64 == 0 && a.zeros &&
            a.ln_x && a.ln_gamma && !a.A2 && !a.bias && !a.rowbias && a.alpha == 1.f && (a.epi == EPI_LN_ADJ || (a.C2 && !a.accumulate)) && (!a.R || a.ldr % 8 == 0);
+  }
   if (dtype == DT_F32 || a.Z1 * a.Z2 != 1 || a.gather != GATHER_NONE || a.N % 128 || a.M <= 0) return 0;
   if (a.epi == EPI_GEGLU_ADJ && a.N % 64) return 0;
-  const int dt = gemm_uses_dma(dtype, a);
-  if (dt == 518 || dt >= 530) return a.N % 256 == 0;
-  return dt == 128 || dt == 130 || dt == 132 || dt == 256 || (dt >= 512 && dt <= 517);
+  const GemmTile* t = pick_async_tile(dtype, a);
+  if (!t || !(t->flags & TILE_GEGLU) || t->bn % 128) return 0;
+  return !(t->flags & TILE_EPI_N256) || a.N % 256 == 0;
 }
 
-// split-K for the ring kernels: long-K problems that leave CUs idle (weights then stream from HBM once, in parallel)
-int gemm_pick_splitk_dma(const GemmArgs& a, int tile) {
-  if (!a.slab) return 1;
-  const int T = (tile == 518 || tile >= 530) ? 256 : (tile == 128 || tile == 130 || tile == 132 || tile == 256 || (tile >= 512 && tile <= 517) || tile == 521 || tile == 522) ? 128 : 64;
-  const int TMm = (tile == 256 || tile == 513 || tile == 516 || tile == 517 || tile == 518 || tile >= 530) ? 256 : tile == 523 ? 128 : (tile == 521 || tile == 522) ? 64 : T;
-  const long tiles = (long)((a.M + TMm - 1) / TMm) * ((a.N + T - 1) / T) * a.Z1 * a.Z2;
+static int gemm_kch(const GemmArgs&) { return g_kch ? g_kch : 4; }
+
+// The heuristic K split of one product on tile t, before the clamps of gemm_plan (1 = none): long-K problems that leave CUs idle (weights then
+// stream from HBM once, in parallel)
+static long pick_splitk(int dtype, const GemmArgs& a, const GemmTile& t) {
+  const long tiles = gemm_tile_count(t, a);
+  if (t.family == FAM_HALO) {
+    // one resident block per CU: time ~ rounds x (chunks per block + ~2 chunks of prologue / epilogue); measured optimum on
+    // the path's layers (profiles/r01_gemm_microbench.txt): 64^2 -> 1, 32^2 -> 2, 16^2 -> 5 splits
+    const int nch = a.Cin / 64;
+    long best = 1L << 60, s = 1;
+    for (long c = 1; c <= nch; ++c) {
+      const long cost = ((tiles * c + 255) / 256) * ((nch + c - 1) / c + 2);
+      if (cost < best) { best = cost; s = c; }
+    }
+    return s;
+  }
+  if (t.family == FAM_REG) {                     // under-filled launches of the 64x64 tile
+    const int nk = (a.K + (dtype == DT_F32 ? 4 : 8) * gemm_kch(a) - 1) / ((dtype == DT_F32 ? 4 : 8) * gemm_kch(a));
+    if (t.bm == 128 || tiles >= 768 || nk < 32) return 1;
+    const long s = std::min<long>((1024 + tiles - 1) / tiles, nk / 8);   // aim at ~4 blocks per CU, keep >= 8 K steps per block
+    return std::min<long>(s, 32);
+  }
+  if (t.flags & TILE_NOSPLIT) return 1;
   const int nk = (a.K + 31) / 32;
-  long s;
-  const ShapeOverride* ov = g_force_splitk ? nullptr : find_override(a);
-  if (g_force_splitk) s = g_force_splitk;
-  else if (ov && ov->split) s = ov->split;
-  else if (tile >= 512) {                     // 2 resident blocks per CU: aim at ~450 blocks, >= 8 stages of 64 each
+  if (t.family != FAM_RING32) {                 // 2 resident blocks per CU: aim at ~450 blocks, >= 8 stages of 64 each
     // (512 until the deferred reductions moved the slab gathers into the consumers: 448 / 384 measure 0.5 % ahead of 512 there, 320 / 256 behind;
     // 768: +4 % -- profiles/r03_ab_sessions.txt)
     static const long target = getenv("DPB_SPLITK_TARGET") ? atol(getenv("DPB_SPLITK_TARGET")) : 448;   // tuning switch
     // >= 192 tiles (3/4 of the CUs hold a block): splitting only pays for K >= 4096 and only two-fold -- measured per shape in
     // profiles/r02_gemm_split_microbench.txt (5120x640: K 1920 / 2560 24 / 32 us unsplit vs 34 / 41 us three-fold, K 5120 52 us two-fold vs
     // 58 unsplit; 1280x3840x1280 25 vs 36 us; 320x10240x1280 18 vs 25 us)
-    if (tile == 518 || tile == 530 || tile == 540) return 1;  // one block per CU by construction: never split
-    if (tiles >= 192) s = (tiles < 256 && nk >= 128) ? 2 : 1;
-    else {
-      s = std::max<long>(1, (target + tiles / 2) / tiles);
-      s = std::min<long>(s, std::max(1, nk / 16));
-    }
-  } else {
-    if (tiles >= 256 || nk < 64) return 1;      // only when CUs would idle and K is long enough to amortise the slabs
-    s = (1024 + tiles - 1) / tiles;
-    s = std::min<long>(s, nk / 12);             // keep >= 12 K steps per block (ring depth 3)
-    s = std::min<long>(s, 32);
+    if (tiles >= 192) return (tiles < 256 && nk >= 128) ? 2 : 1;
+    return std::min<long>(std::max<long>(1, (target + tiles / 2) / tiles), std::max(1, nk / 16));
   }
-  s = std::min<long>(s, nk);
-  const long per = (long)a.M * a.N * a.Z1 * a.Z2 * 4;
-  if (s * per > (long)a.slab_bytes) s = (long)a.slab_bytes / per;
-  return (int)std::max<long>(s, 1);
+  if (tiles >= 256 || nk < 64) return 1;        // only when CUs would idle and K is long enough to amortise the slabs
+  const long s = std::min<long>((1024 + tiles - 1) / tiles, nk / 12);   // keep >= 12 K steps per block (ring depth 3)
+  return std::min<long>(s, 32);
 }
 
-int gemm_kch(const GemmArgs& a) {
-  if (g_kch) return g_kch;
-  return 4;
-}
-
-// number of K splits for under-filled launches (1 = none)
-int gemm_pick_splitk(int dtype, const GemmArgs& a) {
-  if (a.A2 || !a.slab) return 1;
-  const int BK = (dtype == DT_F32 ? 4 : 8) * gemm_kch(a);
-  const int T = gemm_uses_big_tile(dtype, a) ? 128 : 64;
-  const long tiles = (long)((a.M + T - 1) / T) * ((a.N + T - 1) / T) * a.Z1 * a.Z2;
-  const int nk = (a.K + BK - 1) / BK;
-  long s;
-  const ShapeOverride* ov = g_force_splitk ? nullptr : find_override(a);
-  if (g_force_splitk) {
-    s = g_force_splitk;
-  } else if (ov && ov->split) {
-    s = ov->split;
-  } else {
-    if (T == 128 || tiles >= 768 || nk < 32) return 1;
-    s = (1024 + tiles - 1) / tiles;             // aim at ~4 blocks per CU
-    s = std::min<long>(s, nk / 8);              // keep >= 8 K steps per block
-    s = std::min<long>(s, 32);
-  }
-  s = std::min<long>(s, nk);
-  const long per = (long)a.M * a.N * a.Z1 * a.Z2 * 4;
-  if (s * per > (long)a.slab_bytes) s = (long)a.slab_bytes / per;
-  return (int)std::max<long>(s, 1);
-}
-
-// ---- the launch plan of one product: which kernel, which tile, how many K splits.  A pure host function (dpb_debug_gemm_plan exposes it, so
-// the dispatch rules are testable without a GPU); EVERY path's split count passes the slab-capacity clamp here, in one place.
-enum { PLAN_REG64 = 0, PLAN_REG128 = 1, PLAN_RING = 2, PLAN_HALO = 3 };
+// ---- the launch plan of one product: which tile, how many K splits.  A pure host function (dpb_debug_gemm_plan exposes it, so the dispatch
+// rules are testable without a GPU).  The forced split count is looked up here and EVERY path's split count passes the K-step and
+// slab-capacity clamps here, in one place -- no rule can return around them.
 GemmPlan gemm_plan(int dtype, const GemmArgs& a) {
-  GemmPlan pl{PLAN_REG64, 0, 1};
-  long s = 1;
-  if (gemm_uses_halo(dtype, a)) {
-    // 3x3 stride-1 convolutions: halo-tile kernel (gemm_halo.hip), one 256x128 tile per block, K split over 64-channel chunks
-    pl.kind = PLAN_HALO; pl.tile = 600;
-    const long tiles = (long)((a.M + 255) / 256) * ((a.N + 127) / 128);
-    const int nch = a.Cin / 64;
-    const ShapeOverride* ov = g_force_splitk ? nullptr : find_override(a);
-    if (g_force_splitk) s = g_force_splitk;
-    else if (ov && ov->split) s = ov->split;
-    else if (a.slab) {
-      // one resident block per CU: time ~ rounds x (chunks per block + ~2 chunks of prologue / epilogue); measured optimum on
-      // the path's layers (profiles/r01_gemm_microbench.txt): 64^2 -> 1, 32^2 -> 2, 16^2 -> 5 splits
-      long best = 1L << 60;
-      for (long c = 1; c <= nch; ++c) {
-        const long cost = ((tiles * c + 255) / 256) * ((nch + c - 1) / c + 2);
-        if (cost < best) { best = cost; s = c; }
-      }
-    }
-    s = std::min<long>(s, nch);
+  const GemmTile* t;
+  if (a.M <= 0 || a.N <= 0 || a.K <= 0) { set_error("gemm: empty problem M=%d N=%d K=%d", a.M, a.N, a.K); return GemmPlan{-1, 0, 1, nullptr}; }
+  if (wants_halo(dtype, a)) {
+    t = &kGemmTiles[T_HALO];                      // 3x3 stride-1 convolutions: one 256x128 tile per block, K split over 64-channel chunks
+  } else if (a.epi != EPI_PLAIN && !gemm_epi_supported(dtype, a)) {
+    set_error("gemm: fused epilogue %d requested for a launch no ring kernel with 128-column tiles takes (M=%d N=%d K=%d)", a.epi, a.M, a.N, a.K);
+    return GemmPlan{-1, 0, 1, nullptr};
+  } else if (a.epi == EPI_LN_TAN || a.epi == EPI_LN_ADJ) {
+    t = &kGemmTiles[T_R64_LN];
   } else {
-    if (a.epi != EPI_PLAIN && !gemm_epi_supported(dtype, a)) {
-      set_error("gemm: fused epilogue %d requested for a launch no ring kernel with 128-column tiles takes (M=%d N=%d K=%d)", a.epi, a.M, a.N, a.K);
-      pl.kind = -1;
-      return pl;
-    }
-    if (a.epi == EPI_LN_TAN || a.epi == EPI_LN_ADJ) {
-      pl.kind = PLAN_RING; pl.tile = 520; s = 1;
-    } else if (const int dt = gemm_uses_dma(dtype, a)) {
-      pl.kind = PLAN_RING; pl.tile = dt;
-      s = (a.epi != EPI_PLAIN || dt == 540) ? 1 : gemm_pick_splitk_dma(a, dt);      // (the weights-resident kernel never splits K, whatever a debug override asks)
-    } else {
-      pl.kind = gemm_uses_big_tile(dtype, a) ? PLAN_REG128 : PLAN_REG64;
-      pl.tile = pl.kind == PLAN_REG128 ? 128 : 64;
-      s = gemm_pick_splitk(dtype, a);
-    }
+    t = pick_async_tile(dtype, a);
+    if (!t) t = pick_reg_tile(dtype, a);
   }
-  const long per = (long)a.M * a.N * a.Z1 * a.Z2 * 4;          // one fp32 slab
-  if (s > 1 && (!a.slab || s * per > (long)a.slab_bytes)) s = a.slab ? (long)a.slab_bytes / per : 1;
-  pl.splitk = (int)std::max<long>(s, 1);
-  return pl;
+  long s = 1;
+  // fused epilogues need the whole K range in one block (the halo kernel has none and never looks at GemmArgs::epi); the register-staged kernel
+  // splits single operand pairs only
+  if (a.slab && (a.epi == EPI_PLAIN || t->family == FAM_HALO) && !(t->flags & TILE_NOSLAB) && !(t->family == FAM_REG && a.A2)) {
+    s = forced_splitk(a);
+    if (!s) s = pick_splitk(dtype, a, *t);
+    // at least one K step per split: 64-channel chunks (halo), the kernel's own K chunk (register-staged), 32 (rings)
+    const int kstep = t->family == FAM_REG ? (dtype == DT_F32 ? 4 : 8) * gemm_kch(a) : 32;
+    s = std::min<long>(s, t->family == FAM_HALO ? a.Cin / 64 : (a.K + kstep - 1) / kstep);
+    const long per = (long)a.M * a.N * a.Z1 * a.Z2 * 4;          // one fp32 slab
+    if (s > 1 && s * per > (long)a.slab_bytes) s = (long)a.slab_bytes / per;
+  }
+  return GemmPlan{gemm_plan_kind(*t), t->code, (int)std::max<long>(s, 1), t};
 }
 
 template <typename T, int BM, int BN, int KCH>
@@ -728,7 +695,7 @@ static void launch_reg_t(const GemmArgs& a, dim3 grid, hipStream_t st) {
 }
 
 template <typename T>
-static int launch_t(int dtype, GemmArgs a, hipStream_t st) {
+static int launch_t(int dtype, GemmArgs a, hipStream_t st, const GemmPlan* plan) {
   constexpr int CH = TT<T>::CH;
   if (a.K % CH || a.lda % CH || a.ldb % CH || (a.gather != GATHER_NONE && a.Cin % CH)) {
     set_error("gemm: K=%d lda=%d ldb=%d Cin=%d must be multiples of %d", a.K, a.lda, a.ldb, a.Cin, CH);
@@ -738,7 +705,6 @@ static int launch_t(int dtype, GemmArgs a, hipStream_t st) {
     set_error("gemm: second operand pair misaligned or combined with a gather");
     return -1;
   }
-  if (a.M <= 0 || a.N <= 0 || a.K <= 0) { set_error("gemm: empty problem M=%d N=%d K=%d", a.M, a.N, a.K); return -1; }
   a.vec_ok = !(a.ldc & 7) && !(a.sC1 & 7) && !(a.sC2 & 7) && (!a.R || (!(a.ldr & 7) && !(a.sR1 & 7) && !(a.sR2 & 7))) &&
              (!a.rowbias || !(a.N & 7)) && !((uintptr_t)a.C & 15) && !((uintptr_t)a.R & 15) && !((uintptr_t)a.bias & 15);
   const int Z = a.Z1 * a.Z2;
@@ -748,21 +714,23 @@ static int launch_t(int dtype, GemmArgs a, hipStream_t st) {
     const int force = g_force_order >= 0 ? g_force_order : env_order;
     a.order = force >= 0 ? force : (ub > ua ? 1 : 0);
   }
-  const GemmPlan pl = gemm_plan(dtype, a);
-  if (pl.kind < 0) return -1;
+  const GemmPlan pl = plan ? *plan : gemm_plan(dtype, a);
+  if (!pl.row) return -1;
+  const GemmTile& t = *pl.row;
   a.splitk = pl.splitk;
-  if (pl.kind == PLAN_HALO) {
-    if (int r = launch_conv_halo(a, st)) return r;
-  } else if (pl.kind == PLAN_RING) {
-    if (int r = pl.tile == 540 ? launch_gemm_wres(a, st) : pl.tile >= 530 ? launch_gemm_p8(a, pl.tile, st) : pl.tile >= 512 ? launch_gemm_ring64(a, pl.tile, st) : launch_gemm_dma(a, pl.tile, st)) return r;
-  } else if (pl.kind == PLAN_REG128) {
-    dim3 grid(((a.M + 127) / 128) * ((a.N + 127) / 128), Z, a.splitk);
-    launch_reg_t<T, 128, 128, 4>(a, grid, st);
-  } else {
-    dim3 grid(((a.M + 63) / 64) * ((a.N + 63) / 64), Z, a.splitk);
-    if (gemm_kch(a) == 8) launch_reg_t<T, 64, 64, 8>(a, grid, st);
-    else launch_reg_t<T, 64, 64, 4>(a, grid, st);
+  int r = 0;
+  switch (t.family) {
+    case FAM_HALO: r = launch_conv_halo(a, st); break;
+    case FAM_WRES: r = launch_gemm_wres(a, st); break;
+    case FAM_P8: r = launch_gemm_p8(a, t.code, st); break;
+    case FAM_RING64: r = launch_gemm_ring64(a, t, st); break;
+    case FAM_RING32: r = launch_gemm_dma(a, t, st); break;
+    default:
+      if (t.bm == 128) launch_reg_t<T, 128, 128, 4>(a, gemm_tile_grid(t, a), st);
+      else if (gemm_kch(a) == 8) launch_reg_t<T, 64, 64, 8>(a, gemm_tile_grid(t, a), st);
+      else launch_reg_t<T, 64, 64, 4>(a, gemm_tile_grid(t, a), st);
   }
+  if (r) return r;
   if (a.splitk > 1) {
     const bool plain = Z == 1 && a.alpha == 1.f && !a.bias && !a.rowbias && !a.accumulate && a.ldc == a.N && a.vec_ok && !(a.N & 7) && a.epi == EPI_PLAIN;
     if (t_pending && plain) {
@@ -787,19 +755,21 @@ int launch_gemm_reduce(int dtype, const GemmArgs& a, hipStream_t st) {
   return 0;
 }
 
-int launch_gemm(int dtype, const GemmArgs& a, hipStream_t st, int* launches, GemmArgs* pending) {
+int launch_gemm(int dtype, const GemmArgs& a, hipStream_t st, int* launches, GemmArgs* pending, const GemmPlan* plan) {
   GemmArgs b = a;
   b.fl = dtype == DT_F16;           // 16-bit flavour of the specialised kernels (H16<fl>)
   t_reduce_launched = 0;
   if (pending) pending->splitk = 1;
   t_pending = pending;
   static const int trace = getenv("DPB_GEMM_TRACE") ? atoi(getenv("DPB_GEMM_TRACE")) : 0;   // debugging: print every product, synchronise after it
+  GemmPlan traced;
   if (trace) {
-    fprintf(stderr, "gemm M=%d N=%d K=%d Z=%d gather=%d epi=%d lda=%d ldb=%d ldc=%d ldr=%d acc=%d R=%d bias=%d rowbias=%d kind=%d\n", b.M, b.N, b.K, b.Z1 * b.Z2, b.gather,
-            b.epi, b.lda, b.ldb, b.ldc, b.ldr, b.accumulate, b.R != nullptr, b.bias != nullptr, b.rowbias != nullptr, gemm_uses_dma(dtype, b));
+    if (!plan) { traced = gemm_plan(dtype, b); plan = &traced; }
+    fprintf(stderr, "gemm M=%d N=%d K=%d Z=%d gather=%d epi=%d lda=%d ldb=%d ldc=%d ldr=%d acc=%d R=%d bias=%d rowbias=%d tile=%d splitk=%d\n", b.M, b.N, b.K, b.Z1 * b.Z2, b.gather,
+            b.epi, b.lda, b.ldb, b.ldc, b.ldr, b.accumulate, b.R != nullptr, b.bias != nullptr, b.rowbias != nullptr, plan->tile, plan->splitk);
     fflush(stderr);
   }
-  const int r = DPB_DISPATCH_T(dtype, T, launch_t<T>(dtype, b, st));
+  const int r = DPB_DISPATCH_T(dtype, T, launch_t<T>(dtype, b, st, plan));
   if (trace && hipStreamSynchronize(st) != hipSuccess) fprintf(stderr, "gemm: the launch above failed\n");
   t_pending = nullptr;
   if (launches) *launches = 1 + t_reduce_launched;

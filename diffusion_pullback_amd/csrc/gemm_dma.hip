@@ -238,35 +238,12 @@ __global__ __launch_bounds__(256) void gemm_dma_kernel(GemmArgs p) {
   }
 }
 
-template <int BM, int BN, int S, int FL>
-static void launch_dma_f(const GemmArgs& a, dim3 grid, hipStream_t st) {
-  switch (a.gather) {
-    case GATHER_NONE:
-      if (a.epi == EPI_GEGLU_TAN) hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, S, GATHER_NONE, FL, EPI_GEGLU_TAN>), grid, dim3(256), 0, st, a);
-      else if (a.epi == EPI_GEGLU_ADJ) hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, S, GATHER_NONE, FL, EPI_GEGLU_ADJ>), grid, dim3(256), 0, st, a);
-      else if (a.epi == EPI_GEGLU_FWD) hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, S, GATHER_NONE, FL, EPI_GEGLU_FWD>), grid, dim3(256), 0, st, a);
-      else hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, S, GATHER_NONE, FL>), grid, dim3(256), 0, st, a);
-      break;
-    case GATHER_CONV: hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, S, GATHER_CONV, FL>), grid, dim3(256), 0, st, a); break;
-    case GATHER_CONVT: hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, S, GATHER_CONVT, FL>), grid, dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, S, GATHER_UPCONV, FL>), grid, dim3(256), 0, st, a); break;
-  }
-}
-template <int BM, int BN, int S>
-static void launch_dma_t(const GemmArgs& a, dim3 grid, hipStream_t st) {
-  if (a.fl) launch_dma_f<BM, BN, S, 1>(a, grid, st);
-  else launch_dma_f<BM, BN, S, 0>(a, grid, st);
-}
-
-int launch_gemm_dma(const GemmArgs& a, int tile, hipStream_t st) {
-  const int sk = a.splitk > 1 ? a.splitk : 1;
-  const int Z = a.Z1 * a.Z2;
-  auto tiles = [&](int bm, int bn) { return dim3(((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn), Z, sk); };
-  if (tile == 128) launch_dma_t<128, 128, 4>(a, tiles(128, 128), st);
-  else if (tile == 130) launch_dma_t<128, 128, 3>(a, tiles(128, 128), st);        // 48 KiB ring -> 3 blocks/CU (default)
-  else if (tile == 256) launch_dma_t<256, 128, 3>(a, tiles(256, 128), st);        // wave tile 128x64, 72 KiB ring
-  else if (tile == 132) launch_dma_t<128, 128, 2>(a, tiles(128, 128), st);
-  else launch_dma_t<64, 64, 4>(a, tiles(64, 64), st);
+int launch_gemm_dma(const GemmArgs& a, const GemmTile& t, hipStream_t st) {   // the FAM_RING32 rows of the tile table (kernels.h)
+  const int r = gemm_family_launch<FAM_RING32>(a, t, [&](auto row, auto fl, auto epi, auto gather) {
+    constexpr GemmTile R = kGemmTiles[decltype(row)::value];
+    hipLaunchKernelGGL((gemm_dma_kernel<R.bm, R.bn, R.stages, decltype(gather)::value, decltype(fl)::value, decltype(epi)::value>), gemm_tile_grid(R, a), dim3(R.waves * 64), 0, st, a);
+  }, GemmTileSeq{});
+  if (r) return r;
   DPB_CHECK(hipGetLastError());
   return 0;
 }

@@ -305,78 +305,20 @@ __global__ __launch_bounds__(WAVES * 64) void gemm_ring64_kernel(GemmArgs p) {
   });
 }
 
-template <int BM, int BN, int S, int WAVES, int FL>
-static void launch_ring64_f(const GemmArgs& a, dim3 grid, hipStream_t st) {
-  switch (a.gather) {
-    case GATHER_NONE:
-      if constexpr (BN == 128) {                  // the fused GEGLU epilogues pair the two 64-column waves of a 128-column tile
-        if (a.epi == EPI_GEGLU_TAN) { hipLaunchKernelGGL((gemm_ring64_kernel<BM, BN, S, GATHER_NONE, WAVES, FL, EPI_GEGLU_TAN>), grid, dim3(WAVES * 64), 0, st, a); break; }
-        if (a.epi == EPI_GEGLU_ADJ) { hipLaunchKernelGGL((gemm_ring64_kernel<BM, BN, S, GATHER_NONE, WAVES, FL, EPI_GEGLU_ADJ>), grid, dim3(WAVES * 64), 0, st, a); break; }
-        if (a.epi == EPI_GEGLU_FWD) { hipLaunchKernelGGL((gemm_ring64_kernel<BM, BN, S, GATHER_NONE, WAVES, FL, EPI_GEGLU_FWD>), grid, dim3(WAVES * 64), 0, st, a); break; }
-      }
-      hipLaunchKernelGGL((gemm_ring64_kernel<BM, BN, S, GATHER_NONE, WAVES, FL>), grid, dim3(WAVES * 64), 0, st, a);
-      break;
-    case GATHER_CONV: hipLaunchKernelGGL((gemm_ring64_kernel<BM, BN, S, GATHER_CONV, WAVES, FL>), grid, dim3(WAVES * 64), 0, st, a); break;
-    case GATHER_CONVT: hipLaunchKernelGGL((gemm_ring64_kernel<BM, BN, S, GATHER_CONVT, WAVES, FL>), grid, dim3(WAVES * 64), 0, st, a); break;
-    default: hipLaunchKernelGGL((gemm_ring64_kernel<BM, BN, S, GATHER_UPCONV, WAVES, FL>), grid, dim3(WAVES * 64), 0, st, a); break;
-  }
-}
-template <int BM, int BN, int S, int WAVES = 4>
-static void launch_ring64_t(const GemmArgs& a, dim3 grid, hipStream_t st) {
-  if (a.fl) launch_ring64_f<BM, BN, S, WAVES, 1>(a, grid, st);
-  else launch_ring64_f<BM, BN, S, WAVES, 0>(a, grid, st);
-}
-
-// tile codes: 512 = 128x128 S3 (96 KiB, 1 block/CU), 513 = 256x128 S3 (144 KiB), 514 = 128x128 S4, 515 = 128x128 S2 (2 blocks/CU),
-// 516 = 256x128 S3 with 8 waves (64x64 wave tiles, one shared B tile), 517 = the same with S2 (96 KiB),
-// 518 = 256x256 S2 with 8 waves (64x128 wave tiles, 128 KiB ring: half the L2->LDS bytes per flop of 128x128; plain rows only).
+// The FAM_RING64 rows of the tile table (kernels.h) -- geometry, stages, waves, and which gather / epilogue variants of the kernel exist per tile:
+// 518, 520 and the half tiles restrict them so that the instantiations do not multiply.
 // (64x64 tiles on this ring for the small 1280^3 / 320x1280x1280 products: measured equal to the BK=32 64x64 ring within 0.3 % end to end --
 // those launches are latency-bound, not DMA-bound; removed.)
 // (320x128 / 320x64 tiles -- the M = 64 k rows of the 8x8-level layers at k = 5 in ONE tile, weight panel streamed once -- were built
 // and measured in round 2: one 4-wave block per CU is latency-bound, 47-52 us against 41 us for 128x128 S2 with split-K 8; removed.)
-int launch_gemm_ring64(const GemmArgs& a, int tile, hipStream_t st) {
-  const int sk = a.splitk > 1 ? a.splitk : 1;
-  const int Z = a.Z1 * a.Z2;
-  auto tiles = [&](int bm, int bn) { return dim3(((a.M + bm - 1) / bm) * ((a.N + bn - 1) / bn), Z, sk); };
-  if (tile == 513) launch_ring64_t<256, 128, 3>(a, tiles(256, 128), st);
-  else if (tile == 516) launch_ring64_t<256, 128, 3, 8>(a, tiles(256, 128), st);
-  else if (tile == 517) launch_ring64_t<256, 128, 2, 8>(a, tiles(256, 128), st);
-  else if (tile == 518) {
-    if (a.gather != GATHER_NONE) { set_error("gemm: the 256x256 ring tile takes plain-row operands only"); return -1; }
-    const dim3 g = tiles(256, 256);
-#define DPB_RING518(FLV, EPIV) hipLaunchKernelGGL((gemm_ring64_kernel<256, 256, 2, GATHER_NONE, 8, FLV, EPIV>), g, dim3(512), 0, st, a)
-    if (a.epi == EPI_GEGLU_TAN) { if (a.fl) DPB_RING518(1, EPI_GEGLU_TAN); else DPB_RING518(0, EPI_GEGLU_TAN); }
-    else if (a.epi == EPI_GEGLU_ADJ) { if (a.fl) DPB_RING518(1, EPI_GEGLU_ADJ); else DPB_RING518(0, EPI_GEGLU_ADJ); }
-    else if (a.epi == EPI_GEGLU_FWD) { if (a.fl) DPB_RING518(1, EPI_GEGLU_FWD); else DPB_RING518(0, EPI_GEGLU_FWD); }
-    else { if (a.fl) DPB_RING518(1, EPI_PLAIN); else DPB_RING518(0, EPI_PLAIN); }
-#undef DPB_RING518
-  }
-  else if (tile == 520) {                       // row-complete 128 x 320 tile with a fused LayerNorm epilogue (plain rows, N = 320, no split)
-    if (a.gather != GATHER_NONE || a.N != 320 || sk != 1 || (a.epi != EPI_LN_TAN && a.epi != EPI_LN_ADJ)) { set_error("gemm: tile 520 is the N = 320 LayerNorm-epilogue tile"); return -1; }
-    const dim3 g = tiles(128, 320);
-#define DPB_RING520(FLV, EPIV) hipLaunchKernelGGL((gemm_ring64_kernel<128, 320, 2, GATHER_NONE, 4, FLV, EPIV>), g, dim3(256), 0, st, a)
-    if (a.epi == EPI_LN_TAN) { if (a.fl) DPB_RING520(1, EPI_LN_TAN); else DPB_RING520(0, EPI_LN_TAN); }
-    else { if (a.fl) DPB_RING520(1, EPI_LN_ADJ); else DPB_RING520(0, EPI_LN_ADJ); }
-#undef DPB_RING520
-  }
-  else if (tile == 521 && a.epi == EPI_PLAIN && (a.gather == GATHER_CONV || a.gather == GATHER_CONVT)) {   // the same half tile as an implicit-GEMM convolution
-    const dim3 g = tiles(64, 128);
-    if (a.gather == GATHER_CONV) { if (a.fl) hipLaunchKernelGGL((gemm_ring64_kernel<64, 128, 3, GATHER_CONV, 4, 1, EPI_PLAIN>), g, dim3(256), 0, st, a); else hipLaunchKernelGGL((gemm_ring64_kernel<64, 128, 3, GATHER_CONV, 4, 0, EPI_PLAIN>), g, dim3(256), 0, st, a); }
-    else { if (a.fl) hipLaunchKernelGGL((gemm_ring64_kernel<64, 128, 3, GATHER_CONVT, 4, 1, EPI_PLAIN>), g, dim3(256), 0, st, a); else hipLaunchKernelGGL((gemm_ring64_kernel<64, 128, 3, GATHER_CONVT, 4, 0, EPI_PLAIN>), g, dim3(256), 0, st, a); }
-  }
-  else if (tile >= 521 && tile <= 523) {        // half tiles for the <= 256-tile launches of the 32x32 level (plain rows, plain epilogue): twice the blocks, 2-3 per CU
-    if (a.gather != GATHER_NONE || a.epi != EPI_PLAIN) { set_error("gemm: tile %d takes plain-row operands and the plain epilogue only", tile); return -1; }
-#define DPB_RINGH(BMV, BNV, SV) do { const dim3 g = tiles(BMV, BNV); \
-      if (a.fl) hipLaunchKernelGGL((gemm_ring64_kernel<BMV, BNV, SV, GATHER_NONE, 4, 1, EPI_PLAIN>), g, dim3(256), 0, st, a); \
-      else hipLaunchKernelGGL((gemm_ring64_kernel<BMV, BNV, SV, GATHER_NONE, 4, 0, EPI_PLAIN>), g, dim3(256), 0, st, a); } while (0)
-    if (tile == 521) DPB_RINGH(64, 128, 3);      // 72 KiB ring: 2 blocks per CU
-    else if (tile == 522) DPB_RINGH(64, 128, 2); // 48 KiB ring: 3 blocks per CU
-    else DPB_RINGH(128, 64, 3);
-#undef DPB_RINGH
-  }
-  else if (tile == 514) launch_ring64_t<128, 128, 4>(a, tiles(128, 128), st);
-  else if (tile == 515) launch_ring64_t<128, 128, 2>(a, tiles(128, 128), st);
-  else launch_ring64_t<128, 128, 3>(a, tiles(128, 128), st);
+int launch_gemm_ring64(const GemmArgs& a, const GemmTile& t, hipStream_t st) {
+  if ((t.flags & TILE_LN) && (a.N != t.bn || a.splitk > 1)) { set_error("gemm: tile %d is the row-complete N = %d LayerNorm-epilogue tile, unsplit", t.code, t.bn); return -1; }
+  const int r = gemm_family_launch<FAM_RING64>(a, t, [&](auto row, auto fl, auto epi, auto gather) {
+    constexpr GemmTile R = kGemmTiles[decltype(row)::value];
+    hipLaunchKernelGGL((gemm_ring64_kernel<R.bm, R.bn, R.stages, decltype(gather)::value, R.waves, decltype(fl)::value, decltype(epi)::value>), gemm_tile_grid(R, a),
+                       dim3(R.waves * 64), 0, st, a);
+  }, GemmTileSeq{});
+  if (r) return r;
   DPB_CHECK(hipGetLastError());
   return 0;
 }

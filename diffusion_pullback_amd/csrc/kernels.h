@@ -1,6 +1,8 @@
 // Host-side launch interface of the gfx950 kernels (internal; the public C-ABI is include/dpb.h).
 #pragma once
 #include <algorithm>
+#include <type_traits>
+#include <utility>
 
 #include "common.h"
 
@@ -46,36 +48,125 @@ struct GemmArgs {
   int fl = 0;                         // 16-bit flavour of the specialised kernels: 0 bf16, 1 f16 (filled in by launch_gemm)
   int order = 0;                      // block processing order per XCD: 0 A-major, 1 B-major (weight-heavy); filled in by launch_gemm
 };
+// ---- the tile table: ONE row per tile the library can launch.  Everything the host code knows about a tile -- its geometry, its codes, which
+// launcher and which kernel variants it has, how the profile labels it -- is read from its row; a new tile is a new row (and its kernel).
+enum GemmFamily { FAM_REG = 0, FAM_RING32, FAM_RING64, FAM_P8, FAM_WRES, FAM_HALO };   // gemm.hip | gemm_dma.hip | gemm_ring64.hip | gemm_p8.hip | gemm_wres.hip | gemm_halo.hip
+enum : unsigned {
+  TILE_CONV = 1,      // takes the forward / transposed gathers (GATHER_CONV, GATHER_CONVT), plain epilogue
+  TILE_UPCONV = 2,    // ... and the upsampling gather
+  TILE_CIN64 = 4,     // gathers whole 64-channel K tiles only (Cin % 64 == 0)
+  TILE_GEGLU = 8,     // built with the fused GEGLU epilogues (plain rows); the dispatch uses them on tiles of whole 128-column blocks only
+  TILE_LN = 16,       // the row-complete tile: built with the fused LayerNorm epilogues and nothing else; N = bn, selected by the epilogue, never forced
+  TILE_EPI_N256 = 32, // fused epilogues need N % 256 == 0
+  TILE_NOSPLIT = 64,  // one block per CU by construction: the heuristic never splits K (a forced split count is honoured)
+  TILE_NOSLAB = 128,  // no split-K path at all: one K range per block whatever is forced
+};
+enum GemmTileId { T_REG64 = 0, T_REG128, T_R32_S4, T_R32_S3, T_R32_S2, T_R32_TALL, T_R32_64, T_R32_64B, T_R64_S3, T_R64_TALL, T_R64_S4, T_R64_S2, T_R64_TALL8,
+                  T_R64_TALL8_S2, T_R64_256, T_R64_LN, T_R64_HALF, T_R64_HALF_S2, T_R64_HALFN, T_P8, T_WRES, T_HALO, GEMM_TILES, T_NONE = -1 };
+struct GemmTile {
+  int family;
+  int code;        // what gemm_plan / dpb_debug_gemm_plan report
+  int forced;      // what dpb_debug_set("gemm_tile") / DPB_GEMM_OVERRIDE accept (0: not forceable)
+  int bm, bn, stages, waves;
+  int kind;        // profile kind of dpb_engine_profile_read (include/dpb.h)
+  unsigned flags;
+  int substitute;  // the row a forced code falls back to for a product this tile does not take (T_NONE: forced unconditionally)
+};
+constexpr unsigned TILE_ANY = TILE_CONV | TILE_UPCONV;
+inline constexpr GemmTile kGemmTiles[GEMM_TILES] = {
+    //  family     code forced  bm   bn   S  waves kind  flags                                                          substitute
+    {FAM_REG,      64,  64,    64,  64,  0, 4,    0,    TILE_ANY,                                                      T_NONE},   // register-staged (all dtypes, dual operand pairs)
+    {FAM_REG,      128, 128,   128, 128, 0, 4,    1,    TILE_ANY,                                                      T_NONE},
+    {FAM_RING32,   128, 129,   128, 128, 4, 4,    2,    TILE_ANY | TILE_GEGLU,                                         T_NONE},
+    {FAM_RING32,   130, 131,   128, 128, 3, 4,    2,    TILE_ANY | TILE_GEGLU,                                         T_NONE},   // 48 KiB ring -> 3 blocks/CU
+    {FAM_RING32,   132, 133,   128, 128, 2, 4,    2,    TILE_ANY | TILE_GEGLU,                                         T_NONE},
+    {FAM_RING32,   256, 257,   256, 128, 3, 4,    2,    TILE_ANY | TILE_GEGLU,                                         T_NONE},   // wave tile 128x64, 72 KiB ring
+    {FAM_RING32,   64,  65,    64,  64,  4, 4,    3,    TILE_ANY | TILE_GEGLU,                                         T_NONE},   // (its GEGLU variants are built, never dispatched)
+    {FAM_RING32,   66,  67,    64,  64,  4, 4,    3,    TILE_ANY | TILE_GEGLU,                                         T_NONE},   // an alias of 65: the same launch under its own codes
+    {FAM_RING64,   512, 512,   128, 128, 3, 4,    4,    TILE_ANY | TILE_GEGLU,                                         T_NONE},   // 96 KiB ring, 1 block/CU
+    {FAM_RING64,   513, 513,   256, 128, 3, 4,    4,    TILE_ANY | TILE_GEGLU,                                         T_NONE},   // 144 KiB
+    {FAM_RING64,   514, 514,   128, 128, 4, 4,    4,    TILE_ANY | TILE_GEGLU,                                         T_NONE},
+    {FAM_RING64,   515, 515,   128, 128, 2, 4,    4,    TILE_ANY | TILE_GEGLU,                                         T_NONE},   // 2 blocks/CU: the default ring
+    {FAM_RING64,   516, 516,   256, 128, 3, 8,    4,    TILE_ANY | TILE_GEGLU,                                         T_NONE},   // 64x64 wave tiles, one shared B tile
+    {FAM_RING64,   517, 517,   256, 128, 2, 8,    4,    TILE_ANY | TILE_GEGLU,                                         T_NONE},   // 96 KiB
+    {FAM_RING64,   518, 518,   256, 256, 2, 8,    6,    TILE_GEGLU | TILE_EPI_N256 | TILE_NOSPLIT,                     T_R64_S2}, // 64x128 wave tiles, 128 KiB ring: half the L2->LDS bytes per flop of 128x128; plain rows only
+    {FAM_RING64,   520, 0,     128, 320, 2, 4,    4,    TILE_LN | TILE_NOSLAB,                                         T_NONE},   // row-complete N = 320 tile, fused LayerNorm epilogue
+    {FAM_RING64,   521, 521,   64,  128, 3, 4,    4,    TILE_CONV,                                                     T_R64_S2}, // half tiles for launches of <= 256 tiles: 72 KiB ring, 2 blocks/CU (also as an implicit-GEMM convolution)
+    {FAM_RING64,   522, 522,   64,  128, 2, 4,    4,    0,                                                             T_R64_S2}, // 48 KiB ring: 3 blocks/CU
+    {FAM_RING64,   523, 523,   128, 64,  3, 4,    4,    0,                                                             T_R64_S2},
+    {FAM_P8,       530, 530,   256, 256, 2, 8,    11,   TILE_ANY | TILE_CIN64 | TILE_GEGLU | TILE_EPI_N256 | TILE_NOSPLIT, T_R64_S2}, // 8-phase ping-pong loop, 256x256x64
+    {FAM_WRES,     540, 540,   32,  320, 0, 5,    12,   TILE_NOSLAB,                                                   T_R64_S2}, // weights-resident streaming: 32-row tiles past a resident 320-column weight slice (gemm_wres_supported)
+    {FAM_HALO,     600, 600,   256, 128, 0, 8,    5,    TILE_CONV | TILE_CIN64,                                        T_NONE},   // halo-tile 3x3 convolution (conv_halo_supported)
+};
+constexpr const GemmTile* gemm_tile_forced(int forced) {   // the lookup by code: the forced codes are the unique ones (64 / 128 name a register-staged AND a ring tile as plan codes)
+  for (const GemmTile& t : kGemmTiles)
+    if (forced && t.forced == forced) return &t;
+  return nullptr;
+}
+constexpr int gemm_plan_kind(const GemmTile& t) { return t.family == FAM_REG ? (t.bm == 128) : t.family == FAM_HALO ? 3 : 2; }
+// which (gather, epilogue) variants of a tile's kernel are built -- the launchers instantiate exactly these, the dispatch never plans another
+constexpr bool gemm_tile_builds(const GemmTile& t, int gather, int epi) {
+  if (gather == GATHER_UPCONV ? !(t.flags & TILE_UPCONV) : (gather != GATHER_NONE && !(t.flags & TILE_CONV))) return false;
+  if (epi == EPI_PLAIN) return !(t.flags & TILE_LN);
+  if (gather != GATHER_NONE) return false;
+  return (t.flags & ((epi == EPI_LN_TAN || epi == EPI_LN_ADJ) ? TILE_LN : TILE_GEGLU)) != 0;
+}
+inline long gemm_tile_count(const GemmTile& t, const GemmArgs& a) { return (long)((a.M + t.bm - 1) / t.bm) * ((a.N + t.bn - 1) / t.bn) * a.Z1 * a.Z2; }
+inline dim3 gemm_tile_grid(const GemmTile& t, const GemmArgs& a) { return dim3(((a.M + t.bm - 1) / t.bm) * ((a.N + t.bn - 1) / t.bn), a.Z1 * a.Z2, a.splitk > 1 ? a.splitk : 1); }
+// The launchers of the ring families: runs launch(row, fl, epi, gather) -- four std::integral_constant tags: the index of `t` in the table and the
+// (GemmArgs::fl, epi, gather) of `a` -- if `t` is a row of family FAM and that variant of its kernel is built; an error otherwise.
+template <int V> using GemmTag = std::integral_constant<int, V>;
+template <int... Vs, typename F>
+int gemm_tag_switch(int v, F&& f) {   // f(GemmTag<V>{}) for the V of Vs... that equals v; -1 if none does
+  int r = -1;
+  (void)((v == Vs && ((r = f(GemmTag<Vs>{})), true)) || ...);
+  return r;
+}
+void gemm_variant_error(const GemmTile& t, const GemmArgs& a);
+template <int FAM, typename F, int... Is>
+int gemm_family_launch(const GemmArgs& a, const GemmTile& t, F&& launch, std::integer_sequence<int, Is...>) {
+  const int r = gemm_tag_switch<Is...>((int)(&t - kGemmTiles), [&](auto row) {
+    return gemm_tag_switch<0, 1>(a.fl, [&](auto fl) {
+      return gemm_tag_switch<EPI_PLAIN, EPI_GEGLU_TAN, EPI_GEGLU_ADJ, EPI_LN_TAN, EPI_LN_ADJ, EPI_GEGLU_FWD>(a.epi, [&](auto epi) {
+        return gemm_tag_switch<GATHER_NONE, GATHER_CONV, GATHER_CONVT, GATHER_UPCONV>(a.gather, [&](auto gather) {
+          constexpr GemmTile R = kGemmTiles[decltype(row)::value];
+          if constexpr (R.family == FAM && gemm_tile_builds(R, decltype(gather)::value, decltype(epi)::value)) { launch(row, fl, epi, gather); return 0; }
+          else return -1;
+        });
+      });
+    });
+  });
+  if (r) gemm_variant_error(t, a);
+  return r;
+}
+using GemmTileSeq = std::make_integer_sequence<int, GEMM_TILES>;
+
+// The launch plan of one product: its tile row (nullptr: refused, dpb_last_error says why) and K split.  kind / tile: what dpb_debug_gemm_plan reports.
+struct GemmPlan { int kind, tile, splitk; const GemmTile* row; };   // kind: gemm_plan_kind(*row), -1 error; tile: row->code
 // *launches: kernels enqueued (1, or 2 with splitk_reduce_kernel).  `pending` != nullptr: if the launch is split over K and its epilogue is plain
 // (one batch entry, alpha 1, no bias / row bias / accumulate, dense rows), the reduce kernel is NOT launched -- *pending receives the prepared
 // arguments (pending->splitk > 1) and the caller either hands the slabs to a consumer that reduces them itself (SlabSrc, norm.hip) or calls
-// launch_gemm_reduce; otherwise pending->splitk is set to 1.
-struct GemmPlan { int kind, tile, splitk; };   // kind: 0 / 1 register-staged 64x64 / 128x128, 2 LDS ring (tile = its code), 3 halo-tile convolution; -1 error
-int launch_gemm(int dtype, const GemmArgs& a, hipStream_t st, int* launches = nullptr, GemmArgs* pending = nullptr);
+// launch_gemm_reduce; otherwise pending->splitk is set to 1.  `plan`: the gemm_plan of these arguments if the caller already asked for it.
+int launch_gemm(int dtype, const GemmArgs& a, hipStream_t st, int* launches = nullptr, GemmArgs* pending = nullptr, const GemmPlan* plan = nullptr);
 int launch_gemm_reduce(int dtype, const GemmArgs& pending, hipStream_t st);
-GemmPlan gemm_plan(int dtype, const GemmArgs& a);   // host-only: the kernel launch_gemm picks, with its K split (clamped to the slab scratch)
-int gemm_uses_big_tile(int dtype, const GemmArgs& a);
-void gemm_debug_set(int tile, int splitk, int kch);
-int gemm_kch(const GemmArgs& a);
-int launch_gemm_dma(const GemmArgs& a, int tile, hipStream_t st);   // bf16, single operand pair, no split-K (gemm_dma.hip); tile 128 | 64 | 66 (64 with a 6-stage ring)
-int launch_gemm_ring64(const GemmArgs& a, int tile, hipStream_t st);   // BK = 64 ring (gemm_ring64.hip); tile 512 | 513 | 514 | 515
+GemmPlan gemm_plan(int dtype, const GemmArgs& a);   // host-only: the tile launch_gemm picks, with its K split (clamped to the slab scratch)
+void gemm_debug_set(int tile, int splitk, int kch);   // tuning overrides for micro-benchmarks (0 = heuristic): forced code, split count, K chunks of the 64x64 register-staged tile
+int launch_gemm_dma(const GemmArgs& a, const GemmTile& t, hipStream_t st);      // BK = 32 LDS ring, 16-bit, single operand pair (gemm_dma.hip): the FAM_RING32 rows
+int launch_gemm_ring64(const GemmArgs& a, const GemmTile& t, hipStream_t st);   // BK = 64 ring (gemm_ring64.hip): the FAM_RING64 rows
 bool gemm_p8_fits32(const GemmArgs& a);                                // its 32-bit element offsets reach every operand row
-int launch_gemm_p8(const GemmArgs& a, int tile, hipStream_t st);      // 8-phase ping-pong loop (gemm_p8.hip); tile 530 = 256x256x64, 8 waves
+int launch_gemm_p8(const GemmArgs& a, int tile, hipStream_t st);      // 8-phase ping-pong loop (gemm_p8.hip): the FAM_P8 row, by its code
 int conv_halo_supported(const GemmArgs& a);                        // 3x3 stride-1 convolution in halo-tile form (gemm_halo.hip)
 int launch_conv_halo(const GemmArgs& a, hipStream_t st);
 void conv_halo_debug_loop(int on);   // 1 (default): the 8-phase main loop of the halo convolution; 0: the ring loop, bitwise A/B
-int gemm_uses_halo(int dtype, const GemmArgs& a);
 int gemm_epi_supported(int dtype, const GemmArgs& a);   // can this launch take GemmArgs::epi != EPI_PLAIN?
-int gemm_uses_dma(int dtype, const GemmArgs& a);   // 0 = register-staged kernel, else the tile code for launch_gemm_dma
 void gemm_debug_dma_auto(int on);
 void gn_debug_deterministic(int on);
 int gn_deterministic();
-bool gemm_wres_supported(int dtype, const GemmArgs& a);                // weights-resident streaming kernel (gemm_wres.hip, tile code 540): K = 320, N % 320 == 0, plain epilogue
+bool gemm_wres_supported(int dtype, const GemmArgs& a);                // weights-resident streaming kernel (gemm_wres.hip): K = 320, N % 320 == 0, plain epilogue
 int launch_gemm_wres(const GemmArgs& a, hipStream_t st);
 void gemm_debug_wres(int on);   // 1 (default): the dispatch may pick the weights-resident kernel; 0: round-5 dispatch, bitwise A/B
 void gemm_debug_p8(int on);     // 1 (default): the dispatch may pick the 8-phase tile; 0: round-4 dispatch (rings / halo kernel), bitwise A/B
 void gemm_debug_order(int o);   // -1 heuristic, 0 A-major, 1 B-major
-int gemm_pick_splitk_dma(const GemmArgs& a, int tile);   // tuning overrides for micro-benchmarks (0 = heuristic)   // 1: 128x128 tile instantiation, 0: 64x64
 
 // ---------------------------------------------------------------- normalisation
 enum { MODE_PRIMAL = 0, MODE_TANGENT = 1, MODE_ADJOINT = 2 };

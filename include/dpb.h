@@ -245,7 +245,7 @@ int dpb_embed_tokens(const int32_t* ids, const void* tok_table, const void* pos_
 int dpb_engine_stats(const dpb_engine* e, int64_t* launches, double* gemm_flops, double* gemm_bytes);
 /* Measurement aid (bench.py roofline leg, never on in a timed region): bracket every GEMM launch with HIP
  * events on the engine's stream; _read synchronises and sums the launches of one GEMM kernel kind: count, total
- * milliseconds, algorithmic flops.  kind: 0 register-staged 64x64, 1 register-staged 128x128, 2 BK=32 ring 128x128 /
+ * milliseconds, algorithmic flops.  kind (for products: the `kind` column of the tile table, kernels.h): 0 register-staged 64x64, 1 register-staged 128x128, 2 BK=32 ring 128x128 /
  * 256x128, 3 BK=32 ring 64x64, 4 BK=64 ring with 128-column tiles (gemm_ring64.hip), 5 halo-tile 3x3 convolution (gemm_halo.hip), 6 BK=64 ring
  * with the 256x256 tile, 11 the 8-phase 256x256 tile (gemm_p8.hip: two wave groups alternating between load and matrix segments, counted vmcnt), 12 the
  * weights-resident streaming kernel of the K = 320 linear layers (gemm_wres.hip: weight slice in registers, activation rows streamed through an LDS ring);
@@ -262,9 +262,9 @@ int dpb_engine_profile_dump(dpb_engine* e, const char* csv_path);
  * this returns that correction so that the raw bracket times can be reconstructed (raw = reported + overhead per launch). */
 int dpb_engine_profile_overhead(const dpb_engine* e, double* bracket_overhead_ms);
 /* Tuning overrides for micro-benchmarks and the bitwise kernel-equivalence tests (0 / -1 = heuristic): "gemm_tile"
- * (64, 128: register-staged; 129, 131, 133, 257, 65, 67: BK=32 rings; 512..518: BK=64 rings, 518 = 256x256 tile for plain-row operands, 530 = the 8-phase 256x256 tile (gemm_p8.hip), 540 = the weights-resident streaming kernel (gemm_wres.hip; products it does not take fall back to 515), 521 / 522 / 523 =
- * half tiles 64x128 (3 / 2 stages) and 128x64 for plain-row operands;
- * 600: halo-tile 3x3 convolution), "gemm_splitk" (n), "gemm_kch", "p8" (1, default: the dispatch may pick the 8-phase tile; 0 = the ring / halo dispatch of round 4), "wres" (1, default: K = 320 / N % 320 == 0 plain products of >= 8192 rows go to the weights-resident kernel; 0 = the round-5 dispatch; bitwise equal), "halo_loop" (1, default: the halo-tile convolution runs its 8-phase main loop; 0 = its ring loop, also DPB_HALO_LOOP=0; bitwise equal), "gemm_dma_auto" (0|1), "gemm_order" (-1 | 0 A-major | 1 B-major block
+ * (the forced code of one row of the tile table kGemmTiles in diffusion_pullback_amd/csrc/kernels.h -- the ONE list of every tile the library launches:
+ * family, plan code, forced code, block geometry, stages, waves, profile kind, capabilities, and the substitute row that runs a product the forced tile
+ * does not take; a value that names no row leaves the heuristic in charge, with the halo-tile convolution off), "gemm_splitk" (n), "gemm_kch", "p8" (1, default: the dispatch may pick the 8-phase tile; 0 = the ring / halo dispatch of round 4), "wres" (1, default: K = 320 / N % 320 == 0 plain products go to the weights-resident kernel from 49 152 rows (N = 320) / 147 456 rows (wider N) on; 0 = the round-5 dispatch; bitwise equal), "halo_loop" (1, default: the halo-tile convolution runs its 8-phase main loop; 0 = its ring loop, also DPB_HALO_LOOP=0; bitwise equal), "gemm_dma_auto" (0|1), "gemm_order" (-1 | 0 A-major | 1 B-major block
  * order per XCD), "gn_deterministic" (1, default: GroupNorm statistics of the two-pass kernels reduced in a fixed order -> bitwise
  * reproducible runs; 0 = the round-1 atomic statistics, A/B only), "graph_iterate" (0|1: dpb_pullback_iterate replays a captured hipGraph on a non-default stream;
  * measured equal to eager launches, default 0), "attn_shared" (2, default: shared-probability key-major adjoint of the head-dim-40
@@ -284,8 +284,8 @@ int dpb_debug_set(const char* key, int value);
 
 /* Host-only (no GPU work): the launch plan the GEMM dispatch picks for a product C[M][N] = A[M][K] B[N][K]^T -- plain rows (conv_hw = 0) or
  * a 3x3 / stride 1 / pad 1 convolution on conv_hw x conv_hw images of conv_cin channels (K = 9 conv_cin) -- with `slab_bytes` of split-K
- * scratch.  kind: 0 / 1 register-staged 64x64 / 128x128 tile, 2 asynchronous LDS ring (tile = its code, see dpb_debug_set), 3 halo-tile
- * convolution; epilogue 0 plain, 1 / 2 fused GEGLU tangent / adjoint.  splitk x M x N x 4 bytes never exceeds slab_bytes.  Lets the
+ * scratch.  kind: 0 / 1 register-staged 64x64 / 128x128 tile, 2 asynchronous kernel (LDS rings, 8-phase tile, weights-resident kernel), 3 halo-tile
+ * convolution; tile: the plan code of its row in the tile table (kernels.h; see dpb_debug_set); epilogue 0 plain, 1 / 2 / 5 fused GEGLU tangent / adjoint / forward.  splitk x M x N x 4 bytes never exceeds slab_bytes.  Lets the
  * dispatch rules be tested on a machine without a GPU (tests/test_host_logic.py). */
 int dpb_debug_gemm_plan(int dtype, int M, int N, int K, int conv_hw, int conv_cin, int epilogue, int64_t slab_bytes, int* kind, int* tile,
                         int* splitk);

@@ -297,6 +297,55 @@ def test_gemm_override_environment_changes_the_plan_of_the_named_shape_only():
     assert forced[3][2] == 1                                               # and with 1 MB of scratch nothing splits
 
 
+def _plan_sweep_module():
+    import importlib.util
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_golden_gemm_plans.py")
+    spec = importlib.util.spec_from_file_location("make_golden_gemm_plans", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_gemm_plans_reproduce_the_recorded_dispatch():
+    """The dispatch is pinned entry for entry: tests/golden/gemm_plans.npz holds (return code, kind, tile, splitk) of dpb_debug_gemm_plan over the
+    sweep of tests/golden/make_golden_gemm_plans.py -- the primary grid under every epilogue and three slab sizes, a ragged set, every dpb_debug_set
+    dispatch switch and (in child processes) every dispatch environment switch -- recorded from the commit named inside the file.  A refactor of
+    the dispatch reproduces all of them; a deliberate rule change regenerates the file."""
+    import numpy as np
+    mod = _plan_sweep_module()
+    fix = np.load(mod.OUT)
+    assert str(fix["sweep"]) == mod.sweep_hash(), "the sweep changed since the fixture was recorded: regenerate it from the commit to be kept"
+    want = fix["plans"].astype(np.int64)
+    got = np.asarray(mod.record(), dtype=np.int64)
+    assert got.shape == want.shape and want.shape[0] > 100000, (got.shape, want.shape)
+    bad = np.flatnonzero((got != want).any(axis=1))
+    assert bad.size == 0, (f"{bad.size} of {want.shape[0]} plans differ from commit {fix['commit']}; first: " +
+                           "; ".join(f"{mod.describe(int(i))}: recorded {want[i].tolist()} got {got[i].tolist()}" for i in bad[:5]))
+
+
+def test_gemm_tile_table_forced_codes_report_their_plan_code_and_family_kind():
+    """Every forced code of dpb_debug_set("gemm_tile") (include/dpb.h), given a product its tile takes, is planned as that tile: the reported tile is
+    the row's plan code (the BK = 32 rings report code - 1) and the plan kind follows the family -- 0 / 1 register-staged, 2 ring / 8-phase /
+    weights-resident, 3 halo-tile convolution."""
+    import ctypes as C
+    from diffusion_pullback_amd import lib as L
+    lib = L.load()
+    # forced code -> (plan code, plan kind); 520 (the fused-LayerNorm tile) is not a forced code: the epilogue selects it
+    rows = {64: (64, 0), 128: (128, 1), 129: (128, 2), 131: (130, 2), 133: (132, 2), 257: (256, 2), 65: (64, 2), 67: (66, 2), 600: (600, 3), 530: (530, 2),
+            540: (540, 2), **{c: (c, 2) for c in (512, 513, 514, 515, 516, 517, 518, 521, 522, 523)}}
+    k, t, s = C.c_int(), C.c_int(), C.c_int()
+    try:
+        for code, (tile, kind) in rows.items():
+            L.check(lib.dpb_debug_set(b"gemm_tile", code))
+            dt = L.DPB_F32 if code == 128 else L.DPB_BF16                # a plain 256 x 320 x 320 product: every tile but the halo convolution takes it
+            q = (dt, 256, 128, 576, 16, 64) if code == 600 else (dt, 256, 320, 320, 0, 0)
+            L.check(lib.dpb_debug_gemm_plan(*q, 0, 64 << 20, C.byref(k), C.byref(t), C.byref(s)))
+            assert (t.value, k.value) == (tile, kind) and s.value >= 1, (code, k.value, t.value, s.value)
+    finally:
+        L.check(lib.dpb_debug_set(b"gemm_tile", 0))
+
+
 def test_bench_names_the_baseline_config_it_measures():
     """bench.py's config.workload: every --op down/up run is BASELINE configs[4] with its tap, k = 10 / edit ctx / strong mode is configs[3],
     DDPM is configs[1], the default is configs[2] (r02 review: 16 sweep lines were labelled configs[2])."""
