@@ -150,11 +150,11 @@ static int pick_fwd(T* S, long nrows, int Lk, int ld, int causal_Lq, hipStream_t
   constexpr int CH = TT<T>::CH;
   int need = (ld / CH + 63) / 64;
   dim3 grid((unsigned)((nrows + 3) / 4)), blk(256);
-  if (need <= 1) hipLaunchKernelGGL((softmax_fwd_kernel<T, 1>), grid, blk, 0, st, S, nrows, Lk, ld, causal_Lq);
-  else if (need <= 2) hipLaunchKernelGGL((softmax_fwd_kernel<T, 2>), grid, blk, 0, st, S, nrows, Lk, ld, causal_Lq);
-  else if (need <= 4) hipLaunchKernelGGL((softmax_fwd_kernel<T, 4>), grid, blk, 0, st, S, nrows, Lk, ld, causal_Lq);
-  else if (need <= 8) hipLaunchKernelGGL((softmax_fwd_kernel<T, 8>), grid, blk, 0, st, S, nrows, Lk, ld, causal_Lq);
-  else if (need <= 16) hipLaunchKernelGGL((softmax_fwd_kernel<T, 16>), grid, blk, 0, st, S, nrows, Lk, ld, causal_Lq);
+  if (need <= 1) DPB_LAUNCH((softmax_fwd_kernel<T, 1>), grid, blk, 0, st, S, nrows, Lk, ld, causal_Lq);
+  else if (need <= 2) DPB_LAUNCH((softmax_fwd_kernel<T, 2>), grid, blk, 0, st, S, nrows, Lk, ld, causal_Lq);
+  else if (need <= 4) DPB_LAUNCH((softmax_fwd_kernel<T, 4>), grid, blk, 0, st, S, nrows, Lk, ld, causal_Lq);
+  else if (need <= 8) DPB_LAUNCH((softmax_fwd_kernel<T, 8>), grid, blk, 0, st, S, nrows, Lk, ld, causal_Lq);
+  else if (need <= 16) DPB_LAUNCH((softmax_fwd_kernel<T, 16>), grid, blk, 0, st, S, nrows, Lk, ld, causal_Lq);
   else { set_error("softmax: row length %d too long", ld); return -1; }
   DPB_CHECK(hipGetLastError());
   return 0;
@@ -171,11 +171,11 @@ static int pick_jvp(const T* P, T* dS, float* D, long nrows, int Z2, int kps, in
   constexpr int CH = TT<T>::CH;
   int need = (ld / CH + 63) / 64;
   dim3 grid((unsigned)((nrows + 3) / 4)), blk(256);
-  if (need <= 1) hipLaunchKernelGGL((softmax_jvp_kernel<T, 1>), grid, blk, 0, st, P, dS, D, nrows, Z2, kps, Lq, Lk, ld);
-  else if (need <= 2) hipLaunchKernelGGL((softmax_jvp_kernel<T, 2>), grid, blk, 0, st, P, dS, D, nrows, Z2, kps, Lq, Lk, ld);
-  else if (need <= 4) hipLaunchKernelGGL((softmax_jvp_kernel<T, 4>), grid, blk, 0, st, P, dS, D, nrows, Z2, kps, Lq, Lk, ld);
-  else if (need <= 8) hipLaunchKernelGGL((softmax_jvp_kernel<T, 8>), grid, blk, 0, st, P, dS, D, nrows, Z2, kps, Lq, Lk, ld);
-  else if (need <= 16) hipLaunchKernelGGL((softmax_jvp_kernel<T, 16>), grid, blk, 0, st, P, dS, D, nrows, Z2, kps, Lq, Lk, ld);
+  if (need <= 1) DPB_LAUNCH((softmax_jvp_kernel<T, 1>), grid, blk, 0, st, P, dS, D, nrows, Z2, kps, Lq, Lk, ld);
+  else if (need <= 2) DPB_LAUNCH((softmax_jvp_kernel<T, 2>), grid, blk, 0, st, P, dS, D, nrows, Z2, kps, Lq, Lk, ld);
+  else if (need <= 4) DPB_LAUNCH((softmax_jvp_kernel<T, 4>), grid, blk, 0, st, P, dS, D, nrows, Z2, kps, Lq, Lk, ld);
+  else if (need <= 8) DPB_LAUNCH((softmax_jvp_kernel<T, 8>), grid, blk, 0, st, P, dS, D, nrows, Z2, kps, Lq, Lk, ld);
+  else if (need <= 16) DPB_LAUNCH((softmax_jvp_kernel<T, 16>), grid, blk, 0, st, P, dS, D, nrows, Z2, kps, Lq, Lk, ld);
   else { set_error("softmax: row length %d too long", ld); return -1; }
   DPB_CHECK(hipGetLastError());
   return 0;
@@ -191,7 +191,7 @@ int launch_softmax_adjT(int dtype, const void* PT, void* gPT, const float* D, lo
                         hipStream_t st) {
   long total = Z * Lk * (ld / dt_chunk(dtype));
   unsigned grid = (unsigned)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-  DPB_DISPATCH_STMT(dtype, T, hipLaunchKernelGGL((softmax_adjT_kernel<T>), dim3(grid), dim3(256), 0, st, (const T*)PT, (T*)gPT, D, Z, Z2, kps, Lk, Lq, ld));
+  DPB_DISPATCH_STMT(dtype, T, DPB_LAUNCH((softmax_adjT_kernel<T>), dim3(grid), dim3(256), 0, st, (const T*)PT, (T*)gPT, D, Z, Z2, kps, Lk, Lq, ld));
   DPB_CHECK(hipGetLastError());
   return 0;
 }
@@ -200,9 +200,9 @@ int launch_transpose(int dtype, const void* in, void* out, int Z1, int Z2, long 
                      long outZstride, hipStream_t st) {
   dim3 grid((ldout + 31) / 32, (Ccols + 31) / 32, Z1 * Z2);
   if (dtype == DT_F32)   // pure data movement: the two 16-bit types share the bf16 instantiation
-    hipLaunchKernelGGL((transpose_kernel<float>), grid, dim3(256), 0, st, (const float*)in, (float*)out, Z2, s1, s2, R, Ccols, ldin, ldout, outZstride);
+    DPB_LAUNCH((transpose_kernel<float>), grid, dim3(256), 0, st, (const float*)in, (float*)out, Z2, s1, s2, R, Ccols, ldin, ldout, outZstride);
   else
-    hipLaunchKernelGGL((transpose_kernel<bf16>), grid, dim3(256), 0, st, (const bf16*)in, (bf16*)out, Z2, s1, s2, R, Ccols, ldin, ldout, outZstride);
+    DPB_LAUNCH((transpose_kernel<bf16>), grid, dim3(256), 0, st, (const bf16*)in, (bf16*)out, Z2, s1, s2, R, Ccols, ldin, ldout, outZstride);
   DPB_CHECK(hipGetLastError());
   return 0;
 }

@@ -1197,49 +1197,15 @@ int launch_attn_cross(const CrossAttnArgs& f, int nt, hipStream_t st) {
   const int waves = f.L >= 128 ? 4 : f.L / 32;
   dim3 grid(f.L / (waves * 32), nt * f.H);
   if (!head_dim_ok(f.d)) { set_error("cross attention: head dim %d unsupported", f.d); return -1; }
-  DPB_ATT_DISPATCH(f.d, f.fl, hipLaunchKernelGGL((attn_cross_kernel<D, FL>), grid, dim3(waves * 64), 0, st, a));
+  DPB_ATT_DISPATCH(f.d, f.fl, DPB_LAUNCH((attn_cross_kernel<D, FL>), grid, dim3(waves * 64), 0, st, a));
   DPB_CHECK(hipGetLastError());
   return 0;
-}
-
-// row statistics of the primal probabilities from the materialised scaled scores S (before softmax):
-// one wave per row; stats[row] = (max, 1 / sum exp(S - max))
-template <int FL>
-__global__ __launch_bounds__(256) void row_stats_kernel(const bf16* S, float* stats, long nrows, int Lk, int ld) {
-  const int lane = threadIdx.x & 63;
-  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= nrows) return;
-  const bf16* sp = S + row * ld;
-  float m = -INFINITY;
-  for (int c = lane * 8; c < Lk; c += 512) {
-    float v[8];
-    H16<FL>::load8(sp + c, v);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) if (c + e < Lk) m = fmaxf(m, v[e]);
-  }
-  m = wave_max(m);
-  float s = 0.f;
-  for (int c = lane * 8; c < Lk; c += 512) {
-    float v[8];
-    H16<FL>::load8(sp + c, v);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) if (c + e < Lk) s += __expf(v[e] - m);
-  }
-  s = wave_sum(s);
-  if (lane == 0) { stats[2 * row] = m; stats[2 * row + 1] = 1.f / s; }
 }
 
 int fused_attention_supported(int dtype, int d, int L, int kv_const) {
   // L >= 256 in whole blocks; or the one-stage case L = 64 at head dim 160 (the 8x8 level of SD-1.x: one 64-key stage, half of the block's waves idle) --
   // three launches per iteration instead of the materialised path's ~19 tiny ones
   return dtype != DT_F32 && !kv_const && head_dim_ok(d) && ((L >= 256 && L % (att_waves(d) * 32) == 0) || (d == 160 && L == 64));
-}
-
-int launch_row_stats(int fl, const void* S, float* stats, long nrows, int Lk, int ld, hipStream_t st) {
-  if (fl) hipLaunchKernelGGL((row_stats_kernel<1>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, (const bf16*)S, stats, nrows, Lk, ld);
-  else hipLaunchKernelGGL((row_stats_kernel<0>), dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, st, (const bf16*)S, stats, nrows, Lk, ld);
-  DPB_CHECK(hipGetLastError());
-  return 0;
 }
 
 static int attn_xcd_on() { static int on = getenv("DPB_ATTN_XCD") ? atoi(getenv("DPB_ATTN_XCD")) : 0; return on; }
@@ -1265,13 +1231,13 @@ int launch_attn_fwd_fused(const FusedAttnArgs& f, int batch, void* O, float* sta
   static const int fwd4 = getenv("DPB_ATTN_FWD4") ? atoi(getenv("DPB_ATTN_FWD4")) : 1;   // tuning switch
   if (fwd4 && att_waves(f.d) == 8 && f.L % 128 == 0 && f.L >= 256 && (long)grid.x * grid.y < 256) {
     dim3 g4(f.L / 128, batch * f.H);
-    if (f.d == 40) { if (f.fl) hipLaunchKernelGGL((attn_fwd_kernel<40, 1, 4>), g4, dim3(256), 0, st, a, (bf16*)O, stats); else hipLaunchKernelGGL((attn_fwd_kernel<40, 0, 4>), g4, dim3(256), 0, st, a, (bf16*)O, stats); }
-    else if (f.d == 64) { if (f.fl) hipLaunchKernelGGL((attn_fwd_kernel<64, 1, 4>), g4, dim3(256), 0, st, a, (bf16*)O, stats); else hipLaunchKernelGGL((attn_fwd_kernel<64, 0, 4>), g4, dim3(256), 0, st, a, (bf16*)O, stats); }
-    else { if (f.fl) hipLaunchKernelGGL((attn_fwd_kernel<80, 1, 4>), g4, dim3(256), 0, st, a, (bf16*)O, stats); else hipLaunchKernelGGL((attn_fwd_kernel<80, 0, 4>), g4, dim3(256), 0, st, a, (bf16*)O, stats); }
+    if (f.d == 40) { if (f.fl) DPB_LAUNCH((attn_fwd_kernel<40, 1, 4>), g4, dim3(256), 0, st, a, (bf16*)O, stats); else DPB_LAUNCH((attn_fwd_kernel<40, 0, 4>), g4, dim3(256), 0, st, a, (bf16*)O, stats); }
+    else if (f.d == 64) { if (f.fl) DPB_LAUNCH((attn_fwd_kernel<64, 1, 4>), g4, dim3(256), 0, st, a, (bf16*)O, stats); else DPB_LAUNCH((attn_fwd_kernel<64, 0, 4>), g4, dim3(256), 0, st, a, (bf16*)O, stats); }
+    else { if (f.fl) DPB_LAUNCH((attn_fwd_kernel<80, 1, 4>), g4, dim3(256), 0, st, a, (bf16*)O, stats); else DPB_LAUNCH((attn_fwd_kernel<80, 0, 4>), g4, dim3(256), 0, st, a, (bf16*)O, stats); }
     DPB_CHECK(hipGetLastError());
     return 0;
   }
-  DPB_ATT_DISPATCH(f.d, f.fl, hipLaunchKernelGGL((attn_fwd_kernel<D, FL>), grid, dim3(att_waves(D) * 64), 0, st, a, (bf16*)O, stats));
+  DPB_ATT_DISPATCH(f.d, f.fl, DPB_LAUNCH((attn_fwd_kernel<D, FL>), grid, dim3(att_waves(D) * 64), 0, st, a, (bf16*)O, stats));
   DPB_CHECK(hipGetLastError());
   return 0;
 }
@@ -1294,13 +1260,13 @@ int launch_attn_jvp_fused(const FusedAttnArgs& f, int nt, hipStream_t st) {
   if (!head_dim_ok(f.d)) { set_error("fused attention: head dim %d unsupported", f.d); return -1; }
   if (att_block_waves(f.d, f.L, nt * f.H) == 4 && f.d == 40) {
     dim3 g4(f.L / 128, nt * f.H);
-    if (f.fl) hipLaunchKernelGGL((attn_jvp_kernel<40, 1, 4>), g4, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((attn_jvp_kernel<40, 0, 4>), g4, dim3(256), 0, st, a);
+    if (f.fl) DPB_LAUNCH((attn_jvp_kernel<40, 1, 4>), g4, dim3(256), 0, st, a);
+    else DPB_LAUNCH((attn_jvp_kernel<40, 0, 4>), g4, dim3(256), 0, st, a);
     DPB_CHECK(hipGetLastError());
     return 0;
   }
   dim3 grid((f.L + att_waves(f.d) * 32 - 1) / (att_waves(f.d) * 32), nt * f.H);
-  DPB_ATT_DISPATCH(f.d, f.fl, hipLaunchKernelGGL((attn_jvp_kernel<D, FL>), grid, dim3(att_waves(D) * 64), 0, st, a));
+  DPB_ATT_DISPATCH(f.d, f.fl, DPB_LAUNCH((attn_jvp_kernel<D, FL>), grid, dim3(att_waves(D) * 64), 0, st, a));
   DPB_CHECK(hipGetLastError());
   return 0;
 }
@@ -1321,9 +1287,7 @@ static int attn_adj_route(int d, int L, int kps, int nt, bool have_drow) {
   if (dsh && (shared & 2) && L % 64 == 0 && kps >= 4 && nt % kps == 0 && have_drow) r |= 2;
   return r;
 }
-// launches of launch_attn_adj_fused: query-major + key-major (+ the row-dot pre-pass when the key-major shared kernel cannot take D_t from the multi-cotangent one)
 int attn_adj_route_bits(int d, int L, int kps, int nt) { return attn_adj_route(d, L, kps, nt, true); }
-int attn_adj_launches(int d, int L, int kps, int nt) { const int r = attn_adj_route(d, L, kps, nt, true); return 2 + (r == 2); }
 
 int launch_attn_adj_fused(const FusedAttnArgs& f, int nt, hipStream_t st) {
   FusedArgs a = to_args(f);
@@ -1335,12 +1299,12 @@ int launch_attn_adj_fused(const FusedAttnArgs& f, int nt, hipStream_t st) {
     const int ngrp = (f.kps + TJ - 1) / TJ;
     const dim3 gq(f.L / 128, (nt / f.kps) * f.H * ngrp);
     if (route & 2) a.Dout = a.Drow;               // the row dots D_t = gO_t . O it computes anyway, left for the key-major kernel
-#define DPB_ADJQ(DV, FLV) hipLaunchKernelGGL((attn_adj_q_multi_kernel<DV, TJ, FLV>), gq, dim3(256), 0, st, a)
+#define DPB_ADJQ(DV, FLV) DPB_LAUNCH((attn_adj_q_multi_kernel<DV, TJ, FLV>), gq, dim3(256), 0, st, a)
     if (f.d == 40) { if (f.fl) DPB_ADJQ(40, 1); else DPB_ADJQ(40, 0); }
     else { if (f.fl) DPB_ADJQ(64, 1); else DPB_ADJQ(64, 0); }
 #undef DPB_ADJQ
   } else {
-    DPB_ATT_DISPATCH(f.d, f.fl, hipLaunchKernelGGL((attn_adj_q_kernel<D, FL>), grid, dim3(att_waves(D) * 64), 0, st, a));
+    DPB_ATT_DISPATCH(f.d, f.fl, DPB_LAUNCH((attn_adj_q_kernel<D, FL>), grid, dim3(att_waves(D) * 64), 0, st, a));
   }
   if (route & 2) {
     constexpr int TJ = 5;
@@ -1349,18 +1313,18 @@ int launch_attn_adj_fused(const FusedAttnArgs& f, int nt, hipStream_t st) {
     const unsigned nrd = (unsigned)(((long)nt * f.L * f.H + 255) / 256);
 #define DPB_ADJKV(DV, FLV)                                                                                                          \
     do {                                                                                                                              \
-      if (!(route & 1)) hipLaunchKernelGGL((attn_rowdot_kernel<DV, FLV>), dim3(nrd), dim3(256), 0, st, a, nt);                       \
-      hipLaunchKernelGGL((attn_adj_kv_shared_kernel<DV, TJ, FLV>), gs, dim3(SHK<DV, TJ>::NT), 0, st, a);                             \
+      if (!(route & 1)) DPB_LAUNCH((attn_rowdot_kernel<DV, FLV>), dim3(nrd), dim3(256), 0, st, a, nt);                              \
+      DPB_LAUNCH((attn_adj_kv_shared_kernel<DV, TJ, FLV>), gs, dim3(SHK<DV, TJ>::NT), 0, st, a);                                    \
     } while (0)
     if (f.d == 40) { if (f.fl) DPB_ADJKV(40, 1); else DPB_ADJKV(40, 0); }
     else { if (f.fl) DPB_ADJKV(64, 1); else DPB_ADJKV(64, 0); }
 #undef DPB_ADJKV
   } else if (att_block_waves(f.d, f.L, nt * f.H) == 4 && f.d == 40) {
     dim3 g4(f.L / 128, nt * f.H);
-    if (f.fl) hipLaunchKernelGGL((attn_adj_kv_kernel<40, 1, 4>), g4, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL((attn_adj_kv_kernel<40, 0, 4>), g4, dim3(256), 0, st, a);
+    if (f.fl) DPB_LAUNCH((attn_adj_kv_kernel<40, 1, 4>), g4, dim3(256), 0, st, a);
+    else DPB_LAUNCH((attn_adj_kv_kernel<40, 0, 4>), g4, dim3(256), 0, st, a);
   } else {
-    DPB_ATT_DISPATCH(f.d, f.fl, hipLaunchKernelGGL((attn_adj_kv_kernel<D, FL>), grid, dim3(att_waves(D) * 64), 0, st, a));
+    DPB_ATT_DISPATCH(f.d, f.fl, DPB_LAUNCH((attn_adj_kv_kernel<D, FL>), grid, dim3(att_waves(D) * 64), 0, st, a));
   }
   DPB_CHECK(hipGetLastError());
   return 0;

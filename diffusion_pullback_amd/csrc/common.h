@@ -325,4 +325,13 @@ __device__ inline float dgelu_(float x) {
 void set_error(const char* fmt, ...);
 const char* last_error();
 
+// Kernels this thread has enqueued, counted AT the launch: every kernel launch of the library goes through DPB_LAUNCH (hipMemsetAsync / hipMemcpyAsync
+// are not kernels of ours and are not counted).  The engine reports a pass's launches as a difference of this counter (engine.cpp, where it is defined).
+extern thread_local long launch_count;
+#define DPB_LAUNCH(...)                 \
+  do {                                  \
+    ++dpb::launch_count;                \
+    hipLaunchKernelGGL(__VA_ARGS__);    \
+  } while (0)
+
 }  // namespace dpb

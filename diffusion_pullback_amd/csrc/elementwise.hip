@@ -84,9 +84,9 @@ static int geglu_t(int mode, const GegluArgs& a, hipStream_t st) {
   if (a.il && (a.il != 64 || a.F % 64)) { set_error("geglu: interleave %d with F=%d unsupported (blocks of 64)", a.il, a.F); return -1; }
   long nrows = (long)(mode == MODE_PRIMAL ? a.Bp : a.NT) * a.rows_per_sample;
   unsigned g = grid_for(nrows * (a.F / TT<T>::CH));
-  if (mode == MODE_PRIMAL) hipLaunchKernelGGL((geglu_kernel<T, MODE_PRIMAL>), dim3(g), dim3(256), 0, st, a, nrows);
-  else if (mode == MODE_TANGENT) hipLaunchKernelGGL((geglu_kernel<T, MODE_TANGENT>), dim3(g), dim3(256), 0, st, a, nrows);
-  else hipLaunchKernelGGL((geglu_kernel<T, MODE_ADJOINT>), dim3(g), dim3(256), 0, st, a, nrows);
+  if (mode == MODE_PRIMAL) DPB_LAUNCH((geglu_kernel<T, MODE_PRIMAL>), dim3(g), dim3(256), 0, st, a, nrows);
+  else if (mode == MODE_TANGENT) DPB_LAUNCH((geglu_kernel<T, MODE_TANGENT>), dim3(g), dim3(256), 0, st, a, nrows);
+  else DPB_LAUNCH((geglu_kernel<T, MODE_ADJOINT>), dim3(g), dim3(256), 0, st, a, nrows);
   DPB_CHECK(hipGetLastError());
   return 0;
 }
@@ -124,11 +124,11 @@ static int unary_t(int op, const void* x, void* y, long n, hipStream_t st) {
   if (n % TT<T>::CH) { set_error("elementwise: n=%ld not chunk aligned", n); return -1; }
   long nc = n / TT<T>::CH;
   unsigned g = grid_for(nc);
-  if (op == 0) hipLaunchKernelGGL((unary_kernel<T, 0>), dim3(g), dim3(256), 0, st, (const T*)x, (T*)y, nc);
-  else if (op == 1) hipLaunchKernelGGL((unary_kernel<T, 1>), dim3(g), dim3(256), 0, st, (const T*)x, (T*)y, nc);
-  else if (op == 3) hipLaunchKernelGGL((unary_kernel<T, 3>), dim3(g), dim3(256), 0, st, (const T*)x, (T*)y, nc);
-  else if (op == 4) hipLaunchKernelGGL((unary_kernel<T, 4>), dim3(g), dim3(256), 0, st, (const T*)x, (T*)y, nc);
-  else hipLaunchKernelGGL((unary_kernel<T, 2>), dim3(g), dim3(256), 0, st, (const T*)x, (T*)y, nc);
+  if (op == 0) DPB_LAUNCH((unary_kernel<T, 0>), dim3(g), dim3(256), 0, st, (const T*)x, (T*)y, nc);
+  else if (op == 1) DPB_LAUNCH((unary_kernel<T, 1>), dim3(g), dim3(256), 0, st, (const T*)x, (T*)y, nc);
+  else if (op == 3) DPB_LAUNCH((unary_kernel<T, 3>), dim3(g), dim3(256), 0, st, (const T*)x, (T*)y, nc);
+  else if (op == 4) DPB_LAUNCH((unary_kernel<T, 4>), dim3(g), dim3(256), 0, st, (const T*)x, (T*)y, nc);
+  else DPB_LAUNCH((unary_kernel<T, 2>), dim3(g), dim3(256), 0, st, (const T*)x, (T*)y, nc);
   DPB_CHECK(hipGetLastError());
   return 0;
 }
@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256) void embed_tokens_kernel(const int* ids, const
 }
 int launch_embed_tokens(int dtype, const int* ids, const void* tok, const void* pos, float* out, int batch, int L, int C, int vocab, hipStream_t st) {
   if (batch <= 0 || L <= 0 || C <= 0 || vocab <= 0) { set_error("embed_tokens: empty problem"); return -1; }
-  DPB_DISPATCH_STMT(dtype, T, hipLaunchKernelGGL((embed_tokens_kernel<T>), dim3(L, batch), dim3(256), 0, st, ids, (const T*)tok, (const T*)pos, out, L, C, vocab));
+  DPB_DISPATCH_STMT(dtype, T, DPB_LAUNCH((embed_tokens_kernel<T>), dim3(L, batch), dim3(256), 0, st, ids, (const T*)tok, (const T*)pos, out, L, C, vocab));
   DPB_CHECK(hipGetLastError());
   return 0;
 }
@@ -189,7 +189,7 @@ int launch_copy_cols(int dtype, const void* src, int lds_, int cs0, void* dst, i
   int CH = dt_chunk(dtype);
   if (ncols % CH || cs0 % CH || cd0 % CH || lds_ % CH || ldd % CH) { set_error("copy_cols: misaligned window"); return -1; }
   unsigned g = grid_for(rows * (ncols / CH));
-  DPB_DISPATCH_STMT(dtype, T, hipLaunchKernelGGL((copy_cols_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)src, lds_, cs0, (T*)dst, ldd, cd0, rows, ncols, accumulate));
+  DPB_DISPATCH_STMT(dtype, T, DPB_LAUNCH((copy_cols_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)src, lds_, cs0, (T*)dst, ldd, cd0, rows, ncols, accumulate));
   DPB_CHECK(hipGetLastError());
   return 0;
 }
@@ -214,7 +214,7 @@ int launch_zero_cols(int dtype, void* dst, int ldd, int cd0, long rows, int ncol
   int CH = dt_chunk(dtype);
   if (ncols % CH || cd0 % CH || ldd % CH || cd0 + ncols > ldd) { set_error("zero_cols: misaligned window"); return -1; }
   unsigned g = grid_for(rows * (ncols / CH));
-  DPB_DISPATCH_STMT(dtype, T, hipLaunchKernelGGL((zero_cols_kernel<T>), dim3(g), dim3(256), 0, st, (T*)dst, ldd, cd0, rows, ncols));
+  DPB_DISPATCH_STMT(dtype, T, DPB_LAUNCH((zero_cols_kernel<T>), dim3(g), dim3(256), 0, st, (T*)dst, ldd, cd0, rows, ncols));
   DPB_CHECK(hipGetLastError());
   return 0;
 }
@@ -254,13 +254,13 @@ __global__ __launch_bounds__(256) void nhwc_to_nchw_kernel(const T* src, float* 
 }
 int launch_nchw_to_nhwc(int dtype, const float* src, void* dst, int n, int C, int HW, int Cpad, hipStream_t st) {
   dim3 grid((HW + 31) / 32, (Cpad + 31) / 32, n);
-  DPB_DISPATCH_STMT(dtype, T, hipLaunchKernelGGL((nchw_to_nhwc_kernel<T>), grid, dim3(256), 0, st, src, (T*)dst, C, HW, Cpad));
+  DPB_DISPATCH_STMT(dtype, T, DPB_LAUNCH((nchw_to_nhwc_kernel<T>), grid, dim3(256), 0, st, src, (T*)dst, C, HW, Cpad));
   DPB_CHECK(hipGetLastError());
   return 0;
 }
 int launch_nhwc_to_nchw(int dtype, const void* src, float* dst, int n, int C, int HW, int Cpad, hipStream_t st) {
   dim3 grid((HW + 31) / 32, (C + 31) / 32, n);
-  DPB_DISPATCH_STMT(dtype, T, hipLaunchKernelGGL((nhwc_to_nchw_kernel<T>), grid, dim3(256), 0, st, (const T*)src, dst, C, HW, Cpad));
+  DPB_DISPATCH_STMT(dtype, T, DPB_LAUNCH((nhwc_to_nchw_kernel<T>), grid, dim3(256), 0, st, (const T*)src, dst, C, HW, Cpad));
   DPB_CHECK(hipGetLastError());
   return 0;
 }
@@ -337,13 +337,12 @@ static int shift_tap_t(void* h, const float* u, const int* dir, const float* sca
     ShiftRows rows;
     const int nb = std::min(SHIFT_MAX_ROWS, batch - b0);
     for (int r = 0; r < nb; ++r) { rows.dir[r] = dir[b0 + r]; rows.scale[r] = scale[b0 + r]; }
-    if (C % TT<T>::CH == 0) hipLaunchKernelGGL((shift_tap_kernel<T, TT<T>::CH>), grid, dim3(256), 0, st, (T*)h, u, rows, b0, nb, bcast, C, Cv, HW);
-    else hipLaunchKernelGGL((shift_tap_kernel<T, 1>), grid, dim3(256), 0, st, (T*)h, u, rows, b0, nb, bcast, C, Cv, HW);
+    if (C % TT<T>::CH == 0) DPB_LAUNCH((shift_tap_kernel<T, TT<T>::CH>), grid, dim3(256), 0, st, (T*)h, u, rows, b0, nb, bcast, C, Cv, HW);
+    else DPB_LAUNCH((shift_tap_kernel<T, 1>), grid, dim3(256), 0, st, (T*)h, u, rows, b0, nb, bcast, C, Cv, HW);
     DPB_CHECK(hipGetLastError());
   }
   return 0;
 }
-int shift_tap_launches(int batch) { return (batch + SHIFT_MAX_ROWS - 1) / SHIFT_MAX_ROWS; }
 int launch_shift_tap(int dtype, void* h, const float* u, const int* dir, const float* scale, int batch, int bcast, int C, int Cv, long HW,
                      hipStream_t st) {
   if (batch < 1 || C < 1 || Cv < 1 || Cv > C || HW < 1) { set_error("shift_tap: empty or inconsistent problem"); return -1; }
@@ -359,7 +358,6 @@ __global__ __launch_bounds__(256) void replicate_rows_kernel(ReplTable t, int ba
     for (int b = 1; b < batch; ++b) p[(long)b * n + i] = v;
   }
 }
-int replicate_rows_launches(int nbufs) { return (nbufs + REPL_MAX_BUFS - 1) / REPL_MAX_BUFS; }
 int launch_replicate_rows(void* const* bufs, const size_t* sample_bytes, int nbufs, int batch, hipStream_t st) {
   if (batch < 2) return 0;
   for (int i0 = 0; i0 < nbufs; i0 += REPL_MAX_BUFS) {
@@ -372,7 +370,7 @@ int launch_replicate_rows(void* const* bufs, const size_t* sample_bytes, int nbu
       t.chunks[i] = (long)(sample_bytes[i0 + i] / 16);
       most = std::max(most, t.chunks[i]);
     }
-    hipLaunchKernelGGL(replicate_rows_kernel, dim3(std::min(grid_for(most), 2048u), n), dim3(256), 0, st, t, batch);
+    DPB_LAUNCH(replicate_rows_kernel, dim3(std::min(grid_for(most), 2048u), n), dim3(256), 0, st, t, batch);
     DPB_CHECK(hipGetLastError());
   }
   return 0;
@@ -415,7 +413,7 @@ __global__ __launch_bounds__(256) void pool2x2_kernel(const T* in, T* out, int n
 int launch_pool2x2_sum(int dtype, const void* in, void* out, int n, int H, int W, int C, int accumulate, hipStream_t st) {
   int CH = dt_chunk(dtype);
   unsigned g = grid_for((long)n * H * W * (C / CH));
-  DPB_DISPATCH_STMT(dtype, T, hipLaunchKernelGGL((pool2x2_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)in, (T*)out, n, H, W, C, accumulate));
+  DPB_DISPATCH_STMT(dtype, T, DPB_LAUNCH((pool2x2_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)in, (T*)out, n, H, W, C, accumulate));
   DPB_CHECK(hipGetLastError());
   return 0;
 }
@@ -430,7 +428,7 @@ __global__ __launch_bounds__(256) void ddim_kernel(const float* x, const float* 
 }
 int launch_ddim_step(const float* x, const float* e, float* out, float* x0, long n, float a_t, float a_next, hipStream_t st) {
   // same operation order as the reference (utils.py:301-306): sqrt in fp32 of the fp32 alphas
-  hipLaunchKernelGGL(ddim_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, e, out, x0, n, sqrtf(a_t), sqrtf(1.f - a_t), sqrtf(a_next),
+  DPB_LAUNCH(ddim_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, e, out, x0, n, sqrtf(a_t), sqrtf(1.f - a_t), sqrtf(a_next),
                      sqrtf(1.f - a_next));
   DPB_CHECK(hipGetLastError());
   return 0;
@@ -445,7 +443,7 @@ __global__ __launch_bounds__(256) void lincomb_kernel(const float* x, const floa
   }
 }
 int launch_lincomb(const float* x, const float* y, const float* z, float* out, long n, float a, float b, float c, hipStream_t st) {
-  hipLaunchKernelGGL(lincomb_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, y, z, out, n, a, b, c);
+  DPB_LAUNCH(lincomb_kernel, dim3(grid_for(n)), dim3(256), 0, st, x, y, z, out, n, a, b, c);
   DPB_CHECK(hipGetLastError());
   return 0;
 }

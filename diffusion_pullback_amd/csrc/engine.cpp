@@ -34,6 +34,7 @@ void set_error(const char* fmt, ...) {
   va_end(ap);
 }
 const char* last_error() { return g_err; }
+thread_local long launch_count = 0;   // common.h: DPB_LAUNCH counts here
 
 static inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
 static inline int round8(int v) { return (v + 7) / 8 * 8; }
@@ -137,6 +138,13 @@ int fail(const char* fmt, ...) {
   return -1;
 }
 
+// the launches of one pass (dpb_engine_stats): what DPB_LAUNCH counted while the pass ran, on every way out of it
+struct LaunchSpan {
+  dpb_engine* e; long at;
+  explicit LaunchSpan(dpb_engine* e_) : e(e_), at(launch_count) {}
+  ~LaunchSpan() { e->n_launch = launch_count - at; }
+};
+
 void gemm_prep(dpb_engine* e, GemmArgs& a) {
   a.slab = (float*)(e->ws + e->slab);
   a.zeros = e->ws + e->zeros;
@@ -156,7 +164,6 @@ int g_ln_kmax = getenv("DPB_LN_FUSE_KMAX") ? atoi(getenv("DPB_LN_FUSE_KMAX")) : 
 int flush_pending(dpb_engine* e) {                 // the designated consumer did not come next: reduce the parked product the ordinary way
   if (!e->pend.on) return 0;
   e->pend.on = false;
-  e->n_launch++;
   return launch_gemm_reduce(e->dtype, e->pend.a, e->stream);
 }
 
@@ -191,12 +198,10 @@ int gemm(dpb_engine* e, GemmArgs a, bool can_defer = false) {
   const double kk = (double)a.K + (a.A2 ? a.K2 : 0);
   e->flops += 2.0 * a.M * (double)a.N * kk * a.Z1 * a.Z2;
   e->gbytes += ((double)a.M * a.K + (double)a.N * a.K + (double)a.M * a.N) * a.Z1 * a.Z2 * e->es;
-  int nl = 1;                                   // kernels enqueued: the product itself (+ splitk_reduce_kernel for split-K launches)
   const GemmPlan pl = gemm_plan(e->dtype, a);   // the one dispatch of this launch: launch_gemm runs it, the bracket is labelled with its tile's profile kind
   // (-1 with profiling off) the same bracket helpers as the attention launches (an event that cannot be created or recorded costs the bracket, never leaks its partner)
   const int pi = prof_open(e, 2.0 * a.M * (double)a.N * kk * a.Z1 * a.Z2, pl.row ? pl.row->kind : 0, a.M, a.N, a.K, a.Z1 * a.Z2, a.gather);
-  const int r = launch_gemm(e->dtype, a, e->stream, &nl, pend, &pl);
-  e->n_launch += nl;
+  const int r = launch_gemm(e->dtype, a, e->stream, pend, &pl);
   e->pend.on = pend && pend->splitk > 1;
   prof_close(e, pi);
   return r;
@@ -210,7 +215,6 @@ int conv_fwd(dpb_engine* e, const Op& op, int mode, int n) {
   const Buf& bi = e->bufs[d.in0];
   const Buf& bo = e->bufs[d.out];
   if (mode == 1 && !e->bact[d.in0]) {   // only the residual carries a tangent
-    e->n_launch++;
     return launch_axpy(e->dtype, e->T(d.res), e->T(d.out), (long)n * bo.rows * bo.C, 0, e->stream);
   }
   GemmArgs g;
@@ -350,7 +354,6 @@ int conv_adj(dpb_engine* e, const Op& op, int n) {
       g.H = Ho; g.W = Wo; g.Cin = Cout; g.Ho = Ho; g.Wo = Wo; g.KS = KS; g.stride = 1; g.pad = 1;
       g.C = e->ws + e->convtmp;
       if (int r = gemm(e, g)) return r;
-      e->n_launch++;
       if (int r = launch_pool2x2_sum(e->dtype, e->ws + e->convtmp, e->G(d.in0), n, H, W, bi.C, e->ginit[d.in0], e->stream)) return r;
     }
     e->ginit[d.in0] = 1;
@@ -363,7 +366,6 @@ residual:
       // over instead of copying it (38 copies of up to 13 MB per adjoint pass on SD-1.5); dpb_vjp restores the plan
       std::swap(br.g_off, e->bufs[d.out].g_off);
     } else {
-      e->n_launch++;
       if (int r = launch_axpy(e->dtype, e->G(d.out), e->G(d.res), (long)n * bo.rows * bo.C, e->ginit[d.res], e->stream)) return r;
     }
     e->ginit[d.res] = 1;
@@ -392,7 +394,7 @@ bool consumes_pending(dpb_engine* e, const Op& op, int mode) {
   if (e->pend.a.N != bi.C) return false;
   if (op.d.kind == DPB_OP_GROUPNORM) {
     GNArgs a; a.HW = bi.rows; a.C = bi.C; a.G = op.d.ip[0]; a.NT = 1;
-    return groupnorm_launches(e->dtype, mode, a) == 1;
+    return groupnorm_is_one_launch(e->dtype, a);
   }
   return true;
 }
@@ -427,7 +429,6 @@ int gn_run(dpb_engine* e, const Op& op, int mode, int n) {
     }
     take_pending(e, a.src, a.d, mode == MODE_TANGENT && (e->uses[d.in0] > 1 || d.in0 == e->cur_tap));
   }
-  e->n_launch += groupnorm_launches(e->dtype, mode, a);
   return launch_groupnorm(e->dtype, mode, a, e->stream);
 }
 
@@ -457,7 +458,6 @@ int ln_run(dpb_engine* e, const Op& op, int mode, int n) {
     }
     take_pending(e, a.src, a.d, mode == MODE_TANGENT && (e->uses[d.in0] > 1 || d.in0 == e->cur_tap));
   }
-  e->n_launch++;
   return launch_layernorm(e->dtype, mode, a, e->stream);
 }
 
@@ -485,7 +485,6 @@ int geglu_run(dpb_engine* e, const Op& op, int mode, int n) {
       e->ginit[d.in0] = 1;
     }
   }
-  e->n_launch++;
   return launch_geglu(e->dtype, mode, a, e->stream);
 }
 
@@ -495,7 +494,6 @@ int concat_run(dpb_engine* e, const Op& op, int mode, int n) {
   const Buf& b1 = e->bufs[d.in1];
   const Buf& bo = e->bufs[d.out];
   const long rows = (long)n * bo.rows;
-  e->n_launch += 2;
   if (mode == MODE_ADJOINT) {
     if (e->bact[d.in0]) {
       if (int r = launch_copy_cols(e->dtype, e->G(d.out), bo.C, 0, e->G(d.in0), b0.C, 0, rows, b0.C, e->ginit[d.in0], e->stream)) return r;
@@ -552,7 +550,6 @@ int attn_primal(dpb_engine* e, const Op& op, int B) {
   const AttnPtrs x = attn_ptrs(e, d, p, 0);
   if (p.fused) {   // flash forward: O and the row statistics, no L x L object; the kernels build transposed operand fragments with
                    // LDS transpose reads from the row tiles, so no per-head transposed copies are kept either
-    e->n_launch += 1;
     FusedAttnArgs f;
     fill_fused(e, p, x, f, 1, scale);
     const double fl = 2.0 * p.Lq * (double)p.Lk * p.d * 2 * B * H;
@@ -569,14 +566,12 @@ int attn_primal(dpb_engine* e, const Op& op, int B) {
     f.Q = x.Q; f.K = x.K; f.V = x.V; f.BT = nullptr; f.X = nullptr; f.Y = x.O;
     f.L = p.Lq; f.Lk = p.Lk; f.Lkp = p.Lkp; f.C = x.ldq; f.Ck = x.ldk; f.Cx = x.ldq; f.Cy = x.ldo;
     f.H = H; f.d = p.d; f.kps = 1; f.primal = 1; f.scale = scale; f.fl = e->dtype == DT_F16;
-    e->n_launch++;
     const double fl = 2.0 * p.Lq * (double)p.Lk * p.d * 2 * B * H;
     e->flops += fl;
     const int pi = prof_open(e, fl, 10, p.Lq, p.Lk, p.d, B * H, 2);
     const int r = launch_attn_cross(f, B, e->stream);
     prof_close(e, pi);
     if (r || e->fwd_only) return r;
-    e->n_launch += 2;
     if (int r2 = launch_transpose(e->dtype, x.V, ws + p.VT, B, H, (long)p.Lk * x.ldv, p.d, p.Lk, p.d, x.ldv, p.Lkp, (long)p.d * p.Lkp, e->stream)) return r2;
     return launch_transpose(e->dtype, x.K, ws + p.KT, B, H, (long)p.Lk * x.ldk, p.d, p.Lk, p.d, x.ldk, p.Lkp, (long)p.d * p.Lkp, e->stream);
   }
@@ -586,16 +581,11 @@ int attn_primal(dpb_engine* e, const Op& op, int B) {
   g.C = ws + p.P; g.ldc = p.Lkp; g.sC1 = (long)H * p.Lq * p.Lkp; g.sC2 = (long)p.Lq * p.Lkp;
   g.M = p.Lq; g.N = p.Lk; g.K = p.d; g.Z1 = B; g.Z2 = H; g.alpha = scale;
   if (int r = gemm(e, g)) return r;
-  e->n_launch += 3;
-  if (p.fused) {
-    e->n_launch++;
-    if (int r = launch_row_stats(e->dtype == DT_F16, ws + p.P, (float*)(ws + p.stats), (long)B * H * p.Lq, p.Lk, p.Lkp, e->stream)) return r;
-  }
   if (int r = launch_softmax_fwd(e->dtype, ws + p.P, (long)B * H, p.Lq, p.Lk, p.Lkp, p.causal, e->stream)) return r;
   // V^T, K^T per head ([d][Lkp], zero padded)
   if (int r = launch_transpose(e->dtype, x.V, ws + p.VT, B, H, (long)p.Lk * x.ldv, p.d, p.Lk, p.d, x.ldv, p.Lkp, (long)p.d * p.Lkp, e->stream)) return r;
-  if (e->fwd_only) e->n_launch--;   // K^T serves the adjoint only
-  else if (int r = launch_transpose(e->dtype, x.K, ws + p.KT, B, H, (long)p.Lk * x.ldk, p.d, p.Lk, p.d, x.ldk, p.Lkp, (long)p.d * p.Lkp, e->stream)) return r;
+  if (!e->fwd_only)                 // K^T serves the adjoint only
+    if (int r = launch_transpose(e->dtype, x.K, ws + p.KT, B, H, (long)p.Lk * x.ldk, p.d, p.Lk, p.d, x.ldk, p.Lkp, (long)p.d * p.Lkp, e->stream)) return r;
   GemmArgs o;   // O = P V
   o.A = ws + p.P; o.lda = p.Lkp; o.sA1 = (long)H * p.Lq * p.Lkp; o.sA2 = (long)p.Lq * p.Lkp;
   o.B = ws + p.VT; o.ldb = p.Lkp; o.sB1 = (long)H * p.d * p.Lkp; o.sB2 = (long)p.d * p.Lkp;
@@ -603,9 +593,7 @@ int attn_primal(dpb_engine* e, const Op& op, int B) {
   o.M = p.Lq; o.N = p.d; o.K = p.Lkp; o.Z1 = B; o.Z2 = H;
   if (int r = gemm(e, o)) return r;
   if (!p.kv_const && !e->fwd_only) {
-    e->n_launch += 2;
-    if (!p.fused)
-      if (int r = launch_transpose(e->dtype, ws + p.P, ws + p.PT, B * H, 1, (long)p.Lq * p.Lkp, 0, p.Lq, p.Lk, p.Lkp, p.Lqp, (long)p.Lk * p.Lqp, e->stream)) return r;
+    if (int r = launch_transpose(e->dtype, ws + p.P, ws + p.PT, B * H, 1, (long)p.Lq * p.Lkp, 0, p.Lq, p.Lk, p.Lkp, p.Lqp, (long)p.Lk * p.Lqp, e->stream)) return r;
     if (int r = launch_transpose(e->dtype, x.Q, ws + p.QT, B, H, (long)p.Lq * x.ldq, p.d, p.Lq, p.d, x.ldq, p.Lqp, (long)p.d * p.Lqp, e->stream)) return r;
   }
   return 0;
@@ -627,7 +615,6 @@ int attn_tangent(dpb_engine* e, const Op& op, int nt) {
   char* S1 = ws + e->S1;
   const AttnPtrs x = attn_ptrs(e, d, p, 0), t = attn_ptrs(e, d, p, 1);
   if (p.fused) {
-    e->n_launch += 1;
     FusedAttnArgs f;
     fill_fused(e, p, x, f, kps, scale);
     f.dQ = t.Q; f.dK = t.K; f.dV = t.V; f.dO = t.O;
@@ -643,7 +630,6 @@ int attn_tangent(dpb_engine* e, const Op& op, int nt) {
     f.Q = x.Q; f.K = x.K; f.V = x.V; f.BT = ws + p.VT; f.X = t.Q; f.Y = t.O;
     f.L = p.Lq; f.Lk = p.Lk; f.Lkp = p.Lkp; f.C = x.ldq; f.Ck = x.ldk; f.Cx = t.ldq; f.Cy = t.ldo;
     f.H = H; f.d = p.d; f.kps = kps; f.adjoint = 0; f.scale = scale; f.fl = e->dtype == DT_F16;
-    e->n_launch++;
     const double fl = 2.0 * p.Lq * (double)p.Lk * p.d * 2 * nt * H;
     e->flops += fl;
     const int pi = prof_open(e, fl, 10, p.Lq, p.Lk, p.d, nt * H, 0);
@@ -662,7 +648,6 @@ int attn_tangent(dpb_engine* e, const Op& op, int nt) {
     g.K2 = p.d;
   }
   if (int r = gemm(e, g)) return r;
-  e->n_launch++;
   if (int r = launch_softmax_jvp(e->dtype, ws + p.P, S1, nullptr, (long)nt * H, H, kps, p.Lq, p.Lk, p.Lkp, e->stream)) return r;
   GemmArgs o;   // dO = dP V
   o.A = S1; o.lda = p.Lkp; o.sA1 = (long)H * p.Lq * p.Lkp; o.sA2 = (long)p.Lq * p.Lkp;
@@ -671,7 +656,6 @@ int attn_tangent(dpb_engine* e, const Op& op, int nt) {
   o.M = p.Lq; o.N = p.d; o.K = p.Lkp; o.Z1 = nt; o.Z2 = H;
   if (!p.kv_const) {   // + P dV in the same launch
     char* T1 = ws + e->T1;
-    e->n_launch++;
     if (int r = launch_transpose(e->dtype, t.V, T1, nt, H, (long)p.Lk * t.ldv, p.d, p.Lk, p.d, t.ldv, p.Lkp, (long)p.d * p.Lkp, e->stream)) return r;
     o.A2 = ws + p.P; o.lda2 = p.Lkp; o.sA21 = (long)H * p.Lq * p.Lkp; o.sA22 = (long)p.Lq * p.Lkp; o.divA2 = kps;
     o.B2 = T1; o.ldb2 = p.Lkp; o.sB21 = (long)H * p.d * p.Lkp; o.sB22 = (long)p.d * p.Lkp; o.divB2 = 1;
@@ -697,7 +681,6 @@ int attn_adjoint(dpb_engine* e, const Op& op, int nt) {
   const int accQ = e->ginit[d.in0], accK = p.kv_const ? 0 : e->ginit[d.in1] || kq || (!p.fused && vk),
             accV = p.kv_const ? 0 : e->ginit[d.in2] || vq;
   if (p.fused) {
-    e->n_launch += attn_adj_launches(p.d, p.Lq, kps, nt);
     FusedAttnArgs f;
     fill_fused(e, p, x, f, kps, scale);
     f.gO = gO; f.gQ = (void*)c.Q; f.gK = (void*)c.K; f.gV = (void*)c.V; f.Drow = Dv;
@@ -716,7 +699,6 @@ int attn_adjoint(dpb_engine* e, const Op& op, int nt) {
     f.Q = x.Q; f.K = x.K; f.V = x.V; f.BT = ws + p.KT; f.X = gO; f.Y = (void*)c.Q;
     f.L = p.Lq; f.Lk = p.Lk; f.Lkp = p.Lkp; f.C = x.ldq; f.Ck = x.ldk; f.Cx = c.ldo; f.Cy = c.ldq;
     f.H = H; f.d = p.d; f.kps = kps; f.adjoint = 1; f.accumulate = accQ; f.scale = scale; f.fl = e->dtype == DT_F16;
-    e->n_launch++;
     const double fl = 2.0 * p.Lq * (double)p.Lk * p.d * 2 * nt * H;
     e->flops += fl;
     const int pi = prof_open(e, fl, 10, p.Lq, p.Lk, p.d, nt * H, 1);
@@ -732,7 +714,6 @@ int attn_adjoint(dpb_engine* e, const Op& op, int nt) {
   g.C = S1; g.ldc = p.Lkp; g.sC1 = (long)H * p.Lq * p.Lkp; g.sC2 = (long)p.Lq * p.Lkp;
   g.M = p.Lq; g.N = p.Lk; g.K = p.d; g.Z1 = nt; g.Z2 = H;
   if (int r = gemm(e, g)) return r;
-  e->n_launch++;
   if (int r = launch_softmax_jvp(e->dtype, ws + p.P, S1, p.kv_const ? nullptr : Dv, (long)nt * H, H, kps, p.Lq, p.Lk, p.Lkp, e->stream)) return r;
   GemmArgs q;   // gQ (+)= scale * gS K
   q.A = S1; q.lda = p.Lkp; q.sA1 = (long)H * p.Lq * p.Lkp; q.sA2 = (long)p.Lq * p.Lkp;
@@ -745,7 +726,6 @@ int attn_adjoint(dpb_engine* e, const Op& op, int nt) {
   if (p.kv_const) return 0;
   char* T1 = ws + e->T1;
   char* S2 = ws + e->S2;
-  e->n_launch += 2;
   // gO^T per head [d][Lqp]
   if (int r = launch_transpose(e->dtype, gO, T1, nt, H, (long)p.Lq * c.ldo, p.d, p.Lq, p.d, c.ldo, p.Lqp, (long)p.d * p.Lqp, e->stream)) return r;
   GemmArgs v;   // gV (+)= P^T gO
@@ -787,7 +767,6 @@ int run_op(dpb_engine* e, const Op& op, int mode, int n) {
     case DPB_OP_SILU: {
       if (mode != MODE_PRIMAL) return fail("SILU / quick-GELU ops are primal only (time-embedding path, text encoder)");
       const Buf& b = e->bufs[op.d.in0];
-      e->n_launch++;
       if (op.d.ip[0] == 2)
         return launch_gelu(e->dtype, e->P(op.d.in0), e->P(op.d.out), (long)(b.kind == DPB_BUF_SHARED ? 1 : n) * b.rows * b.C, e->stream);
       if (op.d.ip[0] == 1)
@@ -1095,7 +1074,6 @@ int dpb_engine_set_workspace(dpb_engine* e, void* ws, size_t bytes) {
 static int shift_seed(dpb_engine* e, int batch, int xb, int last) {
   const int src = e->fwd_seed, ps = e->producer[src];
   const Buf& bs = e->bufs[src];
-  e->n_launch += shift_tap_launches(batch);
   if (int r = launch_shift_tap(e->dtype, e->P(src), e->fwd_u, e->fwd_dir, e->fwd_scale, batch, xb < batch, bs.C, bs.Cv, bs.rows, e->stream)) return r;
   if (xb == batch) return 0;
   std::vector<char> seen(e->bufs.size(), 0);
@@ -1114,7 +1092,6 @@ static int shift_seed(dpb_engine* e, int batch, int xb, int last) {
     if (d.kind == DPB_OP_ATTENTION) need(d.in2);
     if (d.kind == DPB_OP_CONV) need(d.res);
   }
-  e->n_launch += replicate_rows_launches((int)ptr.size());
   return launch_replicate_rows(ptr.data(), bytes.data(), (int)ptr.size(), batch, e->stream);
 }
 
@@ -1123,16 +1100,15 @@ static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const 
   if (!e->ws) return fail("workspace not set (dpb_engine_set_workspace)");
   if (batch < 1 || batch > e->maxB) return fail("batch=%d outside [1,%d]", batch, e->maxB);
   if (upto_buf < 0 || upto_buf >= (int)e->bufs.size() || e->producer[upto_buf] < 0) return fail("invalid upto buffer %d", upto_buf);
-  e->n_launch = 0; e->flops = 0; e->gbytes = 0;
+  const LaunchSpan span(e);
+  e->flops = 0; e->gbytes = 0;
   const Buf& bx = e->bufs[e->x_buf];
   const int xb = e->fwd_u ? e->fwd_xb : batch;     // samples of x / ctx (dpb_forward_shift with a shared prefix: 1)
-  e->n_launch++;
   if (int r = launch_nchw_to_nhwc(e->dtype, x, e->P(e->x_buf), xb, e->x_channels, bx.rows, bx.C, e->stream)) return r;
   if (e->ctx_buf >= 0) {
     if (!ctx) return fail("this network needs ctx (encoder_hidden_states)");
     const Buf& bc = e->bufs[e->ctx_buf];
     // ctx is already [batch][rows][Cv] channel-last (Cv = un-padded width): cast (and zero-pad to C) via the nchw kernel with HW=1
-    e->n_launch++;
     if (int r = launch_nchw_to_nhwc(e->dtype, ctx, e->P(e->ctx_buf), xb * bc.rows, bc.Cv, 1, bc.C, e->stream)) return r;
   }
   if (e->temb_buf >= 0 && !e->temb_keep) {
@@ -1151,7 +1127,6 @@ static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const 
     float* stage = (float*)(e->ws + e->io_in);
     DPB_CHECK(hipMemcpyAsync(stage, emb.data(), emb.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
     DPB_CHECK(hipStreamSynchronize(e->stream));   // emb is a host temporary
-    e->n_launch++;
     if (int r = launch_nchw_to_nhwc(e->dtype, stage, e->P(e->temb_buf), 1, (int)emb.size(), 1, (int)emb.size(), e->stream)) return r;
   }
   if (e->pstats_bytes && !gn_deterministic()) DPB_CHECK(hipMemsetAsync(e->ws + e->pstats_off, 0, e->pstats_bytes, e->stream));   // atomic statistics path accumulates
@@ -1168,7 +1143,6 @@ static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const 
       if (int r = shift_seed(e, batch, xb, last)) return r;
     } else if (i == seed_op) {                     // dpb_forward_from: the caller's activation replaces the one just computed
       const Buf& bs = e->bufs[e->fwd_seed];
-      e->n_launch++;
       if (int r = launch_nchw_to_nhwc(e->dtype, e->fwd_h, e->P(e->fwd_seed), batch, bs.Cv, bs.rows, bs.C, e->stream)) return r;
     }
   }
@@ -1249,9 +1223,9 @@ int dpb_read_buffer(dpb_engine* e, int buf, int channels, float* out) {
 static int jvp_pass(dpb_engine* e, int src, int tap, const float* V, int nt, float* U) {
   if (!e || !V) return fail("null argument");
   if (int r = check_pair(e, src, tap, nt)) return r;
-  e->n_launch = 0; e->flops = 0; e->gbytes = 0;
+  const LaunchSpan span(e);
+  e->flops = 0; e->gbytes = 0;
   const Buf& bx = e->bufs[src];
-  e->n_launch++;
   if (int r = launch_nchw_to_nhwc(e->dtype, V, e->T(src), nt, seed_channels(e, src), bx.rows, bx.C, e->stream)) return r;
   if (e->tstats_bytes && !gn_deterministic()) DPB_CHECK(hipMemsetAsync(e->ws + e->tstats_off, 0, e->tstats_bytes, e->stream));   // atomic statistics accumulate
   const int last = e->producer[tap];
@@ -1264,7 +1238,6 @@ static int jvp_pass(dpb_engine* e, int src, int tap, const float* V, int nt, flo
   if (int r = flush_pending(e)) return r;
   if (!U) return 0;
   const Buf& bt = e->bufs[tap];
-  e->n_launch++;
   return launch_nhwc_to_nchw(e->dtype, e->T(tap), U, nt, bt.Cv, bt.rows, bt.C, e->stream);
 }
 
@@ -1283,12 +1256,12 @@ int dpb_jvp_between(dpb_engine* e, int src_buf, int dst_buf, const float* V, int
 static int vjp_pass(dpb_engine* e, int src, int tap, const float* U, int nt, float* W) {
   if (!e || !W) return fail("null argument");
   if (int r = check_pair(e, src, tap, nt)) return r;
-  e->n_launch = 0; e->flops = 0; e->gbytes = 0;
+  const LaunchSpan span(e);
+  e->flops = 0; e->gbytes = 0;
   const Buf& bt = e->bufs[tap];
   std::fill(e->ginit.begin(), e->ginit.end(), 0);
   for (auto& b : e->bufs) b.g_off = b.g_off0;
   if (U) {
-    e->n_launch++;
     if (int r = launch_nchw_to_nhwc(e->dtype, U, e->G(tap), nt, bt.Cv, bt.rows, bt.C, e->stream)) return r;
   } else {
     e->bufs[tap].g_off = e->bufs[tap].t_off;       // restored from g_off0 at the start of the next adjoint pass
@@ -1307,7 +1280,6 @@ static int vjp_pass(dpb_engine* e, int src, int tap, const float* U, int nt, flo
     return src == e->x_buf ? fail("tap buffer %d is not connected to x", tap) : fail("dst buffer %d is not connected to source buffer %d", tap, src);
   }
   const Buf& bx = e->bufs[src];
-  e->n_launch++;
   const int r = launch_nhwc_to_nchw(e->dtype, e->G(src), W, nt, seed_channels(e, src), bx.rows, bx.C, e->stream);
   // Invariant of Buf::g_off / t_off: between passes every buffer's cotangent storage is its own (g_off == g_off0).  Inside the pass the residual adjoint
   // swaps g_off between buffers and U == nullptr lends the tap's TANGENT storage to its cotangent; undo both here so that nothing that reads G() or
@@ -1429,16 +1401,18 @@ static int iterate_pass(dpb_engine* e, int src, int tap, float* V, float* U, flo
   const int B = e->cur_batch;
   const int nt = k * B;
   const long N = (long)e->bufs[src].rows * seed_channels(e, src);
-  long launches = 0; double fl = 0, gb = 0;
+  const long at = launch_count;                     // the sub-passes' LaunchSpans overwrite n_launch as they go: the assignment at the end is what counts
+  long replayed = 0;                                // launches of the graph replays, less those counted while the graph was captured (they did not run)
+  double fl = 0, gb = 0;
   const bool alias_ok = e->bufs[tap].Cv == e->bufs[tap].C && g_iter_alias;   // (padded tap channels: the conversion kernels zero them, an alias would not)
   auto body = [&](bool want_u) -> int {             // one power iteration: k JVPs, k VJPs, re-orthonormalisation, V <- V_new; no host sync
     // U = J V_prev is an OUTPUT of the last iteration only (utils.py:810): before that the tap's tangent goes straight from T(tap) into the adjoint
     // pass -- no nhwc -> fp32 nchw -> nhwc round trip (two launches per iteration, bitwise the same values)
     const bool keep = alias_ok && !want_u;
     if (int r = jvp_pass(e, src, tap, V, nt, keep ? nullptr : U)) return r;
-    launches += e->n_launch; fl += e->flops; gb += e->gbytes;
+    fl += e->flops; gb += e->gbytes;
     if (int r = vjp_pass(e, src, tap, keep ? nullptr : U, nt, Wm)) return r;
-    launches += e->n_launch; fl += e->flops; gb += e->gbytes;
+    fl += e->flops; gb += e->gbytes;
     {                                               // independent k x N re-orthonormalisation per sample, all samples in one set of four launches
       OrthArgs a;                                   // (in place, V is Vprev: see dpb.h)
       a.W = Wm; a.Vprev = V; a.V = V; a.s = s; a.conv = conv; a.scratch = (double*)orth_scratch; a.k = k; a.N = N;
@@ -1454,7 +1428,6 @@ static int iterate_pass(dpb_engine* e, int src, int tap, float* V, float* U, flo
         }
       }
     }
-    launches += g_orth_batch ? 4 : 4 * B;
     return 0;
   };
   int it = 0;
@@ -1467,12 +1440,12 @@ static int iterate_pass(dpb_engine* e, int src, int tap, float* V, float* U, flo
       ++it;
       if (e->gexec) { (void)hipGraphExecDestroy(e->gexec); e->gexec = nullptr; }
       hipGraph_t g = nullptr;
-      const long l0 = launches; const double f0 = fl, b0 = gb;
+      const long l0 = launch_count; const double f0 = fl, b0 = gb;
       DPB_CHECK(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
       const int r = body(true);                     // the captured iteration always writes U (it may be the last one replayed)
       const hipError_t ce = hipStreamEndCapture(e->stream, &g);
-      e->g_launches = launches - l0; e->g_flops = fl - f0; e->g_bytes = gb - b0;
-      launches = l0; fl = f0; gb = b0;               // captured, not executed
+      e->g_launches = launch_count - l0; e->g_flops = fl - f0; e->g_bytes = gb - b0;
+      replayed -= e->g_launches; fl = f0; gb = b0;   // captured, not executed
       if (r) { if (g) (void)hipGraphDestroy(g); return r; }
       DPB_CHECK(ce);
       DPB_CHECK(hipGraphInstantiate(&e->gexec, g, nullptr, nullptr, 0));
@@ -1481,12 +1454,12 @@ static int iterate_pass(dpb_engine* e, int src, int tap, float* V, float* U, flo
     }
     for (; it < n_iters; ++it) {
       DPB_CHECK(hipGraphLaunch(e->gexec, e->stream));
-      launches += e->g_launches; fl += e->g_flops; gb += e->g_bytes;
+      replayed += e->g_launches; fl += e->g_flops; gb += e->g_bytes;
     }
   }
   for (; it < n_iters; ++it)
     if (int r = body(it == n_iters - 1)) return r;
-  e->n_launch = launches; e->flops = fl; e->gbytes = gb;
+  e->n_launch = launch_count - at + replayed; e->flops = fl; e->gbytes = gb;
   return 0;
 }
 

@@ -450,7 +450,6 @@ void gemm_debug_p8(int on) { g_p8 = on; }
 static int g_wres = 1;
 void gemm_debug_wres(int on) { g_wres = on; }
 void gemm_variant_error(const GemmTile& t, const GemmArgs& a) { set_error("gemm: tile %d has no kernel of this family for gather %d with epilogue %d", t.code, a.gather, a.epi); }
-static thread_local int t_reduce_launched = 0;   // set by launch_t when a splitk_reduce_kernel launch followed the product
 static thread_local GemmArgs* t_pending = nullptr;   // launch_gemm(..., pending): where a deferrable reduction is parked instead of launched
 
 static const GemmTile* pick_reg_tile(int dtype, const GemmArgs& a) {
@@ -687,10 +686,10 @@ GemmPlan gemm_plan(int dtype, const GemmArgs& a) {
 template <typename T, int BM, int BN, int KCH>
 static void launch_reg_t(const GemmArgs& a, dim3 grid, hipStream_t st) {
   switch (a.gather) {
-    case GATHER_NONE: hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KCH, GATHER_NONE>), grid, dim3(256), 0, st, a); break;
-    case GATHER_CONV: hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KCH, GATHER_CONV>), grid, dim3(256), 0, st, a); break;
-    case GATHER_CONVT: hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KCH, GATHER_CONVT>), grid, dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL((gemm_kernel<T, BM, BN, KCH, GATHER_UPCONV>), grid, dim3(256), 0, st, a); break;
+    case GATHER_NONE: DPB_LAUNCH((gemm_kernel<T, BM, BN, KCH, GATHER_NONE>), grid, dim3(256), 0, st, a); break;
+    case GATHER_CONV: DPB_LAUNCH((gemm_kernel<T, BM, BN, KCH, GATHER_CONV>), grid, dim3(256), 0, st, a); break;
+    case GATHER_CONVT: DPB_LAUNCH((gemm_kernel<T, BM, BN, KCH, GATHER_CONVT>), grid, dim3(256), 0, st, a); break;
+    default: DPB_LAUNCH((gemm_kernel<T, BM, BN, KCH, GATHER_UPCONV>), grid, dim3(256), 0, st, a); break;
   }
 }
 
@@ -738,8 +737,7 @@ static int launch_t(int dtype, GemmArgs a, hipStream_t st, const GemmPlan* plan)
     } else {
       long total = (long)a.M * a.N * Z / 4;
       unsigned g = (unsigned)std::max<long>(1, std::min<long>((total + 255) / 256, 4096));
-      hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(g), dim3(256), 0, st, a);
-      t_reduce_launched = 1;
+      DPB_LAUNCH((splitk_reduce_kernel<T>), dim3(g), dim3(256), 0, st, a);
     }
   }
   DPB_CHECK(hipGetLastError());
@@ -750,15 +748,14 @@ int launch_gemm_reduce(int dtype, const GemmArgs& a, hipStream_t st) {
   if (a.splitk <= 1) return 0;
   const long total = (long)a.M * a.N * a.Z1 * a.Z2 / 4;
   const unsigned g = (unsigned)std::max<long>(1, std::min<long>((total + 255) / 256, 4096));
-  DPB_DISPATCH_STMT(dtype, T, hipLaunchKernelGGL((splitk_reduce_kernel<T>), dim3(g), dim3(256), 0, st, a));
+  DPB_DISPATCH_STMT(dtype, T, DPB_LAUNCH((splitk_reduce_kernel<T>), dim3(g), dim3(256), 0, st, a));
   DPB_CHECK(hipGetLastError());
   return 0;
 }
 
-int launch_gemm(int dtype, const GemmArgs& a, hipStream_t st, int* launches, GemmArgs* pending, const GemmPlan* plan) {
+int launch_gemm(int dtype, const GemmArgs& a, hipStream_t st, GemmArgs* pending, const GemmPlan* plan) {
   GemmArgs b = a;
   b.fl = dtype == DT_F16;           // 16-bit flavour of the specialised kernels (H16<fl>)
-  t_reduce_launched = 0;
   if (pending) pending->splitk = 1;
   t_pending = pending;
   static const int trace = getenv("DPB_GEMM_TRACE") ? atoi(getenv("DPB_GEMM_TRACE")) : 0;   // debugging: print every product, synchronise after it
@@ -772,7 +769,6 @@ int launch_gemm(int dtype, const GemmArgs& a, hipStream_t st, int* launches, Gem
   const int r = DPB_DISPATCH_T(dtype, T, launch_t<T>(dtype, b, st, plan));
   if (trace && hipStreamSynchronize(st) != hipSuccess) fprintf(stderr, "gemm: the launch above failed\n");
   t_pending = nullptr;
-  if (launches) *launches = 1 + t_reduce_launched;
   return r;
 }
 

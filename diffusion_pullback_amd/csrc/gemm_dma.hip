@@ -241,7 +241,7 @@ __global__ __launch_bounds__(256) void gemm_dma_kernel(GemmArgs p) {
 int launch_gemm_dma(const GemmArgs& a, const GemmTile& t, hipStream_t st) {   // the FAM_RING32 rows of the tile table (kernels.h)
   const int r = gemm_family_launch<FAM_RING32>(a, t, [&](auto row, auto fl, auto epi, auto gather) {
     constexpr GemmTile R = kGemmTiles[decltype(row)::value];
-    hipLaunchKernelGGL((gemm_dma_kernel<R.bm, R.bn, R.stages, decltype(gather)::value, decltype(fl)::value, decltype(epi)::value>), gemm_tile_grid(R, a), dim3(R.waves * 64), 0, st, a);
+    DPB_LAUNCH((gemm_dma_kernel<R.bm, R.bn, R.stages, decltype(gather)::value, decltype(fl)::value, decltype(epi)::value>), gemm_tile_grid(R, a), dim3(R.waves * 64), 0, st, a);
   }, GemmTileSeq{});
   if (r) return r;
   DPB_CHECK(hipGetLastError());

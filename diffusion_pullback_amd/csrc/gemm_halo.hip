@@ -505,8 +505,8 @@ void conv_halo_debug_loop(int on) { g_halo_loop = on; }
 template <int GATHER, int FL>
 static void launch_halo_g(const GemmArgs& a, dim3 grid, hipStream_t st) {
   static const int loop_env = getenv("DPB_HALO_LOOP") ? atoi(getenv("DPB_HALO_LOOP")) : 1;   // A/B switch (0: the ring loop)
-  if (loop_env && g_halo_loop) hipLaunchKernelGGL((conv_halo_kernel<GATHER, FL, 1>), grid, dim3(512), 0, st, a);
-  else hipLaunchKernelGGL((conv_halo_kernel<GATHER, FL, 0>), grid, dim3(512), 0, st, a);
+  if (loop_env && g_halo_loop) DPB_LAUNCH((conv_halo_kernel<GATHER, FL, 1>), grid, dim3(512), 0, st, a);
+  else DPB_LAUNCH((conv_halo_kernel<GATHER, FL, 0>), grid, dim3(512), 0, st, a);
 }
 
 int launch_conv_halo(const GemmArgs& a, hipStream_t st) {

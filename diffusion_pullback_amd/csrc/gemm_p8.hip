@@ -471,8 +471,8 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(GemmArgs p) {
 template <int FL>
 static void launch_p8_f(const GemmArgs& a, dim3 grid, hipStream_t st) {
   const bool fast = a.gather == GATHER_NONE && a.K % 64 == 0;
-#define DPB_P8(G, E) do { if (fast) hipLaunchKernelGGL((gemm_p8_kernel<G, FL, E, (G == GATHER_NONE)>), grid, dim3(512), 0, st, a); \
-                          else hipLaunchKernelGGL((gemm_p8_kernel<G, FL, E, 0>), grid, dim3(512), 0, st, a); } while (0)
+#define DPB_P8(G, E) do { if (fast) DPB_LAUNCH((gemm_p8_kernel<G, FL, E, (G == GATHER_NONE)>), grid, dim3(512), 0, st, a); \
+                          else DPB_LAUNCH((gemm_p8_kernel<G, FL, E, 0>), grid, dim3(512), 0, st, a); } while (0)
   switch (a.gather) {
     case GATHER_NONE:
       if (a.epi == EPI_GEGLU_TAN) DPB_P8(GATHER_NONE, EPI_GEGLU_TAN);

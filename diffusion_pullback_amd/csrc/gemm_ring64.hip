@@ -315,7 +315,7 @@ int launch_gemm_ring64(const GemmArgs& a, const GemmTile& t, hipStream_t st) {
   if ((t.flags & TILE_LN) && (a.N != t.bn || a.splitk > 1)) { set_error("gemm: tile %d is the row-complete N = %d LayerNorm-epilogue tile, unsplit", t.code, t.bn); return -1; }
   const int r = gemm_family_launch<FAM_RING64>(a, t, [&](auto row, auto fl, auto epi, auto gather) {
     constexpr GemmTile R = kGemmTiles[decltype(row)::value];
-    hipLaunchKernelGGL((gemm_ring64_kernel<R.bm, R.bn, R.stages, decltype(gather)::value, R.waves, decltype(fl)::value, decltype(epi)::value>), gemm_tile_grid(R, a),
+    DPB_LAUNCH((gemm_ring64_kernel<R.bm, R.bn, R.stages, decltype(gather)::value, R.waves, decltype(fl)::value, decltype(epi)::value>), gemm_tile_grid(R, a),
                        dim3(R.waves * 64), 0, st, a);
   }, GemmTileSeq{});
   if (r) return r;

@@ -236,8 +236,8 @@ int launch_gemm_wres(const GemmArgs& a, hipStream_t st) {
   const int ntiles = (a.M + 31) / 32;
   const dim3 grid((unsigned)std::min(cus, ntiles), (unsigned)(a.N / 320));
   const bool hasx = a.R || a.accumulate;
-  if (a.fl) { if (hasx) hipLaunchKernelGGL((gemm_wres_kernel<1, 1>), grid, dim3(320), 0, st, a); else hipLaunchKernelGGL((gemm_wres_kernel<1, 0>), grid, dim3(320), 0, st, a); }
-  else { if (hasx) hipLaunchKernelGGL((gemm_wres_kernel<0, 1>), grid, dim3(320), 0, st, a); else hipLaunchKernelGGL((gemm_wres_kernel<0, 0>), grid, dim3(320), 0, st, a); }
+  if (a.fl) { if (hasx) DPB_LAUNCH((gemm_wres_kernel<1, 1>), grid, dim3(320), 0, st, a); else DPB_LAUNCH((gemm_wres_kernel<1, 0>), grid, dim3(320), 0, st, a); }
+  else { if (hasx) DPB_LAUNCH((gemm_wres_kernel<0, 1>), grid, dim3(320), 0, st, a); else DPB_LAUNCH((gemm_wres_kernel<0, 0>), grid, dim3(320), 0, st, a); }
   DPB_CHECK(hipGetLastError());
   return 0;
 }

@@ -143,11 +143,11 @@ using GemmTileSeq = std::make_integer_sequence<int, GEMM_TILES>;
 
 // The launch plan of one product: its tile row (nullptr: refused, dpb_last_error says why) and K split.  kind / tile: what dpb_debug_gemm_plan reports.
 struct GemmPlan { int kind, tile, splitk; const GemmTile* row; };   // kind: gemm_plan_kind(*row), -1 error; tile: row->code
-// *launches: kernels enqueued (1, or 2 with splitk_reduce_kernel).  `pending` != nullptr: if the launch is split over K and its epilogue is plain
+// `pending` != nullptr: if the launch is split over K and its epilogue is plain
 // (one batch entry, alpha 1, no bias / row bias / accumulate, dense rows), the reduce kernel is NOT launched -- *pending receives the prepared
 // arguments (pending->splitk > 1) and the caller either hands the slabs to a consumer that reduces them itself (SlabSrc, norm.hip) or calls
 // launch_gemm_reduce; otherwise pending->splitk is set to 1.  `plan`: the gemm_plan of these arguments if the caller already asked for it.
-int launch_gemm(int dtype, const GemmArgs& a, hipStream_t st, int* launches = nullptr, GemmArgs* pending = nullptr, const GemmPlan* plan = nullptr);
+int launch_gemm(int dtype, const GemmArgs& a, hipStream_t st, GemmArgs* pending = nullptr, const GemmPlan* plan = nullptr);
 int launch_gemm_reduce(int dtype, const GemmArgs& pending, hipStream_t st);
 GemmPlan gemm_plan(int dtype, const GemmArgs& a);   // host-only: the tile launch_gemm picks, with its K split (clamped to the slab scratch)
 void gemm_debug_set(int tile, int splitk, int kch);   // tuning overrides for micro-benchmarks (0 = heuristic): forced code, split count, K chunks of the 64x64 register-staged tile
@@ -197,7 +197,7 @@ struct GNArgs {
   SlabSrc src;                    // tangent / adjoint, one-launch kernel only: d comes from split-K slabs
 };
 int launch_groupnorm(int dtype, int mode, const GNArgs& a, hipStream_t st);
-int groupnorm_launches(int dtype, int mode, const GNArgs& a);
+bool groupnorm_is_one_launch(int dtype, const GNArgs& a);   // launch_groupnorm runs the one-launch kernel (the one that can take split-K slabs: SlabSrc) for this C, G, HW
 
 struct LNArgs {
   const void* x = nullptr; const void* d = nullptr; void* y = nullptr;
@@ -247,9 +247,7 @@ struct CrossAttnArgs {
 };
 int cross_attention_supported(int dtype, int d, int Lq, int Lk, int kv_const);
 int launch_attn_cross(const CrossAttnArgs& f, int nt, hipStream_t st);
-int launch_row_stats(int fl, const void* S, float* stats, long nrows, int Lk, int ld, hipStream_t st);
 int attn_adj_route_bits(int d, int L, int kps, int nt);   // bit 0: multi-cotangent query-major kernel, bit 1: shared-probability key-major kernel
-int attn_adj_launches(int d, int L, int kps, int nt);   // kernels launch_attn_adj_fused enqueues for such a layer (2 or 3)
 int attn_jvp_block_waves(int d, int L, int pairs);   // waves per block of the fused tangent kernel launch_attn_jvp_fused picks (pairs = nt * heads)
 int launch_attn_fwd_fused(const FusedAttnArgs& f, int batch, void* O, float* stats, hipStream_t st);   // primal O + row statistics
 int launch_attn_jvp_fused(const FusedAttnArgs& f, int nt, hipStream_t st);
@@ -288,13 +286,11 @@ constexpr int SHIFT_MAX_ROWS = 64;
 struct ShiftRows { int dir[SHIFT_MAX_ROWS]; float scale[SHIFT_MAX_ROWS]; };
 int launch_shift_tap(int dtype, void* h, const float* u, const int* dir, const float* scale, int batch, int bcast, int C, int Cv, long HW,
                      hipStream_t st);
-int shift_tap_launches(int batch);           // kernels launch_shift_tap enqueues
 // sample 0 of each of `nbufs` buffers (sample_bytes[i] bytes per sample, a multiple of 16; 16-byte aligned) copied to samples 1 .. batch-1 in
 // place: one launch per REPL_MAX_BUFS buffers, the descriptor table in the kernel arguments, 16-byte copies
 constexpr int REPL_MAX_BUFS = 32;
 struct ReplTable { void* p[REPL_MAX_BUFS]; long chunks[REPL_MAX_BUFS]; };
 int launch_replicate_rows(void* const* bufs, const size_t* sample_bytes, int nbufs, int batch, hipStream_t st);
-int replicate_rows_launches(int nbufs);      // kernels launch_replicate_rows enqueues (for batch >= 2)
 // 2x2 sum pooling of a cotangent (adjoint of nearest x2 upsampling): in [n][2H*2W][C] -> out [n][H*W][C]
 int launch_pool2x2_sum(int dtype, const void* in, void* out, int n, int H, int W, int C, int accumulate, hipStream_t st);
 

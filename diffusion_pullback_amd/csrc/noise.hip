@@ -155,11 +155,11 @@ int launch_perturb_unit(const float* x, const float* noise, uint64_t seed, int64
   const dim3 grid((unsigned)nsl, (unsigned)B), block(NOISE_THREADS);
   double* partial = (double*)scratch;
   if (vec) {
-    hipLaunchKernelGGL(noise_sumsq_kernel<true>, grid, block, 0, st, noise, seed, first, n, partial);
-    hipLaunchKernelGGL(noise_apply_kernel<true>, grid, block, 0, st, x, noise, seed, first, n, norm, (const double*)partial, out, noise_out);
+    DPB_LAUNCH(noise_sumsq_kernel<true>, grid, block, 0, st, noise, seed, first, n, partial);
+    DPB_LAUNCH(noise_apply_kernel<true>, grid, block, 0, st, x, noise, seed, first, n, norm, (const double*)partial, out, noise_out);
   } else {
-    hipLaunchKernelGGL(noise_sumsq_kernel<false>, grid, block, 0, st, noise, seed, first, n, partial);
-    hipLaunchKernelGGL(noise_apply_kernel<false>, grid, block, 0, st, x, noise, seed, first, n, norm, (const double*)partial, out, noise_out);
+    DPB_LAUNCH(noise_sumsq_kernel<false>, grid, block, 0, st, noise, seed, first, n, partial);
+    DPB_LAUNCH(noise_apply_kernel<false>, grid, block, 0, st, x, noise, seed, first, n, norm, (const double*)partial, out, noise_out);
   }
   DPB_CHECK(hipGetLastError());
   return 0;

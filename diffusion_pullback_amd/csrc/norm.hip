@@ -544,8 +544,7 @@ __global__ void gn_finalize(GNArgs a, double* st, int n_groups, double inv_n, do
   st[2 * i + 1] = 1.0 / sqrt(v + eps);
 }
 
-// pixels per block and statistics blocks per sample / tangent of the two-pass kernels: ONE rule for gn_launch and for groupnorm_launches
-// (the engine's launch count and its "is this a one-launch GroupNorm" test), so the two cannot drift
+// pixels per block and statistics blocks per sample / tangent of the two-pass kernels
 static int gn_two_pass_ppb(int HW, int n) {
   static const long gn_blocks = getenv("DPB_GN_BLOCKS") ? atol(getenv("DPB_GN_BLOCKS")) : 512;   // tuning override
   int ppb = 64;
@@ -563,7 +562,7 @@ static int gn_launch(const GNArgs& a, hipStream_t st) {
     const int cpc = gc * (a.C / a.G) / CH, ppi = 512 / cpc, sweeps = (a.HW + ppi - 1) / ppi;
     dim3 grid(a.G / gc, n);
     if (sweeps > 4) { set_error("groupnorm: %d sweeps exceed the one-launch kernel's register window", sweeps); return -1; }
-    hipLaunchKernelGGL((gn_fused_kernel<T, MODE, 4>), grid, dim3(512), 0, st, a, gc);
+    DPB_LAUNCH((gn_fused_kernel<T, MODE, 4>), grid, dim3(512), 0, st, a, gc);
     DPB_CHECK(hipGetLastError());
     return 0;
   }
@@ -582,23 +581,19 @@ static int gn_launch(const GNArgs& a, hipStream_t st) {
   }           // (atomic path: the caller has zeroed pstats / tstats -- one memset per pass in the engine)
   GNArgs b = a;
   b.red = a.det && (int)grid.x <= GN_RED_MAX;     // the apply blocks add the partials themselves (32 ... 256 L2-resident loads per thread quarter)
-  hipLaunchKernelGGL((gn_kernel<T, MODE, true>), grid, dim3(256), lds, st, b, ppb);
-  if (a.det && !b.red) hipLaunchKernelGGL((gn_reduce_kernel<T, MODE>), dim3(n), dim3(1024), 0, st, b, (int)grid.x);
+  DPB_LAUNCH((gn_kernel<T, MODE, true>), grid, dim3(256), lds, st, b, ppb);
+  if (a.det && !b.red) DPB_LAUNCH((gn_reduce_kernel<T, MODE>), dim3(n), dim3(1024), 0, st, b, (int)grid.x);
   if (MODE == MODE_PRIMAL && !a.det) {
     int ng = a.Bp * a.G;
-    hipLaunchKernelGGL(gn_finalize<T>, dim3((ng + 255) / 256), dim3(256), 0, st, a, a.pstats, ng, 1.0 / ((double)a.HW * (a.C / a.G)), (double)a.eps);
+    DPB_LAUNCH(gn_finalize<T>, dim3((ng + 255) / 256), dim3(256), 0, st, a, a.pstats, ng, 1.0 / ((double)a.HW * (a.C / a.G)), (double)a.eps);
   }
-  hipLaunchKernelGGL((gn_kernel<T, MODE, false>), grid, dim3(256), 0, st, b, ppb);
+  DPB_LAUNCH((gn_kernel<T, MODE, false>), grid, dim3(256), 0, st, b, ppb);
   DPB_CHECK(hipGetLastError());
   return 0;
 }
 
-int groupnorm_launches(int dtype, int mode, const GNArgs& a) {   // kernels launch_groupnorm issues (engine statistics)
-  if (gn_fused_groups(a.C, a.G, a.HW, dt_chunk(dtype), dtype == DT_F32 ? 4 : 2)) return 1;
-  if (!a.det) return mode == MODE_PRIMAL ? 3 : 2;
-  const int n = mode == MODE_PRIMAL ? a.Bp : a.NT;
-  const int ppb = gn_two_pass_ppb(a.HW, n);
-  return (a.HW + ppb - 1) / ppb <= GN_RED_MAX ? 2 : 3;
+bool groupnorm_is_one_launch(int dtype, const GNArgs& a) {   // the route test of gn_launch, for the engine (which hands split-K slabs to that kernel only)
+  return gn_fused_groups(a.C, a.G, a.HW, dt_chunk(dtype), dtype == DT_F32 ? 4 : 2) != 0;
 }
 
 int launch_groupnorm(int dtype, int mode, const GNArgs& a, hipStream_t st) {
@@ -801,8 +796,8 @@ __global__ __launch_bounds__(256) void ln_rows_kernel(LNArgs a, long nrows) {
 template <typename T, int MODE, int LPR>
 static bool ln_rows_launch(const LNArgs& a, long nrows, int ni, hipStream_t st) {
   const dim3 grid((unsigned)((nrows + 4 * (64 / LPR) - 1) / (4 * (64 / LPR))));
-  if (ni == 3) hipLaunchKernelGGL((ln_rows_kernel<T, MODE, LPR, 3>), grid, dim3(256), 0, st, a, nrows);
-  else if (ni == 5) hipLaunchKernelGGL((ln_rows_kernel<T, MODE, LPR, 5>), grid, dim3(256), 0, st, a, nrows);
+  if (ni == 3) DPB_LAUNCH((ln_rows_kernel<T, MODE, LPR, 3>), grid, dim3(256), 0, st, a, nrows);
+  else if (ni == 5) DPB_LAUNCH((ln_rows_kernel<T, MODE, LPR, 5>), grid, dim3(256), 0, st, a, nrows);
   else return false;
   return true;
 }
@@ -828,10 +823,10 @@ static int ln_launch(const LNArgs& a, hipStream_t st) {
   }
   const dim3 grid((unsigned)((nrows + 3) / 4));
   const int need = (a.C / CH + 63) / 64;
-  if (need <= 1) hipLaunchKernelGGL((ln_kernel<T, MODE, 1>), grid, dim3(256), 0, st, a, nrows);
-  else if (need <= 2) hipLaunchKernelGGL((ln_kernel<T, MODE, 2>), grid, dim3(256), 0, st, a, nrows);
-  else if (need <= 3) hipLaunchKernelGGL((ln_kernel<T, MODE, 3>), grid, dim3(256), 0, st, a, nrows);
-  else hipLaunchKernelGGL((ln_kernel<T, MODE, 5>), grid, dim3(256), 0, st, a, nrows);
+  if (need <= 1) DPB_LAUNCH((ln_kernel<T, MODE, 1>), grid, dim3(256), 0, st, a, nrows);
+  else if (need <= 2) DPB_LAUNCH((ln_kernel<T, MODE, 2>), grid, dim3(256), 0, st, a, nrows);
+  else if (need <= 3) DPB_LAUNCH((ln_kernel<T, MODE, 3>), grid, dim3(256), 0, st, a, nrows);
+  else DPB_LAUNCH((ln_kernel<T, MODE, 5>), grid, dim3(256), 0, st, a, nrows);
   DPB_CHECK(hipGetLastError());
   return 0;
 }

@@ -405,35 +405,35 @@ int launch_orth(const OrthArgs& a, hipStream_t st) {
   double* Cm = a.scratch;
   double* Gp = Cm + k * k;
   double* acc = Gp + (size_t)2 * nbg * k * k;
-  hipLaunchKernelGGL(gram_kernel, dim3(nbg, k * B, (k + 15) / 16), dim3(256), 0, st, a.W, a.Vprev, Gp, k, a.N, ob);
+  DPB_LAUNCH(gram_kernel, dim3(nbg, k * B, (k + 15) / 16), dim3(256), 0, st, a.W, a.Vprev, Gp, k, a.N, ob);
   // Eigen-solve: k <= 5 the one-wave cyclic kernel of rounds 1-5 (the headline's bits are unchanged; at k = 5 the two take the same time), above that
   // the round-robin kernel -- four waves up to k = 16 (8: 127 -> 78 us per dpb_orth, 10: 223 -> 134, 16: 528 -> 215), sixteen beyond
   // (50: 6.3 -> 1.2 ms; profiles/r06_eig_parallel.txt).  DPB_EIG_PAR=0: the cyclic kernel wherever it exists (k <= 56), 2: round-robin for every k.
   static const int par = getenv("DPB_EIG_PAR") ? atoi(getenv("DPB_EIG_PAR")) : 1;
   const bool cyclic = par == 0 ? k <= KMAX_REG : (par == 2 ? false : k <= 5);
   if (cyclic && k <= 16) {
-    hipLaunchKernelGGL((eig_kernel<16>), dim3(B), dim3(64), 0, st, Gp, (int)nbg, Cm, a.s, k, ob);
+    DPB_LAUNCH((eig_kernel<16>), dim3(B), dim3(64), 0, st, Gp, (int)nbg, Cm, a.s, k, ob);
   } else if (cyclic) {
-    hipLaunchKernelGGL((eig_kernel<KMAX_REG>), dim3(B), dim3(64), 0, st, Gp, (int)nbg, Cm, a.s, k, ob);
+    DPB_LAUNCH((eig_kernel<KMAX_REG>), dim3(B), dim3(64), 0, st, Gp, (int)nbg, Cm, a.s, k, ob);
   } else if (k <= 16) {
-    hipLaunchKernelGGL((eig_par_kernel<16, false, 256>), dim3(B), dim3(256), 0, st, Gp, (int)nbg, Cm, a.s, k, ob);
+    DPB_LAUNCH((eig_par_kernel<16, false, 256>), dim3(B), dim3(256), 0, st, Gp, (int)nbg, Cm, a.s, k, ob);
   } else if (k <= 32) {
-    hipLaunchKernelGGL((eig_par_kernel<32, false, 1024>), dim3(B), dim3(1024), 0, st, Gp, (int)nbg, Cm, a.s, k, ob);
+    DPB_LAUNCH((eig_par_kernel<32, false, 1024>), dim3(B), dim3(1024), 0, st, Gp, (int)nbg, Cm, a.s, k, ob);
   } else if (k <= 64) {
-    hipLaunchKernelGGL((eig_par_kernel<64, false, 1024>), dim3(B), dim3(1024), 0, st, Gp, (int)nbg, Cm, a.s, k, ob);
+    DPB_LAUNCH((eig_par_kernel<64, false, 1024>), dim3(B), dim3(1024), 0, st, Gp, (int)nbg, Cm, a.s, k, ob);
   } else if (k <= 96) {
-    hipLaunchKernelGGL((eig_par_kernel<96, false, 1024>), dim3(B), dim3(1024), 0, st, Gp, (int)nbg, Cm, a.s, k, ob);
+    DPB_LAUNCH((eig_par_kernel<96, false, 1024>), dim3(B), dim3(1024), 0, st, Gp, (int)nbg, Cm, a.s, k, ob);
   } else {
-    hipLaunchKernelGGL((eig_par_kernel<KMAX_ALL, true, 1024>), dim3(B), dim3(1024), 0, st, Gp, (int)nbg, Cm, a.s, k, ob);
+    DPB_LAUNCH((eig_par_kernel<KMAX_ALL, true, 1024>), dim3(B), dim3(1024), 0, st, Gp, (int)nbg, Cm, a.s, k, ob);
   }
   if (k <= 16) {
-    hipLaunchKernelGGL((orth_apply_kernel<16>), dim3(nb, B), dim3(256), 0, st, a.W, a.Vprev, a.V, Cm, acc, k, a.N, ob);
+    DPB_LAUNCH((orth_apply_kernel<16>), dim3(nb, B), dim3(256), 0, st, a.W, a.Vprev, a.V, Cm, acc, k, a.N, ob);
   } else if (k <= KMAX_REG) {
-    hipLaunchKernelGGL((orth_apply_kernel<KMAX_REG>), dim3(nb, B), dim3(256), 0, st, a.W, a.Vprev, a.V, Cm, acc, k, a.N, ob);
+    DPB_LAUNCH((orth_apply_kernel<KMAX_REG>), dim3(nb, B), dim3(256), 0, st, a.W, a.Vprev, a.V, Cm, acc, k, a.N, ob);
   } else {
-    hipLaunchKernelGGL(orth_apply_tiled_kernel, dim3(nb, B), dim3(256), sizeof(double) * 16 * k, st, a.W, a.Vprev, a.V, Cm, acc, k, a.N, ob);
+    DPB_LAUNCH(orth_apply_tiled_kernel, dim3(nb, B), dim3(256), sizeof(double) * 16 * k, st, a.W, a.Vprev, a.V, Cm, acc, k, a.N, ob);
   }
-  hipLaunchKernelGGL(orth_finish_kernel, dim3(B), dim3(1), 0, st, acc, (int)nb, a.conv, ob);
+  DPB_LAUNCH(orth_finish_kernel, dim3(B), dim3(1), 0, st, acc, (int)nb, a.conv, ob);
   DPB_CHECK(hipGetLastError());
   return 0;
 }

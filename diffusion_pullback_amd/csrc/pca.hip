@@ -235,12 +235,12 @@ size_t pca_scratch_bytes(int q, long N, long D) { return pca_invalid(q, N, D) ? 
 
 template <int QT>
 static void prod_samples(const float* H, const float* m, const float* P, long psi, long psn, float* Y, int q, long N, long D, hipStream_t st) {
-  hipLaunchKernelGGL((pca_prod_samples_kernel<QT>), dim3((unsigned)((D + 127) / 128)), dim3(256), 0, st, H, m, P, psi, psn, Y, q, N, D);
+  DPB_LAUNCH((pca_prod_samples_kernel<QT>), dim3((unsigned)((D + 127) / 128)), dim3(256), 0, st, H, m, P, psi, psn, Y, q, N, D);
 }
 template <int QT>
 static void prod_features(const float* H, const float* m, const float* Q, long qsi, long qsd, float* Zp, int q, long N, long D, long ch, int ns,
                           hipStream_t st) {
-  hipLaunchKernelGGL((pca_prod_features_kernel<QT>), dim3((unsigned)((N + 127) / 128), ns), dim3(256), 0, st, H, m, Q, qsi, qsd, Zp, q, N, D, ch);
+  DPB_LAUNCH((pca_prod_features_kernel<QT>), dim3((unsigned)((N + 127) / 128), ns), dim3(256), 0, st, H, m, Q, qsi, qsd, Zp, q, N, D, ch);
 }
 
 int launch_pca_lowrank(const float* H, long N, long D, const float* R, int q, int niter, float* u, float* s, void* scratch, size_t scratch_bytes,
@@ -275,7 +275,7 @@ int launch_pca_lowrank(const float* H, long N, long D, const float* R, int q, in
       default: prod_features<4>(H, m, Q, qsi, qsd, Zp, q, N, D, ch, ns, st); break;
     }
     const long qn = (long)q * N;
-    hipLaunchKernelGGL(pca_split_sum_kernel, dim3((unsigned)((qn + 255) / 256)), dim3(256), 0, st, Zp, ns, qn, Z);
+    DPB_LAUNCH(pca_split_sum_kernel, dim3((unsigned)((qn + 255) / 256)), dim3(256), 0, st, Zp, ns, qn, Z);
   };
   auto orth = [&](const float* W, float* V, long len) -> int {
     OrthArgs a;                                           // Vprev = W: the rows are signed to overlap W's (any sign spans the same space)
@@ -284,7 +284,7 @@ int launch_pca_lowrank(const float* H, long N, long D, const float* R, int q, in
     return launch_orth(a, st);
   };
 
-  hipLaunchKernelGGL(pca_mean_kernel, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, H, N, D, m);
+  DPB_LAUNCH(pca_mean_kernel, dim3((unsigned)((D + 255) / 256)), dim3(256), 0, st, H, N, D, m);
   if (N < D) {
     // _svd_lowrank transposes: A = Hc^T [D][N], R [N][q].  Basis rows Qd [q][D] (Q^T of get_approximate_basis).
     prodA(R, 1, q, Wd);                                   // X = A R          -> X^T = R^T Hc
@@ -297,9 +297,9 @@ int launch_pca_lowrank(const float* H, long N, long D, const float* R, int q, in
     }
     prodB(Qd, D, 1, Wn);                                  // B = Q^H A = Q^T Hc^T [q][N]
     if (int r = orth(Wn, Qn, N)) return r;                // svd(B): Vb rows (unused), mixing matrix in orth_s
-    hipLaunchKernelGGL(pca_svd_finish_kernel, dim3(1), dim3(ORTH_MAX_RANK), 0, st, orth_s, q, s, ubt);
+    DPB_LAUNCH(pca_svd_finish_kernel, dim3(1), dim3(ORTH_MAX_RANK), 0, st, orth_s, q, s, ubt);
     // after the swap the reference's u (_svd_lowrank's V) is Q Ub [D][q]: rows Ub^T Qd
-    hipLaunchKernelGGL(pca_rotate_kernel, dim3((unsigned)((D + 255) / 256 < 1024 ? (D + 255) / 256 : 1024)), dim3(256), 0, st, ubt, Qd, u, q, D);
+    DPB_LAUNCH(pca_rotate_kernel, dim3((unsigned)((D + 255) / 256 < 1024 ? (D + 255) / 256 : 1024)), dim3(256), 0, st, ubt, Qd, u, q, D);
   } else {
     // A = Hc [N][D], R [D][q].  Basis rows Qn [q][N].
     prodB(R, 1, q, Wn);                                   // X = A R = Hc R    -> [q][N]
@@ -312,7 +312,7 @@ int launch_pca_lowrank(const float* H, long N, long D, const float* R, int q, in
     }
     prodA(Qn, N, 1, Wd);                                  // B = Q^H A [q][D]
     if (int r = orth(Wd, u, D)) return r;                 // svd(B): its right singular vectors (rows) are the reference's u, as rows
-    hipLaunchKernelGGL(pca_svd_finish_kernel, dim3(1), dim3(ORTH_MAX_RANK), 0, st, orth_s, q, s, ubt);
+    DPB_LAUNCH(pca_svd_finish_kernel, dim3(1), dim3(ORTH_MAX_RANK), 0, st, orth_s, q, s, ubt);
   }
   DPB_CHECK(hipGetLastError());
   return 0;

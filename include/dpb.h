@@ -241,7 +241,8 @@ int dpb_lincomb(const float* x, const float* y, const float* z, float* out, int6
 int dpb_embed_tokens(const int32_t* ids, const void* tok_table, const void* pos_table, int dtype, float* out, int batch,
                      int tokens, int channels, int vocab, void* hip_stream);
 
-/* Introspection used by tests / bench: number of kernel launches and algorithmic GEMM flops of the last pass. */
+/* Introspection used by tests / bench: number of kernel launches and algorithmic GEMM flops of the last pass.  `launches` is the number of
+ * kernels the pass enqueued, counted at the launch itself; memsets and copies are not included. */
 int dpb_engine_stats(const dpb_engine* e, int64_t* launches, double* gemm_flops, double* gemm_bytes);
 /* Measurement aid (bench.py roofline leg, never on in a timed region): bracket every GEMM launch with HIP
  * events on the engine's stream; _read synchronises and sums the launches of one GEMM kernel kind: count, total
