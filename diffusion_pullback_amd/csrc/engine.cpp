@@ -86,28 +86,18 @@ struct dpb_engine {
   size_t pbW = 0;                          // pullback loop fp32 staging of W = J^T J V
   size_t temb_host_stage = 0;
   int cur_batch = 0;
-  std::vector<int> uses;            // buffer -> number of ops reading it (in0 / in1 / in2 / res)
-  int cur_tap = -1;                 // tap buffer of the pass being run
-  // Seed of the tangent / adjoint pass being run: x_buf for the encoder entry points, any buffer for the *_between ones.  A buffer (op) is
-  // ACTIVE for a seed if it is reachable forward from it (an op: one of its differentiated inputs is); only active buffers carry tangents and
-  // cotangents.  For x_buf the flags are exactly !is_const.  One flag vector per seed, computed on first use (set_seed).
-  int src = -1;
-  const char* bact = nullptr;       // [n_buffers] activity of the current seed's buffers
-  const char* oact = nullptr;       // [n_ops]     activity of the current seed's ops
+  std::vector<int> uses;            // buffer -> number of ops reading it (op_inputs)
+  // A buffer (op) is ACTIVE for a seed -- x_buf for the encoder entry points, any buffer for the *_between ones -- if it is reachable forward from
+  // it (an op: one of its differentiated inputs is); only active buffers carry tangents and cotangents.  For x_buf the flags are exactly
+  // !is_const.  One flag vector per seed, computed on first use (seed_flags); a pass carries its seed's flags in its Pass.
   std::vector<std::vector<char>> act_cache;   // seed buffer -> [n_buffers + n_ops] flags (empty: not computed yet)
   int primal_last = -1;             // last op whose primal state (with the tangent / adjoint stash) is resident; -1: none
-  int fwd_seed = -1;                // dpb_forward_from: buffer overwritten by fwd_h after its producer has run
-  const float* fwd_h = nullptr;
-  // dpb_forward_shift: after the producer of fwd_seed has run, P(fwd_seed)[b] <- P(fwd_seed)[b or 0] + fwd_scale[b] * fwd_u[fwd_dir[b]] (no overwrite by
-  // fwd_h).  fwd_xb: samples of x / ctx, i.e. the batch of ops 0 .. producer[fwd_seed]; 1 < batch: the shared prefix, the rest of the tape runs on copies
-  const float* fwd_u = nullptr; const int32_t* fwd_dir = nullptr; const float* fwd_scale = nullptr;
-  int fwd_xb = 0;
+  // Scratch of the pass being run, kept here only because a pass must not allocate: every pass function resets the ones it uses at its start,
+  // nothing in them is read across passes.  (What a pass depends on is in its Pass, what it reports in n_launch / flops / gbytes.)
   struct { bool on = false; GemmArgs a; } pend;   // a split-K product whose reduction is deferred to the normalisation op that consumes it
-  bool fwd_only = false;            // dpb_forward: primal pass that keeps no tangent / adjoint stash (DDIM loop)
-  bool temb_keep = false;           // dpb_local_pca_sample, chunks after the first: P(temb_buf) already holds this t's embedding (no upload, no sync)
-  std::vector<char> ginit;
+  std::vector<char> ginit;          // adjoint: buffers whose cotangent has been written (first write / accumulate)
   std::vector<char> skip;           // ops whose work a fused epilogue of another op has done in the current pass
-  long n_launch = 0;
+  long n_launch = 0;                // dpb_engine_stats: the last pass's launches, GEMM flops and bytes
   double flops = 0, gbytes = 0;
   // captured power iteration (dpb_debug_set("graph_iterate", 1)), valid for one (tap, k, batch, buffer set)
   struct GraphKey {
@@ -136,6 +126,43 @@ int fail(const char* fmt, ...) {
   vsnprintf(g_err, sizeof(g_err), fmt, ap);
   va_end(ap);
   return -1;
+}
+
+// What a primal pass is asked for beyond (x, t, ctx, upto): built by the entry point that means it, handed down by value.
+struct Forward {
+  bool stash = true;                // keep the tangent / adjoint stash (dpb_primal); false: forward only (dpb_forward, the DDIM loop)
+  bool temb_resident = false;       // P(temb_buf) already holds this t's embedding (dpb_local_pca_sample, chunks after the first): no upload, no sync
+  int seed = -1;                    // buffer replaced after its producer has run (-1: none), by ...
+  const float* h = nullptr;         // ... the caller's activation (dpb_forward_from), or
+  // ... P(seed)[b] <- P(seed)[b or 0] + scale[b] * u[dir[b]] (dpb_forward_shift).  xbatch: samples of x / ctx, i.e. the batch of ops
+  // 0 .. producer[seed]; 1 < batch: the shared prefix, the rest of the tape runs on copies
+  const float* u = nullptr; const int32_t* dir = nullptr; const float* scale = nullptr;
+  int xbatch = 0;
+};
+
+// Everything an op function may know about the pass it runs in.  Built on the stack by primal_pass / jvp_pass / vjp_pass.
+struct Pass {
+  int mode, tap;                    // MODE_*; the buffer the pass ends at (adjoint: starts from)
+  int src;                          // seed buffer: x_buf for the encoder entry points and the primal pass, any buffer for the *_between ones
+  const char *bact, *oact;          // [n_buffers], [n_ops] activity for that seed (seed_flags)
+  Forward fwd;                      // primal only
+  Pass(const dpb_engine* e, int mode_, int tap_, int src_, const char* flags)
+      : mode(mode_), tap(tap_), src(src_), bact(flags), oact(flags + e->bufs.size()) {}
+};
+
+// The buffers an op reads: in0; in1 of ATTENTION and CONCAT; in2 of ATTENTION; res of CONV (when it has one).  An id its op kind does not
+// read means nothing (include/dpb.h) and is never looked at.
+struct OpInputs {
+  int id[4], n;
+  const int* begin() const { return id; }
+  const int* end() const { return id + n; }
+};
+OpInputs op_inputs(const dpb_op_desc& d) {
+  OpInputs r{{d.in0}, 1};
+  if (d.kind == DPB_OP_ATTENTION || d.kind == DPB_OP_CONCAT) r.id[r.n++] = d.in1;
+  if (d.kind == DPB_OP_ATTENTION) r.id[r.n++] = d.in2;
+  if (d.kind == DPB_OP_CONV && d.res >= 0) r.id[r.n++] = d.res;
+  return r;
 }
 
 // the launches of one pass (dpb_engine_stats): what DPB_LAUNCH counted while the pass ran, on every way out of it
@@ -195,12 +222,12 @@ int gemm(dpb_engine* e, GemmArgs a, bool can_defer = false) {
     if (int r = flush_pending(e)) return r;
   gemm_prep(e, a);
   GemmArgs* pend = (can_defer && g_lazy_reduce) ? &e->pend.a : nullptr;
-  const double kk = (double)a.K + (a.A2 ? a.K2 : 0);
-  e->flops += 2.0 * a.M * (double)a.N * kk * a.Z1 * a.Z2;
+  const double fl = 2.0 * a.M * (double)a.N * ((double)a.K + (a.A2 ? a.K2 : 0)) * a.Z1 * a.Z2;
+  e->flops += fl;
   e->gbytes += ((double)a.M * a.K + (double)a.N * a.K + (double)a.M * a.N) * a.Z1 * a.Z2 * e->es;
   const GemmPlan pl = gemm_plan(e->dtype, a);   // the one dispatch of this launch: launch_gemm runs it, the bracket is labelled with its tile's profile kind
   // (-1 with profiling off) the same bracket helpers as the attention launches (an event that cannot be created or recorded costs the bracket, never leaks its partner)
-  const int pi = prof_open(e, 2.0 * a.M * (double)a.N * kk * a.Z1 * a.Z2, pl.row ? pl.row->kind : 0, a.M, a.N, a.K, a.Z1 * a.Z2, a.gather);
+  const int pi = prof_open(e, fl, pl.row ? pl.row->kind : 0, a.M, a.N, a.K, a.Z1 * a.Z2, a.gather);
   const int r = launch_gemm(e->dtype, a, e->stream, pend, &pl);
   e->pend.on = pend && pend->splitk > 1;
   prof_close(e, pi);
@@ -208,13 +235,14 @@ int gemm(dpb_engine* e, GemmArgs a, bool can_defer = false) {
 }
 
 // ------------------------------------------------------------------ CONV
-// mode 0 primal (n=B), 1 tangent (n=nt)
-int conv_fwd(dpb_engine* e, const Op& op, int mode, int n) {
+// primal (n=B) or tangent (n=nt)
+int conv_fwd(dpb_engine* e, const Op& op, const Pass& ps, int n) {
   const dpb_op_desc& d = op.d;
+  const int mode = ps.mode;
   const int H = d.ip[0], W = d.ip[1], Cin = d.ip[2], Ho = d.ip[3], Wo = d.ip[4], Cout = d.ip[5], KS = d.ip[6];
   const Buf& bi = e->bufs[d.in0];
   const Buf& bo = e->bufs[d.out];
-  if (mode == 1 && !e->bact[d.in0]) {   // only the residual carries a tangent
+  if (mode == 1 && !ps.bact[d.in0]) {   // only the residual carries a tangent
     return launch_axpy(e->dtype, e->T(d.res), e->T(d.out), (long)n * bo.rows * bo.C, 0, e->stream);
   }
   GemmArgs g;
@@ -243,7 +271,7 @@ int conv_fwd(dpb_engine* e, const Op& op, int mode, int n) {
       g.rowbias_div = 1 << 30;
     }
   }
-  if (d.res >= 0 && (mode == 0 || e->bact[d.res])) {
+  if (d.res >= 0 && (mode == 0 || ps.bact[d.res])) {
     g.R = mode == 0 ? e->P(d.res) : e->T(d.res);
     g.ldr = e->bufs[d.res].C;
   }
@@ -269,7 +297,7 @@ int conv_fwd(dpb_engine* e, const Op& op, int mode, int n) {
       return gemm(e, f);
     }
   }
-  if (mode == 0 && e->fwd_only && op.geglu_next >= 0 && g_geglu_fwd && !shared_out && d.out != e->cur_tap && d.out != e->fwd_seed) {   // (a pass that stops AT h needs h written)
+  if (mode == 0 && !ps.fwd.stash && op.geglu_next >= 0 && g_geglu_fwd && !shared_out && d.out != ps.tap && d.out != ps.fwd.seed) {   // (a pass that stops AT h needs h written)
     // forward only (dpb_forward): an FF-in product that runs unsplit anyway applies GEGLU in its epilogue -- h [rows][2F] is neither written nor
     // re-read (84 MB per 64x64-level layer at batch 2), one launch less; bitwise the separate product + GEGLU kernel
     const dpb_op_desc& gd = e->ops[op.geglu_next].d;
@@ -288,13 +316,13 @@ int conv_fwd(dpb_engine* e, const Op& op, int mode, int n) {
   return gemm(e, g, mode == 1 && !shared_out);
 }
 
-int conv_adj(dpb_engine* e, const Op& op, int n) {
+int conv_adj(dpb_engine* e, const Op& op, const Pass& ps, int n) {
   const dpb_op_desc& d = op.d;
   const int H = d.ip[0], W = d.ip[1], Cin = d.ip[2], Ho = d.ip[3], Wo = d.ip[4], KS = d.ip[6];
   const Buf& bi = e->bufs[d.in0];
   const Buf& bo = e->bufs[d.out];
   const int Cout = bo.C;              // padded channel count of the cotangent (w[1] is [Cin][KS*KS*CoutPadded])
-  if (e->bact[d.in0]) {
+  if (ps.bact[d.in0]) {
     if (!d.w[1]) return fail("conv op has no transposed weight (w[1]) but its adjoint is needed");
     GemmArgs g;
     g.A = e->G(d.out);
@@ -308,7 +336,7 @@ int conv_adj(dpb_engine* e, const Op& op, int n) {
     // the LayerNorm that wrote this product's input: its adjoint in the epilogue (K <= 1024: beyond -- the FF-in adjoint, K = 8 C -- the
     // row-complete tile's one block per CU loses more in the K loop than the fusion saves: g_ln_fuse bit 1 forces it for A/Bs)
     // (not when the input is the seed: the LayerNorm / GEGLU that wrote it is upstream of the pass, its cotangent G(seed) is the result)
-    if (gather == GATHER_NONE && op.ln_prev >= 0 && g_ln_fuse && e->uses[d.in0] == 1 && d.in0 != e->src && (g.K <= g_ln_kmax || (g_ln_fuse & 2))) {
+    if (gather == GATHER_NONE && op.ln_prev >= 0 && g_ln_fuse && e->uses[d.in0] == 1 && d.in0 != ps.src && (g.K <= g_ln_kmax || (g_ln_fuse & 2))) {
       const dpb_op_desc& ld = e->ops[op.ln_prev].d;
       GemmArgs f = g;
       f.M = n * bi.rows;
@@ -322,7 +350,7 @@ int conv_adj(dpb_engine* e, const Op& op, int n) {
         goto residual;
       }
     }
-    if (gather == GATHER_NONE && op.geglu_prev >= 0 && d.in0 != e->src) {   // FF-out adjoint: GEGLU's adjoint in the epilogue, gy [rows][F] is never written
+    if (gather == GATHER_NONE && op.geglu_prev >= 0 && d.in0 != ps.src) {   // FF-out adjoint: GEGLU's adjoint in the epilogue, gy [rows][F] is never written
       const dpb_op_desc& gd = e->ops[op.geglu_prev].d;
       GemmArgs f = g;
       f.M = n * bi.rows;
@@ -335,7 +363,7 @@ int conv_adj(dpb_engine* e, const Op& op, int n) {
         goto residual;
       }
     }
-    const bool lone = e->uses[d.in0] == 1 && d.in0 != e->src;     // the cotangent has this one contribution: its producer's adjoint may add the slabs
+    const bool lone = e->uses[d.in0] == 1 && d.in0 != ps.src;     // the cotangent has this one contribution: its producer's adjoint may add the slabs
     if (gather == GATHER_NONE) {
       g.M = n * bi.rows;
       g.C = e->G(d.in0);
@@ -359,7 +387,7 @@ int conv_adj(dpb_engine* e, const Op& op, int n) {
     e->ginit[d.in0] = 1;
   }
 residual:
-  if (d.res >= 0 && e->bact[d.res]) {
+  if (d.res >= 0 && ps.bact[d.res]) {
     Buf& br = e->bufs[d.res];
     if (!e->ginit[d.res] && br.rows == bo.rows && br.C == bo.C && br.kind == bo.kind) {
       // first cotangent of the residual stream: G(out) is dead once its producer (this op) has run, so hand its storage
@@ -399,7 +427,25 @@ bool consumes_pending(dpb_engine* e, const Op& op, int mode) {
   return true;
 }
 
-int gn_run(dpb_engine* e, const Op& op, int mode, int n) {
+// What GNArgs / LNArgs / GegluArgs share (same member names, kernels.h): the sample counts and, by mode, the input d, the output y and the
+// first-write / accumulate flag of the cotangent
+template <class A>
+void fill_io(dpb_engine* e, const dpb_op_desc& d, const Pass& ps, int n, A& a) {
+  if (ps.mode == MODE_PRIMAL) { a.Bp = n; a.y = e->P(d.out); return; }
+  a.Bp = e->cur_batch; a.NT = n; a.kps = n / e->cur_batch;
+  if (ps.mode == MODE_TANGENT) { a.d = e->T(d.in0); a.y = e->T(d.out); return; }
+  a.d = e->G(d.out); a.y = e->G(d.in0);
+  a.accumulate = e->ginit[d.in0];
+  e->ginit[d.in0] = 1;
+}
+// ... and for the two normalisations, whose d may come from the parked product's slabs
+template <class A>
+void fill_norm_io(dpb_engine* e, const dpb_op_desc& d, const Pass& ps, int n, A& a) {
+  fill_io(e, d, ps, n, a);
+  if (ps.mode != MODE_PRIMAL) take_pending(e, a.src, a.d, ps.mode == MODE_TANGENT && (e->uses[d.in0] > 1 || d.in0 == ps.tap));
+}
+
+int gn_run(dpb_engine* e, const Op& op, const Pass& ps, int n) {
   const dpb_op_desc& d = op.d;
   const Buf& bi = e->bufs[d.in0];
   GNArgs a;
@@ -411,28 +457,11 @@ int gn_run(dpb_engine* e, const Op& op, int mode, int n) {
   a.part = (float*)(e->ws + e->gnpart); a.part_bytes = e->gnpart_bytes; a.ticket = (int*)(e->ws + e->gnticket);
   a.det = gn_deterministic();
   a.HW = bi.rows; a.C = bi.C; a.G = d.ip[0]; a.silu = d.ip[1]; a.eps = d.fp[0];
-  a.Bp = e->cur_batch;
-  if (mode == MODE_PRIMAL) {
-    a.Bp = n;
-    a.y = e->P(d.out);
-  } else {
-    a.NT = n;
-    a.kps = n / e->cur_batch;
-    if (mode == MODE_TANGENT) {
-      a.d = e->T(d.in0);
-      a.y = e->T(d.out);
-    } else {
-      a.d = e->G(d.out);
-      a.y = e->G(d.in0);
-      a.accumulate = e->ginit[d.in0];
-      e->ginit[d.in0] = 1;
-    }
-    take_pending(e, a.src, a.d, mode == MODE_TANGENT && (e->uses[d.in0] > 1 || d.in0 == e->cur_tap));
-  }
-  return launch_groupnorm(e->dtype, mode, a, e->stream);
+  fill_norm_io(e, d, ps, n, a);
+  return launch_groupnorm(e->dtype, ps.mode, a, e->stream);
 }
 
-int ln_run(dpb_engine* e, const Op& op, int mode, int n) {
+int ln_run(dpb_engine* e, const Op& op, const Pass& ps, int n) {
   const dpb_op_desc& d = op.d;
   const Buf& bi = e->bufs[d.in0];
   LNArgs a;
@@ -440,78 +469,46 @@ int ln_run(dpb_engine* e, const Op& op, int mode, int n) {
   a.gamma = (const float*)d.w[0];
   a.beta = (const float*)d.w[1];
   a.rows_per_sample = bi.rows; a.C = bi.C; a.eps = d.fp[0];
-  a.Bp = e->cur_batch;
-  if (mode == MODE_PRIMAL) {
-    a.Bp = n;
-    a.y = e->P(d.out);
-  } else {
-    a.NT = n;
-    a.kps = n / e->cur_batch;
-    if (mode == MODE_TANGENT) {
-      a.d = e->T(d.in0);
-      a.y = e->T(d.out);
-    } else {
-      a.d = e->G(d.out);
-      a.y = e->G(d.in0);
-      a.accumulate = e->ginit[d.in0];
-      e->ginit[d.in0] = 1;
-    }
-    take_pending(e, a.src, a.d, mode == MODE_TANGENT && (e->uses[d.in0] > 1 || d.in0 == e->cur_tap));
-  }
-  return launch_layernorm(e->dtype, mode, a, e->stream);
+  fill_norm_io(e, d, ps, n, a);
+  return launch_layernorm(e->dtype, ps.mode, a, e->stream);
 }
 
-int geglu_run(dpb_engine* e, const Op& op, int mode, int n) {
+int geglu_run(dpb_engine* e, const Op& op, const Pass& ps, int n) {
   const dpb_op_desc& d = op.d;
   const Buf& bi = e->bufs[d.in0];
   GegluArgs a;
   a.h = e->P(d.in0);
   a.rows_per_sample = bi.rows; a.F = bi.C / 2; a.il = d.ip[1];
-  a.Bp = e->cur_batch;
-  if (mode == MODE_PRIMAL) {
-    a.Bp = n;
-    a.y = e->P(d.out);
-    a.stash = !e->fwd_only;
-  } else {
-    a.NT = n;
-    a.kps = n / e->cur_batch;
-    if (mode == MODE_TANGENT) {
-      a.d = e->T(d.in0);
-      a.y = e->T(d.out);
-    } else {
-      a.d = e->G(d.out);
-      a.y = e->G(d.in0);
-      a.accumulate = e->ginit[d.in0];
-      e->ginit[d.in0] = 1;
-    }
-  }
-  return launch_geglu(e->dtype, mode, a, e->stream);
+  a.stash = ps.fwd.stash;
+  fill_io(e, d, ps, n, a);
+  return launch_geglu(e->dtype, ps.mode, a, e->stream);
 }
 
-int concat_run(dpb_engine* e, const Op& op, int mode, int n) {
+int concat_run(dpb_engine* e, const Op& op, const Pass& ps, int n) {
   const dpb_op_desc& d = op.d;
+  const int mode = ps.mode;
   const Buf& b0 = e->bufs[d.in0];
   const Buf& b1 = e->bufs[d.in1];
   const Buf& bo = e->bufs[d.out];
   const long rows = (long)n * bo.rows;
   if (mode == MODE_ADJOINT) {
-    if (e->bact[d.in0]) {
+    if (ps.bact[d.in0]) {
       if (int r = launch_copy_cols(e->dtype, e->G(d.out), bo.C, 0, e->G(d.in0), b0.C, 0, rows, b0.C, e->ginit[d.in0], e->stream)) return r;
       e->ginit[d.in0] = 1;
     }
-    if (e->bact[d.in1]) {
+    if (ps.bact[d.in1]) {
       if (int r = launch_copy_cols(e->dtype, e->G(d.out), bo.C, b0.C, e->G(d.in1), b1.C, 0, rows, b1.C, e->ginit[d.in1], e->stream)) return r;
       e->ginit[d.in1] = 1;
     }
     return 0;
   }
-  if (mode == MODE_TANGENT && (!e->bact[d.in0] || !e->bact[d.in1])) {
+  if (mode == MODE_TANGENT && (!ps.bact[d.in0] || !ps.bact[d.in1])) {
     // one operand does not depend on the seed (the skip half of an up-block concat when the pass starts at a tap): its window of the tangent
     // is zero -- written on every pass, since a pass of another seed may have left a tangent in that storage
     char* o = e->T(d.out);
-    if (int r = e->bact[d.in0] ? launch_copy_cols(e->dtype, e->T(d.in0), b0.C, 0, o, bo.C, 0, rows, b0.C, 0, e->stream)
+    if (int r = ps.bact[d.in0] ? launch_copy_cols(e->dtype, e->T(d.in0), b0.C, 0, o, bo.C, 0, rows, b0.C, 0, e->stream)
                                : launch_zero_cols(e->dtype, o, bo.C, 0, rows, b0.C, e->stream)) return r;
-    return e->bact[d.in1] ? launch_copy_cols(e->dtype, e->T(d.in1), b1.C, 0, o, bo.C, b0.C, rows, b1.C, 0, e->stream)
+    return ps.bact[d.in1] ? launch_copy_cols(e->dtype, e->T(d.in1), b1.C, 0, o, bo.C, b0.C, rows, b1.C, 0, e->stream)
                           : launch_zero_cols(e->dtype, o, bo.C, b0.C, rows, b1.C, e->stream);
   }
   char* o = mode == MODE_PRIMAL ? e->P(d.out) : e->T(d.out);
@@ -539,12 +536,60 @@ static AttnPtrs attn_ptrs(dpb_engine* e, const dpb_op_desc& d, const AttnPlan& p
   return a;
 }
 
-static void fill_fused(dpb_engine* e, const AttnPlan& p, const AttnPtrs& x, FusedAttnArgs& f, int kps, float scale);
+void fill_fused(dpb_engine* e, const AttnPlan& p, const AttnPtrs& x, FusedAttnArgs& f, int kps, float scale) {
+  char* ws = e->ws;
+  f.Q = x.Q; f.K = x.K; f.V = x.V; f.O = x.O; f.VT = ws + p.VT; f.KT = ws + p.KT; f.QT = ws + p.QT;
+  f.stats = (const float*)(ws + p.stats);
+  f.L = p.Lq; f.C = x.ldq; f.Co = x.ldo; f.H = p.heads; f.d = p.d; f.kps = kps; f.scale = scale; f.fl = e->dtype == DT_F16;
+}
+// one-launch constant-K/V attention: Y [..][Cy] from X [..][Cx] (and BT, the per-head transpose the pass needs) on the primal q, k, v
+void fill_cross(dpb_engine* e, const AttnPlan& p, const AttnPtrs& x, CrossAttnArgs& f, int kps, float scale, const void* BT, const void* X, int Cx,
+                void* Y, int Cy) {
+  f.Q = x.Q; f.K = x.K; f.V = x.V; f.BT = BT; f.X = X; f.Y = Y;
+  f.L = p.Lq; f.Lk = p.Lk; f.Lkp = p.Lkp; f.C = x.ldq; f.Ck = x.ldk; f.Cx = Cx; f.Cy = Cy;
+  f.H = p.heads; f.d = p.d; f.kps = kps; f.scale = scale; f.fl = e->dtype == DT_F16;
+}
 
-int attn_primal(dpb_engine* e, const Op& op, int B) {
+// one attention launch with its flops (n_prod L x L x d products per sample or tangent and head) counted and its measurement bracket around it
+template <class F>
+int attn_launch(dpb_engine* e, const AttnPlan& p, int kind, int n_prod, int Z1, int gather, F launch) {
+  const double fl = 2.0 * p.Lq * (double)p.Lk * p.d * n_prod * Z1 * p.heads;
+  e->flops += fl;
+  const int pi = prof_open(e, fl, kind, p.Lq, p.Lk, p.d, Z1 * p.heads, gather);
+  const int r = launch();
+  prof_close(e, pi);
+  return r;
+}
+
+// The operands of the materialised path's batched products (z1: sample or tangent, z2: head) have one of two per-head layouts:
+//   rows: head h is the column window [h d, (h + 1) d) of a [L][ld] row buffer   -> sample stride L ld, head stride d
+//   tile: head h is a dense [rows][Lp] tile of a [Z][H][rows][Lp] scratch tensor -> sample stride H rows Lp, head stride rows Lp
+// div: the operand is a primal one, shared by the `div` tangents of a sample.
+enum Side { SIDE_A, SIDE_B, SIDE_C, SIDE_A2, SIDE_B2 };
+void set_side(GemmArgs& g, Side s, const void* ptr, int ld, long s1, long s2, int div) {
+  switch (s) {
+    case SIDE_A: g.A = ptr; g.lda = ld; g.sA1 = s1; g.sA2 = s2; g.divA = div; break;
+    case SIDE_B: g.B = ptr; g.ldb = ld; g.sB1 = s1; g.sB2 = s2; g.divB = div; break;
+    case SIDE_C: g.C = (void*)ptr; g.ldc = ld; g.sC1 = s1; g.sC2 = s2; break;
+    case SIDE_A2: g.A2 = ptr; g.lda2 = ld; g.sA21 = s1; g.sA22 = s2; g.divA2 = div; break;
+    case SIDE_B2: g.B2 = ptr; g.ldb2 = ld; g.sB21 = s1; g.sB22 = s2; g.divB2 = div; break;
+  }
+}
+void side_rows(GemmArgs& g, Side s, const void* ptr, int ld, int L, int d, int div = 1) { set_side(g, s, ptr, ld, (long)L * ld, d, div); }
+void side_tile(GemmArgs& g, Side s, const void* ptr, int H, int rows, int Lp, int div = 1) {
+  set_side(g, s, ptr, Lp, (long)H * rows * Lp, (long)rows * Lp, div);
+}
+void dims(GemmArgs& g, int M, int N, int K, int Z1, int Z2, float alpha = 1.f) { g.M = M; g.N = N; g.K = K; g.Z1 = Z1; g.Z2 = Z2; g.alpha = alpha; }
+// rows layout [Z][L][ld] -> per-head transposes [Z][H][d][Lp] (zero padded)
+int head_transpose(dpb_engine* e, const AttnPlan& p, const void* in, int ld, void* out, int Z, int L, int Lp) {
+  return launch_transpose(e->dtype, in, out, Z, p.heads, (long)L * ld, p.d, L, p.d, ld, Lp, (long)p.d * Lp, e->stream);
+}
+
+int attn_primal(dpb_engine* e, const Op& op, const Pass& ps, int B) {
   const dpb_op_desc& d = op.d;
   const AttnPlan& p = e->plans[op.attn];
   const int H = p.heads;
+  const bool stash = ps.fwd.stash;
   const float scale = 1.f / sqrtf((float)p.d);
   char* ws = e->ws;
   const AttnPtrs x = attn_ptrs(e, d, p, 0);
@@ -552,58 +597,41 @@ int attn_primal(dpb_engine* e, const Op& op, int B) {
                    // LDS transpose reads from the row tiles, so no per-head transposed copies are kept either
     FusedAttnArgs f;
     fill_fused(e, p, x, f, 1, scale);
-    const double fl = 2.0 * p.Lq * (double)p.Lk * p.d * 2 * B * H;
-    e->flops += fl;
-    const int pi = prof_open(e, fl, 7, p.Lq, p.Lk, p.d, B * H, 0);
-    const int r = launch_attn_fwd_fused(f, B, x.O, (float*)(ws + p.stats), e->stream);
-    prof_close(e, pi);
-    return r;
+    return attn_launch(e, p, 7, 2, B, 0, [&] { return launch_attn_fwd_fused(f, B, x.O, (float*)(ws + p.stats), e->stream); });
   }
   if (p.cross && g_cross_primal) {
     // text-conditioned layers: O = softmax(scale Q K^T) V in ONE launch (the 77 keys fit one masked tile; V^T is built in LDS), instead of
     // GEMM + softmax + transpose + GEMM; the tangent / adjoint kernels of the pullback passes still read the per-head V^T / K^T copies
     CrossAttnArgs f;
-    f.Q = x.Q; f.K = x.K; f.V = x.V; f.BT = nullptr; f.X = nullptr; f.Y = x.O;
-    f.L = p.Lq; f.Lk = p.Lk; f.Lkp = p.Lkp; f.C = x.ldq; f.Ck = x.ldk; f.Cx = x.ldq; f.Cy = x.ldo;
-    f.H = H; f.d = p.d; f.kps = 1; f.primal = 1; f.scale = scale; f.fl = e->dtype == DT_F16;
-    const double fl = 2.0 * p.Lq * (double)p.Lk * p.d * 2 * B * H;
-    e->flops += fl;
-    const int pi = prof_open(e, fl, 10, p.Lq, p.Lk, p.d, B * H, 2);
-    const int r = launch_attn_cross(f, B, e->stream);
-    prof_close(e, pi);
-    if (r || e->fwd_only) return r;
-    if (int r2 = launch_transpose(e->dtype, x.V, ws + p.VT, B, H, (long)p.Lk * x.ldv, p.d, p.Lk, p.d, x.ldv, p.Lkp, (long)p.d * p.Lkp, e->stream)) return r2;
-    return launch_transpose(e->dtype, x.K, ws + p.KT, B, H, (long)p.Lk * x.ldk, p.d, p.Lk, p.d, x.ldk, p.Lkp, (long)p.d * p.Lkp, e->stream);
+    fill_cross(e, p, x, f, 1, scale, nullptr, nullptr, x.ldq, x.O, x.ldo);
+    f.primal = 1;
+    const int r = attn_launch(e, p, 10, 2, B, 2, [&] { return launch_attn_cross(f, B, e->stream); });
+    if (r || !stash) return r;
+    if (int r2 = head_transpose(e, p, x.V, x.ldv, ws + p.VT, B, p.Lk, p.Lkp)) return r2;
+    return head_transpose(e, p, x.K, x.ldk, ws + p.KT, B, p.Lk, p.Lkp);
   }
   GemmArgs g;   // S = scale * Q K^T
-  g.A = x.Q; g.lda = x.ldq; g.sA1 = (long)p.Lq * x.ldq; g.sA2 = p.d;
-  g.B = x.K; g.ldb = x.ldk; g.sB1 = (long)p.Lk * x.ldk; g.sB2 = p.d;
-  g.C = ws + p.P; g.ldc = p.Lkp; g.sC1 = (long)H * p.Lq * p.Lkp; g.sC2 = (long)p.Lq * p.Lkp;
-  g.M = p.Lq; g.N = p.Lk; g.K = p.d; g.Z1 = B; g.Z2 = H; g.alpha = scale;
+  side_rows(g, SIDE_A, x.Q, x.ldq, p.Lq, p.d);
+  side_rows(g, SIDE_B, x.K, x.ldk, p.Lk, p.d);
+  side_tile(g, SIDE_C, ws + p.P, H, p.Lq, p.Lkp);
+  dims(g, p.Lq, p.Lk, p.d, B, H, scale);
   if (int r = gemm(e, g)) return r;
   if (int r = launch_softmax_fwd(e->dtype, ws + p.P, (long)B * H, p.Lq, p.Lk, p.Lkp, p.causal, e->stream)) return r;
   // V^T, K^T per head ([d][Lkp], zero padded)
-  if (int r = launch_transpose(e->dtype, x.V, ws + p.VT, B, H, (long)p.Lk * x.ldv, p.d, p.Lk, p.d, x.ldv, p.Lkp, (long)p.d * p.Lkp, e->stream)) return r;
-  if (!e->fwd_only)                 // K^T serves the adjoint only
-    if (int r = launch_transpose(e->dtype, x.K, ws + p.KT, B, H, (long)p.Lk * x.ldk, p.d, p.Lk, p.d, x.ldk, p.Lkp, (long)p.d * p.Lkp, e->stream)) return r;
+  if (int r = head_transpose(e, p, x.V, x.ldv, ws + p.VT, B, p.Lk, p.Lkp)) return r;
+  if (stash)                        // K^T serves the adjoint only
+    if (int r = head_transpose(e, p, x.K, x.ldk, ws + p.KT, B, p.Lk, p.Lkp)) return r;
   GemmArgs o;   // O = P V
-  o.A = ws + p.P; o.lda = p.Lkp; o.sA1 = (long)H * p.Lq * p.Lkp; o.sA2 = (long)p.Lq * p.Lkp;
-  o.B = ws + p.VT; o.ldb = p.Lkp; o.sB1 = (long)H * p.d * p.Lkp; o.sB2 = (long)p.d * p.Lkp;
-  o.C = x.O; o.ldc = x.ldo; o.sC1 = (long)p.Lq * x.ldo; o.sC2 = p.d;
-  o.M = p.Lq; o.N = p.d; o.K = p.Lkp; o.Z1 = B; o.Z2 = H;
+  side_tile(o, SIDE_A, ws + p.P, H, p.Lq, p.Lkp);
+  side_tile(o, SIDE_B, ws + p.VT, H, p.d, p.Lkp);
+  side_rows(o, SIDE_C, x.O, x.ldo, p.Lq, p.d);
+  dims(o, p.Lq, p.d, p.Lkp, B, H);
   if (int r = gemm(e, o)) return r;
-  if (!p.kv_const && !e->fwd_only) {
+  if (!p.kv_const && stash) {
     if (int r = launch_transpose(e->dtype, ws + p.P, ws + p.PT, B * H, 1, (long)p.Lq * p.Lkp, 0, p.Lq, p.Lk, p.Lkp, p.Lqp, (long)p.Lk * p.Lqp, e->stream)) return r;
-    if (int r = launch_transpose(e->dtype, x.Q, ws + p.QT, B, H, (long)p.Lq * x.ldq, p.d, p.Lq, p.d, x.ldq, p.Lqp, (long)p.d * p.Lqp, e->stream)) return r;
+    if (int r = head_transpose(e, p, x.Q, x.ldq, ws + p.QT, B, p.Lq, p.Lqp)) return r;
   }
   return 0;
-}
-
-static void fill_fused(dpb_engine* e, const AttnPlan& p, const AttnPtrs& x, FusedAttnArgs& f, int kps, float scale) {
-  char* ws = e->ws;
-  f.Q = x.Q; f.K = x.K; f.V = x.V; f.O = x.O; f.VT = ws + p.VT; f.KT = ws + p.KT; f.QT = ws + p.QT;
-  f.stats = (const float*)(ws + p.stats);
-  f.L = p.Lq; f.C = x.ldq; f.Co = x.ldo; f.H = p.heads; f.d = p.d; f.kps = kps; f.scale = scale; f.fl = e->dtype == DT_F16;
 }
 
 int attn_tangent(dpb_engine* e, const Op& op, int nt) {
@@ -618,47 +646,36 @@ int attn_tangent(dpb_engine* e, const Op& op, int nt) {
     FusedAttnArgs f;
     fill_fused(e, p, x, f, kps, scale);
     f.dQ = t.Q; f.dK = t.K; f.dV = t.V; f.dO = t.O;
-    const double fl = 2.0 * p.Lq * (double)p.Lk * p.d * 5 * nt * H;     // dS (2 products), dP V, P dV + the recomputed scores: 5 L x L x d products
-    e->flops += fl;
-    const int pi = prof_open(e, fl, 8, p.Lq, p.Lk, p.d, nt * H, attn_jvp_block_waves(p.d, p.Lq, nt * H));
-    const int r = launch_attn_jvp_fused(f, nt, e->stream);
-    prof_close(e, pi);
-    return r;
+    // dS (2 products), dP V, P dV + the recomputed scores: 5 L x L x d products
+    return attn_launch(e, p, 8, 5, nt, attn_jvp_block_waves(p.d, p.Lq, nt * H), [&] { return launch_attn_jvp_fused(f, nt, e->stream); });
   }
   if (p.cross) {   // constant K/V: dO = [P o (scale dQ K^T - delta)] V in one launch
     CrossAttnArgs f;
-    f.Q = x.Q; f.K = x.K; f.V = x.V; f.BT = ws + p.VT; f.X = t.Q; f.Y = t.O;
-    f.L = p.Lq; f.Lk = p.Lk; f.Lkp = p.Lkp; f.C = x.ldq; f.Ck = x.ldk; f.Cx = t.ldq; f.Cy = t.ldo;
-    f.H = H; f.d = p.d; f.kps = kps; f.adjoint = 0; f.scale = scale; f.fl = e->dtype == DT_F16;
-    const double fl = 2.0 * p.Lq * (double)p.Lk * p.d * 2 * nt * H;
-    e->flops += fl;
-    const int pi = prof_open(e, fl, 10, p.Lq, p.Lk, p.d, nt * H, 0);
-    const int r = launch_attn_cross(f, nt, e->stream);
-    prof_close(e, pi);
-    return r;
+    fill_cross(e, p, x, f, kps, scale, ws + p.VT, t.Q, t.ldq, t.O, t.ldo);
+    return attn_launch(e, p, 10, 2, nt, 0, [&] { return launch_attn_cross(f, nt, e->stream); });
   }
   GemmArgs g;   // dS = scale * dQ K^T
-  g.A = t.Q; g.lda = t.ldq; g.sA1 = (long)p.Lq * t.ldq; g.sA2 = p.d;
-  g.B = x.K; g.ldb = x.ldk; g.sB1 = (long)p.Lk * x.ldk; g.sB2 = p.d; g.divB = kps;
-  g.C = S1; g.ldc = p.Lkp; g.sC1 = (long)H * p.Lq * p.Lkp; g.sC2 = (long)p.Lq * p.Lkp;
-  g.M = p.Lq; g.N = p.Lk; g.K = p.d; g.Z1 = nt; g.Z2 = H; g.alpha = scale;
+  side_rows(g, SIDE_A, t.Q, t.ldq, p.Lq, p.d);
+  side_rows(g, SIDE_B, x.K, x.ldk, p.Lk, p.d, kps);
+  side_tile(g, SIDE_C, S1, H, p.Lq, p.Lkp);
+  dims(g, p.Lq, p.Lk, p.d, nt, H, scale);
   if (!p.kv_const) {   // + scale * Q dK^T in the same launch (second operand pair)
-    g.A2 = x.Q; g.lda2 = x.ldq; g.sA21 = (long)p.Lq * x.ldq; g.sA22 = p.d; g.divA2 = kps;
-    g.B2 = t.K; g.ldb2 = t.ldk; g.sB21 = (long)p.Lk * t.ldk; g.sB22 = p.d; g.divB2 = 1;
+    side_rows(g, SIDE_A2, x.Q, x.ldq, p.Lq, p.d, kps);
+    side_rows(g, SIDE_B2, t.K, t.ldk, p.Lk, p.d);
     g.K2 = p.d;
   }
   if (int r = gemm(e, g)) return r;
   if (int r = launch_softmax_jvp(e->dtype, ws + p.P, S1, nullptr, (long)nt * H, H, kps, p.Lq, p.Lk, p.Lkp, e->stream)) return r;
   GemmArgs o;   // dO = dP V
-  o.A = S1; o.lda = p.Lkp; o.sA1 = (long)H * p.Lq * p.Lkp; o.sA2 = (long)p.Lq * p.Lkp;
-  o.B = ws + p.VT; o.ldb = p.Lkp; o.sB1 = (long)H * p.d * p.Lkp; o.sB2 = (long)p.d * p.Lkp; o.divB = kps;
-  o.C = t.O; o.ldc = t.ldo; o.sC1 = (long)p.Lq * t.ldo; o.sC2 = p.d;
-  o.M = p.Lq; o.N = p.d; o.K = p.Lkp; o.Z1 = nt; o.Z2 = H;
+  side_tile(o, SIDE_A, S1, H, p.Lq, p.Lkp);
+  side_tile(o, SIDE_B, ws + p.VT, H, p.d, p.Lkp, kps);
+  side_rows(o, SIDE_C, t.O, t.ldo, p.Lq, p.d);
+  dims(o, p.Lq, p.d, p.Lkp, nt, H);
   if (!p.kv_const) {   // + P dV in the same launch
     char* T1 = ws + e->T1;
-    if (int r = launch_transpose(e->dtype, t.V, T1, nt, H, (long)p.Lk * t.ldv, p.d, p.Lk, p.d, t.ldv, p.Lkp, (long)p.d * p.Lkp, e->stream)) return r;
-    o.A2 = ws + p.P; o.lda2 = p.Lkp; o.sA21 = (long)H * p.Lq * p.Lkp; o.sA22 = (long)p.Lq * p.Lkp; o.divA2 = kps;
-    o.B2 = T1; o.ldb2 = p.Lkp; o.sB21 = (long)H * p.d * p.Lkp; o.sB22 = (long)p.d * p.Lkp; o.divB2 = 1;
+    if (int r = head_transpose(e, p, t.V, t.ldv, T1, nt, p.Lk, p.Lkp)) return r;
+    side_tile(o, SIDE_A2, ws + p.P, H, p.Lq, p.Lkp, kps);
+    side_tile(o, SIDE_B2, T1, H, p.d, p.Lkp);
     o.K2 = p.Lkp;
   }
   return gemm(e, o);
@@ -685,41 +702,31 @@ int attn_adjoint(dpb_engine* e, const Op& op, int nt) {
     fill_fused(e, p, x, f, kps, scale);
     f.gO = gO; f.gQ = (void*)c.Q; f.gK = (void*)c.K; f.gV = (void*)c.V; f.Drow = Dv;
     f.accQ = accQ; f.accK = accK; f.accV = accV;
-    const double fl = 2.0 * p.Lq * (double)p.Lk * p.d * 7 * nt * H;     // query-major: scores, gP, gQ (3); key-major: scores^T, gP^T, gV, gK (4)
-    e->flops += fl;
-    const int pi = prof_open(e, fl, 9, p.Lq, p.Lk, p.d, nt * H, attn_adj_route_bits(p.d, p.Lq, kps, nt));
-    const int r = launch_attn_adj_fused(f, nt, e->stream);
-    prof_close(e, pi);
-    if (r) return r;
+    // query-major: scores, gP, gQ (3); key-major: scores^T, gP^T, gV, gK (4)
+    if (int r = attn_launch(e, p, 9, 7, nt, attn_adj_route_bits(p.d, p.Lq, kps, nt), [&] { return launch_attn_adj_fused(f, nt, e->stream); })) return r;
     e->ginit[d.in0] = e->ginit[d.in1] = e->ginit[d.in2] = 1;
     return 0;
   }
   if (p.cross) {   // constant K/V: gQ (+)= scale [P o (gO V^T - delta)] K in one launch
     CrossAttnArgs f;
-    f.Q = x.Q; f.K = x.K; f.V = x.V; f.BT = ws + p.KT; f.X = gO; f.Y = (void*)c.Q;
-    f.L = p.Lq; f.Lk = p.Lk; f.Lkp = p.Lkp; f.C = x.ldq; f.Ck = x.ldk; f.Cx = c.ldo; f.Cy = c.ldq;
-    f.H = H; f.d = p.d; f.kps = kps; f.adjoint = 1; f.accumulate = accQ; f.scale = scale; f.fl = e->dtype == DT_F16;
-    const double fl = 2.0 * p.Lq * (double)p.Lk * p.d * 2 * nt * H;
-    e->flops += fl;
-    const int pi = prof_open(e, fl, 10, p.Lq, p.Lk, p.d, nt * H, 1);
-    const int r = launch_attn_cross(f, nt, e->stream);
-    prof_close(e, pi);
-    if (r) return r;
+    fill_cross(e, p, x, f, kps, scale, ws + p.KT, gO, c.ldo, (void*)c.Q, c.ldq);
+    f.adjoint = 1; f.accumulate = accQ;
+    if (int r = attn_launch(e, p, 10, 2, nt, 1, [&] { return launch_attn_cross(f, nt, e->stream); })) return r;
     e->ginit[d.in0] = 1;
     return 0;
   }
   GemmArgs g;   // gP = gO V^T
-  g.A = gO; g.lda = c.ldo; g.sA1 = (long)p.Lq * c.ldo; g.sA2 = p.d;
-  g.B = x.V; g.ldb = x.ldv; g.sB1 = (long)p.Lk * x.ldv; g.sB2 = p.d; g.divB = kps;
-  g.C = S1; g.ldc = p.Lkp; g.sC1 = (long)H * p.Lq * p.Lkp; g.sC2 = (long)p.Lq * p.Lkp;
-  g.M = p.Lq; g.N = p.Lk; g.K = p.d; g.Z1 = nt; g.Z2 = H;
+  side_rows(g, SIDE_A, gO, c.ldo, p.Lq, p.d);
+  side_rows(g, SIDE_B, x.V, x.ldv, p.Lk, p.d, kps);
+  side_tile(g, SIDE_C, S1, H, p.Lq, p.Lkp);
+  dims(g, p.Lq, p.Lk, p.d, nt, H);
   if (int r = gemm(e, g)) return r;
   if (int r = launch_softmax_jvp(e->dtype, ws + p.P, S1, p.kv_const ? nullptr : Dv, (long)nt * H, H, kps, p.Lq, p.Lk, p.Lkp, e->stream)) return r;
   GemmArgs q;   // gQ (+)= scale * gS K
-  q.A = S1; q.lda = p.Lkp; q.sA1 = (long)H * p.Lq * p.Lkp; q.sA2 = (long)p.Lq * p.Lkp;
-  q.B = ws + p.KT; q.ldb = p.Lkp; q.sB1 = (long)H * p.d * p.Lkp; q.sB2 = (long)p.d * p.Lkp; q.divB = kps;
-  q.C = (void*)c.Q; q.ldc = c.ldq; q.sC1 = (long)p.Lq * c.ldq; q.sC2 = p.d;
-  q.M = p.Lq; q.N = p.d; q.K = p.Lkp; q.Z1 = nt; q.Z2 = H; q.alpha = scale;
+  side_tile(q, SIDE_A, S1, H, p.Lq, p.Lkp);
+  side_tile(q, SIDE_B, ws + p.KT, H, p.d, p.Lkp, kps);
+  side_rows(q, SIDE_C, c.Q, c.ldq, p.Lq, p.d);
+  dims(q, p.Lq, p.d, p.Lkp, nt, H, scale);
   q.accumulate = accQ;
   if (int r = gemm(e, q)) return r;
   e->ginit[d.in0] = 1;
@@ -727,51 +734,49 @@ int attn_adjoint(dpb_engine* e, const Op& op, int nt) {
   char* T1 = ws + e->T1;
   char* S2 = ws + e->S2;
   // gO^T per head [d][Lqp]
-  if (int r = launch_transpose(e->dtype, gO, T1, nt, H, (long)p.Lq * c.ldo, p.d, p.Lq, p.d, c.ldo, p.Lqp, (long)p.d * p.Lqp, e->stream)) return r;
+  if (int r = head_transpose(e, p, gO, c.ldo, T1, nt, p.Lq, p.Lqp)) return r;
   GemmArgs v;   // gV (+)= P^T gO
-  v.A = ws + p.PT; v.lda = p.Lqp; v.sA1 = (long)H * p.Lk * p.Lqp; v.sA2 = (long)p.Lk * p.Lqp; v.divA = kps;
-  v.B = T1; v.ldb = p.Lqp; v.sB1 = (long)H * p.d * p.Lqp; v.sB2 = (long)p.d * p.Lqp;
-  v.C = (void*)c.V; v.ldc = c.ldv; v.sC1 = (long)p.Lk * c.ldv; v.sC2 = p.d;
-  v.M = p.Lk; v.N = p.d; v.K = p.Lqp; v.Z1 = nt; v.Z2 = H;
+  side_tile(v, SIDE_A, ws + p.PT, H, p.Lk, p.Lqp, kps);
+  side_tile(v, SIDE_B, T1, H, p.d, p.Lqp);
+  side_rows(v, SIDE_C, c.V, c.ldv, p.Lk, p.d);
+  dims(v, p.Lk, p.d, p.Lqp, nt, H);
   v.accumulate = accV;
   if (int r = gemm(e, v)) return r;
   GemmArgs t;   // gP^T = V gO^T
-  t.A = x.V; t.lda = x.ldv; t.sA1 = (long)p.Lk * x.ldv; t.sA2 = p.d; t.divA = kps;
-  t.B = gO; t.ldb = c.ldo; t.sB1 = (long)p.Lq * c.ldo; t.sB2 = p.d;
-  t.C = S2; t.ldc = p.Lqp; t.sC1 = (long)H * p.Lk * p.Lqp; t.sC2 = (long)p.Lk * p.Lqp;
-  t.M = p.Lk; t.N = p.Lq; t.K = p.d; t.Z1 = nt; t.Z2 = H;
+  side_rows(t, SIDE_A, x.V, x.ldv, p.Lk, p.d, kps);
+  side_rows(t, SIDE_B, gO, c.ldo, p.Lq, p.d);
+  side_tile(t, SIDE_C, S2, H, p.Lk, p.Lqp);
+  dims(t, p.Lk, p.Lq, p.d, nt, H);
   if (int r = gemm(e, t)) return r;
   if (int r = launch_softmax_adjT(e->dtype, ws + p.PT, S2, Dv, (long)nt * H, H, kps, p.Lk, p.Lq, p.Lqp, e->stream)) return r;
   GemmArgs k;   // gK (+)= scale * gS^T Q
-  k.A = S2; k.lda = p.Lqp; k.sA1 = (long)H * p.Lk * p.Lqp; k.sA2 = (long)p.Lk * p.Lqp;
-  k.B = ws + p.QT; k.ldb = p.Lqp; k.sB1 = (long)H * p.d * p.Lqp; k.sB2 = (long)p.d * p.Lqp; k.divB = kps;
-  k.C = (void*)c.K; k.ldc = c.ldk; k.sC1 = (long)p.Lk * c.ldk; k.sC2 = p.d;
-  k.M = p.Lk; k.N = p.d; k.K = p.Lqp; k.Z1 = nt; k.Z2 = H; k.alpha = scale;
+  side_tile(k, SIDE_A, S2, H, p.Lk, p.Lqp);
+  side_tile(k, SIDE_B, ws + p.QT, H, p.d, p.Lqp, kps);
+  side_rows(k, SIDE_C, c.K, c.ldk, p.Lk, p.d);
+  dims(k, p.Lk, p.d, p.Lqp, nt, H, scale);
   k.accumulate = accK;
   if (int r = gemm(e, k)) return r;
   e->ginit[d.in1] = e->ginit[d.in2] = 1;
   return 0;
 }
 
-int run_op(dpb_engine* e, const Op& op, int mode, int n) {
+int run_op(dpb_engine* e, const Op& op, const Pass& ps, int n) {
+  const int mode = ps.mode;
   if (e->pend.on && !consumes_pending(e, op, mode))
     if (int r = flush_pending(e)) return r;
   switch (op.d.kind) {
-    case DPB_OP_CONV: return mode == MODE_ADJOINT ? conv_adj(e, op, n) : conv_fwd(e, op, mode, n);
-    case DPB_OP_GROUPNORM: return gn_run(e, op, mode, n);
-    case DPB_OP_LAYERNORM: return ln_run(e, op, mode, n);
-    case DPB_OP_GEGLU: return geglu_run(e, op, mode, n);
-    case DPB_OP_CONCAT: return concat_run(e, op, mode, n);
+    case DPB_OP_CONV: return mode == MODE_ADJOINT ? conv_adj(e, op, ps, n) : conv_fwd(e, op, ps, n);
+    case DPB_OP_GROUPNORM: return gn_run(e, op, ps, n);
+    case DPB_OP_LAYERNORM: return ln_run(e, op, ps, n);
+    case DPB_OP_GEGLU: return geglu_run(e, op, ps, n);
+    case DPB_OP_CONCAT: return concat_run(e, op, ps, n);
     case DPB_OP_ATTENTION:
-      return mode == MODE_PRIMAL ? attn_primal(e, op, n) : mode == MODE_TANGENT ? attn_tangent(e, op, n) : attn_adjoint(e, op, n);
+      return mode == MODE_PRIMAL ? attn_primal(e, op, ps, n) : mode == MODE_TANGENT ? attn_tangent(e, op, n) : attn_adjoint(e, op, n);
     case DPB_OP_SILU: {
       if (mode != MODE_PRIMAL) return fail("SILU / quick-GELU ops are primal only (time-embedding path, text encoder)");
       const Buf& b = e->bufs[op.d.in0];
-      if (op.d.ip[0] == 2)
-        return launch_gelu(e->dtype, e->P(op.d.in0), e->P(op.d.out), (long)(b.kind == DPB_BUF_SHARED ? 1 : n) * b.rows * b.C, e->stream);
-      if (op.d.ip[0] == 1)
-        return launch_quick_gelu(e->dtype, e->P(op.d.in0), e->P(op.d.out), (long)(b.kind == DPB_BUF_SHARED ? 1 : n) * b.rows * b.C, e->stream);
-      return launch_silu(e->dtype, e->P(op.d.in0), e->P(op.d.out), (long)(b.kind == DPB_BUF_SHARED ? 1 : n) * b.rows * b.C, e->stream);
+      const auto act = op.d.ip[0] == 2 ? launch_gelu : op.d.ip[0] == 1 ? launch_quick_gelu : launch_silu;
+      return act(e->dtype, e->P(op.d.in0), e->P(op.d.out), (long)(b.kind == DPB_BUF_SHARED ? 1 : n) * b.rows * b.C, e->stream);
     }
   }
   return fail("unknown op kind %d", op.d.kind);
@@ -786,58 +791,68 @@ int check_tap(dpb_engine* e, int tap, int nt) {
   return 0;
 }
 
-// make `src` the seed of the passes that follow: its activity flags (computed once per seed and cached)
-int set_seed(dpb_engine* e, int src) {
+// the activity flags of seed `src` ([n_buffers] buffers, then [n_ops] ops), computed once per seed and cached; nullptr (and the error set) if
+// the tape cannot be differentiated from src.  Changes nothing but the cache.
+const char* seed_flags(dpb_engine* e, int src) {
   const int nb = (int)e->bufs.size(), no = (int)e->ops.size();
   std::vector<char>& a = e->act_cache[src];
-  if (a.empty()) {
-    std::vector<char> f(nb + no, 0);
-    if (src == e->x_buf) {                        // the create-time flags, unchanged
-      for (int b = 0; b < nb; ++b) f[b] = !e->bufs[b].is_const;
-      for (int i = 0; i < no; ++i) f[nb + i] = !e->ops[i].is_const;
-    } else {
-      f[src] = 1;
-      for (int i = e->producer[src] + 1; i < no; ++i) {   // ops up to producer[src] cannot read a buffer written later (SSA tape order)
-        const Op& op = e->ops[i];
-        const dpb_op_desc& d = op.d;
-        bool on = f[d.in0];
-        if (d.kind == DPB_OP_ATTENTION || d.kind == DPB_OP_CONCAT) on = on || f[d.in1];
-        if (d.kind == DPB_OP_ATTENTION) on = on || f[d.in2];
-        if (d.kind == DPB_OP_CONV && d.res >= 0) on = on || f[d.res];
-        if (d.kind == DPB_OP_SILU && on) return fail("op %d (SILU / GELU, primal only) depends on source buffer %d", i, src);
-        if (on && d.kind == DPB_OP_ATTENTION) {   // the attention kernels were planned for x: the query and (k, v) must have the same activity as for x
-          const AttnPlan& p = e->plans[op.attn];
-          if (!f[d.in0] || f[d.in1] != f[d.in2] || (bool)f[d.in1] == p.kv_const)
-            return fail("attention op %d: q, k, v depend on source buffer %d differently than on x (unsupported)", i, src);
+  if (!a.empty()) return a.data();
+  std::vector<char> f(nb + no, 0);
+  if (src == e->x_buf) {                          // the create-time flags, unchanged
+    for (int b = 0; b < nb; ++b) f[b] = !e->bufs[b].is_const;
+    for (int i = 0; i < no; ++i) f[nb + i] = !e->ops[i].is_const;
+  } else {
+    f[src] = 1;
+    for (int i = e->producer[src] + 1; i < no; ++i) {   // ops up to producer[src] cannot read a buffer written later (SSA tape order)
+      const Op& op = e->ops[i];
+      const dpb_op_desc& d = op.d;
+      bool on = false;
+      for (int b : op_inputs(d)) on = on || f[b];
+      if (d.kind == DPB_OP_SILU && on) { fail("op %d (SILU / GELU, primal only) depends on source buffer %d", i, src); return nullptr; }
+      if (on && d.kind == DPB_OP_ATTENTION) {   // the attention kernels were planned for x: the query and (k, v) must have the same activity as for x
+        const AttnPlan& p = e->plans[op.attn];
+        if (!f[d.in0] || f[d.in1] != f[d.in2] || (bool)f[d.in1] == p.kv_const) {
+          fail("attention op %d: q, k, v depend on source buffer %d differently than on x (unsupported)", i, src);
+          return nullptr;
         }
-        f[nb + i] = on;
-        if (on) f[d.out] = 1;
       }
+      f[nb + i] = on;
+      if (on) f[d.out] = 1;
     }
-    a.swap(f);
   }
-  e->src = src;
-  e->bact = a.data();
-  e->oact = a.data() + nb;
-  return 0;
+  a.swap(f);
+  return a.data();
 }
 
 // channels of the seed's fp32 NCHW boundary: the network input's true channels, a tap's valid channels
 int seed_channels(const dpb_engine* e, int src) { return src == e->x_buf ? e->x_channels : e->bufs[src].Cv; }
 
-// the checks of check_tap, plus (src != x_buf) those of a pass between two inner buffers; makes src the seed
-int check_pair(dpb_engine* e, int src, int dst, int nt) {
-  if (int r = check_tap(e, dst, nt)) return r;
-  if (src != e->x_buf) {
-    if (src < 0 || src >= (int)e->bufs.size() || e->producer[src] < 0 || e->bufs[src].kind != DPB_BUF_ACT) return fail("invalid source buffer %d", src);
-    if (e->bufs[src].is_const) return fail("source buffer %d does not depend on x", src);
-    if (e->producer[dst] > e->primal_last)
-      return fail("no primal state up to dst buffer %d (produced by op %d, the primal pass covers ops 0..%d): run dpb_primal with upto_buf = dst or later",
-                  dst, e->producer[dst], e->primal_last);
+// The one validation of a (src, dst) pair; *flags: the seed's activity.  src must be an x-dependent activation an op produced, dst an op's
+// output downstream of it.  pass: a tangent / adjoint pass -- x_buf is a seed too (the encoder Jacobian), and between two inner buffers the
+// primal state must reach dst; otherwise a forward seeded at src (dpb_forward_from / _shift), which computes its own.
+enum PairUse { FOR_FORWARD, FOR_PASS };
+int check_pair(dpb_engine* e, int src, int dst, PairUse use, const char** flags = nullptr) {
+  const int nb = (int)e->bufs.size();
+  const bool pass = use == FOR_PASS, inner = !(pass && src == e->x_buf);
+  if (inner) {
+    if (src < 0 || src >= nb || e->producer[src] < 0 || e->bufs[src].kind != DPB_BUF_ACT) return fail("invalid source buffer %d (an activation produced by an op)", src);
+    if (e->bufs[src].is_const) return fail("invalid source buffer %d: it does not depend on x", src);
   }
-  if (int r = set_seed(e, src)) return r;
-  if (dst == src || !e->bact[dst]) return fail("dst buffer %d is not downstream of source buffer %d", dst, src);
+  if (dst < 0 || dst >= nb || e->producer[dst] < 0) return fail("invalid dst buffer %d", dst);
+  if (pass && inner && e->producer[dst] > e->primal_last)
+    return fail("no primal state up to dst buffer %d (produced by op %d, the primal pass covers ops 0..%d): run dpb_primal with upto_buf = dst or later",
+                dst, e->producer[dst], e->primal_last);
+  const char* f = seed_flags(e, src);
+  if (!f) return -1;
+  if (dst == src || !f[dst]) return fail("dst buffer %d is not downstream of source buffer %d", dst, src);
+  if (flags) *flags = f;
   return 0;
+}
+
+// the checks of a tangent / adjoint pass from src to tap with nt directions
+int check_pass(dpb_engine* e, int src, int tap, int nt, const char** flags = nullptr) {
+  if (int r = check_tap(e, tap, nt)) return r;
+  return check_pair(e, src, tap, FOR_PASS, flags);
 }
 
 }  // namespace
@@ -877,15 +892,13 @@ int dpb_engine_create(const dpb_net_desc* net, dpb_engine** out) {
     Op op;
     op.d = net->ops[i];
     const dpb_op_desc& d = op.d;
-    if (!okb(d.in0) || !okb(d.out)) return bad("bad buffer id", i);
-    bool c = e->bufs[d.in0].is_const;
-    if (d.kind == DPB_OP_ATTENTION || d.kind == DPB_OP_CONCAT) {
-      if (!okb(d.in1)) return bad("bad in1", i);
-      c = c && e->bufs[d.in1].is_const;
+    if (!okb(d.out)) return bad("bad buffer id", i);
+    bool c = true;                                 // the output depends on x if any buffer the op reads does
+    for (int b : op_inputs(d)) {
+      if (!okb(b)) return bad("bad buffer id", i);
+      c = c && e->bufs[b].is_const;
     }
     if (d.kind == DPB_OP_ATTENTION) {
-      if (!okb(d.in2)) return bad("bad in2", i);
-      c = c && e->bufs[d.in2].is_const;
       AttnPlan p;
       p.heads = d.ip[0];
       p.oq = d.ip[1]; p.ok = d.ip[2]; p.ov = d.ip[3];
@@ -908,7 +921,6 @@ int dpb_engine_create(const dpb_net_desc* net, dpb_engine** out) {
       e->plans.push_back(p);
     }
     if (d.kind == DPB_OP_CONV) {
-      if (d.res >= 0) { if (!okb(d.res)) return bad("bad res", i); c = c && e->bufs[d.res].is_const; }
       if (d.rowbias >= 0 && (!okb(d.rowbias) || e->bufs[d.rowbias].kind != DPB_BUF_SHARED)) return bad("rowbias must be a SHARED buffer", i);
       if (d.rowbias >= 0 && (d.ip[10] < 0 || d.ip[10] % 8 || d.ip[10] + round8(d.ip[5]) > e->bufs[d.rowbias].C)) return bad("bad rowbias column window", i);
       if (!d.w[0]) return bad("missing weight", i);
@@ -924,8 +936,7 @@ int dpb_engine_create(const dpb_net_desc* net, dpb_engine** out) {
   {
     std::vector<int> uses(nb, 0), user(nb, -1);
     for (size_t i = 0; i < e->ops.size(); ++i) {
-      const dpb_op_desc& d = e->ops[i].d;
-      for (int b : {d.in0, d.in1, d.in2, d.res}) if (b >= 0 && b < nb) { uses[b]++; user[b] = (int)i; }
+      for (int b : op_inputs(e->ops[i].d)) { uses[b]++; user[b] = (int)i; }
     }
     e->uses = uses;
     // LayerNorm fused into the neighbouring product's epilogue (row-complete 128 x 320 ring tile, 16-bit engines): tangent -- the product that
@@ -1038,7 +1049,7 @@ int dpb_engine_create(const dpb_net_desc* net, dpb_engine** out) {
   e->ws_bytes = off;
   e->ginit.assign(nb, 0);
   e->act_cache.assign(nb, std::vector<char>());
-  if (set_seed(e, e->x_buf)) { delete e; return -1; }
+  if (!seed_flags(e, e->x_buf)) { delete e; return -1; }
   *out = e;
   return 0;
 }
@@ -1066,44 +1077,40 @@ int dpb_engine_set_workspace(dpb_engine* e, void* ws, size_t bytes) {
   return 0;
 }
 
-// dpb_forward_shift, right after op producer[fwd_seed]: the `batch` shifted copies of the tap, then (shared prefix, xb == 1 < batch) sample 0 of every
-// buffer the rest of the pass still reads broadcast to the other samples.  That set comes from the tape: the per-sample inputs (in0 / in1 / in2 / res)
-// of the ops in (producer[fwd_seed], last] that were written at or before producer[fwd_seed] or are network inputs (ctx) -- the skips, the net-wide K/V
+// dpb_forward_shift, right after op producer[f.seed]: the `batch` shifted copies of the tap, then (shared prefix, xb == 1 < batch) sample 0 of every
+// buffer the rest of the pass still reads broadcast to the other samples.  That set comes from the tape: the per-sample inputs (op_inputs) of the
+// ops in (producer[f.seed], last] that were written at or before producer[f.seed] or are network inputs (ctx) -- the skips, the net-wide K/V
 // projection of the context.  SHARED buffers (time-embedding path, row biases) have one copy for any batch; the tap itself is written by shift_tap.
 // Nothing else crosses the seam: a primal normalisation op computes its statistics from its own input, it takes none from that input's producer.
-static int shift_seed(dpb_engine* e, int batch, int xb, int last) {
-  const int src = e->fwd_seed, ps = e->producer[src];
+static int shift_seed(dpb_engine* e, const Forward& f, int batch, int xb, int last) {
+  const int src = f.seed, ps = e->producer[src];
   const Buf& bs = e->bufs[src];
-  if (int r = launch_shift_tap(e->dtype, e->P(src), e->fwd_u, e->fwd_dir, e->fwd_scale, batch, xb < batch, bs.C, bs.Cv, bs.rows, e->stream)) return r;
+  if (int r = launch_shift_tap(e->dtype, e->P(src), f.u, f.dir, f.scale, batch, xb < batch, bs.C, bs.Cv, bs.rows, e->stream)) return r;
   if (xb == batch) return 0;
   std::vector<char> seen(e->bufs.size(), 0);
   std::vector<void*> ptr;
   std::vector<size_t> bytes;
-  auto need = [&](int b) {
-    if (b < 0 || b == src || seen[b] || e->bufs[b].kind == DPB_BUF_SHARED || e->producer[b] > ps) return;
-    seen[b] = 1;
-    ptr.push_back(e->P(b));
-    bytes.push_back((size_t)e->bufs[b].rows * e->bufs[b].C * e->es);
-  };
-  for (int i = ps + 1; i <= last; ++i) {
-    const dpb_op_desc& d = e->ops[i].d;
-    need(d.in0);
-    if (d.kind == DPB_OP_ATTENTION || d.kind == DPB_OP_CONCAT) need(d.in1);
-    if (d.kind == DPB_OP_ATTENTION) need(d.in2);
-    if (d.kind == DPB_OP_CONV) need(d.res);
-  }
+  for (int i = ps + 1; i <= last; ++i)
+    for (int b : op_inputs(e->ops[i].d)) {
+      if (b == src || seen[b] || e->bufs[b].kind == DPB_BUF_SHARED || e->producer[b] > ps) continue;
+      seen[b] = 1;
+      ptr.push_back(e->P(b));
+      bytes.push_back((size_t)e->bufs[b].rows * e->bufs[b].C * e->es);
+    }
   return launch_replicate_rows(ptr.data(), bytes.data(), (int)ptr.size(), batch, e->stream);
 }
 
-static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const float* ctx, int upto_buf) {
+static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const float* ctx, int upto_buf, const Forward& f) {
   if (!e || !x) return fail("null argument");
   if (!e->ws) return fail("workspace not set (dpb_engine_set_workspace)");
   if (batch < 1 || batch > e->maxB) return fail("batch=%d outside [1,%d]", batch, e->maxB);
   if (upto_buf < 0 || upto_buf >= (int)e->bufs.size() || e->producer[upto_buf] < 0) return fail("invalid upto buffer %d", upto_buf);
   const LaunchSpan span(e);
   e->flops = 0; e->gbytes = 0;
+  Pass ps(e, MODE_PRIMAL, upto_buf, e->x_buf, seed_flags(e, e->x_buf));
+  ps.fwd = f;
   const Buf& bx = e->bufs[e->x_buf];
-  const int xb = e->fwd_u ? e->fwd_xb : batch;     // samples of x / ctx (dpb_forward_shift with a shared prefix: 1)
+  const int xb = f.u ? f.xbatch : batch;           // samples of x / ctx (dpb_forward_shift with a shared prefix: 1)
   if (int r = launch_nchw_to_nhwc(e->dtype, x, e->P(e->x_buf), xb, e->x_channels, bx.rows, bx.C, e->stream)) return r;
   if (e->ctx_buf >= 0) {
     if (!ctx) return fail("this network needs ctx (encoder_hidden_states)");
@@ -1111,16 +1118,16 @@ static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const 
     // ctx is already [batch][rows][Cv] channel-last (Cv = un-padded width): cast (and zero-pad to C) via the nchw kernel with HW=1
     if (int r = launch_nchw_to_nhwc(e->dtype, ctx, e->P(e->ctx_buf), xb * bc.rows, bc.Cv, 1, bc.C, e->stream)) return r;
   }
-  if (e->temb_buf >= 0 && !e->temb_keep) {
+  if (e->temb_buf >= 0 && !f.temb_resident) {
     // sinusoidal timestep embedding, computed on the host in fp32 exactly as the reference frameworks do
     // (diffusion.py:783-804 / diffusers Timesteps), uploaded through the io staging area.
     const int dim = e->temb_dim, half = dim / 2;
     std::vector<float> emb(e->bufs[e->temb_buf].C, 0.f);
     for (int i = 0; i < half; ++i) {
-      float f;
-      if (e->temb_hm1) f = expf((float)i * (float)(-(log(10000.0) / (double)(half - 1))));   // diffusion.py:797-798
-      else f = expf(((float)(-log(10000.0)) * (float)i) / (float)half);                      // diffusers get_timestep_embedding
-      float ang = t * f;
+      float fr;
+      if (e->temb_hm1) fr = expf((float)i * (float)(-(log(10000.0) / (double)(half - 1))));   // diffusion.py:797-798
+      else fr = expf(((float)(-log(10000.0)) * (float)i) / (float)half);                      // diffusers get_timestep_embedding
+      float ang = t * fr;
       float s = sinf(ang), c = cosf(ang);
       if (e->temb_flip) { emb[i] = c; emb[half + i] = s; } else { emb[i] = s; emb[half + i] = c; }
     }
@@ -1131,56 +1138,51 @@ static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const 
   }
   if (e->pstats_bytes && !gn_deterministic()) DPB_CHECK(hipMemsetAsync(e->ws + e->pstats_off, 0, e->pstats_bytes, e->stream));   // atomic statistics path accumulates
   e->cur_batch = batch;
-  e->cur_tap = upto_buf; e->pend.on = false;
+  e->pend.on = false;
   const int last = e->producer[upto_buf];
-  const int seed_op = e->fwd_seed >= 0 ? e->producer[e->fwd_seed] : -1;
+  const int seed_op = f.seed >= 0 ? e->producer[f.seed] : -1;
   e->primal_last = -1;
   std::fill(e->skip.begin(), e->skip.end(), 0);
   for (int i = 0; i <= last; ++i) {
     if (!e->skip[i])                               // (forward only: a GEGLU applied by the epilogue of the FF-in product)
-      if (int r = run_op(e, e->ops[i], MODE_PRIMAL, i <= seed_op ? xb : batch)) return r;
-    if (i == seed_op && e->fwd_u) {                // dpb_forward_shift: the tap just computed, shifted per row (of sample 0 for every row when xb == 1)
-      if (int r = shift_seed(e, batch, xb, last)) return r;
+      if (int r = run_op(e, e->ops[i], ps, i <= seed_op ? xb : batch)) return r;
+    if (i == seed_op && f.u) {                     // dpb_forward_shift: the tap just computed, shifted per row (of sample 0 for every row when xb == 1)
+      if (int r = shift_seed(e, f, batch, xb, last)) return r;
     } else if (i == seed_op) {                     // dpb_forward_from: the caller's activation replaces the one just computed
-      const Buf& bs = e->bufs[e->fwd_seed];
-      if (int r = launch_nchw_to_nhwc(e->dtype, e->fwd_h, e->P(e->fwd_seed), batch, bs.Cv, bs.rows, bs.C, e->stream)) return r;
+      const Buf& bs = e->bufs[f.seed];
+      if (int r = launch_nchw_to_nhwc(e->dtype, f.h, e->P(f.seed), batch, bs.Cv, bs.rows, bs.C, e->stream)) return r;
     }
   }
-  if (!e->fwd_only) e->primal_last = last;
+  if (f.stash) e->primal_last = last;
   return 0;
 }
 
 int dpb_primal(dpb_engine* e, const float* x, int batch, float t, const float* ctx, int upto_buf) {
-  if (e) e->fwd_only = false;
-  return primal_pass(e, x, batch, t, ctx, upto_buf);
+  return primal_pass(e, x, batch, t, ctx, upto_buf, Forward());
 }
 
-int dpb_forward(dpb_engine* e, const float* x, int batch, float t, const float* ctx, int upto_buf, int channels, float* out) {
+// dpb_forward and the entry points built on it: a primal pass that keeps no stash (f.stash == false), read out at upto_buf
+static int forward_pass(dpb_engine* e, const float* x, int batch, float t, const float* ctx, int upto_buf, int channels, float* out, const Forward& f) {
   if (!e || !out) return fail("null argument");
-  e->fwd_only = true;
-  int r = primal_pass(e, x, batch, t, ctx, upto_buf);
-  e->fwd_only = false;
+  int r = primal_pass(e, x, batch, t, ctx, upto_buf, f);
   if (!r) r = dpb_read_buffer(e, upto_buf, channels, out);
   e->cur_batch = 0;                                // no stash was kept: dpb_jvp / dpb_vjp / dpb_pullback_iterate refuse until the next dpb_primal
   return r;
 }
 
+int dpb_forward(dpb_engine* e, const float* x, int batch, float t, const float* ctx, int upto_buf, int channels, float* out) {
+  Forward f;
+  f.stash = false;
+  return forward_pass(e, x, batch, t, ctx, upto_buf, channels, out, f);
+}
+
 int dpb_forward_from(dpb_engine* e, const float* x, int batch, float t, const float* ctx, int src_buf, const float* h, int dst_buf, int channels,
                      float* out) {
   if (!e || !out || !h) return fail("null argument");
-  const int nb = (int)e->bufs.size();
-  if (src_buf < 0 || src_buf >= nb || e->producer[src_buf] < 0 || e->bufs[src_buf].kind != DPB_BUF_ACT || e->bufs[src_buf].is_const)
-    return fail("invalid source buffer %d (an x-dependent activation produced by an op)", src_buf);
-  if (dst_buf < 0 || dst_buf >= nb || e->producer[dst_buf] < 0) return fail("invalid dst buffer %d", dst_buf);
-  const int prev = e->src;
-  if (int r = set_seed(e, src_buf)) return r;
-  const bool down = dst_buf != src_buf && e->bact[dst_buf];
-  set_seed(e, prev);
-  if (!down) return fail("dst buffer %d is not downstream of source buffer %d", dst_buf, src_buf);
-  e->fwd_seed = src_buf; e->fwd_h = h;
-  const int r = dpb_forward(e, x, batch, t, ctx, dst_buf, channels, out);
-  e->fwd_seed = -1; e->fwd_h = nullptr;
-  return r;
+  if (int r = check_pair(e, src_buf, dst_buf, FOR_FORWARD)) return r;
+  Forward f;
+  f.stash = false; f.seed = src_buf; f.h = h;
+  return forward_pass(e, x, batch, t, ctx, dst_buf, channels, out, f);
 }
 
 int dpb_forward_shift(dpb_engine* e, const float* x, int xbatch, int batch, float t, const float* ctx, int src_buf, const float* u, int nu,
@@ -1193,19 +1195,10 @@ int dpb_forward_shift(dpb_engine* e, const float* x, int xbatch, int batch, floa
   if (!u) return fail("null argument");
   for (int b = 0; b < batch; ++b)
     if (dir[b] < -1 || dir[b] >= nu) return fail("dir[%d]=%d outside [-1,%d) (-1: no shift)", b, dir[b], nu);
-  const int nb = (int)e->bufs.size();
-  if (src_buf < 0 || src_buf >= nb || e->producer[src_buf] < 0 || e->bufs[src_buf].kind != DPB_BUF_ACT || e->bufs[src_buf].is_const)
-    return fail("invalid source buffer %d (an x-dependent activation produced by an op)", src_buf);
-  if (dst_buf < 0 || dst_buf >= nb || e->producer[dst_buf] < 0) return fail("invalid dst buffer %d", dst_buf);
-  const int prev = e->src;
-  if (int r = set_seed(e, src_buf)) return r;
-  const bool down = dst_buf != src_buf && e->bact[dst_buf];
-  set_seed(e, prev);
-  if (!down) return fail("dst buffer %d is not downstream of source buffer %d", dst_buf, src_buf);
-  e->fwd_seed = src_buf; e->fwd_u = u; e->fwd_dir = dir; e->fwd_scale = scale; e->fwd_xb = xbatch;
-  const int r = dpb_forward(e, x, batch, t, ctx, dst_buf, channels, out);
-  e->fwd_seed = -1; e->fwd_u = nullptr; e->fwd_dir = nullptr; e->fwd_scale = nullptr; e->fwd_xb = 0;
-  return r;
+  if (int r = check_pair(e, src_buf, dst_buf, FOR_FORWARD)) return r;
+  Forward f;
+  f.stash = false; f.seed = src_buf; f.u = u; f.dir = dir; f.scale = scale; f.xbatch = xbatch;
+  return forward_pass(e, x, batch, t, ctx, dst_buf, channels, out, f);
 }
 
 int dpb_read_buffer(dpb_engine* e, int buf, int channels, float* out) {
@@ -1222,7 +1215,9 @@ int dpb_read_buffer(dpb_engine* e, int buf, int channels, float* out) {
 // src: the seed buffer (x_buf: the encoder Jacobian); ops up to producer[src] and ops whose output does not depend on src do not run
 static int jvp_pass(dpb_engine* e, int src, int tap, const float* V, int nt, float* U) {
   if (!e || !V) return fail("null argument");
-  if (int r = check_pair(e, src, tap, nt)) return r;
+  const char* flags;
+  if (int r = check_pass(e, src, tap, nt, &flags)) return r;
+  const Pass ps(e, MODE_TANGENT, tap, src, flags);
   const LaunchSpan span(e);
   e->flops = 0; e->gbytes = 0;
   const Buf& bx = e->bufs[src];
@@ -1230,10 +1225,10 @@ static int jvp_pass(dpb_engine* e, int src, int tap, const float* V, int nt, flo
   if (e->tstats_bytes && !gn_deterministic()) DPB_CHECK(hipMemsetAsync(e->ws + e->tstats_off, 0, e->tstats_bytes, e->stream));   // atomic statistics accumulate
   const int last = e->producer[tap];
   std::fill(e->skip.begin(), e->skip.end(), 0);
-  e->cur_tap = tap; e->pend.on = false;
+  e->pend.on = false;
   for (int i = e->producer[src] + 1; i <= last; ++i) {
-    if (!e->oact[i] || e->skip[i]) continue;
-    if (int r = run_op(e, e->ops[i], MODE_TANGENT, nt)) return r;
+    if (!ps.oact[i] || e->skip[i]) continue;
+    if (int r = run_op(e, e->ops[i], ps, nt)) return r;
   }
   if (int r = flush_pending(e)) return r;
   if (!U) return 0;
@@ -1255,7 +1250,9 @@ int dpb_jvp_between(dpb_engine* e, int src_buf, int dst_buf, const float* V, int
 // trip through U is the identity on 16-bit and fp32 values alike, so the results are bitwise those of the two conversion kernels it replaces)
 static int vjp_pass(dpb_engine* e, int src, int tap, const float* U, int nt, float* W) {
   if (!e || !W) return fail("null argument");
-  if (int r = check_pair(e, src, tap, nt)) return r;
+  const char* flags;
+  if (int r = check_pass(e, src, tap, nt, &flags)) return r;
+  const Pass ps(e, MODE_ADJOINT, tap, src, flags);
   const LaunchSpan span(e);
   e->flops = 0; e->gbytes = 0;
   const Buf& bt = e->bufs[tap];
@@ -1268,11 +1265,11 @@ static int vjp_pass(dpb_engine* e, int src, int tap, const float* U, int nt, flo
   }
   e->ginit[tap] = 1;
   if (e->tstats_bytes && !gn_deterministic()) DPB_CHECK(hipMemsetAsync(e->ws + e->tstats_off, 0, e->tstats_bytes, e->stream));
-  e->cur_tap = tap; e->pend.on = false;
+  e->pend.on = false;
   for (int i = e->producer[tap]; i > e->producer[src]; --i) {   // (the seed's producer and everything before it: upstream of the pass)
     const Op& op = e->ops[i];
-    if (!e->oact[i] || !e->ginit[op.d.out]) continue;
-    if (int r = run_op(e, op, MODE_ADJOINT, nt)) return r;
+    if (!ps.oact[i] || !e->ginit[op.d.out]) continue;
+    if (int r = run_op(e, op, ps, nt)) return r;
   }
   if (int r = flush_pending(e)) return r;
   if (!e->ginit[src]) {
@@ -1298,12 +1295,15 @@ int dpb_vjp_between(dpb_engine* e, int src_buf, int dst_buf, const float* U, int
   return vjp_pass(e, src_buf, dst_buf, U, nt, W);
 }
 
+static OrthArgs orth_args(const float* W, const float* Vprev, float* V, float* s, float* conv, void* scratch, size_t scratch_bytes, int k, long N) {
+  OrthArgs a;
+  a.W = W; a.Vprev = Vprev; a.V = V; a.s = s; a.conv = conv; a.scratch = (double*)scratch; a.scratch_bytes = scratch_bytes; a.k = k; a.N = N;
+  return a;
+}
+
 int dpb_orth(const float* W, const float* Vprev, float* V, float* s, float* conv, void* scratch, int k, int64_t N, void* stream) {
   if (!W || !Vprev || !V || !s || !conv || !scratch) return fail("null argument");
-  OrthArgs a;
-  a.W = W; a.Vprev = Vprev; a.V = V; a.s = s; a.conv = conv; a.scratch = (double*)scratch; a.k = k; a.N = N;
-  a.scratch_bytes = orth_scratch_bytes(k, N);      // the caller's contract (include/dpb.h)
-  return launch_orth(a, (hipStream_t)stream);
+  return launch_orth(orth_args(W, Vprev, V, s, conv, scratch, orth_scratch_bytes(k, N) /* the caller's contract (include/dpb.h) */, k, N), (hipStream_t)stream);
 }
 
 int dpb_orth_checked(const float* W, const float* Vprev, float* V, float* s, float* conv, void* scratch, size_t scratch_bytes, int k, int64_t N,
@@ -1312,10 +1312,7 @@ int dpb_orth_checked(const float* W, const float* Vprev, float* V, float* s, flo
   if (k < 1 || k > ORTH_MAX_RANK || N < 1) return fail("dpb_orth: k=%d outside [1,%d] or N=%lld < 1", k, ORTH_MAX_RANK, (long long)N);
   const size_t need = orth_scratch_bytes(k, N);
   if (scratch_bytes < need) return fail("dpb_orth: scratch of %zu bytes, dpb_orth_scratch_bytes(%d, %lld) = %zu", scratch_bytes, k, (long long)N, need);
-  OrthArgs a;
-  a.W = W; a.Vprev = Vprev; a.V = V; a.s = s; a.conv = conv; a.scratch = (double*)scratch; a.k = k; a.N = N;
-  a.scratch_bytes = scratch_bytes;
-  return launch_orth(a, (hipStream_t)stream);
+  return launch_orth(orth_args(W, Vprev, V, s, conv, scratch, scratch_bytes, k, N), (hipStream_t)stream);
 }
 
 size_t dpb_orth_scratch_bytes(int k, int64_t N) { return (k < 1 || k > ORTH_MAX_RANK || N < 1) ? 0 : orth_scratch_bytes(k, N); }
@@ -1383,10 +1380,10 @@ int dpb_local_pca_sample(dpb_engine* e, const float* x, float t, const float* ct
     const int B = (int)std::min<int64_t>(e->maxB, count - c0);
     r = launch_perturb_unit(x, noise ? noise + c0 * l.n_in : nullptr, seed, first + c0, B, l.n_in, 1.f, xb, nullptr, sc + l.part,
                             l.total - l.part, e->stream);
-    e->temb_keep = c0 > 0;                         // same t as the chunk before: its embedding is still in P(temb_buf)
-    if (!r) r = dpb_forward(e, xb, B, t, cb, upto_buf, channels, H + c0 * D);
+    Forward f;
+    f.stash = false; f.temb_resident = c0 > 0;     // same t as the chunk before: its embedding is still in P(temb_buf)
+    if (!r) r = forward_pass(e, xb, B, t, cb, upto_buf, channels, H + c0 * D, f);
   }
-  e->temb_keep = false;
   return r;
 }
 
@@ -1414,9 +1411,7 @@ static int iterate_pass(dpb_engine* e, int src, int tap, float* V, float* U, flo
     if (int r = vjp_pass(e, src, tap, keep ? nullptr : U, nt, Wm)) return r;
     fl += e->flops; gb += e->gbytes;
     {                                               // independent k x N re-orthonormalisation per sample, all samples in one set of four launches
-      OrthArgs a;                                   // (in place, V is Vprev: see dpb.h)
-      a.W = Wm; a.Vprev = V; a.V = V; a.s = s; a.conv = conv; a.scratch = (double*)orth_scratch; a.k = k; a.N = N;
-      a.scratch_bytes = orth_scratch_bytes(k, N);
+      OrthArgs a = orth_args(Wm, V, V, s, conv, orth_scratch, orth_scratch_bytes(k, N), k, N);   // (in place, V is Vprev: see dpb.h)
       a.batch = B; a.stride_w = (long)k * N; a.stride_v = (long)k * N; a.stride_s = k; a.stride_conv = 2; a.scratch_stride = orth_stride;
       if (g_orth_batch) {
         if (int r = launch_orth(a, e->stream)) return r;
@@ -1487,7 +1482,7 @@ int dpb_pullback_iterate_between(dpb_engine* e, int src_buf, int dst_buf, float*
   if (!e || !V || !U || !s || !conv || !scratch) return fail("null argument");
   if (k < 1 || k > ORTH_MAX_RANK) return fail("pca_rank k=%d outside [1,%d]", k, ORTH_MAX_RANK);
   const int B = e->cur_batch;
-  if (int r = check_pair(e, src_buf, dst_buf, k * (B > 0 ? B : 1))) return r;
+  if (int r = check_pass(e, src_buf, dst_buf, k * (B > 0 ? B : 1))) return r;
   if ((uintptr_t)scratch % 256) return fail("scratch must be 256-byte aligned");
   const size_t need = between_scratch_bytes(e, src_buf, k, B);
   if (scratch_bytes < need) return fail("scratch of %zu bytes, the iteration needs %zu (dpb_pullback_scratch_bytes)", scratch_bytes, need);

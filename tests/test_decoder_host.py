@@ -145,3 +145,60 @@ def test_decoder_host_checks_without_gpu():
         assert l.dpb_forward_from(h, dummy, 1, 1.0, dummy, mid, dummy, down, 32, dummy) != 0 and b"not downstream" in l.dpb_last_error()
     finally:
         l.dpb_engine_destroy(h)
+
+
+def _small_net(l, lib, junk=None, concat_in1=2):
+    """A hand-numbered tape on x [16][32]: SiLU(temb), GroupNorm, LayerNorm, FF-in product -> GEGLU (interleaved) -> FF-out product (+ x), concat.
+    Buffer 0 is the GEGLU input, so any op that wrongly counts as a reader of id 0 trips the "no other consumer" check.  junk: the value written
+    into every input id the op kind does not read (in1 / in2 of CONV, GROUPNORM, LAYERNORM, GEGLU, SILU; in2 of CONCAT; res of non-CONV ops);
+    None leaves them at -1.  Returns (rc, workspace bytes, error text)."""
+    A, S = lib.BUF_ACT, lib.BUF_SHARED
+    buffers = [(16, 128, A), (1, 8, S), (16, 32, A), (16, 32, A), (16, 32, A), (16, 64, A), (16, 32, A), (16, 64, A), (1, 8, S)]
+    h, temb, x, gn, ln, gg, ff, cat, st = range(9)
+    conv = lambda cin, cout: [4, 4, cin, 4, 4, cout, 1, 1, 0, lib.GATHER_NONE, 0, 0]
+    # (kind, in0, in1, in2, out, res, ip)
+    tape = [(lib.OP_SILU, temb, -1, -1, st, -1, [0] * 12),
+            (lib.OP_GROUPNORM, x, -1, -1, gn, -1, [8, 0] + [0] * 10),
+            (lib.OP_LAYERNORM, gn, -1, -1, ln, -1, [0] * 12),
+            (lib.OP_CONV, ln, -1, -1, h, -1, conv(32, 128)),
+            (lib.OP_GEGLU, h, -1, -1, gg, -1, [0, 64] + [0] * 10),
+            (lib.OP_CONV, gg, -1, -1, ff, x, conv(64, 32)),
+            (lib.OP_CONCAT, ff, concat_in1, -1, cat, -1, [0] * 12)]
+    bufs = (lib.BufferDesc * len(buffers))(*[lib.BufferDesc(r, c, k, 0) for r, c, k in buffers])
+    ops = (lib.OpDesc * len(tape))()
+    weights = (C.c_float * 16)()                   # create only looks at which weight pointers are set
+    for o, (kind, in0, in1, in2, out, res, ip) in zip(ops, tape):
+        unread_in = kind != lib.OP_CONCAT and junk is not None
+        o.kind, o.in0, o.out, o.rowbias = kind, in0, out, -1
+        o.in1 = junk if unread_in else in1
+        o.in2 = junk if junk is not None else in2
+        o.res = junk if junk is not None and kind != lib.OP_CONV else res
+        for j in range(12):
+            o.ip[j] = ip[j]
+        o.fp[0] = 1e-5
+        o.w[0] = o.w[1] = C.addressof(weights)
+    net = lib.NetDesc()
+    net.dtype = lib.DPB_F32; net.max_batch = 2; net.max_tangents = 4; net.n_buffers = len(buffers); net.n_ops = len(tape)
+    net.buffers, net.ops = bufs, ops
+    net.x_buf, net.x_channels, net.temb_buf, net.temb_dim, net.ctx_buf = x, 32, temb, 8, -1
+    e = C.c_void_p()
+    rc = l.dpb_engine_create(C.byref(net), C.byref(e))
+    err = l.dpb_last_error().decode()
+    ws = l.dpb_engine_workspace_bytes(e) if rc == 0 else 0
+    if rc == 0:
+        l.dpb_engine_destroy(e)
+    return rc, ws, err
+
+
+def test_input_ids_an_op_kind_does_not_read_mean_nothing():
+    """include/dpb.h: an input id the op kind does not read means nothing.  The same tape with -1 and with 0 in every such id creates the same
+    engine; a genuine second reader of the GEGLU input is still refused."""
+    from diffusion_pullback_amd import lib
+    l = lib.load()
+    rc, ws, err = _small_net(l, lib)
+    assert rc == 0 and ws > 0, err
+    rc0, ws0, err0 = _small_net(l, lib, junk=0)
+    assert rc0 == 0, err0
+    assert ws0 == ws
+    rc2, _, err2 = _small_net(l, lib, concat_in1=0)                    # CONCAT does read in1: buffer 0 has two consumers
+    assert rc2 != 0 and "no other consumer" in err2, err2

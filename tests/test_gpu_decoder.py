@@ -308,3 +308,27 @@ def test_decoder_error_paths():
         short.local_decoder_pullback_zt(z, t, ctx, op="mid", block_idx=0, pca_rank=2, chunk_size=2, max_iter=1)
     with pytest.raises(ValueError, match="up to eps"):
         short.get_h_to_e(z, t, ctx, torch.zeros(1, 64, 4, 4), "mid", 0)
+
+
+def test_passes_leave_nothing_behind_for_the_next_pass():
+    """A pass with another seed, or a call refused in validation, leaves nothing behind that a later pass reads: jvp_between, jvp, (a refused
+    forward_from), vjp_between -- then the same three passes again, bit for bit."""
+    from diffusion_pullback_amd import DpbError
+    f, cfg, p = _sd()
+    e = _net("sd", cfg, p, torch.bfloat16, max_rank=2).engine
+    z, t, ctx = f["z"], float(f["t"]), f["ctx"]
+    mid = ("mid", 0)
+    g = torch.Generator().manual_seed(11)
+    V = torch.randn(2, e.tap_numel(mid), generator=g).to(DEV)
+    Vx = torch.randn(2, e.n_in, generator=g).to(DEV)
+    e.primal(z, t, ctx, "eps")
+    U1 = e.jvp_between(mid, "eps", V)
+    A1 = e.jvp(mid, Vx)
+    with pytest.raises(DpbError, match="not downstream"):
+        e.forward_from(z, t, ctx, mid, torch.zeros(1, e.tap_numel(mid)), dst=("down", 0))
+    W1 = e.vjp_between(mid, "eps", U1)
+    U2 = e.jvp_between(mid, "eps", V)
+    A2 = e.jvp(mid, Vx)
+    W2 = e.vjp_between(mid, "eps", U1)
+    assert torch.equal(U1, U2) and torch.equal(A1, A2) and torch.equal(W1, W2)
+    assert U1.abs().max() > 0 and A1.abs().max() > 0 and W1.abs().max() > 0
