@@ -76,6 +76,10 @@ struct dpb_engine {
   std::vector<AttnPlan> plans;
   std::vector<int> producer;        // buffer -> op index producing it (-1 for inputs)
   int x_buf = -1, x_channels = 0, temb_buf = -1, temb_dim = 0, temb_flip = 0, temb_hm1 = 0, ctx_buf = -1;
+  // Per-sample timesteps (dpb_primal_t): every SHARED buffer has max_batch rows, and the SHARED ops run once per sample into that sample's row.
+  // That is sound only if nothing but a SHARED op or a row bias reads a SHARED buffer; empty: it is, else what stands against it (found at create).
+  std::string per_sample_t_why;
+  bool temb_read = false;           // some op reads temb_buf (an autoencoder or text-encoder tape only fills the slot: its output does not depend on t)
   hipStream_t stream = 0;
   char* ws = nullptr;
   size_t ws_bytes = 0;
@@ -146,6 +150,8 @@ struct Pass {
   int src;                          // seed buffer: x_buf for the encoder entry points and the primal pass, any buffer for the *_between ones
   const char *bact, *oact;          // [n_buffers], [n_ops] activity for that seed (seed_flags)
   Forward fwd;                      // primal only
+  bool per_sample_t = false;        // primal only: the samples have timesteps of their own -- row b of every SHARED buffer is sample b's
+  int srow = 0;                     // ... and the row the SHARED op being run reads and writes (0: the one row of a shared timestep)
   Pass(const dpb_engine* e, int mode_, int tap_, int src_, const char* flags)
       : mode(mode_), tap(tap_), src(src_), bact(flags), oact(flags + e->bufs.size()) {}
 };
@@ -171,6 +177,12 @@ struct LaunchSpan {
   explicit LaunchSpan(dpb_engine* e_) : e(e_), at(launch_count) {}
   ~LaunchSpan() { e->n_launch = launch_count - at; }
 };
+
+// primal storage of a buffer as the op being run sees it: of a SHARED buffer, the row of the sample the op runs for
+char* primal_ptr(const dpb_engine* e, const Pass& ps, int b) {
+  const Buf& bf = e->bufs[b];
+  return e->P(b) + (bf.kind == DPB_BUF_SHARED ? (size_t)ps.srow * bf.rows * bf.C * e->es : 0);
+}
 
 void gemm_prep(dpb_engine* e, GemmArgs& a) {
   a.slab = (float*)(e->ws + e->slab);
@@ -248,9 +260,9 @@ int conv_fwd(dpb_engine* e, const Op& op, const Pass& ps, int n) {
   GemmArgs g;
   const bool shared_out = bo.kind == DPB_BUF_SHARED;
   const int ns = shared_out ? 1 : n;
-  g.A = mode == 0 ? e->P(d.in0) : e->T(d.in0);
+  g.A = mode == 0 ? primal_ptr(e, ps, d.in0) : e->T(d.in0);
   g.B = d.w[0];
-  g.C = mode == 0 ? e->P(d.out) : e->T(d.out);
+  g.C = mode == 0 ? primal_ptr(e, ps, d.out) : e->T(d.out);
   g.N = Cout;
   g.K = KS * KS * Cin;
   g.ldb = g.K;
@@ -268,11 +280,12 @@ int conv_fwd(dpb_engine* e, const Op& op, const Pass& ps, int n) {
     if (d.rowbias >= 0) {
       g.rowbias = e->P(d.rowbias) + (size_t)d.ip[10] * e->es;      // ip[10]: column window of a net-wide fused projection (tape.py shared_begin)
       g.rows_per_sample = bo.rows;
-      g.rowbias_div = 1 << 30;
+      g.ldrb = e->bufs[d.rowbias].rows * e->bufs[d.rowbias].C;     // the pitch of the fused projection's rows, not this op's N
+      g.rowbias_div = ps.per_sample_t ? 1 : 1 << 30;               // one row per sample, or row 0 for every sample
     }
   }
   if (d.res >= 0 && (mode == 0 || ps.bact[d.res])) {
-    g.R = mode == 0 ? e->P(d.res) : e->T(d.res);
+    g.R = mode == 0 ? primal_ptr(e, ps, d.res) : e->T(d.res);
     g.ldr = e->bufs[d.res].C;
   }
   if (mode == 1 && op.ln_next >= 0 && g_ln_fuse) {   // the LayerNorm that reads this product's output: its tangent leaves the same launch
@@ -776,7 +789,7 @@ int run_op(dpb_engine* e, const Op& op, const Pass& ps, int n) {
       if (mode != MODE_PRIMAL) return fail("SILU / quick-GELU ops are primal only (time-embedding path, text encoder)");
       const Buf& b = e->bufs[op.d.in0];
       const auto act = op.d.ip[0] == 2 ? launch_gelu : op.d.ip[0] == 1 ? launch_quick_gelu : launch_silu;
-      return act(e->dtype, e->P(op.d.in0), e->P(op.d.out), (long)(b.kind == DPB_BUF_SHARED ? 1 : n) * b.rows * b.C, e->stream);
+      return act(e->dtype, primal_ptr(e, ps, op.d.in0), primal_ptr(e, ps, op.d.out), (long)(b.kind == DPB_BUF_SHARED ? 1 : n) * b.rows * b.C, e->stream);
     }
   }
   return fail("unknown op kind %d", op.d.kind);
@@ -926,6 +939,17 @@ int dpb_engine_create(const dpb_net_desc* net, dpb_engine** out) {
       if (!d.w[0]) return bad("missing weight", i);
       if (d.ip[2] != e->bufs[d.in0].C || e->bufs[d.out].C != round8(d.ip[5])) return bad("conv channel mismatch", i);
     }
+    for (int b : op_inputs(d)) e->temb_read = e->temb_read || b == e->temb_buf;
+    if (e->per_sample_t_why.empty()) {              // per-sample timesteps: SHARED buffers are read by SHARED ops and as row biases only
+      char why[160] = "";
+      const bool so = e->bufs[d.out].kind == DPB_BUF_SHARED;
+      for (int b : op_inputs(d))
+        if ((e->bufs[b].kind == DPB_BUF_SHARED) != so)
+          snprintf(why, sizeof(why), "op %d reads %s buffer %d into %s buffer %d", i, so ? "per-sample" : "SHARED", b, so ? "SHARED" : "per-sample", d.out);
+      if (so && !(d.kind == DPB_OP_SILU || (d.kind == DPB_OP_CONV && d.ip[9] == DPB_GATHER_NONE && d.rowbias < 0)))
+        snprintf(why, sizeof(why), "op %d writes SHARED buffer %d and is neither a linear layer nor an activation", i, d.out);
+      e->per_sample_t_why = why;
+    }
     op.is_const = c;
     e->bufs[d.out].is_const = c;
     if (e->producer[d.out] >= 0) return bad("buffer written twice (tape must be SSA)", i);
@@ -976,7 +1000,7 @@ int dpb_engine_create(const dpb_net_desc* net, dpb_engine** out) {
   auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
   const size_t es = e->es;
   for (auto& b : e->bufs) {
-    size_t n = b.kind == DPB_BUF_SHARED ? 1 : e->maxB;
+    size_t n = e->maxB;                             // SHARED buffers too: one row per sample when the samples' timesteps differ (dpb_primal_t)
     b.p_off = take(n * b.rows * (size_t)b.C * es);
   }
   for (auto& b : e->bufs)
@@ -1100,7 +1124,23 @@ static int shift_seed(dpb_engine* e, const Forward& f, int batch, int xb, int la
   return launch_replicate_rows(ptr.data(), bytes.data(), (int)ptr.size(), batch, e->stream);
 }
 
-static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const float* ctx, int upto_buf, const Forward& f) {
+// the sinusoidal timestep embedding, computed on the host in fp32 exactly as the reference frameworks do (diffusion.py:783-804 / diffusers
+// Timesteps); emb: C(temb_buf) floats, the padding beyond temb_dim left as it is
+static void temb_row(const dpb_engine* e, float t, float* emb) {
+  const int half = e->temb_dim / 2;
+  for (int i = 0; i < half; ++i) {
+    float fr;
+    if (e->temb_hm1) fr = expf((float)i * (float)(-(log(10000.0) / (double)(half - 1))));   // diffusion.py:797-798
+    else fr = expf(((float)(-log(10000.0)) * (float)i) / (float)half);                      // diffusers get_timestep_embedding
+    float ang = t * fr;
+    float s = sinf(ang), c = cosf(ang);
+    if (e->temb_flip) { emb[i] = c; emb[half + i] = s; } else { emb[i] = s; emb[half + i] = c; }
+  }
+}
+
+// tv: null -- the batch shares t; else `batch` DISTINCT timesteps (dpb_primal_t has validated them and the tape): sample b's embedding goes to row b
+// of P(temb_buf) and every SHARED op runs once per sample, at the M = 1 of the shared-timestep pass, into that sample's row
+static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const float* ctx, int upto_buf, const Forward& f, const float* tv = nullptr) {
   if (!e || !x) return fail("null argument");
   if (!e->ws) return fail("workspace not set (dpb_engine_set_workspace)");
   if (batch < 1 || batch > e->maxB) return fail("batch=%d outside [1,%d]", batch, e->maxB);
@@ -1109,6 +1149,7 @@ static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const 
   e->flops = 0; e->gbytes = 0;
   Pass ps(e, MODE_PRIMAL, upto_buf, e->x_buf, seed_flags(e, e->x_buf));
   ps.fwd = f;
+  ps.per_sample_t = tv != nullptr;
   const Buf& bx = e->bufs[e->x_buf];
   const int xb = f.u ? f.xbatch : batch;           // samples of x / ctx (dpb_forward_shift with a shared prefix: 1)
   if (int r = launch_nchw_to_nhwc(e->dtype, x, e->P(e->x_buf), xb, e->x_channels, bx.rows, bx.C, e->stream)) return r;
@@ -1119,22 +1160,16 @@ static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const 
     if (int r = launch_nchw_to_nhwc(e->dtype, ctx, e->P(e->ctx_buf), xb * bc.rows, bc.Cv, 1, bc.C, e->stream)) return r;
   }
   if (e->temb_buf >= 0 && !f.temb_resident) {
-    // sinusoidal timestep embedding, computed on the host in fp32 exactly as the reference frameworks do
-    // (diffusion.py:783-804 / diffusers Timesteps), uploaded through the io staging area.
-    const int dim = e->temb_dim, half = dim / 2;
-    std::vector<float> emb(e->bufs[e->temb_buf].C, 0.f);
-    for (int i = 0; i < half; ++i) {
-      float fr;
-      if (e->temb_hm1) fr = expf((float)i * (float)(-(log(10000.0) / (double)(half - 1))));   // diffusion.py:797-798
-      else fr = expf(((float)(-log(10000.0)) * (float)i) / (float)half);                      // diffusers get_timestep_embedding
-      float ang = t * fr;
-      float s = sinf(ang), c = cosf(ang);
-      if (e->temb_flip) { emb[i] = c; emb[half + i] = s; } else { emb[i] = s; emb[half + i] = c; }
-    }
+    // uploaded through the io staging area: one copy and one synchronisation, however many timesteps
+    const int nrow = tv ? batch : 1;
+    const size_t C = e->bufs[e->temb_buf].C;
+    std::vector<float> emb(nrow * C, 0.f);
+    for (int b = 0; b < nrow; ++b) temb_row(e, tv ? tv[b] : t, emb.data() + b * C);
     float* stage = (float*)(e->ws + e->io_in);
     DPB_CHECK(hipMemcpyAsync(stage, emb.data(), emb.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
     DPB_CHECK(hipStreamSynchronize(e->stream));   // emb is a host temporary
-    if (int r = launch_nchw_to_nhwc(e->dtype, stage, e->P(e->temb_buf), 1, (int)emb.size(), 1, (int)emb.size(), e->stream)) return r;
+    for (int b = 0; b < nrow; ++b)                // (one launch per row: the launch of the shared-timestep pass, whatever the batch)
+      if (int r = launch_nchw_to_nhwc(e->dtype, stage + b * C, e->P(e->temb_buf) + b * C * e->es, 1, (int)C, 1, (int)C, e->stream)) return r;
   }
   if (e->pstats_bytes && !gn_deterministic()) DPB_CHECK(hipMemsetAsync(e->ws + e->pstats_off, 0, e->pstats_bytes, e->stream));   // atomic statistics path accumulates
   e->cur_batch = batch;
@@ -1144,8 +1179,11 @@ static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const 
   e->primal_last = -1;
   std::fill(e->skip.begin(), e->skip.end(), 0);
   for (int i = 0; i <= last; ++i) {
-    if (!e->skip[i])                               // (forward only: a GEGLU applied by the epilogue of the FF-in product)
+    if (e->skip[i]) continue;                      // (forward only: a GEGLU applied by the epilogue of the FF-in product)
+    const int reps = tv && e->bufs[e->ops[i].d.out].kind == DPB_BUF_SHARED ? batch : 1;   // a SHARED op under per-sample timesteps: once per sample
+    for (ps.srow = 0; ps.srow < reps; ++ps.srow)
       if (int r = run_op(e, e->ops[i], ps, i <= seed_op ? xb : batch)) return r;
+    ps.srow = 0;
     if (i == seed_op && f.u) {                     // dpb_forward_shift: the tap just computed, shifted per row (of sample 0 for every row when xb == 1)
       if (int r = shift_seed(e, f, batch, xb, last)) return r;
     } else if (i == seed_op) {                     // dpb_forward_from: the caller's activation replaces the one just computed
@@ -1161,10 +1199,33 @@ int dpb_primal(dpb_engine* e, const float* x, int batch, float t, const float* c
   return primal_pass(e, x, batch, t, ctx, upto_buf, Forward());
 }
 
+// The checks of the per-sample entry points.  *tv: null when every entry of t equals t[0] (the call IS the shared-timestep one), else t.
+static int check_timesteps(dpb_engine* e, int batch, const float* t, const float** tv) {
+  if (!e || !t) return fail("null argument");
+  if (batch < 1 || batch > e->maxB) return fail("batch=%d outside [1,%d]", batch, e->maxB);
+  *tv = nullptr;
+  for (int b = 0; b < batch; ++b) {
+    if (!isfinite(t[b])) return fail("t[%d] is not finite", b);
+    if (t[b] != t[0]) *tv = t;
+  }
+  if (!*tv) return 0;
+  if (e->temb_buf < 0 || !e->temb_read) return fail("distinct timesteps on a network without a timestep embedding (no op reads temb_buf): its samples cannot differ in t");
+  if (e->bufs[e->temb_buf].kind != DPB_BUF_SHARED || e->bufs[e->temb_buf].rows != 1) return fail("distinct timesteps need temb_buf to be a SHARED buffer of one row");
+  if (!e->per_sample_t_why.empty()) return fail("distinct timesteps are unsupported on this tape: %s", e->per_sample_t_why.c_str());
+  return 0;
+}
+
+int dpb_primal_t(dpb_engine* e, const float* x, int batch, const float* t, const float* ctx, int upto_buf) {
+  const float* tv;
+  if (int r = check_timesteps(e, batch, t, &tv)) return r;
+  return primal_pass(e, x, batch, t[0], ctx, upto_buf, Forward(), tv);
+}
+
 // dpb_forward and the entry points built on it: a primal pass that keeps no stash (f.stash == false), read out at upto_buf
-static int forward_pass(dpb_engine* e, const float* x, int batch, float t, const float* ctx, int upto_buf, int channels, float* out, const Forward& f) {
+static int forward_pass(dpb_engine* e, const float* x, int batch, float t, const float* ctx, int upto_buf, int channels, float* out, const Forward& f,
+                        const float* tv = nullptr) {
   if (!e || !out) return fail("null argument");
-  int r = primal_pass(e, x, batch, t, ctx, upto_buf, f);
+  int r = primal_pass(e, x, batch, t, ctx, upto_buf, f, tv);
   if (!r) r = dpb_read_buffer(e, upto_buf, channels, out);
   e->cur_batch = 0;                                // no stash was kept: dpb_jvp / dpb_vjp / dpb_pullback_iterate refuse until the next dpb_primal
   return r;
@@ -1174,6 +1235,14 @@ int dpb_forward(dpb_engine* e, const float* x, int batch, float t, const float* 
   Forward f;
   f.stash = false;
   return forward_pass(e, x, batch, t, ctx, upto_buf, channels, out, f);
+}
+
+int dpb_forward_t(dpb_engine* e, const float* x, int batch, const float* t, const float* ctx, int upto_buf, int channels, float* out) {
+  const float* tv;
+  if (int r = check_timesteps(e, batch, t, &tv)) return r;
+  Forward f;
+  f.stash = false;
+  return forward_pass(e, x, batch, t[0], ctx, upto_buf, channels, out, f, tv);
 }
 
 int dpb_forward_from(dpb_engine* e, const float* x, int batch, float t, const float* ctx, int src_buf, const float* h, int dst_buf, int channels,

@@ -335,7 +335,7 @@ __device__ __forceinline__ void epilogue_slab(const GemmArgs& p, bf16* C, const 
         const int mc = min(mrow0 + (it0 + u) * RPI + r0, p.M - 1);
         if (R) rr[u] = *reinterpret_cast<const uint4*>(R + (long)mc * p.ldr + n);
         if (p.accumulate) ro[u] = *reinterpret_cast<const uint4*>(C + (long)mc * p.ldc + n);
-        if (p.rowbias) rb[u] = *reinterpret_cast<const uint4*>((const bf16*)p.rowbias + (long)((mc / p.rows_per_sample) / p.rowbias_div) * p.N + n);
+        if (p.rowbias) rb[u] = *reinterpret_cast<const uint4*>((const bf16*)p.rowbias + (long)((mc / p.rows_per_sample) / p.rowbias_div) * p.ldrb + n);
       }
 #pragma unroll
       for (int u = 0; u < BT; ++u) {
@@ -381,7 +381,7 @@ __device__ __forceinline__ void epilogue_slab(const GemmArgs& p, bf16* C, const 
       for (int e = 0; e < 8 && n + e < p.N; ++e) {
         float x = p.alpha * v[e];
         if (p.bias) x += p.bias[n + e];
-        if (p.rowbias) x += ld16<FL>((const bf16*)p.rowbias + (long)smp * p.N + n + e);
+        if (p.rowbias) x += ld16<FL>((const bf16*)p.rowbias + (long)smp * p.ldrb + n + e);
         if (R) x += ld16<FL>(R + (long)m * p.ldr + n + e);
         if (p.accumulate) x += ld16<FL>(cp + e);
         st16<FL>(cp + e, x);

@@ -318,7 +318,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
         }
         if (p.rowbias) {
           float b8[8];
-          V8<T>::load((const T*)p.rowbias + (long)smp * p.N + n, b8);
+          V8<T>::load((const T*)p.rowbias + (long)smp * p.ldrb + n, b8);
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] += b8[e];
         }
@@ -339,7 +339,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs p) {
         for (int e = 0; e < 8 && n + e < p.N; ++e) {
           float x = p.alpha * v[e];
           if (p.bias) x += p.bias[n + e];
-          if (p.rowbias) x += TT<T>::ld((const T*)p.rowbias + (long)smp * p.N + n + e);
+          if (p.rowbias) x += TT<T>::ld((const T*)p.rowbias + (long)smp * p.ldrb + n + e);
           if (R) x += TT<T>::ld(R + (long)m * p.ldr + n + e);
           if (p.accumulate) x += TT<T>::ld(cp + e);
           TT<T>::st(cp + e, x);
@@ -370,7 +370,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmArgs p) {
       // behind the last sum
       float bias8[8], rb8[8], r8[8], old8[8];
       if (p.bias) V8<float>::load(p.bias + n, bias8);
-      if (p.rowbias) V8<T>::load((const T*)p.rowbias + (long)((m / p.rows_per_sample) / p.rowbias_div) * p.N + n, rb8);
+      if (p.rowbias) V8<T>::load((const T*)p.rowbias + (long)((m / p.rows_per_sample) / p.rowbias_div) * p.ldrb + n, rb8);
       if (p.R) V8<T>::load((const T*)p.R + (long)z1 * p.sR1 + (long)z2 * p.sR2 + (long)m * p.ldr + n, r8);
       if (p.accumulate) V8<T>::load(cp, old8);
       float v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -432,7 +432,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmArgs p) {
     const int z1 = z / p.Z2, z2 = z % p.Z2;
     float x = p.alpha * acc;
     if (p.bias) x += p.bias[n];
-    if (p.rowbias) x += TT<T>::ld((const T*)p.rowbias + (long)((m / p.rows_per_sample) / p.rowbias_div) * p.N + n);
+    if (p.rowbias) x += TT<T>::ld((const T*)p.rowbias + (long)((m / p.rows_per_sample) / p.rowbias_div) * p.ldrb + n);
     if (p.R) x += TT<T>::ld((const T*)p.R + (long)z1 * p.sR1 + (long)z2 * p.sR2 + (long)m * p.ldr + n);
     T* cp = (T*)p.C + (long)z1 * p.sC1 + (long)z2 * p.sC2 + (long)m * p.ldc + n;
     if (p.accumulate) x += TT<T>::ld(cp);

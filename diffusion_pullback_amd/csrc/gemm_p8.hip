@@ -409,7 +409,7 @@ __global__ __launch_bounds__(512) void gemm_p8_kernel(GemmArgs p) {
             if (!act) continue;
             if (R) o.rr[u] = *reinterpret_cast<const uint4*>(R + (long)mc * p.ldr + n);
             if (p.accumulate) o.ro[u] = *reinterpret_cast<const uint4*>(C + (long)mc * p.ldc + n);
-            if (p.rowbias) o.rb[u] = *reinterpret_cast<const uint4*>((const bf16*)p.rowbias + (long)((mc / p.rows_per_sample) / p.rowbias_div) * p.N + n);
+            if (p.rowbias) o.rb[u] = *reinterpret_cast<const uint4*>((const bf16*)p.rowbias + (long)((mc / p.rows_per_sample) / p.rowbias_div) * p.ldrb + n);
           }
         };
         load_ops(0, ops[0]);

@@ -16,8 +16,9 @@ enum { EPI_PLAIN = 0, EPI_GEGLU_TAN = 1, EPI_GEGLU_ADJ = 2, EPI_LN_TAN = 3, EPI_
 struct GemmArgs {
   const void* A = nullptr; const void* B = nullptr; void* C = nullptr; const void* R = nullptr;
   const float* bias = nullptr;
-  const void* rowbias = nullptr;      // [samples][N] in T; sample(m) = (m / rows_per_sample) / rowbias_div
+  const void* rowbias = nullptr;      // [samples][ldrb] in T, the first N columns of a row are this product's; sample(m) = (m / rows_per_sample) / rowbias_div
   int rows_per_sample = 1, rowbias_div = 1;
+  int ldrb = 0;                       // row pitch of rowbias in elements (a column window of a wider buffer: not N); multiplies sample(m), so one shared row needs none
   int M = 0, N = 0, K = 0;
   int lda = 0, ldb = 0, ldc = 0, ldr = 0;
   // two-level batch z = z1 * Z2 + z2 ; per-operand offset = (z1 / div) * s1 + z2 * s2  (elements)

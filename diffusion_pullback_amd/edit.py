@@ -2,11 +2,11 @@
 
 Mirrors the public surface of the reference's ``modules/edit.py``:
   * ``EditStableDiffusion``  (reference src/modules/edit.py:31-535)
-      run_DDIMinversion :112-183, run_edit_local_encoder_pullback_zt :185-307, DDIMforwardsteps :385-482,
-      x_space_guidance :484-502, run_DDIMforward :101-110
+      run_DDIMinversion :112-183, run_edit_local_encoder_pullback_zt :185-307, run_sample_encoder_local_tangent_space_zt :310-383,
+      DDIMforwardsteps :385-482, x_space_guidance :484-502, run_DDIMforward :101-110
   * ``EditUncondDiffusion``  (reference src/modules/edit.py:540-779, :1601-1734)
-      run_DDIMinversion :613-678, run_edit_local_encoder_pullback_zt :680-779, DDIMforwardsteps :1601-1714,
-      x_space_guidance :1716-1734
+      run_DDIMinversion :613-678, run_edit_local_encoder_pullback_zt :680-779, run_sample_encoder_local_tangent_space_zt :1517-1599,
+      DDIMforwardsteps :1601-1714, x_space_guidance :1716-1734
 
 Kept from the reference: the step counts (inv_steps-2 inversion steps, ``edit_t_idx`` forward steps,
 ``x_space_guidance_num_step`` guidance steps, the rest decode), the ``[::len // vis_num]`` subsample,
@@ -64,6 +64,15 @@ def save_spectrum_plot(s: torch.Tensor, path: str, dpi=None) -> None:
     plt.close()
 
 
+def save_vT_visualisation(vT: torch.Tensor, lat_shape, path: str) -> None:
+    """vT [k, N_in] shown through the 3 principal channel directions of its pixels, min-max normalised (edit.py:253-263, :359-369)"""
+    pix = vT.view(-1, *lat_shape).permute(0, 2, 3, 1).reshape(-1, lat_shape[0]).float()
+    _, _, basis = torch.pca_lowrank(pix, q=min(3, pix.shape[1]), center=True, niter=2)
+    vis = torch.einsum("bcwh,cp->bpwh", vT.view(-1, *lat_shape).float(), basis)
+    vis = vis - vis.min()
+    save_image(vis / vis.max(), path)
+
+
 class _SeededPrompts:
     """Stand-in for pipe._encode_prompt (edit.py:505-522): a deterministic embedding per prompt string."""
 
@@ -97,6 +106,56 @@ class _EditBase(object):
     def _basis_paths(self, save_dir, name):
         os.makedirs(save_dir, exist_ok=True)
         return [os.path.join(save_dir, p + name + ".pt") for p in ("u-", "s-", "vT-")]
+
+    def _random_latent(self, idx):
+        """dataset 'Random': entry idx of a dataset of Gaussian latents (the caller's dataset, or one seeded by (seed, idx): the same latent
+        whenever idx is asked for, as a dataset entry is)"""
+        if self.dataset is not None:
+            return self.dataset[idx].to(device=self.device, dtype=self.dtype)
+        g = torch.Generator().manual_seed((int(self.seed) << 20) + int(idx))
+        return torch.randn(1, self.c_in, self.image_size, self.image_size, generator=g).to(device=self.device, dtype=self.dtype)
+
+    def _pending_tangent_spaces(self, h_t, num_local_basis, save_dir, exp_name):
+        """the (basis index, h_t) pairs still to sample, in the reference's order (h_t outer, basis index inner), with their EXP_NAME and files;
+        a pair whose u-, s- and vT- files all exist is skipped (edit.py:337-339, :1560-1562)"""
+        os.makedirs(save_dir, exist_ok=True)
+        pending = []
+        for ht in (list(h_t) if isinstance(h_t, (list, tuple)) else [h_t]):
+            for idx in range(num_local_basis):
+                name = exp_name(idx, ht)
+                paths = self._basis_paths(save_dir, name)
+                if all(os.path.exists(p) for p in paths):
+                    print(f"!!!ALREADY SAMPLED LOCAL BASIS IDX : {idx}!!!")
+                    continue
+                pending.append((idx, ht, name, paths))
+        return pending
+
+    def _sample_tangent_spaces(self, pending, make_xt, ctx, op, block_idx, pca_rank, thr, save_dir, finish):
+        """The pending pairs through unet.local_encoder_pullback_batch, in groups of at most min(max_batch, max_rank // pca_rank): the samples of
+        a group -- each at its own (x_t, t) -- advance together, each stopped by its own rule.  make_xt(idx, h_t) -> (x_t [1, ...], t) is
+        called group by group; finish(name, s, vT, lat_shape) writes the pictures of one basis.  min_iter / max_iter: the reference's call-site
+        constants (edit.py:354-357, :1581-1584)."""
+        eng = getattr(self.unet, "engine", None)
+        group = min(getattr(eng, "max_batch", 1), getattr(self.unet, "max_rank", pca_rank) // pca_rank)
+        if group < 1:
+            raise ValueError(f"pca_rank={pca_rank} exceeds the {getattr(self.unet, 'max_rank', None)} tangents this U-Net engine was built for")
+        self.last_tangent_inputs = {}                          # (basis index, h_t) -> (x_t, t) of this call (introspection for tests)
+        for g0 in range(0, len(pending), group):
+            part = pending[g0:g0 + group]
+            xs, ts = [], []
+            for idx, ht, name, _ in part:
+                print(f"!!!SAMPLE LOCAL BASIS IDX : {idx}!!!")
+                xt, t = make_xt(idx, ht)
+                xs.append(xt.to(device=self.device, dtype=self.dtype)); ts.append(float(t))
+                self.last_tangent_inputs[(idx, ht)] = (xs[-1], ts[-1])
+            with T.phase("local_encoder_pullback_batch (power iteration)"):
+                u, s, vT, _ = self.unet.local_encoder_pullback_batch(torch.cat(xs, dim=0), torch.tensor(ts), ctx, op=op, block_idx=block_idx,
+                                                                     pca_rank=pca_rank, min_iter=10, max_iter=50, convergence_threshold=thr)
+            for b, (idx, ht, name, (u_path, s_path, vT_path)) in enumerate(part):
+                ub, sb, vb = u[b].clone(), s[b].clone(), vT[b].clone()      # (clones: a saved view would carry the whole group's storage)
+                finish(name, sb, vb, xs[b].shape[1:])
+                save_spectrum_plot(sb, os.path.join(save_dir, f"eigenvalue_spectrum-{name}.png"), dpi=80)   # edit.py:374-377, :1586-1589
+                torch.save(ub, u_path); torch.save(sb, s_path); torch.save(vb, vT_path)
 
 
 # =================================================================== Stable Diffusion
@@ -183,6 +242,47 @@ class EditStableDiffusion(_EditBase):
         return latents
 
     @torch.no_grad()
+    def run_sample_encoder_local_tangent_space_zt(self, h_t, op, block_idx, pca_rank=50, num_local_basis=10, use_edit_prompt=None, edit_prompt=None,
+                                                  vis_vT=True):
+        """Reference: src/modules/edit.py:310-383 -- the local tangent spaces (u, s, vT) of num_local_basis latents at h_t, saved for analysis.
+        h_t: a float, or a list (the loop of src/main.py:61-76 over EDIT_T_LIST in one call).  The pending (basis index, h_t) pairs -- each at its
+        own (z_t, t): inversion or a Random latent, then DDIMforwardsteps to h_t -- advance together through local_encoder_pullback_batch instead
+        of one call each; min_iter=10, max_iter=50, threshold 1e-3 as at edit.py:354-357 (its chunk_size only splits the reference's passes).
+        Files: u- / s- / vT-<EXP_NAME>.pt, eigenvalue_spectrum-<EXP_NAME>.png and (vis_vT) vT-<EXP_NAME>.png in the basis directory of
+        run_edit_local_encoder_pullback_zt (the reference's own directory and the -ver_ suffix of its EXP_NAME need attributes it never defines:
+        sd_ver, scheduler_name; the after_res / after_sa suffixes belong to taps that do not exist here).  edit_prompt sets the prompt (None: the
+        driver's own); use_edit_prompt, the reference's alternative, picks from caption lists that do not exist here and raises ValueError.  With a
+        list h_t a basis index is inverted once per call, not once per h_t."""
+        if use_edit_prompt is not None:                        # edit.py:323: exactly one of the two; the caption lists use_edit_prompt picks from do not exist here
+            raise ValueError("use_edit_prompt selects from caption lists that are not available: pass edit_prompt (None keeps the driver's edit prompt)")
+        if edit_prompt is not None:                                                             # edit.py:324
+            self.edit_prompt = edit_prompt
+            self.edit_prompt_emb = self._get_prompt_emb(self.edit_prompt)
+        self.scheduler.set_timesteps(self.for_steps)
+        save_dir = os.path.join(self.input_root, f"local_encoder_pullback_stable_diffusion-dataset_{self.dataset_name}-num_steps_{self.for_steps}-pca_rank_{pca_rank}")
+        exp_name = lambda idx, ht: f'zt-{self.dataset_name}_{idx}-{ht}T-"{self.edit_prompt}"-{op}-block_{block_idx}-seed_{self.seed}'
+        pending = self._pending_tangent_spaces(h_t, num_local_basis, save_dir, exp_name)
+
+        zTs = {}                                               # (a list h_t asks for the same latent once per h_t: one inversion per basis index and call)
+
+        def make_zt(idx, ht):
+            if idx not in zTs:
+                zTs[idx] = self._random_latent(idx) if self.dataset_name == "Random" else self.run_DDIMinversion(idx=idx)   # edit.py:344-348
+            zT = zTs[idx]
+            self.scheduler.set_timesteps(self.for_steps, device=self.device)
+            h_t_idx = int((self.scheduler.timesteps - ht * 1000).abs().argmin())                # edit.py:316
+            if h_t_idx == 0:                                   # (DDIMforwardsteps announces its first step before it looks for the last: nothing to run)
+                return zT, self.scheduler.timesteps[0]
+            zt, t, _ = self.DDIMforwardsteps(zT, t_start_idx=0, t_end_idx=h_t_idx)              # edit.py:350-351
+            return zt, t
+
+        def finish(name, s, vT, lat_shape):
+            self.EXP_NAME = name
+            if vis_vT:
+                save_vT_visualisation(vT, lat_shape, os.path.join(save_dir, f"vT-{name}.png"))  # edit.py:359-369
+        self._sample_tangent_spaces(pending, make_zt, self.edit_prompt_emb, op, block_idx, pca_rank, 1e-3, save_dir, finish)
+
+    @torch.no_grad()
     def DDIMforwardsteps(self, zt, t_start_idx, t_end_idx, **kwargs):
         print("start DDIMforward")
         self._phase = "DDIM forward to edit_t: U-Net forwards" if t_end_idx != -1 else "DDIM decode of the edited latents: U-Net forwards"
@@ -258,12 +358,7 @@ class EditStableDiffusion(_EditBase):
             vT = vT.to(device=self.device, dtype=self.dtype)
             torch.save(u, u_path); torch.save(s, s_path); torch.save(vT, vT_path)
             save_spectrum_plot(s, os.path.join(save_dir, f"eigenvalue_spectrum-{name}.png"))        # edit.py:249-251
-            # vT shown through the 3 principal channel directions of its pixels, min-max normalised (edit.py:253-263)
-            pix = vT.view(-1, *zT.shape[1:]).permute(0, 2, 3, 1).reshape(-1, zT.shape[1]).float()
-            _, _, basis = torch.pca_lowrank(pix, q=min(3, pix.shape[1]), center=True, niter=2)
-            vis = torch.einsum("bcwh,cp->bpwh", vT.view(-1, *zT.shape[1:]).float(), basis)
-            vis = vis - vis.min()
-            save_image(vis / vis.max(), os.path.join(self.obs_folder, f"vT-{name}.png"))
+            save_vT_visualisation(vT, zT.shape[1:], os.path.join(self.obs_folder, f"vT-{name}.png"))    # edit.py:253-263
         self.last_basis = (u, vT)
         u = u / u.norm(dim=0, keepdim=True)                                                     # edit.py:267-268
         vT = vT / vT.norm(dim=1, keepdim=True)
@@ -410,6 +505,31 @@ class EditUncondDiffusion(_EditBase):
         if save_image_:
             save_image((xt / 2 + 0.5).clamp(0, 1), os.path.join(self.result_folder, f"x0_gen-{self.EXP_NAME}.png"), nrow=xt.size(0))
         return xt if return_xt else None
+
+    @torch.no_grad()
+    def run_sample_encoder_local_tangent_space_zt(self, h_t, op, block_idx, pca_rank=50, num_local_basis=100, fix_xt=False, fix_t=False):
+        """Reference: src/modules/edit.py:1517-1599 -- the local tangent spaces (u, s, vT) of num_local_basis noise images at h_t.  h_t: a float,
+        or a list (the loop of src/main.py:80-91 in one call).  fix_xt pairs x = x_T with t(h_t), fix_t pairs x_t(h_t) with t = T (the two ablations
+        of edit.py:1571-1576; not both).  The pending (basis index, h_t) pairs advance together through local_encoder_pullback_batch -- under
+        fix_xt the rows of a group differ in t only; min_iter=10, max_iter=50, threshold 1e-4 as at edit.py:1581-1584.  Files: u- / s- /
+        vT-<EXP_NAME>.pt and eigenvalue_spectrum-<EXP_NAME>.png in the basis directory of run_edit_local_encoder_pullback_zt with -fix_xt / -fix_t
+        appended (the reference's own directory needs a scheduler_name it never defines)."""
+        assert (not fix_xt) or (not fix_t)                                                      # edit.py:1539
+        self.scheduler.set_timesteps(self.for_steps)
+        save_dir = os.path.join(self.input_root, f"local_encoder_pullback_uncond-model_{self.model_name}-dataset_{self.dataset_name}-num_steps_{self.for_steps}-pca_rank_{pca_rank}")
+        save_dir += "-fix_xt" if fix_xt else "-fix_t" if fix_t else ""                          # edit.py:1547-1550
+        exp_name = lambda idx, ht: f"xt-{self.dataset_name}_{idx}-{ht}T-{op}-block_{block_idx}-seed_{self.seed}"
+        pending = self._pending_tangent_spaces(h_t, num_local_basis, save_dir, exp_name)
+
+        def make_xt(idx, ht):
+            xT = self._random_latent(idx)                                                       # edit.py:1568: the dataset of this job holds x_T
+            self.scheduler.set_timesteps(self.for_steps, device=self.device)
+            h_t_idx = int((self.scheduler.timesteps - ht * 1000).abs().argmin())                # edit.py:1543
+            if fix_xt:                                         # edit.py:1572-1573: x = x_T (DDIMforwardsteps(.., t_end_idx=0) returns its input), t of h_t
+                return xT, self.scheduler.timesteps[h_t_idx]
+            xt, t, _ = self.DDIMforwardsteps(xT, t_start_idx=0, t_end_idx=h_t_idx)
+            return xt, self.scheduler.timesteps[0] if fix_t else t                              # edit.py:1575-1576
+        self._sample_tangent_spaces(pending, make_xt, None, op, block_idx, pca_rank, 1e-4, save_dir, lambda name, s, vT, lat_shape: setattr(self, "EXP_NAME", name))
 
     @torch.no_grad()
     def x_space_guidance(self, xt, t_idx, vk, single_edit_step):

@@ -22,6 +22,21 @@ def _f32(t: torch.Tensor, device) -> torch.Tensor:
     return t.detach().to(device=device, dtype=torch.float32).contiguous()
 
 
+def timesteps(t, batch: int):
+    """The one rule for a timestep argument of a call on `batch` samples.  A scalar, a 0-d or a 1-element t is shared by the batch: returns the
+    float.  A t of exactly `batch` elements is per-sample: returns the list of floats, collapsed to the one float when they are all equal.  Any
+    other length raises ValueError (the batch would silently run at t[0])."""
+    if torch.is_tensor(t):
+        v = [float(a) for a in t.detach().reshape(-1).to(torch.float32).tolist()]
+    elif isinstance(t, (list, tuple)):
+        v = [float(torch.tensor(a, dtype=torch.float32).item()) for a in t]
+    else:
+        v = [float(torch.tensor(t, dtype=torch.float32).item())]
+    if len(v) != 1 and len(v) != int(batch):
+        raise ValueError(f"timestep has {len(v)} elements for a batch of {batch}: one (shared by the batch) or one per sample")
+    return v[0] if all(a == v[0] for a in v) else v
+
+
 class Engine:
     def __init__(self, tape: Tape, temb_dim: int, flip_sin_to_cos: bool, half_minus_one: bool, x_channels: int,
                  max_batch: int = 1, max_tangents: int = 16):
@@ -107,13 +122,18 @@ class Engine:
             ctx = None
         return x, b, ctx
 
-    def primal(self, x: torch.Tensor, t: float, ctx: Optional[torch.Tensor], tap) -> None:
-        """x [B,C,H,W]; ctx [B,L,D] or None.  Keeps the activations resident for jvp/vjp."""
+    def primal(self, x: torch.Tensor, t, ctx: Optional[torch.Tensor], tap) -> None:
+        """x [B,C,H,W]; ctx [B,L,D] or None; t a float, or a sequence / tensor of B timesteps (row b is the net at t[b]: dpb_primal_t).
+        Keeps the activations resident for jvp/vjp."""
         buf = self.tape.taps[tap]
         with torch.cuda.device(self.device):
             self._set_stream()
             x, b, ctx = self._inputs(x, ctx)
-            L.check(self.lib.dpb_primal(self.h, _ptr(x), b, float(t), _ptr(ctx), buf))
+            t = timesteps(t, b)
+            if isinstance(t, float):
+                L.check(self.lib.dpb_primal(self.h, _ptr(x), b, t, _ptr(ctx), buf))
+            else:
+                L.check(self.lib.dpb_primal_t(self.h, _ptr(x), b, (C.c_float * b)(*t), _ptr(ctx), buf))
             self.batch = b
 
     def read(self, tap) -> torch.Tensor:
@@ -130,7 +150,8 @@ class Engine:
     def forward(self, x, t, ctx=None, tap="eps", out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Forward only (dpb_forward): the U-Net calls of the DDIM / guidance loop and get_h.  Keeps no tangent / adjoint stash,
         so jvp / vjp / iterate need a primal() first (the engine refuses otherwise).  out: a contiguous fp32 device tensor of
-        B * C * H * W elements to write into (a row slice of a feature matrix); returned viewed as [B, C, H, W]."""
+        B * C * H * W elements to write into (a row slice of a feature matrix); returned viewed as [B, C, H, W].  t: a float, or a sequence /
+        tensor of B timesteps (dpb_forward_t)."""
         buf = self.tape.taps[tap]
         c, h, w = self.tape.tap_shape[buf]
         with torch.cuda.device(self.device):
@@ -142,7 +163,11 @@ class Engine:
                 if not (out.is_cuda and out.device == x.device and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == b * c * h * w):
                     raise L.DpbError(f"out must be a contiguous fp32 tensor of {b * c * h * w} elements on {x.device}")
                 out = out.view(b, c, h, w)
-            L.check(self.lib.dpb_forward(self.h, _ptr(x), b, float(t), _ptr(ctx), buf, c, _ptr(out)))
+            t = timesteps(t, b)
+            if isinstance(t, float):
+                L.check(self.lib.dpb_forward(self.h, _ptr(x), b, t, _ptr(ctx), buf, c, _ptr(out)))
+            else:
+                L.check(self.lib.dpb_forward_t(self.h, _ptr(x), b, (C.c_float * b)(*t), _ptr(ctx), buf, c, _ptr(out)))
             self.batch = 0
         return out
 

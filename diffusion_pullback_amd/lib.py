@@ -61,6 +61,9 @@ SYMBOLS = {
     "dpb_engine_set_workspace": (_I, [_P, _P, C.c_size_t]),
     "dpb_primal": (_I, [_P, _P, _I, _F, _P, _I]),
     "dpb_forward": (_I, [_P, _P, _I, _F, _P, _I, _I, _P]),
+    # per-sample timesteps: t is a host array of `batch` floats
+    "dpb_primal_t": (_I, [_P, _P, _I, C.POINTER(_F), _P, _I]),
+    "dpb_forward_t": (_I, [_P, _P, _I, C.POINTER(_F), _P, _I, _I, _P]),
     "dpb_read_buffer": (_I, [_P, _I, _I, _P]),
     "dpb_jvp": (_I, [_P, _I, _P, _I, _P]),
     "dpb_vjp": (_I, [_P, _I, _P, _I, _P]),

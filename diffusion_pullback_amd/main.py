@@ -10,6 +10,10 @@ New flags (not in the reference): --pca_rank, --op, --block_idx, --dtype bf16, -
 file; default: seeded synthetic weights, there are no checkpoints offline), --net_scale (reduced nets),
 --vae (none | synthetic | <state-dict file>: decode the edited latents to PNGs with the on-device AutoencoderKL),
 --text_encoder (none | synthetic | <state-dict file>) + --tokenizer_dir (CLIP vocab.json / merges.txt): on-device prompt encoder.
+``--run_sample_encoder_local_tangent_space_zt True`` (reference src/main.py:45-91) samples the local tangent spaces of --num_local_basis latents at
+every timestep of --h_t_list (comma-separated; default: the single --h_t), with --fix_xt / --fix_t for the unconditional net; the pending
+(latent, h_t) pairs advance together, each at its own timestep.  The reference's call sites fix pca_rank=50 and loop over its EDIT_T_LIST (and, for
+SD, over MS-COCO captions, which are not available offline): here --pca_rank, --h_t_list and --edit_prompt say the same.
 """
 from __future__ import annotations
 
@@ -52,6 +56,9 @@ _FLAGS = [  # (name, type, default) -- define_argparser.py:20-110, live path onl
     ("h_t", float, 0.8), ("edit_t", float, 1.0), ("x_edit_step_size", float, 0), ("pca_device", str, "cpu"), ("buffer_device", str, "cpu"),
     ("save_result_as", str, "image"), ("run_ddim_forward", str2bool, False), ("run_ddim_inversion", str2bool, False),
     ("run_edit_local_encoder_pullback_zt", str2bool, False),
+    # define_argparser.py: the tangent-space sampling job of main.py:45-91 (h_t_list is new: the reference edits EDIT_T_LIST in its source)
+    ("run_sample_encoder_local_tangent_space_zt", str2bool, False), ("num_local_basis", int, 10), ("h_t_list", str, ""),
+    ("fix_xt", str2bool, False), ("fix_t", str2bool, False),
     # new
     ("pca_rank", int, 2), ("op", str, "mid"), ("block_idx", int, 0), ("vis_num", int, 4), ("vis_num_pc", int, 2), ("weights", str, ""),
     ("net_scale", str, "full"), ("vae", str, "none"), ("text_encoder", str, "none"), ("tokenizer_dir", str, ""),
@@ -76,6 +83,12 @@ def parse_args(argv=None):
     if args.memory_bound is not None and args.memory_bound < 1:
         p.error("--memory_bound must be a positive integer")
     args.memory_bound_given = args.memory_bound
+    try:
+        args.h_t_values = [float(v) for v in args.h_t_list.split(",") if v.strip()] or [args.h_t]
+    except ValueError:
+        p.error("--h_t_list must be comma-separated numbers, e.g. 0.8,0.5")
+    if args.fix_xt and args.fix_t:
+        p.error("--fix_xt and --fix_t exclude each other")
     if extra:
         print(f"note: ignoring flags of experiments outside the pullback path: {extra}")
     return args
@@ -125,6 +138,18 @@ def preset(args):
     return args
 
 
+# tangents advanced together by the tangent-space job: 2 samples at pca_rank 50, 10 at 10.  The workspace grows with them.  Computed, not measured
+# (dpb_engine_workspace_bytes of the whole SD-v1.5 tape in bf16, on the host): 159.7 GiB at max_batch 2 / 100 tangents, 79.9 GiB at 1 / 50, of the
+# MI355X's 288 GB; --memory_bound lowers the group
+TANGENT_BUDGET = 100
+
+
+def tangent_space_group(args) -> int:
+    """samples local_encoder_pullback_batch advances together in the tangent-space job: the pending pairs, bounded by memory_bound and TANGENT_BUDGET"""
+    pairs = max(1, args.num_local_basis) * len(args.h_t_values)
+    return max(1, min(pairs, args.memory_bound, TANGENT_BUDGET // max(args.pca_rank, 1)))
+
+
 def build_unet(args) -> PullbackUNet:
     from . import weights as W
     small = args.net_scale != "full"
@@ -134,6 +159,10 @@ def build_unet(args) -> PullbackUNet:
         # 2 * vis_num_pc chains together: batch 4 * vis_num_pc for the guidance step, 2 * vis_num_pc * (vis_num + 1) decode trajectories
         max_batch = max(max_batch, min(args.trajectory_batch, 2 * args.vis_num_pc * (args.vis_num + 1)) * (2 if args.guidance_scale > 1.0 else 1),
                         min(args.trajectory_batch, 4 * args.vis_num_pc))
+    max_rank = max(args.pca_rank, 2)
+    if getattr(args, "run_sample_encoder_local_tangent_space_zt", False):       # the group of (latent, h_t) pairs: batch and tangents for all of it
+        max_batch = max(max_batch, tangent_space_group(args))
+        max_rank = max(max_rank, tangent_space_group(args) * args.pca_rank)
     if args.is_stable_diffusion:
         cfg = cf.sd_config_for(args.model_name)           # SD-v1.x or SD-2(.1)-base; anything else raises
         if small:
@@ -143,7 +172,7 @@ def build_unet(args) -> PullbackUNet:
         W.check_shapes(params, cf.sd_param_shapes(cfg), f"{args.model_name} U-Net")
         if small:
             args.image_size = cfg.sample_size
-        return PullbackUNet("sd", cfg, params, dtype=args.compute_dtype, device=args.device, max_batch=max_batch, max_rank=max(args.pca_rank, 2))
+        return PullbackUNet("sd", cfg, params, dtype=args.compute_dtype, device=args.device, max_batch=max_batch, max_rank=max_rank)
     cfg = cf.CELEBA_HQ_256 if not small else cf.DDPMConfig(ch=32, ch_mult=(1, 2, 2), num_res_blocks=1, attn_resolutions=(16,), resolution=32)
     if args.weights:                                      # diffusers UNet2DModel keys (google/ddpm-ema-celebahq-256) or vendored names
         params = W.ddpm_hf_to_vendored_names(torch.load(args.weights, map_location="cpu"), cfg)
@@ -152,7 +181,7 @@ def build_unet(args) -> PullbackUNet:
     W.check_shapes(params, cf.ddpm_param_shapes(cfg), f"{args.model_name} U-Net")
     if small:
         args.image_size = cfg.resolution
-    return PullbackUNet("ddpm", cfg, params, dtype=args.compute_dtype, device=args.device, max_batch=max_batch, max_rank=max(args.pca_rank, 2))
+    return PullbackUNet("ddpm", cfg, params, dtype=args.compute_dtype, device=args.device, max_batch=max_batch, max_rank=max_rank)
 
 
 def build_vae(args):
@@ -210,6 +239,13 @@ def main(argv=None):
         else:
             edit.run_edit_local_encoder_pullback_zt(idx=args.sample_idx, op=args.op, block_idx=args.block_idx, vis_num=args.vis_num,
                                                     vis_num_pc=args.vis_num_pc, pca_rank=args.pca_rank)
+    if args.run_sample_encoder_local_tangent_space_zt:                           # main.py:45-91
+        kw = dict(h_t=args.h_t_values if args.h_t_list else args.h_t, op=args.op, block_idx=args.block_idx, pca_rank=args.pca_rank,
+                  num_local_basis=args.num_local_basis)
+        if args.is_stable_diffusion:
+            edit.run_sample_encoder_local_tangent_space_zt(use_edit_prompt=None, edit_prompt=args.edit_prompt, **kw)
+        else:
+            edit.run_sample_encoder_local_tangent_space_zt(fix_xt=args.fix_xt, fix_t=args.fix_t, **kw)
     if args.run_ddim_forward:
         edit.run_DDIMforward(num_samples=5)
     if args.run_ddim_inversion:

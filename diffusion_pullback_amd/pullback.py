@@ -31,6 +31,7 @@ import torch
 
 from . import lib as L
 from .engine import Engine, pca_lowrank
+from .engine import timesteps as _timesteps
 from .tape import build_ddpm, build_sd
 
 MAX_RANK = 56          # default tangent capacity of an engine (workspace sizing)
@@ -44,10 +45,13 @@ class UNetOutput:
         self.sample = sample
 
 
-def _t_float(t) -> float:
-    if torch.is_tensor(t):
-        return float(t.reshape(-1)[0].to(torch.float32).item())
-    return float(torch.tensor(t, dtype=torch.float32).item())
+def _t_shared(t, batch: int, what: str) -> float:
+    """the timestep of a call that takes ONE for its batch: engine.timesteps' rule, and distinct per-sample timesteps are refused by name"""
+    v = t.reshape(-1).tolist() if torch.is_tensor(t) else list(t) if isinstance(t, (list, tuple)) else [t]
+    if len(set(float(a) for a in v)) > 1:                  # whatever the batch: several timesteps are what this call cannot take
+        raise ValueError(f"{what} takes one timestep for its batch, got {len(v)} with distinct values: per-sample timesteps are honoured by get_h, the "
+                         "U-Net call, pullback_fixed, decoder_pullback_fixed, global_pca_zt and local_encoder_pullback_batch only")
+    return _timesteps(t, batch)                            # (equal entries: one timestep, if there is one or one per sample)
 
 
 class PullbackUNet:
@@ -85,7 +89,7 @@ class PullbackUNet:
         sample = x if sample is None else sample
         timestep = t if timestep is None else timestep
         key = self._tap(op, block_idx)
-        h = self.engine.forward(sample, _t_float(timestep), encoder_hidden_states, key)
+        h = self.engine.forward(sample, timestep, encoder_hidden_states, key)       # a timestep per sample is honoured (engine.timesteps)
         if verbose:
             print(f"op : {op}, block_idx : {block_idx}, return h.shape : {h.shape}")
         return h.to(sample.dtype)
@@ -102,7 +106,7 @@ class PullbackUNet:
             if "uk" in shift:
                 raise TypeError("the DDPM forward takes the shift as u= (uk= is forward_dh's name for it)")
             return self._forward_shifted(sample, timestep, None, shift.get("u"), shift.get("op"), shift.get("block_idx"))
-        eps = self.engine.forward(sample, _t_float(timestep), encoder_hidden_states, "eps").to(sample.dtype)
+        eps = self.engine.forward(sample, timestep, encoder_hidden_states, "eps").to(sample.dtype)
         return UNetOutput(eps) if self.kind == "sd" else eps
 
     # ------------------------------------------------------------------ h-space shift: the forward pass with h + u at the tap
@@ -118,7 +122,8 @@ class PullbackUNet:
         if rows not in (1, b):
             raise ValueError(f"u holds {rows} shifts of the tap for a batch of {b}: 1 (broadcast) or one per sample")
         dirs = [0] * b if rows == 1 else list(range(b))
-        e = self.engine.forward_shift(sample, _t_float(timestep), ctx, key, u.reshape(rows, d), dirs, [1.0] * b, "eps")
+        e = self.engine.forward_shift(sample, _t_shared(timestep, b, "the h-space shifted forward (forward_dh, unet(x, t, u=...))"), ctx, key,
+                                      u.reshape(rows, d), dirs, [1.0] * b, "eps")
         return e.to(sample.dtype)
 
     def forward_dh(self, sample=None, timestep=None, encoder_hidden_states=None, cross_attention_kwargs=None, op=None, block_idx=None, uk=None,
@@ -130,7 +135,7 @@ class PullbackUNet:
         if self.kind != "sd":
             raise TypeError("forward_dh is the SD form; the DDPM net takes unet(x, t, u=, op=, block_idx=)")
         if op is None and block_idx is None and uk is None:
-            return self.engine.forward(sample, _t_float(timestep), encoder_hidden_states, "eps").to(sample.dtype)
+            return self.engine.forward(sample, _t_shared(timestep, sample.shape[0], "forward_dh"), encoder_hidden_states, "eps").to(sample.dtype)
         e = self._forward_shifted(sample, timestep, encoder_hidden_states, uk, op, block_idx)
         if verbose:
             print(f"op : {op}, block_idx : {block_idx}, return eps.shape : {tuple(e.shape)}")
@@ -155,7 +160,7 @@ class PullbackUNet:
         U = u.detach().to(device=self.device, dtype=torch.float32)
         U = (U / U.norm(dim=0, keepdim=True)).T.contiguous()                     # [k, D] rows, unit norm (as the edit drivers: edit.py:267)
         rows = [(i, a) for i in pcs for a in scales]
-        tt = _t_float(t)
+        tt = _t_shared(t, 1, "h_traversal")
         out = [eng.forward_shift(x, tt, ctx, key, U, [r[0] for r in rows[i0:i0 + eng.max_batch]], [r[1] for r in rows[i0:i0 + eng.max_batch]], "eps")
                for i0 in range(0, len(rows), eng.max_batch)]
         c, hh, ww = eng.tape.tap_shape[eng.tape.taps["eps"]]
@@ -189,7 +194,7 @@ class PullbackUNet:
             tdist.broadcast(Vc, src=tdist.get_global_rank(self.k_shard_group, 0) if self.k_shard_group is not None else 0, group=self.k_shard_group)
             V = Vc.to(self.device)
         time_s = time.time()
-        eng.primal(x, _t_float(t), ctx, key)
+        eng.primal(x, _timesteps(t, 1), ctx, key)
         U = s = None
         self.last_history = []                                 # per-iteration ||V_prev - V||_2 (what the reference prints, utils.py:804)
         lo, hi = pdist.k_shard(k, tdist.get_rank(self.k_shard_group), tdist.get_world_size(self.k_shard_group)) if shard else (0, k)
@@ -233,6 +238,65 @@ class PullbackUNet:
         chunks = pca_rank // chunk_size if pca_rank % chunk_size == 0 else pca_rank // chunk_size + 1   # utils.py:178
         return self._pullback(x, t, None, op, block_idx, pca_rank, chunks, min_iter, max_iter, convergence_threshold, V0)
 
+    def local_encoder_pullback_batch(self, samples, timesteps, encoder_hidden_states=None, op=None, block_idx=None, pca_rank=50, min_iter=10,
+                                     max_iter=100, convergence_threshold=1e-3, V0=None):
+        """local_encoder_pullback_zt / _xt of B samples advanced together, each at a timestep of its own: sample b gets what the single-sample
+        method returns for (samples[b], timesteps[b], encoder_hidden_states[b]) -- the local tangent spaces of the reference's
+        run_sample_encoder_local_tangent_space_zt (src/modules/edit.py:310-383, :1517-1599), whose (sample, t) pairs it visits one call at a time.
+        samples [B, ...]; timesteps: one, or B; encoder_hidden_states [1 or B, L, D] (SD); convergence_threshold: a float or B floats; V0: None
+        (drawn per sample on the CPU generator, in sample order), [k, N_in] shared or [B, k, N_in].  Returns u [B, N_h, k] (a transposed view,
+        columns J V_prev), s [B, k], vT [B, k, N_in] and iters [B] (int64, iterations run for the sample, as last_iters counts them).
+        One primal at the B timesteps, then per iteration ONE fused pass of all B * k directions (dpb_pullback_iterate) and one read-back of
+        conv [B, 2].  A sample that meets the sign-aligned stop rule (module docstring) at iteration i keeps a snapshot of its (u, s, vT) of
+        that iteration; the iterations that go on for the others do not touch it.  Needs B <= max_batch and B * pca_rank <= max_rank."""
+        eng = self.engine
+        B, k = int(samples.shape[0]), int(pca_rank)
+        if not (1 <= B <= eng.max_batch):
+            raise ValueError(f"a batch of {B} samples outside [1, max_batch = {eng.max_batch}] of this engine")
+        if not (1 <= k <= RANK_LIMIT) or B * k > self.max_rank:
+            raise ValueError(f"{B} samples x pca_rank={k} = {B * k} tangents: the engine was built for max_rank={self.max_rank} (max_tangents), and "
+                             f"pca_rank must lie in [1, {RANK_LIMIT}]")
+        if max_iter < 1:
+            raise ValueError(f"max_iter={max_iter} < 1")
+        key = self._tap(op, block_idx)
+        n_in = eng.n_in
+        thr = convergence_threshold
+        thr = [float(a) for a in (thr.reshape(-1).tolist() if torch.is_tensor(thr) else thr if isinstance(thr, (list, tuple)) else [thr])]
+        if len(thr) not in (1, B):
+            raise ValueError(f"convergence_threshold has {len(thr)} entries for a batch of {B}: one or one per sample")
+        thr = thr * B if len(thr) == 1 else thr
+        if V0 is None:
+            V0 = torch.stack([torch.linalg.qr(torch.randn(n_in, k, dtype=torch.float))[0].T for _ in range(B)])   # utils.py:750-753, per sample
+        if V0.numel() not in (k * n_in, B * k * n_in):
+            raise ValueError(f"V0 has {V0.numel()} elements: [k, N_in] = [{k}, {n_in}] (shared) or [B, k, N_in] with B = {B}")
+        V = V0.reshape(-1, n_in).to(device=self.device, dtype=torch.float32)
+        V = (V.repeat(B, 1) if V.shape[0] == k and B > 1 else V).contiguous().clone()
+        time_s = time.time()
+        eng.primal(samples, timesteps, encoder_hidden_states, key)
+        n_h = eng.tap_numel(key)
+        u_out = torch.empty(B, k, n_h, dtype=torch.float32, device=self.device)
+        s_out = torch.empty(B, k, dtype=torch.float32, device=self.device)
+        v_out = torch.empty(B, k, n_in, dtype=torch.float32, device=self.device)
+        iters = torch.zeros(B, dtype=torch.int64)
+        self.last_history = []                                 # per iteration: the B values of ||V_prev - V||_2
+        for i in range(max_iter):
+            V, U, s, conv = eng.iterate(key, V, 1)
+            conv = conv.tolist()                               # the only host sync per iteration
+            self.last_history.append([c[0] for c in conv])
+            if self.verbose:
+                print(f"power method : {i}-th step convergence : ", [c[0] for c in conv])
+            for b in range(B):
+                if iters[b] == 0 and ((conv[b][1] <= thr[b] and i > min_iter) or i == max_iter - 1):
+                    iters[b] = i + 1
+                    u_out[b], s_out[b], v_out[b] = U.view(B, k, n_h)[b], s.view(B, k)[b], V.view(B, k, n_in)[b]
+            if bool((iters > 0).all()):
+                break
+        self.last_iters = int(iters.max())
+        if self.verbose:
+            print("power method runtime ==", time.time() - time_s)
+        dt = samples.dtype if samples.dtype in (torch.float32, torch.float64) else torch.float32
+        return u_out.transpose(1, 2).to(dt), s_out.to(dt), v_out.to(dt), iters
+
     # ------------------------------------------------------------------ decoder side: h -> eps
     def _decoder_tap(self, op, block_idx):
         key = self._tap(op, block_idx)
@@ -249,7 +313,7 @@ class PullbackUNet:
         if sample.shape[0] != 1:
             raise ValueError("get_h_to_e expects a single sample (batch 1): its skips are repeated input_h.size(0) times, as the reference does")
         x = sample.expand(b, *sample.shape[1:])
-        e = self.engine.forward_from(x, _t_float(timestep), ctx, key, input_h, "eps")
+        e = self.engine.forward_from(x, _t_shared(timestep, b, "get_h_to_e"), ctx, key, input_h, "eps")
         if verbose:
             print(f"op : {op}, block_idx : {block_idx}, input_h.shape : {tuple(input_h.shape)}, return eps.shape : {tuple(e.shape)}")
         return e.to(sample.dtype)
@@ -284,7 +348,7 @@ class PullbackUNet:
             V0 = q.T
         V = V0.reshape(k, n_h).to(device=self.device, dtype=torch.float32).contiguous()
         time_s = time.time()
-        eng.primal(x, _t_float(t), ctx, "eps")
+        eng.primal(x, _timesteps(t, 1), ctx, "eps")
         U = s = None
         self.last_history = []
         for i in range(max_iter):
@@ -340,7 +404,7 @@ class PullbackUNet:
         V0 [b*k, N_h] or [k, N_h] (shared by the b samples); returns (u [N_h, b*k], s, vT [b*k, N_eps], conv [b, 2])."""
         key = self._decoder_tap(op, block_idx)
         eng = self.engine
-        eng.primal(x, _t_float(t), ctx, "eps")
+        eng.primal(x, t, ctx, "eps")                     # (a timestep per sample is honoured)
         b = x.shape[0]
         V = V0.reshape(-1, eng.tap_numel(key)).to(device=self.device, dtype=torch.float32)
         if V.shape[0] == pca_rank and b > 1:
@@ -351,7 +415,7 @@ class PullbackUNet:
     def pullback_fixed(self, x, t, ctx, op, block_idx, pca_rank, n_iters, V0):
         """Fixed-iteration variant with no host synchronisation (what bench.py times)."""
         key = self._tap(op, block_idx)
-        self.engine.primal(x, _t_float(t), ctx, key)
+        self.engine.primal(x, t, ctx, key)              # (a timestep per sample is honoured)
         b = x.shape[0]                                  # b samples advance together; V0 is [b*k, N] or [k, N] (shared)
         V = V0.reshape(-1, self.engine.n_in).to(device=self.device, dtype=torch.float32)
         if V.shape[0] == pca_rank and b > 1:
@@ -369,7 +433,7 @@ class PullbackUNet:
             raise ValueError("pullback_k_sharded works on a single sample")
         key = self._tap(op, block_idx)
         eng = self.engine
-        eng.primal(x, _t_float(t), ctx, key)
+        eng.primal(x, _timesteps(t, 1), ctx, key)
         V = V0.reshape(pca_rank, eng.n_in).to(device=self.device, dtype=torch.float32).contiguous()
 
         def jtj(Vl):
@@ -396,12 +460,12 @@ class PullbackUNet:
         if memory_bound < 1:
             raise ValueError(f"memory_bound={memory_bound} < 1")
         time_s = time.time()
-        tt = _t_float(timestep)
+        tt = _timesteps(timestep, n)                      # one float, or a timestep per sample: sliced with the chunks
         H = torch.empty(n, d, dtype=torch.float32, device=self.device)
         step = min(int(memory_bound), eng.max_batch)     # the reference's chunks hold <= memory_bound samples; the engine's batch bounds them too
         for i0 in range(0, n, step):
             b = min(step, n - i0)
-            eng.forward(sample[i0:i0 + b], tt, encoder_hidden_states, key, out=H[i0:i0 + b])
+            eng.forward(sample[i0:i0 + b], tt if isinstance(tt, float) else tt[i0:i0 + b], encoder_hidden_states, key, out=H[i0:i0 + b])
         if self.verbose:
             torch.cuda.synchronize(self.device)
             c, hh, ww = eng.tape.tap_shape[eng.tape.taps[key]]
@@ -436,7 +500,7 @@ class PullbackUNet:
             raise ValueError(f"u must be [{d}] or [{d}, k] (features of the tap ({op}, {block_idx}))")
         U = u.reshape(1, d) if u.dim() == 1 else u.reshape(d, -1).T
         U = U.to(device=self.device, dtype=torch.float32).contiguous()
-        eng.primal(sample, _t_float(timestep), encoder_hidden_states, key)
+        eng.primal(sample, _t_shared(timestep, 1, "inv_jac"), encoder_hidden_states, key)
         W = torch.cat([eng.vjp(key, ui) for ui in U.split(self.max_rank)], dim=0)
         vT = -W / W.norm(dim=1, keepdim=True)
         return vT.to(sample.dtype)
@@ -485,7 +549,7 @@ class PullbackUNet:
         elif seed is None:
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())      # the global CPU generator: torch.manual_seed governs
         time_s = time.time()
-        H = eng.local_pca_sample(sample, _t_float(timestep), encoder_hidden_states, key, n, noise=noise, seed=0 if seed is None else int(seed))
+        H = eng.local_pca_sample(sample, _t_shared(timestep, 1, "local_pca"), encoder_hidden_states, key, n, noise=noise, seed=0 if seed is None else int(seed))
         if self.verbose:
             torch.cuda.synchronize(self.device)
             print("h sampling t ==", time.time() - time_s)
@@ -539,6 +603,7 @@ def bind(unet, kind: str, cfg, dtype=torch.float32, device="cuda:0", **kw) -> Pu
     unet._dpb = impl
     unet.get_h = types.MethodType(lambda self, *a, **k: self._dpb.get_h(*a, **k), unet)
     unet.get_h_to_e = types.MethodType(lambda self, *a, **k: self._dpb.get_h_to_e(*a, **k), unet)
+    unet.local_encoder_pullback_batch = types.MethodType(lambda self, *a, **k: self._dpb.local_encoder_pullback_batch(*a, **k), unet)
     if kind == "sd":
         unet.local_encoder_pullback_zt = types.MethodType(lambda self, *a, **k: self._dpb.local_encoder_pullback_zt(*a, **k), unet)
         unet.local_decoder_pullback_zt = types.MethodType(lambda self, *a, **k: self._dpb.local_decoder_pullback_zt(*a, **k), unet)

@@ -44,7 +44,8 @@ enum {
 };
 enum { DPB_GATHER_NONE = 0, DPB_GATHER_CONV = 1, DPB_GATHER_UPCONV = 3 };
 enum { DPB_BUF_ACT = 0,     /* per-sample activation [rows][channels]                                   */
-       DPB_BUF_SHARED = 1   /* one copy shared by the batch, independent of x (time-embedding path)     */ };
+       DPB_BUF_SHARED = 1   /* independent of x (time-embedding path): one copy shared by the batch, or one
+                               row per sample when the samples' timesteps differ (dpb_primal_t)          */ };
 
 typedef struct dpb_buffer_desc {
   int32_t rows;       /* H*W or token count, per sample */
@@ -58,7 +59,7 @@ typedef struct dpb_op_desc {
   int32_t in0, in1, in2;     /* input buffer ids, -1 = none */
   int32_t out;               /* output buffer id */
   int32_t res;               /* CONV: buffer added to the output (residual / shortcut), -1 = none */
-  int32_t rowbias;           /* CONV: DPB_BUF_SHARED buffer [1][Cout] added to every row (temb projection), -1 */
+  int32_t rowbias;           /* CONV: DPB_BUF_SHARED buffer [1][>= Cout] added to every row (temb projection; dpb_primal_t: sample b's row to sample b's rows), -1 */
   int32_t ip[12];            /* CONV: H W Cin Ho Wo Cout KS stride pad gather rowbias_col (first column of this op's Cout-wide window in the rowbias buffer) ; GROUPNORM: G silu ;
                                 ATTENTION: heads oq ok ov causal ; GEGLU: F interleave(0|64)                                               */
   float fp[4];               /* GROUPNORM/LAYERNORM: eps */
@@ -107,6 +108,21 @@ int dpb_primal(dpb_engine* e, const float* x, int batch, float t, const float* c
  * stash (no K^T / Q^T / P^T copies, GEGLU inputs left untouched), result copied to `out` as fp32 NCHW [batch][channels][rows(upto_buf)].
  * Invalidates the engine's primal state: dpb_jvp / dpb_vjp / dpb_pullback_iterate fail until the next dpb_primal. */
 int dpb_forward(dpb_engine* e, const float* x, int batch, float t, const float* ctx, int upto_buf, int channels, float* out);
+/* Per-sample timesteps (additive to ABI version 1): dpb_primal / dpb_forward with t a HOST array of `batch` entries.  Row b of every activation is
+ * the net at (x_b, t[b], ctx_b) -- the ordinary batched U-Net call unet(sample, timestep = tensor([t0, t1, ...]), ...), and the batch of the
+ * reference's local-tangent-space job whose rows differ only in t (fix_xt; src/modules/edit.py:1517-1599).  When all entries are equal the call IS
+ * the scalar entry point: same launches, same bits.  Otherwise the x-independent chain (sinusoid, the time-embedding linears, SiLU, the fused
+ * time_emb_proj product) runs once per sample, with the launches of a scalar call, into that sample's row of the DPB_BUF_SHARED buffers (each has
+ * max_batch rows in the workspace), and every ResBlock product reads its row bias at row sample(m): sample b's bias row has the bits of a scalar
+ * call at t[b], and an activation row the bits of the same batch run at the scalar t[b].  A few small launches per sample, in the primal only:
+ * dpb_jvp / dpb_vjp / dpb_pullback_iterate, the *_between passes and dpb_read_buffer read the stash and work unchanged (dpb_read_buffer of a SHARED
+ * buffer returns sample 0's row).  No device allocation; one host synchronisation, as dpb_primal.  dpb_forward_from, dpb_forward_shift and
+ * dpb_local_pca_sample take one t for their batch.
+ * Refused (dpb_last_error): null t, batch outside [1, max_batch], a non-finite t[b]; distinct timesteps on a network without a timestep
+ * embedding (temb_buf = -1, or a temb_buf that no op reads: the VAE and text-encoder tapes only fill the slot) or on a tape where something other than a SHARED op (a Linear or an activation writing a
+ * SHARED buffer) or a row bias reads a SHARED buffer (found at dpb_engine_create, the message names the op). */
+int dpb_primal_t(dpb_engine* e, const float* x, int batch, const float* t /*host [batch]*/, const float* ctx, int upto_buf);
+int dpb_forward_t(dpb_engine* e, const float* x, int batch, const float* t /*host [batch]*/, const float* ctx, int upto_buf, int channels, float* out);
 /* Copy a primal activation out as fp32 NCHW [batch][channels][rows] (first `channels` channels). */
 int dpb_read_buffer(dpb_engine* e, int buf, int channels, float* out);
 
