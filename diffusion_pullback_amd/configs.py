@@ -452,3 +452,165 @@ def clip_init_params(cfg: CLIPTextConfig, seed: int = 0, gain: float = 1.0, dtyp
             t = gain * torch.randn(shp, generator=g) / math.sqrt(math.prod(shp[1:]))
         p[name] = t.to(dtype)
     return p
+
+
+# =================================================================== guided-diffusion (ADM) U-Net, pixel space, unconditional
+@dataclass(frozen=True)
+class ADMConfig:
+    """OpenAI guided-diffusion ``UNetModel`` as ``create_model`` builds it (reference src/models/guided_diffusion/script_util.py:379-435,
+    unet.py:398-618).  ``attention_resolutions`` are feature-map sides, as create_model takes them (its "32,16,8"); the module itself is
+    given the downsampling rates image_size // side (``attention_ds``).  Every GroupNorm has 32 groups and eps 1e-5 (nn.py GroupNorm32)."""
+    image_size: int = 256
+    model_channels: int = 128
+    num_res_blocks: int = 1
+    channel_mult: Tuple[int, ...] = (1, 1, 2, 2, 4, 4)
+    attention_resolutions: Tuple[int, ...] = (16,)
+    num_heads: int = 1
+    num_head_channels: int = -1
+    use_scale_shift_norm: bool = False
+    resblock_updown: bool = False
+    use_new_attention_order: bool = False
+    learn_sigma: bool = False
+    in_channels: int = 3
+    class_cond: bool = False
+    groups: int = 32
+    gn_eps: float = 1e-5
+
+    @property
+    def temb_ch(self) -> int:
+        return self.model_channels * 4
+
+    @property
+    def out_channels(self) -> int:
+        return 2 * self.in_channels if self.learn_sigma else self.in_channels
+
+    @property
+    def attention_ds(self) -> Tuple[int, ...]:
+        return tuple(self.image_size // r for r in self.attention_resolutions)
+
+    def heads_for(self, c: int) -> int:
+        if self.num_head_channels == -1:
+            return self.num_heads
+        if c % self.num_head_channels:
+            raise ValueError(f"q,k,v channels {c} is not divisible by num_head_channels {self.num_head_channels}")
+        return c // self.num_head_channels
+
+
+# script_util.py:166-190 (P2_DICT: FFHQ_P2 / AFHQ_P2 / Flower_P2) and :140-164 (LSUN_DICT: LSUN_bedroom / _cat / _horse); channel_mult is
+# create_model's default for 256 x 256 images (script_util.py:400-401)
+ADM_P2_256 = ADMConfig(image_size=256, model_channels=128, num_res_blocks=1, attention_resolutions=(16,), num_head_channels=64,
+                       use_scale_shift_norm=True, resblock_updown=True, learn_sigma=True)
+ADM_LSUN_256 = ADMConfig(image_size=256, model_channels=256, num_res_blocks=2, attention_resolutions=(32, 16, 8), num_head_channels=64,
+                         use_scale_shift_norm=True, resblock_updown=True, learn_sigma=True)
+ADM_MODEL_NAMES = {"FFHQ_P2": ADM_P2_256, "AFHQ_P2": ADM_P2_256, "Flower_P2": ADM_P2_256,
+                   "LSUN_bedroom": ADM_LSUN_256, "LSUN_cat": ADM_LSUN_256, "LSUN_horse": ADM_LSUN_256}
+
+
+def adm_blocks(cfg: ADMConfig):
+    """The module tree of UNetModel.__init__ (unet.py:482-618) as a flat list, in state_dict order: (name, kind, cin, cout, ds) with kind one of
+    'conv_in' | 'res' | 'res_down' | 'res_up' | 'attn' | 'down' | 'up' and ds the downsampling rate of the block's INPUT.  The one walk of
+    the architecture: the parameter shapes here and the tape builder read it."""
+    if cfg.class_cond:
+        raise ValueError("class-conditional guided-diffusion models (label_emb) are not supported")
+    mc = cfg.model_channels
+    out = []
+    ch = int(cfg.channel_mult[0] * mc)
+    out.append(("input_blocks.0.0", "conv_in", cfg.in_channels, ch, 1))
+    chans = [ch]
+    ds, i = 1, 1
+    for level, mult in enumerate(cfg.channel_mult):
+        for _ in range(cfg.num_res_blocks):
+            out.append((f"input_blocks.{i}.0", "res", ch, int(mult * mc), ds))
+            ch = int(mult * mc)
+            if ds in cfg.attention_ds:
+                out.append((f"input_blocks.{i}.1", "attn", ch, ch, ds))
+            chans.append(ch)
+            i += 1
+        if level != len(cfg.channel_mult) - 1:
+            out.append((f"input_blocks.{i}.0", "res_down" if cfg.resblock_updown else "down", ch, ch, ds))
+            chans.append(ch)
+            ds *= 2
+            i += 1
+    out.append(("middle_block.0", "res", ch, ch, ds))
+    out.append(("middle_block.1", "attn", ch, ch, ds))
+    out.append(("middle_block.2", "res", ch, ch, ds))
+    i = 0
+    for level, mult in list(enumerate(cfg.channel_mult))[::-1]:
+        for j in range(cfg.num_res_blocks + 1):
+            ich = chans.pop()
+            out.append((f"output_blocks.{i}.0", "res", ch + ich, int(mc * mult), ds))
+            ch = int(mc * mult)
+            n = 1
+            if ds in cfg.attention_ds:
+                out.append((f"output_blocks.{i}.{n}", "attn", ch, ch, ds))
+                n += 1
+            if level and j == cfg.num_res_blocks:
+                out.append((f"output_blocks.{i}.{n}", "res_up" if cfg.resblock_updown else "up", ch, ch, ds))
+                ds //= 2
+            i += 1
+    return out
+
+
+def adm_param_shapes(cfg: ADMConfig) -> Dict[str, Tuple[int, ...]]:
+    """Names/shapes of every parameter, in the order of the reference module's state_dict (written from its module tree, unet.py:162-224,
+    :269-296, :451-618; the 1x1 projections of the attention block are Conv1d: [out, in, 1])."""
+    s: Dict[str, Tuple[int, ...]] = {}
+
+    def put(n, *shape):
+        s[n + ".weight"] = tuple(shape); s[n + ".bias"] = (shape[0],)
+
+    put("time_embed.0", cfg.temb_ch, cfg.model_channels); put("time_embed.2", cfg.temb_ch, cfg.temb_ch)
+    ch = None
+    for name, kind, cin, cout, _ in adm_blocks(cfg):
+        if kind == "conv_in":
+            put(name, cout, cin, 3, 3)
+        elif kind.startswith("res"):
+            put(name + ".in_layers.0", cin); put(name + ".in_layers.2", cout, cin, 3, 3)
+            put(name + ".emb_layers.1", 2 * cout if cfg.use_scale_shift_norm else cout, cfg.temb_ch)
+            put(name + ".out_layers.0", cout); put(name + ".out_layers.3", cout, cout, 3, 3)
+            if cin != cout:
+                put(name + ".skip_connection", cout, cin, 1, 1)
+        elif kind == "attn":
+            put(name + ".norm", cin); put(name + ".qkv", 3 * cin, cin, 1); put(name + ".proj_out", cin, cin, 1)
+        elif kind == "down":
+            put(name + ".op", cout, cin, 3, 3)
+        else:
+            put(name + ".conv", cout, cin, 3, 3)
+        ch = cout
+    ch0 = int(cfg.channel_mult[0] * cfg.model_channels)
+    put("out.0", ch); put("out.2", cfg.out_channels, ch0, 3, 3)
+    return s
+
+
+def adm_qkv_rows(c: int, heads: int, new_order: bool) -> torch.Tensor:
+    """Row r of the engine's fused projection -- windows q | k | v, each [heads][d] -- is row adm_qkv_rows(...)[r] of the reference's ``qkv``
+    weight: QKVAttentionLegacy stores [heads][3][d] (unet.py:349), QKVAttention [3][heads][d] (unet.py:382-390)."""
+    d = c // heads
+    part, h, j = torch.meshgrid(torch.arange(3), torch.arange(heads), torch.arange(d), indexing="ij")
+    src = part * c + h * d + j if new_order else h * 3 * d + part * d + j
+    return src.reshape(-1)
+
+
+def adm_init_params(cfg: ADMConfig, seed: int = 0, gain: float = 1.0, spectrum: "Spectrum | None" = None, dtype=torch.float32) -> Params:
+    """Seeded synthetic weights at the exact architecture shapes (CPU generator), rule of ddpm_init_params.  The layers the reference
+    zero-initialises (zero_module: every ResBlock's last convolution, every proj_out, the output convolution) get seeded non-zero values like
+    the rest: with zeros every block is its skip path.  ``spectrum`` shapes the middle block's attention (Spectrum)."""
+    g = torch.Generator().manual_seed(seed)
+    p: Params = {}
+    for name, shp in adm_param_shapes(cfg).items():
+        if name.endswith(".weight") and len(shp) == 1:          # norm gamma
+            p[name] = (1.0 + 0.1 * torch.randn(shp, generator=g)).to(dtype)
+        elif name.endswith(".bias"):
+            p[name] = (0.05 * torch.randn(shp, generator=g)).to(dtype)
+        else:
+            p[name] = (gain * torch.randn(shp, generator=g) / math.sqrt(math.prod(shp[1:]))).to(dtype)
+    if spectrum is not None:
+        c = p["middle_block.1.proj_out.weight"].shape[0]
+        q = adm_qkv_rows(c, cfg.heads_for(c), cfg.use_new_attention_order)[:c]      # the query rows of the fused projection
+        tmp = {"o": p["middle_block.1.proj_out.weight"], "q": p["middle_block.1.qkv.weight"][q]}
+        _shape_spectrum(tmp, "o", "q", spectrum, seed)
+        p["middle_block.1.proj_out.weight"] = tmp["o"]
+        w = p["middle_block.1.qkv.weight"].clone()
+        w[q] = tmp["q"]
+        p["middle_block.1.qkv.weight"] = w
+    return p

@@ -1,5 +1,5 @@
 // HBM-bound elementwise kernels: GEGLU (primal/tangent/adjoint), SiLU, accumulate, channel-window copies,
-// NCHW<->NHWC boundary transposes, 2x2 sum pooling (adjoint of nearest upsampling), DDIM step.
+// NCHW<->NHWC boundary transposes, 2x2 pooling / nearest upsampling (each the other's adjoint), DDIM step.
 // All use 16-byte chunks per lane and grid-stride loops.
 #include "kernels.h"
 
@@ -377,7 +377,7 @@ int launch_replicate_rows(void* const* bufs, const size_t* sample_bytes, int nbu
 }
 
 template <typename T>
-__global__ __launch_bounds__(256) void pool2x2_kernel(const T* in, T* out, int n, int H, int W, int C, int accumulate) {
+__global__ __launch_bounds__(256) void pool2x2_kernel(const T* in, T* out, int n, int H, int W, int C, int accumulate, float scale) {
   constexpr int CH = TT<T>::CH;
   const int cch = C / CH;
   const long total = (long)n * H * W * cch;
@@ -401,6 +401,8 @@ __global__ __launch_bounds__(256) void pool2x2_kernel(const T* in, T* out, int n
         for (int e = 0; e < CH; ++e) acc[e] += v[e];
       }
     T* op = out + ((s * H + y) * W + x) * C + c;
+#pragma unroll
+    for (int e = 0; e < CH; ++e) acc[e] *= scale;            // (1: the sum itself, bit for bit)
     if (accumulate) {
       float o[CH];
       Vec<T>::load(op, o);
@@ -410,10 +412,59 @@ __global__ __launch_bounds__(256) void pool2x2_kernel(const T* in, T* out, int n
     Vec<T>::store(op, acc);
   }
 }
+// out[s][Y][X][c] (+)= scale * in[s][Y / 2][X / 2][c] on the 2H x 2W grid: nearest x2 upsampling (scale 1) and the adjoint of the 2x2 average
+// pool (scale 0.25).  One thread per 16-byte chunk of the OUTPUT (coalesced stores; each input chunk is read by four threads, from L2).
+template <typename T>
+__global__ __launch_bounds__(256) void up2x2_kernel(const T* in, T* out, int n, int H, int W, int C, int accumulate, float scale) {
+  constexpr int CH = TT<T>::CH;
+  const int cch = C / CH;
+  const long total = (long)n * 4 * H * W * cch;
+  for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+    const int c = (int)(idx % cch) * CH;
+    long pix = idx / cch;
+    const int X = (int)(pix % (2 * W));
+    pix /= 2 * W;
+    const int Y = (int)(pix % (2 * H));
+    const long s = pix / (2 * H);
+    float v[CH];
+    Vec<T>::load(in + ((s * H + (Y >> 1)) * W + (X >> 1)) * C + c, v);
+#pragma unroll
+    for (int e = 0; e < CH; ++e) v[e] *= scale;
+    T* op = out + ((s * 2 * H + Y) * 2 * W + X) * C + c;
+    if (accumulate) {
+      float o[CH];
+      Vec<T>::load(op, o);
+#pragma unroll
+      for (int e = 0; e < CH; ++e) v[e] += o[e];
+    }
+    Vec<T>::store(op, v);
+  }
+}
+static int resample_check(const char* what, int dtype, const void* in, const void* out, int n, int H, int W, int C) {
+  if (!in || !out || n < 1 || H < 1 || W < 1 || C < 1 || C % dt_chunk(dtype)) {
+    set_error("%s: n=%d H=%d W=%d C=%d (C must be a positive multiple of the 16-byte chunk)", what, n, H, W, C);
+    return -1;
+  }
+  return 0;
+}
+int launch_pool2x2(int dtype, const void* in, void* out, int n, int H, int W, int C, float scale, int accumulate, hipStream_t st) {
+  if (resample_check("pool2x2", dtype, in, out, n, H, W, C)) return -1;
+  unsigned g = grid_for((long)n * H * W * (C / dt_chunk(dtype)));
+  DPB_DISPATCH_STMT(dtype, T, DPB_LAUNCH((pool2x2_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)in, (T*)out, n, H, W, C, accumulate, scale));
+  DPB_CHECK(hipGetLastError());
+  return 0;
+}
+int launch_up2x2(int dtype, const void* in, void* out, int n, int H, int W, int C, float scale, int accumulate, hipStream_t st) {
+  if (resample_check("up2x2", dtype, in, out, n, H, W, C)) return -1;
+  unsigned g = grid_for((long)n * 4 * H * W * (C / dt_chunk(dtype)));
+  DPB_DISPATCH_STMT(dtype, T, DPB_LAUNCH((up2x2_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)in, (T*)out, n, H, W, C, accumulate, scale));
+  DPB_CHECK(hipGetLastError());
+  return 0;
+}
 int launch_pool2x2_sum(int dtype, const void* in, void* out, int n, int H, int W, int C, int accumulate, hipStream_t st) {
   int CH = dt_chunk(dtype);
   unsigned g = grid_for((long)n * H * W * (C / CH));
-  DPB_DISPATCH_STMT(dtype, T, DPB_LAUNCH((pool2x2_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)in, (T*)out, n, H, W, C, accumulate));
+  DPB_DISPATCH_STMT(dtype, T, DPB_LAUNCH((pool2x2_kernel<T>), dim3(g), dim3(256), 0, st, (const T*)in, (T*)out, n, H, W, C, accumulate, 1.f));
   DPB_CHECK(hipGetLastError());
   return 0;
 }

@@ -58,6 +58,7 @@ struct Op {
   bool is_const = true;
   int attn = -1;             // index into plans
   size_t pstats = 0, tstats = 0;   // GroupNorm stat slots (offsets)
+  size_t aff = 0;            // modulated GroupNorm: its per-sample affine tables, gamma_b [maxB][C] then beta_b [maxB][C] (fp32; offset)
   int geglu_next = -1;       // CONV (FF-in): the GEGLU op that is the only consumer of its output (interleaved layout) -> fused tangent epilogue
   int geglu_prev = -1;       // CONV (FF-out): the GEGLU op that produces its input                                   -> fused adjoint epilogue
   int ln_next = -1;          // CONV: the LayerNorm op that reads its 320-wide output  -> tangent: product + LayerNorm tangent in one launch (EPI_LN_TAN)
@@ -75,6 +76,7 @@ struct dpb_engine {
   std::vector<Op> ops;
   std::vector<AttnPlan> plans;
   std::vector<int> producer;        // buffer -> op index producing it (-1 for inputs)
+  std::vector<std::vector<int>> mod_users;   // op -> the modulated GroupNorm ops whose (scale, shift) its output holds: their affine tables are filled right after it
   int x_buf = -1, x_channels = 0, temb_buf = -1, temb_dim = 0, temb_flip = 0, temb_hm1 = 0, ctx_buf = -1;
   // Per-sample timesteps (dpb_primal_t): every SHARED buffer has max_batch rows, and the SHARED ops run once per sample into that sample's row.
   // That is sound only if nothing but a SHARED op or a row bias reads a SHARED buffer; empty: it is, else what stands against it (found at create).
@@ -156,8 +158,9 @@ struct Pass {
       : mode(mode_), tap(tap_), src(src_), bact(flags), oact(flags + e->bufs.size()) {}
 };
 
-// The buffers an op reads: in0; in1 of ATTENTION and CONCAT; in2 of ATTENTION; res of CONV (when it has one).  An id its op kind does not
-// read means nothing (include/dpb.h) and is never looked at.
+// The buffers an op reads: in0; in1 of ATTENTION and CONCAT; in2 of ATTENTION; res of CONV (when it has one); in1 of a modulated GROUPNORM (the
+// SHARED embedding projection: read in the primal pass only, it carries no tangent).  An id its op kind does not read means nothing
+// (include/dpb.h) and is never looked at.
 struct OpInputs {
   int id[4], n;
   const int* begin() const { return id; }
@@ -168,8 +171,10 @@ OpInputs op_inputs(const dpb_op_desc& d) {
   if (d.kind == DPB_OP_ATTENTION || d.kind == DPB_OP_CONCAT) r.id[r.n++] = d.in1;
   if (d.kind == DPB_OP_ATTENTION) r.id[r.n++] = d.in2;
   if (d.kind == DPB_OP_CONV && d.res >= 0) r.id[r.n++] = d.res;
+  if (d.kind == DPB_OP_GROUPNORM && d.ip[2]) r.id[r.n++] = d.in1;
   return r;
 }
+bool gn_modulated(const dpb_op_desc& d) { return d.kind == DPB_OP_GROUPNORM && d.ip[2] != 0; }
 
 // the launches of one pass (dpb_engine_stats): what DPB_LAUNCH counted while the pass ran, on every way out of it
 struct LaunchSpan {
@@ -465,6 +470,11 @@ int gn_run(dpb_engine* e, const Op& op, const Pass& ps, int n) {
   a.x = e->P(d.in0);
   a.gamma = (const float*)d.w[0];
   a.beta = (const float*)d.w[1];
+  if (gn_modulated(d)) {                           // scale-shift norm: sample b's affine (fill_affine, primal pass), in all three modes
+    a.gamma = (const float*)(e->ws + op.aff);
+    a.beta = a.gamma + (size_t)e->maxB * bi.C;
+    a.astride = bi.C;
+  }
   a.pstats = (double*)(e->ws + op.pstats);
   a.tstats = (double*)(e->ws + op.tstats);
   a.part = (float*)(e->ws + e->gnpart); a.part_bytes = e->gnpart_bytes; a.ticket = (int*)(e->ws + e->gnticket);
@@ -495,6 +505,43 @@ int geglu_run(dpb_engine* e, const Op& op, const Pass& ps, int n) {
   a.stash = ps.fwd.stash;
   fill_io(e, d, ps, n, a);
   return launch_geglu(e->dtype, ps.mode, a, e->stream);
+}
+
+// The affine tables of the modulated GroupNorm ops that read the output of op `src` (the fused embedding projection, just computed): rows
+// 0 .. batch-1 -- the batch of the CALL, also when the projection itself ran in a shared prefix at batch 1 -- from row b of the projection when
+// the samples have timesteps of their own, row 0 otherwise (the rule of a row bias: conv_fwd's rowbias_div).
+int fill_affine(dpb_engine* e, int src, const Pass& ps, int batch) {
+  const std::vector<int>& users = e->mod_users[src];
+  if (users.empty()) return 0;
+  const Buf& be = e->bufs[e->ops[src].d.out];
+  std::vector<AdaGNOp> t(users.size());
+  for (size_t i = 0; i < users.size(); ++i) {
+    const Op& u = e->ops[users[i]];
+    const int C = e->bufs[u.d.in0].C;
+    t[i].gamma = (const float*)u.d.w[0]; t[i].beta = (const float*)u.d.w[1];
+    t[i].emb = e->P(u.d.in1) + (size_t)u.d.ip[3] * e->es;
+    t[i].og = (float*)(e->ws + u.aff); t[i].ob = t[i].og + (size_t)e->maxB * C;
+    t[i].C = C;
+  }
+  return launch_adagn_affine(e->dtype, t.data(), (int)t.size(), (long)be.rows * be.C, batch, ps.per_sample_t ? 1 : 0, e->stream);
+}
+
+// 2x2 resampling (DPB_OP_RESAMPLE): primal and tangent are the map itself; the adjoint of the average pool is 0.25 x nearest upsampling, the
+// adjoint of nearest upsampling the 2x2 sum, either added to what the cotangent of the input already holds (first write / accumulate)
+int resample_run(dpb_engine* e, const Op& op, const Pass& ps, int n) {
+  const dpb_op_desc& d = op.d;
+  const bool up = d.ip[0] == 1;
+  const int H = d.ip[1], W = d.ip[2], C = e->bufs[d.in0].C;
+  const int h = up ? H : H / 2, w = up ? W : W / 2;            // the small side
+  if (ps.mode == MODE_ADJOINT) {
+    const int acc = e->ginit[d.in0];
+    e->ginit[d.in0] = 1;
+    return up ? launch_pool2x2(e->dtype, e->G(d.out), e->G(d.in0), n, h, w, C, 1.f, acc, e->stream)
+              : launch_up2x2(e->dtype, e->G(d.out), e->G(d.in0), n, h, w, C, 0.25f, acc, e->stream);
+  }
+  const char* in = ps.mode == MODE_PRIMAL ? e->P(d.in0) : e->T(d.in0);
+  char* out = ps.mode == MODE_PRIMAL ? e->P(d.out) : e->T(d.out);
+  return up ? launch_up2x2(e->dtype, in, out, n, h, w, C, 1.f, 0, e->stream) : launch_pool2x2(e->dtype, in, out, n, h, w, C, 0.25f, 0, e->stream);
 }
 
 int concat_run(dpb_engine* e, const Op& op, const Pass& ps, int n) {
@@ -783,6 +830,7 @@ int run_op(dpb_engine* e, const Op& op, const Pass& ps, int n) {
     case DPB_OP_LAYERNORM: return ln_run(e, op, ps, n);
     case DPB_OP_GEGLU: return geglu_run(e, op, ps, n);
     case DPB_OP_CONCAT: return concat_run(e, op, ps, n);
+    case DPB_OP_RESAMPLE: return resample_run(e, op, ps, n);
     case DPB_OP_ATTENTION:
       return mode == MODE_PRIMAL ? attn_primal(e, op, ps, n) : mode == MODE_TANGENT ? attn_tangent(e, op, n) : attn_adjoint(e, op, n);
     case DPB_OP_SILU: {
@@ -939,12 +987,30 @@ int dpb_engine_create(const dpb_net_desc* net, dpb_engine** out) {
       if (!d.w[0]) return bad("missing weight", i);
       if (d.ip[2] != e->bufs[d.in0].C || e->bufs[d.out].C != round8(d.ip[5])) return bad("conv channel mismatch", i);
     }
+    if (d.kind == DPB_OP_GROUPNORM) {
+      const Buf& gi = e->bufs[d.in0];
+      if (gn_modulated(d)) {
+        if (e->bufs[d.in1].kind != DPB_BUF_SHARED || e->bufs[d.in1].rows != 1 || e->producer[d.in1] < 0)
+          return bad("modulated groupnorm: in1 must be a one-row SHARED buffer produced by an earlier op (the embedding projection)", i);
+        if (gi.kind != DPB_BUF_ACT) return bad("modulated groupnorm: the normalised buffer must be a per-sample activation", i);
+        if (d.ip[3] < 0 || d.ip[3] % 8 || d.ip[3] + 2 * gi.C > e->bufs[d.in1].C) return bad("modulated groupnorm: bad (scale | shift) column window", i);
+        if (!d.w[0] || !d.w[1]) return bad("modulated groupnorm: missing gamma / beta", i);
+      }
+    }
+    if (d.kind == DPB_OP_RESAMPLE) {
+      const Buf& ri = e->bufs[d.in0];
+      const Buf& ro = e->bufs[d.out];
+      const int H = d.ip[1], W = d.ip[2];
+      if (d.ip[0] != 0 && d.ip[0] != 1) return bad("resample: ip[0] must be 0 (2x2 average pool) or 1 (nearest x2 upsample)", i);
+      if (H < 1 || W < 1 || (long)H * W != ri.rows || ri.C != ro.C || ri.kind != DPB_BUF_ACT || ro.kind != DPB_BUF_ACT) return bad("resample: input shape mismatch", i);
+      if (d.ip[0] == 0 ? (H % 2 || W % 2 || (long)(H / 2) * (W / 2) != ro.rows) : (long)4 * H * W != ro.rows) return bad("resample: output shape mismatch", i);
+    }
     for (int b : op_inputs(d)) e->temb_read = e->temb_read || b == e->temb_buf;
     if (e->per_sample_t_why.empty()) {              // per-sample timesteps: SHARED buffers are read by SHARED ops and as row biases only
       char why[160] = "";
       const bool so = e->bufs[d.out].kind == DPB_BUF_SHARED;
       for (int b : op_inputs(d))
-        if ((e->bufs[b].kind == DPB_BUF_SHARED) != so)
+        if ((e->bufs[b].kind == DPB_BUF_SHARED) != so && !(gn_modulated(d) && b == d.in1))   // (a modulated GroupNorm reads its sample's row through the affine tables)
           snprintf(why, sizeof(why), "op %d reads %s buffer %d into %s buffer %d", i, so ? "per-sample" : "SHARED", b, so ? "SHARED" : "per-sample", d.out);
       if (so && !(d.kind == DPB_OP_SILU || (d.kind == DPB_OP_CONV && d.ip[9] == DPB_GATHER_NONE && d.rowbias < 0)))
         snprintf(why, sizeof(why), "op %d writes SHARED buffer %d and is neither a linear layer nor an activation", i, d.out);
@@ -956,6 +1022,9 @@ int dpb_engine_create(const dpb_net_desc* net, dpb_engine** out) {
     e->producer[d.out] = i;
     e->ops.push_back(op);
   }
+  e->mod_users.assign(e->ops.size(), std::vector<int>());
+  for (size_t i = 0; i < e->ops.size(); ++i)
+    if (gn_modulated(e->ops[i].d)) e->mod_users[e->producer[e->ops[i].d.in1]].push_back((int)i);
   // ---------------- GEGLU fusion pairs: FF-in conv -> GEGLU (interleaved layout, sole consumer) -> FF-out conv (sole consumer)
   {
     std::vector<int> uses(nb, 0), user(nb, -1);
@@ -1039,6 +1108,7 @@ int dpb_engine_create(const dpb_net_desc* net, dpb_engine** out) {
         op.tstats = e->tstats_bytes;
         e->tstats_bytes += (size_t)e->maxT * d.ip[0] * 2 * sizeof(double);
       }
+      if (gn_modulated(d)) op.aff = take((size_t)2 * e->maxB * e->bufs[d.in0].C * sizeof(float));
     } else if (d.kind == DPB_OP_CONV && d.ip[9] == DPB_GATHER_UPCONV && !op.is_const) {
       ctmp = std::max(ctmp, (size_t)e->maxT * d.ip[3] * d.ip[4] * e->bufs[d.in0].C * es);
     }
@@ -1184,6 +1254,7 @@ static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const 
     for (ps.srow = 0; ps.srow < reps; ++ps.srow)
       if (int r = run_op(e, e->ops[i], ps, i <= seed_op ? xb : batch)) return r;
     ps.srow = 0;
+    if (int r = fill_affine(e, i, ps, batch)) return r;
     if (i == seed_op && f.u) {                     // dpb_forward_shift: the tap just computed, shifted per row (of sample 0 for every row when xb == 1)
       if (int r = shift_seed(e, f, batch, xb, last)) return r;
     } else if (i == seed_op) {                     // dpb_forward_from: the caller's activation replaces the one just computed

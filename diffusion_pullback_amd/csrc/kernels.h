@@ -184,6 +184,7 @@ struct GNArgs {
   const void* d = nullptr;        // tangent dx or cotangent gz [NT][HW][C] (modes 1,2)
   void* y = nullptr;              // output (primal y / tangent dz / cotangent gx)
   const float* gamma = nullptr; const float* beta = nullptr;
+  int astride = 0;                // row stride of gamma / beta per PRIMAL sample: 0 = one shared affine [C]; C = the per-sample tables of a modulated op (AdaGNTable)
   double* pstats = nullptr;       // [Bp][G][2]  primal (sum, sumsq) -> finalised to (mean, rstd) in place
   double* tstats = nullptr;       // [NT][G][2]  tangent / adjoint sums
   float* part = nullptr;          // per-block partial sums [n][blocks][G][2] (scratch shared by every GroupNorm launch of the stream)
@@ -198,6 +199,14 @@ struct GNArgs {
   SlabSrc src;                    // tangent / adjoint, one-launch kernel only: d comes from split-K slabs
 };
 int launch_groupnorm(int dtype, int mode, const GNArgs& a, hipStream_t st);
+// Scale-shift GroupNorm as a per-sample affine: for every modulated op i of the table and sample b < batch
+//   og[i][b][c] = gamma[i][c] (1 + s),  ob[i][b][c] = beta[i][c] (1 + s) + h,   (s, h) = emb[i][row][c], emb[i][row][C + c],  row = per_sample ? b : 0
+// emb[i]: the op's column window of the fused embedding projection (engine dtype, row pitch ld elements).  fp32 arithmetic.  One launch per
+// ADAGN_MAX_OPS ops, the descriptor table in the kernel arguments.
+constexpr int ADAGN_MAX_OPS = 32;
+struct AdaGNTable { const float* gamma[ADAGN_MAX_OPS]; const float* beta[ADAGN_MAX_OPS]; const void* emb[ADAGN_MAX_OPS]; float* og[ADAGN_MAX_OPS]; float* ob[ADAGN_MAX_OPS]; int C[ADAGN_MAX_OPS]; };
+struct AdaGNOp { const float* gamma; const float* beta; const void* emb; float* og; float* ob; int C; };
+int launch_adagn_affine(int dtype, const AdaGNOp* ops, int nops, long ld, int batch, int per_sample, hipStream_t st);
 bool groupnorm_is_one_launch(int dtype, const GNArgs& a);   // launch_groupnorm runs the one-launch kernel (the one that can take split-K slabs: SlabSrc) for this C, G, HW
 
 struct LNArgs {
@@ -294,6 +303,12 @@ struct ReplTable { void* p[REPL_MAX_BUFS]; long chunks[REPL_MAX_BUFS]; };
 int launch_replicate_rows(void* const* bufs, const size_t* sample_bytes, int nbufs, int batch, hipStream_t st);
 // 2x2 sum pooling of a cotangent (adjoint of nearest x2 upsampling): in [n][2H*2W][C] -> out [n][H*W][C]
 int launch_pool2x2_sum(int dtype, const void* in, void* out, int n, int H, int W, int C, int accumulate, hipStream_t st);
+// The two stand-alone 2x2 resampling maps (DPB_OP_RESAMPLE), each the other's adjoint up to the factor; H, W: the SMALL side's size.
+//   pool: in [n][2H*2W][C] -> out [n][H*W][C]   (+)= scale * sum of the 2x2 window   (0.25: average pool; 1: adjoint of the upsample)
+//   up:   in [n][H*W][C]   -> out [n][2H*2W][C] (+)= scale * in[y/2][x/2]            (1: nearest upsample; 0.25: adjoint of the pool)
+// fp32 arithmetic, one rounding; C a multiple of the 16-byte chunk; 64-bit offsets; no atomics.
+int launch_pool2x2(int dtype, const void* in, void* out, int n, int H, int W, int C, float scale, int accumulate, hipStream_t st);
+int launch_up2x2(int dtype, const void* in, void* out, int n, int H, int W, int C, float scale, int accumulate, hipStream_t st);
 
 // ---------------------------------------------------------------- re-orthonormalisation (fp32 in/out, fp64 Gram)
 struct OrthArgs {

@@ -151,9 +151,11 @@ __global__ __launch_bounds__(256) void gn_kernel(GNArgs a, int ppb) {
       const int ch0 = col * CH;
       float mean[CH], rstd[CH], gam[CH], bet[CH], m1[CH], m2[CH];
       int grp[CH];
-      Vec<float>::load(a.gamma + ch0, gam);
-      Vec<float>::load(a.beta + ch0, bet);
-      if constexpr (CH == 8) { Vec<float>::load(a.gamma + ch0 + 4, gam + 4); Vec<float>::load(a.beta + ch0 + 4, bet + 4); }
+      const float* gp = a.gamma + (long)b * a.astride + ch0;        // astride 0: the shared affine; C: sample b's row of a modulated op's tables
+      const float* bp = a.beta + (long)b * a.astride + ch0;
+      Vec<float>::load(gp, gam);
+      Vec<float>::load(bp, bet);
+      if constexpr (CH == 8) { Vec<float>::load(gp + 4, gam + 4); Vec<float>::load(bp + 4, bet + 4); }
       if (cpg >= CH) {
         // a 16-byte chunk spans at most two groups: fetch their statistics once instead of once per channel
         // (the per-channel form cost 48 dependent scalar loads per thread, as much as the thread's whole pixel walk)
@@ -332,9 +334,11 @@ __global__ __launch_bounds__(512) void gn_fused_kernel(GNArgs a, int GC) {
   float gam[CH], bet[CH];
   float mean[2] = {0.f, 0.f}, rstd[2] = {0.f, 0.f};
   if (active) {
-    Vec<float>::load(a.gamma + ch0, gam);
-    Vec<float>::load(a.beta + ch0, bet);
-    if constexpr (CH == 8) { Vec<float>::load(a.gamma + ch0 + 4, gam + 4); Vec<float>::load(a.beta + ch0 + 4, bet + 4); }
+    const float* gp = a.gamma + (long)b * a.astride + ch0;          // (astride: see gn_kernel)
+    const float* bp = a.beta + (long)b * a.astride + ch0;
+    Vec<float>::load(gp, gam);
+    Vec<float>::load(bp, bet);
+    if constexpr (CH == 8) { Vec<float>::load(gp + 4, gam + 4); Vec<float>::load(bp + 4, bet + 4); }
     const int g1 = min(g0 + 1, a.G - 1);
     if (MODE != MODE_PRIMAL) {
       mean[0] = (float)a.pstats[((long)b * a.G + g0) * 2]; rstd[0] = (float)a.pstats[((long)b * a.G + g0) * 2 + 1];
@@ -594,6 +598,37 @@ static int gn_launch(const GNArgs& a, hipStream_t st) {
 
 bool groupnorm_is_one_launch(int dtype, const GNArgs& a) {   // the route test of gn_launch, for the engine (which hands split-K slabs to that kernel only)
   return gn_fused_groups(a.C, a.G, a.HW, dt_chunk(dtype), dtype == DT_F32 ? 4 : 2) != 0;
+}
+
+// ---------------------------------------------------------------- scale-shift GroupNorm: the per-sample affine tables
+// (gamma x^ + beta)(1 + s_b) + h_b = gamma_b x^ + beta_b.  blockIdx.y: the op of the table, blockIdx.z: the sample.
+template <typename T>
+__global__ __launch_bounds__(256) void adagn_affine_kernel(AdaGNTable t, long ld, int per_sample) {
+  const int i = blockIdx.y, b = blockIdx.z, C = t.C[i];
+  const T* e = (const T*)t.emb[i] + (per_sample ? (long)b * ld : 0);
+  for (int c = blockIdx.x * 256 + threadIdx.x; c < C; c += gridDim.x * 256) {
+    const float s = 1.f + TT<T>::ld(e + c), h = TT<T>::ld(e + C + c);
+    t.og[i][(long)b * C + c] = t.gamma[i][c] * s;
+    t.ob[i][(long)b * C + c] = t.beta[i][c] * s + h;
+  }
+}
+int launch_adagn_affine(int dtype, const AdaGNOp* ops, int nops, long ld, int batch, int per_sample, hipStream_t st) {
+  if (batch < 1) { set_error("adagn_affine: batch=%d", batch); return -1; }
+  for (int i0 = 0; i0 < nops; i0 += ADAGN_MAX_OPS) {
+    AdaGNTable t;
+    const int n = std::min(ADAGN_MAX_OPS, nops - i0);
+    int cmax = 1;
+    for (int i = 0; i < n; ++i) {
+      const AdaGNOp& o = ops[i0 + i];
+      if (!o.gamma || !o.beta || !o.emb || !o.og || !o.ob || o.C < 1) { set_error("adagn_affine: op %d of the table is incomplete", i0 + i); return -1; }
+      t.gamma[i] = o.gamma; t.beta[i] = o.beta; t.emb[i] = o.emb; t.og[i] = o.og; t.ob[i] = o.ob; t.C[i] = o.C;
+      cmax = std::max(cmax, o.C);
+    }
+    for (int i = n; i < ADAGN_MAX_OPS; ++i) { t.gamma[i] = t.beta[i] = nullptr; t.emb[i] = nullptr; t.og[i] = t.ob[i] = nullptr; t.C[i] = 0; }
+    DPB_DISPATCH_STMT(dtype, T, DPB_LAUNCH((adagn_affine_kernel<T>), dim3((cmax + 255) / 256, n, batch), dim3(256), 0, st, t, ld, per_sample));
+    DPB_CHECK(hipGetLastError());
+  }
+  return 0;
 }
 
 int launch_groupnorm(int dtype, int mode, const GNArgs& a, hipStream_t st) {

@@ -27,7 +27,7 @@ def dtype_code(dtype) -> int:
         return {torch.float32: DPB_F32, torch.bfloat16: DPB_BF16, torch.float16: DPB_F16}[dtype]
     except KeyError:
         raise DpbError(f"engine dtype must be float32, bfloat16 or float16, got {dtype}") from None
-OP_CONV, OP_GROUPNORM, OP_LAYERNORM, OP_ATTENTION, OP_GEGLU, OP_SILU, OP_CONCAT = 1, 2, 3, 4, 5, 6, 7
+OP_CONV, OP_GROUPNORM, OP_LAYERNORM, OP_ATTENTION, OP_GEGLU, OP_SILU, OP_CONCAT, OP_RESAMPLE = 1, 2, 3, 4, 5, 6, 7, 8
 GATHER_NONE, GATHER_CONV, GATHER_UPCONV = 0, 1, 3
 BUF_ACT, BUF_SHARED = 0, 1
 

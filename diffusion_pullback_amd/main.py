@@ -108,8 +108,10 @@ def preset(args):
     if args.is_stable_diffusion:
         args.exp = f"Stable_Diffusion-{args.dataset_name}-{args.note}"
     else:
-        if args.model_name not in ("CelebA_HQ_HF", "LSUN_church_HF", "FFHQ_HF"):
-            raise ValueError("model_name choice: [CelebA_HQ_HF, LSUN_church_HF, FFHQ_HF]")
+        # define_argparser.py:163-172.  The guided-diffusion names (:165-168) stop the reference with "please download the weight"; here they select
+        # the ADM presets (configs.ADM_MODEL_NAMES) and run on --weights <state dict of the reference's UNetModel> or on synthetic weights
+        if args.model_name not in ("CelebA_HQ_HF", "LSUN_church_HF", "FFHQ_HF") and args.model_name not in cf.ADM_MODEL_NAMES:
+            raise ValueError("model_name choice: [CelebA_HQ_HF, LSUN_church_HF, FFHQ_HF, " + ", ".join(cf.ADM_MODEL_NAMES) + "]")
         args.exp = f"{args.model_name}-{args.dataset_name}-{args.note}"
     args.exp_folder = os.path.join(args.result_folder, args.exp)
     args.obs_folder = os.path.join(args.exp_folder, "obs")
@@ -173,6 +175,18 @@ def build_unet(args) -> PullbackUNet:
         if small:
             args.image_size = cfg.sample_size
         return PullbackUNet("sd", cfg, params, dtype=args.compute_dtype, device=args.device, max_batch=max_batch, max_rank=max_rank)
+    if args.model_name in cf.ADM_MODEL_NAMES:             # the guided-diffusion U-Net (utils.py:68-99: g_DDPM + load_state_dict, names unchanged)
+        cfg = cf.ADM_MODEL_NAMES[args.model_name]
+        if small:
+            cfg = cf.ADMConfig(image_size=32, model_channels=32, channel_mult=(1, 2, 2), num_res_blocks=1, attention_resolutions=(16,),
+                               num_head_channels=16, use_scale_shift_norm=cfg.use_scale_shift_norm, resblock_updown=cfg.resblock_updown,
+                               use_new_attention_order=cfg.use_new_attention_order, learn_sigma=cfg.learn_sigma)
+        params = torch.load(args.weights, map_location="cpu") if args.weights else cf.adm_init_params(cfg, seed=args.seed)
+        W.check_shapes(params, cf.adm_param_shapes(cfg), f"{args.model_name} U-Net")
+        if small:
+            args.image_size = cfg.image_size
+        # eps is the first half of the output convolution (UNetModel.forward returns et): the scheduler keeps learn_sigma = False, as the reference's does
+        return PullbackUNet("adm", cfg, params, dtype=args.compute_dtype, device=args.device, max_batch=max_batch, max_rank=max_rank)
     cfg = cf.CELEBA_HQ_256 if not small else cf.DDPMConfig(ch=32, ch_mult=(1, 2, 2), num_res_blocks=1, attn_resolutions=(16,), resolution=32)
     if args.weights:                                      # diffusers UNet2DModel keys (google/ddpm-ema-celebahq-256) or vendored names
         params = W.ddpm_hf_to_vendored_names(torch.load(args.weights, map_location="cpu"), cfg)

@@ -1,5 +1,8 @@
 """Host-side mirror of the reference's U-Net plugin surface for the pullback path.
 
+Three network kinds: "sd" (diffusers UNet2DConditionModel), "ddpm" (the vendored PullBackDDPM) and "adm" (the vendored guided-diffusion
+UNetModel, src/models/guided_diffusion/unet.py:398-781, which has the x= / t= surface of the DDPM kind).
+
 The reference attaches ``get_h`` / ``local_encoder_pullback_zt`` (Stable Diffusion) and
 ``get_h`` / ``local_encoder_pullback_xt`` (unconditional) onto a diffusers U-Net with
 ``types.MethodType`` (reference src/utils/utils.py:103-104, :326-337).  ``PullbackUNet`` is a
@@ -32,7 +35,7 @@ import torch
 from . import lib as L
 from .engine import Engine, pca_lowrank
 from .engine import timesteps as _timesteps
-from .tape import build_ddpm, build_sd
+from .tape import build_adm, build_ddpm, build_sd
 
 MAX_RANK = 56          # default tangent capacity of an engine (workspace sizing)
 RANK_LIMIT = 128       # largest pca_rank of the library (csrc/kernels.h ORTH_MAX_RANK)
@@ -57,7 +60,9 @@ def _t_shared(t, batch: int, what: str) -> float:
 class PullbackUNet:
     def __init__(self, kind: str, cfg, params, dtype=torch.float32, device="cuda:0", max_batch: int = 5,
                  max_rank: int = MAX_RANK, upto: Optional[Tuple[str, int]] = None, verbose: bool = True):
-        assert kind in ("sd", "ddpm")
+        if kind not in ("sd", "ddpm", "adm"):
+            raise ValueError(f"unknown network kind {kind!r}: 'sd' (diffusers UNet2DConditionModel), 'ddpm' (vendored PullBackDDPM) or 'adm' "
+                             "(guided-diffusion UNetModel)")
         self.kind, self.config, self.dtype_compute = kind, cfg, dtype
         self.device = torch.device(device)
         self.dtype = torch.float32                       # boundary dtype (what callers see)
@@ -66,6 +71,11 @@ class PullbackUNet:
             tape = build_sd(cfg, params, dtype, self.device, upto)
             self.engine = Engine(tape, cfg.block_out_channels[0], True, False, cfg.in_channels, max_batch, max_rank)
             self.in_shape = (cfg.in_channels, cfg.sample_size, cfg.sample_size)
+        elif kind == "adm":
+            # guided-diffusion's timestep_embedding (nn.py): [cos | sin], exponent denominator half -- the SD form of the sinusoid
+            tape = build_adm(cfg, params, dtype, self.device, upto)
+            self.engine = Engine(tape, cfg.model_channels, True, False, cfg.in_channels, max_batch, max_rank)
+            self.in_shape = (cfg.in_channels, cfg.image_size, cfg.image_size)
         else:
             tape = build_ddpm(cfg, params, dtype, self.device, upto)
             self.engine = Engine(tape, cfg.ch, False, True, cfg.in_channels, max_batch, max_rank)
@@ -77,6 +87,8 @@ class PullbackUNet:
 
     # ------------------------------------------------------------------ feature map
     def _tap(self, op, block_idx):
+        if self.kind == "adm" and op is None and block_idx is None:
+            op, block_idx = "mid", 0                      # UNetModel.get_h takes no (op, block_idx): it is the middle block's output (unet.py:686-702)
         key = (op, block_idx)
         if key not in self.engine.tape.taps:
             raise ValueError(f"(op, block_idx) = ({op, block_idx}) is not valid")
@@ -594,7 +606,7 @@ def bind(unet, kind: str, cfg, dtype=torch.float32, device="cuda:0", **kw) -> Pu
     """Attach the HIP-backed methods onto an existing U-Net module, like the reference's
     ``types.MethodType`` injection (utils.py:103-104, :326-337).  ``unet.state_dict()`` uses diffusers' keys: ``UNet2DConditionModel`` for "sd"
     (consumed as is by tape.build_sd), ``UNet2DModel`` for "ddpm" (renamed by weights.ddpm_hf_to_vendored_names; the vendored
-    naming of src/models/ddpm/diffusion.py is accepted unchanged)."""
+    naming of src/models/ddpm/diffusion.py is accepted unchanged), guided-diffusion ``UNetModel`` for "adm" (consumed as is by tape.build_adm)."""
     sd = {k: v.detach().cpu() for k, v in unet.state_dict().items()}
     if kind == "ddpm":                    # diffusers UNet2DModel keys (the reference's live path, utils.py:101-104) -> builder names
         from .weights import ddpm_hf_to_vendored_names

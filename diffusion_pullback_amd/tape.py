@@ -1,11 +1,13 @@
 """Build the op tape (include/dpb.h: dpb_net_desc) of a diffusion U-Net from its config and state dict.
 
-Two architecture families, the ones the reference's live path drives:
+Three architecture families, the ones the reference's U-Net entry points drive:
   * ``build_ddpm``  -- pixel-space DDPM U-Net (HF google/ddpm-ema-celebahq-256 family; parameter
     naming of reference src/models/ddpm/diffusion.py:22-129), used by get_h_uncond /
     local_encoder_pullback_xt (src/utils/utils.py:114-249).
   * ``build_sd``    -- Stable-Diffusion UNet2DConditionModel (diffusers naming), used by get_h /
     local_encoder_pullback_zt (src/utils/utils.py:438-527, :722-816).
+  * ``build_adm``   -- OpenAI guided-diffusion UNetModel (src/models/guided_diffusion/unet.py:398-781): scale-shift GroupNorm,
+    ResBlocks that resample, the ADM attention block; its own get_h / local_encoder_pullback_xt (:686-781).
 
 Weights are repacked once at load time into the layouts the HIP GEMM consumes:
   conv   W  [Cout][ky][kx][Cin_pad]     (forward operand, K contiguous)
@@ -152,6 +154,24 @@ class Tape:
                  w=[self._dev(self.p[name + ".weight"], torch.float32), self._dev(self.p[name + ".bias"], torch.float32), 0, 0])
         return out
 
+    def groupnorm_mod(self, name: str, x: int, groups: int, eps: float, silu: bool, emb: int, col: int) -> int:
+        """scale-shift GroupNorm (guided-diffusion ResBlock with use_scale_shift_norm): GN(x) * (1 + scale) + shift, (scale | shift) the 2C-wide
+        window at column ``col`` of the SHARED embedding projection ``emb`` (include/dpb.h: modulated DPB_OP_GROUPNORM)"""
+        rows, c, _ = self.buffers[x]
+        out = self.buf(rows, c)
+        self._op(kind=L.OP_GROUPNORM, in0=x, in1=emb, out=out, ip=[groups, int(silu), 1, col] + [0] * 8, fp=[eps, 0, 0, 0],
+                 w=[self._dev(self.p[name + ".weight"], torch.float32), self._dev(self.p[name + ".bias"], torch.float32), 0, 0])
+        return out
+
+    def resample(self, x: int, hw: Tuple[int, int], up: bool) -> int:
+        """2x2 average pool (up=False) or nearest x2 upsample of an [h*w][C] map (DPB_OP_RESAMPLE)"""
+        rows, c, _ = self.buffers[x]
+        h, w = hw
+        assert rows == h * w and (up or (h % 2 == 0 and w % 2 == 0)), (rows, hw)
+        out = self.buf(4 * rows if up else rows // 4, c)
+        self._op(kind=L.OP_RESAMPLE, in0=x, out=out, ip=[int(up), h, w] + [0] * 9)
+        return out
+
     def layernorm(self, name: str, x: int, eps: float = 1e-5) -> int:
         rows, c, _ = self.buffers[x]
         out = self.buf(rows, c)
@@ -286,6 +306,102 @@ def _build_ddpm(cfg, params, dtype, device, upto: Optional[Tuple[str, int]] = No
     n = t.groupnorm("norm_out", h, G, eps, True)
     o = t.conv("conv_out", n, (r, r), cfg.out_ch)
     t.tap("eps", o, cfg.out_ch, r, r)
+    return t
+
+
+# =================================================================== guided-diffusion / ADM (pixel space, unconditional)
+def build_adm(cfg, params, dtype, device, upto: Optional[Tuple[str, int]] = None) -> Tape:
+    t = _build_adm(cfg, params, dtype, device, upto)
+    for h in t._deferred:
+        t.shared_end(h)
+    return t
+
+
+def _build_adm(cfg, params, dtype, device, upto: Optional[Tuple[str, int]] = None) -> Tape:
+    """cfg: configs.ADMConfig; params: the state dict of the reference's UNetModel (src/models/guided_diffusion/unet.py:398-618), names
+    unchanged.  Taps: ('mid', 0) -- the reference's get_h (unet.py:686-702) -- and 'eps', the first half of the output convolution when the
+    model learns sigma (UNetModel.forward returns et only, unet.py:680-684: the log-variance rows are never computed)."""
+    from .configs import adm_blocks, adm_qkv_rows
+    blocks = adm_blocks(cfg)                                   # (raises for class-conditional configs)
+    t = Tape(dict(params), dtype, device)                      # (a shallow copy: the repacked attention / output weights below are entries of it)
+    mc, res = cfg.model_channels, cfg.image_size
+    G, eps = cfg.groups, cfg.gn_eps
+    ssn = cfg.use_scale_shift_norm
+    t.temb_in = t.buf(1, _r8(mc), L.BUF_SHARED)
+    e0 = t.conv("time_embed.0", t.temb_in, (1, 1), cfg.temb_ch, ks=1, need_adj=False, kind=L.BUF_SHARED)
+    e1 = t.conv("time_embed.2", t.silu(e0), (1, 1), cfg.temb_ch, ks=1, need_adj=False, kind=L.BUF_SHARED)
+    st = t.silu(e1)                                            # emb_layers.0 of every ResBlock
+    eproj = t.shared_begin(st, L.BUF_SHARED)                   # every ResBlock's emb_layers.1 in one product
+    t._deferred = [eproj]
+    t.x = t.buf(res * res, _r8(cfg.in_channels))
+
+    def resblock(pre, x, cin, cout, r, updown=None):
+        n1 = t.groupnorm(pre + ".in_layers.0", x, G, eps, True)
+        ro = r
+        if updown is not None:                                 # unet.py:239-244: both branches resampled, the convolution after
+            n1 = t.resample(n1, (r, r), updown == "up")
+            x = t.resample(x, (r, r), updown == "up")
+            ro = 2 * r if updown == "up" else r // 2
+        if ssn:
+            c1 = t.conv(pre + ".in_layers.2", n1, (ro, ro), cout)
+            n2 = t.groupnorm_mod(pre + ".out_layers.0", c1, G, eps, True, eproj["out"], t.shared_add(eproj, pre + ".emb_layers.1", 2 * cout))
+        else:
+            c1 = t.conv(pre + ".in_layers.2", n1, (ro, ro), cout, rowbias=eproj["out"], rowbias_off=t.shared_add(eproj, pre + ".emb_layers.1", cout))
+            n2 = t.groupnorm(pre + ".out_layers.0", c1, G, eps, True)
+        sc = t.conv(pre + ".skip_connection", x, (ro, ro), cout, ks=1) if cin != cout else x
+        return t.conv(pre + ".out_layers.3", n2, (ro, ro), cout, res=sc)
+
+    def attn(pre, x, c, r):
+        heads = cfg.heads_for(c)
+        rows = adm_qkv_rows(c, heads, cfg.use_new_attention_order)
+        t.p[pre + ".qkv!.weight"] = t.p[pre + ".qkv.weight"].reshape(3 * c, c)[rows]      # Conv1d [3C, C, 1] -> the engine's q | k | v windows of [heads][d]
+        t.p[pre + ".qkv!.bias"] = t.p[pre + ".qkv.bias"][rows]
+        t.p[pre + ".proj_out!.weight"] = t.p[pre + ".proj_out.weight"].reshape(c, c)
+        t.p[pre + ".proj_out!.bias"] = t.p[pre + ".proj_out.bias"]
+        n = t.groupnorm(pre + ".norm", x, G, eps, False)
+        qkv = t.conv(pre + ".qkv!", n, (r, r), 3 * c, ks=1)
+        a = t.attention(qkv, qkv, qkv, heads, c, (0, c, 2 * c))                           # scale d^-1/2 = the reference's d^-1/4 on q and on k
+        return t.conv(pre + ".proj_out!", a, (r, r), c, ks=1, res=x)
+
+    hs = []
+    h, r = t.x, res
+    i_mid = next(i for i, b in enumerate(blocks) if b[0] == "middle_block.0")
+    for name, kind, cin, cout, ds in blocks[:i_mid]:
+        if kind == "conv_in":
+            h = t.conv(name, h, (r, r), cout)
+        elif kind == "res":
+            h = resblock(name, h, cin, cout, r)
+        elif kind == "attn":
+            h = attn(name, h, cin, r)
+            hs.pop()                                           # the attention block closes the input block its ResBlock opened
+        elif kind == "res_down":
+            h = resblock(name, h, cin, cout, r, "down"); r //= 2
+        else:                                                  # Downsample with conv_resample: 3x3, stride 2, padding 1
+            h = t.conv(name + ".op", h, (r, r), cout, stride=2, pad=1); r //= 2
+        hs.append((h, cout))
+    ch = blocks[i_mid][2]
+    h = resblock("middle_block.0", h, ch, ch, r)
+    h = attn("middle_block.1", h, ch, r)
+    h = resblock("middle_block.2", h, ch, ch, r)
+    t.tap(("mid", 0), h, ch, r, r)
+    if upto == ("mid", 0):
+        return t
+    for name, kind, cin, cout, ds in blocks[i_mid + 3:]:
+        if kind == "res":
+            sk, skc = hs.pop()
+            h = resblock(name, t.concat(h, sk), cin, cout, r)
+        elif kind == "attn":
+            h = attn(name, h, cin, r)
+        elif kind == "res_up":
+            h = resblock(name, h, cin, cout, r, "up"); r *= 2
+        else:                                                  # Upsample with conv_resample: nearest x2, then 3x3
+            h = t.conv(name + ".conv", h, (r, r), cout, upsample=True); r *= 2
+        ch = cout
+    n = t.groupnorm("out.0", h, G, eps, True)
+    co = cfg.in_channels
+    t.p["out.2!.weight"], t.p["out.2!.bias"] = t.p["out.2.weight"][:co], t.p["out.2.bias"][:co]
+    o = t.conv("out.2!", n, (r, r), co)
+    t.tap("eps", o, co, r, r)
     return t
 
 

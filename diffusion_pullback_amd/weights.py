@@ -7,6 +7,8 @@ block naming; the tape builder (tape.build_ddpm) uses the naming of the vendored
 ``ddpm_hf_to_vendored_names`` is the rename between the two -- the inverse of diffusers'
 ``convert_ddpm_original_checkpoint_to_diffusers.py`` -- so ``bind(pipe.unet, "ddpm", ...)`` works on the real checkpoint.
 Stable-Diffusion weights need no rename: tape.build_sd consumes diffusers' ``UNet2DConditionModel`` keys directly.
+Guided-diffusion (ADM) weights need none either: the state dict of the reference's ``UNetModel`` (src/utils/utils.py:68-99: ``g_DDPM`` +
+``load_state_dict``) is consumed as is by tape.build_adm; ``check_shapes(params, configs.adm_param_shapes(cfg), ...)`` validates it.
 """
 from __future__ import annotations
 

@@ -32,7 +32,8 @@ enum { DPB_F32 = 0, DPB_BF16 = 1, DPB_F16 = 2 };   /* storage + MFMA input type;
 /* ---- network description: a tape of NHWC ops over numbered activation buffers ------------- */
 enum {
   DPB_OP_CONV = 1,      /* conv KSxKS / 1x1 / Linear: out = W*in (+bias) (+rowbias[temb]) (+res)      */
-  DPB_OP_GROUPNORM = 2, /* GroupNorm(G, eps) (+SiLU)                                                   */
+  DPB_OP_GROUPNORM = 2, /* GroupNorm(G, eps) (+SiLU); optionally modulated per sample: (gamma x^ + beta)(1 + scale_b) + shift_b,
+                           (scale_b | shift_b) a 2C-wide column window of the SHARED buffer in1 (see dpb_op_desc)          */
   DPB_OP_LAYERNORM = 3, /* LayerNorm over channels                                                     */
   DPB_OP_ATTENTION = 4, /* multi-head softmax(q k^T d^-1/2) v ; in0=q in1=k in2=v                      */
   DPB_OP_GEGLU = 5,     /* [rows][2F] -> [rows][F] : a * gelu_erf(g).  dpb_primal OVERWRITES the input buffer
@@ -40,7 +41,12 @@ enum {
                            have no other consumer (checked at create) and is not a meaningful tap afterwards;
                            dpb_forward leaves it untouched                                              */
   DPB_OP_SILU = 6,      /* elementwise x*sigmoid(x); ip[0] = 1: quick-GELU x*sigmoid(1.702x), 2: erf GELU (primal only) */
-  DPB_OP_CONCAT = 7     /* channel concat of in0, in1                                                  */
+  DPB_OP_CONCAT = 7,    /* channel concat of in0, in1                                                  */
+  DPB_OP_RESAMPLE = 8   /* stand-alone 2x2 resampling of an NHWC map, C unchanged: ip[0] = 0 average pool (H x W -> H/2 x W/2, H and W even),
+                           ip[0] = 1 nearest x2 upsample (H x W -> 2H x 2W); ip[1], ip[2] = input H, W.  The h_upd / x_upd of the guided-diffusion
+                           ResBlock with up / down (reference src/models/guided_diffusion/unet.py:192-197, :239-244: Downsample / Upsample with
+                           use_conv = False, i.e. avg_pool2d(2) and F.interpolate(scale_factor=2, mode="nearest")).  Tangent: the same map;
+                           adjoint of the pool: 0.25 x nearest upsample, of the upsample: the 2x2 sum.  fp32 arithmetic, one rounding    */
 };
 enum { DPB_GATHER_NONE = 0, DPB_GATHER_CONV = 1, DPB_GATHER_UPCONV = 3 };
 enum { DPB_BUF_ACT = 0,     /* per-sample activation [rows][channels]                                   */
@@ -60,8 +66,14 @@ typedef struct dpb_op_desc {
   int32_t out;               /* output buffer id */
   int32_t res;               /* CONV: buffer added to the output (residual / shortcut), -1 = none */
   int32_t rowbias;           /* CONV: DPB_BUF_SHARED buffer [1][>= Cout] added to every row (temb projection; dpb_primal_t: sample b's row to sample b's rows), -1 */
-  int32_t ip[12];            /* CONV: H W Cin Ho Wo Cout KS stride pad gather rowbias_col (first column of this op's Cout-wide window in the rowbias buffer) ; GROUPNORM: G silu ;
-                                ATTENTION: heads oq ok ov causal ; GEGLU: F interleave(0|64)                                               */
+  int32_t ip[12];            /* CONV: H W Cin Ho Wo Cout KS stride pad gather rowbias_col (first column of this op's Cout-wide window in the rowbias buffer) ; GROUPNORM: G silu modulated mod_col ;
+                                ATTENTION: heads oq ok ov causal ; GEGLU: F interleave(0|64) ; RESAMPLE: mode(0 pool | 1 up) H W
+                                GROUPNORM with ip[2] = 1 (scale-shift norm, "AdaGN": out_norm(h) * (1 + scale) + shift, unet.py:250-254): in1 is the
+                                DPB_BUF_SHARED buffer of the ResBlocks' fused embedding projection (produced by an op), ip[3] the first column of this
+                                op's `scale` window [C]; `shift` follows at ip[3] + C.  The primal / forward pass folds both into a per-sample affine
+                                gamma_b = gamma (1 + scale_b), beta_b = beta (1 + scale_b) + shift_b (fp32 tables in the workspace, filled right
+                                after the projection; row b of the projection under dpb_primal_t, row 0 otherwise); scale and shift do not depend on x,
+                                so the tangent / adjoint formulas are those of the plain op with gamma_b.  ip[2] = 0 (in1 ignored, -1): the plain op */
   float fp[4];               /* GROUPNORM/LAYERNORM: eps */
   const void* w[4];          /* CONV: w[0]=W [Cout][KS*KS*Cin] (engine dtype), w[1]=W^T [Cin][KS*KS*Cout]
                                 (engine dtype, for the adjoint; may be NULL for ops never differentiated),
