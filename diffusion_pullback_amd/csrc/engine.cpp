@@ -1467,6 +1467,21 @@ int dpb_pca_lowrank(const float* H, int64_t N, int64_t D, const float* R, int q,
   return launch_pca_lowrank(H, N, D, R, q, niter, u, s, scratch, scratch_bytes, (hipStream_t)stream);
 }
 
+// Principal angles / geodesic distances between the saved local tangent spaces (the analysis run_sample_encoder_local_tangent_space_zt saves its
+// bases for; the reference carries no code for it): angles.hip
+int dpb_cross_gram(const float* X, const float* Y, double* G, int Ra, int Rb, int64_t N, void* stream) {
+  if (!X || !G) return fail("dpb_cross_gram: null argument");
+  return launch_cross_gram(X, Y, G, Ra, Rb, N, (hipStream_t)stream);
+}
+
+size_t dpb_subspace_angles_scratch_bytes(int Ba, int Bb, int k, int64_t N) { return subspace_angles_scratch_bytes(Ba, Bb, k, N); }
+
+int dpb_subspace_angles(const float* A, const float* B, int Ba, int Bb, int k, int64_t N, float* theta, float* dist, void* scratch, size_t scratch_bytes,
+                        void* stream) {
+  if (!A || !theta || !dist || !scratch) return fail("dpb_subspace_angles: null argument");
+  return launch_subspace_angles(A, B, Ba, Bb, k, N, theta, dist, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
 // The perturbed batch and the sampling loop of the reference's local_pca_zt / local_pca_xt (src/utils/utils.py:916-933;
 // src/models/ddpm/diffusion.py:396-409): noise.hip
 size_t dpb_perturb_scratch_bytes(int B, int64_t n) { return perturb_scratch_bytes(B, n); }

@@ -335,6 +335,13 @@ size_t pca_scratch_bytes(int q, long N, long D);         // 0 when invalid
 int launch_pca_lowrank(const float* H, long N, long D, const float* R, int q, int niter, float* u, float* s, void* scratch, size_t scratch_bytes,
                        hipStream_t st);
 
+// ---------------------------------------------------------------- principal angles between subspaces (angles.hip): exact fp64 cross-Gram on the f64 MFMA,
+// then per-basis whitening and a per-pair Jacobi eigen-solve, all fp64.  G [Ra][Rb] fp64; Y = nullptr: Y = X (upper tiles computed, mirrored)
+int launch_cross_gram(const float* X, const float* Y, double* G, int Ra, int Rb, long N, hipStream_t st);
+size_t subspace_angles_scratch_bytes(long Ba, long Bb, int k, long N);   // 0 when invalid
+int launch_subspace_angles(const float* A, const float* B, long Ba, long Bb, int k, long N, float* theta, float* dist, void* scratch, size_t scratch_bytes,
+                           hipStream_t st);
+
 // ---------------------------------------------------------------- the perturbed batch of local PCA (noise.hip)
 // out[b][j] = x[j] + norm * g_b[j] / ||g_b||_2, b < B, j < n (fp32); g_b = noise[b] or Philox4x32-10 normals of (seed, first + b) (dpb.h);
 // noise_out (optional) receives the unnormalised g; scratch: 8-byte aligned, >= perturb_scratch_bytes(B, n) (per-slice fp64 partial sums)

@@ -64,6 +64,20 @@ def save_spectrum_plot(s: torch.Tensor, path: str, dpi=None) -> None:
     plt.close()
 
 
+def save_distance_plot(dist: torch.Tensor, path: str, dpi=None) -> None:
+    """Heat map of a matrix of geodesic distances next to its .pt file (the matplotlib route of save_spectrum_plot); skipped without matplotlib."""
+    try:
+        import matplotlib
+        matplotlib.use("Agg", force=False)
+        import matplotlib.pyplot as plt
+    except Exception:
+        return
+    plt.imshow(dist.detach().float().cpu().numpy(), cmap="viridis")
+    plt.colorbar(label="geodesic distance (rad)")
+    plt.savefig(path, **({"dpi": dpi} if dpi else {}))
+    plt.close()
+
+
 def save_vT_visualisation(vT: torch.Tensor, lat_shape, path: str) -> None:
     """vT [k, N_in] shown through the 3 principal channel directions of its pixels, min-max normalised (edit.py:253-263, :359-369)"""
     pix = vT.view(-1, *lat_shape).permute(0, 2, 3, 1).reshape(-1, lat_shape[0]).float()
@@ -120,15 +134,49 @@ class _EditBase(object):
         a pair whose u-, s- and vT- files all exist is skipped (edit.py:337-339, :1560-1562)"""
         os.makedirs(save_dir, exist_ok=True)
         pending = []
-        for ht in (list(h_t) if isinstance(h_t, (list, tuple)) else [h_t]):
-            for idx in range(num_local_basis):
-                name = exp_name(idx, ht)
-                paths = self._basis_paths(save_dir, name)
-                if all(os.path.exists(p) for p in paths):
-                    print(f"!!!ALREADY SAMPLED LOCAL BASIS IDX : {idx}!!!")
-                    continue
-                pending.append((idx, ht, name, paths))
+        for idx, ht, name, paths in self._tangent_space_pairs(h_t, num_local_basis, save_dir, exp_name):
+            if all(os.path.exists(p) for p in paths):
+                print(f"!!!ALREADY SAMPLED LOCAL BASIS IDX : {idx}!!!")
+                continue
+            pending.append((idx, ht, name, paths))
         return pending
+
+    def _tangent_space_pairs(self, h_t, num_local_basis, save_dir, exp_name):
+        """every (basis index, h_t) pair of the job in the reference's order (h_t outer, basis index inner), with its EXP_NAME and its u- / s- / vT- files"""
+        return [(idx, ht, exp_name(idx, ht), [os.path.join(save_dir, p + exp_name(idx, ht) + ".pt") for p in ("u-", "s-", "vT-")])
+                for ht in (list(h_t) if isinstance(h_t, (list, tuple)) else [h_t]) for idx in range(num_local_basis)]
+
+    @torch.no_grad()
+    def run_tangent_space_distance(self, h_t, op, block_idx, pca_rank=50, num_local_basis=10, space="x", max_bytes=None, **naming):
+        """Principal angles and geodesic distances between the local tangent spaces run_sample_encoder_local_tangent_space_zt saved -- the
+        analysis those files are for (the reference has no code for it).  The job's (basis index, h_t) pairs are listed in the order of
+        _pending_tangent_spaces, in the directory and under the EXP_NAMEs of the sampling job (naming: what the driver's
+        _tangent_space_naming takes -- edit_prompt for Stable Diffusion, fix_xt / fix_t for the unconditional nets).  space "x": the row spans of
+        vT [k, N_in]; "h": the column spans of u [N_h, k] (un-normalised J V: the angles do not need orthonormal rows).  Nothing is sampled here:
+        a missing file raises ValueError with the list of missing names.  The stack goes to the device and through geometry.py (dpb_subspace_angles,
+        self mode).  Writes tangent_space_distance-<space>-<EXP_NAME of the set>.pt -- a dict of names, idx, h_t, theta [P, P, k] (descending) and
+        dist [P, P] = ||theta||_2 -- and a heat map of dist as .png next to it; returns the dict.  Distances only: no means, no transport."""
+        from . import geometry
+        if space not in ("x", "h"):
+            raise ValueError(f"space must be 'x' (vT) or 'h' (u), got {space!r}")
+        save_dir, exp_name = self._tangent_space_naming(op, block_idx, pca_rank, **naming)
+        pairs = self._tangent_space_pairs(h_t, num_local_basis, save_dir, exp_name)
+        files = [paths[2] if space == "x" else paths[0] for _, _, _, paths in pairs]
+        missing = [os.path.basename(f) for f in files if not os.path.exists(f)]
+        if missing:
+            raise ValueError(f"{len(missing)} of {len(files)} tangent-space files are missing in {save_dir}: {missing}; run the sampling job "
+                             "(run_sample_encoder_local_tangent_space_zt) with the same arguments first")
+        with T.phase("tangent-space distances (principal angles)"):
+            bases = [torch.load(f, map_location=self.device).float() for f in files]
+            stack = torch.stack([b if space == "x" else b.T for b in bases]).contiguous()
+            theta, dist = geometry.subspace_angles_and_distance(stack, None, max_bytes)
+        hts = list(h_t) if isinstance(h_t, (list, tuple)) else [h_t]
+        self.EXP_NAME = f"tangent_space_distance-{space}-" + exp_name(f"0to{num_local_basis - 1}", ",".join(str(h) for h in hts))
+        out = dict(names=[name for _, _, name, _ in pairs], idx=[int(i) for i, _, _, _ in pairs], h_t=[float(h) for _, h, _, _ in pairs],
+                   theta=theta.cpu(), dist=dist.cpu())
+        torch.save(out, os.path.join(save_dir, self.EXP_NAME + ".pt"))
+        save_distance_plot(out["dist"], os.path.join(save_dir, self.EXP_NAME + ".png"), dpi=80)
+        return out
 
     def _sample_tangent_spaces(self, pending, make_xt, ctx, op, block_idx, pca_rank, thr, save_dir, finish):
         """The pending pairs through unet.local_encoder_pullback_batch, in groups of at most min(max_batch, max_rank // pca_rank): the samples of
@@ -241,6 +289,14 @@ class EditStableDiffusion(_EditBase):
             latents = self.scheduler.step(noise_pred, t, latents, eta=0).prev_sample
         return latents
 
+    def _tangent_space_naming(self, op, block_idx, pca_rank, edit_prompt=None):
+        """directory and EXP_NAME(idx, h_t) of the tangent-space files; edit_prompt sets the driver's prompt (None keeps it), as the sampling job does"""
+        if edit_prompt is not None and edit_prompt != self.edit_prompt:
+            self.edit_prompt = edit_prompt
+            self.edit_prompt_emb = self._get_prompt_emb(self.edit_prompt)
+        save_dir = os.path.join(self.input_root, f"local_encoder_pullback_stable_diffusion-dataset_{self.dataset_name}-num_steps_{self.for_steps}-pca_rank_{pca_rank}")
+        return save_dir, lambda idx, ht: f'zt-{self.dataset_name}_{idx}-{ht}T-"{self.edit_prompt}"-{op}-block_{block_idx}-seed_{self.seed}'
+
     @torch.no_grad()
     def run_sample_encoder_local_tangent_space_zt(self, h_t, op, block_idx, pca_rank=50, num_local_basis=10, use_edit_prompt=None, edit_prompt=None,
                                                   vis_vT=True):
@@ -259,8 +315,7 @@ class EditStableDiffusion(_EditBase):
             self.edit_prompt = edit_prompt
             self.edit_prompt_emb = self._get_prompt_emb(self.edit_prompt)
         self.scheduler.set_timesteps(self.for_steps)
-        save_dir = os.path.join(self.input_root, f"local_encoder_pullback_stable_diffusion-dataset_{self.dataset_name}-num_steps_{self.for_steps}-pca_rank_{pca_rank}")
-        exp_name = lambda idx, ht: f'zt-{self.dataset_name}_{idx}-{ht}T-"{self.edit_prompt}"-{op}-block_{block_idx}-seed_{self.seed}'
+        save_dir, exp_name = self._tangent_space_naming(op, block_idx, pca_rank)
         pending = self._pending_tangent_spaces(h_t, num_local_basis, save_dir, exp_name)
 
         zTs = {}                                               # (a list h_t asks for the same latent once per h_t: one inversion per basis index and call)
@@ -506,6 +561,13 @@ class EditUncondDiffusion(_EditBase):
             save_image((xt / 2 + 0.5).clamp(0, 1), os.path.join(self.result_folder, f"x0_gen-{self.EXP_NAME}.png"), nrow=xt.size(0))
         return xt if return_xt else None
 
+    def _tangent_space_naming(self, op, block_idx, pca_rank, fix_xt=False, fix_t=False):
+        """directory and EXP_NAME(idx, h_t) of the tangent-space files, -fix_xt / -fix_t appended to the directory (edit.py:1547-1550)"""
+        assert (not fix_xt) or (not fix_t)
+        save_dir = os.path.join(self.input_root, f"local_encoder_pullback_uncond-model_{self.model_name}-dataset_{self.dataset_name}-num_steps_{self.for_steps}-pca_rank_{pca_rank}")
+        save_dir += "-fix_xt" if fix_xt else "-fix_t" if fix_t else ""
+        return save_dir, lambda idx, ht: f"xt-{self.dataset_name}_{idx}-{ht}T-{op}-block_{block_idx}-seed_{self.seed}"
+
     @torch.no_grad()
     def run_sample_encoder_local_tangent_space_zt(self, h_t, op, block_idx, pca_rank=50, num_local_basis=100, fix_xt=False, fix_t=False):
         """Reference: src/modules/edit.py:1517-1599 -- the local tangent spaces (u, s, vT) of num_local_basis noise images at h_t.  h_t: a float,
@@ -516,9 +578,7 @@ class EditUncondDiffusion(_EditBase):
         appended (the reference's own directory needs a scheduler_name it never defines)."""
         assert (not fix_xt) or (not fix_t)                                                      # edit.py:1539
         self.scheduler.set_timesteps(self.for_steps)
-        save_dir = os.path.join(self.input_root, f"local_encoder_pullback_uncond-model_{self.model_name}-dataset_{self.dataset_name}-num_steps_{self.for_steps}-pca_rank_{pca_rank}")
-        save_dir += "-fix_xt" if fix_xt else "-fix_t" if fix_t else ""                          # edit.py:1547-1550
-        exp_name = lambda idx, ht: f"xt-{self.dataset_name}_{idx}-{ht}T-{op}-block_{block_idx}-seed_{self.seed}"
+        save_dir, exp_name = self._tangent_space_naming(op, block_idx, pca_rank, fix_xt=fix_xt, fix_t=fix_t)
         pending = self._pending_tangent_spaces(h_t, num_local_basis, save_dir, exp_name)
 
         def make_xt(idx, ht):

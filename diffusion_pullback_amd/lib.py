@@ -97,6 +97,10 @@ SYMBOLS = {
     "dpb_perturb_unit": (_I, [_P, _P, C.c_uint64, _L, _I, _L, _F, _P, _P, _P, C.c_size_t, _P]),
     "dpb_local_pca_scratch_bytes": (C.c_size_t, [_P]),
     "dpb_local_pca_sample": (_I, [_P, _P, _F, _P, _I, _I, _P, C.c_uint64, _L, _L, _P, _P, C.c_size_t]),
+    # principal angles / geodesic distances between stacks of subspaces (geometry.py): exact fp64 cross-Gram, then fp64 small algebra
+    "dpb_cross_gram": (_I, [_P, _P, _P, _I, _I, _L, _P]),
+    "dpb_subspace_angles_scratch_bytes": (C.c_size_t, [_I, _I, _I, _L]),
+    "dpb_subspace_angles": (_I, [_P, _P, _I, _I, _I, _L, _P, _P, _P, C.c_size_t, _P]),
 }
 
 _lib = None

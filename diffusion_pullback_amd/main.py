@@ -14,6 +14,10 @@ file; default: seeded synthetic weights, there are no checkpoints offline), --ne
 every timestep of --h_t_list (comma-separated; default: the single --h_t), with --fix_xt / --fix_t for the unconditional net; the pending
 (latent, h_t) pairs advance together, each at its own timestep.  The reference's call sites fix pca_rank=50 and loop over its EDIT_T_LIST (and, for
 SD, over MS-COCO captions, which are not available offline): here --pca_rank, --h_t_list and --edit_prompt say the same.
+``--run_tangent_space_distance True --distance_space x|h`` computes what those files are saved for: the principal angles and the geodesic
+distance ||theta||_2 between every two sampled tangent spaces (x: the spans of vT, h: the spans of u), on the GPU (geometry.py).  It honours --h_t_list,
+--num_local_basis, --pca_rank, --op, --block_idx, --edit_prompt, --fix_xt and --fix_t exactly as the sampling job does, reads that job's files (a missing
+one is an error: nothing is sampled silently) and writes tangent_space_distance-<space>-....pt and .png next to them.  Distances only: no means, no transport.
 """
 from __future__ import annotations
 
@@ -59,6 +63,8 @@ _FLAGS = [  # (name, type, default) -- define_argparser.py:20-110, live path onl
     # define_argparser.py: the tangent-space sampling job of main.py:45-91 (h_t_list is new: the reference edits EDIT_T_LIST in its source)
     ("run_sample_encoder_local_tangent_space_zt", str2bool, False), ("num_local_basis", int, 10), ("h_t_list", str, ""),
     ("fix_xt", str2bool, False), ("fix_t", str2bool, False),
+    # new: principal angles / geodesic distances between the sampled tangent spaces (geometry.py); x = the spans of vT, h = the spans of u
+    ("run_tangent_space_distance", str2bool, False),
     # new
     ("pca_rank", int, 2), ("op", str, "mid"), ("block_idx", int, 0), ("vis_num", int, 4), ("vis_num_pc", int, 2), ("weights", str, ""),
     ("net_scale", str, "full"), ("vae", str, "none"), ("text_encoder", str, "none"), ("tokenizer_dir", str, ""),
@@ -79,6 +85,7 @@ def parse_args(argv=None):
     # --memory_bound is NOT a flag of the reference (define_argparser.py:211-221 sets memory_bound to a per-model constant, kept in preset()); here an explicit
     # value is the user's bound on the U-Net batch -- decode chunks, trajectory batching, the guidance chains per call and the engine's max_batch all respect it
     p.add_argument("--memory_bound", type=int, default=None)
+    p.add_argument("--distance_space", type=str, default="x", choices=["x", "h"])
     args, extra = p.parse_known_args(argv)
     if args.memory_bound is not None and args.memory_bound < 1:
         p.error("--memory_bound must be a positive integer")
@@ -260,6 +267,13 @@ def main(argv=None):
             edit.run_sample_encoder_local_tangent_space_zt(use_edit_prompt=None, edit_prompt=args.edit_prompt, **kw)
         else:
             edit.run_sample_encoder_local_tangent_space_zt(fix_xt=args.fix_xt, fix_t=args.fix_t, **kw)
+    if args.run_tangent_space_distance:                                          # after the sampling job when both are asked for: it reads that job's files
+        kw = dict(h_t=args.h_t_values if args.h_t_list else args.h_t, op=args.op, block_idx=args.block_idx, pca_rank=args.pca_rank,
+                  num_local_basis=args.num_local_basis, space=args.distance_space)
+        if args.is_stable_diffusion:
+            edit.run_tangent_space_distance(edit_prompt=args.edit_prompt, **kw)
+        else:
+            edit.run_tangent_space_distance(fix_xt=args.fix_xt, fix_t=args.fix_t, **kw)
     if args.run_ddim_forward:
         edit.run_DDIMforward(num_samples=5)
     if args.run_ddim_inversion:

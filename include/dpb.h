@@ -209,6 +209,43 @@ int dpb_local_pca_sample(dpb_engine* e, const float* x /*[1][N_in]*/, float t, c
                          int64_t first, int64_t count, float* H /*[count][D] rows first.. of the caller's matrix*/,
                          void* scratch, size_t scratch_bytes);
 
+/* ---- principal angles and geodesic distances between subspaces (additive to ABI version 1; engine-independent) ------------------------
+ * The analysis the bases (u, s, vT) of run_sample_encoder_local_tangent_space_zt are saved for (src/modules/edit.py:310-383, :1517-1599; the
+ * reference has no code for it): the principal angles theta_1..theta_k between two k-dimensional subspaces of R^N and the geodesic distance
+ * ||theta||_2 on the Grassmannian.  Distances only: no exponential / logarithm maps, no means, no parallel transport.
+ *
+ * dpb_cross_gram: G[i][j] = sum_n X[i][n] Y[j][n].  X [Ra][N], Y [Rb][N] fp32, G [Ra][Rb] FP64 (row stride Rb).  The fp32 inputs are widened on
+ * load and multiplied on the fp64 matrix cores (v_mfma_f64_16x16x4_f64), so every product is exact and only the fp64 accumulation rounds.  Y = NULL
+ * means Y = X (Rb must equal Ra): only the 64 x 64 tiles on and above the diagonal are computed, the others are their mirror images (G is exactly
+ * symmetric).  N is cut into at most eight slices whose length depends on N only; the slices are added into G in slice order by stream-ordered
+ * launches, no atomics: bitwise reproducible, and an entry does not depend on Ra, Rb or its position.  Ra, Rb, N >= 1 (Ra <= 4 194 240), any N
+ * (16-byte loads when N % 4 == 0 and X, Y are 16-byte aligned), 64-bit offsets (X may exceed 4 GiB).  G must not alias X or Y.  No scratch, no device
+ * allocation, no host synchronisation.
+ *
+ * dpb_subspace_angles: A [Ba][k][N], B [Bb][k][N] fp32, stacks of bases, one basis per k rows; the rows need NOT be orthonormal (u is J V_prev,
+ * un-normalised) but must be linearly independent.  theta [Ba][Bb][k] fp32, descending per pair (the convention of scipy.linalg.subspace_angles),
+ * dist [Ba][Bb] fp32 = ||theta||_2 (summed in fp64).  Method, everything after the inputs in fp64: the cross-Gram of all rows as above (one pass
+ * over A and B; nothing of size N is orthonormalised or written); per basis the rows are normalised through the Gram diagonal and the basis is
+ * whitened by the Cholesky factor of its own block, Ghat_ii = L_i L_i^T; per pair M = L_i^-1 Ghat_ij L_j^-T, the eigenvalues l of S = I - M M^T
+ * (two-sided Jacobi, in LDS) clamped to [0, 1], theta = asin(sqrt(l)) for l <= 1/2, else acos(sqrt(1 - l)).  Measured against
+ * scipy.linalg.subspace_angles in float64 on the same fp32 inputs: <= 1e-6 rad per angle for bases of condition number <= ~100, small angles
+ * included (tests/test_gpu_subspace_angles.py).
+ * B = NULL: self mode (Bb must equal Ba): the pairs i < j are computed and mirrored, the diagonal is exactly 0.
+ * Degenerate basis: a zero (or non-finite) row, or a Cholesky pivot (the diagonal entry before its square root) of the row-normalised block
+ * below 1e-10 -- a basis condition number beyond ~1e5.  Every entry of that basis's row / column of theta and dist is NaN (its self-mode diagonal
+ * too); no other entry is affected.
+ * Reproducibility and batch invariance: no atomics, every sum in a fixed order; theta of a pair is a function of the 2k rows of that pair and of
+ * N only -- not of Ba, Bb or the pair's position -- so a pair's result is bitwise the same in a call of its own, in a larger call, and in self
+ * mode (i < j) over the concatenation.
+ * Limits: 1 <= k <= 128, k <= N, 1 <= Ba, Bb <= 65535.  scratch: 256-byte aligned device memory of scratch_bytes >=
+ * dpb_subspace_angles_scratch_bytes(Ba, Bb, k, N) (the fp64 cross-Gram of Ba k x Bb k entries, the whitening matrices, 1024 x 2 k^2 doubles of
+ * workgroup scratch); the size is checked.  theta and dist must not alias A, B or scratch.  No device allocation, no host synchronisation.
+ * Errors via dpb_last_error. */
+int dpb_cross_gram(const float* X, const float* Y /*or NULL: Y = X*/, double* G, int Ra, int Rb, int64_t N, void* hip_stream);
+size_t dpb_subspace_angles_scratch_bytes(int Ba, int Bb, int k, int64_t N);   /* 0 when invalid */
+int dpb_subspace_angles(const float* A, const float* B /*or NULL: self mode*/, int Ba, int Bb, int k, int64_t N, float* theta, float* dist,
+                        void* scratch, size_t scratch_bytes, void* hip_stream);
+
 /* n_iters full power iterations with no host synchronisation: V <- orth(J^T J V), U = J V_prev, for all B samples
  * of the last dpb_primal together (independent bases, one shared weight stream; B*k <= max_tangents).
  * V [B][k][N_in] in/out, U [B][k][N_h] out, s [B][k] out, conv [B][2] out (of the last iteration).
