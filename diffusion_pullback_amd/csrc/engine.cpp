@@ -1482,6 +1482,15 @@ int dpb_subspace_angles(const float* A, const float* B, int Ba, int Bb, int k, i
   return launch_subspace_angles(A, B, Ba, Bb, k, N, theta, dist, scratch, scratch_bytes, (hipStream_t)stream);
 }
 
+// Parallel transport of principal directions from one tangent space to others (run_edit_parallel_transport, src/modules/edit.py:892-909): transport.hip
+size_t dpb_transport_scratch_bytes(int D, int P, int k, int64_t N_h, int64_t N_x) { return transport_scratch_bytes(D, P, k, N_h, N_x); }
+
+int dpb_transport_directions(const float* u_src, const float* u_dst, const float* vT_dst, const int32_t* pcs, int P, int D, int k, int64_t N_h,
+                             int64_t N_x, float* vk, float* coef, float* coef_norm, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!u_src || !u_dst || !vT_dst || !pcs || !vk || !coef || !coef_norm || !scratch) return fail("dpb_transport_directions: null argument");
+  return launch_transport_directions(u_src, u_dst, vT_dst, pcs, P, D, k, N_h, N_x, vk, coef, coef_norm, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
 // The perturbed batch and the sampling loop of the reference's local_pca_zt / local_pca_xt (src/utils/utils.py:916-933;
 // src/models/ddpm/diffusion.py:396-409): noise.hip
 size_t dpb_perturb_scratch_bytes(int B, int64_t n) { return perturb_scratch_bytes(B, n); }

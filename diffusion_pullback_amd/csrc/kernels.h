@@ -342,6 +342,12 @@ size_t subspace_angles_scratch_bytes(long Ba, long Bb, int k, long N);   // 0 wh
 int launch_subspace_angles(const float* A, const float* B, long Ba, long Bb, int k, long N, float* theta, float* dist, void* scratch, size_t scratch_bytes,
                            hipStream_t st);
 
+// ---------------------------------------------------------------- parallel transport of directions between tangent spaces (transport.hip)
+// vk[d][p] = normalise(sum_q c[d][p][q] vhat_dst[d][q]), c[d][p][q] = <uhat_dst[d][q], uhat_src[pcs[p]]> (fp64), coef_norm = ||c||; pcs is a HOST list
+size_t transport_scratch_bytes(long D, int P, int k, long Nh, long Nx);   // 0 when invalid
+int launch_transport_directions(const float* u_src, const float* u_dst, const float* vT_dst, const int32_t* pcs, int P, long D, int k, long Nh, long Nx,
+                                float* vk, float* coef, float* coef_norm, void* scratch, size_t scratch_bytes, hipStream_t st);
+
 // ---------------------------------------------------------------- the perturbed batch of local PCA (noise.hip)
 // out[b][j] = x[j] + norm * g_b[j] / ||g_b||_2, b < B, j < n (fp32); g_b = noise[b] or Philox4x32-10 normals of (seed, first + b) (dpb.h);
 // noise_out (optional) receives the unnormalised g; scratch: 8-byte aligned, >= perturb_scratch_bytes(B, n) (per-slice fp64 partial sums)

@@ -5,8 +5,8 @@ Mirrors the public surface of the reference's ``modules/edit.py``:
       run_DDIMinversion :112-183, run_edit_local_encoder_pullback_zt :185-307, run_sample_encoder_local_tangent_space_zt :310-383,
       DDIMforwardsteps :385-482, x_space_guidance :484-502, run_DDIMforward :101-110
   * ``EditUncondDiffusion``  (reference src/modules/edit.py:540-779, :1601-1734)
-      run_DDIMinversion :613-678, run_edit_local_encoder_pullback_zt :680-779, run_sample_encoder_local_tangent_space_zt :1517-1599,
-      DDIMforwardsteps :1601-1714, x_space_guidance :1716-1734
+      run_DDIMinversion :613-678, run_edit_local_encoder_pullback_zt :680-779, run_edit_parallel_transport :782-948,
+      run_sample_encoder_local_tangent_space_zt :1517-1599, DDIMforwardsteps :1601-1714, x_space_guidance :1716-1734
 
 Kept from the reference: the step counts (inv_steps-2 inversion steps, ``edit_t_idx`` forward steps,
 ``x_space_guidance_num_step`` guidance steps, the rest decode), the ``[::len // vis_num]`` subsample,
@@ -177,6 +177,29 @@ class _EditBase(object):
         torch.save(out, os.path.join(save_dir, self.EXP_NAME + ".pt"))
         save_distance_plot(out["dist"], os.path.join(save_dir, self.EXP_NAME + ".png"), dpi=80)
         return out
+
+    def _guidance_chains_together(self, z, vk, t, emb=None):
+        """n independent chains of x-space guidance (edit.py:484-502, :1716-1734) advanced together: chain i starts at z[i] and moves along vk[i],
+        all at the timestep t.  Per step ONE U-Net call of 2 n rows, [z_1..z_n | z_1 + s v_1 .. z_n + s v_n], split only by the engine's batch limit
+        and an explicit --memory_bound (the pair of a chain is never split).  emb: the [1, L, D] conditioning of every row (None: an unconditional
+        net).  Returns the states [n, x_space_guidance_num_step + 1, ...], the start included."""
+        n = z.size(0)
+        chain = [z]
+        cap = getattr(getattr(self.unet, "engine", None), "max_batch", None) or 2 * n
+        per = max(1, min(n, cap // 2))                                                          # chains per U-Net call
+        if getattr(self, "memory_bound_given", None):
+            per = max(1, min(per, self.memory_bound_given // 2))
+        for _ in range(self.x_space_guidance_num_step):
+            nxt = []
+            for zc, vc in zip(z.split(per), vk.split(per)):
+                m = zc.size(0)
+                et = self._eps(torch.cat([zc, zc + self.x_space_guidance_edit_step * vc], dim=0), t,
+                               None if emb is None else emb.repeat(2 * m, 1, 1))                # edit.py:490
+                et_null, et_edit = et.chunk(2)
+                nxt.append(zc + self.x_space_guidance_scale * (et_edit - et_null))              # edit.py:501
+            z = torch.cat(nxt, dim=0)
+            chain.append(z)
+        return torch.stack(chain, dim=1)
 
     def _sample_tangent_spaces(self, pending, make_xt, ctx, op, block_idx, pca_rank, thr, save_dir, finish):
         """The pending pairs through unet.local_encoder_pullback_batch, in groups of at most min(max_batch, max_rank // pca_rank): the samples of
@@ -459,22 +482,7 @@ class EditStableDiffusion(_EditBase):
         t = self.scheduler.timesteps[self.edit_t_idx]
         self._phase = "x-space guidance: batch-2 U-Net forwards"
         vk = torch.cat([v for _, v in todo], dim=0)                                             # [n, C, H, W]
-        z = original_zt.repeat(n, 1, 1, 1)
-        chain = [z]
-        cap = getattr(getattr(self.unet, "engine", None), "max_batch", None) or 2 * n
-        per = max(1, min(n, cap // 2))                                                          # chains per U-Net call
-        if self.memory_bound_given:
-            per = max(1, min(per, self.memory_bound_given // 2))
-        for _ in range(self.x_space_guidance_num_step):
-            nxt = []
-            for zc, vc in zip(z.split(per), vk.split(per)):
-                m = zc.size(0)
-                et = self._eps(torch.cat([zc, zc + self.x_space_guidance_edit_step * vc], dim=0), t, self.edit_prompt_emb.repeat(2 * m, 1, 1))   # edit.py:490
-                et_null, et_edit = et.chunk(2)
-                nxt.append(zc + self.x_space_guidance_scale * (et_edit - et_null))              # edit.py:501
-            z = torch.cat(nxt, dim=0)
-            chain.append(z)
-        steps = torch.stack(chain, dim=1)                                                       # [n, num_step + 1, C, H, W]
+        steps = self._guidance_chains_together(original_zt.repeat(n, 1, 1, 1), vk, t, self.edit_prompt_emb)   # [n, num_step + 1, C, H, W]
         picked = steps[:, ::(steps.size(1) // vis_num)]                                         # edit.py:301-302, per chain
         m = picked.size(1)
         lat = self.DDIMforwardsteps(picked.reshape(n * m, *lat_shape), t_start_idx=self.edit_t_idx, t_end_idx=-1, finish=False)
@@ -489,6 +497,11 @@ class EditStableDiffusion(_EditBase):
 class EditUncondDiffusion(_EditBase):
     def __init__(self, args, unet=None, dataset=None):
         self.memory_bound = getattr(args, "memory_bound", 50)
+        # > 1: the chains of run_edit_parallel_transport advance together (one U-Net call of 2 n rows per guidance step, one decode batch); 0 / 1: the
+        # reference's order, one chain at a time.  The other jobs of this driver do not read it beyond the batch bound of _chunks.
+        self.trajectory_batch = int(getattr(args, "trajectory_batch", 0) or 0)
+        self.memory_bound_given = getattr(args, "memory_bound_given", None)
+        self.h_t = getattr(args, "h_t", 0.8)
         self.device = torch.device(args.device)
         self.dtype = getattr(args, "dtype", torch.float32)
         self.seed = args.seed
@@ -637,3 +650,124 @@ class EditUncondDiffusion(_EditBase):
                 xt = xt[::(xt.size(0) // vis_num)]
                 self.DDIMforwardsteps(xt, t_start_idx=self.edit_t_idx, t_end_idx=-1, performance_boosting=True)
         return xt
+
+    def parallel_transport_plan(self, sample_idx_0, sample_idx_1, op="mid", block_idx=0, vis_num_pc=2, vis_pc_list=None, h_t=None):
+        """The experiments of run_edit_parallel_transport under the reference's names (edit.py:879-881, :912-914, :944) and in its order.  Returns
+        (sample_idx_0, targets, pcs, h_t, plan); plan holds per pc (runs, vk files): runs = [(EXP_NAME, target position or None, sign)] -- the
+        transported pos / neg of every target, then the original pos / neg of the source, named with sample_idx_1 = sample_idx_0 -- and the
+        vk-....png name of every target."""
+        targets = [int(j) for j in sample_idx_1] if isinstance(sample_idx_1, (list, tuple)) else [int(sample_idx_1)]
+        i0 = int(sample_idx_0)
+        h_t = self.h_t if h_t is None else h_t
+        pcs = list(range(vis_num_pc)) if vis_pc_list is None else [int(p) for p in vis_pc_list]
+        exp = lambda j, pc, tag: (f"xt-{self.dataset_name}-sample_idx_0_{i0}-sample_idx_1_{j}-h_{h_t}T-edit_{self.edit_t}T-{op}-block_{block_idx}"
+                                  f"-seed_{self.seed}-pc_{pc:0=3d}_{tag}")
+        plan = []
+        for pc in pcs:
+            runs = [(exp(j, pc, tag), d, sign) for d, j in enumerate(targets) for sign, tag in ((1, "pos"), (-1, "neg"))]
+            runs += [(exp(i0, pc, tag), None, sign) for sign, tag in ((1, "pos"), (-1, "neg"))]
+            plan.append((runs, [f"vk-sample_idx_0_{i0}-sample_idx_1_{j}-pc_{pc:0=3d}.png" for j in targets]))
+        return i0, targets, pcs, h_t, plan
+
+    @torch.no_grad()
+    def run_edit_parallel_transport(self, sample_idx_0, sample_idx_1, op="mid", block_idx=0, vis_num=4, vis_num_pc=2, vis_pc_list=None, pca_rank=50,
+                                    h_t=None):
+        """Reference: src/modules/edit.py:782-948 -- edit sample_idx_1 along the principal directions of sample_idx_0, carried over by parallel
+        transport: at h_t both samples have a local basis (u, vT); component pc of the source is moved to the target as
+        vk = +-normalise(Vhat_1^T (Uhat_1^T uhat_0[:, pc])) and drives x_space_guidance_num_step guidance steps from x_t(sample_idx_1) at edit_t; the
+        original direction +-vhat_0[pc] does the same from x_t(sample_idx_0).  Each chain is subsampled to vis_num states and decoded into
+        x0_gen-<EXP_NAME>.png; the directions [+transported, -transported, +original, -original] go to vk-....png in the obs folder.  Names and skip
+        rules are the reference's (the original-direction runs carry sample_idx_1 = sample_idx_0; the job is skipped when the last pc's _neg
+        picture exists, an experiment when its own does).
+
+        sample_idx_1 may be a list of targets: one call of the transport kernel serves all of them, the original-direction chains run once and
+        every target gets the reference's names (the job is skipped when every target's last picture exists).  Bases: the files of
+        _tangent_space_naming(op, block_idx, pca_rank) -- what run_sample_encoder_local_tangent_space_zt writes (the reference's directory carries a
+        scheduler_name it never defines) -- and the missing ones of the call are computed together by local_encoder_pullback_batch (min_iter=10,
+        max_iter=50, thr=1e-4, edit.py:833-836), each at its own x_t(h_t), and saved as u- / s- / vT-.  Loaded and fresh bases alike are normalised
+        (inside dpb_transport_directions); the reference normalises only what it loads.  No `pca_rank == 50` assertion.
+        trajectory_batch > 1: all pending chains advance together (_guidance_chains_together) and decode in one batch; <= 1: the reference's order.
+        Returns a dict: vk [D, P, N_x], coef [D, P, k], coef_norm [D, P] of the transport, pcs, targets and the EXP_NAMEs run."""
+        from . import geometry
+        i0, targets, pcs, h_t, plan = self.parallel_transport_plan(sample_idx_0, sample_idx_1, op, block_idx, vis_num_pc, vis_pc_list, h_t)
+        picture = lambda name: os.path.exists(os.path.join(self.result_folder, f"x0_gen-{name}.png"))
+        if pcs and all(picture(plan[-1][0][2 * d + 1][0]) for d in range(len(targets))):          # the last pc's _neg of every target (edit.py:789-797)
+            print("!!!ALREADY DONE EXPERIMENT!!!")
+            return None
+        samples = list(dict.fromkeys([i0] + targets))
+        xT = {i: self._random_latent(i) if self.dataset_name == "Random" else self.run_DDIMinversion(idx=i) for i in samples}      # edit.py:800-805
+        self.scheduler.set_timesteps(self.for_steps, device=self.device)
+        h_t_idx = int((self.scheduler.timesteps - h_t * 1000).abs().argmin())
+        at_h = {i: self.DDIMforwardsteps(xT[i], t_start_idx=0, t_end_idx=h_t_idx)[:2] for i in samples}                           # edit.py:808-809
+
+        # the local bases at h_t: the files of the sampling job; the missing ones of this call together
+        save_dir, exp_name = self._tangent_space_naming(op, block_idx, pca_rank)
+        files = {i: self._basis_paths(save_dir, exp_name(i, h_t)) for i in samples}
+        pending = [(i, h_t, exp_name(i, h_t), files[i]) for i in samples if not (os.path.exists(files[i][0]) and os.path.exists(files[i][2]))]
+        if pending:
+            print("!!!RUN LOCAL PULLBACK!!!")
+            self._sample_tangent_spaces(pending, lambda i, ht: at_h[i], None, op, block_idx, pca_rank, 1e-4, save_dir, lambda *a: None)
+        load = lambda p: torch.load(p, map_location=self.device).to(torch.float32)
+        u = {i: load(files[i][0]) for i in samples}                                             # [N_h, k] columns, as saved
+        vT = {i: load(files[i][2]) for i in samples}                                            # [k, N_x] rows
+        self.last_basis = (u[i0], vT[i0])
+
+        at_edit = {i: self.DDIMforwardsteps(xT[i], t_start_idx=0, t_end_idx=self.edit_t_idx)[0].detach() for i in samples}        # edit.py:867-871
+        shape = at_edit[i0].shape[1:]
+        out = dict(pcs=pcs, targets=targets, names=[])
+        if not pcs:
+            return out
+        with T.phase("parallel transport of the directions"):
+            vk_t, coef, coef_norm = geometry.transport_directions(u[i0].t(), torch.stack([u[j].t() for j in targets]),
+                                                                  torch.stack([vT[j] for j in targets]), pcs)
+            v0 = vT[i0][pcs]
+            v0 = v0 / v0.norm(dim=1, keepdim=True)                                              # edit.py:828, :923-924
+        out.update(vk=vk_t, coef=coef, coef_norm=coef_norm)
+
+        chains, pictures = [], []                              # (name, start x_t [1, ...], direction [1, ...]); (vk- file, chains shown, written after chain)
+        for p, (runs, vk_files) in enumerate(plan):
+            shown = [[] for _ in targets]
+            for name, d, sign in runs:
+                if picture(name) or any(name == c[0] for c in chains):                          # (a target equal to the source carries the original run's name)
+                    print("!!!ALREADY DONE!!!")
+                    continue
+                for own in (shown if d is None else [shown[d]]):                                # the original directions appear in every target's vk- picture
+                    own.append(len(chains))
+                chains.append((name, at_edit[i0 if d is None else targets[d]], (sign * (v0[p] if d is None else vk_t[d, p])).view(1, *shape)))
+            pictures += [(f, own, len(chains) - 1) for f, own in zip(vk_files, shown) if own]
+        out["names"] = [c[0] for c in chains]
+
+        def save(name, x):
+            save_image((x / 2 + 0.5).clamp(0, 1), os.path.join(self.result_folder, f"x0_gen-{name}.png"), nrow=x.size(0))
+
+        def save_vk(after):                                     # edit.py:941-947: once a pc's last chain is done
+            for fname, idxs, last in pictures:
+                if last == after:
+                    save_image(torch.cat([chains[i][2] for i in idxs], dim=0), os.path.join(self.obs_folder, fname))
+
+        self._phase = "x-space guidance: batch-2 U-Net forwards"
+        if self.trajectory_batch > 1 and chains:
+            t = self.scheduler.timesteps[self.edit_t_idx]
+            steps = self._guidance_chains_together(torch.cat([c[1] for c in chains]), torch.cat([c[2] for c in chains]), t)
+            picked = steps[:, ::(steps.size(1) // vis_num)]                                     # edit.py:904, per chain
+            m = picked.size(1)
+            self._phase = "DDIM decode of the edited latents: U-Net forwards"
+            x0 = self.DDIMforwardsteps(picked.reshape(len(chains) * m, *shape), t_start_idx=self.edit_t_idx, t_end_idx=-1, save_image_=False,
+                                       performance_boosting=True)
+            for i, (name, _, _) in enumerate(chains):
+                self.EXP_NAME = name
+                save(name, x0[i * m:(i + 1) * m])
+                save_vk(i)
+        else:
+            for i, (name, start, vk) in enumerate(chains):
+                self.EXP_NAME = name
+                self._phase = "x-space guidance: batch-2 U-Net forwards"
+                xt_list = [start.clone()]
+                for _ in range(self.x_space_guidance_num_step):
+                    xt_list.append(self.x_space_guidance(xt_list[-1], t_idx=self.edit_t_idx, vk=vk, single_edit_step=self.x_space_guidance_edit_step))
+                xt = torch.cat(xt_list, dim=0)
+                self._phase = "DDIM decode of the edited latents: U-Net forwards"
+                self.DDIMforwardsteps(xt[::int(xt.size(0) / vis_num)], t_start_idx=self.edit_t_idx, t_end_idx=-1, performance_boosting=True)
+                save_vk(i)
+        self._phase = _EditBase._phase
+        return out

@@ -6,12 +6,15 @@ For two k-dimensional subspaces of R^N with principal angles theta_1 >= ... >= t
 algebra per basis and per pair; see ``include/dpb.h`` for the method, the limits and the NaN rule.  Held to ``scipy.linalg.subspace_angles`` in
 float64 at 1e-6 rad per angle -- small angles included, which the usual fp32 ``qr`` / ``svdvals`` / ``arccos`` route misses by 1e-4 .. 7e-4 rad.
 
-Distances only: no exponential / logarithm maps, no Frechet means, no parallel transport.  There is no CPU fallback: inputs live on a HIP device.
+``transport_directions`` is the direction arithmetic of ``run_edit_parallel_transport`` (``csrc/transport.hip``): a source direction of h-space
+expressed in a target's basis and carried to the target's x-space, fp64 on the h-space side, a fixed-order fp32 stream on the x-space side.
+
+No exponential / logarithm maps and no Frechet means.  There is no CPU fallback: inputs live on a HIP device.
 """
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional, Tuple
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -135,6 +138,56 @@ def subspace_angles_and_distance(A: torch.Tensor, B: Optional[torch.Tensor] = No
                 raise ValueError(f"degenerate bases (a zero row, or rows dependent beyond a condition number of ~1e5): indices {rows}")
             raise ValueError(f"degenerate bases (a zero row, or rows dependent beyond a condition number of ~1e5): indices {rows} of A, {cols} of B")
     return theta, dist
+
+
+def transport_directions(u_src: torch.Tensor, u_dst: torch.Tensor, vT_dst: torch.Tensor, pcs: Optional[Sequence[int]] = None,
+                         check: bool = True) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The directions of run_edit_parallel_transport (dpb_transport_directions): the source's h-space direction u_src[pc], expressed in each
+    target's h-space basis and carried to x-space through that target's own u / vT pairing.
+
+    Layout: ROWS.  u_src [k, N_h]; u_dst [D, k, N_h] with vT_dst [D, k, N_x], or one target as u_dst [k, N_h] with vT_dst [k, N_x].  The saved files
+    hold ``u-`` as [N_h, k] columns and ``vT-`` as [k, N_x] rows: pass ``u.t()`` (any strides; inputs are made contiguous fp32).  Rows need not be
+    normalised.  pcs: the components of the source to transport, entries in [0, k) in any order (None: all k).
+
+    Returns vk [D, P, N_x] (unit norm), coef [D, P, k] with coef[d, p] = Uhat_d^T uhat_src[pcs[p]], and coef_norm [D, P] = ||coef[d, p]||_2: the share
+    of the source direction that the target's h-tangent space holds (its cosine to that space only when Uhat_d is orthonormal).  The result of a
+    target is bitwise the same alone and inside any stack.  check: raise ValueError naming the degenerate (target, pc) pairs -- a zero or non-finite
+    source row, a zero target row, a target exactly orthogonal to the direction; one host sync -- False returns their NaNs.  No CPU fallback."""
+    lib = L.load()
+    u_src = _device_f32(u_src, "u_src")
+    if u_src.dim() != 2 or u_src.numel() == 0:
+        raise ValueError(f"u_src must be one basis [k, N_h] of rows, got {tuple(u_src.shape)}")
+    u_dst = _stack(u_dst, "u_dst").to(u_src.device)
+    vT_dst = _stack(vT_dst, "vT_dst").to(u_src.device)
+    k, nh = u_src.shape
+    d, nx = vT_dst.shape[0], vT_dst.shape[2]
+    if tuple(u_dst.shape) != (d, k, nh) or vT_dst.shape[1] != k:
+        raise ValueError(f"u_src is [k = {k}, N_h = {nh}]: u_dst must be [D, {k}, {nh}] and vT_dst [D, {k}, N_x] with the same D, got "
+                         f"{tuple(u_dst.shape)} and {tuple(vT_dst.shape)}")
+    if k > MAX_RANK:
+        raise ValueError(f"k = {k} rows per basis exceeds the supported rank {MAX_RANK}")
+    pcs = list(range(k)) if pcs is None else [int(p) for p in pcs]
+    if not 1 <= len(pcs) <= k or any(p < 0 or p >= k for p in pcs):
+        raise ValueError(f"pcs must hold 1 .. k = {k} entries in [0, {k}), got {pcs}")
+    npc = len(pcs)
+    with torch.cuda.device(u_src.device):
+        st = C.c_void_p(torch.cuda.current_stream(u_src.device).cuda_stream)
+        need = int(lib.dpb_transport_scratch_bytes(d, npc, k, nh, nx))
+        if need == 0:
+            raise L.DpbError(f"dpb_transport_directions does not take D = {d}, P = {npc}, k = {k}, N_h = {nh}, N_x = {nx}")
+        scratch = torch.empty(need, dtype=torch.uint8, device=u_src.device)
+        vk = torch.empty(d, npc, nx, dtype=torch.float32, device=u_src.device)
+        coef = torch.empty(d, npc, k, dtype=torch.float32, device=u_src.device)
+        coef_norm = torch.empty(d, npc, dtype=torch.float32, device=u_src.device)
+        L.check(lib.dpb_transport_directions(u_src.data_ptr(), u_dst.data_ptr(), vT_dst.data_ptr(), (C.c_int32 * npc)(*pcs), npc, d, k, nh, nx,
+                                             vk.data_ptr(), coef.data_ptr(), coef_norm.data_ptr(), scratch.data_ptr(), need, st))
+    if check:
+        bad = torch.isnan(coef_norm) | torch.isnan(vk).any(dim=2)
+        if bool(bad.any()):
+            pairs = [(int(i), pcs[int(j)]) for i, j in bad.nonzero().tolist()]
+            raise ValueError("degenerate transport (a zero or non-finite source row, a zero target row, or a target exactly orthogonal to the "
+                             f"direction): (target, pc) pairs {pairs}")
+    return vk, coef, coef_norm
 
 
 def subspace_angles(A: torch.Tensor, B: Optional[torch.Tensor] = None, max_bytes: Optional[int] = None) -> torch.Tensor:

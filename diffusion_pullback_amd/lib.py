@@ -101,6 +101,9 @@ SYMBOLS = {
     "dpb_cross_gram": (_I, [_P, _P, _P, _I, _I, _L, _P]),
     "dpb_subspace_angles_scratch_bytes": (C.c_size_t, [_I, _I, _I, _L]),
     "dpb_subspace_angles": (_I, [_P, _P, _I, _I, _I, _L, _P, _P, _P, C.c_size_t, _P]),
+    # parallel transport of directions between tangent spaces (geometry.transport_directions): pcs is a host int32 array
+    "dpb_transport_scratch_bytes": (C.c_size_t, [_I, _I, _I, _L, _L]),
+    "dpb_transport_directions": (_I, [_P, _P, _P, C.POINTER(C.c_int32), _I, _I, _I, _L, _L, _P, _P, _P, _P, C.c_size_t, _P]),
 }
 
 _lib = None

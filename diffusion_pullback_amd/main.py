@@ -17,7 +17,12 @@ SD, over MS-COCO captions, which are not available offline): here --pca_rank, --
 ``--run_tangent_space_distance True --distance_space x|h`` computes what those files are saved for: the principal angles and the geodesic
 distance ||theta||_2 between every two sampled tangent spaces (x: the spans of vT, h: the spans of u), on the GPU (geometry.py).  It honours --h_t_list,
 --num_local_basis, --pca_rank, --op, --block_idx, --edit_prompt, --fix_xt and --fix_t exactly as the sampling job does, reads that job's files (a missing
-one is an error: nothing is sampled silently) and writes tangent_space_distance-<space>-....pt and .png next to them.  Distances only: no means, no transport.
+one is an error: nothing is sampled silently) and writes tangent_space_distance-<space>-....pt and .png next to them.  Distances only: no means.
+``--run_edit_parallel_transport True --sample_idx_0 i --sample_idx_1 j`` (the reference's flags, define_argparser.py:117-119; unconditional nets only, with
+--is_stable_diffusion models it is an error) edits sample j along the principal directions of sample i carried over by parallel transport between their
+local tangent spaces at --h_t, and sample i along its own, at --edit_t; --sample_idx_1_list 1,2,3 (new) serves several targets in one call.  It honours
+--op, --block_idx, --pca_rank (the reference's call site fixes 50), --vis_num, --vis_num_pc and --trajectory_batch, reads the u- / vT- files of the sampling job when they are there and
+computes the missing ones together.
 """
 from __future__ import annotations
 
@@ -65,6 +70,8 @@ _FLAGS = [  # (name, type, default) -- define_argparser.py:20-110, live path onl
     ("fix_xt", str2bool, False), ("fix_t", str2bool, False),
     # new: principal angles / geodesic distances between the sampled tangent spaces (geometry.py); x = the spans of vT, h = the spans of u
     ("run_tangent_space_distance", str2bool, False),
+    # define_argparser.py:117-119: the parallel-transport edit job (unconditional nets); sample_idx_1_list is new: several targets in one call
+    ("run_edit_parallel_transport", str2bool, False), ("sample_idx_0", int, 0), ("sample_idx_1", int, 0), ("sample_idx_1_list", str, ""),
     # new
     ("pca_rank", int, 2), ("op", str, "mid"), ("block_idx", int, 0), ("vis_num", int, 4), ("vis_num_pc", int, 2), ("weights", str, ""),
     ("net_scale", str, "full"), ("vae", str, "none"), ("text_encoder", str, "none"), ("tokenizer_dir", str, ""),
@@ -96,6 +103,13 @@ def parse_args(argv=None):
         p.error("--h_t_list must be comma-separated numbers, e.g. 0.8,0.5")
     if args.fix_xt and args.fix_t:
         p.error("--fix_xt and --fix_t exclude each other")
+    try:
+        args.sample_idx_1_values = [int(v) for v in args.sample_idx_1_list.split(",") if v.strip()] or [args.sample_idx_1]
+    except ValueError:
+        p.error("--sample_idx_1_list must be comma-separated integers, e.g. 1,2,3")
+    if args.run_edit_parallel_transport and "stable-diffusion" in args.model_name:
+        p.error("--run_edit_parallel_transport is a job of the unconditional nets only: the reference has no Stable Diffusion parallel transport "
+                "(its run_edit_parallel_transport belongs to EditUncondDiffusion)")
     if extra:
         print(f"note: ignoring flags of experiments outside the pullback path: {extra}")
     return args
@@ -159,6 +173,12 @@ def tangent_space_group(args) -> int:
     return max(1, min(pairs, args.memory_bound, TANGENT_BUDGET // max(args.pca_rank, 1)))
 
 
+def transport_group(args) -> int:
+    """samples whose local bases run_edit_parallel_transport computes together: the source and its targets, bounded like tangent_space_group"""
+    samples = len(set([args.sample_idx_0] + list(args.sample_idx_1_values)))
+    return max(1, min(samples, args.memory_bound, TANGENT_BUDGET // max(args.pca_rank, 1)))
+
+
 def build_unet(args) -> PullbackUNet:
     from . import weights as W
     small = args.net_scale != "full"
@@ -172,6 +192,14 @@ def build_unet(args) -> PullbackUNet:
     if getattr(args, "run_sample_encoder_local_tangent_space_zt", False):       # the group of (latent, h_t) pairs: batch and tangents for all of it
         max_batch = max(max_batch, tangent_space_group(args))
         max_rank = max(max_rank, tangent_space_group(args) * args.pca_rank)
+    if getattr(args, "run_edit_parallel_transport", False):
+        # the basis group: (1 + targets) samples x pca_rank tangents, in groups when that exceeds the budget ...
+        max_batch = max(max_batch, transport_group(args))
+        max_rank = max(max_rank, transport_group(args) * args.pca_rank)
+        if getattr(args, "trajectory_batch", 0) > 1:
+            # ... and the chains together: 2 * vis_num_pc per target and for the source, 2 rows each per guidance step, vis_num + 1 decode states each
+            n = 2 * args.vis_num_pc * (1 + len(args.sample_idx_1_values))
+            max_batch = max(max_batch, min(args.trajectory_batch, 2 * n), min(args.trajectory_batch, n * (args.vis_num + 1)))
     if args.is_stable_diffusion:
         cfg = cf.sd_config_for(args.model_name)           # SD-v1.x or SD-2(.1)-base; anything else raises
         if small:
@@ -274,6 +302,11 @@ def main(argv=None):
             edit.run_tangent_space_distance(edit_prompt=args.edit_prompt, **kw)
         else:
             edit.run_tangent_space_distance(fix_xt=args.fix_xt, fix_t=args.fix_t, **kw)
+    if args.run_edit_parallel_transport:                                         # main.py:36-40 (which fixes op='mid', block_idx=0, vis_num=4, vis_num_pc=2, pca_rank=50)
+        edit.run_edit_parallel_transport(sample_idx_0=args.sample_idx_0,
+                                         sample_idx_1=args.sample_idx_1_values if args.sample_idx_1_list else args.sample_idx_1, op=args.op,
+                                         block_idx=args.block_idx, vis_num=args.vis_num, vis_num_pc=args.vis_num_pc, pca_rank=args.pca_rank,
+                                         h_t=args.h_t)
     if args.run_ddim_forward:
         edit.run_DDIMforward(num_samples=5)
     if args.run_ddim_inversion:

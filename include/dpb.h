@@ -212,7 +212,7 @@ int dpb_local_pca_sample(dpb_engine* e, const float* x /*[1][N_in]*/, float t, c
 /* ---- principal angles and geodesic distances between subspaces (additive to ABI version 1; engine-independent) ------------------------
  * The analysis the bases (u, s, vT) of run_sample_encoder_local_tangent_space_zt are saved for (src/modules/edit.py:310-383, :1517-1599; the
  * reference has no code for it): the principal angles theta_1..theta_k between two k-dimensional subspaces of R^N and the geodesic distance
- * ||theta||_2 on the Grassmannian.  Distances only: no exponential / logarithm maps, no means, no parallel transport.
+ * ||theta||_2 on the Grassmannian.  Distances only: no exponential / logarithm maps, no means (transport of directions: the next section).
  *
  * dpb_cross_gram: G[i][j] = sum_n X[i][n] Y[j][n].  X [Ra][N], Y [Rb][N] fp32, G [Ra][Rb] FP64 (row stride Rb).  The fp32 inputs are widened on
  * load and multiplied on the fp64 matrix cores (v_mfma_f64_16x16x4_f64), so every product is exact and only the fp64 accumulation rounds.  Y = NULL
@@ -245,6 +245,31 @@ int dpb_cross_gram(const float* X, const float* Y /*or NULL: Y = X*/, double* G,
 size_t dpb_subspace_angles_scratch_bytes(int Ba, int Bb, int k, int64_t N);   /* 0 when invalid */
 int dpb_subspace_angles(const float* A, const float* B /*or NULL: self mode*/, int Ba, int Bb, int k, int64_t N, float* theta, float* dist,
                         void* scratch, size_t scratch_bytes, void* hip_stream);
+
+/* ---- parallel transport of directions between tangent spaces (additive to ABI version 1; engine-independent) ---------------------------
+ * The direction arithmetic of run_edit_parallel_transport (src/modules/edit.py:892-909): the source sample's h-space direction u_src[pc] is
+ * expressed in a target's h-space basis and carried to x-space through that target's own pairing of u and vT rows,
+ *   c[d][p][q] = <uhat_dst[d][q], uhat_src[pcs[p]]>,   w[d][p] = sum_q c[d][p][q] vhat_dst[d][q],   vk[d][p] = w[d][p] / ||w[d][p]||_2,
+ * where uhat / vhat are the rows scaled to unit length (the rows need NOT come normalised: u is J V_prev).
+ * Inputs, device fp32 row stacks: u_src [k][N_h]; u_dst [D][k][N_h]; vT_dst [D][k][N_x]; pcs: a HOST list of P entries in [0, k), in any order
+ * (it travels as a kernel argument).  Outputs, device fp32: vk [D][P][N_x] (unit norm), coef [D][P][k] = c, coef_norm [D][P] = ||c||_2 -- the share of
+ * the source direction that the target's h-tangent space holds; it is the cosine of the angle between the direction and that space ONLY when the
+ * rows of uhat_dst[d] are orthonormal (for a skewed basis it can exceed 1).
+ * Method: the overlaps u_dst u_src^T through dpb_cross_gram (exact products, fp64 accumulation); the row sums of squares of u_src, u_dst and vT_dst
+ * in fp64 by a fixed-order reduction; c in fp64, rounded once for coef, and divided by ||vT_dst[d][q]|| in fp64 and rounded once for the streaming
+ * kernel; that kernel reads vT_dst once and accumulates w in fp32 with one fma per term in the order q = 0 .. k-1 (so |w - exact| obeys the
+ * k-term dot-product bound); ||w||^2 in fp64 from per-workgroup partial sums of the w written, added in a fixed order; one in-place scaling.
+ * Degenerate rule: a zero or non-finite source row pcs[p] makes coef, coef_norm and vk of every (d, p) NaN; a zero or non-finite row of u_dst[d] or
+ * vT_dst[d], or c[d][p] = 0 exactly, makes them NaN for that (d, p) (w = 0 with c != 0 leaves vk[d][p] NaN alone).  No other entry is affected.
+ * Reproducibility and batch invariance: no atomics, every sum one fixed chain that depends on k, N_h and N_x only; the results of target d are
+ * bitwise a function of that target's rows, u_src, pcs and the sizes -- the same in a call of its own and inside any stack, whatever the alignment.
+ * Limits: 1 <= k <= 128, 1 <= P <= k, 1 <= D <= 65535, N_h, N_x >= 1 (16-byte accesses when the length is a multiple of 4 and the pointers are 16-byte
+ * aligned), 64-bit offsets.  scratch: 256-byte aligned device memory of scratch_bytes >= dpb_transport_scratch_bytes(D, P, k, N_h, N_x); the size is
+ * checked.  Outputs must not alias inputs or scratch.  No device allocation, no host synchronisation.  Errors via dpb_last_error. */
+size_t dpb_transport_scratch_bytes(int D, int P, int k, int64_t N_h, int64_t N_x);   /* 0 when invalid */
+int dpb_transport_directions(const float* u_src, const float* u_dst, const float* vT_dst, const int32_t* pcs /*host*/, int P, int D, int k,
+                             int64_t N_h, int64_t N_x, float* vk, float* coef, float* coef_norm, void* scratch, size_t scratch_bytes,
+                             void* hip_stream);
 
 /* n_iters full power iterations with no host synchronisation: V <- orth(J^T J V), U = J V_prev, for all B samples
  * of the last dpb_primal together (independent bases, one shared weight stream; B*k <= max_tangents).
