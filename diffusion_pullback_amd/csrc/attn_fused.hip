@@ -1035,10 +1035,11 @@ struct CrossArgs {
   int L, Lk, Lkp, C, Ck, Cx, Cy, H, kps, a_is_v, accumulate, xcd;
   int primal;                         // 1: Y = P V (the forward pass itself: no X, no delta); BT may be null -- B^T is then built in LDS from the row tile
   float scale, c_in, c_out;
+  float* Pst;                         // primal only, may be null: fp32 probabilities [B][L][H][80] for the folded route (keys >= Lk: 0; keys >= 80 not stored)
 };
 constexpr int XKEYS = 96, XLDT = XKEYS + 4;
 
-template <int D, int FL>
+template <int D, int FL, bool PST = false>   // PST: the primal launch that also stores its probabilities (a.Pst); every other launch is the PST = false kernel
 __global__ __launch_bounds__(256) void attn_cross_kernel(CrossArgs a) {
   using F = FA<D>;
   __shared__ __attribute__((aligned(16))) bf16 sm[2 * XKEYS * F::LDR + F::DO * XLDT];
@@ -1129,6 +1130,16 @@ __global__ __launch_bounds__(256) void attn_cross_kernel(CrossArgs a) {
       delta += t[kb][r];
     }
   delta += __shfl_xor(delta, 32, 64);
+  if constexpr (PST) {                                  // a lane holds keys kb*32 + 8g + 4 lhi .. + 3 of its query: one 16-byte store each
+    float* pr = a.Pst + (((long)b * a.L + q) * a.H + h) * 80;
+#pragma unroll
+    for (int kb = 0; kb < 3; ++kb)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const int key = kb * 32 + 8 * g + 4 * lhi;
+        if (key < 80) *reinterpret_cast<float4*>(pr + key) = make_float4(s[kb][g * 4], s[kb][g * 4 + 1], s[kb][g * 4 + 2], s[kb][g * 4 + 3]);
+      }
+  }
   f32x16 acc[F::ND];
 #pragma unroll
   for (int d = 0; d < F::ND; ++d)
@@ -1192,12 +1203,13 @@ int launch_attn_cross(const CrossAttnArgs& f, int nt, hipStream_t st) {
   a.L = f.L; a.Lk = f.Lk; a.Lkp = f.Lkp; a.C = f.C; a.Ck = f.Ck; a.Cx = f.Cx; a.Cy = f.Cy; a.H = f.H; a.kps = f.kps;
   a.a_is_v = f.adjoint; a.accumulate = f.accumulate; a.scale = f.scale; a.xcd = 0;   // every block loads its own small K/V tile: nothing to share
   a.c_in = f.adjoint ? 1.f : f.scale; a.c_out = f.adjoint ? f.scale : 1.f;
-  a.primal = f.primal;
+  a.primal = f.primal; a.Pst = f.primal ? f.Pstash : nullptr;
   if (f.primal) { a.a_is_v = 0; a.c_in = 1.f; a.c_out = 1.f; a.accumulate = 0; }
   const int waves = f.L >= 128 ? 4 : f.L / 32;
   dim3 grid(f.L / (waves * 32), nt * f.H);
   if (!head_dim_ok(f.d)) { set_error("cross attention: head dim %d unsupported", f.d); return -1; }
-  DPB_ATT_DISPATCH(f.d, f.fl, DPB_LAUNCH((attn_cross_kernel<D, FL>), grid, dim3(waves * 64), 0, st, a));
+  if (a.Pst) DPB_ATT_DISPATCH(f.d, f.fl, DPB_LAUNCH((attn_cross_kernel<D, FL, true>), grid, dim3(waves * 64), 0, st, a));
+  else DPB_ATT_DISPATCH(f.d, f.fl, DPB_LAUNCH((attn_cross_kernel<D, FL>), grid, dim3(waves * 64), 0, st, a));
   DPB_CHECK(hipGetLastError());
   return 0;
 }

@@ -51,6 +51,13 @@ struct AttnPlan {            // per attention op, persisted from the primal pass
   bool kv_const = false, fused = false, cross = false;   // cross: constant K/V, one-launch tangent / adjoint (attn_cross_kernel)
   int oq = 0, ok = 0, ov = 0;                      // column offsets of q / k / v inside their buffers (fused QKV projection)
   size_t P = 0, PT = 0, KT = 0, VT = 0, QT = 0, stats = 0;   // offsets
+  // Folded route of a text-conditioned layer (fold_route below): K and V are constants of the sample, so to_q -> attention -> to_out is two products,
+  // z Gt^T with the softmax Jacobian as its epilogue (EPI_XATT) and w Fk^T (+ residual); the adjoint is the mirror image with F and Gk.
+  bool fold_ok = false;                            // the tape has the shape the route needs (found at create)
+  bool fold_live = false;                          // the last stashing primal built the operands below
+  int q_op = -1, o_op = -1;                        // the to_q and to_out products around the op
+  size_t Gt = 0, Gk = 0, F = 0, Fk = 0, Pf = 0;    // offsets: Gt, F [H 128][C]; Gk, Fk [C][H 80] (16 bit); Pf fp32 probabilities [Lq][H][80]
+  const char* gA = nullptr;                        // adjoint pass: the cotangent of to_out's output as conv_adj(to_out) found it (the residual swap may rename it)
 };
 
 struct Op {
@@ -63,6 +70,7 @@ struct Op {
   int geglu_prev = -1;       // CONV (FF-out): the GEGLU op that produces its input                                   -> fused adjoint epilogue
   int ln_next = -1;          // CONV: the LayerNorm op that reads its 320-wide output  -> tangent: product + LayerNorm tangent in one launch (EPI_LN_TAN)
   int ln_prev = -1;          // CONV: the LayerNorm op whose output is its only input -> adjoint: product + LayerNorm adjoint in one launch (EPI_LN_ADJ)
+  int fold_plan = -1, fold_role = 0;   // CONV next to a text-conditioned attention op that can take the folded route: its plan; 1 = to_q, 2 = to_out
 };
 
 }  // namespace dpb
@@ -233,6 +241,23 @@ void prof_close(dpb_engine* e, int idx) {
 int g_geglu_fwd = getenv("DPB_GEGLU_FWD") ? atoi(getenv("DPB_GEGLU_FWD")) : 1;
 // one-launch forward of the text-conditioned attention layers (A/B switch: DPB_CROSS_PRIMAL=0, dpb_debug_set("cross_primal", 0): the materialised path)
 int g_cross_primal = getenv("DPB_CROSS_PRIMAL") ? atoi(getenv("DPB_CROSS_PRIMAL")) : 1;
+// Folded text-conditioned attention (A/B switch: DPB_CROSS_FOLD, dpb_debug_set("cross_fold", v)): 0 off; 1 the rule of fold_route; 2 wherever the tape
+// allows it (tests at C = 320); v > 2: the rule, for layers of at least v channels (one level at a time)
+int g_cross_fold = getenv("DPB_CROSS_FOLD") ? atoi(getenv("DPB_CROSS_FOLD")) : 1;
+// THE route rule.  The layer is on the one-launch cross route with its to_q / to_out neighbours private to it (fold_ok, found at create); one sample
+// (Gt, Gk, F, Fk are operands of the sample); and the folded products cost no more MACs per row than the chain they replace:
+// (128 + 80) H C against 2 C^2 + 4 * 96 C.  SD-1.x (8 heads): C >= 640; SD-2.x (H = C / 64) and every C < 640: never.
+bool fold_route(const dpb_engine* e, const AttnPlan& p) {
+  if (!g_cross_fold || !p.fold_ok || e->cur_batch != 1 || !g_cross_primal) return false;
+  if (g_cross_fold == 2) return true;
+  const long H = p.heads, C = H * p.d;
+  return 208 * H * C <= 2 * C * C + 384 * C && (g_cross_fold == 1 || C >= g_cross_fold);
+}
+// ... and whether a tangent / adjoint pass takes it: the operands are there and the pass runs the whole chain (seeded upstream of to_q, ending at
+// or after to_out), so neither the q tangent nor the attention output is anybody's input or result
+bool fold_on(const dpb_engine* e, const Pass& ps, const AttnPlan& p) {
+  return p.fold_live && fold_route(e, p) && e->producer[ps.src] < p.q_op && e->producer[ps.tap] >= p.o_op;
+}
 int gemm(dpb_engine* e, GemmArgs a, bool can_defer = false) {
   // a product parked by an EARLIER gemm() of the same op (run_op has flushed everything older) must be reduced before this one reuses the slabs
   if (e->pend.on)
@@ -293,6 +318,12 @@ int conv_fwd(dpb_engine* e, const Op& op, const Pass& ps, int n) {
     g.R = mode == 0 ? primal_ptr(e, ps, d.res) : e->T(d.res);
     g.ldr = e->bufs[d.res].C;
   }
+  if (mode == 1 && op.fold_role && fold_on(e, ps, e->plans[op.fold_plan])) {
+    const AttnPlan& p = e->plans[op.fold_plan];
+    if (op.fold_role == 1) return 0;               // to_q: folded into Gt, the q tangent is never formed
+    g.A = e->ws + e->S1; g.lda = 80 * p.heads;     // to_out: second folded product, w Fk^T (+ residual), K = 80 H
+    g.B = e->ws + p.Fk; g.K = g.ldb = 80 * p.heads;
+  }
   if (mode == 1 && op.ln_next >= 0 && g_ln_fuse) {   // the LayerNorm that reads this product's output: its tangent leaves the same launch
     const dpb_op_desc& ld = e->ops[op.ln_next].d;
     GemmArgs f = g;
@@ -351,6 +382,16 @@ int conv_adj(dpb_engine* e, const Op& op, const Pass& ps, int n) {
     g.ldb = g.K;
     g.ldc = bi.C;
     const int gather = d.ip[9];
+    if (op.fold_role && fold_on(e, ps, e->plans[op.fold_plan])) {
+      AttnPlan& p = e->plans[op.fold_plan];
+      if (op.fold_role == 2) {                     // to_out: folded into F -- attn_adjoint reads this op's cotangent itself; G(d.in0) stays unwritten
+        p.gA = e->G(d.out);
+        e->ginit[d.in0] = 1;
+        goto residual;
+      }
+      g.A = e->ws + e->S1; g.lda = 80 * p.heads;   // to_q: second folded product, w Gk^T (the softmax scale is in Gk), K = 80 H
+      g.B = e->ws + p.Gk; g.K = g.ldb = 80 * p.heads;
+    }
     // the LayerNorm that wrote this product's input: its adjoint in the epilogue (K <= 1024: beyond -- the FF-in adjoint, K = 8 C -- the
     // row-complete tile's one block per CU loses more in the K loop than the fusion saves: g_ln_fuse bit 1 forces it for A/Bs)
     // (not when the input is the seed: the LayerNorm / GEGLU that wrote it is upstream of the pass, its cotangent G(seed) is the result)
@@ -645,6 +686,47 @@ int head_transpose(dpb_engine* e, const AttnPlan& p, const void* in, int ld, voi
   return launch_transpose(e->dtype, in, out, Z, p.heads, (long)L * ld, p.d, L, p.d, ld, Lp, (long)p.d * Lp, e->stream);
 }
 
+// The operands of the folded route for the one sample of the pass, from its K, V (primal, 77 live rows) and the two weights; four batched products
+// over the heads, fp32 accumulation, one rounding each.  The pad rows 77..127 of a head window of Gt / F and the pad columns 77..79 of Gk / Fk are
+// never written: they are the zeros dpb_engine_set_workspace left (and EPI_XATT does not look at what a pad row produced).
+//   Gt[h][j][c] = Gk[c][80 h + j] = scale K_h[j] . Wq[h d .., c]      F[h][j][c] = Fk[c][80 h + j] = V_h[j] . Wo[c, h d ..]
+int fold_build(dpb_engine* e, const AttnPlan& p, const AttnPtrs& x, float scale) {
+  const int H = p.heads, C = H * p.d, W = 80 * H;
+  const void* WqT = e->ops[p.q_op].d.w[1];         // [C][C]: row = input channel, column = q channel
+  const void* Wo = e->ops[p.o_op].d.w[0];          // [C][C]: row = output channel, column = attention channel
+  char* ws = e->ws;
+  for (int which = 0; which < 2; ++which) {
+    const void* kv = which ? x.V : x.K; const int ldkv = which ? x.ldv : x.ldk;
+    const void* w = which ? Wo : WqT;
+    const float alpha = which ? 1.f : scale;
+    GemmArgs t;                                    // key-major: [H 128][C]
+    side_rows(t, SIDE_A, kv, ldkv, p.Lk, p.d);
+    side_rows(t, SIDE_B, w, C, C, p.d);
+    set_side(t, SIDE_C, ws + (which ? p.F : p.Gt), C, 0, 128L * C, 1);
+    dims(t, p.Lk, C, p.d, 1, H, alpha);
+    if (int r = gemm(e, t)) return r;
+    GemmArgs k;                                    // channel-major: [C][80 H]
+    side_rows(k, SIDE_A, w, C, C, p.d);
+    side_rows(k, SIDE_B, kv, ldkv, p.Lk, p.d);
+    set_side(k, SIDE_C, ws + (which ? p.Fk : p.Gk), W, 0, 80, 1);
+    dims(k, C, p.Lk, p.d, 1, H, alpha);
+    if (int r = gemm(e, k)) return r;
+  }
+  return 0;
+}
+
+// first folded product of a pass: X [nt rows][C] against the key-major operand B, softmax Jacobian in the epilogue -> e->S1 [nt rows][80 H]
+int fold_product1(dpb_engine* e, const AttnPlan& p, const void* X, int ldx, size_t B, int nt) {
+  const int H = p.heads, C = H * p.d;
+  GemmArgs g;
+  g.A = X; g.lda = ldx; g.B = e->ws + B; g.ldb = C;
+  g.C = e->ws + e->S1; g.ldc = 80 * H;
+  g.M = nt * p.Lq; g.N = 128 * H; g.K = C;
+  g.epi = EPI_XATT; g.xatt_p = (const float*)(e->ws + p.Pf); g.xatt_h = H; g.xatt_lk = p.Lk;
+  g.rows_per_sample = p.Lq; g.epi_kps = nt / e->cur_batch;
+  return gemm(e, g);
+}
+
 int attn_primal(dpb_engine* e, const Op& op, const Pass& ps, int B) {
   const dpb_op_desc& d = op.d;
   const AttnPlan& p = e->plans[op.attn];
@@ -665,10 +747,19 @@ int attn_primal(dpb_engine* e, const Op& op, const Pass& ps, int B) {
     CrossAttnArgs f;
     fill_cross(e, p, x, f, 1, scale, nullptr, nullptr, x.ldq, x.O, x.ldo);
     f.primal = 1;
+    // the folded route's stash, when the pass keeps one and runs the whole chain: the fp32 probabilities from this launch, the operands after it
+    const bool fold = stash && fold_route(e, p) && e->producer[ps.tap] >= p.o_op;
+    if (fold) f.Pstash = (float*)(ws + p.Pf);
     const int r = attn_launch(e, p, 10, 2, B, 2, [&] { return launch_attn_cross(f, B, e->stream); });
     if (r || !stash) return r;
+    // (the head transposes stay: the one-launch route runs on the same stash when the switch is flipped between passes)
     if (int r2 = head_transpose(e, p, x.V, x.ldv, ws + p.VT, B, p.Lk, p.Lkp)) return r2;
-    return head_transpose(e, p, x.K, x.ldk, ws + p.KT, B, p.Lk, p.Lkp);
+    if (int r2 = head_transpose(e, p, x.K, x.ldk, ws + p.KT, B, p.Lk, p.Lkp)) return r2;
+    if (fold) {
+      if (int r2 = fold_build(e, p, x, scale)) return r2;
+      e->plans[op.attn].fold_live = true;
+    }
+    return 0;
   }
   GemmArgs g;   // S = scale * Q K^T
   side_rows(g, SIDE_A, x.Q, x.ldq, p.Lq, p.d);
@@ -694,7 +785,7 @@ int attn_primal(dpb_engine* e, const Op& op, const Pass& ps, int B) {
   return 0;
 }
 
-int attn_tangent(dpb_engine* e, const Op& op, int nt) {
+int attn_tangent(dpb_engine* e, const Op& op, const Pass& ps, int nt) {
   const dpb_op_desc& d = op.d;
   const AttnPlan& p = e->plans[op.attn];
   const int H = p.heads, kps = nt / e->cur_batch;
@@ -708,6 +799,10 @@ int attn_tangent(dpb_engine* e, const Op& op, int nt) {
     f.dQ = t.Q; f.dK = t.K; f.dV = t.V; f.dO = t.O;
     // dS (2 products), dP V, P dV + the recomputed scores: 5 L x L x d products
     return attn_launch(e, p, 8, 5, nt, attn_jvp_block_waves(p.d, p.Lq, nt * H), [&] { return launch_attn_jvp_fused(f, nt, e->stream); });
+  }
+  if (p.cross && fold_on(e, ps, p)) {   // folded: w = P o (z Gt^T - delta), to_q skipped before, to_out multiplies by Fk after
+    const int zb = e->ops[p.q_op].d.in0;
+    return fold_product1(e, p, e->T(zb), e->bufs[zb].C, p.Gt, nt);
   }
   if (p.cross) {   // constant K/V: dO = [P o (scale dQ K^T - delta)] V in one launch
     CrossAttnArgs f;
@@ -741,7 +836,7 @@ int attn_tangent(dpb_engine* e, const Op& op, int nt) {
   return gemm(e, o);
 }
 
-int attn_adjoint(dpb_engine* e, const Op& op, int nt) {
+int attn_adjoint(dpb_engine* e, const Op& op, const Pass& ps, int nt) {
   const dpb_op_desc& d = op.d;
   const AttnPlan& p = e->plans[op.attn];
   const int H = p.heads, kps = nt / e->cur_batch;
@@ -765,6 +860,11 @@ int attn_adjoint(dpb_engine* e, const Op& op, int nt) {
     // query-major: scores, gP, gQ (3); key-major: scores^T, gP^T, gV, gK (4)
     if (int r = attn_launch(e, p, 9, 7, nt, attn_adj_route_bits(p.d, p.Lq, kps, nt), [&] { return launch_attn_adj_fused(f, nt, e->stream); })) return r;
     e->ginit[d.in0] = e->ginit[d.in1] = e->ginit[d.in2] = 1;
+    return 0;
+  }
+  if (p.cross && fold_on(e, ps, p)) {   // folded: w = P o (g F^T - delta) from to_out's cotangent; to_q's adjoint multiplies by Gk (G(q) stays unwritten)
+    if (int r = fold_product1(e, p, p.gA, e->bufs[e->ops[p.o_op].d.out].C, p.F, nt)) return r;
+    e->ginit[d.in0] = 1;
     return 0;
   }
   if (p.cross) {   // constant K/V: gQ (+)= scale [P o (gO V^T - delta)] K in one launch
@@ -832,7 +932,7 @@ int run_op(dpb_engine* e, const Op& op, const Pass& ps, int n) {
     case DPB_OP_CONCAT: return concat_run(e, op, ps, n);
     case DPB_OP_RESAMPLE: return resample_run(e, op, ps, n);
     case DPB_OP_ATTENTION:
-      return mode == MODE_PRIMAL ? attn_primal(e, op, ps, n) : mode == MODE_TANGENT ? attn_tangent(e, op, n) : attn_adjoint(e, op, n);
+      return mode == MODE_PRIMAL ? attn_primal(e, op, ps, n) : mode == MODE_TANGENT ? attn_tangent(e, op, ps, n) : attn_adjoint(e, op, ps, n);
     case DPB_OP_SILU: {
       if (mode != MODE_PRIMAL) return fail("SILU / quick-GELU ops are primal only (time-embedding path, text encoder)");
       const Buf& b = e->bufs[op.d.in0];
@@ -1062,6 +1162,23 @@ int dpb_engine_create(const dpb_net_desc* net, dpb_engine** out) {
         if (cd.kind == DPB_OP_CONV && cd.ip[9] == DPB_GATHER_NONE && cd.in0 == d.out) e->ops[ci].geglu_prev = (int)j;
       }
     }
+    // Text-conditioned attention between a to_q and a to_out product that are its own (q read by nothing else, the output read by nothing else,
+    // the three ops adjacent on the tape, whole [rows][C] buffers): the structural half of fold_route; the one-launch cross route is checked with the plan below
+    for (size_t j = 1; j + 1 < e->ops.size(); ++j) {
+      const dpb_op_desc& d = e->ops[j].d;
+      if (d.kind != DPB_OP_ATTENTION || e->ops[j].is_const) continue;
+      AttnPlan& p = e->plans[e->ops[j].attn];
+      const int C = p.heads * p.d;
+      if (!p.kv_const || p.causal || e->dtype == DT_F32 || p.oq != 0 || e->bufs[d.in0].C != C || e->bufs[d.out].C != C || p.Lk > 80) continue;
+      const dpb_op_desc &qd = e->ops[j - 1].d, &od = e->ops[j + 1].d;
+      auto plain = [&](const dpb_op_desc& c) {
+        return c.kind == DPB_OP_CONV && c.ip[9] == DPB_GATHER_NONE && c.ip[6] == 1 && c.ip[2] == C && c.ip[5] == C && c.rowbias < 0 && c.w[1] &&
+               e->bufs[c.in0].kind == DPB_BUF_ACT && e->bufs[c.out].kind == DPB_BUF_ACT;
+      };
+      if (!plain(qd) || qd.out != d.in0 || qd.res >= 0 || uses[d.in0] != 1 || e->ops[j - 1].is_const) continue;
+      if (!plain(od) || od.in0 != d.out || uses[d.out] != 1) continue;
+      p.q_op = (int)j - 1; p.o_op = (int)j + 1; p.fold_ok = true;
+    }
     e->skip.assign(e->ops.size(), 0);
   }
   // ---------------- memory plan
@@ -1089,6 +1206,16 @@ int dpb_engine_create(const dpb_net_desc* net, dpb_engine** out) {
       p.cross = !p.causal && cross_attention_supported(e->dtype, p.d, p.Lq, p.Lk, p.kv_const) && !getenv("DPB_NO_CROSS_ATTN") &&
                 e->bufs[d.in1].C == e->bufs[d.in2].C;
       if (!p.fused) p.P = take((size_t)e->maxB * H * p.Lq * p.Lkp * es);
+      p.fold_ok = p.fold_ok && p.cross;
+      if (p.fold_ok) {                             // the folded route's operands and probabilities, for the one sample it serves; its scratch is S1
+        const size_t C = H * p.d;
+        p.Gt = take(H * 128 * C * es); p.F = take(H * 128 * C * es);
+        p.Gk = take(C * 80 * H * es); p.Fk = take(C * 80 * H * es);
+        p.Pf = take((size_t)p.Lq * H * 80 * sizeof(float));
+        s1 = std::max(s1, (size_t)e->maxT * H * p.Lq * 80 * es);
+        e->ops[p.q_op].fold_plan = e->ops[p.o_op].fold_plan = op.attn;
+        e->ops[p.q_op].fold_role = 1; e->ops[p.o_op].fold_role = 2;
+      }
       p.VT = take((size_t)e->maxB * H * p.d * p.Lkp * es);
       p.KT = take((size_t)e->maxB * H * p.d * p.Lkp * es);
       if (!p.fused) s1 = std::max(s1, (size_t)e->maxT * H * p.Lq * p.Lkp * es);
@@ -1247,6 +1374,7 @@ static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const 
   const int last = e->producer[upto_buf];
   const int seed_op = f.seed >= 0 ? e->producer[f.seed] : -1;
   e->primal_last = -1;
+  for (auto& p : e->plans) p.fold_live = false;    // the folded operands belong to the primal pass that built them
   std::fill(e->skip.begin(), e->skip.end(), 0);
   for (int i = 0; i <= last; ++i) {
     if (e->skip[i]) continue;                      // (forward only: a GEGLU applied by the epilogue of the FF-in product)
@@ -1761,6 +1889,7 @@ int dpb_debug_set(const char* key, int value) {
   else if (!strcmp(key, "lazy_reduce")) { g_lazy_reduce = value; return 0; }
   else if (!strcmp(key, "ln_fuse")) { g_ln_fuse = value; return 0; }
   else if (!strcmp(key, "cross_primal")) { g_cross_primal = value; return 0; }
+  else if (!strcmp(key, "cross_fold")) { g_cross_fold = value; return 0; }
   else if (!strcmp(key, "geglu_fwd")) { g_geglu_fwd = value; return 0; }
   else if (!strcmp(key, "iter_alias")) { g_iter_alias = value; return 0; }
   else return fail("unknown debug key %s", key);
@@ -1778,6 +1907,7 @@ int dpb_debug_gemm_plan(int dtype, int M, int N, int K, int conv_hw, int conv_ci
   a.zeros = dummy;
   if (slab_bytes > 0) { a.slab = (float*)dummy; a.slab_bytes = (size_t)slab_bytes; }
   a.epi = epilogue;
+  if (epilogue == EPI_XATT) { a.xatt_p = (const float*)dummy; a.xatt_h = N / 128; a.xatt_lk = 77; a.ldc = 80 * a.xatt_h; a.C = dummy; }   // N = 128 heads
   if (conv_hw > 0) {                           // 3x3, stride 1, pad 1 on conv_hw x conv_hw images of conv_cin channels
     if (conv_cin <= 0 || K != 9 * conv_cin || M % (conv_hw * conv_hw)) return fail("conv plan: K must be 9*cin and M whole images");
     a.gather = GATHER_CONV; a.H = a.W = a.Ho = a.Wo = conv_hw; a.Cin = conv_cin; a.KS = 3; a.stride = 1; a.pad = 1; a.lda = conv_cin;
@@ -1786,6 +1916,20 @@ int dpb_debug_gemm_plan(int dtype, int M, int N, int K, int conv_hw, int conv_ci
   if (!pl.row) return -1;
   *kind = pl.kind; *tile = pl.tile; *splitk = pl.splitk;
   return 0;
+}
+
+int dpb_debug_cross_fold(const dpb_engine* e, int index, int64_t* info) {
+  if (!e || !info) return fail("null argument");
+  int n = 0;
+  for (size_t i = 0; i < e->ops.size(); ++i) {
+    if (e->ops[i].d.kind != DPB_OP_ATTENTION || !e->plans[e->ops[i].attn].fold_ok) continue;
+    if (n++ != index) continue;
+    const AttnPlan& p = e->plans[e->ops[i].attn];
+    const int64_t v[12] = {(int64_t)i, p.fold_live, p.heads * p.d, p.heads, p.Lq, p.Lk, (int64_t)p.Gt, (int64_t)p.Gk, (int64_t)p.F, (int64_t)p.Fk, (int64_t)p.Pf, (int64_t)e->S1};
+    memcpy(info, v, sizeof(v));
+    return 0;
+  }
+  return fail("dpb_debug_cross_fold: the tape has %d layers that can take the folded route, index %d", n, index);
 }
 
 int dpb_engine_stats(const dpb_engine* e, int64_t* launches, double* gemm_flops, double* gemm_bytes) {

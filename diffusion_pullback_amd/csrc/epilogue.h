@@ -12,6 +12,10 @@
 //   EPI_GEGLU_FWD  forward pass only (dpb_forward): y = a*gelu(g) from the FF-in product, bitwise the unfused product + GEGLU kernel
 //   EPI_LN_TAN     (row-complete tile: BN = N, epilogue_ln below) h = acc (+R) -> C, and the LayerNorm tangent of h at the primal row -> C2
 //   EPI_LN_ADJ     (row-complete tile) the LayerNorm adjoint of acc (= cotangent of the LayerNorm output) (+)-> C
+//   EPI_XATT       the softmax Jacobian of a text-conditioned attention layer whose constant K / V are folded into the weights (engine.cpp,
+//                  fold_*): a 128-column tile holds one head's dS = z G_h (tangent) or gP = gO F_h (adjoint) for the 77 keys; with the
+//                  primal probabilities P (fp32, p.xatt_p) the wave pair writes w = P o (acc - sum_j P_j acc_j), 80 columns per head,
+//                  compactly at C[m][80 h + j] -- the K operand of the second folded product.  No transcendental.
 #pragma once
 #include "kernels.h"
 
@@ -234,6 +238,54 @@ __device__ __forceinline__ void epilogue_slab(const GemmArgs& p, bf16* C, const 
         for (int e = 0; e < 8; ++e) o[e] = p.alpha * (da[e] * ap[e] + dg[e] * gp[e]);
         store8_at<FL>(cb, C + (long)m * p.ldc + ((n0 + wx * WN) >> 1) + c8 * 8, o);
       }
+    }
+    return;
+  }
+  if constexpr (EPI == EPI_XATT) {
+    // the wave pair (wx = 0, 1) holds 32 rows x 128 columns = one head's window of acc = z G_h (tangent) or gO F_h (adjoint); 16 rows per wave, 8 rows
+    // at a time, 8 lanes per row: lane c8 holds columns 8 c8 .. 8 c8 + 7 of the first half and, for c8 < 2, columns 64 + 8 c8 .. of the second (the
+    // rest of the window is padding).  A column the probabilities leave out (P = 0: j >= xatt_lk) contributes nothing whatever the product holds there.
+    static_assert(WN == 64, "EPI_XATT: 128-column tiles in the wave-pair form");
+    const float* s0 = smem_f + (wave & ~1) * 32 * SLD;
+    const float* s1 = s0 + 32 * SLD;
+    const int Hh = p.xatt_h, h = n0 >> 7, c8 = lane & 7, rg = lane >> 3;
+    const bool hi = c8 < 2;
+    float pa[2][8], pb[2][8];
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {                           // the probabilities do not depend on the product: their loads go out before the staged values are read
+      const int mc = min(mrow0 + wx * 16 + it * 8 + rg, p.M - 1);
+      const int smp = mc / p.rows_per_sample, l = mc - smp * p.rows_per_sample;
+      const float* pp = p.xatt_p + (((long)(smp / p.epi_kps) * p.rows_per_sample + l) * Hh + h) * 80 + c8 * 8;
+      Vec<float>::load(pp, pa[it]); Vec<float>::load(pp + 4, pa[it] + 4);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) pb[it][e] = 0.f;
+      if (hi) { Vec<float>::load(pp + 64, pb[it]); Vec<float>::load(pp + 68, pb[it] + 4); }
+    }
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int row = wx * 16 + it * 8 + rg, m = mrow0 + row;
+      float a8[8], b8[8];
+      Vec<float>::load(s0 + row * SLD + c8 * 8, a8); Vec<float>::load(s0 + row * SLD + c8 * 8 + 4, a8 + 4);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) b8[e] = 0.f;
+      if (hi) { Vec<float>::load(s1 + row * SLD + c8 * 8, b8); Vec<float>::load(s1 + row * SLD + c8 * 8 + 4, b8 + 4); }
+      float ds = 0.f;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        if (c8 * 8 + e >= p.xatt_lk) a8[e] = 0.f;
+        if (64 + c8 * 8 + e >= p.xatt_lk) b8[e] = 0.f;
+        ds += pa[it][e] * a8[e] + pb[it][e] * b8[e];
+      }
+      const float delta = seg8_sum(ds);                        // whole 8-lane groups share a row: the shuffles stay inside the group
+      if (m >= p.M) continue;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {                            // (the padding columns as +0, not as the -0 a zero probability times a negative gives)
+        a8[e] = c8 * 8 + e < p.xatt_lk ? pa[it][e] * (a8[e] - delta) : 0.f;
+        b8[e] = 64 + c8 * 8 + e < p.xatt_lk ? pb[it][e] * (b8[e] - delta) : 0.f;
+      }
+      bf16* cp = C + (long)m * p.ldc + h * 80 + c8 * 8;
+      store8_at<FL>(cb, cp, a8);
+      if (hi) store8_at<FL>(cb, cp + 64, b8);
     }
     return;
   }

@@ -545,6 +545,13 @@ static bool wants_halo(int dtype, const GemmArgs& a) {
 // tile, weights-resident kernel) -- 16-bit, one operand pair -- or nullptr for the register-staged kernel (pick_reg_tile).
 static const GemmTile* pick_async_tile(int dtype, const GemmArgs& a) {
   if (dtype == DT_F32 || a.A2 || !a.zeros) return nullptr;
+  // the folded text-attention epilogue lives in two tiles of the BK = 64 ring, the half tile while 128 x 128 tiles would leave
+  // every CU at most one block (the 8x8 and 16x16 levels at k = 5: 24 / 80 tiles, unsplit -- the heuristic would hand them to the 64x64 ring)
+  if (a.epi == EPI_XATT) {
+    const GemmTile* f = gemm_tile_forced(forced_code(a));          // (a forced code that names one of the two is honoured: tests of the 128 x 128 form at few rows)
+    if (f && (f->flags & TILE_XATT)) return f;
+    return &kGemmTiles[gemm_tile_count(kGemmTiles[T_R64_S2], a) < 256 ? T_R64_HALF : T_R64_S2];
+  }
   if (const GemmTile* f = gemm_tile_forced(forced_code(a))) {
     // a forced code: its tile, or that row's substitute for a product the tile does not take.  A code that names no row (and the halo code on a
     // product the halo kernel does not take) falls through to the heuristic -- with the halo kernel off (wants_halo)
@@ -605,6 +612,9 @@ int gemm_epi_supported(int dtype, const GemmArgs& a) {
            a.ln_x && a.ln_gamma && !a.A2 && !a.bias && !a.rowbias && a.alpha == 1.f && (a.epi == EPI_LN_ADJ || (a.C2 && !a.accumulate)) && (!a.R || a.ldr % 8 == 0);
   }
   if (dtype == DT_F32 || a.Z1 * a.Z2 != 1 || a.gather != GATHER_NONE || a.N % 128 || a.M <= 0) return 0;
+  if (a.epi == EPI_XATT)                                         // one 128-column tile per head, 80 stored columns each; nothing else in the epilogue
+    return a.xatt_p && a.xatt_h > 0 && a.N == 128 * a.xatt_h && a.ldc == 80 * a.xatt_h && a.xatt_lk > 0 && a.xatt_lk <= 80 && a.K % 8 == 0 && a.zeros && !a.A2 &&
+           !a.bias && !a.rowbias && !a.R && !a.accumulate && a.alpha == 1.f && a.rows_per_sample > 0 && a.epi_kps > 0 && !((uintptr_t)a.C & 15);
   if (a.epi == EPI_GEGLU_ADJ && a.N % 64) return 0;
   const GemmTile* t = pick_async_tile(dtype, a);
   if (!t || !(t->flags & TILE_GEGLU) || t->bn % 128) return 0;

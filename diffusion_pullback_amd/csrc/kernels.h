@@ -12,7 +12,7 @@ namespace dpb {
 // C[z][m][n] = alpha * sum_k A[z][m][k] * B[z][n][k]  (+bias[n]) (+rowbias[sample(m)][n]) (+R[z][m][n]) (+C if accumulate)
 // A: plain rows (lda) or gathered NHWC pixels (conv).  B is always [N][K], K contiguous.
 enum { GATHER_NONE = 0, GATHER_CONV = 1, GATHER_CONVT = 2, GATHER_UPCONV = 3 };
-enum { EPI_PLAIN = 0, EPI_GEGLU_TAN = 1, EPI_GEGLU_ADJ = 2, EPI_LN_TAN = 3, EPI_LN_ADJ = 4, EPI_GEGLU_FWD = 5 };   // fused epilogues of the ring GEMMs (epilogue.h)
+enum { EPI_PLAIN = 0, EPI_GEGLU_TAN = 1, EPI_GEGLU_ADJ = 2, EPI_LN_TAN = 3, EPI_LN_ADJ = 4, EPI_GEGLU_FWD = 5, EPI_XATT = 6 };   // fused epilogues of the ring GEMMs (epilogue.h)
 struct GemmArgs {
   const void* A = nullptr; const void* B = nullptr; void* C = nullptr; const void* R = nullptr;
   const float* bias = nullptr;
@@ -46,6 +46,10 @@ struct GemmArgs {
   // EPI_LN_ADJ adds the LayerNorm adjoint of the product (the cotangent of the LayerNorm OUTPUT) to C.  ln_x: primal LayerNorm input [prows][N]
   // (row m belongs to primal row ((m / rows_per_sample) / epi_kps) * rows_per_sample + m % rows_per_sample), ln_gamma fp32 [N]
   const void* ln_x = nullptr; const float* ln_gamma = nullptr; float ln_eps = 1e-5f; void* C2 = nullptr;
+  // folded text-attention epilogue (EPI_XATT, 128-column tiles of gemm_ring64.hip, no split-K): one 128-column tile is one head's scores against the
+  // folded operand (xatt_lk live columns, the rest of the window padding); with the primal probabilities xatt_p fp32 [prows][xatt_h][80] (row
+  // indexing as hprim) the tile leaves as w = P o (acc - sum_j P_j acc_j), columns j < 80 stored compactly at C[m][80 h + j] (ldc = 80 xatt_h)
+  const float* xatt_p = nullptr; int xatt_h = 0, xatt_lk = 0;
   int fl = 0;                         // 16-bit flavour of the specialised kernels: 0 bf16, 1 f16 (filled in by launch_gemm)
   int order = 0;                      // block processing order per XCD: 0 A-major, 1 B-major (weight-heavy); filled in by launch_gemm
 };
@@ -61,6 +65,7 @@ enum : unsigned {
   TILE_EPI_N256 = 32, // fused epilogues need N % 256 == 0
   TILE_NOSPLIT = 64,  // one block per CU by construction: the heuristic never splits K (a forced split count is honoured)
   TILE_NOSLAB = 128,  // no split-K path at all: one K range per block whatever is forced
+  TILE_XATT = 256,    // built with the folded text-attention epilogue (EPI_XATT, plain rows)
 };
 enum GemmTileId { T_REG64 = 0, T_REG128, T_R32_S4, T_R32_S3, T_R32_S2, T_R32_TALL, T_R32_64, T_R32_64B, T_R64_S3, T_R64_TALL, T_R64_S4, T_R64_S2, T_R64_TALL8,
                   T_R64_TALL8_S2, T_R64_256, T_R64_LN, T_R64_HALF, T_R64_HALF_S2, T_R64_HALFN, T_P8, T_WRES, T_HALO, GEMM_TILES, T_NONE = -1 };
@@ -87,12 +92,12 @@ inline constexpr GemmTile kGemmTiles[GEMM_TILES] = {
     {FAM_RING64,   512, 512,   128, 128, 3, 4,    4,    TILE_ANY | TILE_GEGLU,                                         T_NONE},   // 96 KiB ring, 1 block/CU
     {FAM_RING64,   513, 513,   256, 128, 3, 4,    4,    TILE_ANY | TILE_GEGLU,                                         T_NONE},   // 144 KiB
     {FAM_RING64,   514, 514,   128, 128, 4, 4,    4,    TILE_ANY | TILE_GEGLU,                                         T_NONE},
-    {FAM_RING64,   515, 515,   128, 128, 2, 4,    4,    TILE_ANY | TILE_GEGLU,                                         T_NONE},   // 2 blocks/CU: the default ring
+    {FAM_RING64,   515, 515,   128, 128, 2, 4,    4,    TILE_ANY | TILE_GEGLU | TILE_XATT,                                      T_NONE},   // 2 blocks/CU: the default ring
     {FAM_RING64,   516, 516,   256, 128, 3, 8,    4,    TILE_ANY | TILE_GEGLU,                                         T_NONE},   // 64x64 wave tiles, one shared B tile
     {FAM_RING64,   517, 517,   256, 128, 2, 8,    4,    TILE_ANY | TILE_GEGLU,                                         T_NONE},   // 96 KiB
     {FAM_RING64,   518, 518,   256, 256, 2, 8,    6,    TILE_GEGLU | TILE_EPI_N256 | TILE_NOSPLIT,                     T_R64_S2}, // 64x128 wave tiles, 128 KiB ring: half the L2->LDS bytes per flop of 128x128; plain rows only
     {FAM_RING64,   520, 0,     128, 320, 2, 4,    4,    TILE_LN | TILE_NOSLAB,                                         T_NONE},   // row-complete N = 320 tile, fused LayerNorm epilogue
-    {FAM_RING64,   521, 521,   64,  128, 3, 4,    4,    TILE_CONV,                                                     T_R64_S2}, // half tiles for launches of <= 256 tiles: 72 KiB ring, 2 blocks/CU (also as an implicit-GEMM convolution)
+    {FAM_RING64,   521, 521,   64,  128, 3, 4,    4,    TILE_CONV | TILE_XATT,                                         T_R64_S2}, // half tiles for launches of <= 256 tiles: 72 KiB ring, 2 blocks/CU (also as an implicit-GEMM convolution)
     {FAM_RING64,   522, 522,   64,  128, 2, 4,    4,    0,                                                             T_R64_S2}, // 48 KiB ring: 3 blocks/CU
     {FAM_RING64,   523, 523,   128, 64,  3, 4,    4,    0,                                                             T_R64_S2},
     {FAM_P8,       530, 530,   256, 256, 2, 8,    11,   TILE_ANY | TILE_CIN64 | TILE_GEGLU | TILE_EPI_N256 | TILE_NOSPLIT, T_R64_S2}, // 8-phase ping-pong loop, 256x256x64
@@ -110,6 +115,7 @@ constexpr bool gemm_tile_builds(const GemmTile& t, int gather, int epi) {
   if (gather == GATHER_UPCONV ? !(t.flags & TILE_UPCONV) : (gather != GATHER_NONE && !(t.flags & TILE_CONV))) return false;
   if (epi == EPI_PLAIN) return !(t.flags & TILE_LN);
   if (gather != GATHER_NONE) return false;
+  if (epi == EPI_XATT) return (t.flags & TILE_XATT) != 0;
   return (t.flags & ((epi == EPI_LN_TAN || epi == EPI_LN_ADJ) ? TILE_LN : TILE_GEGLU)) != 0;
 }
 inline long gemm_tile_count(const GemmTile& t, const GemmArgs& a) { return (long)((a.M + t.bm - 1) / t.bm) * ((a.N + t.bn - 1) / t.bn) * a.Z1 * a.Z2; }
@@ -128,7 +134,7 @@ template <int FAM, typename F, int... Is>
 int gemm_family_launch(const GemmArgs& a, const GemmTile& t, F&& launch, std::integer_sequence<int, Is...>) {
   const int r = gemm_tag_switch<Is...>((int)(&t - kGemmTiles), [&](auto row) {
     return gemm_tag_switch<0, 1>(a.fl, [&](auto fl) {
-      return gemm_tag_switch<EPI_PLAIN, EPI_GEGLU_TAN, EPI_GEGLU_ADJ, EPI_LN_TAN, EPI_LN_ADJ, EPI_GEGLU_FWD>(a.epi, [&](auto epi) {
+      return gemm_tag_switch<EPI_PLAIN, EPI_GEGLU_TAN, EPI_GEGLU_ADJ, EPI_LN_TAN, EPI_LN_ADJ, EPI_GEGLU_FWD, EPI_XATT>(a.epi, [&](auto epi) {
         return gemm_tag_switch<GATHER_NONE, GATHER_CONV, GATHER_CONVT, GATHER_UPCONV>(a.gather, [&](auto gather) {
           constexpr GemmTile R = kGemmTiles[decltype(row)::value];
           if constexpr (R.family == FAM && gemm_tile_builds(R, decltype(gather)::value, decltype(epi)::value)) { launch(row, fl, epi, gather); return 0; }
@@ -253,6 +259,7 @@ struct CrossAttnArgs {
   const void* X = nullptr; void* Y = nullptr;            // dQ -> dO (tangent) or gO -> gQ (adjoint)
   int L = 0, Lk = 0, Lkp = 0, C = 0, Ck = 0, Cx = 0, Cy = 0, H = 0, d = 0, kps = 1, adjoint = 0, accumulate = 0, fl = 0;
   int primal = 0;                                        // 1: the forward pass itself, Y = softmax(scale Q K^T) V (X unused; BT may be null: built in LDS)
+  float* Pstash = nullptr;                               // primal only: also store the fp32 probabilities [B][L][H][80] (keys >= Lk: zeros) for the folded route (EPI_XATT)
   float scale = 1.f;
 };
 int cross_attention_supported(int dtype, int d, int Lq, int Lk, int kv_const);

@@ -363,7 +363,10 @@ int dpb_engine_profile_overhead(const dpb_engine* e, double* bracket_overhead_ms
  * no faster there), "lazy_reduce" (1, default: a split-K product consumed by a one-launch GroupNorm or a
  * LayerNorm leaves its fp32 slabs to that kernel instead of running splitk_reduce_kernel; 0 = always reduce; bitwise the same results),
  * "ln_fuse" (0, default since round 6: separate launches; 1 = LayerNorm in the epilogue of the 320-wide products), "cross_primal" (1, default: the forward of a text-conditioned attention layer is
- * ONE launch; 0 = GEMM + softmax + transpose + GEMM), "geglu_fwd" (1, default: dpb_forward applies GEGLU in the epilogue of the unsplit FF-in products), "iter_alias" (1, default: inside dpb_pullback_iterate the tap's
+ * ONE launch; 0 = GEMM + softmax + transpose + GEMM), "cross_fold" (also DPB_CROSS_FOLD.  The tangent / adjoint of a text-conditioned attention layer with its to_q and
+ * to_out products as TWO products: the sample's constant K / V are multiplied into the weights by the stashing primal pass, the softmax Jacobian is the epilogue of the
+ * first product.  1, default: where the folded products cost no more MACs than the chain -- 208 heads C <= 2 C^2 + 384 C, one sample; 0 = off; 2 = wherever the tape allows it;
+ * v > 2 = as 1 for layers of at least v channels), "geglu_fwd" (1, default: dpb_forward applies GEGLU in the epilogue of the unsplit FF-in products), "iter_alias" (1, default: inside dpb_pullback_iterate the tap's
  * tangent passes from the tangent to the adjoint pass on the device, U is written by the last iteration only; 0 = fp32 round trip through U every iteration; bitwise equal).
  * Environment, read once per process (tuning / ablation only): DPB_GEMM_OVERRIDE="MxNxK:gather=code/split,..." forces
  * kernel and split count per product shape; DPB_P8 (0: no 8-phase tile), DPB_WRES (0: no weights-resident kernel), DPB_WRES_MIN_M, DPB_TILE256, DPB_CONV_HALO, DPB_SPLITK_TARGET, DPB_GEMM_ORDER, DPB_GN_FUSED, DPB_GN_BLOCKS,
@@ -372,6 +375,13 @@ int dpb_engine_profile_overhead(const dpb_engine* e, double* bracket_overhead_ms
  * eigen-solve of rounds 1-5 for every k <= 56, 2: the round-robin one for every k), DPB_ORTH_BATCH (0: the samples of a batch re-orthonormalised one by one); DPB_GEMM_TRACE=1 prints every
  * product and synchronises after it (debugging). */
 int dpb_debug_set(const char* key, int value);
+
+/* Introspection for the tests of the folded text-conditioned attention route ("cross_fold" below; additive to ABI version 1).  index counts the
+ * attention layers of the tape that CAN take the route (constant K / V on the one-launch cross route, 16-bit engine, to_q and to_out products
+ * private to the layer); past the last one the call fails.  info[12] = {op index, 1 if the last dpb_primal built the folded operands, C, heads,
+ * query rows, keys, and the workspace byte offsets of Gt [heads 128][C], Gk [C][heads 80], F [heads 128][C], Fk [C][heads 80] (engine dtype),
+ * the fp32 probabilities [rows][heads][80] and the scratch [nt rows][heads 80] the first folded product of a pass writes}. */
+int dpb_debug_cross_fold(const dpb_engine* e, int index, int64_t* info);
 
 /* Host-only (no GPU work): the launch plan the GEMM dispatch picks for a product C[M][N] = A[M][K] B[N][K]^T -- plain rows (conv_hw = 0) or
  * a 3x3 / stride 1 / pad 1 convolution on conv_hw x conv_hw images of conv_cin channels (K = 9 conv_cin) -- with `slab_bytes` of split-K
