@@ -2,7 +2,8 @@
 (code 515) computes.  With profiling on, each launch is bracketed with the profile kind of the tile the dispatch planned: the `big` column of
 dpb_engine_profile_dump must be the kind include/dpb.h documents for the forced code -- the label bench.py's roofline sorts launches by -- and
 primal, tangent and cotangent must equal the code-515 run bit for bit (same K16 MFMA sequence per output element; the halo-tile convolution
-accumulates chunk-major: 2e-3 relative, as in test_gpu_parity.py)."""
+accumulates chunk-major: 2e-3 relative, as in test_gpu_parity.py).  Code 515 itself, like every other forced code, is pinned to an fp64 reference in
+tests/test_gpu_product_ops.py."""
 import csv
 
 import pytest
