@@ -127,10 +127,12 @@ __global__ __launch_bounds__(64) void eig_kernel(const double* Gp, int nbg, doub
       }
   }
   if (r == 0) {
-    for (int i = 0; i < k; ++i) order[i] = i;
-    for (int i = 0; i < k; ++i)          // selection sort, descending eigenvalue
-      for (int j = i + 1; j < k; ++j)
-        if (A[order[j]][order[j]] > A[order[i]][order[i]]) { int t = order[i]; order[i] = order[j]; order[j] = t; }
+    for (int i = 0; i < k; ++i) {        // insertion sort, descending eigenvalue; ties by index, as eig_par_kernel (an exchange sort displaces them)
+      const double v = A[i][i];
+      int j = i;
+      for (; j > 0 && A[order[j - 1]][order[j - 1]] < v; --j) order[j] = order[j - 1];
+      order[j] = i;
+    }
   }
   __syncthreads();
   if (r < k) {

@@ -149,6 +149,9 @@ int dpb_vjp(dpb_engine* e, int tap_buf, const float* U, int nt, float* W);
  * conv[0] = ||V - Vprev||_2, conv[1] = max(|V - Vprev| - 1e-5|V|).  scratch: device memory of >= dpb_orth_scratch_bytes(k, N) bytes (Gram
  * matrix and distance partials per block, added in block order: the result is bitwise reproducible).  V may alias Vprev (in place:
  * every element of Vprev is read by the thread that overwrites it, after the Gram pass has finished with it).
+ * Domain: this is the Gram method (eigen-decomposition of W W^T in fp64), which squares the condition number: V and s have full fp32 accuracy up
+ * to cond(W) ~ 1e4; beyond that the trailing vectors degrade (tests/test_gpu_orth.py).  Rows of W that are exactly orthogonal to all
+ * others are not mixed; equal singular values among them come out in input order.
  * Replaces: torch.linalg.svd + dist/allclose inputs, utils.py:799-806.  Engine-independent. */
 int dpb_orth(const float* W, const float* Vprev, float* V, float* s, float* conv, void* scratch, int k, int64_t N,
              void* hip_stream);
