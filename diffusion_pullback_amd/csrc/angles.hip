@@ -219,6 +219,14 @@ __global__ __launch_bounds__(256) void angles_prep_kernel(double* Dg, int* flags
   }
 }
 
+// the whitening of n bases in place (also the Frechet mean's, frechet.hip): Dg [n][k][k] Gram blocks -> W, flags [n]; 1 <= k <= ORTH_MAX_RANK
+void launch_angles_prep(double* Dg, int* flags, int n, int k, hipStream_t st) {
+  if (k <= 16) DPB_LAUNCH((angles_prep_kernel<16>), dim3(n), dim3(256), 0, st, Dg, flags, k);
+  else if (k <= 32) DPB_LAUNCH((angles_prep_kernel<32>), dim3(n), dim3(256), 0, st, Dg, flags, k);
+  else if (k <= 64) DPB_LAUNCH((angles_prep_kernel<64>), dim3(n), dim3(256), 0, st, Dg, flags, k);
+  else DPB_LAUNCH((angles_prep_kernel<ORTH_MAX_RANK>), dim3(n), dim3(256), 0, st, Dg, flags, k);
+}
+
 // ------------------------------------------------------------------------------------------------------------ per pair: angles
 // Workgroups walk the pairs p = blockIdx.x, blockIdx.x + gridDim.x, ...; pair (i, j) = (p / Bb, p % Bb).  T = W_i G_ij and M = T W_j^T go through this
 // workgroup's two k x k slots of global scratch (L2), S = I - M M^T lives in LDS, its eigenvalues come from a two-sided Jacobi iteration in the round-robin
@@ -415,14 +423,8 @@ int launch_subspace_angles(const float* A, const float* B, long Ba, long Bb, int
   // ... and each basis's own k x k block, one batch entry per basis, into the slot its whitening matrix W will take
   gram_launches(A, A, Wa, k, k, N, k, (int)Ba, (long)k * N, (long)k * N, (long)k * k, 1, st);
   if (!self) gram_launches(B, B, Wb, k, k, N, k, (int)Bb, (long)k * N, (long)k * N, (long)k * k, 1, st);
-  auto prep = [&](double* W, int* f, int n) {
-    if (k <= 16) DPB_LAUNCH((angles_prep_kernel<16>), dim3(n), dim3(256), 0, st, W, f, k);
-    else if (k <= 32) DPB_LAUNCH((angles_prep_kernel<32>), dim3(n), dim3(256), 0, st, W, f, k);
-    else if (k <= 64) DPB_LAUNCH((angles_prep_kernel<64>), dim3(n), dim3(256), 0, st, W, f, k);
-    else DPB_LAUNCH((angles_prep_kernel<ORTH_MAX_RANK>), dim3(n), dim3(256), 0, st, W, f, k);
-  };
-  prep(Wa, fa, (int)Ba);
-  if (!self) prep(Wb, fb, (int)Bb);
+  launch_angles_prep(Wa, fa, (int)Ba, k, st);
+  if (!self) launch_angles_prep(Wb, fb, (int)Bb, k, st);
   const dim3 pg((unsigned)l.nblk);
   if (k <= 16) DPB_LAUNCH((angles_pair_kernel<16, 256>), pg, dim3(256), 0, st, Wa, Wb, fa, fb, Gab, (long)Rb, work, theta, dist, (int)Ba, (int)Bb, k, sf);
   else if (k <= 32) DPB_LAUNCH((angles_pair_kernel<32, 1024>), pg, dim3(1024), 0, st, Wa, Wb, fa, fb, Gab, (long)Rb, work, theta, dist, (int)Ba, (int)Bb, k, sf);

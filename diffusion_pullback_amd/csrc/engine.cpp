@@ -1619,6 +1619,26 @@ int dpb_transport_directions(const float* u_src, const float* u_dst, const float
   return launch_transport_directions(u_src, u_dst, vT_dst, pcs, P, D, k, N_h, N_x, vk, coef, coef_norm, scratch, scratch_bytes, (hipStream_t)stream);
 }
 
+// Frechet (Karcher) mean on the Grassmannian of many local bases, the global basis of run_edit_global_frechet_mean_zt (src/modules/edit.py:951-1246):
+// frechet.hip
+size_t dpb_frechet_scratch_bytes(int B, int k, int64_t N, int max_iter) { return frechet_scratch_bytes(B, k, N, max_iter); }
+
+int dpb_frechet_init(const float* X, int B, int k, int64_t N, int init, int max_iter, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!X || !scratch) return fail("dpb_frechet_init: null argument");
+  return launch_frechet_init(X, B, k, N, max_iter, init, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int dpb_frechet_iterate(int n_iter, double step, double tol, int B, int k, int64_t N, int max_iter, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!scratch) return fail("dpb_frechet_iterate: null argument");
+  return launch_frechet_iterate(B, k, N, max_iter, n_iter, step, tol, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int dpb_frechet_finish(const float* X, float* Y, float* weight, float* theta, double* info, int B, int k, int64_t N, int max_iter, void* scratch,
+                       size_t scratch_bytes, void* stream) {
+  if (!X || !Y || !weight || !theta || !info || !scratch) return fail("dpb_frechet_finish: null argument");
+  return launch_frechet_finish(X, B, k, N, max_iter, Y, weight, theta, info, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
 // The perturbed batch and the sampling loop of the reference's local_pca_zt / local_pca_xt (src/utils/utils.py:916-933;
 // src/models/ddpm/diffusion.py:396-409): noise.hip
 size_t dpb_perturb_scratch_bytes(int B, int64_t n) { return perturb_scratch_bytes(B, n); }

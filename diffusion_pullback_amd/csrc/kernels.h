@@ -349,6 +349,19 @@ size_t subspace_angles_scratch_bytes(long Ba, long Bb, int k, long N);   // 0 wh
 int launch_subspace_angles(const float* A, const float* B, long Ba, long Bb, int k, long N, float* theta, float* dist, void* scratch, size_t scratch_bytes,
                            hipStream_t st);
 
+// per-basis whitening shared by the angles and the Frechet mean: Dg [n][k][k] fp64 (each basis's own Gram block) -> W = L^-1 D^-1/2 in place (lower
+// triangular, W G W^T = I), flags [n] = 1 for a degenerate basis (its slot is then left as it was); one workgroup per basis, k <= ORTH_MAX_RANK
+void launch_angles_prep(double* Dg, int* flags, int n, int k, hipStream_t st);
+
+// ---------------------------------------------------------------- Frechet (Karcher) mean on the Grassmannian of B bases of k rows (frechet.hip): the
+// Riemannian iteration on coefficients against the whitened Gram of all rows; X [B][k][N] fp32, everything between in fp64; see include/dpb.h
+constexpr int FRECHET_MAX_RANK = 64;   // three k x k fp64 matrices (S, its eigenvectors, M_i) of the per-basis log map live in LDS
+size_t frechet_scratch_bytes(long B, int k, long N, long max_iter);   // 0 when invalid
+int launch_frechet_init(const float* X, long B, int k, long N, long max_iter, int init, void* scratch, size_t scratch_bytes, hipStream_t st);
+int launch_frechet_iterate(long B, int k, long N, long max_iter, int n_iter, double step, double tol, void* scratch, size_t scratch_bytes, hipStream_t st);
+int launch_frechet_finish(const float* X, long B, int k, long N, long max_iter, float* Y, float* weight, float* theta, double* info, void* scratch,
+                          size_t scratch_bytes, hipStream_t st);
+
 // ---------------------------------------------------------------- parallel transport of directions between tangent spaces (transport.hip)
 // vk[d][p] = normalise(sum_q c[d][p][q] vhat_dst[d][q]), c[d][p][q] = <uhat_dst[d][q], uhat_src[pcs[p]]> (fp64), coef_norm = ||c||; pcs is a HOST list
 size_t transport_scratch_bytes(long D, int P, int k, long Nh, long Nx);   // 0 when invalid

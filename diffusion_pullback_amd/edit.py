@@ -6,6 +6,7 @@ Mirrors the public surface of the reference's ``modules/edit.py``:
       DDIMforwardsteps :385-482, x_space_guidance :484-502, run_DDIMforward :101-110
   * ``EditUncondDiffusion``  (reference src/modules/edit.py:540-779, :1601-1734)
       run_DDIMinversion :613-678, run_edit_local_encoder_pullback_zt :680-779, run_edit_parallel_transport :782-948,
+      run_edit_global_frechet_mean_zt :951-1246 (its global basis: geometry.frechet_mean),
       run_sample_encoder_local_tangent_space_zt :1517-1599, DDIMforwardsteps :1601-1714, x_space_guidance :1716-1734
 
 Kept from the reference: the step counts (inv_steps-2 inversion steps, ``edit_t_idx`` forward steps,
@@ -78,6 +79,23 @@ def save_distance_plot(dist: torch.Tensor, path: str, dpi=None) -> None:
     plt.close()
 
 
+def save_projection_plot(cu: Optional[torch.Tensor], cv: torch.Tensor, path: str) -> None:
+    """The sorted magnitudes of a direction's coefficients in the local basis, 'u' (h-space; None: there is no h-space direction) and 'v' (x-space):
+    projection_coeff-<EXP_NAME>.png of the global-basis job (edit.py:1168-1172); skipped without matplotlib."""
+    try:
+        import matplotlib
+        matplotlib.use("Agg", force=False)
+        import matplotlib.pyplot as plt
+    except Exception:
+        return
+    for c, label in ((cu, "u"), (cv, "v")):
+        if c is not None:
+            plt.scatter(range(c.numel()), sorted(c.detach().float().abs().cpu().tolist()), label=label)
+    plt.legend()
+    plt.savefig(path, dpi=80)
+    plt.close()
+
+
 def save_vT_visualisation(vT: torch.Tensor, lat_shape, path: str) -> None:
     """vT [k, N_in] shown through the 3 principal channel directions of its pixels, min-max normalised (edit.py:253-263, :359-369)"""
     pix = vT.view(-1, *lat_shape).permute(0, 2, 3, 1).reshape(-1, lat_shape[0]).float()
@@ -126,6 +144,9 @@ class _EditBase(object):
         whenever idx is asked for, as a dataset entry is)"""
         if self.dataset is not None:
             return self.dataset[idx].to(device=self.device, dtype=self.dtype)
+        return self._seeded_latent(idx)
+
+    def _seeded_latent(self, idx):
         g = torch.Generator().manual_seed((int(self.seed) << 20) + int(idx))
         return torch.randn(1, self.c_in, self.image_size, self.image_size, generator=g).to(device=self.device, dtype=self.dtype)
 
@@ -574,12 +595,14 @@ class EditUncondDiffusion(_EditBase):
             save_image((xt / 2 + 0.5).clamp(0, 1), os.path.join(self.result_folder, f"x0_gen-{self.EXP_NAME}.png"), nrow=xt.size(0))
         return xt if return_xt else None
 
-    def _tangent_space_naming(self, op, block_idx, pca_rank, fix_xt=False, fix_t=False):
-        """directory and EXP_NAME(idx, h_t) of the tangent-space files, -fix_xt / -fix_t appended to the directory (edit.py:1547-1550)"""
+    def _tangent_space_naming(self, op, block_idx, pca_rank, fix_xt=False, fix_t=False, dataset_name=None):
+        """directory and EXP_NAME(idx, h_t) of the tangent-space files, -fix_xt / -fix_t appended to the directory (edit.py:1547-1550); dataset_name:
+        another dataset's files (the global-basis job reads the 'Random' ones whatever dataset it edits)"""
         assert (not fix_xt) or (not fix_t)
-        save_dir = os.path.join(self.input_root, f"local_encoder_pullback_uncond-model_{self.model_name}-dataset_{self.dataset_name}-num_steps_{self.for_steps}-pca_rank_{pca_rank}")
+        ds = self.dataset_name if dataset_name is None else dataset_name
+        save_dir = os.path.join(self.input_root, f"local_encoder_pullback_uncond-model_{self.model_name}-dataset_{ds}-num_steps_{self.for_steps}-pca_rank_{pca_rank}")
         save_dir += "-fix_xt" if fix_xt else "-fix_t" if fix_t else ""
-        return save_dir, lambda idx, ht: f"xt-{self.dataset_name}_{idx}-{ht}T-{op}-block_{block_idx}-seed_{self.seed}"
+        return save_dir, lambda idx, ht: f"xt-{ds}_{idx}-{ht}T-{op}-block_{block_idx}-seed_{self.seed}"
 
     @torch.no_grad()
     def run_sample_encoder_local_tangent_space_zt(self, h_t, op, block_idx, pca_rank=50, num_local_basis=100, fix_xt=False, fix_t=False):
@@ -737,14 +760,18 @@ class EditUncondDiffusion(_EditBase):
             pictures += [(f, own, len(chains) - 1) for f, own in zip(vk_files, shown) if own]
         out["names"] = [c[0] for c in chains]
 
-        def save(name, x):
-            save_image((x / 2 + 0.5).clamp(0, 1), os.path.join(self.result_folder, f"x0_gen-{name}.png"), nrow=x.size(0))
-
         def save_vk(after):                                     # edit.py:941-947: once a pc's last chain is done
             for fname, idxs, last in pictures:
                 if last == after:
                     save_image(torch.cat([chains[i][2] for i in idxs], dim=0), os.path.join(self.obs_folder, fname))
 
+        self._run_direction_chains(chains, vis_num, shape, save_vk)
+        return out
+
+    def _run_direction_chains(self, chains, vis_num, shape, after=lambda i: None):
+        """chains: (EXP_NAME, start x_t [1, ...], direction [1, ...]).  Each takes x_space_guidance_num_step guidance steps at edit_t, is subsampled to
+        vis_num states and decoded into x0_gen-<EXP_NAME>.png; after(i) runs once chain i's picture is written.  trajectory_batch > 1: all chains
+        advance together (_guidance_chains_together) and decode in one batch; <= 1: one after another, the reference's order."""
         self._phase = "x-space guidance: batch-2 U-Net forwards"
         if self.trajectory_batch > 1 and chains:
             t = self.scheduler.timesteps[self.edit_t_idx]
@@ -756,8 +783,8 @@ class EditUncondDiffusion(_EditBase):
                                        performance_boosting=True)
             for i, (name, _, _) in enumerate(chains):
                 self.EXP_NAME = name
-                save(name, x0[i * m:(i + 1) * m])
-                save_vk(i)
+                save_image((x0[i * m:(i + 1) * m] / 2 + 0.5).clamp(0, 1), os.path.join(self.result_folder, f"x0_gen-{name}.png"), nrow=m)
+                after(i)
         else:
             for i, (name, start, vk) in enumerate(chains):
                 self.EXP_NAME = name
@@ -768,6 +795,115 @@ class EditUncondDiffusion(_EditBase):
                 xt = torch.cat(xt_list, dim=0)
                 self._phase = "DDIM decode of the edited latents: U-Net forwards"
                 self.DDIMforwardsteps(xt[::int(xt.size(0) / vis_num)], t_start_idx=self.edit_t_idx, t_end_idx=-1, performance_boosting=True)
-                save_vk(i)
+                after(i)
         self._phase = _EditBase._phase
+
+    def global_frechet_mean_paths(self, op="mid", block_idx=0, pca_rank=50, num_local_basis=100, frechet_mean_space="x", h_t=None):
+        """(basis file, info file) of the global basis, in the reference's layout (edit.py:983-987; the directory without the scheduler_name the
+        reference never defines): u- (space h) or v- (space x) + <h_t>T-<op>-block_<b>-seed_<seed>-num_local_basis_<n>.pt holds [N, k] columns"""
+        h_t = self.h_t if h_t is None else h_t
+        save_dir = os.path.join(self.input_root, f"global_frechet_mean_uncond-model_{self.model_name}-dataset_{self.dataset_name}-num_steps_{self.for_steps}-pca_rank_{pca_rank}")
+        name = f"{h_t}T-{op}-block_{block_idx}-seed_{self.seed}-num_local_basis_{num_local_basis}"
+        tag = "u" if frechet_mean_space == "h" else "v"
+        return os.path.join(save_dir, f"{tag}-{name}.pt"), os.path.join(save_dir, f"info-{tag}-{name}.pt")
+
+    @torch.no_grad()
+    def run_edit_global_frechet_mean_zt(self, idx, op="mid", block_idx=0, vis_num=4, vis_num_pc=None, vis_pc_list=None, pca_rank=50, num_local_basis=100,
+                                        local_projection=True, frechet_mean_space="x", h_t=None, frechet_max_iter=1000, frechet_tol=1e-6):
+        """Reference: src/modules/edit.py:951-1246 -- edit sample idx along the directions of a GLOBAL basis, the Frechet mean on the Grassmannian of
+        num_local_basis local tangent spaces at h_t (frechet_mean_space "x": the row spans of vT; "h": the column spans of u).
+
+        Local bases: the xt-Random_<i>-... files of the 'Random' sampling directory (what run_sample_encoder_local_tangent_space_zt writes with
+        --dataset_name Random); the missing ones are computed together through _sample_tangent_spaces on seeded Gaussian latents and saved there.
+        Global basis: geometry.frechet_mean (frechet_max_iter, frechet_tol; not converging is printed, not an error), rows in canonical order -- row 0
+        the direction the local spaces share most -- written as [N, k] columns under global_frechet_mean_paths with an info- file (cost history,
+        weight, theta, iterations) beside it; an existing file is loaded and column-normalised (edit.py:990-1003).  The reference calls a
+        compute_frechet_basis it never defines (pymanopt, 10 000 iterations).
+        Edit: the sample's own local basis (u, vT) at h_t is loaded or computed and saved (edit.py:1087-1133); with local_projection the global
+        direction is projected on it, vk = normalise(vT^T (vT v)) for space x and normalise(vT^T (u^T u_k)) for space h (edit.py:1159-1165), both
+        through geometry.transport_directions; local_projection=False uses v itself and is valid for space x only (for h the reference leaves vk
+        undefined).  Then the x-space-guidance path of the driver's other jobs: chains named xt-<dataset>_<idx>-h_<h_t>T-edit_<edit_t>T-<op>-block_<b>-
+        seed_<seed>-pc_<pc>_{pos,neg}, pictures x0_gen-<name>.png, projection_coeff-<name>.png in the obs folder; the job is skipped when the last
+        pc's _neg picture exists, an experiment when its own does.  trajectory_batch as in run_edit_parallel_transport.  The reference's parallel-h
+        and h_space_guidance branches are not built.  Returns a dict: basis [k, N] (rows), vk [P, N_x], pcs, names, info (None for a loaded basis)."""
+        from . import geometry
+        if frechet_mean_space not in ("x", "h"):
+            raise ValueError(f"frechet_mean_space must be 'x' (the spans of vT) or 'h' (the spans of u), got {frechet_mean_space!r}")
+        if frechet_mean_space == "h" and not local_projection:
+            raise ValueError("local_projection=False is valid for frechet_mean_space 'x' only: an h-space direction reaches x-space through the sample's "
+                             "own local basis (the reference leaves vk undefined there)")
+        h_t = self.h_t if h_t is None else h_t
+        pcs = list(range(vis_num_pc or 0)) if vis_pc_list is None else [int(p) for p in vis_pc_list]
+        exp = lambda pc, tag: f"xt-{self.dataset_name}_{idx}-h_{h_t}T-edit_{self.edit_t}T-{op}-block_{block_idx}-seed_{self.seed}-pc_{pc:0=3d}_{tag}"
+        picture = lambda name: os.path.exists(os.path.join(self.result_folder, f"x0_gen-{name}.png"))
+        if pcs and picture(exp(pcs[-1], "neg")):                                                # edit.py:971-980
+            print("!!!ALREADY DONE EXP :", exp(pcs[-1], "neg"), "!!!")
+            return None
+        self.scheduler.set_timesteps(self.for_steps, device=self.device)
+        h_t_idx = int((self.scheduler.timesteps - h_t * 1000).abs().argmin())
+        load = lambda p: torch.load(p, map_location=self.device).to(torch.float32)
+
+        # the global basis: the saved file, or the mean of the local bases
+        basis_path, info_path = self.global_frechet_mean_paths(op, block_idx, pca_rank, num_local_basis, frechet_mean_space, h_t)
+        os.makedirs(os.path.dirname(basis_path), exist_ok=True)
+        info = None
+        if os.path.exists(basis_path):
+            cols = load(basis_path)
+            basis = (cols / cols.norm(dim=0, keepdim=True)).t().contiguous()                    # edit.py:993, :1002
+        else:
+            local_dir, local_name = self._tangent_space_naming(op, block_idx, pca_rank, dataset_name="Random")
+            pairs = self._tangent_space_pairs(h_t, num_local_basis, local_dir, local_name)
+            pending = [p for p in pairs if not (os.path.exists(p[3][0]) and os.path.exists(p[3][2]))]    # edit.py:1020
+            if pending:
+                os.makedirs(local_dir, exist_ok=True)
+                latent = self._random_latent if self.dataset_name == "Random" else self._seeded_latent
+                self._sample_tangent_spaces(pending, lambda i, ht: self.DDIMforwardsteps(latent(i), t_start_idx=0, t_end_idx=h_t_idx)[:2], None, op,
+                                            block_idx, pca_rank, 1e-4, local_dir, lambda *a: None)
+            with T.phase("Frechet mean of the local bases"):
+                stack = torch.stack([load(p[3][2]) if frechet_mean_space == "x" else load(p[3][0]).t() for p in pairs]).contiguous()
+                basis, info = geometry.frechet_mean(stack, max_iter=frechet_max_iter, tol=frechet_tol)
+            print(f"Frechet mean of {num_local_basis} local bases in {frechet_mean_space}-space: {info['iterations']} steps, gradient norm "
+                  f"{info['grad_norm']:.3e}, cost {info['cost'][0]:.6f} -> {info['cost'][-1]:.6f}" + ("" if info["converged"] else
+                  f" -- NOT converged to {frechet_tol:g} in {frechet_max_iter} steps"))
+            torch.save(basis.t().contiguous().cpu(), basis_path)
+            info = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in info.items()}
+            torch.save(dict(info, space=frechet_mean_space, names=[p[2] for p in pairs]), info_path)
+
+        # the sample, its own local basis at h_t, its state at edit_t
+        xT = self._random_latent(idx) if self.dataset_name == "Random" else self.run_DDIMinversion(idx=idx)      # edit.py:1082-1085
+        own_dir, own_name = self._tangent_space_naming(op, block_idx, pca_rank)
+        files = self._basis_paths(own_dir, own_name(idx, h_t))
+        have = os.path.exists(files[0]) and os.path.exists(files[2])
+        if local_projection and not have:
+            print("!!!SAMPLE LOCAL TANGENT SPACE!!!")
+            at_h = self.DDIMforwardsteps(xT, t_start_idx=0, t_end_idx=h_t_idx)[:2]
+            self._sample_tangent_spaces([(idx, h_t, own_name(idx, h_t), files)], lambda i, ht: at_h, None, op, block_idx, pca_rank, 1e-4, own_dir,
+                                        lambda *a: None)
+            have = True
+        if have:
+            u, vT = load(files[0]), load(files[2])
+            self.last_basis = (u, vT)
+        original_xt = self.DDIMforwardsteps(xT, t_start_idx=0, t_end_idx=self.edit_t_idx)[0].detach()            # edit.py:1136-1137
+        shape = original_xt.shape[1:]
+        out = dict(basis=basis, pcs=pcs, names=[], info=info)
+        if not pcs:
+            return out
+        if local_projection:
+            with T.phase("projection of the global directions on the local basis"):
+                vk = geometry.transport_directions(basis, vT if frechet_mean_space == "x" else u.t(), vT, pcs)[0][0]      # [P, N_x]
+        else:
+            vk = basis[pcs] / basis[pcs].norm(dim=1, keepdim=True)                              # edit.py:1155-1156
+        out["vk"] = vk
+        chains = []
+        for p, pc in enumerate(pcs):
+            for sign, tag in ((1, "pos"), (-1, "neg")):
+                if picture(exp(pc, tag)):                                                       # edit.py:1147-1148
+                    continue
+                chains.append((exp(pc, tag), original_xt, (sign * vk[p]).view(1, *shape)))
+                if local_projection:
+                    uk = sign * basis[pc] if frechet_mean_space == "h" else None
+                    save_projection_plot(None if uk is None else (u / u.norm(dim=0, keepdim=True)).t() @ uk,
+                                         (vT / vT.norm(dim=1, keepdim=True)) @ (sign * vk[p]), os.path.join(self.obs_folder, f"projection_coeff-{exp(pc, tag)}.png"))
+        out["names"] = [c[0] for c in chains]
+        self._run_direction_chains(chains, vis_num, shape)
         return out

@@ -9,19 +9,28 @@ float64 at 1e-6 rad per angle -- small angles included, which the usual fp32 ``q
 ``transport_directions`` is the direction arithmetic of ``run_edit_parallel_transport`` (``csrc/transport.hip``): a source direction of h-space
 expressed in a target's basis and carried to the target's x-space, fp64 on the h-space side, a fixed-order fp32 stream on the x-space side.
 
-No exponential / logarithm maps and no Frechet means.  There is no CPU fallback: inputs live on a HIP device.
+``frechet_mean`` is the Frechet (Karcher) mean on the Grassmannian of many such bases -- the global basis of ``run_edit_global_frechet_mean_zt``
+(``csrc/frechet.hip``): the Riemannian fixed-step iteration on coefficients against the whitened fp64 Gram of all rows, one streaming pass over the
+rows before it and one after it.
+
+There are still no public exponential / logarithm maps: they exist only inside the mean's iteration, on coefficients.  There is no CPU fallback:
+inputs live on a HIP device.
 """
 from __future__ import annotations
 
 import ctypes as C
 from typing import Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import lib as L
 
 MAX_RANK = 128                       # ORTH_MAX_RANK of the library
+FRECHET_MAX_RANK = 64                # FRECHET_MAX_RANK of the library (three k x k fp64 matrices of the log map live in LDS)
 DEFAULT_MAX_BYTES = 4 << 30          # device scratch of one call (the fp64 cross-Gram of the block dominates: 8 (B k)^2 bytes)
+
+DEGENERATE = "degenerate bases (a zero row, or rows dependent beyond a condition number of ~1e5)"
 
 
 def _device_f32(t, what: str) -> torch.Tensor:
@@ -135,8 +144,8 @@ def subspace_angles_and_distance(A: torch.Tensor, B: Optional[torch.Tensor] = No
             rows = bad.all(dim=1).nonzero().flatten().tolist()
             cols = bad.all(dim=0).nonzero().flatten().tolist()
             if self_mode:
-                raise ValueError(f"degenerate bases (a zero row, or rows dependent beyond a condition number of ~1e5): indices {rows}")
-            raise ValueError(f"degenerate bases (a zero row, or rows dependent beyond a condition number of ~1e5): indices {rows} of A, {cols} of B")
+                raise ValueError(f"{DEGENERATE}: indices {rows}")
+            raise ValueError(f"{DEGENERATE}: indices {rows} of A, {cols} of B")
     return theta, dist
 
 
@@ -188,6 +197,81 @@ def transport_directions(u_src: torch.Tensor, u_dst: torch.Tensor, vT_dst: torch
             raise ValueError("degenerate transport (a zero or non-finite source row, a zero target row, or a target exactly orthogonal to the "
                              f"direction): (target, pc) pairs {pairs}")
     return vk, coef, coef_norm
+
+
+def frechet_mean(A: torch.Tensor, init: int = 0, max_iter: int = 1000, tol: float = 1e-6, step: float = 1.0, check_every: int = 16,
+                 max_bytes: Optional[int] = None, check: bool = True) -> Tuple[torch.Tensor, dict]:
+    """The Frechet (Karcher) mean on the Grassmannian of the row spans of A [B, k, N]: the k-dimensional subspace Y minimising
+    (1 / 2B) sum_i ||theta(Y, A_i)||_2^2, by Y <- Exp_Y(step * mean_i Log_Y(A_i)) started at the span of A[init] (dpb_frechet_init / _iterate / _finish;
+    see include/dpb.h for the method and the limits).  Rows need not be orthonormal, only independent; any float dtype is converted to contiguous fp32.
+
+    Returns Y [k, N] fp32 with orthonormal rows in canonical order -- row 0 is the direction the members share most -- and info: ``iterations``
+    (steps taken), ``converged`` (the gradient norm ||mean Log||_F fell below tol), ``grad_norm`` (the last one computed), ``cost`` (fp64 numpy history
+    of (1/2) mean_i sum theta^2, the start included, iterations + 1 entries), ``grad_norm_history``, ``weight`` [k] (fp32, descending: the mean cos^2
+    with which the members hold each row of Y) and ``theta`` [B, k] (fp32: the principal angles of Y to every member, descending).
+
+    The iteration runs in chunks of check_every steps with no host sync inside a chunk; the status read after each chunk is the only sync, and the steps
+    of a chunk after convergence are empty launches.  Not reaching tol within max_iter is not an error: converged is False.  The fp64 Gram of all B k
+    rows must fit max_bytes (8 (B k)^2 bytes plus the coefficient buffers).  check: raise ValueError naming the degenerate bases, or the basis whose
+    largest principal angle to the iterate left the log map's domain (pi/2 - 1e-6); False returns the NaNs and, in info, ``degenerate`` and ``domain``.
+    A cost that rises by more than 1e-12 relative between two steps raises DpbError: the step is too long for this set.  Bitwise reproducible."""
+    lib = L.load()
+    A = _stack(A, "A")
+    b, k, n = A.shape
+    if k > FRECHET_MAX_RANK:
+        raise ValueError(f"k = {k} rows per basis exceeds the rank {FRECHET_MAX_RANK} the Frechet mean supports")
+    if k > n:
+        raise ValueError(f"k = {k} rows per basis exceeds their length N = {n}: they cannot be independent")
+    init, max_iter, check_every = int(init), int(max_iter), int(check_every)
+    if not 0 <= init < b:
+        raise ValueError(f"init = {init} outside [0, B = {b})")
+    if max_iter < 0 or check_every < 1 or not tol >= 0 or not step > 0:
+        raise ValueError(f"max_iter = {max_iter} must be >= 0, check_every = {check_every} >= 1, tol = {tol} >= 0 and step = {step} > 0")
+    max_bytes = DEFAULT_MAX_BYTES if max_bytes is None else int(max_bytes)
+    need = int(lib.dpb_frechet_scratch_bytes(b, k, n, max_iter))
+    if need == 0:
+        raise L.DpbError(f"dpb_frechet does not take B = {b}, k = {k}, N = {n}, max_iter = {max_iter}")
+    if need > max_bytes:
+        raise ValueError(f"the Frechet mean of B = {b} bases of k = {k} rows needs {need} bytes of device scratch (the fp64 Gram of all {b * k} rows), "
+                         f"max_bytes is {max_bytes}")
+    with torch.cuda.device(A.device):
+        st = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
+        scratch = torch.empty(need, dtype=torch.uint8, device=A.device)
+        Y = torch.empty(k, n, dtype=torch.float32, device=A.device)
+        weight = torch.empty(k, dtype=torch.float32, device=A.device)
+        theta = torch.empty(b, k, dtype=torch.float32, device=A.device)
+        info_d = torch.empty(8 + 2 * max_iter + 1 + b, dtype=torch.float64, device=A.device)
+        L.check(lib.dpb_frechet_init(A.data_ptr(), b, k, n, init, max_iter, scratch.data_ptr(), need, st))
+        asked = 0
+        while asked < max_iter:
+            steps = min(check_every, max_iter - asked)
+            L.check(lib.dpb_frechet_iterate(steps, float(step), float(tol), b, k, n, max_iter, scratch.data_ptr(), need, st))
+            asked += steps
+            if int(scratch[:4].view(torch.int32).item()) != 0:          # status.done: the one host sync of the chunk
+                break
+        L.check(lib.dpb_frechet_finish(A.data_ptr(), Y.data_ptr(), weight.data_ptr(), theta.data_ptr(), info_d.data_ptr(), b, k, n, max_iter,
+                                       scratch.data_ptr(), need, st))
+        raw = info_d.cpu().numpy()
+    iters, done, domain = int(raw[0]), int(raw[2]), int(raw[3])
+    cost = raw[8:8 + iters + 1].copy()
+    ghist = raw[8 + max_iter + 1:8 + max_iter + 1 + iters + (1 if done == 1 else 0)].copy()
+    degenerate = np.nonzero(raw[8 + 2 * max_iter + 1:] != 0)[0].tolist()
+    info = {"iterations": iters, "converged": done == 1, "grad_norm": float(ghist[-1]) if len(ghist) else float("nan"), "cost": cost,
+            "grad_norm_history": ghist, "weight": weight, "theta": theta, "degenerate": degenerate, "domain": domain if done == 2 else None}
+    if check:
+        if degenerate:
+            raise ValueError(f"{DEGENERATE}: indices {degenerate}")
+        if done == 2:
+            raise ValueError(f"basis {domain} left the log map's domain at step {iters}: its largest principal angle to the iterate exceeds pi/2 - 1e-6 "
+                             f"(start from another init, or drop the basis)")
+    if raw[5] != 0 and not degenerate:
+        raise L.DpbError("frechet_mean: the iterate lost rank (its Gram has a pivot below 1e-10): use a smaller step")
+    rise = cost[1:] - cost[:-1]
+    worst = np.nonzero(rise > 1e-12 * cost[:-1] + 1e-15 * k)[0]        # (1e-15 k: the rounding floor of k squared angles from fp64 sin^2)
+    if len(worst):
+        j = int(worst[0])
+        raise L.DpbError(f"frechet_mean: the cost rose from {cost[j]!r} to {cost[j + 1]!r} at step {j + 1}: use a smaller step than {step}")
+    return Y, info
 
 
 def subspace_angles(A: torch.Tensor, B: Optional[torch.Tensor] = None, max_bytes: Optional[int] = None) -> torch.Tensor:

@@ -105,6 +105,11 @@ SYMBOLS = {
     # parallel transport of directions between tangent spaces (geometry.transport_directions): pcs is a host int32 array
     "dpb_transport_scratch_bytes": (C.c_size_t, [_I, _I, _I, _L, _L]),
     "dpb_transport_directions": (_I, [_P, _P, _P, C.POINTER(C.c_int32), _I, _I, _I, _L, _L, _P, _P, _P, _P, C.c_size_t, _P]),
+    # Frechet mean of subspaces (geometry.frechet_mean): init / iterate / finish on one scratch block
+    "dpb_frechet_scratch_bytes": (C.c_size_t, [_I, _I, _L, _I]),
+    "dpb_frechet_init": (_I, [_P, _I, _I, _L, _I, _I, _P, C.c_size_t, _P]),
+    "dpb_frechet_iterate": (_I, [_I, C.c_double, C.c_double, _I, _I, _L, _I, _P, C.c_size_t, _P]),
+    "dpb_frechet_finish": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _P, C.c_size_t, _P]),
 }
 
 _lib = None

@@ -23,6 +23,12 @@ one is an error: nothing is sampled silently) and writes tangent_space_distance-
 local tangent spaces at --h_t, and sample i along its own, at --edit_t; --sample_idx_1_list 1,2,3 (new) serves several targets in one call.  It honours
 --op, --block_idx, --pca_rank (the reference's call site fixes 50), --vis_num, --vis_num_pc and --trajectory_batch, reads the u- / vT- files of the sampling job when they are there and
 computes the missing ones together.
+``--run_edit_global_frechet_mean_zt True --frechet_mean_space x|h --num_local_basis n`` (the reference's flags, define_argparser.py:112-113; unconditional
+nets only) edits --sample_idx along the rows of a global basis: the Frechet mean on the Grassmannian of the n local tangent spaces of the 'Random'
+sampling directory at --h_t (x: the spans of vT, h: the spans of u; missing ones are sampled together), computed on the GPU (geometry.frechet_mean,
+--frechet_max_iter, --frechet_tol: both new; the reference hands the problem to pymanopt) and cached as v- / u-....pt with an info- file beside it.
+--local_projection False (space x only) skips the projection on the sample's own tangent space.  It honours --op, --block_idx, --pca_rank,
+--vis_num, --vis_num_pc and --trajectory_batch as the transport job does.
 """
 from __future__ import annotations
 
@@ -72,6 +78,11 @@ _FLAGS = [  # (name, type, default) -- define_argparser.py:20-110, live path onl
     ("run_tangent_space_distance", str2bool, False),
     # define_argparser.py:117-119: the parallel-transport edit job (unconditional nets); sample_idx_1_list is new: several targets in one call
     ("run_edit_parallel_transport", str2bool, False), ("sample_idx_0", int, 0), ("sample_idx_1", int, 0), ("sample_idx_1_list", str, ""),
+    # define_argparser.py:112-114: the global-basis edit job (unconditional nets).  local_projection defaults to True here, the default of the method
+    # (the reference's flag defaults to False, with which its h-space branch leaves vk undefined); frechet_max_iter / frechet_tol are new (the
+    # reference hands pymanopt 10 000 iterations)
+    ("run_edit_global_frechet_mean_zt", str2bool, False), ("frechet_mean_space", str, "x"), ("frechet_max_iter", int, 1000),
+    ("frechet_tol", float, 1e-6), ("local_projection", str2bool, True),
     # new
     ("pca_rank", int, 2), ("op", str, "mid"), ("block_idx", int, 0), ("vis_num", int, 4), ("vis_num_pc", int, 2), ("weights", str, ""),
     ("net_scale", str, "full"), ("vae", str, "none"), ("text_encoder", str, "none"), ("tokenizer_dir", str, ""),
@@ -110,6 +121,13 @@ def parse_args(argv=None):
     if args.run_edit_parallel_transport and "stable-diffusion" in args.model_name:
         p.error("--run_edit_parallel_transport is a job of the unconditional nets only: the reference has no Stable Diffusion parallel transport "
                 "(its run_edit_parallel_transport belongs to EditUncondDiffusion)")
+    if args.run_edit_global_frechet_mean_zt and "stable-diffusion" in args.model_name:
+        p.error("--run_edit_global_frechet_mean_zt is a job of the unconditional nets only: the reference has no Stable Diffusion global Frechet basis "
+                "(its run_edit_global_frechet_mean_zt belongs to EditUncondDiffusion)")
+    if args.run_edit_global_frechet_mean_zt and args.frechet_mean_space not in ("x", "h"):
+        p.error("--frechet_mean_space must be x (the spans of vT) or h (the spans of u)")
+    if args.run_edit_global_frechet_mean_zt and args.frechet_mean_space == "h" and not args.local_projection:
+        p.error("--local_projection False is valid for --frechet_mean_space x only")
     if extra:
         print(f"note: ignoring flags of experiments outside the pullback path: {extra}")
     return args
@@ -179,6 +197,11 @@ def transport_group(args) -> int:
     return max(1, min(samples, args.memory_bound, TANGENT_BUDGET // max(args.pca_rank, 1)))
 
 
+def frechet_group(args) -> int:
+    """local bases run_edit_global_frechet_mean_zt may have to sample together: up to num_local_basis, bounded like tangent_space_group"""
+    return max(1, min(max(1, args.num_local_basis), args.memory_bound, TANGENT_BUDGET // max(args.pca_rank, 1)))
+
+
 def build_unet(args) -> PullbackUNet:
     from . import weights as W
     small = args.net_scale != "full"
@@ -199,6 +222,13 @@ def build_unet(args) -> PullbackUNet:
         if getattr(args, "trajectory_batch", 0) > 1:
             # ... and the chains together: 2 * vis_num_pc per target and for the source, 2 rows each per guidance step, vis_num + 1 decode states each
             n = 2 * args.vis_num_pc * (1 + len(args.sample_idx_1_values))
+            max_batch = max(max_batch, min(args.trajectory_batch, 2 * n), min(args.trajectory_batch, n * (args.vis_num + 1)))
+    if getattr(args, "run_edit_global_frechet_mean_zt", False):
+        # the local bases the job may have to sample, in groups; and the 2 * vis_num_pc chains together
+        max_batch = max(max_batch, frechet_group(args))
+        max_rank = max(max_rank, frechet_group(args) * args.pca_rank)
+        if getattr(args, "trajectory_batch", 0) > 1:
+            n = 2 * args.vis_num_pc
             max_batch = max(max_batch, min(args.trajectory_batch, 2 * n), min(args.trajectory_batch, n * (args.vis_num + 1)))
     if args.is_stable_diffusion:
         cfg = cf.sd_config_for(args.model_name)           # SD-v1.x or SD-2(.1)-base; anything else raises
@@ -307,6 +337,11 @@ def main(argv=None):
                                          sample_idx_1=args.sample_idx_1_values if args.sample_idx_1_list else args.sample_idx_1, op=args.op,
                                          block_idx=args.block_idx, vis_num=args.vis_num, vis_num_pc=args.vis_num_pc, pca_rank=args.pca_rank,
                                          h_t=args.h_t)
+    if args.run_edit_global_frechet_mean_zt:                                     # (the reference's main.py never calls it; its method's own defaults otherwise)
+        edit.run_edit_global_frechet_mean_zt(idx=args.sample_idx, op=args.op, block_idx=args.block_idx, vis_num=args.vis_num, vis_num_pc=args.vis_num_pc,
+                                             pca_rank=args.pca_rank, num_local_basis=args.num_local_basis, local_projection=args.local_projection,
+                                             frechet_mean_space=args.frechet_mean_space, h_t=args.h_t, frechet_max_iter=args.frechet_max_iter,
+                                             frechet_tol=args.frechet_tol)
     if args.run_ddim_forward:
         edit.run_DDIMforward(num_samples=5)
     if args.run_ddim_inversion:

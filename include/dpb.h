@@ -215,7 +215,7 @@ int dpb_local_pca_sample(dpb_engine* e, const float* x /*[1][N_in]*/, float t, c
 /* ---- principal angles and geodesic distances between subspaces (additive to ABI version 1; engine-independent) ------------------------
  * The analysis the bases (u, s, vT) of run_sample_encoder_local_tangent_space_zt are saved for (src/modules/edit.py:310-383, :1517-1599; the
  * reference has no code for it): the principal angles theta_1..theta_k between two k-dimensional subspaces of R^N and the geodesic distance
- * ||theta||_2 on the Grassmannian.  Distances only: no exponential / logarithm maps, no means (transport of directions: the next section).
+ * ||theta||_2 on the Grassmannian.  Distances only (transport of directions: the next section; the Frechet mean: the one after).
  *
  * dpb_cross_gram: G[i][j] = sum_n X[i][n] Y[j][n].  X [Ra][N], Y [Rb][N] fp32, G [Ra][Rb] FP64 (row stride Rb).  The fp32 inputs are widened on
  * load and multiplied on the fp64 matrix cores (v_mfma_f64_16x16x4_f64), so every product is exact and only the fp64 accumulation rounds.  Y = NULL
@@ -273,6 +273,49 @@ size_t dpb_transport_scratch_bytes(int D, int P, int k, int64_t N_h, int64_t N_x
 int dpb_transport_directions(const float* u_src, const float* u_dst, const float* vT_dst, const int32_t* pcs /*host*/, int P, int D, int k,
                              int64_t N_h, int64_t N_x, float* vk, float* coef, float* coef_norm, void* scratch, size_t scratch_bytes,
                              void* hip_stream);
+
+/* ---- Frechet (Karcher) mean of subspaces on the Grassmannian (additive to ABI version 1; engine-independent) ----------------------------
+ * The global basis of run_edit_global_frechet_mean_zt (src/modules/edit.py:951-1246; the reference calls a compute_frechet_basis it never defines
+ * and hands the problem to pymanopt): the minimiser Y of (1 / 2B) sum_i ||theta(Y, span X_i)||_2^2 over k-dimensional subspaces, by the Riemannian
+ * fixed-step iteration  Y <- Exp_Y(step * (1/B) sum_i Log_Y(X_i)).  X [B][k][N] fp32, one basis per k rows; the rows need NOT be orthonormal, only
+ * independent.  R = B k.  There are still no public exponential / logarithm maps: they exist only inside this iteration, on coefficients.
+ *
+ * Method.  Every iterate lies in the span of the R given rows, so the iteration runs on coefficients: with Q_i = W_i X_i the whitened bases (W_i as
+ * in dpb_subspace_angles), Y = C Q, and all it needs is the whitened Gram Ghat = Q Q^T [R][R] fp64, formed once from dpb_cross_gram (exact products).
+ * Per step, all fp64: M = C Ghat (block i is Y Q_i^T; one pass over Ghat on the fp64 matrix cores); per basis the eigen-decomposition
+ * I - M_i M_i^T = V sin^2(theta) V^T (two-sided Jacobi in LDS), theta = asin(sqrt(l)) for l <= 1/2, else acos(c) with c^2 = ||(V^T M_i)_t||^2 (a sum of
+ * squares keeps the relative accuracy of a small cosine, which 1 - l has lost and theta / (sin cos) divides by), and the log map
+ * F_i (M_i Q_i - M_i M_i^T Y) with F_i = V theta / (sin cos) V^T; the mean tangent's coefficients C_T; T T^T = (C_T Ghat) C_T^T = P Sigma^2 P^T (the second
+ * pass over Ghat, Jacobi); the gradient norm g = ||Sigma||_2 = ||T||_F; C <- P cos(step Sigma) P^T C + P sin(step Sigma) / Sigma P^T C_T, re-orthonormalised
+ * by the Cholesky factor of its own Gram.  The cost (1/2) mean_i sum theta^2 of the iterate a step starts from and g are appended to a device history.
+ *
+ * dpb_frechet_init: forms Ghat and sets C to the identity in block `init` (Y = span X_init); clears the status.
+ * dpb_frechet_iterate: n_iter steps.  A step that finds g < tol sets status.done = 1 and does not move Y; a basis whose largest angle to the iterate
+ *   exceeds pi/2 - 1e-6 is outside the log map's domain: status.done = 2, status.domain = its index; a full history (max_iter steps): done = 3.  Once
+ *   done, the remaining steps of this call and of later calls are no-ops (every kernel reads the flag and returns), so a call never waits for the host.
+ * dpb_frechet_finish: the canonical basis of the mean -- C rotated by the eigenvectors of (1/B) sum_i M_i M_i^T, descending; weight [k] fp32 holds the
+ *   eigenvalues, the mean cos^2 with which the local spaces hold that direction (row 0: the direction they share most; row signs are whatever the
+ *   solve returns, deterministically) -- then Y [k][N] fp32 = (C blockdiag(W)) X in one pass over X (fp32 rows widened on load, summed over the rows in
+ *   index order on the fp64 matrix cores, rounded once), theta [B][k] fp32: the principal angles of the mean to every member, descending, and info
+ *   [8 + 2 max_iter + 1 + B] fp64: {steps taken, last g, status.done, status.domain, cost entries (steps + 1), re-orthonormalisation failed, 0, 0},
+ *   cost [max_iter + 1] (the start included, the final iterate last), g [max_iter] (one per step, one more when done = 1), degenerate flag per basis [B].
+ *   finish does not change the state: iterating may go on after it.
+ * Status block: the first 32 bytes of scratch are {int32 done, int32 domain, int32 steps, int32 reorth_failed, double g, double cost}; a caller that
+ *   iterates in chunks reads them between calls (its only synchronisation).
+ * Degenerate basis (the rule of dpb_subspace_angles: a zero or non-finite row, a Cholesky pivot below 1e-10): its flag is set, its blocks of Ghat
+ *   are NaN, and NaN spreads to Y, weight, theta and the histories.
+ * Reproducibility: no atomics, every sum one fixed chain (the sums over rows are cut at bounds that depend on R only, the sums over bases run in
+ *   index order): the result is bitwise the same run to run, and iterate(a) followed by iterate(b) is bitwise iterate(a + b).
+ * Limits: 1 <= k <= 64 (three k x k fp64 matrices of the log map live in LDS), k <= N, 1 <= B <= 65535, B k <= 2^20, 0 <= max_iter <= 2^24; 8 R^2
+ * bytes of Ghat must fit the scratch.  All three calls take the same B, k, N, max_iter and the same scratch: 256-byte aligned device memory of
+ * scratch_bytes >= dpb_frechet_scratch_bytes(B, k, N, max_iter) (checked).  Outputs must not alias X or scratch.  No device allocation, no host
+ * synchronisation.  Errors via dpb_last_error. */
+size_t dpb_frechet_scratch_bytes(int B, int k, int64_t N, int max_iter);   /* 0 when invalid */
+int dpb_frechet_init(const float* X, int B, int k, int64_t N, int init, int max_iter, void* scratch, size_t scratch_bytes, void* hip_stream);
+int dpb_frechet_iterate(int n_iter, double step, double tol, int B, int k, int64_t N, int max_iter, void* scratch, size_t scratch_bytes,
+                        void* hip_stream);
+int dpb_frechet_finish(const float* X, float* Y, float* weight, float* theta, double* info, int B, int k, int64_t N, int max_iter, void* scratch,
+                       size_t scratch_bytes, void* hip_stream);
 
 /* n_iters full power iterations with no host synchronisation: V <- orth(J^T J V), U = J V_prev, for all B samples
  * of the last dpb_primal together (independent bases, one shared weight stream; B*k <= max_tangents).
