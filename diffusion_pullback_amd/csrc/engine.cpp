@@ -1639,6 +1639,27 @@ int dpb_frechet_finish(const float* X, float* Y, float* weight, float* theta, do
   return launch_frechet_finish(X, B, k, N, max_iter, Y, weight, theta, info, scratch, scratch_bytes, (hipStream_t)stream);
 }
 
+// The Hungarian-matched mean of local bases, the global basis of run_edit_global_hungarian_mean_zt (src/modules/edit.py:1249-1514): hungarian.hip
+size_t dpb_linear_assignment_scratch_bytes(int B, int k) { return linear_assignment_scratch_bytes(B, k); }
+
+int dpb_linear_assignment(const double* cost, int B, int k, int32_t* col_of_row, double* total, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!cost || !col_of_row || !total || !scratch) return fail("dpb_linear_assignment: null argument");
+  return launch_linear_assignment(cost, B, k, col_of_row, total, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+size_t dpb_matched_mean_scratch_bytes(int B, int k, int64_t N) { return matched_mean_scratch_bytes(B, k, N); }
+
+int dpb_matched_mean(const float* X, int B, int k, int64_t N, const float* anchor, int init, int distance, float* Y, int32_t* perm, int32_t* sign,
+                     double* info, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!X || !Y || !perm || !sign || !info || !scratch) return fail("dpb_matched_mean: null argument");
+  return launch_matched_mean(X, B, k, N, anchor, init, distance, Y, perm, sign, info, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int dpb_row_sumsq(const float* X, int64_t rows, int64_t N, double* ss, void* stream) {
+  if (!X || !ss) return fail("dpb_row_sumsq: null argument");
+  return launch_rowsumsq(X, rows, N, ss, (hipStream_t)stream);
+}
+
 // The perturbed batch and the sampling loop of the reference's local_pca_zt / local_pca_xt (src/utils/utils.py:916-933;
 // src/models/ddpm/diffusion.py:396-409): noise.hip
 size_t dpb_perturb_scratch_bytes(int B, int64_t n) { return perturb_scratch_bytes(B, n); }

@@ -362,9 +362,20 @@ int launch_frechet_iterate(long B, int k, long N, long max_iter, int n_iter, dou
 int launch_frechet_finish(const float* X, long B, int k, long N, long max_iter, float* Y, float* weight, float* theta, double* info, void* scratch,
                           size_t scratch_bytes, hipStream_t st);
 
+// ---------------------------------------------------------------- the Hungarian-matched mean of B bases of k rows (hungarian.hip): a batched
+// linear-assignment solver (shortest augmenting paths in LDS, one workgroup per problem) and a streaming mean of permuted, signed rows; see include/dpb.h
+constexpr int HUNGARIAN_MAX_RANK = 128;   // the k x k fp64 cost matrix lives in LDS: 128 KiB of the 160 KiB a workgroup may declare
+size_t linear_assignment_scratch_bytes(long B, int k);   // 0 when invalid
+int launch_linear_assignment(const double* cost, long B, int k, int32_t* col_of_row, double* total, void* scratch, size_t scratch_bytes, hipStream_t st);
+size_t matched_mean_scratch_bytes(long B, int k, long N);   // 0 when invalid
+int launch_matched_mean(const float* X, long B, int k, long N, const float* anchor, int init, int distance, float* Y, int32_t* perm, int32_t* sign,
+                        double* info, void* scratch, size_t scratch_bytes, hipStream_t st);
+
 // ---------------------------------------------------------------- parallel transport of directions between tangent spaces (transport.hip)
 // vk[d][p] = normalise(sum_q c[d][p][q] vhat_dst[d][q]), c[d][p][q] = <uhat_dst[d][q], uhat_src[pcs[p]]> (fp64), coef_norm = ||c||; pcs is a HOST list
 size_t transport_scratch_bytes(long D, int P, int k, long Nh, long Nx);   // 0 when invalid
+// ss[r] = sum_n X[r][n]^2 in fp64, the fixed-order reduction of the transport kernel (a chain that depends on N only); X [rows][N] fp32
+int launch_rowsumsq(const float* X, long rows, long N, double* ss, hipStream_t st);
 int launch_transport_directions(const float* u_src, const float* u_dst, const float* vT_dst, const int32_t* pcs, int P, long D, int k, long Nh, long Nx,
                                 float* vk, float* coef, float* coef_norm, void* scratch, size_t scratch_bytes, hipStream_t st);
 

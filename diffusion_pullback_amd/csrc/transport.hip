@@ -207,6 +207,14 @@ size_t transport_scratch_bytes(long D, int P, int k, long Nh, long Nx) {
   return transport_layout(D, P, k, Nh, Nx, l) ? l.total : 0;
 }
 
+int launch_rowsumsq(const float* X, long rows, long N, double* ss, hipStream_t st) {
+  if (rows < 1 || rows > 0x7fffffffL || N < 1) { set_error("dpb_row_sumsq: rows=%ld outside [1,2^31) or N=%ld < 1", rows, N); return -1; }
+  const int vec = (N % 4 == 0 && (uintptr_t)X % 16 == 0) ? 1 : 0;
+  DPB_LAUNCH(rowsumsq_kernel, dim3((unsigned)rows), dim3(TR_NT), 0, st, X, N, ss, vec);
+  DPB_CHECK(hipGetLastError());
+  return 0;
+}
+
 int launch_transport_directions(const float* u_src, const float* u_dst, const float* vT_dst, const int32_t* pcs, int P, long D, int k, long Nh, long Nx,
                                 float* vk, float* coef, float* coef_norm, void* scratch, size_t scratch_bytes, hipStream_t st) {
   TransportLayout l;

@@ -7,6 +7,7 @@ Mirrors the public surface of the reference's ``modules/edit.py``:
   * ``EditUncondDiffusion``  (reference src/modules/edit.py:540-779, :1601-1734)
       run_DDIMinversion :613-678, run_edit_local_encoder_pullback_zt :680-779, run_edit_parallel_transport :782-948,
       run_edit_global_frechet_mean_zt :951-1246 (its global basis: geometry.frechet_mean),
+      run_edit_global_hungarian_mean_zt :1249-1514 (its global bases: geometry.hungarian_mean),
       run_sample_encoder_local_tangent_space_zt :1517-1599, DDIMforwardsteps :1601-1714, x_space_guidance :1716-1734
 
 Kept from the reference: the step counts (inv_steps-2 inversion steps, ``edit_t_idx`` forward steps,
@@ -869,6 +870,21 @@ class EditUncondDiffusion(_EditBase):
             info = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in info.items()}
             torch.save(dict(info, space=frechet_mean_space, names=[p[2] for p in pairs]), info_path)
 
+        return self._edit_along_global_basis(idx, op, block_idx, vis_num, pcs, pca_rank, h_t, frechet_mean_space, local_projection, basis,
+                                             basis if frechet_mean_space == "h" else None, dict(basis=basis, pcs=pcs, names=[], info=info))
+
+    def _edit_along_global_basis(self, idx, op, block_idx, vis_num, pcs, pca_rank, h_t, space, local_projection, basis, basis_h, out):
+        """The common tail of the global-basis jobs (edit.py:1082-1246, :1354-1468): edit sample idx along rows pcs of `basis` [k, N] -- rows of x-space
+        (space "x") or of h-space ("h").  The sample's own local basis (u, vT) at h_t is loaded or computed and saved; with local_projection
+        vk = normalise(vT^T (vT v)) for x and normalise(vT^T (u^T u_k)) for h, both through geometry.transport_directions; without it (x only) v itself.
+        Then the x-space-guidance chains xt-<dataset>_<idx>-h_<h_t>T-edit_<edit_t>T-<op>-block_<b>-seed_<seed>-pc_<pc>_{pos,neg}, an experiment skipped
+        when its picture exists, and projection_coeff-<name>.png (its u series from rows pcs of basis_h [k, N_h], when given).  Fills and returns out."""
+        from . import geometry
+        exp = lambda pc, tag: f"xt-{self.dataset_name}_{idx}-h_{h_t}T-edit_{self.edit_t}T-{op}-block_{block_idx}-seed_{self.seed}-pc_{pc:0=3d}_{tag}"
+        picture = lambda name: os.path.exists(os.path.join(self.result_folder, f"x0_gen-{name}.png"))
+        load = lambda p: torch.load(p, map_location=self.device).to(torch.float32)
+        self.scheduler.set_timesteps(self.for_steps, device=self.device)
+        h_t_idx = int((self.scheduler.timesteps - h_t * 1000).abs().argmin())
         # the sample, its own local basis at h_t, its state at edit_t
         xT = self._random_latent(idx) if self.dataset_name == "Random" else self.run_DDIMinversion(idx=idx)      # edit.py:1082-1085
         own_dir, own_name = self._tangent_space_naming(op, block_idx, pca_rank)
@@ -885,12 +901,11 @@ class EditUncondDiffusion(_EditBase):
             self.last_basis = (u, vT)
         original_xt = self.DDIMforwardsteps(xT, t_start_idx=0, t_end_idx=self.edit_t_idx)[0].detach()            # edit.py:1136-1137
         shape = original_xt.shape[1:]
-        out = dict(basis=basis, pcs=pcs, names=[], info=info)
         if not pcs:
             return out
         if local_projection:
             with T.phase("projection of the global directions on the local basis"):
-                vk = geometry.transport_directions(basis, vT if frechet_mean_space == "x" else u.t(), vT, pcs)[0][0]      # [P, N_x]
+                vk = geometry.transport_directions(basis, vT if space == "x" else u.t(), vT, pcs)[0][0]      # [P, N_x]
         else:
             vk = basis[pcs] / basis[pcs].norm(dim=1, keepdim=True)                              # edit.py:1155-1156
         out["vk"] = vk
@@ -901,9 +916,97 @@ class EditUncondDiffusion(_EditBase):
                     continue
                 chains.append((exp(pc, tag), original_xt, (sign * vk[p]).view(1, *shape)))
                 if local_projection:
-                    uk = sign * basis[pc] if frechet_mean_space == "h" else None
+                    uk = sign * basis_h[pc] if basis_h is not None else None
                     save_projection_plot(None if uk is None else (u / u.norm(dim=0, keepdim=True)).t() @ uk,
                                          (vT / vT.norm(dim=1, keepdim=True)) @ (sign * vk[p]), os.path.join(self.obs_folder, f"projection_coeff-{exp(pc, tag)}.png"))
         out["names"] = [c[0] for c in chains]
         self._run_direction_chains(chains, vis_num, shape)
         return out
+
+    def global_hungarian_mean_paths(self, op="mid", block_idx=0, pca_rank=50, h_t=None):
+        """{"u": (basis file, info file), "v": ...} of the two Hungarian global bases, in the reference's layout (edit.py:1270-1274; the directory
+        without the scheduler_name the reference never defines): {u,v}-<h_t>T-<op>-block_<b>-seed_<seed>.pt holds [N, k] columns.  The reference's
+        name does not carry num_local_basis; the info- file beside it does."""
+        h_t = self.h_t if h_t is None else h_t
+        save_dir = os.path.join(self.input_root, f"global_hungarian_mean_uncond-model_{self.model_name}-dataset_{self.dataset_name}-num_steps_{self.for_steps}-pca_rank_{pca_rank}")
+        name = f"{h_t}T-{op}-block_{block_idx}-seed_{self.seed}"
+        return {tag: (os.path.join(save_dir, f"{tag}-{name}.pt"), os.path.join(save_dir, f"info-{tag}-{name}.pt")) for tag in ("u", "v")}
+
+    @torch.no_grad()
+    def run_edit_global_hungarian_mean_zt(self, idx, op="mid", block_idx=0, vis_num=4, vis_num_pc=None, vis_pc_list=None, pca_rank=50, num_local_basis=100,
+                                          local_projection=True, hungarian_mean_space="x", h_t=None, hungarian_distance="1/cosine",
+                                          hungarian_max_sweeps=20):
+        """Reference: src/modules/edit.py:1249-1514 -- edit sample idx along the directions of the other GLOBAL basis, the Hungarian-matched mean of
+        num_local_basis local tangent spaces at h_t: the k singular directions of every local basis are matched one to one, and sign by sign, to those
+        of local basis 0, and the matched unit vectors are averaged (geometry.hungarian_mean; hungarian_distance '1/cosine' is the reference's call,
+        hungarian_max_sweeps re-matches against the mean until nothing changes).  "Direction 3" then means the same thing at every sample, where the
+        rows of the Frechet basis are canonical only up to an eigen-ordering.  The reference calls a compute_hungarian_basis it never defines.
+
+        Local bases: the xt-Random_<i>-... files of the 'Random' sampling directory; the missing ones are sampled together, as in
+        run_edit_global_frechet_mean_zt.  Global bases: BOTH are computed, as the reference does -- u- from the stack of u^T, v- from the stack of vT --
+        and written as [N, k] columns under global_hungarian_mean_paths, each with an info- file (perm, sign, cost, weight, names, num_local_basis,
+        distance, sweeps, converged).  An existing file is loaded and normalised, u by column and v as edit.py:1282-1283 does (along dim 1 of the
+        [N, k] file); an info- file that records another num_local_basis or distance raises ValueError (no info- file: a reference-written cache,
+        loaded as is).  The reference's v load branch reloads u (edit.py:1350-1352): not reproduced.
+        Edit: the common tail of the global-basis jobs (_edit_along_global_basis).  hungarian_mean_space "x": vk = normalise(vT^T (vT vhat_pc)), the
+        reference's live path; "h": vk = normalise(vT^T (u^T uhat_pc)), the route the Frechet job uses to bring an h-direction to x.
+        local_projection=False is valid for "x" only.  The reference's parallel-h and h_space_guidance branches are not built.
+        Returns a dict: basis_u [k, N_h], basis_v [k, N_x] (rows), vk [P, N_x], pcs, names, info ({"u": ..., "v": ...}, None for a loaded basis)."""
+        from . import geometry
+        if hungarian_mean_space not in ("x", "h"):
+            raise ValueError(f"hungarian_mean_space must be 'x' (the directions of vT) or 'h' (the directions of u), got {hungarian_mean_space!r}")
+        if hungarian_mean_space == "h" and not local_projection:
+            raise ValueError("local_projection=False is valid for hungarian_mean_space 'x' only: an h-space direction reaches x-space through the "
+                             "sample's own local basis")
+        if hungarian_distance not in geometry.HUNGARIAN_DISTANCES:
+            raise ValueError(f"hungarian_distance must be one of {sorted(geometry.HUNGARIAN_DISTANCES)}, got {hungarian_distance!r}")
+        h_t = self.h_t if h_t is None else h_t
+        pcs = list(range(vis_num_pc or 0)) if vis_pc_list is None else [int(p) for p in vis_pc_list]
+        exp = lambda pc, tag: f"xt-{self.dataset_name}_{idx}-h_{h_t}T-edit_{self.edit_t}T-{op}-block_{block_idx}-seed_{self.seed}-pc_{pc:0=3d}_{tag}"
+        if pcs and os.path.exists(os.path.join(self.result_folder, f"x0_gen-{exp(pcs[-1], 'neg')}.png")):
+            print("!!!ALREADY DONE EXP :", exp(pcs[-1], "neg"), "!!!")
+            return None
+        self.scheduler.set_timesteps(self.for_steps, device=self.device)
+        h_t_idx = int((self.scheduler.timesteps - h_t * 1000).abs().argmin())
+        load = lambda p: torch.load(p, map_location=self.device).to(torch.float32)
+
+        paths = self.global_hungarian_mean_paths(op, block_idx, pca_rank, h_t)
+        os.makedirs(os.path.dirname(paths["u"][0]), exist_ok=True)
+        bases, infos = {}, {"u": None, "v": None}
+        for tag, (basis_path, info_path) in paths.items():
+            if not os.path.exists(basis_path):
+                continue
+            if os.path.exists(info_path):
+                rec = torch.load(info_path, weights_only=False)
+                if rec.get("num_local_basis") != num_local_basis or rec.get("distance") != hungarian_distance:
+                    raise ValueError(f"{info_path} records num_local_basis = {rec.get('num_local_basis')}, distance = {rec.get('distance')!r}; asked for "
+                                     f"{num_local_basis}, {hungarian_distance!r} (the basis file's name does not carry them: move it away to recompute)")
+            cols = load(basis_path)
+            cols = cols / cols.norm(dim=0 if tag == "u" else 1, keepdim=True)                   # edit.py:1282-1283
+            bases[tag] = cols.t().contiguous()
+        if len(bases) < 2:
+            local_dir, local_name = self._tangent_space_naming(op, block_idx, pca_rank, dataset_name="Random")
+            pairs = self._tangent_space_pairs(h_t, num_local_basis, local_dir, local_name)
+            pending = [p for p in pairs if not (os.path.exists(p[3][0]) and os.path.exists(p[3][2]))]    # edit.py:1298
+            if pending:
+                os.makedirs(local_dir, exist_ok=True)
+                latent = self._random_latent if self.dataset_name == "Random" else self._seeded_latent
+                self._sample_tangent_spaces(pending, lambda i, ht: self.DDIMforwardsteps(latent(i), t_start_idx=0, t_end_idx=h_t_idx)[:2], None, op,
+                                            block_idx, pca_rank, 1e-4, local_dir, lambda *a: None)
+            for tag in ("u", "v"):
+                if tag in bases:
+                    continue
+                with T.phase("Hungarian mean of the local bases"):
+                    stack = torch.stack([load(p[3][0]).t() if tag == "u" else load(p[3][2]) for p in pairs]).contiguous()
+                    basis, info = geometry.hungarian_mean(stack, init=0, distance=hungarian_distance, max_sweeps=hungarian_max_sweeps)   # edit.py:1339, :1347
+                print(f"Hungarian mean ({tag}) of {num_local_basis} local bases: {info['sweeps']} sweeps, changed {info['changed']}, mean weight "
+                      f"{float(info['weight'].mean()):.4f}" + ("" if info["converged"] else f" -- NOT converged in {hungarian_max_sweeps} sweeps"))
+                torch.save(basis.t().contiguous().cpu(), paths[tag][0])
+                info = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in info.items()}
+                info.update(names=[p[2] for p in pairs], num_local_basis=num_local_basis)
+                torch.save(info, paths[tag][1])
+                bases[tag], infos[tag] = basis, info
+        use = "u" if hungarian_mean_space == "h" else "v"
+        out = dict(basis_u=bases["u"], basis_v=bases["v"], pcs=pcs, names=[], info=infos if (infos["u"] or infos["v"]) else None)
+        return self._edit_along_global_basis(idx, op, block_idx, vis_num, pcs, pca_rank, h_t, hungarian_mean_space, local_projection, bases[use],
+                                             bases["u"], out)

@@ -13,6 +13,10 @@ expressed in a target's basis and carried to the target's x-space, fp64 on the h
 (``csrc/frechet.hip``): the Riemannian fixed-step iteration on coefficients against the whitened fp64 Gram of all rows, one streaming pass over the
 rows before it and one after it.
 
+``linear_assignment`` and ``hungarian_mean`` are the other global basis, of ``run_edit_global_hungarian_mean_zt`` (``csrc/hungarian.hip``): the
+directions of every basis matched one to one and sign by sign to an anchor's by a batched assignment solver on the device, and the matched unit
+vectors averaged in one streaming pass -- a mean of directions, where the Frechet mean is a mean of subspaces.
+
 There are still no public exponential / logarithm maps: they exist only inside the mean's iteration, on coefficients.  There is no CPU fallback:
 inputs live on a HIP device.
 """
@@ -272,6 +276,117 @@ def frechet_mean(A: torch.Tensor, init: int = 0, max_iter: int = 1000, tol: floa
         j = int(worst[0])
         raise L.DpbError(f"frechet_mean: the cost rose from {cost[j]!r} to {cost[j + 1]!r} at step {j + 1}: use a smaller step than {step}")
     return Y, info
+
+
+def linear_assignment(cost: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The batched linear-assignment problem: cost [B, k, k] (or one [k, k]) float64 on the device -> (col_of_row [B, k] int32, total [B] float64), the
+    permutation minimising sum_i cost[b, i, col_of_row[b, i]] and that sum (dpb_linear_assignment: shortest augmenting paths, one workgroup per
+    problem, ties broken on the lowest column index -- a function of the matrix alone, bitwise the same alone and in a batch).  k <= 128.  A problem
+    with a non-finite entry returns -1 / NaN and spoils no other.  No host sync."""
+    lib = L.load()
+    if not torch.is_tensor(cost) or not cost.is_cuda:
+        raise ValueError("cost must be a tensor on a HIP device (there is no CPU path)")
+    if cost.dtype != torch.float64:
+        raise ValueError(f"cost must be float64, got {cost.dtype}")
+    cost = cost.detach().contiguous()
+    if cost.dim() == 2:
+        cost = cost[None]
+    if cost.dim() != 3 or cost.shape[1] != cost.shape[2] or cost.numel() == 0:
+        raise ValueError(f"cost must be a stack of square matrices [B, k, k], got {tuple(cost.shape)}")
+    b, k, _ = cost.shape
+    if k > MAX_RANK:
+        raise ValueError(f"k = {k} exceeds the size {MAX_RANK} the assignment solver supports")
+    need = int(lib.dpb_linear_assignment_scratch_bytes(b, k))
+    if need == 0:
+        raise L.DpbError(f"dpb_linear_assignment does not take B = {b}, k = {k}")
+    with torch.cuda.device(cost.device):
+        st = C.c_void_p(torch.cuda.current_stream(cost.device).cuda_stream)
+        scratch = torch.empty(need, dtype=torch.uint8, device=cost.device)
+        col = torch.empty(b, k, dtype=torch.int32, device=cost.device)
+        total = torch.empty(b, dtype=torch.float64, device=cost.device)
+        L.check(lib.dpb_linear_assignment(cost.data_ptr(), b, k, col.data_ptr(), total.data_ptr(), scratch.data_ptr(), need, st))
+    return col, total
+
+
+HUNGARIAN_DISTANCES = {"1/cosine": 0, "cosine": 1}
+
+
+def hungarian_mean(A: torch.Tensor, init: int = 0, distance: str = "1/cosine", max_sweeps: int = 20, anchor: Optional[torch.Tensor] = None,
+                   max_bytes: Optional[int] = None, check: bool = True) -> Tuple[torch.Tensor, dict]:
+    """The Hungarian-matched mean of the directions of A [B, k, N]: with xhat the rows scaled to unit length in fp64 and the anchor Y = xhat[init]
+    (or ``anchor`` [k, N]), a sweep matches every basis's rows one to one to the anchor's by the assignment pi_b minimising
+    sum_i d(<y_i, xhat_{b, pi_b(i)}>), d = 1 / max(|c|, 2^-40) ('1/cosine', the reference's call) or 1 - |c| ('cosine'), takes the sign of each
+    matched overlap, and sets Y_i = normalise(sum_b sign_b(i) xhat_{b, pi_b(i)}), rounded to fp32 once; that Y is the next sweep's anchor.  Sweeps stop
+    when no pi_b and no sign changed (``converged``) or after max_sweeps (1: the plain anchor-matched mean); '1/cosine' has no monotone objective, so
+    not converging is reported, not raised.  See include/dpb.h (dpb_matched_mean) for the kernels and the limits; any float dtype is converted to
+    contiguous fp32; k <= 128.
+
+    Returns Y [k, N] fp32 with unit rows in the ANCHOR's order -- row i is the direction matched to anchor row i; the rows are not orthogonalised --
+    and info: ``perm`` [B, k] int32 (pi_b(i)), ``sign`` [B, k] int32, ``cost`` [sweeps, B] float64 numpy (each sweep's assignment totals),
+    ``sweeps``, ``converged``, ``changed`` (list: (b, i) entries that changed per sweep; the first counts all B k), ``weight`` [k] fp32 (the mean over
+    b of |<y_i, xhat_{b, pi_b(i)}>| against the final Y) and ``degenerate`` (indices).  One host read per sweep.  check: raise ValueError naming the
+    degenerate bases (a zero or non-finite row); False returns the NaNs.  Bitwise reproducible; perm[b] and sign[b] do not depend on the other bases
+    of the stack given the same anchor."""
+    lib = L.load()
+    A = _stack(A, "A")
+    b, k, n = A.shape
+    if distance not in HUNGARIAN_DISTANCES:
+        raise ValueError(f"distance must be one of {sorted(HUNGARIAN_DISTANCES)}, got {distance!r}")
+    if k > MAX_RANK:
+        raise ValueError(f"k = {k} rows per basis exceeds the rank {MAX_RANK} the Hungarian mean supports")
+    init, max_sweeps = int(init), int(max_sweeps)
+    if not 0 <= init < b:
+        raise ValueError(f"init = {init} outside [0, B = {b})")
+    if max_sweeps < 1:
+        raise ValueError(f"max_sweeps = {max_sweeps} must be >= 1")
+    if anchor is not None:
+        anchor = _device_f32(anchor, "anchor").to(A.device)
+        if tuple(anchor.shape) != (k, n):
+            raise ValueError(f"anchor must be [k = {k}, N = {n}], got {tuple(anchor.shape)}")
+    max_bytes = DEFAULT_MAX_BYTES if max_bytes is None else int(max_bytes)
+    need = int(lib.dpb_matched_mean_scratch_bytes(b, k, n))
+    if need == 0:
+        raise L.DpbError(f"dpb_matched_mean does not take B = {b}, k = {k}, N = {n}")
+    if need > max_bytes:
+        raise ValueError(f"the Hungarian mean of B = {b} bases of k = {k} rows needs {need} bytes of device scratch, max_bytes is {max_bytes}")
+    dist = HUNGARIAN_DISTANCES[distance]
+    with torch.cuda.device(A.device):
+        st = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
+        scratch = torch.empty(need, dtype=torch.uint8, device=A.device)
+        Y = [torch.empty(k, n, dtype=torch.float32, device=A.device) for _ in range(2)]      # (a sweep's output must not alias its anchor)
+        perm = torch.full((b, k), -1, dtype=torch.int32, device=A.device)
+        sign = torch.zeros(b, k, dtype=torch.int32, device=A.device)
+        info_d = torch.empty(1 + 2 * b, dtype=torch.float64, device=A.device)
+        costs, changed, converged, degenerate = [], [], False, []
+        cur = anchor
+        for s in range(max_sweeps):
+            out = Y[s % 2]
+            L.check(lib.dpb_matched_mean(A.data_ptr(), b, k, n, None if cur is None else cur.data_ptr(), init, dist, out.data_ptr(), perm.data_ptr(),
+                                         sign.data_ptr(), info_d.data_ptr(), scratch.data_ptr(), need, st))
+            raw = info_d.cpu().numpy()                                   # the one host read of the sweep
+            cur = out
+            costs.append(raw[1:1 + b].copy())
+            changed.append(int(raw[0]))
+            degenerate = np.nonzero(raw[1 + b:] != 0)[0].tolist()
+            if degenerate:
+                break
+            if changed[-1] == 0:
+                converged = True
+                break
+        if check and degenerate:
+            raise ValueError(f"degenerate bases (a zero or non-finite row, in the basis or in the anchor): indices {degenerate}")
+        # weight: |<y_i, xhat_{b, pi_b(i)}>| against the final Y, from the same exact overlaps and row norms
+        G = torch.empty(k, b * k, dtype=torch.float64, device=A.device)
+        ss = torch.empty(b * k + k, dtype=torch.float64, device=A.device)
+        L.check(lib.dpb_cross_gram(cur.data_ptr(), A.data_ptr(), G.data_ptr(), k, b * k, n, st))
+        L.check(lib.dpb_row_sumsq(A.data_ptr(), b * k, n, ss.data_ptr(), st))
+        L.check(lib.dpb_row_sumsq(cur.data_ptr(), k, n, ss[b * k:].data_ptr(), st))
+        c = G.view(k, b, k) / (ss[b * k:].sqrt()[:, None, None] * ss[:b * k].sqrt().view(1, b, k))
+        picked = c.gather(2, perm.t().clamp(min=0).long()[:, :, None])[:, :, 0]          # [k, B]
+        weight = picked.abs().mean(dim=1).to(torch.float32)
+    info = {"perm": perm, "sign": sign, "cost": np.stack(costs), "sweeps": len(costs), "converged": converged, "changed": changed, "weight": weight,
+            "degenerate": degenerate, "distance": distance}
+    return cur, info
 
 
 def subspace_angles(A: torch.Tensor, B: Optional[torch.Tensor] = None, max_bytes: Optional[int] = None) -> torch.Tensor:

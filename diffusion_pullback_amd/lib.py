@@ -110,6 +110,12 @@ SYMBOLS = {
     "dpb_frechet_init": (_I, [_P, _I, _I, _L, _I, _I, _P, C.c_size_t, _P]),
     "dpb_frechet_iterate": (_I, [_I, C.c_double, C.c_double, _I, _I, _L, _I, _P, C.c_size_t, _P]),
     "dpb_frechet_finish": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _P, C.c_size_t, _P]),
+    # Hungarian-matched mean of directions (geometry.linear_assignment / hungarian_mean): the batched solver, one sweep, the fp64 row sums of squares
+    "dpb_linear_assignment_scratch_bytes": (C.c_size_t, [_I, _I]),
+    "dpb_linear_assignment": (_I, [_P, _I, _I, _P, _P, _P, C.c_size_t, _P]),
+    "dpb_matched_mean_scratch_bytes": (C.c_size_t, [_I, _I, _L]),
+    "dpb_matched_mean": (_I, [_P, _I, _I, _L, _P, _I, _I, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "dpb_row_sumsq": (_I, [_P, _L, _L, _P, _P]),
 }
 
 _lib = None

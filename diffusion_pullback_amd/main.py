@@ -29,6 +29,10 @@ sampling directory at --h_t (x: the spans of vT, h: the spans of u; missing ones
 --frechet_max_iter, --frechet_tol: both new; the reference hands the problem to pymanopt) and cached as v- / u-....pt with an info- file beside it.
 --local_projection False (space x only) skips the projection on the sample's own tangent space.  It honours --op, --block_idx, --pca_rank,
 --vis_num, --vis_num_pc and --trajectory_batch as the transport job does.
+``--run_edit_global_hungarian_mean_zt True --hungarian_mean_space x|h`` (the reference's flags, define_argparser.py:121-122; unconditional nets only)
+edits --sample_idx along the other global basis: the Hungarian-matched mean of the same local bases -- the directions of every basis matched one to
+one and sign by sign to those of basis 0 and averaged (geometry.hungarian_mean; --hungarian_distance 1/cosine|cosine and --hungarian_max_sweeps are
+new).  Both bases are computed and cached, u-....pt from the u's and v-....pt from the vT's, each with an info- file; x edits along v, h along u.
 """
 from __future__ import annotations
 
@@ -83,6 +87,10 @@ _FLAGS = [  # (name, type, default) -- define_argparser.py:20-110, live path onl
     # reference hands pymanopt 10 000 iterations)
     ("run_edit_global_frechet_mean_zt", str2bool, False), ("frechet_mean_space", str, "x"), ("frechet_max_iter", int, 1000),
     ("frechet_tol", float, 1e-6), ("local_projection", str2bool, True),
+    # define_argparser.py:121-122: the other global-basis job (unconditional nets); hungarian_mean_space defaults to x, what the reference's method
+    # does (its flag has no consumer); hungarian_distance / hungarian_max_sweeps are new (the reference passes distance='1/cosine')
+    ("run_edit_global_hungarian_mean_zt", str2bool, False), ("hungarian_mean_space", str, "x"), ("hungarian_distance", str, "1/cosine"),
+    ("hungarian_max_sweeps", int, 20),
     # new
     ("pca_rank", int, 2), ("op", str, "mid"), ("block_idx", int, 0), ("vis_num", int, 4), ("vis_num_pc", int, 2), ("weights", str, ""),
     ("net_scale", str, "full"), ("vae", str, "none"), ("text_encoder", str, "none"), ("tokenizer_dir", str, ""),
@@ -128,6 +136,17 @@ def parse_args(argv=None):
         p.error("--frechet_mean_space must be x (the spans of vT) or h (the spans of u)")
     if args.run_edit_global_frechet_mean_zt and args.frechet_mean_space == "h" and not args.local_projection:
         p.error("--local_projection False is valid for --frechet_mean_space x only")
+    if args.run_edit_global_hungarian_mean_zt and "stable-diffusion" in args.model_name:
+        p.error("--run_edit_global_hungarian_mean_zt is a job of the unconditional nets only: the reference has no Stable Diffusion global Hungarian "
+                "basis (its run_edit_global_hungarian_mean_zt belongs to EditUncondDiffusion)")
+    if args.run_edit_global_hungarian_mean_zt and args.hungarian_mean_space not in ("x", "h"):
+        p.error("--hungarian_mean_space must be x (the directions of vT) or h (the directions of u)")
+    if args.run_edit_global_hungarian_mean_zt and args.hungarian_mean_space == "h" and not args.local_projection:
+        p.error("--local_projection False is valid for --hungarian_mean_space x only")
+    if args.run_edit_global_hungarian_mean_zt and args.hungarian_distance not in ("1/cosine", "cosine"):
+        p.error("--hungarian_distance must be 1/cosine (the reference's call) or cosine")
+    if args.run_edit_global_hungarian_mean_zt and args.hungarian_max_sweeps < 1:
+        p.error("--hungarian_max_sweeps must be >= 1")
     if extra:
         print(f"note: ignoring flags of experiments outside the pullback path: {extra}")
     return args
@@ -198,7 +217,7 @@ def transport_group(args) -> int:
 
 
 def frechet_group(args) -> int:
-    """local bases run_edit_global_frechet_mean_zt may have to sample together: up to num_local_basis, bounded like tangent_space_group"""
+    """local bases a global-basis job (run_edit_global_frechet_mean_zt, run_edit_global_hungarian_mean_zt) may have to sample together: up to num_local_basis, bounded like tangent_space_group"""
     return max(1, min(max(1, args.num_local_basis), args.memory_bound, TANGENT_BUDGET // max(args.pca_rank, 1)))
 
 
@@ -223,8 +242,8 @@ def build_unet(args) -> PullbackUNet:
             # ... and the chains together: 2 * vis_num_pc per target and for the source, 2 rows each per guidance step, vis_num + 1 decode states each
             n = 2 * args.vis_num_pc * (1 + len(args.sample_idx_1_values))
             max_batch = max(max_batch, min(args.trajectory_batch, 2 * n), min(args.trajectory_batch, n * (args.vis_num + 1)))
-    if getattr(args, "run_edit_global_frechet_mean_zt", False):
-        # the local bases the job may have to sample, in groups; and the 2 * vis_num_pc chains together
+    if getattr(args, "run_edit_global_frechet_mean_zt", False) or getattr(args, "run_edit_global_hungarian_mean_zt", False):
+        # the local bases either global-basis job may have to sample, in groups; and the 2 * vis_num_pc chains together
         max_batch = max(max_batch, frechet_group(args))
         max_rank = max(max_rank, frechet_group(args) * args.pca_rank)
         if getattr(args, "trajectory_batch", 0) > 1:
@@ -342,6 +361,11 @@ def main(argv=None):
                                              pca_rank=args.pca_rank, num_local_basis=args.num_local_basis, local_projection=args.local_projection,
                                              frechet_mean_space=args.frechet_mean_space, h_t=args.h_t, frechet_max_iter=args.frechet_max_iter,
                                              frechet_tol=args.frechet_tol)
+    if args.run_edit_global_hungarian_mean_zt:                                   # (the reference's main.py never calls it; its method's own defaults otherwise)
+        edit.run_edit_global_hungarian_mean_zt(idx=args.sample_idx, op=args.op, block_idx=args.block_idx, vis_num=args.vis_num,
+                                               vis_num_pc=args.vis_num_pc, pca_rank=args.pca_rank, num_local_basis=args.num_local_basis,
+                                               local_projection=args.local_projection, hungarian_mean_space=args.hungarian_mean_space, h_t=args.h_t,
+                                               hungarian_distance=args.hungarian_distance, hungarian_max_sweeps=args.hungarian_max_sweeps)
     if args.run_ddim_forward:
         edit.run_DDIMforward(num_samples=5)
     if args.run_ddim_inversion:

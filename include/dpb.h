@@ -317,6 +317,52 @@ int dpb_frechet_iterate(int n_iter, double step, double tol, int B, int k, int64
 int dpb_frechet_finish(const float* X, float* Y, float* weight, float* theta, double* info, int B, int k, int64_t N, int max_iter, void* scratch,
                        size_t scratch_bytes, void* hip_stream);
 
+/* ---- the Hungarian-matched mean of directions (additive to ABI version 1; engine-independent) -----------------------------------------
+ * The global basis of run_edit_global_hungarian_mean_zt (src/modules/edit.py:1249-1514; the reference calls a compute_hungarian_basis it never
+ * defines, with initial_local_basis_idx=0, distance='1/cosine').  Where the Frechet mean averages subspaces, this one averages DIRECTIONS: the k rows
+ * of every basis are matched one to one, and sign by sign, to the rows of an anchor, and the matched unit vectors are averaged.  X [B][k][N] fp32,
+ * one basis per k rows; rows need not be unit length (xhat: a row divided by its fp64 norm), and nothing here needs them orthogonal.
+ *
+ * dpb_linear_assignment: the batched solver.  cost [B][k][k] fp64, row-major; col_of_row [B][k] int32 and total [B] fp64 out: the permutation that
+ *   minimises sum_i cost[b][i][col_of_row[b][i]], and that sum (added in row order).  One workgroup per problem; the shortest-augmenting-path
+ *   (Jonker-Volgenant) method in fp64 with the matrix, the duals, the predecessors and both matchings in LDS; every Dijkstra step relaxes all
+ *   unscanned columns at once and takes the (value, index) minimum that breaks ties on the LOWEST column index, so the result is a function of the
+ *   matrix alone: problem b is bitwise the same alone and in any batch, run to run.  Among several optimal assignments it returns one; its total is
+ *   the optimum.  Costs must be finite: a problem with a NaN or an infinity (or whose path sums overflow) gets col_of_row = -1 and total = NaN, and no
+ *   other problem is touched.  Limits: 1 <= k <= 128 (8 k^2 bytes of LDS: 128 KiB at k = 128; a 32 KiB instantiation serves k <= 64),
+ *   1 <= B <= 2^20.  scratch: 256-byte aligned device memory of >= dpb_linear_assignment_scratch_bytes(B, k) bytes (checked; the block is reserved:
+ *   the solver's state lives in LDS).
+ *
+ * dpb_matched_mean: ONE sweep.  anchor [k][N] fp32, or NULL for X[init] (0 <= init < B; ignored when anchor is given).  With yhat the anchor's unit
+ *   rows: c_b[i][j] = <yhat_i, xhat_{b,j}> from dpb_cross_gram(anchor, X) (exact products) divided by the row norms (the fixed-order fp64 sums of
+ *   squares of dpb_row_sumsq), the cost d = 1 / max(|c|, 2^-40) (distance 0, '1/cosine') or 1 - |c| (distance 1, 'cosine'), formed in fp64 while the
+ *   solver loads its matrix; perm[b] = the assignment of d (as dpb_linear_assignment), sign[b][i] = -1 if c_b[i][perm[b][i]] < 0, else +1; then
+ *   Y[i] = normalise(sum_b sign[b][i] xhat_{b, perm[b][i]}): one pass over X, b in index order, one fp64 fma per term, the norm from per-chunk partial
+ *   sums added in chunk order, ONE rounding to fp32.  Row i of Y is the direction matched to anchor row i.
+ *   perm, sign [B][k] int32 are read as the previous sweep's assignment and written as the new one (first sweep: fill perm with -1).
+ *   info [1 + 2 B] fp64: {the number of (b, i) entries whose perm or sign changed, total cost per basis [B], degenerate flag per basis [B]}.  The caller
+ *   owns the sweeps: Y of one call is the anchor of the next, until info[0] == 0 (one host read per sweep) or its cap; with 'cosine' a sweep cannot
+ *   decrease sum_b sum_i |<y_i, xhat_{b,perm}>|, with '1/cosine' nothing guarantees termination.
+ *   Degenerate basis (the rule of dpb_transport_directions: a zero or non-finite row, in basis b or in the anchor): its flag is 1, its perm -1, its
+ *   sign 0, its total NaN, and NaN spreads to Y.
+ *   Reproducibility and batch invariance: no atomics, every sum one fixed chain; perm[b], sign[b] and total[b] are a function of the anchor, the rows
+ *   of basis b, k and N only -- bitwise the same in a call of its own and inside any stack; Y is bitwise the same run to run.
+ *   Limits: 1 <= k <= 128, 1 <= B <= 2^20, B k <= 2^24, N >= 1 (any N; 16-byte accesses when N % 4 == 0 and the pointers are 16-byte aligned,
+ *   64-bit offsets throughout).  scratch: 256-byte aligned, >= dpb_matched_mean_scratch_bytes(B, k, N) (checked): the k x B k overlaps, the row
+ *   norms, and the fp64 sums [k][N] before they are normalised.  Y must not alias X, anchor or scratch.
+ *
+ * dpb_row_sumsq: ss[r] = sum_n X[r][n]^2 in fp64, X [rows][N] fp32 -- the fixed-order reduction the transport and the matched mean use (a chain
+ *   that depends on N only).
+ * No device allocation, no host synchronisation.  Errors via dpb_last_error. */
+size_t dpb_linear_assignment_scratch_bytes(int B, int k);   /* 0 when invalid */
+int dpb_linear_assignment(const double* cost /*[B][k][k]*/, int B, int k, int32_t* col_of_row /*[B][k]*/, double* total /*[B]*/, void* scratch,
+                          size_t scratch_bytes, void* hip_stream);
+size_t dpb_matched_mean_scratch_bytes(int B, int k, int64_t N);   /* 0 when invalid */
+int dpb_matched_mean(const float* X, int B, int k, int64_t N, const float* anchor /*[k][N] or NULL: X[init]*/, int init, int distance,
+                     float* Y /*[k][N]*/, int32_t* perm /*[B][k]*/, int32_t* sign /*[B][k]*/, double* info /*[1 + 2 B]*/, void* scratch,
+                     size_t scratch_bytes, void* hip_stream);
+int dpb_row_sumsq(const float* X, int64_t rows, int64_t N, double* ss /*[rows]*/, void* hip_stream);
+
 /* n_iters full power iterations with no host synchronisation: V <- orth(J^T J V), U = J V_prev, for all B samples
  * of the last dpb_primal together (independent bases, one shared weight stream; B*k <= max_tangents).
  * V [B][k][N_in] in/out, U [B][k][N_h] out, s [B][k] out, conv [B][2] out (of the last iteration).
