@@ -50,9 +50,9 @@ def concat(out, a, b):
     return dict(op="concat", out=out, src=a, src2=b)
 
 
-def linear(out, src, name, cout, res=None):
-    """ks = 1 product y = x W^T + b (+ res)"""
-    return dict(op="linear", out=out, src=src, name=name, cout=cout, res=res)
+def linear(out, src, name, cout, res=None, interleave=0):
+    """ks = 1 product y = x W^T + b (+ res); interleave = 64: the output columns in the a0 g0 a1 g1 ... layout of a GEGLU projection (Tape.conv)"""
+    return dict(op="linear", out=out, src=src, name=name, cout=cout, res=res, interleave=interleave)
 
 
 def build_tape(steps: List[dict], params: Dict[str, torch.Tensor], dtype, device, rows: int, ch: int):
@@ -76,7 +76,7 @@ def build_tape(steps: List[dict], params: Dict[str, torch.Tensor], dtype, device
         elif op == "concat":
             o = t.concat(src, b[s["src2"]])
         elif op == "linear":
-            o = t.conv(s["name"], src, (rows, 1), s["cout"], ks=1, res=b[s["res"]] if s["res"] else -1)
+            o = t.conv(s["name"], src, (rows, 1), s["cout"], ks=1, res=b[s["res"]] if s["res"] else -1, interleave=s.get("interleave", 0))
         else:
             raise ValueError(op)
         b[s["out"]] = o
@@ -162,6 +162,8 @@ def evaluate(steps: List[dict], params: Dict[str, torch.Tensor], x: torch.Tensor
                 y = y + P(s["name"] + ".bias")
             if s["res"]:
                 y = y + v[s["res"]]
+            if s.get("interleave"):
+                y = y[..., interleave_perm(s["cout"] // 2, s["interleave"]).to(y.device)]
         else:
             raise ValueError(op)
         v[s["out"]] = y
@@ -309,6 +311,16 @@ BOUNDS = {
     ("concat", F32): {"primal": (2.6e-07, 1.5e-07), "tangent": (4.4e-07, 2.0e-07), "adjoint": (4.2e-07, 2.1e-07)},
     ("concat", BF): {"primal": (8.9e-03, 4.1e-03), "tangent": (9.9e-03, 5.0e-03), "adjoint": (1.2e-02, 5.1e-03)},
     ("concat", F16): {"primal": (7.7e-04, 5.1e-04), "tangent": (1.6e-03, 6.3e-04), "adjoint": (1.7e-03, 6.4e-04)},
+    # the fused product epilogues (tests/test_gpu_epilogue_ops.py; maxima in its docstring)
+    ("epi_geglu", F32): {"primal": (8.4e-07, 6.0e-07), "tangent": (9.8e-07, 6.2e-07), "adjoint": (9.6e-07, 7.3e-07)},
+    ("epi_geglu", BF): {"primal": (1.3e-02, 7.1e-03), "tangent": (1.5e-02, 7.2e-03), "adjoint": (1.4e-02, 7.2e-03)},
+    ("epi_geglu", F16): {"primal": (1.4e-03, 8.8e-04), "tangent": (1.8e-03, 9.0e-04), "adjoint": (1.7e-03, 9.0e-04)},
+    ("epi_geglu_fwd", F32): {"primal": (8.4e-07, 6.0e-07)},
+    ("epi_geglu_fwd", BF): {"primal": (1.3e-02, 7.1e-03)},
+    ("epi_geglu_fwd", F16): {"primal": (1.4e-03, 8.8e-04)},
+    ("epi_ln", F32): {"primal": (1.0e-06, 7.1e-07), "tangent": (1.2e-06, 7.8e-07), "adjoint": (9.2e-07, 7.3e-07)},
+    ("epi_ln", BF): {"primal": (8.0e-03, 6.1e-03), "tangent": (9.1e-03, 6.5e-03), "adjoint": (8.5e-03, 6.3e-03)},
+    ("epi_ln", F16): {"primal": (1.1e-03, 7.4e-04), "tangent": (1.2e-03, 8.2e-04), "adjoint": (1.1e-03, 8.0e-04)},
 }
 
 
