@@ -17,8 +17,12 @@ rows before it and one after it.
 directions of every basis matched one to one and sign by sign to an anchor's by a batched assignment solver on the device, and the matched unit
 vectors averaged in one streaming pass -- a mean of directions, where the Frechet mean is a mean of subspaces.
 
-There are still no public exponential / logarithm maps: they exist only inside the mean's iteration, on coefficients.  There is no CPU fallback:
-inputs live on a HIP device.
+``principal_vectors``, ``grassmann_log``, ``grassmann_geodesic`` and ``grassmann_exp`` are the geodesics of the Grassmannian between pairs of such
+bases (``csrc/geodesic.hip``): which directions two tangent spaces share, the tangent that leads from one to the other, the points of the geodesic
+between them (interpolated or extrapolated) and the geodesic shot from a space along a tangent -- per pair from the exact fp64 Grams, then one
+streaming pass that holds both rotated tiles in registers and writes every output slice from them.
+
+There is no CPU fallback: inputs live on a HIP device.
 """
 from __future__ import annotations
 
@@ -276,6 +280,108 @@ def frechet_mean(A: torch.Tensor, init: int = 0, max_iter: int = 1000, tol: floa
         j = int(worst[0])
         raise L.DpbError(f"frechet_mean: the cost rose from {cost[j]!r} to {cost[j + 1]!r} at step {j + 1}: use a smaller step than {step}")
     return Y, info
+
+
+CUT_LOCUS = "pairs at the cut locus (largest principal angle above pi/2 - 1e-6: the geodesic is not unique there)"
+
+
+def _times(ts) -> list:
+    ts = [float(ts)] if isinstance(ts, (int, float)) else [float(t) for t in ts]
+    if not 1 <= len(ts) <= 64:
+        raise ValueError(f"ts must hold 1 .. 64 parameters, got {len(ts)}")
+    return ts
+
+
+def _grassmann_call(X, Y, mode: int, ts, check: bool, max_bytes: Optional[int], names: Tuple[str, str]):
+    """the one driver of the four public calls: mode 0 principal vectors, 1 log, 2 geodesic (dpb_grassmann_pair), 3 exp (dpb_grassmann_exp)"""
+    lib = L.load()
+    X, Y = _device_f32(X, names[0]), _device_f32(Y, names[1])       # (both on a device before any shape is judged: no CPU fallback)
+    broadcast = mode != 3 and X.dim() == 2 and Y.dim() == 3
+    X = _stack(X, names[0])
+    Y = _stack(Y, names[1]).to(X.device)
+    d, k, n = Y.shape
+    if tuple(X.shape[1:]) != (k, n) or (X.shape[0] != d and not broadcast):
+        raise ValueError(f"{names[1]} holds {d} bases of k = {k} rows of length N = {n}: {names[0]} must be [{d}, {k}, {n}]"
+                         + ("" if mode == 3 else f" or one basis [{k}, {n}]") + f", got {tuple(X.shape)}")
+    if k > FRECHET_MAX_RANK:
+        raise ValueError(f"k = {k} rows per basis exceeds the rank {FRECHET_MAX_RANK} the Grassmann geodesics support")
+    if k > n:
+        raise ValueError(f"k = {k} rows per basis exceeds their length N = {n}: they cannot be independent")
+    timed = mode >= 2
+    ts = _times(ts) if timed else []
+    j = len(ts) if timed else 2
+    max_bytes = DEFAULT_MAX_BYTES if max_bytes is None else int(max_bytes)
+    need = int(lib.dpb_grassmann_scratch_bytes(d, j, k, n))
+    if need == 0:
+        raise L.DpbError(f"dpb_grassmann does not take D = {d}, J = {j}, k = {k}, N = {n}")
+    if need > max_bytes:
+        raise ValueError(f"the Grassmann geodesics of D = {d} pairs of k = {k} rows need {need} bytes of device scratch, max_bytes is {max_bytes}")
+    with torch.cuda.device(X.device):
+        st = C.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
+        scratch = torch.empty(need, dtype=torch.uint8, device=X.device)
+        spec = torch.empty(d, k, dtype=torch.float32, device=X.device)
+        flags = torch.empty(d, dtype=torch.int32, device=X.device)
+        tarr = (C.c_double * max(len(ts), 1))(*ts)
+        if timed:
+            out0 = torch.empty(d, j, k, n, dtype=torch.float32, device=X.device)
+            out1 = None
+        else:
+            out0 = torch.empty(d, k, n, dtype=torch.float32, device=X.device)
+            out1 = torch.empty(d, k, n, dtype=torch.float32, device=X.device)
+        if mode == 3:
+            L.check(lib.dpb_grassmann_exp(X.data_ptr(), Y.data_ptr(), d, k, n, tarr, j, out0.data_ptr(), spec.data_ptr(), flags.data_ptr(),
+                                          scratch.data_ptr(), need, st))
+        else:
+            L.check(lib.dpb_grassmann_pair(X.data_ptr(), 0 if broadcast else k * n, Y.data_ptr(), d, k, n, mode, tarr, j, out0.data_ptr(),
+                                           None if out1 is None else out1.data_ptr(), spec.data_ptr(), flags.data_ptr(), scratch.data_ptr(), need, st))
+    if check:
+        fl = flags.cpu().numpy()                                    # the one host sync
+        if (fl == 1).any():
+            raise ValueError(f"{DEGENERATE}: indices {np.nonzero(fl == 1)[0].tolist()}")
+        if (fl == 2).any():
+            raise ValueError(f"{CUT_LOCUS}: indices {np.nonzero(fl == 2)[0].tolist()}")
+    return out0, out1, spec
+
+
+def principal_vectors(A: torch.Tensor, B: torch.Tensor, check: bool = True, max_bytes: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The principal vectors of the pairs (A[d], B[d]): Pa [D, k, N] in span A[d] and Pb [D, k, N] in span B[d], both with orthonormal rows, and
+    theta [D, k] (fp32, descending: the order of subspace_angles) with Pa[d] Pb[d]^T = diag(cos theta[d]), cos theta >= 0 -- row i of the two is the
+    pair of directions the spaces hold at angle theta_i (dpb_grassmann_pair, mode 0; see include/dpb.h for the method, the sign rule and the limits).
+
+    Layout: ROWS.  A and B [D, k, N]; A [k, N] against a stack B [D, k, N] is broadcast; [k, N] with [k, N] is D = 1 (the leading axis is kept).  Rows
+    need not be orthonormal, only independent; any float dtype is converted to contiguous fp32; k <= 64.  A pair's result is bitwise the same alone,
+    at any position of a stack and broadcast.  check: raise ValueError naming the degenerate pairs, or the pairs at the cut locus (largest angle
+    above pi/2 - 1e-6); one host sync -- False returns their NaNs.  No CPU fallback."""
+    pa, pb, theta = _grassmann_call(A, B, 0, None, check, max_bytes, ("A", "B"))
+    return pa, pb, theta
+
+
+def grassmann_log(A: torch.Tensor, B: torch.Tensor, check: bool = True, max_bytes: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The log map at span A[d] of span B[d] as (P, H, theta): P [D, k, N] an orthonormal basis of span A[d] (the principal vectors on A's side) and H
+    [D, k, N] the images of its rows -- the tangent is the linear map p_i -> h_i = (theta_i / sin theta_i)(pb_i - cos theta_i p_i).  h_i is orthogonal
+    to span A[d], ||h_i|| = theta_i, and ||H[d]||_F is the geodesic distance.  grassmann_exp(P, H, t) walks the geodesic: t = 1 arrives at span B[d].
+    Pairing, inputs, check and limits as principal_vectors (dpb_grassmann_pair, mode 1)."""
+    p, h, theta = _grassmann_call(A, B, 1, None, check, max_bytes, ("A", "B"))
+    return p, h, theta
+
+
+def grassmann_geodesic(A: torch.Tensor, B: torch.Tensor, ts, check: bool = True, max_bytes: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Points of the geodesic from span A[d] (t = 0) to span B[d] (t = 1): Y [D, T, k, N] with orthonormal rows, Y[d, j] a basis of the point at
+    ts[j], and theta [D, k].  ts: a float or a sequence of up to 64; any real t (beyond [0, 1] the geodesic is extrapolated).  Row i of Y[d, j] is
+    sin((1 - t) theta_i) / sin theta_i pa_i + sin(t theta_i) / sin theta_i pb_i over the principal vectors; all T slices are written from one pass
+    over the 2k rows.  Pairing, inputs, check and limits as principal_vectors (dpb_grassmann_pair, mode 2)."""
+    y, _, theta = _grassmann_call(A, B, 2, ts, check, max_bytes, ("A", "B"))
+    return y, theta
+
+
+def grassmann_exp(P: torch.Tensor, H: torch.Tensor, ts, check: bool = True, max_bytes: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The exp map: the geodesic shot from span P[d] along the tangent (P[d], H[d]), at ts: Y [D, T, k, N] with orthonormal rows and sigma [D, k]
+    (fp32, descending: the singular values of the tangent, ||sigma||_2 the speed).  P [D, k, N] any independent rows, H [D, k, N] anything: the tangent
+    is the linear map p_i -> the component of h_i orthogonal to span P[d].  With (P, H) of grassmann_log(A, B), Y at t reproduces
+    grassmann_geodesic(A, B, t) as a subspace.  No domain limit.  check: raise ValueError naming the pairs whose P is degenerate; one host sync --
+    False returns their NaNs (dpb_grassmann_exp; see include/dpb.h).  No CPU fallback."""
+    y, _, sigma = _grassmann_call(P, H, 3, ts, check, max_bytes, ("P", "H"))
+    return y, sigma
 
 
 def linear_assignment(cost: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -110,6 +110,10 @@ SYMBOLS = {
     "dpb_frechet_init": (_I, [_P, _I, _I, _L, _I, _I, _P, C.c_size_t, _P]),
     "dpb_frechet_iterate": (_I, [_I, C.c_double, C.c_double, _I, _I, _L, _I, _P, C.c_size_t, _P]),
     "dpb_frechet_finish": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _P, C.c_size_t, _P]),
+    # Grassmann geodesics (geometry.principal_vectors / grassmann_log / grassmann_geodesic / grassmann_exp): ts is a host double array
+    "dpb_grassmann_scratch_bytes": (C.c_size_t, [_I, _I, _I, _L]),
+    "dpb_grassmann_pair": (_I, [_P, _L, _P, _I, _I, _L, _I, C.POINTER(C.c_double), _I, _P, _P, _P, _P, _P, C.c_size_t, _P]),
+    "dpb_grassmann_exp": (_I, [_P, _P, _I, _I, _L, C.POINTER(C.c_double), _I, _P, _P, _P, _P, C.c_size_t, _P]),
     # Hungarian-matched mean of directions (geometry.linear_assignment / hungarian_mean): the batched solver, one sweep, the fp64 row sums of squares
     "dpb_linear_assignment_scratch_bytes": (C.c_size_t, [_I, _I]),
     "dpb_linear_assignment": (_I, [_P, _I, _I, _P, _P, _P, C.c_size_t, _P]),

@@ -317,6 +317,43 @@ int dpb_frechet_iterate(int n_iter, double step, double tol, int B, int k, int64
 int dpb_frechet_finish(const float* X, float* Y, float* weight, float* theta, double* info, int B, int k, int64_t N, int max_iter, void* scratch,
                        size_t scratch_bytes, void* hip_stream);
 
+/* ---- Grassmann geodesics: principal vectors, log and exp maps (additive to ABI version 1; engine-independent) --------------------------
+ * Pairs (A_d, B_d), d < D, of bases of k rows in R^N, fp32, rows independent but not necessarily orthonormal (ROWS convention).  a_stride = k N:
+ * A [D][k][N]; a_stride = 0: one A [k][N] paired with every B_d.  Everything between input and output is fp64 (csrc/geodesic.hip).
+ * Method, per pair, from the exact Grams A A^T, B B^T, A B^T (dpb_cross_gram) and the whitenings Wa, Wb of dpb_subspace_angles:
+ *   M = Wa (A B^T) Wb^T;  I - M M^T = V sin^2(theta) V^T (two-sided Jacobi with vectors);  U = V^T M, row i of norm cos(theta_i);  theta from
+ *   asin(sqrt(lambda)) for lambda <= 1/2 and from acos ||U_i|| above, DESCENDING with ties by index (the order of dpb_subspace_angles);
+ *   principal vectors Pa = (V^T Wa) A, Pb = (diag(1 / cos theta) U Wb) B: orthonormal rows, Pa Pb^T = diag(cos theta), cos theta >= 0; sign: the
+ *   entry of largest magnitude of each row of V^T (lowest index on ties) is positive.
+ *   Every output row is alpha_i pa_i + beta_i pb_i, formed in fp64 from the two rotated tiles in ONE pass over the 2k rows (fp64 matrix cores, rows
+ *   summed in index order) and rounded to fp32 once:
+ *     mode 2, geodesic from span A (t = 0) to span B (t = 1), any real t: alpha = sin((1 - t) theta) / sin theta, beta = sin(t theta) / sin theta
+ *       (1 - t and t where sin theta = 0);
+ *     mode 1, log map: the tangent at span A is the linear map pa_i -> h_i = (theta_i / sin theta_i)(pb_i - cos theta_i pa_i); h_i is orthogonal to
+ *       span A, ||h_i|| = theta_i, ||H||_F the geodesic distance.
+ *   out0 / out1: mode 0: Pa, Pb, each [D][k][N]; mode 1: Pa, H; mode 2: Y [D][J][k][N] at ts[0 .. J) (a HOST array), out1 NULL.  theta [D][k] fp32.
+ * dpb_grassmann_exp: P_d, H_d [k][N] (each [D][k][N]); the tangent at span P is the linear map p_i -> the component of h_i orthogonal to span P (well
+ *   defined for a non-orthonormal P; H is arbitrary).  With W the whitening of P, Q = W P, K = (W H) Q^T and Hq = W H - K Q as coefficients on the 2k
+ *   given rows: Hq Hq^T = W (H H^T) W^T - K K^T = V sigma^2 V^T (Jacobi), sigma descending, and row i of Y[d][j] is
+ *   cos(t_j sigma_i) (V^T Q)_i + (sin(t_j sigma_i) / sigma_i) (V^T Hq)_i (the second coefficient is t_j at sigma_i = 0).  sigma [D][k] fp32.  No
+ *   domain limit.  exp of the (P, H) of mode 1 reproduces the geodesic of mode 2 as a subspace.
+ * flags [D]: 0 ok; 1 a degenerate basis of the pair (the whitening's rule: a zero or non-finite row, a Cholesky pivot of the row-normalised Gram
+ *   below 1e-10); 2 (dpb_grassmann_pair only) the largest principal angle exceeds pi/2 - 1e-6: the geodesic is not unique at the cut locus and
+ *   1 / cos theta is unbounded.  A flagged pair has NaN in ALL its outputs; it spoils no other pair.
+ * Reproducibility: no atomics, every sum one fixed chain: a pair's result is bitwise the same alone, at any position of any stack, and with A
+ *   broadcast (a_stride = 0).
+ * Limits: 1 <= k <= 64 (three k x k fp64 matrices and the Jacobi workspace live in LDS), k <= N, 1 <= D <= 65535, 1 <= J <= 64, a_stride in {0, k N}.
+ *   scratch: 256-byte aligned device memory of scratch_bytes >= dpb_grassmann_scratch_bytes(D, J, k, N) (checked; J = 2 for modes 0 and 1).  The
+ *   accuracy is that of the Gram route: a general mixing of the rows of condition c loses sqrt(eps) c at small angles (row scaling does not: the
+ *   whitening removes it first).  Outputs must not alias inputs or scratch.  No device allocation, no host synchronisation.  Errors via dpb_last_error. */
+size_t dpb_grassmann_scratch_bytes(int D, int J, int k, int64_t N);          /* 0 when invalid (k outside [1, 64], k > N, ...) */
+int dpb_grassmann_pair(const float* A, int64_t a_stride /*0: one A for all D*/, const float* B, int D, int k, int64_t N,
+                       int mode /*0 principal vectors, 1 log, 2 geodesic*/, const double* ts /*host [J], mode 2*/, int J,
+                       float* out0, float* out1, float* theta /*[D][k]*/, int32_t* flags /*[D]: 0 ok, 1 degenerate, 2 domain*/,
+                       void* scratch, size_t scratch_bytes, void* hip_stream);
+int dpb_grassmann_exp(const float* P, const float* H, int D, int k, int64_t N, const double* ts /*host [J]*/, int J,
+                      float* Y /*[D][J][k][N]*/, float* sigma /*[D][k]*/, int32_t* flags, void* scratch, size_t scratch_bytes, void* hip_stream);
+
 /* ---- the Hungarian-matched mean of directions (additive to ABI version 1; engine-independent) -----------------------------------------
  * The global basis of run_edit_global_hungarian_mean_zt (src/modules/edit.py:1249-1514; the reference calls a compute_hungarian_basis it never
  * defines, with initial_local_basis_idx=0, distance='1/cosine').  Where the Frechet mean averages subspaces, this one averages DIRECTIONS: the k rows
