@@ -13,6 +13,7 @@
 // both functions of N only -- so an entry does not depend on the number of rows, on the tile it falls in or on the launch; the small algebra sums
 // sequentially per element.  theta of a pair is therefore a function of the 2k rows of the pair and of N, bitwise.
 #include "kernels.h"
+#include "geom.h"
 
 namespace dpb {
 
@@ -221,35 +222,39 @@ __global__ __launch_bounds__(256) void angles_prep_kernel(double* Dg, int* flags
 
 // the whitening of n bases in place (also the Frechet mean's, frechet.hip): Dg [n][k][k] Gram blocks -> W, flags [n]; 1 <= k <= ORTH_MAX_RANK
 void launch_angles_prep(double* Dg, int* flags, int n, int k, hipStream_t st) {
-  if (k <= 16) DPB_LAUNCH((angles_prep_kernel<16>), dim3(n), dim3(256), 0, st, Dg, flags, k);
-  else if (k <= 32) DPB_LAUNCH((angles_prep_kernel<32>), dim3(n), dim3(256), 0, st, Dg, flags, k);
-  else if (k <= 64) DPB_LAUNCH((angles_prep_kernel<64>), dim3(n), dim3(256), 0, st, Dg, flags, k);
-  else DPB_LAUNCH((angles_prep_kernel<ORTH_MAX_RANK>), dim3(n), dim3(256), 0, st, Dg, flags, k);
+  DPB_BY_RANK128(k, (void)NT; DPB_LAUNCH((angles_prep_kernel<KM>), dim3(n), dim3(256), 0, st, Dg, flags, k));
+}
+
+// one workgroup per block b of a stacked Gram: dst[b][r][c] = G[(b rstep + r) ld + b k + c] (launch_gram_blocks, kernels.h; also frechet.hip, geodesic.hip)
+__global__ __launch_bounds__(256) void gram_blocks_kernel(const double* G, double* dst, long ld, int rstep, int k) {
+  const long b = blockIdx.x;
+  for (int e = threadIdx.x; e < k * k; e += 256) dst[b * k * k + e] = G[(b * rstep + e / k) * ld + b * k + e % k];
+}
+
+void launch_gram_blocks(const double* G, double* dst, int n, long ld, int rstep, int k, hipStream_t st) {
+  DPB_LAUNCH(gram_blocks_kernel, dim3(n), dim3(256), 0, st, G, dst, ld, rstep, k);
 }
 
 // ------------------------------------------------------------------------------------------------------------ per pair: angles
 // Workgroups walk the pairs p = blockIdx.x, blockIdx.x + gridDim.x, ...; pair (i, j) = (p / Bb, p % Bb).  T = W_i G_ij and M = T W_j^T go through this
 // workgroup's two k x k slots of global scratch (L2), S = I - M M^T lives in LDS, its eigenvalues come from a two-sided Jacobi iteration in the round-robin
-// order (floor(k/2) disjoint rotations per step; the ordering and thresholds of orth.hip's eigen-solve, without eigenvectors).
+// order (jacobi_round_robin of geom.h, without eigenvectors).
 template <int KMAX, int NT>
 __global__ __launch_bounds__(NT) void angles_pair_kernel(const double* Wa, const double* Wb, const int* fa, const int* fb, const double* Gab, long ldg,
                                                          double* work, float* theta, float* dist, int Ba, int Bb, int k, int self) {
-  constexpr int NW = NT / 64;
   __shared__ double A[KMAX][KMAX + 1];
-  __shared__ double rc[KMAX / 2 + 1], rsn[KMAX / 2 + 1], lam[KMAX], th[KMAX], red[2][NW];
-  __shared__ int rp[KMAX / 2 + 1], rq[KMAX / 2 + 1];
-  static_assert(sizeof(double) * (KMAX * (KMAX + 1) + 2 * (KMAX / 2 + 1) + 2 * KMAX + 2 * NW) + sizeof(int) * 2 * (KMAX / 2 + 1) <= 160 * 1024,
-                "angles_pair_kernel exceeds the gfx950 LDS");
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  __shared__ double lam[KMAX], th[KMAX];
+  __shared__ JacobiWs<KMAX> ws;
+  static_assert(sizeof(double) * (KMAX * (KMAX + 1) + 2 * KMAX) + sizeof(JacobiWs<KMAX>) <= 160 * 1024, "angles_pair_kernel exceeds the gfx950 LDS");
+  const int t = threadIdx.x;
   double* const Tm = work + (long)blockIdx.x * 2 * k * k;
   double* const Mm = Tm + (long)k * k;
-  const double nan = __longlong_as_double(0x7ff8000000000000LL);
   for (long p = blockIdx.x; p < (long)Ba * Bb; p += gridDim.x) {
     const int i = (int)(p / Bb), j = (int)(p % Bb);
     if (self && i > j) continue;
     const bool degenerate = fa[i] != 0 || fb[j] != 0;
     if (degenerate || (self && i == j)) {          // NaN for a degenerate basis's row and column; the self-mode diagonal is exactly 0
-      const float v = degenerate ? (float)nan : 0.f;
+      const float v = degenerate ? (float)nan64() : 0.f;
       for (int e = t; e < k; e += NT) {
         theta[((long)i * Bb + j) * k + e] = v;
         if (self) theta[((long)j * Bb + i) * k + e] = v;
@@ -285,73 +290,15 @@ __global__ __launch_bounds__(NT) void angles_pair_kernel(const double* Wa, const
       }
     }
     __syncthreads();
-    const int m = (k + 1) & ~1, half = m / 2, steps = m - 1;      // players 0 .. m-1 (player k is a bye when k is odd)
-    for (int sweep = 0; sweep < 30 && k > 1; ++sweep) {
-      double off = 0, diag = 0;                    // converged when the off-diagonal mass is negligible: fixed-order reduction, uniform result
-      for (int r = wave; r < k; r += NW)
-        for (int c = lane; c < k; c += 64) {
-          const double v = A[r][c] * A[r][c];
-          if (r == c) diag += v; else if (r < c) off += v;
-        }
-      for (int o = 32; o > 0; o >>= 1) { off += __shfl_xor(off, o, 64); diag += __shfl_xor(diag, o, 64); }
-      if (lane == 0) { red[0][wave] = off; red[1][wave] = diag; }
-      __syncthreads();
-      off = 0; diag = 0;
-#pragma unroll
-      for (int w = 0; w < NW; ++w) { off += red[0][w]; diag += red[1][w]; }
-      __syncthreads();
-      if (off <= 1e-28 * diag) break;
-      for (int st = 0; st < steps; ++st) {
-        if (t < half) {                            // the step's pairs and their angles
-          int pp = t == 0 ? m - 1 : (st + t) % (m - 1);
-          int qq = t == 0 ? st % (m - 1) : (st - t + (m - 1)) % (m - 1);
-          if (pp > qq) { const int w = pp; pp = qq; qq = w; }
-          double c = 1.0, s = 0.0;
-          if (qq < k) {
-            const double apq = A[pp][qq], app = A[pp][pp], aqq = A[qq][qq];
-            if (!(fabs(apq) <= 1e-300 || fabs(apq) <= 1e-18 * sqrt(fabs(app * aqq)))) {
-              const double tau = (aqq - app) / (2.0 * apq);
-              const double tt = (tau >= 0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(tau * tau + 1.0));
-              c = 1.0 / sqrt(tt * tt + 1.0); s = tt * c;
-            }
-          }
-          rp[t] = pp; rq[t] = qq < k ? qq : pp; rc[t] = c; rsn[t] = s;      // (bye or negligible element: s = 0, skipped below)
-        }
-        __syncthreads();
-        for (int h = wave; h < half; h += NW) {    // A <- A J: the wave takes rotation h, its lanes the rows
-          const int pp = rp[h], qq = rq[h];
-          const double c = rc[h], s = rsn[h];
-          if (s == 0.0) continue;                  // wave-uniform
-          for (int r = lane; r < k; r += 64) {
-            const double arp = A[r][pp], arq = A[r][qq];
-            A[r][pp] = c * arp - s * arq;
-            A[r][qq] = s * arp + c * arq;
-          }
-        }
-        __syncthreads();
-        for (int h = wave; h < half; h += NW) {    // A <- J^T A: its lanes the columns
-          const int pp = rp[h], qq = rq[h];
-          const double c = rc[h], s = rsn[h];
-          if (s == 0.0) continue;
-          for (int r = lane; r < k; r += 64) {
-            const double apr = A[pp][r], aqr = A[qq][r];
-            A[pp][r] = c * apr - s * aqr;
-            A[qq][r] = s * apr + c * aqr;
-          }
-        }
-        __syncthreads();
-      }
-    }
+    jacobi_round_robin<KMAX, NT>(A, JacobiNoVecs{}, ws, k);
     if (t < k) {
       const double l = A[t][t];
       lam[t] = l < 0.0 ? 0.0 : (l > 1.0 ? 1.0 : l);          // (a NaN stays a NaN and reaches the output)
     }
     __syncthreads();
     if (t < k) {                                   // descending; ties by index (rank counting)
-      int rank = 0;
       const double mine = lam[t];
-      for (int e = 0; e < k; ++e) rank += (lam[e] > mine || (lam[e] == mine && e < t)) ? 1 : 0;
-      th[rank] = mine <= 0.5 ? asin(sqrt(mine)) : acos(sqrt(1.0 - mine));
+      th[rank_desc<false>(lam, k, t)] = mine <= 0.5 ? asin(sqrt(mine)) : acos(sqrt(1.0 - mine));
     }
     __syncthreads();
     for (int e = t; e < k; e += NT) {
@@ -376,16 +323,15 @@ namespace {
 struct AnglesLayout { size_t gab = 0, wa = 0, wb = 0, flags = 0, work = 0, total = 0; long nblk = 0; };
 bool angles_layout(long Ba, long Bb, int k, long N, AnglesLayout& l) {
   if (Ba < 1 || Bb < 1 || Ba > ANGLES_MAX_BASES || Bb > ANGLES_MAX_BASES || k < 1 || k > ORTH_MAX_RANK || N < 1 || k > N) return false;
-  size_t off = 0;
-  auto take = [&](size_t b) { const size_t o = off; off += (b + 255) / 256 * 256; return o; };
+  ScratchCarver s;
   const size_t kk = (size_t)k * k * sizeof(double);
   l.nblk = Ba * Bb < ANGLES_PAIR_BLOCKS ? Ba * Bb : ANGLES_PAIR_BLOCKS;
-  l.gab = take((size_t)Ba * k * (size_t)Bb * k * sizeof(double));
-  l.wa = take((size_t)Ba * kk);
-  l.wb = take((size_t)Bb * kk);
-  l.flags = take((size_t)(Ba + Bb) * sizeof(int));
-  l.work = take((size_t)l.nblk * 2 * kk);
-  l.total = off;
+  l.gab = s.take((size_t)Ba * k * (size_t)Bb * k * sizeof(double));
+  l.wa = s.take((size_t)Ba * kk);
+  l.wb = s.take((size_t)Bb * kk);
+  l.flags = s.take((size_t)(Ba + Bb) * sizeof(int));
+  l.work = s.take((size_t)l.nblk * 2 * kk);
+  l.total = s.off;
   return true;
 }
 }  // namespace
@@ -404,11 +350,7 @@ int launch_subspace_angles(const float* A, const float* B, long Ba, long Bb, int
   }
   const bool self = B == nullptr;
   if (self && Ba != Bb) { set_error("dpb_subspace_angles: B = NULL (self mode) needs Bb = Ba, got Ba=%ld, Bb=%ld", Ba, Bb); return -1; }
-  if ((uintptr_t)scratch % 256) { set_error("dpb_subspace_angles: scratch must be 256-byte aligned"); return -1; }
-  if (scratch_bytes < l.total) {
-    set_error("dpb_subspace_angles: scratch of %zu bytes, dpb_subspace_angles_scratch_bytes(%ld, %ld, %d, %ld) = %zu needed", scratch_bytes, Ba, Bb, k, N, l.total);
-    return -1;
-  }
+  if (check_scratch("dpb_subspace_angles", scratch, scratch_bytes, l.total, "dpb_subspace_angles_scratch_bytes(%ld, %ld, %d, %ld)", Ba, Bb, k, N) != 0) return -1;
   if ((Ba * k + GT - 1) / GT > 65535) { set_error("dpb_subspace_angles: Ba * k = %ld above %d rows", Ba * k, 65535 * GT); return -1; }
   char* base = (char*)scratch;
   double* Gab = (double*)(base + l.gab);
@@ -426,10 +368,7 @@ int launch_subspace_angles(const float* A, const float* B, long Ba, long Bb, int
   launch_angles_prep(Wa, fa, (int)Ba, k, st);
   if (!self) launch_angles_prep(Wb, fb, (int)Bb, k, st);
   const dim3 pg((unsigned)l.nblk);
-  if (k <= 16) DPB_LAUNCH((angles_pair_kernel<16, 256>), pg, dim3(256), 0, st, Wa, Wb, fa, fb, Gab, (long)Rb, work, theta, dist, (int)Ba, (int)Bb, k, sf);
-  else if (k <= 32) DPB_LAUNCH((angles_pair_kernel<32, 1024>), pg, dim3(1024), 0, st, Wa, Wb, fa, fb, Gab, (long)Rb, work, theta, dist, (int)Ba, (int)Bb, k, sf);
-  else if (k <= 64) DPB_LAUNCH((angles_pair_kernel<64, 1024>), pg, dim3(1024), 0, st, Wa, Wb, fa, fb, Gab, (long)Rb, work, theta, dist, (int)Ba, (int)Bb, k, sf);
-  else DPB_LAUNCH((angles_pair_kernel<ORTH_MAX_RANK, 1024>), pg, dim3(1024), 0, st, Wa, Wb, fa, fb, Gab, (long)Rb, work, theta, dist, (int)Ba, (int)Bb, k, sf);
+  DPB_BY_RANK128(k, DPB_LAUNCH((angles_pair_kernel<KM, NT>), pg, dim3(NT), 0, st, Wa, Wb, fa, fb, Gab, (long)Rb, work, theta, dist, (int)Ba, (int)Bb, k, sf));
   DPB_CHECK(hipGetLastError());
   return 0;
 }

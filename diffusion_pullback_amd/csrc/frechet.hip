@@ -13,11 +13,9 @@
 // on R only and the four partial sums are added in wave order; sums over the bases run in index order.  A step reads and writes device state only, so
 // iterate(a) then iterate(b) is bitwise iterate(a + b).
 #include "kernels.h"
-#include "fr_jacobi.h"
+#include "geom.h"
 
 namespace dpb {
-
-typedef double fr_d4 __attribute__((ext_vector_type(4)));
 
 struct FrCtl {            // the first bytes of the scratch block (documented in dpb.h: the caller may read them)
   int done;               // 0 running, 1 converged (g < tol), 2 a basis left the log map's domain, 3 the history is full
@@ -30,25 +28,7 @@ struct FrCtl {            // the first bytes of the scratch block (documented in
 constexpr double FR_HALF_PI = 1.57079632679489661923;
 constexpr double FR_DOMAIN = FR_HALF_PI - 1e-6;      // a largest principal angle beyond this is outside the log map's domain
 
-__device__ inline double fr_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-// the descending order of the rank counting: a NaN sorts before every number and ties go by index, so the ranks are a permutation whatever the values
-__device__ inline bool fr_before(double other, double mine, bool other_first) {
-  const bool on = other != other, mn = mine != mine;
-  if (on || mn) return on && (!mn || other_first);
-  return other > mine || (other == mine && other_first);
-}
-
-// ------------------------------------------------------------------------------------------------------------ the eigen-solve
-// fr_jacobi / FrJacobiWs: fr_jacobi.h (shared with geodesic.hip)
-
 // ------------------------------------------------------------------------------------------------------------ init
-// each basis's diagonal block of G into the slot its whitening matrix will take
-__global__ __launch_bounds__(256) void fr_diag_copy_kernel(const double* G, double* W, int R, int k) {
-  const long i = blockIdx.x;
-  for (int e = threadIdx.x; e < k * k; e += 256) W[i * k * k + e] = G[(i * k + e / k) * R + i * k + e % k];
-}
-
 // block (i, j), i <= j, of G in place: Ghat_ij = W_i G_ij W_j^T, mirrored into (j, i); the diagonal blocks are the identity; a degenerate basis's blocks NaN
 template <int KMAX>
 __global__ __launch_bounds__(256) void fr_whiten_kernel(double* G, const double* W, const int* flags, int R, int k) {
@@ -58,7 +38,7 @@ __global__ __launch_bounds__(256) void fr_whiten_kernel(double* G, const double*
   double* Gij = G + ((long)i * k) * R + (long)j * k;
   double* Gji = G + ((long)j * k) * R + (long)i * k;
   if (flags[i] || flags[j]) {
-    for (int e = t; e < k * k; e += 256) { Gij[(long)(e / k) * R + e % k] = fr_nan(); Gji[(long)(e % k) * R + e / k] = fr_nan(); }
+    for (int e = t; e < k * k; e += 256) { Gij[(long)(e / k) * R + e % k] = nan64(); Gji[(long)(e % k) * R + e / k] = nan64(); }
     return;
   }
   if (i == j) {
@@ -105,9 +85,9 @@ __global__ __launch_bounds__(256) void fr_product_kernel(const double* G, const 
   const int c0 = blockIdx.x * 16;
   const int steps = (R + 3) / 4, q = (steps + 3) / 4;
   const int s0 = wave * q, s1 = s0 + q < steps ? s0 + q : steps;
-  fr_d4 acc[KT];
+  geom_d4 acc[KT];
 #pragma unroll
-  for (int m = 0; m < KT; ++m) acc[m] = fr_d4{0.0, 0.0, 0.0, 0.0};
+  for (int m = 0; m < KT; ++m) acc[m] = geom_d4{0.0, 0.0, 0.0, 0.0};
   const bool cok = c0 + j < R;
   for (int s = s0; s < s1; ++s) {
     const int r = 4 * s + g;
@@ -143,8 +123,8 @@ __global__ __launch_bounds__(NT) void fr_basis_kernel(const double* Mt, double* 
   if (mode == 0 && ctl->done) return;
   __shared__ double A[KMAX][KMAX + 1], V[KMAX][KMAX + 1], Mm[KMAX][KMAX + 1];
   __shared__ double lam[KMAX], thr[KMAX], ths[KMAX], fv[KMAX], hv[KMAX];
-  __shared__ FrJacobiWs<KMAX> ws;
-  static_assert(sizeof(double) * (3 * KMAX * (KMAX + 1) + 5 * KMAX) + sizeof(FrJacobiWs<KMAX>) <= 160 * 1024, "fr_basis_kernel exceeds the gfx950 LDS");
+  __shared__ JacobiWs<KMAX> ws;
+  static_assert(sizeof(double) * (3 * KMAX * (KMAX + 1) + 5 * KMAX) + sizeof(JacobiWs<KMAX>) <= 160 * 1024, "fr_basis_kernel exceeds the gfx950 LDS");
   const int t = threadIdx.x;
   const long i = blockIdx.x;
   const double* Mb = Mt + i * k * k;
@@ -162,7 +142,7 @@ __global__ __launch_bounds__(NT) void fr_basis_kernel(const double* Mt, double* 
     }
   }
   __syncthreads();
-  fr_jacobi<KMAX, NT>(A, V, ws, k);
+  jacobi_lds<KMAX, NT>(A, V, ws, k);
   if (t < k) {
     const double l = A[t][t];
     lam[t] = l < 0.0 ? 0.0 : (l > 1.0 ? 1.0 : l);  // (a NaN stays a NaN)
@@ -194,12 +174,7 @@ __global__ __launch_bounds__(NT) void fr_basis_kernel(const double* Mt, double* 
     hv[t] = sn > 0.0 ? th * cs / sn : (sn == 0.0 ? 1.0 : sn);
   }
   __syncthreads();
-  if (t < k) {                                     // descending; ties by index (rank counting)
-    int rank = 0;
-    const double mine = thr[t];
-    for (int e = 0; e < k; ++e) rank += fr_before(thr[e], mine, e < t) ? 1 : 0;
-    ths[rank] = mine;
-  }
+  if (t < k) ths[rank_desc<true>(thr, k, t)] = thr[t];       // descending; ties by index (rank counting)
   __syncthreads();
   for (int e = t; e < k; e += NT) thetas[i * k + e] = ths[e];
   if (t == 0) {
@@ -280,7 +255,7 @@ template <int KMAX, int NT>
 __global__ __launch_bounds__(NT) void fr_step_head_kernel(const double* Ps, double* A1, double* A2, FrCtl* ctl, double* hist_g, int B, int k, double tau,
                                                           double tol) {
   __shared__ double A[KMAX][KMAX + 1], V[KMAX][KMAX + 1], cs[KMAX], sn[KMAX], s2[KMAX];
-  __shared__ FrJacobiWs<KMAX> ws;
+  __shared__ JacobiWs<KMAX> ws;
   __shared__ int conv;
   const int done = ctl->done;
   __syncthreads();
@@ -295,7 +270,7 @@ __global__ __launch_bounds__(NT) void fr_step_head_kernel(const double* Ps, doub
     }
   }
   __syncthreads();
-  fr_jacobi<KMAX, NT>(A, V, ws, k);
+  jacobi_lds<KMAX, NT>(A, V, ws, k);
   if (t < k) {
     const double l = A[t][t];
     s2[t] = l < 0.0 ? 0.0 : l;
@@ -366,7 +341,7 @@ __global__ __launch_bounds__(256) void fr_apply_kernel(double* Ct, const double*
     const int b = e / k, a = e % k;
     double s = 0.0;
     for (int c = 0; c <= a; ++c) s += Wn[a * k + c] * Cn[base + b * k + c];
-    Ct[base + e] = nb ? fr_nan() : s;
+    Ct[base + e] = nb ? nan64() : s;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) { ctl->iters += 1; if (nb) ctl->reorth_bad = 1; }
 }
@@ -378,7 +353,7 @@ __global__ __launch_bounds__(NT) void fr_finish_head_kernel(const double* Ps, co
                                                             double* hist_cost, const double* hist_g, double* Rot, float* weight, float* theta, double* info,
                                                             int B, int k, long cap) {
   __shared__ double A[KMAX][KMAX + 1], V[KMAX][KMAX + 1], lam[KMAX];
-  __shared__ FrJacobiWs<KMAX> ws;
+  __shared__ JacobiWs<KMAX> ws;
   const int t = threadIdx.x;
   for (int e = t; e < k * k; e += NT) {
     const int r = e / k, c = e % k;
@@ -390,14 +365,12 @@ __global__ __launch_bounds__(NT) void fr_finish_head_kernel(const double* Ps, co
     }
   }
   __syncthreads();
-  fr_jacobi<KMAX, NT>(A, V, ws, k);
+  jacobi_lds<KMAX, NT>(A, V, ws, k);
   if (t < k) lam[t] = A[t][t];
   __syncthreads();
   if (t < k) {
-    int rank = 0;
-    const double mine = lam[t];
-    for (int e = 0; e < k; ++e) rank += fr_before(lam[e], mine, e < t) ? 1 : 0;
-    weight[rank] = (float)mine;
+    const int rank = rank_desc<true>(lam, k, t);
+    weight[rank] = (float)lam[t];
     for (int c = 0; c < k; ++c) Rot[rank * k + c] = V[c][t];
   }
   for (long e = t; e < (long)B * k; e += NT) theta[e] = (float)thetas[e];
@@ -439,7 +412,7 @@ __global__ __launch_bounds__(256) void fr_finish_coef_kernel(const double* Ct, c
     const int b = e / k, a = e % k;
     double s = 0.0;
     for (int c = b; c < k; ++c) s += Cp[a][c] * Wi[c * k + b];
-    Zt[base + e] = bad ? fr_nan() : s;
+    Zt[base + e] = bad ? nan64() : s;
   }
 }
 
@@ -451,35 +424,15 @@ __global__ __launch_bounds__(256) void fr_stream_kernel(const float* X, const do
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, g = lane >> 4;
   const long n0 = ((long)blockIdx.x * 4 + wave) * 64 + 4 * j;       // this lane's first column
   if (((long)blockIdx.x * 4 + wave) * 64 >= N) return;               // wave-uniform (no workgroup barrier in this kernel)
-  fr_d4 acc[KT][4];
+  geom_d4 acc[KT][4];
 #pragma unroll
   for (int m = 0; m < KT; ++m)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) acc[m][e] = fr_d4{0.0, 0.0, 0.0, 0.0};
+    for (int e = 0; e < 4; ++e) acc[m][e] = geom_d4{0.0, 0.0, 0.0, 0.0};
   for (int r0 = 0; r0 < R; r0 += 4) {
     const int r = r0 + g;
-    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < R && n0 < N) {
-      const float* p = X + (long)r * N + n0;
-      if (vec) {
-        x = *reinterpret_cast<const float4*>(p);   // (n0 % 4 == 0 and N % 4 == 0, so n0 + 3 < N)
-      } else {
-        x.x = p[0];
-        if (n0 + 1 < N) x.y = p[1];
-        if (n0 + 2 < N) x.z = p[2];
-        if (n0 + 3 < N) x.w = p[3];
-      }
-    }
-    double z[KT];
-#pragma unroll
-    for (int m = 0; m < KT; ++m) z[m] = (r < R && 16 * m + j < k) ? Zt[(long)r * k + 16 * m + j] : 0.0;
-#pragma unroll
-    for (int m = 0; m < KT; ++m) {
-      acc[m][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(z[m], (double)x.x, acc[m][0], 0, 0, 0);
-      acc[m][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(z[m], (double)x.y, acc[m][1], 0, 0, 0);
-      acc[m][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(z[m], (double)x.z, acc[m][2], 0, 0, 0);
-      acc[m][3] = __builtin_amdgcn_mfma_f64_16x16x4f64(z[m], (double)x.w, acc[m][3], 0, 0, 0);
-    }
+    const float4 x = r < R ? load4(X + (long)r * N, n0, N, vec) : make_float4(0.f, 0.f, 0.f, 0.f);
+    mfma_rows4<KT>(acc, Zt, r, r < R, j, k, x);
   }
   if (n0 >= N) return;
 #pragma unroll
@@ -488,16 +441,7 @@ __global__ __launch_bounds__(256) void fr_stream_kernel(const float* X, const do
     for (int x = 0; x < 4; ++x) {
       const int a = 16 * m + g + 4 * x;
       if (a >= k) continue;
-      float* p = Y + (long)a * N + n0;
-      const float4 v = make_float4((float)acc[m][0][x], (float)acc[m][1][x], (float)acc[m][2][x], (float)acc[m][3][x]);
-      if (vec) {
-        *reinterpret_cast<float4*>(p) = v;
-      } else {
-        p[0] = v.x;
-        if (n0 + 1 < N) p[1] = v.y;
-        if (n0 + 2 < N) p[2] = v.z;
-        if (n0 + 3 < N) p[3] = v.w;
-      }
+      store4(Y + (long)a * N, n0, N, vec, make_float4((float)acc[m][0][x], (float)acc[m][1][x], (float)acc[m][2][x], (float)acc[m][3][x]));
     }
 }
 
@@ -512,20 +456,19 @@ struct FrLayout {
 };
 bool fr_layout(long B, int k, long N, long cap, FrLayout& l) {
   if (B < 1 || B > FR_MAX_BASES || k < 1 || k > FRECHET_MAX_RANK || N < 1 || k > N || B * k > FR_MAX_ROWS || cap < 0 || cap > FR_MAX_ITER) return false;
-  size_t off = 0;
-  auto take = [&](size_t b) { const size_t o = off; off += (b + 255) / 256 * 256; return o; };
+  ScratchCarver s;
   const size_t R = (size_t)B * k, kk = (size_t)k * k * sizeof(double), rk = R * k * sizeof(double);
-  l.ctl = take(sizeof(FrCtl));
-  l.G = take(R * R * sizeof(double));
-  l.W = take((size_t)B * kk);
-  l.flags = take((2 * (size_t)B + 1) * sizeof(int));      // degenerate [B], domain [B], the re-orthonormalisation's flag
-  l.Ct = take(rk); l.CTt = take(rk); l.Mt = take(rk); l.MTt = take(rk); l.Cn = take(rk); l.Nn = take(rk);
-  l.Ps = take((size_t)B * kk);
-  l.small = take(5 * kk);                                  // H, A1, A2, Gs, Rot
-  l.thetas = take(R * sizeof(double));
-  l.costs = take((size_t)B * sizeof(double));
-  l.hist = take((2 * (size_t)cap + 1) * sizeof(double));   // cost [cap + 1], g [cap]
-  l.total = off;
+  l.ctl = s.take(sizeof(FrCtl));
+  l.G = s.take(R * R * sizeof(double));
+  l.W = s.take((size_t)B * kk);
+  l.flags = s.take((2 * (size_t)B + 1) * sizeof(int));      // degenerate [B], domain [B], the re-orthonormalisation's flag
+  l.Ct = s.take(rk); l.CTt = s.take(rk); l.Mt = s.take(rk); l.MTt = s.take(rk); l.Cn = s.take(rk); l.Nn = s.take(rk);
+  l.Ps = s.take((size_t)B * kk);
+  l.small = s.take(5 * kk);                                  // H, A1, A2, Gs, Rot
+  l.thetas = s.take(R * sizeof(double));
+  l.costs = s.take((size_t)B * sizeof(double));
+  l.hist = s.take((2 * (size_t)cap + 1) * sizeof(double));   // cost [cap + 1], g [cap]
+  l.total = s.off;
   return true;
 }
 struct FrPtrs {
@@ -550,31 +493,12 @@ int fr_check(const char* who, long B, int k, long N, long cap, const void* scrat
               FRECHET_MAX_RANK, N, FR_MAX_ROWS, cap, FR_MAX_ITER);
     return -1;
   }
-  if ((uintptr_t)scratch % 256) { set_error("%s: scratch must be 256-byte aligned", who); return -1; }
-  if (scratch_bytes < l.total) {
-    set_error("%s: scratch of %zu bytes, dpb_frechet_scratch_bytes(%ld, %d, %ld, %ld) = %zu needed", who, scratch_bytes, B, k, N, cap, l.total);
-    return -1;
-  }
-  return 0;
+  return check_scratch(who, scratch, scratch_bytes, l.total, "dpb_frechet_scratch_bytes(%ld, %d, %ld, %ld)", B, k, N, cap);
 }
-// rank classes of the LDS-resident kernels: 16 | 32 | 64 rows, 256 threads for the smallest, 1024 above (as the pair kernel of angles.hip)
-#define FR_BY_RANK(k, ...)                                                \
-  do {                                                                     \
-    if ((k) <= 16) { constexpr int KM = 16, NT = 256; __VA_ARGS__; }       \
-    else if ((k) <= 32) { constexpr int KM = 32, NT = 1024; __VA_ARGS__; } \
-    else { constexpr int KM = 64, NT = 1024; __VA_ARGS__; }                \
-  } while (0)
-#define FR_BY_TILES(k, ...)                                    \
-  do {                                                          \
-    if ((k) <= 16) { constexpr int KT = 1; __VA_ARGS__; }       \
-    else if ((k) <= 32) { constexpr int KT = 2; __VA_ARGS__; }  \
-    else if ((k) <= 48) { constexpr int KT = 3; __VA_ARGS__; }  \
-    else { constexpr int KT = 4; __VA_ARGS__; }                 \
-  } while (0)
 
 void fr_product(const FrPtrs& p, const double* In, double* Out, int R, int k, int force, hipStream_t st) {
   const dim3 grid((R + 15) / 16);
-  FR_BY_TILES(k, DPB_LAUNCH((fr_product_kernel<KT>), grid, dim3(256), 0, st, p.G, In, Out, R, k, p.ctl, force));
+  DPB_BY_TILES(k, DPB_LAUNCH((fr_product_kernel<KT>), grid, dim3(256), 0, st, p.G, In, Out, R, k, p.ctl, force));
 }
 }  // namespace
 
@@ -590,10 +514,10 @@ int launch_frechet_init(const float* X, long B, int k, long N, long max_iter, in
   const FrPtrs p = fr_ptrs(scratch, l, B, k, max_iter);
   const int R = (int)(B * k);
   if (launch_cross_gram(X, nullptr, p.G, R, R, N, st) != 0) return -1;
-  DPB_LAUNCH(fr_diag_copy_kernel, dim3((unsigned)B), dim3(256), 0, st, p.G, p.W, R, k);
+  launch_gram_blocks(p.G, p.W, (int)B, R, k, k, st);                      // each basis's diagonal block of G into the slot its whitening matrix will take
   launch_angles_prep(p.W, p.flags, (int)B, k, st);
   const dim3 wg((unsigned)B, (unsigned)B);
-  FR_BY_RANK(k, (void)NT; DPB_LAUNCH((fr_whiten_kernel<KM>), wg, dim3(256), 0, st, p.G, p.W, p.flags, R, k));
+  DPB_BY_RANK(k, (void)NT; DPB_LAUNCH((fr_whiten_kernel<KM>), wg, dim3(256), 0, st, p.G, p.W, p.flags, R, k));
   DPB_LAUNCH(fr_init_kernel, dim3((unsigned)(((long)R * k + 255) / 256)), dim3(256), 0, st, p.Ct, p.ctl, R, k, init);
   DPB_CHECK(hipGetLastError());
   return 0;
@@ -608,12 +532,12 @@ int launch_frechet_iterate(long B, int k, long N, long max_iter, int n_iter, dou
   const dim3 gb((unsigned)B), one(1), t256(256);
   for (int it = 0; it < n_iter; ++it) {
     fr_product(p, p.Ct, p.Mt, R, k, 0, st);                                                                   // M = C Ghat
-    FR_BY_RANK(k, DPB_LAUNCH((fr_basis_kernel<KM, NT>), gb, dim3(NT), 0, st, p.Mt, p.CTt, p.Ps, p.thetas, p.costs, p.dom, p.ctl, k, 0));
+    DPB_BY_RANK(k, DPB_LAUNCH((fr_basis_kernel<KM, NT>), gb, dim3(NT), 0, st, p.Mt, p.CTt, p.Ps, p.thetas, p.costs, p.dom, p.ctl, k, 0));
     DPB_LAUNCH(fr_mean_head_kernel, one, t256, 0, st, p.Ps, p.H, p.costs, p.dom, p.ctl, p.hist_cost, nb, k, max_iter);
     DPB_LAUNCH(fr_tangent_kernel, gb, t256, 0, st, p.CTt, p.Ct, p.H, p.ctl, nb, k);                           // the mean tangent's coefficients
     fr_product(p, p.CTt, p.MTt, R, k, 0, st);                                                                 // C_T Ghat
     DPB_LAUNCH(fr_block_gram_kernel, gb, t256, 0, st, p.MTt, p.CTt, p.Ps, p.ctl, k);
-    FR_BY_RANK(k, DPB_LAUNCH((fr_step_head_kernel<KM, NT>), one, dim3(NT), 0, st, p.Ps, p.A1, p.A2, p.ctl, p.hist_g, nb, k, step, tol));
+    DPB_BY_RANK(k, DPB_LAUNCH((fr_step_head_kernel<KM, NT>), one, dim3(NT), 0, st, p.Ps, p.A1, p.A2, p.ctl, p.hist_g, nb, k, step, tol));
     DPB_LAUNCH(fr_update_kernel, gb, t256, 0, st, p.Ct, p.CTt, p.Mt, p.MTt, p.A1, p.A2, p.Cn, p.Nn, p.ctl, k);   // the exp map
     DPB_LAUNCH(fr_block_gram_kernel, gb, t256, 0, st, p.Nn, p.Cn, p.Ps, p.ctl, k);
     DPB_LAUNCH(fr_sum_kernel, one, t256, 0, st, p.Ps, p.Gs, p.ctl, nb, k);
@@ -632,13 +556,13 @@ int launch_frechet_finish(const float* X, long B, int k, long N, long max_iter, 
   const int R = (int)(B * k), nb = (int)B;
   const dim3 gb((unsigned)B), one(1), t256(256);
   fr_product(p, p.Ct, p.Mt, R, k, 1, st);
-  FR_BY_RANK(k, DPB_LAUNCH((fr_basis_kernel<KM, NT>), gb, dim3(NT), 0, st, p.Mt, p.CTt, p.Ps, p.thetas, p.costs, p.dom, p.ctl, k, 1));
-  FR_BY_RANK(k, DPB_LAUNCH((fr_finish_head_kernel<KM, NT>), one, dim3(NT), 0, st, p.Ps, p.thetas, p.costs, p.flags, p.ctl, p.hist_cost, p.hist_g, p.Rot,
+  DPB_BY_RANK(k, DPB_LAUNCH((fr_basis_kernel<KM, NT>), gb, dim3(NT), 0, st, p.Mt, p.CTt, p.Ps, p.thetas, p.costs, p.dom, p.ctl, k, 1));
+  DPB_BY_RANK(k, DPB_LAUNCH((fr_finish_head_kernel<KM, NT>), one, dim3(NT), 0, st, p.Ps, p.thetas, p.costs, p.flags, p.ctl, p.hist_cost, p.hist_g, p.Rot,
                            weight, theta, info, nb, k, max_iter));
-  FR_BY_RANK(k, (void)NT; DPB_LAUNCH((fr_finish_coef_kernel<KM>), gb, t256, 0, st, p.Ct, p.Rot, p.W, p.flags, p.Cn, k));
+  DPB_BY_RANK(k, (void)NT; DPB_LAUNCH((fr_finish_coef_kernel<KM>), gb, t256, 0, st, p.Ct, p.Rot, p.W, p.flags, p.Cn, k));
   const int vec = (N % 4 == 0 && (uintptr_t)X % 16 == 0 && (uintptr_t)Y % 16 == 0) ? 1 : 0;
   const dim3 sg((unsigned)((N + 255) / 256));
-  FR_BY_TILES(k, DPB_LAUNCH((fr_stream_kernel<KT>), sg, t256, 0, st, X, p.Cn, Y, R, k, N, vec));
+  DPB_BY_TILES(k, DPB_LAUNCH((fr_stream_kernel<KT>), sg, t256, 0, st, X, p.Cn, Y, R, k, N, vec));
   DPB_CHECK(hipGetLastError());
   return 0;
 }

@@ -19,11 +19,9 @@
 // bitwise the same alone, at any position of a stack, and with A broadcast.
 #include "../../include/dpb.h"
 #include "kernels.h"
-#include "fr_jacobi.h"
+#include "geom.h"
 
 namespace dpb {
-
-typedef double gd_d4 __attribute__((ext_vector_type(4)));
 
 constexpr double GD_HALF_PI = 1.57079632679489661923;
 constexpr double GD_DOMAIN = GD_HALF_PI - 1e-6;      // FR_DOMAIN of frechet.hip: beyond it the geodesic is not unique and 1 / cos theta is unbounded
@@ -34,21 +32,6 @@ constexpr int GD_CHUNK_ROWS = 512;                   // rows per stacked Gram ca
 enum { GD_VECTORS = 0, GD_LOG = 1, GD_GEODESIC = 2, GD_EXP = 3 };
 
 struct GdTs { double t[GD_MAX_SLICES]; };
-
-__device__ inline double gd_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-// the descending order of the rank counting: a NaN sorts before every number and ties go by index (fr_before of frechet.hip)
-__device__ inline bool gd_before(double other, double mine, bool other_first) {
-  const bool on = other != other, mn = mine != mine;
-  if (on || mn) return on && (!mn || other_first);
-  return other > mine || (other == mine && other_first);
-}
-
-// block b of a stacked Gram into its own slot: dst[b][r][c] = G[(b rstep + r) ld + b k + c]   (rstep = k: diagonal blocks; 0: one basis against a stack)
-__global__ __launch_bounds__(256) void gd_blocks_kernel(const double* G, double* dst, long ld, int rstep, int k) {
-  const long b = blockIdx.x;
-  for (int e = threadIdx.x; e < k * k; e += 256) dst[b * k * k + e] = G[(b * rstep + e / k) * ld + b * k + e % k];
-}
 
 struct GdPairArgs {
   const double* Wa; long wa_stride;      // whitening of A_d (of P_d), 0: one for all pairs
@@ -70,8 +53,8 @@ __global__ __launch_bounds__(NT) void gd_pair_kernel(GdPairArgs a) {
   __shared__ double A[KMAX][KMAX + 1], V[KMAX][KMAX + 1], Mm[KMAX][KMAX + 1];
   __shared__ double lam[KMAX], val[KMAX], csv[KMAX], snv[KMAX], sgn[KMAX];
   __shared__ int ord[KMAX];
-  __shared__ FrJacobiWs<KMAX> ws;
-  static_assert(sizeof(double) * (3 * KMAX * (KMAX + 1) + 5 * KMAX) + sizeof(int) * KMAX + sizeof(FrJacobiWs<KMAX>) <= 160 * 1024,
+  __shared__ JacobiWs<KMAX> ws;
+  static_assert(sizeof(double) * (3 * KMAX * (KMAX + 1) + 5 * KMAX) + sizeof(int) * KMAX + sizeof(JacobiWs<KMAX>) <= 160 * 1024,
                 "gd_pair_kernel exceeds the gfx950 LDS");
   const int t = threadIdx.x, k = a.k, S = a.S;
   const long d = blockIdx.x, kk = (long)k * k;
@@ -84,9 +67,9 @@ __global__ __launch_bounds__(NT) void gd_pair_kernel(GdPairArgs a) {
   float* spec = a.spec + d * k;
   const int degenerate = a.fa[d * a.fa_stride] != 0 || (!ex && a.fb[d] != 0);
   if (degenerate) {                                // (uniform) NaN coefficients: every output of the pair is NaN
-    for (int e = t; e < k * k; e += NT) { Z1[e] = gd_nan(); Z2b[e] = gd_nan(); if (ex) Z2a[e] = gd_nan(); }
-    for (int e = t; e < S * k; e += NT) { al[e] = gd_nan(); be[e] = gd_nan(); }
-    for (int e = t; e < k; e += NT) spec[e] = (float)gd_nan();
+    for (int e = t; e < k * k; e += NT) { Z1[e] = nan64(); Z2b[e] = nan64(); if (ex) Z2a[e] = nan64(); }
+    for (int e = t; e < S * k; e += NT) { al[e] = nan64(); be[e] = nan64(); }
+    for (int e = t; e < k; e += NT) spec[e] = (float)nan64();
     if (t == 0) a.flags[d] = 1;
     return;
   }
@@ -136,7 +119,7 @@ __global__ __launch_bounds__(NT) void gd_pair_kernel(GdPairArgs a) {
     }
   }
   __syncthreads();
-  fr_jacobi<KMAX, NT>(A, V, ws, k);
+  jacobi_lds<KMAX, NT>(A, V, ws, k);
   if (t < k) {
     const double l = A[t][t];
     lam[t] = l < 0.0 ? 0.0 : ((!ex && l > 1.0) ? 1.0 : l);      // (a NaN stays a NaN)
@@ -175,18 +158,13 @@ __global__ __launch_bounds__(NT) void gd_pair_kernel(GdPairArgs a) {
     sgn[t] = V[best][t] < 0.0 ? -1.0 : 1.0;
   }
   __syncthreads();
-  if (t < k) {                                     // descending; ties by index (rank counting)
-    int rank = 0;
-    const double mine = val[t];
-    for (int e = 0; e < k; ++e) rank += gd_before(val[e], mine, e < t) ? 1 : 0;
-    ord[rank] = t;
-  }
+  if (t < k) ord[rank_desc<true>(val, k, t)] = t;  // descending; ties by index (rank counting)
   __syncthreads();
   const bool refused = !ex && val[ord[0]] > GD_DOMAIN;         // (uniform)
   if (refused) {
-    for (int e = t; e < k * k; e += NT) { Z1[e] = gd_nan(); Z2b[e] = gd_nan(); }
-    for (int e = t; e < S * k; e += NT) { al[e] = gd_nan(); be[e] = gd_nan(); }
-    for (int e = t; e < k; e += NT) spec[e] = (float)gd_nan();
+    for (int e = t; e < k * k; e += NT) { Z1[e] = nan64(); Z2b[e] = nan64(); }
+    for (int e = t; e < S * k; e += NT) { al[e] = nan64(); be[e] = nan64(); }
+    for (int e = t; e < k; e += NT) spec[e] = (float)nan64();
     if (t == 0) a.flags[d] = 2;
     return;
   }
@@ -241,70 +219,21 @@ __global__ __launch_bounds__(256) void gd_stream_kernel(const float* Xs, long xs
   const double* z1a = Z1a + d * k * k;
   const double* z2a = Z2a + d * k * k;
   const double* z2b = Z2b + d * k * k;
-  gd_d4 acc1[KT][4], acc2[KT][4];
+  geom_d4 acc1[KT][4], acc2[KT][4];
 #pragma unroll
   for (int m = 0; m < KT; ++m)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { acc1[m][e] = gd_d4{0.0, 0.0, 0.0, 0.0}; acc2[m][e] = gd_d4{0.0, 0.0, 0.0, 0.0}; }
+    for (int e = 0; e < 4; ++e) { acc1[m][e] = geom_d4{0.0, 0.0, 0.0, 0.0}; acc2[m][e] = geom_d4{0.0, 0.0, 0.0, 0.0}; }
   for (int r0 = 0; r0 < k; r0 += 4) {              // the rows of X
     const int r = r0 + g;
-    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < k && n0 < N) {
-      const float* p = X + (long)r * N + n0;
-      if (vec) {
-        x = *reinterpret_cast<const float4*>(p);   // (n0 % 4 == 0 and N % 4 == 0, so n0 + 3 < N)
-      } else {
-        x.x = p[0];
-        if (n0 + 1 < N) x.y = p[1];
-        if (n0 + 2 < N) x.z = p[2];
-        if (n0 + 3 < N) x.w = p[3];
-      }
-    }
-    double z[KT], w[KT];
-#pragma unroll
-    for (int m = 0; m < KT; ++m) {
-      const bool ok = r < k && 16 * m + j < k;
-      z[m] = ok ? z1a[(long)r * k + 16 * m + j] : 0.0;
-      w[m] = (EXP && ok) ? z2a[(long)r * k + 16 * m + j] : 0.0;
-    }
-#pragma unroll
-    for (int m = 0; m < KT; ++m) {
-      acc1[m][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(z[m], (double)x.x, acc1[m][0], 0, 0, 0);
-      acc1[m][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(z[m], (double)x.y, acc1[m][1], 0, 0, 0);
-      acc1[m][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(z[m], (double)x.z, acc1[m][2], 0, 0, 0);
-      acc1[m][3] = __builtin_amdgcn_mfma_f64_16x16x4f64(z[m], (double)x.w, acc1[m][3], 0, 0, 0);
-      if (EXP) {
-        acc2[m][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(w[m], (double)x.x, acc2[m][0], 0, 0, 0);
-        acc2[m][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(w[m], (double)x.y, acc2[m][1], 0, 0, 0);
-        acc2[m][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(w[m], (double)x.z, acc2[m][2], 0, 0, 0);
-        acc2[m][3] = __builtin_amdgcn_mfma_f64_16x16x4f64(w[m], (double)x.w, acc2[m][3], 0, 0, 0);
-      }
-    }
+    const float4 x = r < k ? load4(X + (long)r * N, n0, N, vec) : make_float4(0.f, 0.f, 0.f, 0.f);
+    mfma_rows4<KT>(acc1, z1a, r, r < k, j, k, x);
+    if (EXP) mfma_rows4<KT>(acc2, z2a, r, r < k, j, k, x);           // the one loaded x feeds both tiles
   }
   for (int r0 = 0; r0 < k; r0 += 4) {              // the rows of Y
     const int r = r0 + g;
-    float4 x = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (r < k && n0 < N) {
-      const float* p = Y + (long)r * N + n0;
-      if (vec) {
-        x = *reinterpret_cast<const float4*>(p);
-      } else {
-        x.x = p[0];
-        if (n0 + 1 < N) x.y = p[1];
-        if (n0 + 2 < N) x.z = p[2];
-        if (n0 + 3 < N) x.w = p[3];
-      }
-    }
-    double z[KT];
-#pragma unroll
-    for (int m = 0; m < KT; ++m) z[m] = (r < k && 16 * m + j < k) ? z2b[(long)r * k + 16 * m + j] : 0.0;
-#pragma unroll
-    for (int m = 0; m < KT; ++m) {
-      acc2[m][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(z[m], (double)x.x, acc2[m][0], 0, 0, 0);
-      acc2[m][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(z[m], (double)x.y, acc2[m][1], 0, 0, 0);
-      acc2[m][2] = __builtin_amdgcn_mfma_f64_16x16x4f64(z[m], (double)x.z, acc2[m][2], 0, 0, 0);
-      acc2[m][3] = __builtin_amdgcn_mfma_f64_16x16x4f64(z[m], (double)x.w, acc2[m][3], 0, 0, 0);
-    }
+    const float4 x = r < k ? load4(Y + (long)r * N, n0, N, vec) : make_float4(0.f, 0.f, 0.f, 0.f);
+    mfma_rows4<KT>(acc2, z2b, r, r < k, j, k, x);
   }
   if (n0 >= N) return;
   for (int s = 0; s < S; ++s) {
@@ -318,17 +247,9 @@ __global__ __launch_bounds__(256) void gd_stream_kernel(const float* Xs, long xs
         const int i = 16 * m + g + 4 * x;
         if (i >= k) continue;
         const double p = al[i], q = be[i];
-        float* o = O + (long)i * N + n0;
-        const float4 v = make_float4((float)fma(q, acc2[m][0][x], p * acc1[m][0][x]), (float)fma(q, acc2[m][1][x], p * acc1[m][1][x]),
-                                     (float)fma(q, acc2[m][2][x], p * acc1[m][2][x]), (float)fma(q, acc2[m][3][x], p * acc1[m][3][x]));
-        if (vec) {
-          *reinterpret_cast<float4*>(o) = v;
-        } else {
-          o[0] = v.x;
-          if (n0 + 1 < N) o[1] = v.y;
-          if (n0 + 2 < N) o[2] = v.z;
-          if (n0 + 3 < N) o[3] = v.w;
-        }
+        store4(O + (long)i * N, n0, N, vec,
+               make_float4((float)fma(q, acc2[m][0][x], p * acc1[m][0][x]), (float)fma(q, acc2[m][1][x], p * acc1[m][1][x]),
+                           (float)fma(q, acc2[m][2][x], p * acc1[m][2][x]), (float)fma(q, acc2[m][3][x], p * acc1[m][3][x])));
       }
   }
 }
@@ -338,34 +259,19 @@ namespace {
 struct GdLayout { size_t big = 0, wa = 0, wb = 0, gab = 0, flags = 0, z1a = 0, z2a = 0, z2b = 0, alpha = 0, beta = 0, total = 0; long chunk = 0; };
 bool gd_layout(long D, int S, int k, long N, GdLayout& l) {
   if (D < 1 || D > GD_MAX_PAIRS || S < 1 || S > GD_MAX_SLICES || k < 1 || k > FRECHET_MAX_RANK || N < 1 || k > N) return false;
-  size_t off = 0;
-  auto take = [&](size_t b) { const size_t o = off; off += (b + 255) / 256 * 256; return o; };
+  ScratchCarver s;
   const size_t kk = (size_t)k * k * sizeof(double), Sx = S < 2 ? 2 : S;
   l.chunk = GD_CHUNK_ROWS / k < 1 ? 1 : GD_CHUNK_ROWS / k;         // pairs per stacked Gram call
   if (l.chunk > D) l.chunk = D;
   const size_t cr = (size_t)l.chunk * k;
-  l.big = take(cr * cr * sizeof(double));
-  l.wa = take((size_t)D * kk); l.wb = take((size_t)D * kk); l.gab = take((size_t)D * kk);
-  l.flags = take(2 * (size_t)D * sizeof(int));
-  l.z1a = take((size_t)D * kk); l.z2a = take((size_t)D * kk); l.z2b = take((size_t)D * kk);
-  l.alpha = take((size_t)D * Sx * k * sizeof(double)); l.beta = take((size_t)D * Sx * k * sizeof(double));
-  l.total = off;
+  l.big = s.take(cr * cr * sizeof(double));
+  l.wa = s.take((size_t)D * kk); l.wb = s.take((size_t)D * kk); l.gab = s.take((size_t)D * kk);
+  l.flags = s.take(2 * (size_t)D * sizeof(int));
+  l.z1a = s.take((size_t)D * kk); l.z2a = s.take((size_t)D * kk); l.z2b = s.take((size_t)D * kk);
+  l.alpha = s.take((size_t)D * Sx * k * sizeof(double)); l.beta = s.take((size_t)D * Sx * k * sizeof(double));
+  l.total = s.off;
   return true;
 }
-
-#define GD_BY_RANK(k, ...)                                                \
-  do {                                                                     \
-    if ((k) <= 16) { constexpr int KM = 16, NT = 256; __VA_ARGS__; }       \
-    else if ((k) <= 32) { constexpr int KM = 32, NT = 1024; __VA_ARGS__; } \
-    else { constexpr int KM = 64, NT = 1024; __VA_ARGS__; }                \
-  } while (0)
-#define GD_BY_TILES(k, ...)                                    \
-  do {                                                          \
-    if ((k) <= 16) { constexpr int KT = 1; __VA_ARGS__; }       \
-    else if ((k) <= 32) { constexpr int KT = 2; __VA_ARGS__; }  \
-    else if ((k) <= 48) { constexpr int KT = 3; __VA_ARGS__; }  \
-    else { constexpr int KT = 4; __VA_ARGS__; }                 \
-  } while (0)
 
 // X: the first source (A or P), xstride 0 (one for all pairs) or k N; Y: the second (B or H).  S slices (mode GD_VECTORS / GD_LOG: 2, split over O0, O1).
 int gd_run(const char* who, const float* X, long xstride, const float* Y, long D, int k, long N, int mode, const double* ts, int J, float* O0, float* O1,
@@ -380,11 +286,7 @@ int gd_run(const char* who, const float* X, long xstride, const float* Y, long D
   }
   if (xstride != 0 && xstride != (long)k * N) { set_error("%s: a_stride=%ld must be 0 (one basis for all pairs) or k N = %ld", who, xstride, (long)k * N); return -1; }
   if (timed && !ts) { set_error("%s: ts is null", who); return -1; }
-  if ((uintptr_t)scratch % 256) { set_error("%s: scratch must be 256-byte aligned", who); return -1; }
-  if (scratch_bytes < l.total) {
-    set_error("%s: scratch of %zu bytes, dpb_grassmann_scratch_bytes(%ld, %d, %d, %ld) = %zu needed", who, scratch_bytes, D, S, k, N, l.total);
-    return -1;
-  }
+  if (check_scratch(who, scratch, scratch_bytes, l.total, "dpb_grassmann_scratch_bytes(%ld, %d, %d, %ld)", D, S, k, N) != 0) return -1;
   char* base = (char*)scratch;
   double* big = (double*)(base + l.big);
   double* Wa = (double*)(base + l.wa);
@@ -399,15 +301,14 @@ int gd_run(const char* who, const float* X, long xstride, const float* Y, long D
   for (long c0 = 0; c0 < D; c0 += l.chunk) {
     const long c = c0 + l.chunk < D ? l.chunk : D - c0;
     const int cr = (int)(c * k);
-    const dim3 gc((unsigned)c);
     if (xstride) {
       if (launch_cross_gram(X + c0 * kN, nullptr, big, cr, cr, N, st) != 0) return -1;
-      DPB_LAUNCH(gd_blocks_kernel, gc, t256, 0, st, big, Wa + c0 * kk, (long)cr, k, k);
+      launch_gram_blocks(big, Wa + c0 * kk, (int)c, cr, k, k, st);
     }
     if (launch_cross_gram(Y + c0 * kN, nullptr, big, cr, cr, N, st) != 0) return -1;
-    DPB_LAUNCH(gd_blocks_kernel, gc, t256, 0, st, big, Wb + c0 * kk, (long)cr, k, k);
+    launch_gram_blocks(big, Wb + c0 * kk, (int)c, cr, k, k, st);
     if (launch_cross_gram(xstride ? X + c0 * kN : X, Y + c0 * kN, big, xstride ? cr : k, cr, N, st) != 0) return -1;
-    DPB_LAUNCH(gd_blocks_kernel, gc, t256, 0, st, big, Gab + c0 * kk, (long)cr, xstride ? k : 0, k);
+    launch_gram_blocks(big, Gab + c0 * kk, (int)c, cr, xstride ? k : 0, k, st);
   }
   launch_angles_prep(Wa, fa, xstride ? (int)D : 1, k, st);
   if (mode != GD_EXP) launch_angles_prep(Wb, fb, (int)D, k, st);
@@ -417,14 +318,14 @@ int gd_run(const char* who, const float* X, long xstride, const float* Y, long D
   a.alpha = (double*)(base + l.alpha); a.beta = (double*)(base + l.beta);
   a.spec = spec; a.flags = flags; a.S = S; a.k = k; a.mode = mode;
   for (int j = 0; j < GD_MAX_SLICES; ++j) a.ts.t[j] = (timed && j < J) ? ts[j] : 0.0;
-  GD_BY_RANK(k, DPB_LAUNCH((gd_pair_kernel<KM, NT>), dim3((unsigned)D), dim3(NT), 0, st, a));
+  DPB_BY_RANK(k, DPB_LAUNCH((gd_pair_kernel<KM, NT>), dim3((unsigned)D), dim3(NT), 0, st, a));
   const int split = timed ? 0 : 1;
   const int vec = (N % 4 == 0 && (uintptr_t)X % 16 == 0 && (uintptr_t)Y % 16 == 0 && (uintptr_t)O0 % 16 == 0 && (!split || (uintptr_t)O1 % 16 == 0)) ? 1 : 0;
   const dim3 sg((unsigned)((N + 255) / 256), (unsigned)D);
   if (mode == GD_EXP)
-    GD_BY_TILES(k, DPB_LAUNCH((gd_stream_kernel<KT, true>), sg, t256, 0, st, X, xstride, Y, a.Z1a, a.Z2a, a.Z2b, a.alpha, a.beta, O0, O1, split, S, k, N, vec));
+    DPB_BY_TILES(k, DPB_LAUNCH((gd_stream_kernel<KT, true>), sg, t256, 0, st, X, xstride, Y, a.Z1a, a.Z2a, a.Z2b, a.alpha, a.beta, O0, O1, split, S, k, N, vec));
   else
-    GD_BY_TILES(k, DPB_LAUNCH((gd_stream_kernel<KT, false>), sg, t256, 0, st, X, xstride, Y, a.Z1a, a.Z2a, a.Z2b, a.alpha, a.beta, O0, O1, split, S, k, N, vec));
+    DPB_BY_TILES(k, DPB_LAUNCH((gd_stream_kernel<KT, false>), sg, t256, 0, st, X, xstride, Y, a.Z1a, a.Z2a, a.Z2b, a.alpha, a.beta, O0, O1, split, S, k, N, vec));
   DPB_CHECK(hipGetLastError());
   return 0;
 }

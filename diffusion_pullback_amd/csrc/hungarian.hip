@@ -15,6 +15,7 @@
 // The overlaps come from the exact fp64 cross-Gram of angles.hip and the row sums of squares from the fixed-order reduction of transport.hip.
 // Reproducibility: no atomics; every sum is one fixed chain.  Workgroup b of lap_kernel reads nothing but problem b.
 #include "kernels.h"
+#include "geom.h"
 
 #include <cmath>
 
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(KMAX) void lap_kernel(LapArgs a) {
   const long b = blockIdx.x;
   const bool sweep = a.G != nullptr;
   const long R = a.B * k;
-  const double nan_ = __longlong_as_double(0x7ff8000000000000LL), inf_ = __longlong_as_double(0x7ff0000000000000LL);
+  const double nan_ = nan64(), inf_ = __longlong_as_double(0x7ff0000000000000LL);
 
   // ---- the matrix
   int bad = 0;
@@ -180,33 +181,6 @@ __global__ __launch_bounds__(KMAX) void lap_kernel(LapArgs a) {
   }
 }
 
-__device__ inline double hm_block_sum(double v, double* red) {      // the same value in every thread; fixed order: xor butterfly, then the waves in order
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int w = 0; w < HM_NT / 64; ++w) s += red[w];
-  return s;
-}
-
-__device__ inline float4 hm_load4(const float* row, long n, long N, int vec) {      // elements n .. n+3 of a row of length N, zeros past its end
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (n < N) {
-    if (vec) {
-      v = *reinterpret_cast<const float4*>(row + n);                // (vec: N % 4 == 0 and n % 4 == 0, so n + 3 < N)
-    } else {
-      v.x = row[n];
-      if (n + 1 < N) v.y = row[n + 1];
-      if (n + 2 < N) v.z = row[n + 2];
-      if (n + 3 < N) v.w = row[n + 3];
-    }
-  }
-  return v;
-}
-
 // grid (chunks of N, k).  W[i][n] = sum_b mscale[i][b] X[b][msrc[i][b]][n], b in order, one fma per term; part[i][chunk] = the sum of squares of the W
 // written.  Four rows are in flight per thread (the loads of a group of four bases are issued before the first is used).
 __global__ __launch_bounds__(HM_NT) void mean_kernel(const float* X, const int32_t* msrc, const double* mscale, long B, int k, long N, long chunks,
@@ -226,7 +200,7 @@ __global__ __launch_bounds__(HM_NT) void mean_kernel(const float* X, const int32
       float4 x[4];
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        if (bb + q < nb) x[q] = hm_load4(X + ((b0 + bb + q) * k + src_s[bb + q]) * N, n, N, vec);
+        if (bb + q < nb) x[q] = load4(X + ((b0 + bb + q) * k + src_s[bb + q]) * N, n, N, vec);
 #pragma unroll
       for (int q = 0; q < 4; ++q)
         if (bb + q < nb) {
@@ -247,7 +221,7 @@ __global__ __launch_bounds__(HM_NT) void mean_kernel(const float* X, const int32
   s += a1 * a1;
   s += a2 * a2;
   s += a3 * a3;
-  s = hm_block_sum(s, red);
+  s = block_sum<HM_NT>(s, red);
   if (t == 0) part[(long)i * chunks + chunk] = s;
 }
 
@@ -278,7 +252,7 @@ __global__ __launch_bounds__(HM_NT) void changed_kernel(const int32_t* changed, 
   __shared__ double red[HM_NT / 64];
   double c = 0.0;
   for (long b = threadIdx.x; b < B; b += HM_NT) c += (double)changed[b];
-  c = hm_block_sum(c, red);
+  c = block_sum<HM_NT>(c, red);
   if (threadIdx.x == 0) info[0] = c;
 }
 
@@ -296,11 +270,7 @@ size_t linear_assignment_scratch_bytes(long B, int k) {
 int launch_linear_assignment(const double* cost, long B, int k, int32_t* col_of_row, double* total, void* scratch, size_t scratch_bytes, hipStream_t st) {
   const size_t need = linear_assignment_scratch_bytes(B, k);
   if (!need) { set_error("dpb_linear_assignment: B=%ld outside [1,%ld] or k=%d outside [1,%d]", B, HM_MAX_BASES, k, HUNGARIAN_MAX_RANK); return -1; }
-  if ((uintptr_t)scratch % 256) { set_error("dpb_linear_assignment: scratch must be 256-byte aligned"); return -1; }
-  if (scratch_bytes < need) {
-    set_error("dpb_linear_assignment: scratch of %zu bytes, dpb_linear_assignment_scratch_bytes(%ld, %d) = %zu needed", scratch_bytes, B, k, need);
-    return -1;
-  }
+  if (check_scratch("dpb_linear_assignment", scratch, scratch_bytes, need, "dpb_linear_assignment_scratch_bytes(%ld, %d)", B, k) != 0) return -1;
   LapArgs a{};
   a.cost = cost; a.col_of_row = col_of_row; a.total = total; a.B = B; a.k = k;
   lap_launch(a, st);
@@ -312,19 +282,18 @@ namespace {
 struct MeanLayout { size_t g = 0, ssa = 0, ssx = 0, msrc = 0, mscale = 0, changed = 0, w = 0, part = 0, total = 0; long chunks = 0; };
 bool mean_layout(long B, int k, long N, MeanLayout& l) {
   if (B < 1 || B > HM_MAX_BASES || k < 1 || k > HUNGARIAN_MAX_RANK || N < 1 || B * k > HM_MAX_ROWS) return false;
-  size_t off = 0;
-  auto take = [&](size_t b) { const size_t o = off; off += (b + 255) / 256 * 256; return o; };
+  ScratchCarver s;
   l.chunks = (N + HM_CHUNK - 1) / HM_CHUNK;
   if (l.chunks > 0x7fffffffL) return false;
-  l.g = take((size_t)k * B * k * sizeof(double));
-  l.ssa = take((size_t)k * sizeof(double));
-  l.ssx = take((size_t)B * k * sizeof(double));
-  l.msrc = take((size_t)B * k * sizeof(int32_t));
-  l.mscale = take((size_t)B * k * sizeof(double));
-  l.changed = take((size_t)B * sizeof(int32_t));
-  l.w = take((size_t)k * N * sizeof(double));
-  l.part = take((size_t)k * (size_t)l.chunks * sizeof(double));
-  l.total = off;
+  l.g = s.take((size_t)k * B * k * sizeof(double));
+  l.ssa = s.take((size_t)k * sizeof(double));
+  l.ssx = s.take((size_t)B * k * sizeof(double));
+  l.msrc = s.take((size_t)B * k * sizeof(int32_t));
+  l.mscale = s.take((size_t)B * k * sizeof(double));
+  l.changed = s.take((size_t)B * sizeof(int32_t));
+  l.w = s.take((size_t)k * N * sizeof(double));
+  l.part = s.take((size_t)k * (size_t)l.chunks * sizeof(double));
+  l.total = s.off;
   return true;
 }
 }  // namespace
@@ -344,11 +313,7 @@ int launch_matched_mean(const float* X, long B, int k, long N, const float* anch
   }
   if (!anchor && (init < 0 || init >= B)) { set_error("dpb_matched_mean: init=%d outside [0,%ld)", init, B); return -1; }
   if (distance != 0 && distance != 1) { set_error("dpb_matched_mean: distance=%d is neither 0 (1/cosine) nor 1 (cosine)", distance); return -1; }
-  if ((uintptr_t)scratch % 256) { set_error("dpb_matched_mean: scratch must be 256-byte aligned"); return -1; }
-  if (scratch_bytes < l.total) {
-    set_error("dpb_matched_mean: scratch of %zu bytes, dpb_matched_mean_scratch_bytes(%ld, %d, %ld) = %zu needed", scratch_bytes, B, k, N, l.total);
-    return -1;
-  }
+  if (check_scratch("dpb_matched_mean", scratch, scratch_bytes, l.total, "dpb_matched_mean_scratch_bytes(%ld, %d, %ld)", B, k, N) != 0) return -1;
   if (!anchor) anchor = X + (long)init * k * N;
   char* base = (char*)scratch;
   double* G = (double*)(base + l.g);

@@ -1,6 +1,8 @@
 // Host-side launch interface of the gfx950 kernels (internal; the public C-ABI is include/dpb.h).
 #pragma once
 #include <algorithm>
+#include <cstdarg>
+#include <cstdio>
 #include <type_traits>
 #include <utility>
 
@@ -342,6 +344,46 @@ size_t pca_scratch_bytes(int q, long N, long D);         // 0 when invalid
 int launch_pca_lowrank(const float* H, long N, long D, const float* R, int q, int niter, float* u, float* s, void* scratch, size_t scratch_bytes,
                        hipStream_t st);
 
+// ---------------------------------------------------------------- host-side pieces shared by the geometry launchers (the device pieces: geom.h)
+// the parts of a scratch block: take() returns the offset of the next part, each part rounded up to 256 bytes; off is the total so far
+struct ScratchCarver {
+  size_t off = 0;
+  size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) / 256 * 256; return o; }
+};
+// a caller's scratch block must be 256-byte aligned and hold `need` bytes; -1 with the error set if not (sizer...: the C-ABI call that returns `need`,
+// printf-style, as the message names it)
+__attribute__((format(printf, 5, 6))) inline int check_scratch(const char* who, const void* scratch, size_t have, size_t need, const char* sizer, ...) {
+  if ((uintptr_t)scratch % 256) { set_error("%s: scratch must be 256-byte aligned", who); return -1; }
+  if (have >= need) return 0;
+  char call[160];
+  va_list ap;
+  va_start(ap, sizer);
+  vsnprintf(call, sizeof(call), sizer, ap);
+  va_end(ap);
+  set_error("%s: scratch of %zu bytes, %s = %zu needed", who, have, call, need);
+  return -1;
+}
+// rank classes of the LDS-resident kernels: 16 | 32 | 64 rows, 256 threads for the smallest, 1024 above; DPB_BY_RANK128 adds the 128-row class
+#define DPB_BY_RANK(k, ...)                                                \
+  do {                                                                     \
+    if ((k) <= 16) { constexpr int KM = 16, NT = 256; __VA_ARGS__; }       \
+    else if ((k) <= 32) { constexpr int KM = 32, NT = 1024; __VA_ARGS__; } \
+    else { constexpr int KM = 64, NT = 1024; __VA_ARGS__; }                \
+  } while (0)
+#define DPB_BY_RANK128(k, ...)                                             \
+  do {                                                                     \
+    if ((k) <= 64) DPB_BY_RANK(k, __VA_ARGS__);                            \
+    else { constexpr int KM = 128, NT = 1024; __VA_ARGS__; }               \
+  } while (0)
+// 16-column tiles of the fp64 MFMA kernels: KT = ceil(k / 16) for k <= 64
+#define DPB_BY_TILES(k, ...)                                   \
+  do {                                                          \
+    if ((k) <= 16) { constexpr int KT = 1; __VA_ARGS__; }       \
+    else if ((k) <= 32) { constexpr int KT = 2; __VA_ARGS__; }  \
+    else if ((k) <= 48) { constexpr int KT = 3; __VA_ARGS__; }  \
+    else { constexpr int KT = 4; __VA_ARGS__; }                 \
+  } while (0)
+
 // ---------------------------------------------------------------- principal angles between subspaces (angles.hip): exact fp64 cross-Gram on the f64 MFMA,
 // then per-basis whitening and a per-pair Jacobi eigen-solve, all fp64.  G [Ra][Rb] fp64; Y = nullptr: Y = X (upper tiles computed, mirrored)
 int launch_cross_gram(const float* X, const float* Y, double* G, int Ra, int Rb, long N, hipStream_t st);
@@ -352,6 +394,8 @@ int launch_subspace_angles(const float* A, const float* B, long Ba, long Bb, int
 // per-basis whitening shared by the angles and the Frechet mean: Dg [n][k][k] fp64 (each basis's own Gram block) -> W = L^-1 D^-1/2 in place (lower
 // triangular, W G W^T = I), flags [n] = 1 for a degenerate basis (its slot is then left as it was); one workgroup per basis, k <= ORTH_MAX_RANK
 void launch_angles_prep(double* Dg, int* flags, int n, int k, hipStream_t st);
+// block b < n of a stacked Gram into its own slot: dst[b][r][c] = G[(b rstep + r) ld + b k + c]   (rstep = k: diagonal blocks; 0: one basis against a stack)
+void launch_gram_blocks(const double* G, double* dst, int n, long ld, int rstep, int k, hipStream_t st);
 
 // ---------------------------------------------------------------- Frechet (Karcher) mean on the Grassmannian of B bases of k rows (frechet.hip): the
 // Riemannian iteration on coefficients against the whitened Gram of all rows; X [B][k][N] fp32, everything between in fp64; see include/dpb.h

@@ -12,6 +12,7 @@
 // Also emits ||V - V_prev||_2 and max(|V - V_prev| - 1e-5 |V|) so the stop test (utils.py:803-806)
 // needs a single 8-byte read-back.
 #include "kernels.h"
+#include "geom.h"
 
 namespace dpb {
 
@@ -148,25 +149,24 @@ __global__ __launch_bounds__(64) void eig_kernel(const double* Gp, int nbg, doub
   }
 }
 
-// One block of 1024 threads: two-sided Jacobi in the round-robin (tournament) order.  A step rotates floor(k/2) DISJOINT index pairs at once: the angle of
-// a pair (p, q) depends on A[p][p], A[q][q], A[p][q] only, which no other pair of the step touches, so a step is the product of its rotations in any
-// order -- A <- A J for every row (and Q <- Q J), barrier, A <- J^T A for every column, barrier.  k - 1 (k even) or k steps make a sweep that visits every
-// pair once.  Against the one-wave cyclic kernel below (3 barriers per ROTATION): k = 50 is 49 steps of 25 rotations per sweep instead of 1225 dependent
+// One block of NT threads: two-sided Jacobi in the round-robin (tournament) order, floor(k/2) disjoint rotations per step (jacobi_round_robin, geom.h).
+// Against the one-wave cyclic kernel above (3 barriers per ROTATION): k = 50 is 49 steps of 25 rotations per sweep instead of 1225 dependent
 // rotations -- 3.9 ms -> see profiles/r06_eig_parallel.txt.  fp64 throughout; same thresholds, same Gram partial order, same output rules as eig_kernel.
 // QGLOBAL: the eigenvector matrix lives in global memory (the slot of Gram partial 0, free once the partials are summed) when A and Q do not both fit the LDS.
 template <int KMAX, bool QGLOBAL, int NT>
 __global__ __launch_bounds__(NT) void eig_par_kernel(double* Gp, int nbg, double* Cm, float* s_out, int k, OrthBatch ob) {
-  constexpr int NW = NT / 64;
   Gp += blockIdx.x * ob.scratch; Cm += blockIdx.x * ob.scratch; s_out += blockIdx.x * ob.s;
   constexpr int QR = QGLOBAL ? 1 : KMAX, QC = QGLOBAL ? 1 : KMAX + 1;
   __shared__ double A[KMAX][KMAX + 1], Ql[QR][QC];
-  __shared__ double rc[KMAX / 2], rs[KMAX / 2], lam[KMAX], red[2][NW], sgn[KMAX];
-  __shared__ int rp[KMAX / 2], rq[KMAX / 2], order[KMAX];
-  static_assert(sizeof(double) * (KMAX * (KMAX + 1) + QR * QC + 3 * KMAX + 2 * NW) + sizeof(int) * 2 * KMAX <= 160 * 1024, "eig_par_kernel exceeds the gfx950 LDS");
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  __shared__ double lam[KMAX], sgn[KMAX];
+  __shared__ int order[KMAX];
+  __shared__ JacobiWs<KMAX> ws;
+  static_assert(sizeof(double) * (KMAX * (KMAX + 1) + QR * QC + 2 * KMAX) + sizeof(int) * KMAX + sizeof(JacobiWs<KMAX>) <= 160 * 1024, "eig_par_kernel exceeds the gfx950 LDS");
+  const int t = threadIdx.x;
   double* const Xg = Gp + (long)k * k;           // overlaps W . Vprev^T: summed into partial 0's own slot
-  double* const Qg = Gp;                         // QGLOBAL: eigenvectors in partial 0's Gram slot, TRANSPOSED (the lanes of a wave walk the rows of Q: coalesced)
-  auto Qat = [&](int i, int j) -> double& { if constexpr (QGLOBAL) return Qg[(long)j * k + i]; else return Ql[i][j]; };
+  const auto Q = [&] {                           // QGLOBAL: eigenvectors in partial 0's Gram slot, TRANSPOSED
+    if constexpr (QGLOBAL) return JacobiGlobalVecsT{Gp, k}; else return JacobiLdsVecs<KMAX>{Ql};
+  }();
   for (int e = t; e < k * k; e += NT) {          // Gram matrix and overlaps: the blocks' partials added in block order (as eig_kernel)
     double g = 0.0, x = 0.0;
     for (int b0 = 0; b0 < nbg; b0 += 32) {
@@ -188,77 +188,13 @@ __global__ __launch_bounds__(NT) void eig_par_kernel(double* Gp, int nbg, double
   for (int e = t; e < k * k; e += NT) {          // A <- (G + G^T) / 2: the pair (i, j), (j, i) belongs to the thread that holds e = (i, j), i < j
     const int i = e / k, j = e % k;
     if (i < j) { const double v = 0.5 * (A[i][j] + A[j][i]); A[i][j] = v; A[j][i] = v; }
-    Qat(i, j) = i == j ? 1.0 : 0.0;              // (QGLOBAL: partial 0's Gram slot, free since the barrier above)
+    Q.at(i, j) = i == j ? 1.0 : 0.0;             // (QGLOBAL: partial 0's Gram slot, free since the barrier above)
   }
   __syncthreads();
-  const int m = (k + 1) & ~1, half = m / 2, steps = m - 1;      // players 0..m-1 (player k is a bye when k is odd)
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    double off = 0, diag = 0;                    // converged when the off-diagonal mass is negligible: fixed-order block reduction, uniform result
-    for (int i = wave; i < k; i += NW)
-      for (int j = lane; j < k; j += 64) {
-        const double v = A[i][j] * A[i][j];
-        if (i == j) diag += v; else if (i < j) off += v;
-      }
-    for (int o = 32; o > 0; o >>= 1) { off += __shfl_xor(off, o, 64); diag += __shfl_xor(diag, o, 64); }
-    if (lane == 0) { red[0][wave] = off; red[1][wave] = diag; }
-    __syncthreads();
-    off = 0; diag = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) { off += red[0][w]; diag += red[1][w]; }
-    __syncthreads();
-    if (off <= 1e-28 * diag) break;
-    for (int st = 0; st < steps; ++st) {
-      if (t < half) {                            // the step's pairs and their angles
-        int p = t == 0 ? m - 1 : (st + t) % (m - 1);
-        int q = t == 0 ? st % (m - 1) : (st - t + (m - 1)) % (m - 1);
-        if (p > q) { const int w = p; p = q; q = w; }
-        double c = 1.0, s = 0.0;
-        if (q < k) {
-          const double apq = A[p][q], app = A[p][p], aqq = A[q][q];
-          if (!(fabs(apq) <= 1e-300 || fabs(apq) <= 1e-18 * sqrt(fabs(app * aqq)))) {
-            const double theta = (aqq - app) / (2.0 * apq);
-            const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-            c = 1.0 / sqrt(tt * tt + 1.0); s = tt * c;
-          }
-        }
-        rp[t] = p; rq[t] = q < k ? q : p; rc[t] = c; rs[t] = s;       // (bye or negligible element: s = 0, skipped below)
-      }
-      __syncthreads();
-      for (int i = wave; i < half; i += NW) {    // A <- A J, Q <- Q J: the wave takes pair i, its lanes the rows
-        const int p = rp[i], q = rq[i];
-        const double c = rc[i], s = rs[i];
-        if (s == 0.0) continue;                  // wave-uniform
-        for (int r = lane; r < k; r += 64) {
-          const double arp = A[r][p], arq = A[r][q];
-          A[r][p] = c * arp - s * arq;
-          A[r][q] = s * arp + c * arq;
-          const double qrp = Qat(r, p), qrq = Qat(r, q);
-          Qat(r, p) = c * qrp - s * qrq;
-          Qat(r, q) = s * qrp + c * qrq;
-        }
-      }
-      __syncthreads();
-      for (int i = wave; i < half; i += NW) {    // A <- J^T A: the wave takes pair i, its lanes the columns
-        const int p = rp[i], q = rq[i];
-        const double c = rc[i], s = rs[i];
-        if (s == 0.0) continue;
-        for (int r = lane; r < k; r += 64) {
-          const double apr = A[p][r], aqr = A[q][r];
-          A[p][r] = c * apr - s * aqr;
-          A[q][r] = s * apr + c * aqr;
-        }
-      }
-      __syncthreads();
-    }
-  }
+  jacobi_round_robin<KMAX, NT>(A, Q, ws, k);
   if (t < k) lam[t] = A[t][t];
   __syncthreads();
-  if (t < k) {                                   // descending eigenvalue; ties by index (rank counting instead of a serial sort)
-    int rank = 0;
-    const double mine = lam[t];
-    for (int j = 0; j < k; ++j) rank += (lam[j] > mine || (lam[j] == mine && j < t)) ? 1 : 0;
-    order[rank] = t;
-  }
+  if (t < k) order[rank_desc<false>(lam, k, t)] = t;       // descending eigenvalue; ties by index (rank counting instead of a serial sort)
   __syncthreads();
   if (t < k) {
     const int i = t, e = order[i];
@@ -267,13 +203,13 @@ __global__ __launch_bounds__(NT) void eig_par_kernel(double* Gp, int nbg, double
     s_out[i] = (float)sqrt(sig);                  // reference returns s.sqrt() (utils.py:810)
     const double inv = sig > 1e-150 ? 1.0 / sig : 0.0;
     double dot = 0;
-    for (int j = 0; j < k; ++j) dot += Qat(j, e) * inv * Xg[j * k + i];
+    for (int j = 0; j < k; ++j) dot += Q.at(j, e) * inv * Xg[j * k + i];
     sgn[i] = (dot < 0 ? -1.0 : 1.0) * inv;
   }
   __syncthreads();
   for (int id = t; id < k * k; id += NT) {
     const int i = id / k, j = id % k;
-    Cm[id] = sgn[i] * Qat(j, order[i]);
+    Cm[id] = sgn[i] * Q.at(j, order[i]);
   }
 }
 

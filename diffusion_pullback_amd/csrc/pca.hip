@@ -185,7 +185,6 @@ __global__ __launch_bounds__(256) void pca_rotate_kernel(const double* __restric
 }
 
 // ---------------------------------------------------------------- host side
-static inline size_t pca_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // split of the feature reduction: enough blocks to fill the chip (about 2048 waves), at most 64 splits, at least 256 features per split
 static void pca_split(long N, long D, int* nsplit, long* dchunk) {
@@ -206,20 +205,19 @@ static PcaLayout pca_layout(int q, long N, long D) {
   int ns; long ch;
   pca_split(N, D, &ns, &ch);
   PcaLayout L{};
-  size_t o = 0;
-  auto take = [&](size_t bytes) { const size_t at = o; o += pca_align(bytes); return at; };
+  ScratchCarver c;
   const size_t ob_d = orth_scratch_bytes(q, D), ob_n = orth_scratch_bytes(q, N);
-  L.orth = take(ob_d > ob_n ? ob_d : ob_n);
-  L.ubt = take(sizeof(double) * q * q);
-  L.m = take(sizeof(float) * D);
-  L.wd = take(sizeof(float) * q * D);
-  L.qd = take(sizeof(float) * q * D);
-  L.wn = take(sizeof(float) * q * N);
-  L.qn = take(sizeof(float) * q * N);
-  L.zp = take(sizeof(float) * (size_t)ns * q * N);
-  L.s = take(sizeof(float) * q);
-  L.conv = take(sizeof(float) * 2);
-  L.total = o + 256;                                      // + the caller's base alignment
+  L.orth = c.take(ob_d > ob_n ? ob_d : ob_n);
+  L.ubt = c.take(sizeof(double) * q * q);
+  L.m = c.take(sizeof(float) * D);
+  L.wd = c.take(sizeof(float) * q * D);
+  L.qd = c.take(sizeof(float) * q * D);
+  L.wn = c.take(sizeof(float) * q * N);
+  L.qn = c.take(sizeof(float) * q * N);
+  L.zp = c.take(sizeof(float) * (size_t)ns * q * N);
+  L.s = c.take(sizeof(float) * q);
+  L.conv = c.take(sizeof(float) * 2);
+  L.total = c.off + 256;                                      // + the caller's base alignment
   return L;
 }
 

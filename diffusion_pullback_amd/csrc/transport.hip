@@ -11,6 +11,7 @@
 // Reproducibility: no atomics; every sum is one fixed chain whose shape depends on k, N_h and N_x only, never on D, P, the position of a target in the
 // stack or the alignment of the pointers (the 16-byte and the 4-byte load paths give every thread the same elements in the same order).
 #include "kernels.h"
+#include "geom.h"
 
 namespace dpb {
 
@@ -21,47 +22,20 @@ constexpr int TR_MAX_TARGETS = 65535;      // a grid axis
 
 struct TransportPcs { unsigned char pc[ORTH_MAX_RANK]; };      // the host's list travels as a kernel argument (entries < k <= 128)
 
-__device__ inline double tr_block_sum(double v, double* red) {      // the same value in every thread; fixed order: xor butterfly, then the waves in order
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  __syncthreads();                                                  // the previous use of red is over
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int w = 0; w < TR_NT / 64; ++w) s += red[w];
-  return s;
-}
-
-__device__ inline float4 tr_load4(const float* row, long n, long N, int vec) {      // elements n .. n+3 of a row of length N, zeros past its end
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (n < N) {
-    if (vec) {
-      v = *reinterpret_cast<const float4*>(row + n);                // (vec: N % 4 == 0 and n % 4 == 0, so n + 3 < N)
-    } else {
-      v.x = row[n];
-      if (n + 1 < N) v.y = row[n + 1];
-      if (n + 2 < N) v.z = row[n + 2];
-      if (n + 3 < N) v.w = row[n + 3];
-    }
-  }
-  return v;
-}
-
 // ss[r] = sum_n X[r][n]^2 in fp64, one workgroup per row.  Thread t adds the elements of its groups of four (group g = t, t + 256, ...) in index order
-// into ONE accumulator; the 256 accumulators meet in tr_block_sum: a chain that depends on N only.
+// into ONE accumulator; the 256 accumulators meet in block_sum: a chain that depends on N only.
 __global__ __launch_bounds__(TR_NT) void rowsumsq_kernel(const float* X, long N, double* ss, int vec) {
   __shared__ double red[TR_NT / 64];
   const float* row = X + (long)blockIdx.x * N;
   double acc = 0.0;
   for (long n = (long)threadIdx.x * 4; n < N; n += TR_CHUNK) {
-    const float4 v = tr_load4(row, n, N, vec);
+    const float4 v = load4(row, n, N, vec);
     acc += (double)v.x * (double)v.x;
     acc += (double)v.y * (double)v.y;
     acc += (double)v.z * (double)v.z;
     acc += (double)v.w * (double)v.w;
   }
-  const double s = tr_block_sum(acc, red);
+  const double s = block_sum<TR_NT>(acc, red);
   if (threadIdx.x == 0) ss[blockIdx.x] = s;
 }
 
@@ -120,7 +94,7 @@ __global__ __launch_bounds__(TR_NT) void stream_kernel(const float* vT, const fl
     for (int j = 0; j < TR_PT; ++j) acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll 4
     for (int q = 0; q < k; ++q) {
-      const float4 v = tr_load4(V + (long)q * N, n, N, vec);
+      const float4 v = load4(V + (long)q * N, n, N, vec);
       const float4 c0 = *reinterpret_cast<const float4*>(&cs[q * TR_PT]);
       const float4 c1 = *reinterpret_cast<const float4*>(&cs[q * TR_PT + 4]);
       const float c[TR_PT] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y, c1.z, c1.w};
@@ -141,17 +115,8 @@ __global__ __launch_bounds__(TR_NT) void stream_kernel(const float* vT, const fl
       s += (double)acc[j].y * (double)acc[j].y;
       s += (double)acc[j].z * (double)acc[j].z;
       s += (double)acc[j].w * (double)acc[j].w;
-      if (n < N) {
-        if (vec) {
-          *reinterpret_cast<float4*>(o + n) = acc[j];
-        } else {
-          o[n] = acc[j].x;
-          if (n + 1 < N) o[n + 1] = acc[j].y;
-          if (n + 2 < N) o[n + 2] = acc[j].z;
-          if (n + 3 < N) o[n + 3] = acc[j].w;
-        }
-      }
-      s = tr_block_sum(s, red);
+      store4(o, n, N, vec, acc[j]);
+      s = block_sum<TR_NT>(s, red);
       if (threadIdx.x == 0) part[(d * P + p0 + j) * chunks + chunk] = s;
     }
   }
@@ -187,17 +152,16 @@ namespace {
 struct TransportLayout { size_t g = 0, ss_src = 0, ss_u = 0, ss_v = 0, a = 0, part = 0, scale = 0, total = 0; long chunks = 0; };
 bool transport_layout(long D, int P, int k, long Nh, long Nx, TransportLayout& l) {
   if (D < 1 || D > TR_MAX_TARGETS || k < 1 || k > ORTH_MAX_RANK || P < 1 || P > k || Nh < 1 || Nx < 1) return false;
-  size_t off = 0;
-  auto take = [&](size_t b) { const size_t o = off; off += (b + 255) / 256 * 256; return o; };
+  ScratchCarver s;
   l.chunks = (Nx + TR_CHUNK - 1) / TR_CHUNK;
-  l.g = take((size_t)D * k * k * sizeof(double));
-  l.ss_src = take((size_t)k * sizeof(double));
-  l.ss_u = take((size_t)D * k * sizeof(double));
-  l.ss_v = take((size_t)D * k * sizeof(double));
-  l.a = take((size_t)D * P * k * sizeof(float));
-  l.part = take((size_t)D * P * (size_t)l.chunks * sizeof(double));
-  l.scale = take((size_t)D * P * sizeof(float));
-  l.total = off;
+  l.g = s.take((size_t)D * k * k * sizeof(double));
+  l.ss_src = s.take((size_t)k * sizeof(double));
+  l.ss_u = s.take((size_t)D * k * sizeof(double));
+  l.ss_v = s.take((size_t)D * k * sizeof(double));
+  l.a = s.take((size_t)D * P * k * sizeof(float));
+  l.part = s.take((size_t)D * P * (size_t)l.chunks * sizeof(double));
+  l.scale = s.take((size_t)D * P * sizeof(float));
+  l.total = s.off;
   return true;
 }
 }  // namespace
@@ -228,12 +192,8 @@ int launch_transport_directions(const float* u_src, const float* u_dst, const fl
     if (pcs[p] < 0 || pcs[p] >= k) { set_error("dpb_transport_directions: pcs[%d]=%d outside [0,%d)", p, (int)pcs[p], k); return -1; }
     pc.pc[p] = (unsigned char)pcs[p];
   }
-  if ((uintptr_t)scratch % 256) { set_error("dpb_transport_directions: scratch must be 256-byte aligned"); return -1; }
-  if (scratch_bytes < l.total) {
-    set_error("dpb_transport_directions: scratch of %zu bytes, dpb_transport_scratch_bytes(%ld, %d, %d, %ld, %ld) = %zu needed", scratch_bytes, D, P, k,
-              Nh, Nx, l.total);
+  if (check_scratch("dpb_transport_directions", scratch, scratch_bytes, l.total, "dpb_transport_scratch_bytes(%ld, %d, %d, %ld, %ld)", D, P, k, Nh, Nx) != 0)
     return -1;
-  }
   char* base = (char*)scratch;
   double* G = (double*)(base + l.g);
   double* ss_src = (double*)(base + l.ss_src);

@@ -180,7 +180,7 @@ def _split_leg(a):
         name, ns, c = r["Name"], float(r["TotalDurationNs"]), int(r["Calls"])
         key = ("ghat_passes" if "fr_product_kernel" in name else "log_map_eigensolves" if "fr_basis_kernel" in name else
                "finish_stream" if "fr_stream_kernel" in name else "finish_rest" if "fr_finish" in name else "cross_gram" if "cross_gram_kernel" in name else
-               "init_rest" if any(s in name for s in ("fr_diag_copy", "fr_whiten", "fr_init_kernel")) else
+               "init_rest" if any(s in name for s in ("gram_blocks_kernel", "fr_whiten", "fr_init_kernel")) else
                "step_rest" if ("fr_" in name or "angles_prep_kernel" in name) else "other")
         fam[key] += ns
         calls[key] = calls.get(key, 0) + c

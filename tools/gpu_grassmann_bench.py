@@ -125,7 +125,7 @@ def _split_leg(a):
     for r in rows:
         name, ns, c = r["Name"], float(r["TotalDurationNs"]), int(r["Calls"])
         key = ("cross_gram" if "cross_gram_kernel" in name else "pair" if "gd_pair_kernel" in name else "stream" if "gd_stream_kernel" in name else
-               "rest" if ("gd_blocks_kernel" in name or "angles_prep_kernel" in name) else "other")
+               "rest" if ("gram_blocks_kernel" in name or "angles_prep_kernel" in name) else "other")
         fam[key] += ns
         calls[key] = calls.get(key, 0) + c
     per = lambda key: round(fam[key] / 1e6 / a.calls, 4)
