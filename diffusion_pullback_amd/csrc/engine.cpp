@@ -1639,6 +1639,42 @@ int dpb_frechet_finish(const float* X, float* Y, float* weight, float* theta, do
   return launch_frechet_finish(X, B, k, N, max_iter, Y, weight, theta, info, scratch, scratch_bytes, (hipStream_t)stream);
 }
 
+const double* dpb_frechet_ghat(int B, int k, int64_t N, int max_iter, const void* scratch) {
+  if (!scratch) { fail("dpb_frechet_ghat: null argument"); return nullptr; }
+  const double* g = frechet_ghat(B, k, N, max_iter, scratch);
+  if (!g) fail("dpb_frechet_ghat: B=%d, k=%d, N=%lld, max_iter=%d is no Frechet problem", B, k, (long long)N, max_iter);
+  return g;
+}
+
+int dpb_frechet_start(const double* Ct, int B, int k, int64_t N, int max_iter, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!Ct || !scratch) return fail("dpb_frechet_start: null argument");
+  return launch_frechet_start(Ct, B, k, N, max_iter, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+// the flag (extrinsic) mean of many local bases, the global basis of run_edit_global_flag_mean_zt: flagmean.hip
+size_t dpb_flag_mean_scratch_bytes(int B, int k, int64_t N, int r, int max_iter) { return flag_mean_scratch_bytes(B, k, N, r, max_iter, true); }
+size_t dpb_flag_mean_solver_bytes(int B, int k, int r, int max_iter) { return flag_mean_scratch_bytes(B, k, 0, r, max_iter, false); }
+
+int dpb_flag_mean_init(const float* X, const double* Ghat, int B, int k, int64_t N, int r, uint64_t seed, int max_iter, void* scratch,
+                       size_t scratch_bytes, void* stream) {
+  if (!scratch || (X == nullptr) == (Ghat == nullptr)) return fail("dpb_flag_mean_init: null scratch, or not exactly one of X and Ghat given");
+  return launch_flag_mean_init(X, Ghat, B, k, N, r, seed, max_iter, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int dpb_flag_mean_iterate(int n_iter, double tol, const double* Ghat, int B, int k, int64_t N, int r, int max_iter, void* scratch, size_t scratch_bytes,
+                          void* stream) {
+  if (!scratch) return fail("dpb_flag_mean_iterate: null argument");
+  return launch_flag_mean_iterate(Ghat, B, k, N, r, max_iter, n_iter, tol, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int dpb_flag_mean_finish(const float* X, const double* Ghat, float* Y, float* weight, float* theta, double* Ct, double* info, int B, int k, int64_t N,
+                         int r, int max_iter, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!weight || !theta || !Ct || !info || !scratch) return fail("dpb_flag_mean_finish: null argument");
+  if ((X == nullptr) != (Y == nullptr) || (X == nullptr) == (Ghat == nullptr))
+    return fail("dpb_flag_mean_finish: X and Y go together, and exactly one of X and Ghat is given");
+  return launch_flag_mean_finish(X, Ghat, B, k, N, r, max_iter, Y, weight, theta, Ct, info, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
 // The Hungarian-matched mean of local bases, the global basis of run_edit_global_hungarian_mean_zt (src/modules/edit.py:1249-1514): hungarian.hip
 size_t dpb_linear_assignment_scratch_bytes(int B, int k) { return linear_assignment_scratch_bytes(B, k); }
 

@@ -72,6 +72,16 @@ __global__ __launch_bounds__(256) void fr_init_kernel(double* Ct, FrCtl* ctl, in
   if (e == 0) { ctl->done = 0; ctl->domain = -1; ctl->iters = 0; ctl->reorth_bad = 0; ctl->g = 0.0; ctl->cost = 0.0; }
 }
 
+// dpb_frechet_start: the caller's coefficients into Cn and the status cleared (phase 0); the step count cleared again after the whitening (phase 1)
+__global__ __launch_bounds__(256) void fr_start_kernel(const double* src, double* Cn, FrCtl* ctl, long n, int phase) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e < n) Cn[e] = src[e];
+  if (e == 0) {
+    ctl->iters = 0;
+    if (phase == 0) { ctl->done = 0; ctl->domain = -1; ctl->reorth_bad = 0; ctl->g = 0.0; ctl->cost = 0.0; }
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------ the skinny product with Ghat
 // Out^T [R][k] = Ghat [R][R] In^T [R][k] (that is Out = In Ghat, Ghat symmetric) on v_mfma_f64_16x16x4_f64.  A workgroup owns 16 rows of Out^T and reads
 // the matching 16-column strip of Ghat once (128 contiguous bytes per row; by symmetry Ghat[c][r] is read as Ghat[r][c]); its four waves take a quarter of
@@ -502,6 +512,26 @@ void fr_product(const FrPtrs& p, const double* In, double* Out, int R, int k, in
 }
 }  // namespace
 
+// Ghat [R][R] of X [B][k][N] with its whitenings W [B][k][k] and degenerate flags [B]: the exact cross-Gram, each basis's own block whitened as
+// angles.hip does, every block W_i G_ij W_j^T (shared with flagmean.hip)
+int launch_whitened_gram(const float* X, long B, int k, long N, double* G, double* W, int* flags, hipStream_t st) {
+  const int R = (int)(B * k);
+  if (launch_cross_gram(X, nullptr, G, R, R, N, st) != 0) return -1;
+  launch_gram_blocks(G, W, (int)B, R, k, k, st);                          // each basis's diagonal block of G into the slot its whitening matrix will take
+  launch_angles_prep(W, flags, (int)B, k, st);
+  const dim3 wg((unsigned)B, (unsigned)B);
+  DPB_BY_RANK(k, (void)NT; DPB_LAUNCH((fr_whiten_kernel<KM>), wg, dim3(256), 0, st, G, W, flags, R, k));
+  return 0;
+}
+
+// Y [k][N] fp32 = Z [k][R] X [R][N] with Z kept transposed (Zt [R][k]), k <= 64: fr_stream_kernel (shared with flagmean.hip)
+int launch_coef_stream(const float* X, const double* Zt, float* Y, int R, int k, long N, hipStream_t st) {
+  const int vec = (N % 4 == 0 && (uintptr_t)X % 16 == 0 && (uintptr_t)Y % 16 == 0) ? 1 : 0;
+  const dim3 sg((unsigned)((N + 255) / 256));
+  DPB_BY_TILES(k, DPB_LAUNCH((fr_stream_kernel<KT>), sg, dim3(256), 0, st, X, Zt, Y, R, k, N, vec));
+  return 0;
+}
+
 size_t frechet_scratch_bytes(long B, int k, long N, long max_iter) {
   FrLayout l;
   return fr_layout(B, k, N, max_iter, l) ? l.total : 0;
@@ -513,11 +543,7 @@ int launch_frechet_init(const float* X, long B, int k, long N, long max_iter, in
   if (init < 0 || init >= B) { set_error("dpb_frechet_init: init=%d outside [0,%ld)", init, B); return -1; }
   const FrPtrs p = fr_ptrs(scratch, l, B, k, max_iter);
   const int R = (int)(B * k);
-  if (launch_cross_gram(X, nullptr, p.G, R, R, N, st) != 0) return -1;
-  launch_gram_blocks(p.G, p.W, (int)B, R, k, k, st);                      // each basis's diagonal block of G into the slot its whitening matrix will take
-  launch_angles_prep(p.W, p.flags, (int)B, k, st);
-  const dim3 wg((unsigned)B, (unsigned)B);
-  DPB_BY_RANK(k, (void)NT; DPB_LAUNCH((fr_whiten_kernel<KM>), wg, dim3(256), 0, st, p.G, p.W, p.flags, R, k));
+  if (launch_whitened_gram(X, B, k, N, p.G, p.W, p.flags, st) != 0) return -1;
   DPB_LAUNCH(fr_init_kernel, dim3((unsigned)(((long)R * k + 255) / 256)), dim3(256), 0, st, p.Ct, p.ctl, R, k, init);
   DPB_CHECK(hipGetLastError());
   return 0;
@@ -560,9 +586,31 @@ int launch_frechet_finish(const float* X, long B, int k, long N, long max_iter, 
   DPB_BY_RANK(k, DPB_LAUNCH((fr_finish_head_kernel<KM, NT>), one, dim3(NT), 0, st, p.Ps, p.thetas, p.costs, p.flags, p.ctl, p.hist_cost, p.hist_g, p.Rot,
                            weight, theta, info, nb, k, max_iter));
   DPB_BY_RANK(k, (void)NT; DPB_LAUNCH((fr_finish_coef_kernel<KM>), gb, t256, 0, st, p.Ct, p.Rot, p.W, p.flags, p.Cn, k));
-  const int vec = (N % 4 == 0 && (uintptr_t)X % 16 == 0 && (uintptr_t)Y % 16 == 0) ? 1 : 0;
-  const dim3 sg((unsigned)((N + 255) / 256));
-  DPB_BY_TILES(k, DPB_LAUNCH((fr_stream_kernel<KT>), sg, t256, 0, st, X, p.Cn, Y, R, k, N, vec));
+  if (launch_coef_stream(X, p.Cn, Y, R, k, N, st) != 0) return -1;
+  DPB_CHECK(hipGetLastError());
+  return 0;
+}
+
+const double* frechet_ghat(long B, int k, long N, long max_iter, const void* scratch) {
+  FrLayout l;
+  return fr_layout(B, k, N, max_iter, l) ? (const double*)((const char*)scratch + l.G) : nullptr;
+}
+
+// the iteration restarted at the caller's point: C^T = Ct [R][k] (any full-rank coefficients on the whitened rows), whitened by the step's own
+// re-orthonormalisation -- the Cholesky factor of C Ghat C^T; the status cleared
+int launch_frechet_start(const double* Ct, long B, int k, long N, long max_iter, void* scratch, size_t scratch_bytes, hipStream_t st) {
+  FrLayout l;
+  if (fr_check("dpb_frechet_start", B, k, N, max_iter, scratch, scratch_bytes, l) != 0) return -1;
+  const FrPtrs p = fr_ptrs(scratch, l, B, k, max_iter);
+  const int R = (int)(B * k), nb = (int)B;
+  const dim3 gb((unsigned)B), one(1), t256(256);
+  DPB_LAUNCH(fr_start_kernel, dim3((unsigned)(((long)R * k + 255) / 256)), t256, 0, st, Ct, p.Cn, p.ctl, (long)R * k, 0);
+  fr_product(p, p.Cn, p.Nn, R, k, 1, st);
+  DPB_LAUNCH(fr_block_gram_kernel, gb, t256, 0, st, p.Nn, p.Cn, p.Ps, p.ctl, k);
+  DPB_LAUNCH(fr_sum_kernel, one, t256, 0, st, p.Ps, p.Gs, p.ctl, nb, k);
+  launch_angles_prep(p.Gs, p.rbad, 1, k, st);
+  DPB_LAUNCH(fr_apply_kernel, gb, t256, 0, st, p.Ct, p.Cn, p.Gs, p.rbad, p.ctl, k);
+  DPB_LAUNCH(fr_start_kernel, one, t256, 0, st, Ct, p.Cn, p.ctl, 0L, 1);      // (the apply counted a step: none was taken)
   DPB_CHECK(hipGetLastError());
   return 0;
 }

@@ -1,4 +1,4 @@
-// Device pieces shared by the geometry kernels (orth.hip, angles.hip, frechet.hip, geodesic.hip, transport.hip, hungarian.hip): the round-robin Jacobi
+// Device pieces shared by the geometry kernels (orth.hip, angles.hip, frechet.hip, flagmean.hip, geodesic.hip, transport.hip, hungarian.hip): the round-robin Jacobi
 // eigen-solve, the fixed-order block sum, the guarded four-column row access, the row-group step of the fp64 MFMA streams and the descending rank order.
 #pragma once
 #include "kernels.h"

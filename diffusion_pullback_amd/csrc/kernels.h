@@ -406,6 +406,25 @@ int launch_frechet_iterate(long B, int k, long N, long max_iter, int n_iter, dou
 int launch_frechet_finish(const float* X, long B, int k, long N, long max_iter, float* Y, float* weight, float* theta, double* info, void* scratch,
                           size_t scratch_bytes, hipStream_t st);
 
+// the whitened Gram Ghat [R][R] of X with its whitenings W [B][k][k] and flags [B] (dpb_frechet_init's first half), and the streaming finish
+// Y [k][N] = Z X from transposed fp64 coefficients Zt [R][k], k <= 64 -- both shared with flagmean.hip
+int launch_whitened_gram(const float* X, long B, int k, long N, double* G, double* W, int* flags, hipStream_t st);
+int launch_coef_stream(const float* X, const double* Zt, float* Y, int R, int k, long N, hipStream_t st);
+const double* frechet_ghat(long B, int k, long N, long max_iter, const void* scratch);   // Ghat inside a Frechet scratch block; nullptr when invalid
+int launch_frechet_start(const double* Ct, long B, int k, long N, long max_iter, void* scratch, size_t scratch_bytes, hipStream_t st);
+
+// ---------------------------------------------------------------- the flag (extrinsic) mean of B bases of k rows (flagmean.hip): the top-r eigenvectors
+// of the mean projector by block subspace iteration on the whitened Gram; ghat != nullptr: a caller's Ghat (the scratch then holds the solver only)
+constexpr int FLAG_MEAN_MAX_RANK = 64;   // the block of the subspace iteration is at most 64 columns wide: three 64 x 64 fp64 matrices of its head live in LDS
+int flag_mean_block_width(long R, int r);
+size_t flag_mean_scratch_bytes(long B, int k, long N, int r, long max_iter, bool own);   // 0 when invalid
+int launch_flag_mean_init(const float* X, const double* ghat, long B, int k, long N, int r, unsigned long long seed, long max_iter, void* scratch,
+                          size_t scratch_bytes, hipStream_t st);
+int launch_flag_mean_iterate(const double* ghat, long B, int k, long N, int r, long max_iter, int n_iter, double tol, void* scratch, size_t scratch_bytes,
+                             hipStream_t st);
+int launch_flag_mean_finish(const float* X, const double* ghat, long B, int k, long N, int r, long max_iter, float* Y, float* weight, float* theta, double* Ct,
+                            double* info, void* scratch, size_t scratch_bytes, hipStream_t st);
+
 // ---------------------------------------------------------------- the Hungarian-matched mean of B bases of k rows (hungarian.hip): a batched
 // linear-assignment solver (shortest augmenting paths in LDS, one workgroup per problem) and a streaming mean of permuted, signed rows; see include/dpb.h
 constexpr int HUNGARIAN_MAX_RANK = 128;   // the k x k fp64 cost matrix lives in LDS: 128 KiB of the 160 KiB a workgroup may declare

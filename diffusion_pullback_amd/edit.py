@@ -8,6 +8,7 @@ Mirrors the public surface of the reference's ``modules/edit.py``:
       run_DDIMinversion :613-678, run_edit_local_encoder_pullback_zt :680-779, run_edit_parallel_transport :782-948,
       run_edit_global_frechet_mean_zt :951-1246 (its global basis: geometry.frechet_mean),
       run_edit_global_hungarian_mean_zt :1249-1514 (its global bases: geometry.hungarian_mean),
+      run_edit_global_flag_mean_zt (not in the reference; a third global basis: geometry.flag_mean),
       run_sample_encoder_local_tangent_space_zt :1517-1599, DDIMforwardsteps :1601-1714, x_space_guidance :1716-1734
 
 Kept from the reference: the step counts (inv_steps-2 inversion steps, ``edit_t_idx`` forward steps,
@@ -810,7 +811,8 @@ class EditUncondDiffusion(_EditBase):
 
     @torch.no_grad()
     def run_edit_global_frechet_mean_zt(self, idx, op="mid", block_idx=0, vis_num=4, vis_num_pc=None, vis_pc_list=None, pca_rank=50, num_local_basis=100,
-                                        local_projection=True, frechet_mean_space="x", h_t=None, frechet_max_iter=1000, frechet_tol=1e-6):
+                                        local_projection=True, frechet_mean_space="x", h_t=None, frechet_max_iter=1000, frechet_tol=1e-6,
+                                        frechet_init="member"):
         """Reference: src/modules/edit.py:951-1246 -- edit sample idx along the directions of a GLOBAL basis, the Frechet mean on the Grassmannian of
         num_local_basis local tangent spaces at h_t (frechet_mean_space "x": the row spans of vT; "h": the column spans of u).
 
@@ -826,8 +828,12 @@ class EditUncondDiffusion(_EditBase):
         undefined).  Then the x-space-guidance path of the driver's other jobs: chains named xt-<dataset>_<idx>-h_<h_t>T-edit_<edit_t>T-<op>-block_<b>-
         seed_<seed>-pc_<pc>_{pos,neg}, pictures x0_gen-<name>.png, projection_coeff-<name>.png in the obs folder; the job is skipped when the last
         pc's _neg picture exists, an experiment when its own does.  trajectory_batch as in run_edit_parallel_transport.  The reference's parallel-h
-        and h_space_guidance branches are not built.  Returns a dict: basis [k, N] (rows), vk [P, N_x], pcs, names, info (None for a loaded basis)."""
+        and h_space_guidance branches are not built.  Returns a dict: basis [k, N] (rows), vk [P, N_x], pcs, names, info (None for a loaded basis).
+        frechet_init "member" starts the iteration at local basis 0, "flag" at the flag mean of them all (geometry.frechet_mean(init="flag")); the
+        info file of a "flag" run records it as ``init``."""
         from . import geometry
+        if frechet_init not in ("member", "flag"):
+            raise ValueError(f"frechet_init must be 'member' (start at local basis 0) or 'flag' (start at the flag mean), got {frechet_init!r}")
         if frechet_mean_space not in ("x", "h"):
             raise ValueError(f"frechet_mean_space must be 'x' (the spans of vT) or 'h' (the spans of u), got {frechet_mean_space!r}")
         if frechet_mean_space == "h" and not local_projection:
@@ -862,7 +868,9 @@ class EditUncondDiffusion(_EditBase):
                                             block_idx, pca_rank, 1e-4, local_dir, lambda *a: None)
             with T.phase("Frechet mean of the local bases"):
                 stack = torch.stack([load(p[3][2]) if frechet_mean_space == "x" else load(p[3][0]).t() for p in pairs]).contiguous()
-                basis, info = geometry.frechet_mean(stack, max_iter=frechet_max_iter, tol=frechet_tol)
+                basis, info = geometry.frechet_mean(stack, init="flag" if frechet_init == "flag" else 0, max_iter=frechet_max_iter, tol=frechet_tol)
+                if frechet_init == "flag":
+                    info["init"] = "flag"
             print(f"Frechet mean of {num_local_basis} local bases in {frechet_mean_space}-space: {info['iterations']} steps, gradient norm "
                   f"{info['grad_norm']:.3e}, cost {info['cost'][0]:.6f} -> {info['cost'][-1]:.6f}" + ("" if info["converged"] else
                   f" -- NOT converged to {frechet_tol:g} in {frechet_max_iter} steps"))
@@ -872,6 +880,82 @@ class EditUncondDiffusion(_EditBase):
 
         return self._edit_along_global_basis(idx, op, block_idx, vis_num, pcs, pca_rank, h_t, frechet_mean_space, local_projection, basis,
                                              basis if frechet_mean_space == "h" else None, dict(basis=basis, pcs=pcs, names=[], info=info))
+
+    def global_flag_mean_paths(self, op="mid", block_idx=0, pca_rank=50, num_local_basis=100, flag_mean_space="x", h_t=None, flag_rank=None):
+        """(basis file, info file) of the flag-mean global basis, laid out as global_frechet_mean_paths: u- (space h) or v- (space x) +
+        <h_t>T-<op>-block_<b>-seed_<seed>-num_local_basis_<n>-rank_<r>.pt holds [N, r] columns"""
+        h_t = self.h_t if h_t is None else h_t
+        r = pca_rank if not flag_rank else flag_rank
+        save_dir = os.path.join(self.input_root, f"global_flag_mean_uncond-model_{self.model_name}-dataset_{self.dataset_name}-num_steps_{self.for_steps}-pca_rank_{pca_rank}")
+        name = f"{h_t}T-{op}-block_{block_idx}-seed_{self.seed}-num_local_basis_{num_local_basis}-rank_{r}"
+        tag = "u" if flag_mean_space == "h" else "v"
+        return os.path.join(save_dir, f"{tag}-{name}.pt"), os.path.join(save_dir, f"info-{tag}-{name}.pt")
+
+    @torch.no_grad()
+    def run_edit_global_flag_mean_zt(self, idx, op="mid", block_idx=0, vis_num=4, vis_num_pc=None, vis_pc_list=None, pca_rank=50, num_local_basis=100,
+                                     local_projection=True, flag_mean_space="x", h_t=None, flag_rank=None):
+        """Edit sample idx along the rows of the third GLOBAL basis: the flag (extrinsic) mean of num_local_basis local tangent spaces at h_t --
+        the top flag_rank eigenvectors of their mean projector (geometry.flag_mean; flag_mean_space "x": the row spans of vT, "h": the column spans of
+        u).  flag_rank None or 0: pca_rank; 1 <= flag_rank <= pca_rank.  Not in the reference: where the local spaces hold a few shared directions and
+        many of their own the Karcher mean of run_edit_global_frechet_mean_zt is not well posed, and the flag mean's spectrum says how many they share.
+
+        Built like run_edit_global_frechet_mean_zt: the same xt-Random_<i>-... local-basis files of the 'Random' sampling directory, the missing ones
+        sampled together and saved there; the basis written as [N, r] columns under global_flag_mean_paths with an info- file (weight, eigenvalues,
+        gap, theta, iterations, converged, space, names) beside it, an existing file loaded and column-normalised; the printed summary shows the
+        spectrum around row r, so that a missing gap is seen; then the common tail _edit_along_global_basis (local_projection=False: space x only).
+        A pc >= flag_rank raises ValueError.  Returns a dict: basis [r, N] (rows), vk [P, N_x], pcs, names, info (None for a loaded basis)."""
+        from . import geometry
+        if flag_mean_space not in ("x", "h"):
+            raise ValueError(f"flag_mean_space must be 'x' (the spans of vT) or 'h' (the spans of u), got {flag_mean_space!r}")
+        if flag_mean_space == "h" and not local_projection:
+            raise ValueError("local_projection=False is valid for flag_mean_space 'x' only: an h-space direction reaches x-space through the sample's "
+                             "own local basis")
+        r = int(pca_rank if not flag_rank else flag_rank)
+        if not 1 <= r <= pca_rank:
+            raise ValueError(f"flag_rank = {r} outside [1, pca_rank = {pca_rank}]")
+        h_t = self.h_t if h_t is None else h_t
+        pcs = list(range(vis_num_pc or 0)) if vis_pc_list is None else [int(p) for p in vis_pc_list]
+        if any(p < 0 or p >= r for p in pcs):
+            raise ValueError(f"the flag-mean basis has {r} rows: pcs {pcs} must lie in [0, {r})")
+        exp = lambda pc, tag: f"xt-{self.dataset_name}_{idx}-h_{h_t}T-edit_{self.edit_t}T-{op}-block_{block_idx}-seed_{self.seed}-pc_{pc:0=3d}_{tag}"
+        if pcs and os.path.exists(os.path.join(self.result_folder, f"x0_gen-{exp(pcs[-1], 'neg')}.png")):
+            print("!!!ALREADY DONE EXP :", exp(pcs[-1], "neg"), "!!!")
+            return None
+        self.scheduler.set_timesteps(self.for_steps, device=self.device)
+        h_t_idx = int((self.scheduler.timesteps - h_t * 1000).abs().argmin())
+        load = lambda p: torch.load(p, map_location=self.device).to(torch.float32)
+
+        basis_path, info_path = self.global_flag_mean_paths(op, block_idx, pca_rank, num_local_basis, flag_mean_space, h_t, r)
+        os.makedirs(os.path.dirname(basis_path), exist_ok=True)
+        info = None
+        if os.path.exists(basis_path):
+            cols = load(basis_path)
+            basis = (cols / cols.norm(dim=0, keepdim=True)).t().contiguous()
+        else:
+            local_dir, local_name = self._tangent_space_naming(op, block_idx, pca_rank, dataset_name="Random")
+            pairs = self._tangent_space_pairs(h_t, num_local_basis, local_dir, local_name)
+            pending = [p for p in pairs if not (os.path.exists(p[3][0]) and os.path.exists(p[3][2]))]
+            if pending:
+                os.makedirs(local_dir, exist_ok=True)
+                latent = self._random_latent if self.dataset_name == "Random" else self._seeded_latent
+                self._sample_tangent_spaces(pending, lambda i, ht: self.DDIMforwardsteps(latent(i), t_start_idx=0, t_end_idx=h_t_idx)[:2], None, op,
+                                            block_idx, pca_rank, 1e-4, local_dir, lambda *a: None)
+            with T.phase("flag mean of the local bases"):
+                stack = torch.stack([load(p[3][2]) if flag_mean_space == "x" else load(p[3][0]).t() for p in pairs]).contiguous()
+                basis, info = geometry.flag_mean(stack, rank=r)
+            eig = info["eigenvalues"]
+            lo, hi = max(0, r - 3), min(len(eig), r + 3)
+            around = " ".join(f"{v:.4f}" for v in eig[lo:r]) + " | " + " ".join(f"{v:.4f}" for v in eig[r:hi])
+            print(f"flag mean of {num_local_basis} local bases in {flag_mean_space}-space, rank {r}: {info['iterations']} iterations, residual "
+                  f"{info['residual']:.3e}" + ("" if info["converged"] else " -- NOT converged: row r sits inside the bulk of the spectrum")
+                  + f"; mean cos^2 of rows {lo} .. {hi - 1} (| after row {r - 1}): {around}"
+                  + ("" if info["gap"] is None else f"; gap {info['gap']:.4f}"))
+            torch.save(basis.t().contiguous().cpu(), basis_path)
+            info = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in info.items()}
+            torch.save(dict(info, space=flag_mean_space, names=[p[2] for p in pairs]), info_path)
+
+        return self._edit_along_global_basis(idx, op, block_idx, vis_num, pcs, pca_rank, h_t, flag_mean_space, local_projection, basis,
+                                             basis if flag_mean_space == "h" else None, dict(basis=basis, pcs=pcs, names=[], info=info))
 
     def _edit_along_global_basis(self, idx, op, block_idx, vis_num, pcs, pca_rank, h_t, space, local_projection, basis, basis_h, out):
         """The common tail of the global-basis jobs (edit.py:1082-1246, :1354-1468): edit sample idx along rows pcs of `basis` [k, N] -- rows of x-space
@@ -905,7 +989,10 @@ class EditUncondDiffusion(_EditBase):
             return out
         if local_projection:
             with T.phase("projection of the global directions on the local basis"):
-                vk = geometry.transport_directions(basis, vT if space == "x" else u.t(), vT, pcs)[0][0]      # [P, N_x]
+                own = vT if space == "x" else u.t()
+                short = own.shape[0] - basis.shape[0]            # (a basis of fewer rows than the local one: padded with row 0, which no pc beyond names)
+                src = basis if short <= 0 else torch.cat([basis, basis[:1].expand(short, -1)])
+                vk = geometry.transport_directions(src, own, vT, pcs)[0][0]      # [P, N_x]
         else:
             vk = basis[pcs] / basis[pcs].norm(dim=1, keepdim=True)                              # edit.py:1155-1156
         out["vk"] = vk

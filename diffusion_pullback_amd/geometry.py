@@ -9,6 +9,10 @@ float64 at 1e-6 rad per angle -- small angles included, which the usual fp32 ``q
 ``transport_directions`` is the direction arithmetic of ``run_edit_parallel_transport`` (``csrc/transport.hip``): a source direction of h-space
 expressed in a target's basis and carried to the target's x-space, fp64 on the h-space side, a fixed-order fp32 stream on the x-space side.
 
+``flag_mean`` is the flag (extrinsic, chordal) mean of many such bases -- the global basis of ``run_edit_global_flag_mean_zt`` (``csrc/flagmean.hip``):
+the top eigenvectors of the mean projector, by block subspace iteration on the same whitened fp64 Gram; closed form, any rank, nested, and its
+spectrum says how many directions the local spaces share.
+
 ``frechet_mean`` is the Frechet (Karcher) mean on the Grassmannian of many such bases -- the global basis of ``run_edit_global_frechet_mean_zt``
 (``csrc/frechet.hip``): the Riemannian fixed-step iteration on coefficients against the whitened fp64 Gram of all rows, one streaming pass over the
 rows before it and one after it.
@@ -207,7 +211,86 @@ def transport_directions(u_src: torch.Tensor, u_dst: torch.Tensor, vT_dst: torch
     return vk, coef, coef_norm
 
 
-def frechet_mean(A: torch.Tensor, init: int = 0, max_iter: int = 1000, tol: float = 1e-6, step: float = 1.0, check_every: int = 16,
+FLAG_MEAN_MAX_RANK = 64              # FLAG_MEAN_MAX_RANK of the library (the block of the subspace iteration is at most 64 columns wide)
+
+
+def _flag_solve(lib, b: int, k: int, n: int, r: int, max_iter: int, tol: float, check_every: int, seed: int, X, ghat, scratch, need: int, st):
+    """init and the chunked iteration of dpb_flag_mean_* on X (ghat None) or on a caller's Ghat; the status read after a chunk is the only sync"""
+    L.check(lib.dpb_flag_mean_init(None if X is None else X.data_ptr(), ghat, b, k, n, r, seed, max_iter, scratch.data_ptr(), need, st))
+    asked = 0
+    while asked < max_iter:
+        steps = min(check_every, max_iter - asked)
+        L.check(lib.dpb_flag_mean_iterate(steps, float(tol), ghat, b, k, n, r, max_iter, scratch.data_ptr(), need, st))
+        asked += steps
+        if int(scratch[:4].view(torch.int32).item()) != 0:
+            break
+
+
+def _flag_info(raw: np.ndarray, b: int, r: int, weight, theta) -> dict:
+    m = int(raw[3])
+    eig = raw[8:8 + m] / b
+    return {"iterations": int(raw[0]), "converged": int(raw[1]) == 1, "residual": float(raw[2]), "weight": weight, "eigenvalues": eig.copy(),
+            "gap": float(eig[r - 1] - eig[r]) if m > r else None, "theta": theta, "degenerate": np.nonzero(raw[72:72 + b] != 0)[0].tolist()}
+
+
+def flag_mean(A: torch.Tensor, rank: Optional[int] = None, max_iter: int = 1000, tol: float = 1e-12, check_every: int = 16, seed: int = 0,
+              max_bytes: Optional[int] = None, check: bool = True) -> Tuple[torch.Tensor, dict]:
+    """The flag (extrinsic, chordal) mean of the row spans of A [B, k, N]: the top ``rank`` eigenvectors of the mean projector (1/B) sum_i Q_i^T Q_i
+    over the orthonormalised members (Draper et al. 2014) -- closed form, no cut locus, defined for every rank in [1, min(64, B k, N)] (None: k), and
+    nested: rows 0 .. j-1 are the rank-j mean (dpb_flag_mean_init / _iterate / _finish; see include/dpb.h for the method and the limits).  Rows need
+    not be orthonormal, only independent; any float dtype is converted to contiguous fp32; k <= 64.
+
+    Returns Y [rank, N] fp32 with orthonormal rows in descending eigenvalue order and info: ``iterations``, ``converged`` (the relative residual of
+    the top ``rank`` Ritz pairs fell to tol), ``residual`` (the last one computed), ``weight`` [rank] (fp32: eigenvalue j, the mean cos^2 with which the
+    members hold row j), ``eigenvalues`` (fp64 numpy: all m Ritz values of the solver's block, the oversampled ones included -- a gap in them is the
+    number of directions the members share), ``gap`` (weight[rank-1] minus the next one; None when the block is no wider than rank), ``theta``
+    [B, min(rank, k)] (fp32: the principal angles of span Y to every member, descending) and ``degenerate``.
+
+    Block subspace iteration with a Rayleigh-Ritz step per iteration on the whitened fp64 Gram of all B k rows, in chunks of check_every iterations
+    with one status read per chunk.  Not converging within max_iter is not an error -- it is the answer when row ``rank`` sits inside the bulk of the
+    spectrum: converged is False, Y is still orthonormal and weight its Rayleigh quotients.  The Gram must fit max_bytes (8 (B k)^2 bytes plus the
+    block).  check: raise ValueError naming the degenerate bases; False returns the NaNs.  Bitwise reproducible for a given seed (the start block)."""
+    lib = L.load()
+    A = _stack(A, "A")
+    b, k, n = A.shape
+    if k > FRECHET_MAX_RANK:
+        raise ValueError(f"k = {k} rows per basis exceeds the rank {FRECHET_MAX_RANK} the flag mean supports")
+    if k > n:
+        raise ValueError(f"k = {k} rows per basis exceeds their length N = {n}: they cannot be independent")
+    r = k if rank is None else int(rank)
+    top = min(FLAG_MEAN_MAX_RANK, b * k, n)
+    if not 1 <= r <= top:
+        raise ValueError(f"rank = {r} outside [1, min({FLAG_MEAN_MAX_RANK}, B k = {b * k}, N = {n}) = {top}]")
+    max_iter, check_every, seed = int(max_iter), int(check_every), int(seed)
+    if max_iter < 0 or check_every < 1 or not tol >= 0 or seed < 0:
+        raise ValueError(f"max_iter = {max_iter} must be >= 0, check_every = {check_every} >= 1, tol = {tol} >= 0 and seed = {seed} >= 0")
+    max_bytes = DEFAULT_MAX_BYTES if max_bytes is None else int(max_bytes)
+    need = int(lib.dpb_flag_mean_scratch_bytes(b, k, n, r, max_iter))
+    if need == 0:
+        raise L.DpbError(f"dpb_flag_mean does not take B = {b}, k = {k}, N = {n}, r = {r}, max_iter = {max_iter}")
+    if need > max_bytes:
+        raise ValueError(f"the flag mean of B = {b} bases of k = {k} rows needs {need} bytes of device scratch (the fp64 Gram of all {b * k} rows), "
+                         f"max_bytes is {max_bytes}")
+    d = min(r, k)
+    with torch.cuda.device(A.device):
+        st = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
+        scratch = torch.empty(need, dtype=torch.uint8, device=A.device)
+        Y = torch.empty(r, n, dtype=torch.float32, device=A.device)
+        weight = torch.empty(r, dtype=torch.float32, device=A.device)
+        theta = torch.empty(b, d, dtype=torch.float32, device=A.device)
+        Ct = torch.empty(b * k, r, dtype=torch.float64, device=A.device)
+        info_d = torch.empty(72 + b, dtype=torch.float64, device=A.device)
+        _flag_solve(lib, b, k, n, r, max_iter, tol, check_every, seed, A, None, scratch, need, st)
+        L.check(lib.dpb_flag_mean_finish(A.data_ptr(), None, Y.data_ptr(), weight.data_ptr(), theta.data_ptr(), Ct.data_ptr(), info_d.data_ptr(),
+                                         b, k, n, r, max_iter, scratch.data_ptr(), need, st))
+        raw = info_d.cpu().numpy()
+    info = _flag_info(raw, b, r, weight, theta)
+    if check and info["degenerate"]:
+        raise ValueError(f"{DEGENERATE}: indices {info['degenerate']}")
+    return Y, info
+
+
+def frechet_mean(A: torch.Tensor, init=0, max_iter: int = 1000, tol: float = 1e-6, step: float = 1.0, check_every: int = 16,
                  max_bytes: Optional[int] = None, check: bool = True) -> Tuple[torch.Tensor, dict]:
     """The Frechet (Karcher) mean on the Grassmannian of the row spans of A [B, k, N]: the k-dimensional subspace Y minimising
     (1 / 2B) sum_i ||theta(Y, A_i)||_2^2, by Y <- Exp_Y(step * mean_i Log_Y(A_i)) started at the span of A[init] (dpb_frechet_init / _iterate / _finish;
@@ -222,7 +305,11 @@ def frechet_mean(A: torch.Tensor, init: int = 0, max_iter: int = 1000, tol: floa
     of a chunk after convergence are empty launches.  Not reaching tol within max_iter is not an error: converged is False.  The fp64 Gram of all B k
     rows must fit max_bytes (8 (B k)^2 bytes plus the coefficient buffers).  check: raise ValueError naming the degenerate bases, or the basis whose
     largest principal angle to the iterate left the log map's domain (pi/2 - 1e-6); False returns the NaNs and, in info, ``degenerate`` and ``domain``.
-    A cost that rises by more than 1e-12 relative between two steps raises DpbError: the step is too long for this set.  Bitwise reproducible."""
+    A cost that rises by more than 1e-12 relative between two steps raises DpbError: the step is too long for this set.  Bitwise reproducible.
+
+    init="flag" starts at the rank-k flag mean instead of a member (flag_mean: central, so no member is near pi/2 from it): the flag solver runs on the
+    whitened Gram this call has already formed -- there is no second pass over the rows -- for at most 64 iterations (to a residual of 1e-10), and
+    dpb_frechet_start takes its coefficients; info then holds ``flag_iterations`` and ``flag_converged``.  Any other string raises ValueError."""
     lib = L.load()
     A = _stack(A, "A")
     b, k, n = A.shape
@@ -230,7 +317,10 @@ def frechet_mean(A: torch.Tensor, init: int = 0, max_iter: int = 1000, tol: floa
         raise ValueError(f"k = {k} rows per basis exceeds the rank {FRECHET_MAX_RANK} the Frechet mean supports")
     if k > n:
         raise ValueError(f"k = {k} rows per basis exceeds their length N = {n}: they cannot be independent")
-    init, max_iter, check_every = int(init), int(max_iter), int(check_every)
+    from_flag = isinstance(init, str)
+    if from_flag and init != "flag":
+        raise ValueError(f"init must be the index of a member or 'flag', got {init!r}")
+    init, max_iter, check_every = 0 if from_flag else int(init), int(max_iter), int(check_every)
     if not 0 <= init < b:
         raise ValueError(f"init = {init} outside [0, B = {b})")
     if max_iter < 0 or check_every < 1 or not tol >= 0 or not step > 0:
@@ -250,6 +340,23 @@ def frechet_mean(A: torch.Tensor, init: int = 0, max_iter: int = 1000, tol: floa
         theta = torch.empty(b, k, dtype=torch.float32, device=A.device)
         info_d = torch.empty(8 + 2 * max_iter + 1 + b, dtype=torch.float64, device=A.device)
         L.check(lib.dpb_frechet_init(A.data_ptr(), b, k, n, init, max_iter, scratch.data_ptr(), need, st))
+        flag_raw = None
+        if from_flag:
+            flag_iter = 64                                   # (a start, not an answer: row k may sit inside the bulk, where the block never settles)
+            fneed = int(lib.dpb_flag_mean_solver_bytes(b, k, k, flag_iter))
+            ghat = lib.dpb_frechet_ghat(b, k, n, max_iter, scratch.data_ptr())
+            if fneed == 0 or not ghat:
+                raise L.DpbError(f"dpb_flag_mean does not take B = {b}, k = {k}, r = {k} on the Frechet mean's Gram")
+            if need + fneed > max_bytes:
+                raise ValueError(f"the flag start of the Frechet mean needs {fneed} more bytes of device scratch, max_bytes is {max_bytes}")
+            fscratch = torch.empty(fneed, dtype=torch.uint8, device=A.device)
+            fCt = torch.empty(b * k, k, dtype=torch.float64, device=A.device)
+            finfo = torch.empty(72 + b, dtype=torch.float64, device=A.device)
+            _flag_solve(lib, b, k, n, k, flag_iter, 1e-10, check_every, 0, None, ghat, fscratch, fneed, st)
+            L.check(lib.dpb_flag_mean_finish(None, ghat, None, weight.data_ptr(), theta.data_ptr(), fCt.data_ptr(), finfo.data_ptr(), b, k, n, k,
+                                             flag_iter, fscratch.data_ptr(), fneed, st))
+            L.check(lib.dpb_frechet_start(fCt.data_ptr(), b, k, n, max_iter, scratch.data_ptr(), need, st))
+            flag_raw = finfo.cpu().numpy()
         asked = 0
         while asked < max_iter:
             steps = min(check_every, max_iter - asked)
@@ -266,6 +373,8 @@ def frechet_mean(A: torch.Tensor, init: int = 0, max_iter: int = 1000, tol: floa
     degenerate = np.nonzero(raw[8 + 2 * max_iter + 1:] != 0)[0].tolist()
     info = {"iterations": iters, "converged": done == 1, "grad_norm": float(ghist[-1]) if len(ghist) else float("nan"), "cost": cost,
             "grad_norm_history": ghist, "weight": weight, "theta": theta, "degenerate": degenerate, "domain": domain if done == 2 else None}
+    if flag_raw is not None:
+        info["flag_iterations"], info["flag_converged"] = int(flag_raw[0]), int(flag_raw[1]) == 1
     if check:
         if degenerate:
             raise ValueError(f"{DEGENERATE}: indices {degenerate}")

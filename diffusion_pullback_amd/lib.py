@@ -110,6 +110,14 @@ SYMBOLS = {
     "dpb_frechet_init": (_I, [_P, _I, _I, _L, _I, _I, _P, C.c_size_t, _P]),
     "dpb_frechet_iterate": (_I, [_I, C.c_double, C.c_double, _I, _I, _L, _I, _P, C.c_size_t, _P]),
     "dpb_frechet_finish": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _P, C.c_size_t, _P]),
+    "dpb_frechet_ghat": (_P, [_I, _I, _L, _I, _P]),
+    "dpb_frechet_start": (_I, [_P, _I, _I, _L, _I, _P, C.c_size_t, _P]),
+    # flag (extrinsic) mean of subspaces (geometry.flag_mean): init / iterate / finish on one scratch block, or on a caller's Ghat
+    "dpb_flag_mean_scratch_bytes": (C.c_size_t, [_I, _I, _L, _I, _I]),
+    "dpb_flag_mean_solver_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "dpb_flag_mean_init": (_I, [_P, _P, _I, _I, _L, _I, C.c_uint64, _I, _P, C.c_size_t, _P]),
+    "dpb_flag_mean_iterate": (_I, [_I, C.c_double, _P, _I, _I, _L, _I, _I, _P, C.c_size_t, _P]),
+    "dpb_flag_mean_finish": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _P, C.c_size_t, _P]),
     # Grassmann geodesics (geometry.principal_vectors / grassmann_log / grassmann_geodesic / grassmann_exp): ts is a host double array
     "dpb_grassmann_scratch_bytes": (C.c_size_t, [_I, _I, _I, _L]),
     "dpb_grassmann_pair": (_I, [_P, _L, _P, _I, _I, _L, _I, C.POINTER(C.c_double), _I, _P, _P, _P, _P, _P, C.c_size_t, _P]),

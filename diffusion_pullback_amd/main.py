@@ -29,6 +29,10 @@ sampling directory at --h_t (x: the spans of vT, h: the spans of u; missing ones
 --frechet_max_iter, --frechet_tol: both new; the reference hands the problem to pymanopt) and cached as v- / u-....pt with an info- file beside it.
 --local_projection False (space x only) skips the projection on the sample's own tangent space.  It honours --op, --block_idx, --pca_rank,
 --vis_num, --vis_num_pc and --trajectory_batch as the transport job does.
+--frechet_init member|flag (new; default member: local basis 0) starts the iteration at the flag mean of the local bases instead.
+``--run_edit_global_flag_mean_zt True --flag_mean_space x|h --flag_rank r`` (new; unconditional nets only) edits --sample_idx along the rows of the
+flag (extrinsic) mean of the same local bases: the top r eigenvectors of their mean projector (geometry.flag_mean; --flag_rank 0, the default, means
+--pca_rank), cached as v- / u-...-rank_<r>.pt with an info- file that holds the spectrum.  It takes the Frechet job's other flags.
 ``--run_edit_global_hungarian_mean_zt True --hungarian_mean_space x|h`` (the reference's flags, define_argparser.py:121-122; unconditional nets only)
 edits --sample_idx along the other global basis: the Hungarian-matched mean of the same local bases -- the directions of every basis matched one to
 one and sign by sign to those of basis 0 and averaged (geometry.hungarian_mean; --hungarian_distance 1/cosine|cosine and --hungarian_max_sweeps are
@@ -87,6 +91,8 @@ _FLAGS = [  # (name, type, default) -- define_argparser.py:20-110, live path onl
     # reference hands pymanopt 10 000 iterations)
     ("run_edit_global_frechet_mean_zt", str2bool, False), ("frechet_mean_space", str, "x"), ("frechet_max_iter", int, 1000),
     ("frechet_tol", float, 1e-6), ("local_projection", str2bool, True),
+    # new: the start of the Karcher iteration (member: local basis 0; flag: the flag mean), and the flag-mean global-basis job (flag_rank 0: pca_rank)
+    ("frechet_init", str, "member"), ("run_edit_global_flag_mean_zt", str2bool, False), ("flag_mean_space", str, "x"), ("flag_rank", int, 0),
     # define_argparser.py:121-122: the other global-basis job (unconditional nets); hungarian_mean_space defaults to x, what the reference's method
     # does (its flag has no consumer); hungarian_distance / hungarian_max_sweeps are new (the reference passes distance='1/cosine')
     ("run_edit_global_hungarian_mean_zt", str2bool, False), ("hungarian_mean_space", str, "x"), ("hungarian_distance", str, "1/cosine"),
@@ -136,6 +142,17 @@ def parse_args(argv=None):
         p.error("--frechet_mean_space must be x (the spans of vT) or h (the spans of u)")
     if args.run_edit_global_frechet_mean_zt and args.frechet_mean_space == "h" and not args.local_projection:
         p.error("--local_projection False is valid for --frechet_mean_space x only")
+    if args.frechet_init not in ("member", "flag"):
+        p.error("--frechet_init must be member (start at local basis 0) or flag (start at the flag mean of the local bases)")
+    if args.run_edit_global_flag_mean_zt and "stable-diffusion" in args.model_name:
+        p.error("--run_edit_global_flag_mean_zt is a job of the unconditional nets only: the reference has no Stable Diffusion global basis "
+                "(its global-basis jobs belong to EditUncondDiffusion)")
+    if args.run_edit_global_flag_mean_zt and args.flag_mean_space not in ("x", "h"):
+        p.error("--flag_mean_space must be x (the spans of vT) or h (the spans of u)")
+    if args.run_edit_global_flag_mean_zt and args.flag_mean_space == "h" and not args.local_projection:
+        p.error("--local_projection False is valid for --flag_mean_space x only")
+    if args.run_edit_global_flag_mean_zt and not 0 <= args.flag_rank <= args.pca_rank:
+        p.error("--flag_rank must lie in [1, --pca_rank] (0: --pca_rank)")
     if args.run_edit_global_hungarian_mean_zt and "stable-diffusion" in args.model_name:
         p.error("--run_edit_global_hungarian_mean_zt is a job of the unconditional nets only: the reference has no Stable Diffusion global Hungarian "
                 "basis (its run_edit_global_hungarian_mean_zt belongs to EditUncondDiffusion)")
@@ -217,7 +234,7 @@ def transport_group(args) -> int:
 
 
 def frechet_group(args) -> int:
-    """local bases a global-basis job (run_edit_global_frechet_mean_zt, run_edit_global_hungarian_mean_zt) may have to sample together: up to num_local_basis, bounded like tangent_space_group"""
+    """local bases a global-basis job (run_edit_global_frechet_mean_zt, run_edit_global_flag_mean_zt, run_edit_global_hungarian_mean_zt) may have to sample together: up to num_local_basis, bounded like tangent_space_group"""
     return max(1, min(max(1, args.num_local_basis), args.memory_bound, TANGENT_BUDGET // max(args.pca_rank, 1)))
 
 
@@ -242,8 +259,9 @@ def build_unet(args) -> PullbackUNet:
             # ... and the chains together: 2 * vis_num_pc per target and for the source, 2 rows each per guidance step, vis_num + 1 decode states each
             n = 2 * args.vis_num_pc * (1 + len(args.sample_idx_1_values))
             max_batch = max(max_batch, min(args.trajectory_batch, 2 * n), min(args.trajectory_batch, n * (args.vis_num + 1)))
-    if getattr(args, "run_edit_global_frechet_mean_zt", False) or getattr(args, "run_edit_global_hungarian_mean_zt", False):
-        # the local bases either global-basis job may have to sample, in groups; and the 2 * vis_num_pc chains together
+    if (getattr(args, "run_edit_global_frechet_mean_zt", False) or getattr(args, "run_edit_global_hungarian_mean_zt", False)
+            or getattr(args, "run_edit_global_flag_mean_zt", False)):
+        # the local bases a global-basis job may have to sample, in groups; and the 2 * vis_num_pc chains together
         max_batch = max(max_batch, frechet_group(args))
         max_rank = max(max_rank, frechet_group(args) * args.pca_rank)
         if getattr(args, "trajectory_batch", 0) > 1:
@@ -360,7 +378,11 @@ def main(argv=None):
         edit.run_edit_global_frechet_mean_zt(idx=args.sample_idx, op=args.op, block_idx=args.block_idx, vis_num=args.vis_num, vis_num_pc=args.vis_num_pc,
                                              pca_rank=args.pca_rank, num_local_basis=args.num_local_basis, local_projection=args.local_projection,
                                              frechet_mean_space=args.frechet_mean_space, h_t=args.h_t, frechet_max_iter=args.frechet_max_iter,
-                                             frechet_tol=args.frechet_tol)
+                                             frechet_tol=args.frechet_tol, frechet_init=args.frechet_init)
+    if args.run_edit_global_flag_mean_zt:                                        # (not in the reference: the third global basis)
+        edit.run_edit_global_flag_mean_zt(idx=args.sample_idx, op=args.op, block_idx=args.block_idx, vis_num=args.vis_num, vis_num_pc=args.vis_num_pc,
+                                          pca_rank=args.pca_rank, num_local_basis=args.num_local_basis, local_projection=args.local_projection,
+                                          flag_mean_space=args.flag_mean_space, h_t=args.h_t, flag_rank=args.flag_rank)
     if args.run_edit_global_hungarian_mean_zt:                                   # (the reference's main.py never calls it; its method's own defaults otherwise)
         edit.run_edit_global_hungarian_mean_zt(idx=args.sample_idx, op=args.op, block_idx=args.block_idx, vis_num=args.vis_num,
                                                vis_num_pc=args.vis_num_pc, pca_rank=args.pca_rank, num_local_basis=args.num_local_basis,

@@ -317,6 +317,52 @@ int dpb_frechet_iterate(int n_iter, double step, double tol, int B, int k, int64
 int dpb_frechet_finish(const float* X, float* Y, float* weight, float* theta, double* info, int B, int k, int64_t N, int max_iter, void* scratch,
                        size_t scratch_bytes, void* hip_stream);
 
+/* dpb_frechet_start (additive): the iteration restarted at a caller's point, after dpb_frechet_init.  Ct [R][k] fp64 on the device: the point's
+ * coefficients on the whitened rows, transposed as the state keeps them (Y = C Q; any full-rank C).  It overwrites C in the state, whitens it by the
+ * step's own re-orthonormalisation (the Cholesky factor of C Ghat C^T) and clears the status and the histories' count; Ghat is not formed again.
+ * dpb_frechet_ghat: the device address of Ghat [R][R] inside a Frechet scratch block (host arithmetic only; NULL with the error set when the
+ * arguments are no Frechet problem) -- what dpb_flag_mean_* take as a caller's Ghat. */
+const double* dpb_frechet_ghat(int B, int k, int64_t N, int max_iter, const void* scratch);
+int dpb_frechet_start(const double* Ct, int B, int k, int64_t N, int max_iter, void* scratch, size_t scratch_bytes, void* hip_stream);
+
+/* ---- Flag (extrinsic, chordal) mean of subspaces (additive to ABI version 1; engine-independent) -----------------------------------------
+ * The global basis of run_edit_global_flag_mean_zt (Draper et al. 2014; Marrinan et al., CVPR 2014): the top-r eigenvectors of the mean projector
+ * P = (1/B) sum_i Q_i^T Q_i over the orthonormalised bases Q_i = W_i X_i.  Closed form, no cut locus, defined for every rank r, nested (rows 0..j-1
+ * are the rank-j mean); eigenvalue j in [0, 1] is the mean cos^2 with which the members hold row j.  X [B][k][N] fp32 as for dpb_frechet_*; R = B k.
+ *
+ * Method (csrc/flagmean.hip).  Every row lies in the span of the R given rows, Y = C Q, and P Q^T c = (1/B) Q^T Ghat c with Ghat the whitened Gram of
+ * dpb_frechet_init (the same code forms it): the rows of C are eigenvectors of Ghat scaled by lambda^-1/2, so C Ghat C^T = I.  Block subspace
+ * iteration on m = min(64, R, 16 ceil((r + 8) / 16)) columns Z [R][m], orthonormal, started at a fixed function of (seed, R, m) (the identity when
+ * m = R: one step is then exact); per iteration, all fp64: W = Ghat Z (one pass over Ghat on the fp64 matrix cores, a workgroup per 32 rows);
+ * T = Z^T W = S Lambda S^T (two-sided Jacobi in LDS), descending; res = max_{j<r} ||(W S)_j - lambda_j (Z S)_j||_2 / lambda_0; Z <- orth(W S) through
+ * the eigen-decomposition of the Gram of W S, twice (W S V D^-1/2, then the symmetric Z1 (Z1^T Z1)^-1/2), directions below 1e-13 of the largest D
+ * dropped (Ghat is rank deficient when R > N or members share directions exactly).
+ * dpb_flag_mean_init: forms Ghat from X -- or takes the caller's Ghat (X = NULL; dpb_frechet_ghat) -- and the orthonormal start block.
+ * dpb_flag_mean_iterate: n_iter iterations.  An iteration that finds res <= tol sets status.done = 1 and does not move the block; a NaN (a degenerate
+ *   basis) sets done = 2; max_iter iterations taken: done = 3.  Once done the remaining launches of this and later calls are no-ops.
+ * dpb_flag_mean_finish: one more Rayleigh-Ritz step on the block as it stands, taken in the ambient space (the pencil (W^T W, Z^T W): the mean
+ *   projector against the Gram of the rows Z^T Q) -- the rows returned are orthonormal and the values returned are their Rayleigh quotients, converged
+ *   or not; at convergence they are the eigenpairs.  Y [r][N] fp32 (orthonormal rows, descending eigenvalue; with X: one pass over X, fr_stream_kernel's method), weight [r]
+ *   fp32 = lambda_j / B, theta [B][min(r,k)] fp32 (principal angles of span Y to every member, descending; Jacobi on the smaller Gram shape of
+ *   M_i = (C Ghat)_i, large angles from the cosine), Ct [R][r] fp64 (C transposed), info [72 + B] fp64: {iterations, status.done, last residual, m, 0,
+ *   0, 0, 0}, the m Ritz values (B times the mean cos^2) descending in 64 slots (the oversampled ones included), a degenerate flag per basis.  Sign: each row of C has
+ *   its entry of largest magnitude (the lowest index on a tie) positive.  With a caller's Ghat, X = Y = NULL: Y is not formed.  A row beyond the rank of
+ *   the stacked rows is zero, with weight 0.  finish leaves the block where it is.
+ * Status block: the first 32 bytes of scratch are {int32 done, int32 iterations, int32 0, int32 0, double res, double lambda_0}.
+ * Degenerate basis: the rule of dpb_subspace_angles; its blocks of Ghat are NaN, its flag is set, and NaN spreads to every output.
+ * Reproducibility: no atomics, every sum one fixed chain whose cut points depend on R and m only: bitwise the same run to run.
+ * Limits: 1 <= k <= 64, k <= N, 1 <= B <= 65535, B k <= 2^20, 1 <= r <= min(64, R, N), 0 <= max_iter <= 2^24.  Every call takes the same arguments
+ * and the same scratch: 256-byte aligned, dpb_flag_mean_scratch_bytes(B, k, N, r, max_iter) bytes (8 R^2 of them Ghat) -- with a caller's Ghat
+ * (32-byte aligned) dpb_flag_mean_solver_bytes(B, k, r, max_iter).  No device allocation, no host synchronisation.  Errors via dpb_last_error. */
+size_t dpb_flag_mean_scratch_bytes(int B, int k, int64_t N, int r, int max_iter);   /* 0 when invalid */
+size_t dpb_flag_mean_solver_bytes(int B, int k, int r, int max_iter);               /* 0 when invalid */
+int dpb_flag_mean_init(const float* X, const double* Ghat, int B, int k, int64_t N, int r, uint64_t seed, int max_iter, void* scratch,
+                       size_t scratch_bytes, void* hip_stream);
+int dpb_flag_mean_iterate(int n_iter, double tol, const double* Ghat, int B, int k, int64_t N, int r, int max_iter, void* scratch,
+                          size_t scratch_bytes, void* hip_stream);
+int dpb_flag_mean_finish(const float* X, const double* Ghat, float* Y, float* weight, float* theta, double* Ct, double* info, int B, int k, int64_t N,
+                         int r, int max_iter, void* scratch, size_t scratch_bytes, void* hip_stream);
+
 /* ---- Grassmann geodesics: principal vectors, log and exp maps (additive to ABI version 1; engine-independent) --------------------------
  * Pairs (A_d, B_d), d < D, of bases of k rows in R^N, fp32, rows independent but not necessarily orthonormal (ROWS convention).  a_stride = k N:
  * A [D][k][N]; a_stride = 0: one A [k][N] paired with every B_d.  Everything between input and output is fp64 (csrc/geodesic.hip).
