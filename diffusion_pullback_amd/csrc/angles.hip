@@ -156,6 +156,13 @@ int launch_cross_gram(const float* X, const float* Y, double* G, int Ra, int Rb,
   return 0;
 }
 
+// each basis's own Gram block: Dg[b] [k][k] = X_b X_b^T for the n bases of X [n][k][N], one batch entry per basis (the chains of launch_cross_gram: an
+// entry is a function of its two rows and N alone); also flagkmeans.hip
+int launch_self_gram_blocks(const float* X, double* Dg, int n, int k, long N, hipStream_t st) {
+  if (n < 1 || n > 65535 || k < 1 || N < 1) { set_error("self Gram blocks: n=%d outside [1,65535], k=%d or N=%ld below 1", n, k, N); return -1; }
+  return gram_launches(X, X, Dg, k, k, N, k, n, (long)k * N, (long)k * N, (long)k * k, 1, st);
+}
+
 // ------------------------------------------------------------------------------------------------------------ per basis: whitening
 constexpr double ANGLES_MIN_PIVOT = 1e-10;   // smallest Cholesky pivot (the diagonal entry before its square root) of the row-normalised Gram block
 

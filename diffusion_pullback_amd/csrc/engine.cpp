@@ -1675,6 +1675,49 @@ int dpb_flag_mean_finish(const float* X, const double* Ghat, float* Y, float* we
   return launch_flag_mean_finish(X, Ghat, B, k, N, r, max_iter, Y, weight, theta, Ct, info, scratch, scratch_bytes, (hipStream_t)stream);
 }
 
+// the chordal affinity of two stacks of subspaces, and flag k-means on it (geometry.flag_affinity / flag_kmeans): flagkmeans.hip
+size_t dpb_flag_affinity_scratch_bytes(int B, int k, int C, int r, int64_t N) { return flag_affinity_scratch_bytes(B, k, C, r, N); }
+
+int dpb_flag_affinity(const float* A, const float* Y, int B, int k, int C, int r, int64_t N, double* aff, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!A || !Y || !aff || !scratch) return fail("dpb_flag_affinity: null argument");
+  return launch_flag_affinity(A, Y, B, k, C, r, N, aff, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+size_t dpb_flag_kmeans_scratch_bytes(int B, int k, int64_t N, int C, int r) { return flag_kmeans_scratch_bytes(B, k, N, C, r); }
+size_t dpb_flag_kmeans_host_bytes(int B, int k, int64_t N, int C, int r) { return flag_kmeans_host_bytes(B, k, N, C, r); }
+
+const double* dpb_flag_kmeans_affinity(int B, int k, int64_t N, int C, int r, const void* scratch) {
+  const double* a = scratch ? flag_kmeans_affinity(B, k, N, C, r, scratch) : nullptr;
+  if (!a) set_error("dpb_flag_kmeans_affinity: null scratch, or B=%d, k=%d, N=%ld, C=%d, r=%d is no flag k-means problem", B, k, (long)N, C, r);
+  return a;
+}
+
+int dpb_flag_kmeans_init(const float* X, int B, int k, int64_t N, int C, int r, const int32_t* seeds, int n_seeds, void* scratch, size_t scratch_bytes,
+                         void* stream) {
+  if (!X || !seeds || !scratch) return fail("dpb_flag_kmeans_init: null argument");
+  return launch_flag_kmeans_init(X, B, k, N, C, r, seeds, n_seeds, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int dpb_flag_kmeans_gather(int c, int n_c, double* Gc, int B, int k, int64_t N, int C, int r, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!Gc || !scratch) return fail("dpb_flag_kmeans_gather: null argument");
+  return launch_flag_kmeans_gather(B, k, N, C, r, c, n_c, Gc, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int dpb_flag_kmeans_set_centre(int c, int n_c, const double* Ct, int B, int k, int64_t N, int C, int r, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!Ct || !scratch) return fail("dpb_flag_kmeans_set_centre: null argument");
+  return launch_flag_kmeans_set_centre(B, k, N, C, r, c, n_c, Ct, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int dpb_flag_kmeans_assign(int apply, int B, int k, int64_t N, int C, int r, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!scratch) return fail("dpb_flag_kmeans_assign: null argument");
+  return launch_flag_kmeans_assign(B, k, N, C, r, apply, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int dpb_flag_kmeans_finish(const float* X, float* Y, int B, int k, int64_t N, int C, int r, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!X || !Y || !scratch) return fail("dpb_flag_kmeans_finish: null argument");
+  return launch_flag_kmeans_finish(X, B, k, N, C, r, Y, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
 // The Hungarian-matched mean of local bases, the global basis of run_edit_global_hungarian_mean_zt (src/modules/edit.py:1249-1514): hungarian.hip
 size_t dpb_linear_assignment_scratch_bytes(int B, int k) { return linear_assignment_scratch_bytes(B, k); }
 

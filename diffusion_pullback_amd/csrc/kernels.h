@@ -396,6 +396,8 @@ int launch_subspace_angles(const float* A, const float* B, long Ba, long Bb, int
 void launch_angles_prep(double* Dg, int* flags, int n, int k, hipStream_t st);
 // block b < n of a stacked Gram into its own slot: dst[b][r][c] = G[(b rstep + r) ld + b k + c]   (rstep = k: diagonal blocks; 0: one basis against a stack)
 void launch_gram_blocks(const double* G, double* dst, int n, long ld, int rstep, int k, hipStream_t st);
+// each basis's own Gram block straight from the rows: Dg[b] [k][k] = X_b X_b^T, X [n][k][N], n <= 65535 (the chains of launch_cross_gram)
+int launch_self_gram_blocks(const float* X, double* Dg, int n, int k, long N, hipStream_t st);
 
 // ---------------------------------------------------------------- Frechet (Karcher) mean on the Grassmannian of B bases of k rows (frechet.hip): the
 // Riemannian iteration on coefficients against the whitened Gram of all rows; X [B][k][N] fp32, everything between in fp64; see include/dpb.h
@@ -424,6 +426,21 @@ int launch_flag_mean_iterate(const double* ghat, long B, int k, long N, int r, l
                              hipStream_t st);
 int launch_flag_mean_finish(const float* X, const double* ghat, long B, int k, long N, int r, long max_iter, float* Y, float* weight, float* theta, double* Ct,
                             double* info, void* scratch, size_t scratch_bytes, hipStream_t st);
+
+// ---------------------------------------------------------------- flag k-means and the chordal affinity of two stacks (flagkmeans.hip): Lloyd's
+// algorithm with flag-mean centres on coefficients against the whitened Gram; the caller owns the rounds and runs the flag-mean solver per cluster
+size_t flag_affinity_scratch_bytes(long Ba, int k, long Bc, int r, long N);   // 0 when invalid
+int launch_flag_affinity(const float* A, const float* Y, long Ba, int k, long Bc, int r, long N, double* aff, void* scratch, size_t scratch_bytes,
+                         hipStream_t st);
+size_t flag_kmeans_scratch_bytes(long B, int k, long N, long C, int r);       // 0 when invalid
+size_t flag_kmeans_host_bytes(long B, int k, long N, long C, int r);          // the leading part of the block the caller reads; 0 when invalid
+const double* flag_kmeans_affinity(long B, int k, long N, long C, int r, const void* scratch);   // a [B][C] inside the block; nullptr when invalid
+int launch_flag_kmeans_init(const float* X, long B, int k, long N, long C, int r, const int32_t* seeds, int n_seeds, void* scratch, size_t scratch_bytes,
+                            hipStream_t st);
+int launch_flag_kmeans_gather(long B, int k, long N, long C, int r, int c, int n_c, double* Gc, void* scratch, size_t scratch_bytes, hipStream_t st);
+int launch_flag_kmeans_set_centre(long B, int k, long N, long C, int r, int c, int n_c, const double* Ct, void* scratch, size_t scratch_bytes, hipStream_t st);
+int launch_flag_kmeans_assign(long B, int k, long N, long C, int r, int apply, void* scratch, size_t scratch_bytes, hipStream_t st);
+int launch_flag_kmeans_finish(const float* X, long B, int k, long N, long C, int r, float* Y, void* scratch, size_t scratch_bytes, hipStream_t st);
 
 // ---------------------------------------------------------------- the Hungarian-matched mean of B bases of k rows (hungarian.hip): a batched
 // linear-assignment solver (shortest augmenting paths in LDS, one workgroup per problem) and a streaming mean of permuted, signed rows; see include/dpb.h

@@ -201,6 +201,45 @@ class _EditBase(object):
         save_distance_plot(out["dist"], os.path.join(save_dir, self.EXP_NAME + ".png"), dpi=80)
         return out
 
+    @torch.no_grad()
+    def run_tangent_space_clusters(self, h_t, op, block_idx, pca_rank=50, num_local_basis=10, space="x", num_clusters=2, cluster_rank=None,
+                                   max_bytes=None, **naming):
+        """Flag k-means of the local tangent spaces run_sample_encoder_local_tangent_space_zt saved: the (basis index, h_t) pairs clustered into
+        num_clusters families, each with a rank-cluster_rank (None: pca_rank) flag mean as its centre (geometry.flag_kmeans) -- where every other
+        consumer of many bases assumes one global basis for the whole set.  The files are listed, named and refused as run_tangent_space_distance
+        does (a missing one raises ValueError naming it; nothing is sampled); space "x": the row spans of vT, "h": the column spans of u.  Writes
+        tangent_space_clusters-<space>-C<C>-r<r>-<EXP_NAME of the set>.pt -- a dict of names, idx, h_t, labels [P], centres [C, r, N], affinity
+        [P, C], objective, weight [C, r], gap, sizes, converged -- and a heat map of r - affinity, rows sorted by label, as .png next to it; prints
+        every cluster's size and its spectrum around row r, so that a missing gap is seen.  Returns the dict."""
+        from . import geometry
+        if space not in ("x", "h"):
+            raise ValueError(f"space must be 'x' (vT) or 'h' (u), got {space!r}")
+        save_dir, exp_name = self._tangent_space_naming(op, block_idx, pca_rank, **naming)
+        pairs = self._tangent_space_pairs(h_t, num_local_basis, save_dir, exp_name)
+        files = [paths[2] if space == "x" else paths[0] for _, _, _, paths in pairs]
+        missing = [os.path.basename(f) for f in files if not os.path.exists(f)]
+        if missing:
+            raise ValueError(f"{len(missing)} of {len(files)} tangent-space files are missing in {save_dir}: {missing}; run the sampling job "
+                             "(run_sample_encoder_local_tangent_space_zt) with the same arguments first")
+        r = int(cluster_rank) if cluster_rank else int(pca_rank)
+        with T.phase("tangent-space clusters (flag k-means)"):
+            bases = [torch.load(f, map_location=self.device).float() for f in files]
+            stack = torch.stack([b if space == "x" else b.T for b in bases]).contiguous()
+            labels, centres, info = geometry.flag_kmeans(stack, int(num_clusters), rank=r, max_bytes=max_bytes)
+        hts = list(h_t) if isinstance(h_t, (list, tuple)) else [h_t]
+        self.EXP_NAME = f"tangent_space_clusters-{space}-C{int(num_clusters)}-r{r}-" + exp_name(f"0to{num_local_basis - 1}", ",".join(str(h) for h in hts))
+        out = dict(names=[name for _, _, name, _ in pairs], idx=[int(i) for i, _, _, _ in pairs], h_t=[float(h) for _, h, _, _ in pairs],
+                   labels=labels.cpu(), centres=centres.cpu(), affinity=info["affinity"].cpu(), objective=torch.as_tensor(info["objective"]),
+                   weight=info["weight"].cpu(), gap=info["gap"], sizes=torch.as_tensor(info["sizes"]), converged=info["converged"])
+        for c, eig in enumerate(info["eigenvalues"]):
+            lo, hi = max(0, r - 3), min(len(eig), r + 3)
+            around = " ".join(f"{v:.3f}" for v in eig[lo:r]) + " | " + " ".join(f"{v:.3f}" for v in eig[r:hi])
+            print(f"cluster {c}: {int(info['sizes'][c])} members, spectrum rows {lo}..{hi - 1} (| after row {r}): {around}, gap {info['gap'][c]}")
+        torch.save(out, os.path.join(save_dir, self.EXP_NAME + ".pt"))
+        order = torch.argsort(out["labels"], stable=True)
+        save_distance_plot((r - out["affinity"])[order], os.path.join(save_dir, self.EXP_NAME + ".png"), dpi=80)
+        return out
+
     def _guidance_chains_together(self, z, vk, t, emb=None):
         """n independent chains of x-space guidance (edit.py:484-502, :1716-1734) advanced together: chain i starts at z[i] and moves along vk[i],
         all at the timestep t.  Per step ONE U-Net call of 2 n rows, [z_1..z_n | z_1 + s v_1 .. z_n + s v_n], split only by the engine's batch limit

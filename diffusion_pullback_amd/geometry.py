@@ -13,6 +13,10 @@ expressed in a target's basis and carried to the target's x-space, fp64 on the h
 the top eigenvectors of the mean projector, by block subspace iteration on the same whitened fp64 Gram; closed form, any rank, nested, and its
 spectrum says how many directions the local spaces share.
 
+``flag_affinity`` is the chordal affinity sum_j cos^2 theta_j = ||Q_Y Q_A^T||_F^2 between subspaces of different rank, and ``flag_kmeans`` clusters many
+bases into several families, each with a flag mean as its centre -- Lloyd's algorithm on that affinity (``csrc/flagkmeans.hip``), the analysis of
+``run_tangent_space_clusters``: on the same whitened Gram, the flag-mean solver per cluster, one pass over the Gram per round for all clusters.
+
 ``frechet_mean`` is the Frechet (Karcher) mean on the Grassmannian of many such bases -- the global basis of ``run_edit_global_frechet_mean_zt``
 (``csrc/frechet.hip``): the Riemannian fixed-step iteration on coefficients against the whitened fp64 Gram of all rows, one streaming pass over the
 rows before it and one after it.
@@ -31,6 +35,7 @@ There is no CPU fallback: inputs live on a HIP device.
 from __future__ import annotations
 
 import ctypes as C
+import time
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -613,3 +618,257 @@ def subspace_angles(A: torch.Tensor, B: Optional[torch.Tensor] = None, max_bytes
 def geodesic_distance(A: torch.Tensor, B: Optional[torch.Tensor] = None, max_bytes: Optional[int] = None) -> torch.Tensor:
     """Geodesic distance on the Grassmannian, dist [Ba, Bb] = ||theta||_2 over the principal angles of each pair.  See subspace_angles_and_distance."""
     return subspace_angles_and_distance(A, B, max_bytes)[1]
+
+
+def _affinity_block(lib, b: int, c: int, k: int, r: int, n: int, max_bytes: int) -> int:
+    """members per block of flag_affinity: the largest m whose call -- min(m, B) x min(m, C) -- keeps its scratch within max_bytes (at least 1)"""
+    need = lambda m: int(lib.dpb_flag_affinity_scratch_bytes(min(m, b), k, min(m, c), r, n))
+    lo, hi = 1, max(b, c)
+    if need(hi) <= max_bytes:
+        return hi
+    while lo < hi:                                     # need() grows with m
+        mid = (lo + hi + 1) // 2
+        if need(mid) <= max_bytes:
+            lo = mid
+        else:
+            hi = mid - 1
+    return lo
+
+
+def flag_affinity(A: torch.Tensor, Y: torch.Tensor, max_bytes: Optional[int] = None, check: bool = True) -> torch.Tensor:
+    """The chordal affinity aff [B, C] (float64, on the device) between every basis of A [B, k, N] and every basis of Y [C, r, N], r smaller or larger
+    than k: aff[i, c] = sum_j cos^2 theta_j(A_i, Y_c) = ||Q_Y Q_A^T||_F^2 in [0, min(r, k)] -- how much of a rank-r basis a rank-k one holds, where
+    subspace_angles refuses unequal ranks; r - aff is the squared chordal distance flag_kmeans minimises (dpb_flag_affinity; include/dpb.h).  A [k, N]
+    or [r, N] tensor is one basis; rows need not be orthonormal, only independent; any float dtype is converted to contiguous fp32; k, r <= 64.
+
+    Entry (i, c) is bitwise a function of A_i, Y_c and N alone: the same alone, in any stack, and through the blocks of members a stack goes through
+    when one call's scratch would exceed max_bytes.  check: raise ValueError naming the degenerate bases (a NaN row for one of A, a NaN column for
+    one of Y; one host sync); False returns the NaNs and does not synchronise."""
+    lib = L.load()
+    A = _stack(A, "A")
+    Y = _stack(Y, "Y").to(A.device)
+    b, k, n = A.shape
+    c, r = Y.shape[0], Y.shape[1]
+    if Y.shape[2] != n:
+        raise ValueError(f"A holds rows of length N = {n}, Y of N = {Y.shape[2]}: they must match")
+    if k > FLAG_MEAN_MAX_RANK or r > FLAG_MEAN_MAX_RANK:
+        raise ValueError(f"k = {k} or r = {r} rows per basis exceeds the rank {FLAG_MEAN_MAX_RANK} the affinity supports")
+    if max(k, r) > n:
+        raise ValueError(f"k = {k} or r = {r} rows per basis exceeds their length N = {n}: they cannot be independent")
+    max_bytes = DEFAULT_MAX_BYTES if max_bytes is None else int(max_bytes)
+    with torch.cuda.device(A.device):
+        st = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
+        blk = _affinity_block(lib, b, c, k, r, n, max_bytes)
+        need = int(lib.dpb_flag_affinity_scratch_bytes(min(blk, b), k, min(blk, c), r, n))
+        if need == 0:
+            raise L.DpbError(f"dpb_flag_affinity does not take B = {b}, k = {k}, C = {c}, r = {r}, N = {n}")
+        scratch = torch.empty(need, dtype=torch.uint8, device=A.device)
+        aff = torch.empty(b, c, dtype=torch.float64, device=A.device)
+        if blk >= max(b, c):
+            L.check(lib.dpb_flag_affinity(A.data_ptr(), Y.data_ptr(), b, k, c, r, n, aff.data_ptr(), scratch.data_ptr(), need, st))
+        else:
+            for i0 in range(0, b, blk):
+                i1 = min(i0 + blk, b)
+                for j0 in range(0, c, blk):
+                    j1 = min(j0 + blk, c)
+                    part = torch.empty(i1 - i0, j1 - j0, dtype=torch.float64, device=A.device)
+                    L.check(lib.dpb_flag_affinity(A[i0:i1].data_ptr(), Y[j0:j1].data_ptr(), i1 - i0, k, j1 - j0, r, n, part.data_ptr(),
+                                                  scratch.data_ptr(), need, st))
+                    aff[i0:i1, j0:j1] = part
+    if check:
+        bad = torch.isnan(aff)
+        if bool(bad.any()):
+            rows = bad.all(dim=1).nonzero().flatten().tolist()
+            cols = bad.all(dim=0).nonzero().flatten().tolist()
+            raise ValueError(f"{DEGENERATE}: indices {rows} of A, {cols} of Y")
+    return aff
+
+
+def _kmeans_state(scratch: torch.Tensor, host_bytes: int, b: int, c: int) -> dict:
+    """the host part of a dpb_flag_kmeans_* block (include/dpb.h): one device read"""
+    raw = scratch[:host_bytes].cpu().numpy()
+    head = raw[:16].view(np.int32)
+    ints = raw[32:].view(np.int32)
+    return {"moved": int(head[0]), "kept": int(head[1]), "J": float(raw[16:24].view(np.float64)[0]), "sizes": ints[:c].copy(),
+            "changed": ints[c:2 * c].copy(), "seeds": ints[2 * c:3 * c].copy(), "labels": ints[3 * c:3 * c + b].copy(),
+            "flags": ints[3 * c + b:3 * c + 2 * b].copy()}
+
+
+def flag_kmeans(A: torch.Tensor, n_clusters: int, rank: Optional[int] = None, init=0, max_rounds: int = 50, inner_iter: int = 200, tol: float = 1e-12,
+                check_every: int = 16, seed: int = 0, max_bytes: Optional[int] = None, check: bool = True,
+                history: bool = False, timings: bool = False) -> Tuple[torch.Tensor, torch.Tensor, dict]:
+    """Flag k-means: the row spans of A [B, k, N] clustered into n_clusters = C families, each with a rank-``rank`` (None: k) flag mean as its centre --
+    Lloyd's algorithm with r - flag_affinity as the distance.  The rank-r flag mean of a cluster maximises the summed affinity of its members, so the
+    objective J = sum_i (r - a[i, label_i]) cannot rise (dpb_flag_kmeans_*; see include/dpb.h for the method and the limits).  k <= 64, 1 <= C <= B,
+    1 <= rank <= k; rows need not be orthonormal, only independent; any float dtype is converted to contiguous fp32.
+
+    Seeds: ``init`` is a member index -- each further seed is then the member whose smallest chordal distance^2 to the seeds so far is largest, the lowest
+    index on a tie -- or a sequence of C distinct member indices.  Every member starts at its nearest seed.  A round fits every cluster's centre (flag_mean's
+    solver on the cluster's part of the whitened Gram, at most inner_iter iterations to tol in chunks of check_every; a cluster whose member set did
+    not change is not solved again), computes every member's affinity to every centre in one pass over the Gram, and moves member i to argmax_c a[i, c]
+    (lowest c on a tie) if that exceeds its own by more than 1e-12 r; a cluster all of whose members want to leave keeps the one it holds best.  The
+    run stops when no label changed or after max_rounds rounds; the centres and affinities of the final labels are always computed (max_rounds = 0
+    labels by the seeds and fits once).  At the end the clusters are renumbered by their lowest member index.
+
+    Returns labels [B] (int32, on the device), Y [C, rank, N] (fp32, orthonormal rows per centre in descending eigenvalue order) and info: ``rounds``,
+    ``converged``, ``objective`` (fp64 numpy, one entry per fit, the start included), ``monotone`` (no entry rose by more than 1e-12 relative plus
+    1e-15 B r), ``moved`` (per round), ``kept`` (how often the keep rule acted), ``sizes`` [C], ``weight`` [C, rank] (fp32: the mean cos^2 within the
+    cluster), ``eigenvalues`` (per cluster: all Ritz values of its block), ``gap`` [C] (after row rank, or None), ``inner_iterations`` and
+    ``inner_converged`` [C] (of each centre's last fit), ``affinity`` [B, C] (float64, on the device), ``seeds``, ``start`` (the start labels) and
+    ``degenerate``; history=True adds ``history``: the labels after every round that moved a member, in the run's own numbering (cluster c grew from
+    seed c); timings=True adds ``timings``: wall-clock ms of init, of every fit's update and assignment (the host read included) and of finish, with a
+    device synchronisation at each boundary (a measuring aid: it adds host waits).  An inner solve or a run that does not converge, and monotone = False (which can follow from the former), are reported, not raised.
+    check: raise ValueError naming the degenerate members; False gives them label -1 and NaN affinities and clusters the others.  One host read per
+    round (and one per chunk of the inner solves).  Bitwise reproducible."""
+    lib = L.load()
+    A = _stack(A, "A")
+    b, k, n = A.shape
+    if k > FRECHET_MAX_RANK:
+        raise ValueError(f"k = {k} rows per basis exceeds the rank {FRECHET_MAX_RANK} flag k-means supports")
+    if k > n:
+        raise ValueError(f"k = {k} rows per basis exceeds their length N = {n}: they cannot be independent")
+    nc = int(n_clusters)
+    if not 1 <= nc <= b:
+        raise ValueError(f"n_clusters = {nc} outside [1, B = {b}]")
+    r = k if rank is None else int(rank)
+    if not 1 <= r <= k:
+        raise ValueError(f"rank = {r} outside [1, k = {k}]")
+    if isinstance(init, (int, np.integer)):
+        seeds = [int(init)]
+        if not 0 <= seeds[0] < b:
+            raise ValueError(f"init = {seeds[0]} outside [0, B = {b})")
+    else:
+        seeds = [int(s) for s in init]
+        if len(seeds) != nc or len(set(seeds)) != nc or any(s < 0 or s >= b for s in seeds):
+            raise ValueError(f"init must be a member index or {nc} distinct member indices in [0, {b}), got {seeds}")
+    max_rounds, inner_iter, check_every, seed = int(max_rounds), int(inner_iter), int(check_every), int(seed)
+    if max_rounds < 0 or inner_iter < 0 or check_every < 1 or not tol >= 0 or seed < 0:
+        raise ValueError(f"max_rounds = {max_rounds} and inner_iter = {inner_iter} must be >= 0, check_every = {check_every} >= 1, tol = {tol} >= 0 and "
+                         f"seed = {seed} >= 0")
+    max_bytes = DEFAULT_MAX_BYTES if max_bytes is None else int(max_bytes)
+    need = int(lib.dpb_flag_kmeans_scratch_bytes(b, k, n, nc, r))
+    host_bytes = int(lib.dpb_flag_kmeans_host_bytes(b, k, n, nc, r))
+    if need == 0:
+        raise L.DpbError(f"dpb_flag_kmeans does not take B = {b}, k = {k}, N = {n}, C = {nc}, r = {r}")
+    if need > max_bytes:
+        raise ValueError(f"flag k-means of B = {b} bases of k = {k} rows needs {need} bytes of device scratch (the fp64 Gram of all {b * k} rows), "
+                         f"max_bytes is {max_bytes}")
+    fits = {}                                            # cluster -> its last fit: (weight, info_d, members)
+    with torch.cuda.device(A.device):
+        st = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
+        dev = A.device
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        times = {"init_ms": 0.0, "update_ms": [], "assign_ms": [], "finish_ms": 0.0}
+
+        def lap(t0=None):
+            if not timings:
+                return 0.0
+            torch.cuda.synchronize(dev)
+            now = time.perf_counter()
+            return now if t0 is None else (now - t0) * 1e3
+        t0 = lap()
+        L.check(lib.dpb_flag_kmeans_init(A.data_ptr(), b, k, n, nc, r, (C.c_int32 * len(seeds))(*seeds), len(seeds), scratch.data_ptr(), need, st))
+        state = _kmeans_state(scratch, host_bytes, b, nc)
+        times["init_ms"] = lap(t0)
+        degenerate = np.nonzero(state["flags"] != 0)[0].tolist()
+        if check and degenerate:
+            raise ValueError(f"{DEGENERATE}: indices {degenerate}")
+        if degenerate and (set(degenerate) & set(state["seeds"].tolist()) or nc > b - len(degenerate)):
+            raise ValueError(f"{DEGENERATE}: indices {degenerate} leave no {nc} usable seeds (seeds {state['seeds'].tolist()})")
+        start = state["labels"].copy()
+
+        def fit(clusters, sizes):
+            jobs, extra = [], 0
+            for c in clusters:
+                m = int(sizes[c])
+                fneed = int(lib.dpb_flag_mean_solver_bytes(m, k, r, inner_iter))
+                if fneed == 0:
+                    raise L.DpbError(f"dpb_flag_mean does not take B = {m}, k = {k}, r = {r}, max_iter = {inner_iter} on a cluster's Gram")
+                extra += fneed + 8 * (m * k) ** 2
+                if need + extra > max_bytes:
+                    raise ValueError(f"the centres of flag k-means need {extra} more bytes of device scratch (the clusters' parts of the Gram), "
+                                     f"max_bytes is {max_bytes}")
+                gc = torch.empty((m * k) ** 2, dtype=torch.float64, device=dev)
+                fs = torch.empty(fneed, dtype=torch.uint8, device=dev)
+                L.check(lib.dpb_flag_kmeans_gather(c, m, gc.data_ptr(), b, k, n, nc, r, scratch.data_ptr(), need, st))
+                L.check(lib.dpb_flag_mean_init(None, gc.data_ptr(), m, k, n, r, seed, inner_iter, fs.data_ptr(), fneed, st))
+                jobs.append((c, m, gc, fs, fneed))
+            asked, active = 0, jobs
+            while asked < inner_iter and active:
+                steps = min(check_every, inner_iter - asked)
+                for c, m, gc, fs, fneed in active:
+                    L.check(lib.dpb_flag_mean_iterate(steps, float(tol), gc.data_ptr(), m, k, n, r, inner_iter, fs.data_ptr(), fneed, st))
+                asked += steps
+                done = torch.stack([j[3][:4].view(torch.int32) for j in active]).flatten().tolist()      # the one host read of the chunk
+                active = [j for j, d in zip(active, done) if d == 0]
+            for c, m, gc, fs, fneed in jobs:
+                weight = torch.empty(r, dtype=torch.float32, device=dev)
+                theta = torch.empty(m, r, dtype=torch.float32, device=dev)
+                ct = torch.empty(m * k, r, dtype=torch.float64, device=dev)
+                info_d = torch.empty(72 + m, dtype=torch.float64, device=dev)
+                L.check(lib.dpb_flag_mean_finish(None, gc.data_ptr(), None, weight.data_ptr(), theta.data_ptr(), ct.data_ptr(), info_d.data_ptr(), m, k, n,
+                                                 r, inner_iter, fs.data_ptr(), fneed, st))
+                L.check(lib.dpb_flag_kmeans_set_centre(c, m, ct.data_ptr(), b, k, n, nc, r, scratch.data_ptr(), need, st))
+                fits[c] = (weight, info_d, m)
+
+        objective, moved, hist, kept, rounds, converged = [], [], [], 0, 0, False
+        while True:
+            t0 = lap()
+            fit([c for c in range(nc) if state["changed"][c]], state["sizes"])
+            times["update_ms"].append(lap(t0))
+            t0 = lap()
+            apply = rounds < max_rounds
+            L.check(lib.dpb_flag_kmeans_assign(1 if apply else 0, b, k, n, nc, r, scratch.data_ptr(), need, st))
+            state = _kmeans_state(scratch, host_bytes, b, nc)                                            # the one host read of the round
+            times["assign_ms"].append(lap(t0))
+            objective.append(state["J"])
+            if not apply:
+                break
+            rounds += 1
+            moved.append(state["moved"])
+            kept += state["kept"]
+            if state["moved"] == 0:
+                converged = True
+                break
+            hist.append(state["labels"].copy())
+        t0 = lap()
+        Y = torch.empty(nc, r, n, dtype=torch.float32, device=dev)
+        L.check(lib.dpb_flag_kmeans_finish(A.data_ptr(), Y.data_ptr(), b, k, n, nc, r, scratch.data_ptr(), need, st))
+        times["finish_ms"] = lap(t0)
+        off = int(lib.dpb_flag_kmeans_affinity(b, k, n, nc, r, scratch.data_ptr())) - scratch.data_ptr()
+        aff = scratch[off:off + 8 * b * nc].view(torch.float64).view(b, nc).clone()
+        raws = torch.cat([fits[c][1] for c in range(nc)]).cpu().numpy()
+        # the clusters renumbered by their lowest member index
+        labels_h = state["labels"]
+        first = {}
+        for i, c in enumerate(labels_h.tolist()):
+            if c >= 0:
+                first.setdefault(c, i)
+        perm = sorted(first, key=first.get)
+        inv = np.full(nc + 1, -1, dtype=np.int32)
+        inv[perm] = np.arange(nc, dtype=np.int32)
+        labels = torch.from_numpy(inv[labels_h]).to(dev)                                                  # (label -1 reads the last slot: -1)
+        pidx = torch.tensor(perm, dtype=torch.long, device=dev)
+        Y, aff = Y[pidx].contiguous(), aff[:, pidx].contiguous()
+        weight = torch.stack([fits[c][0] for c in perm])
+    eig, gap, inner_it, inner_ok, o = {}, {}, {}, {}, 0
+    for c in range(nc):
+        m = fits[c][2]
+        raw = raws[o:o + 72 + m]
+        o += 72 + m
+        w = int(raw[3])
+        eig[c] = raw[8:8 + w] / m
+        gap[c] = float(eig[c][r - 1] - eig[c][r]) if w > r else None
+        inner_it[c], inner_ok[c] = int(raw[0]), int(raw[1]) == 1
+    objective = np.array(objective, dtype=np.float64)
+    rise = objective[1:] - objective[:-1]
+    info = {"rounds": rounds, "converged": converged, "objective": objective,
+            "monotone": bool(np.all(rise <= 1e-12 * np.abs(objective[:-1]) + 1e-15 * b * r)), "moved": moved, "kept": kept,
+            "sizes": np.array([int(state["sizes"][c]) for c in perm]), "weight": weight, "eigenvalues": [eig[c] for c in perm],
+            "gap": [gap[c] for c in perm], "inner_iterations": [inner_it[c] for c in perm], "inner_converged": [inner_ok[c] for c in perm],
+            "affinity": aff, "seeds": [int(state["seeds"][c]) for c in perm], "start": start, "degenerate": degenerate}
+    if history:
+        info["history"] = hist
+    if timings:
+        info["timings"] = times
+    return labels, Y, info

@@ -118,6 +118,17 @@ SYMBOLS = {
     "dpb_flag_mean_init": (_I, [_P, _P, _I, _I, _L, _I, C.c_uint64, _I, _P, C.c_size_t, _P]),
     "dpb_flag_mean_iterate": (_I, [_I, C.c_double, _P, _I, _I, _L, _I, _I, _P, C.c_size_t, _P]),
     "dpb_flag_mean_finish": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _P, C.c_size_t, _P]),
+    # chordal affinity of two stacks and flag k-means (geometry.flag_affinity / flag_kmeans): seeds is a host int32 array; the caller owns the rounds
+    "dpb_flag_affinity_scratch_bytes": (C.c_size_t, [_I, _I, _I, _I, _L]),
+    "dpb_flag_affinity": (_I, [_P, _P, _I, _I, _I, _I, _L, _P, _P, C.c_size_t, _P]),
+    "dpb_flag_kmeans_scratch_bytes": (C.c_size_t, [_I, _I, _L, _I, _I]),
+    "dpb_flag_kmeans_host_bytes": (C.c_size_t, [_I, _I, _L, _I, _I]),
+    "dpb_flag_kmeans_affinity": (_P, [_I, _I, _L, _I, _I, _P]),
+    "dpb_flag_kmeans_init": (_I, [_P, _I, _I, _L, _I, _I, C.POINTER(C.c_int32), _I, _P, C.c_size_t, _P]),
+    "dpb_flag_kmeans_gather": (_I, [_I, _I, _P, _I, _I, _L, _I, _I, _P, C.c_size_t, _P]),
+    "dpb_flag_kmeans_set_centre": (_I, [_I, _I, _P, _I, _I, _L, _I, _I, _P, C.c_size_t, _P]),
+    "dpb_flag_kmeans_assign": (_I, [_I, _I, _I, _L, _I, _I, _P, C.c_size_t, _P]),
+    "dpb_flag_kmeans_finish": (_I, [_P, _P, _I, _I, _L, _I, _I, _P, C.c_size_t, _P]),
     # Grassmann geodesics (geometry.principal_vectors / grassmann_log / grassmann_geodesic / grassmann_exp): ts is a host double array
     "dpb_grassmann_scratch_bytes": (C.c_size_t, [_I, _I, _I, _L]),
     "dpb_grassmann_pair": (_I, [_P, _L, _P, _I, _I, _L, _I, C.POINTER(C.c_double), _I, _P, _P, _P, _P, _P, C.c_size_t, _P]),

@@ -363,6 +363,58 @@ int dpb_flag_mean_iterate(int n_iter, double tol, const double* Ghat, int B, int
 int dpb_flag_mean_finish(const float* X, const double* Ghat, float* Y, float* weight, float* theta, double* Ct, double* info, int B, int k, int64_t N,
                          int r, int max_iter, void* scratch, size_t scratch_bytes, void* hip_stream);
 
+/* ---- Chordal affinity of subspaces of unequal rank, and flag k-means (additive to ABI version 1; engine-independent) ---------------------
+ * a(A, Y) = sum_j cos^2 theta_j(A, Y) = ||Q_Y Q_A^T||_F^2 in [0, min(r, k)] between a k-dimensional and an r-dimensional subspace of R^N (csrc/flagkmeans.hip).
+ *
+ * dpb_flag_affinity: A [B][k][N], Y [C][r][N] fp32, rows independent but not necessarily orthonormal; aff [B][C] fp64 on the device,
+ *   aff[i][c] = ||W_i (A_i Y_c^T) W'_c^T||_F^2 with W, W' the whitenings of dpb_subspace_angles of each basis's own Gram block: the exact cross-Gram of
+ *   dpb_cross_gram, then one workgroup per pair, every element a sequential fp64 sum and the squares added in a fixed order.  Entry (i, c) is bitwise a
+ *   function of A_i, Y_c and N alone: the same alone and in any stack.  A degenerate A_i (the rule of dpb_subspace_angles) gives NaN in its row, a
+ *   degenerate Y_c in its column.  Limits: 1 <= k, r <= 64, max(k, r) <= N, 1 <= B, C <= 65535.  scratch: 256-byte aligned,
+ *   dpb_flag_affinity_scratch_bytes(B, k, C, r, N) bytes (8 B k C r of them the cross-Gram).
+ *
+ * dpb_flag_kmeans_*: Lloyd's algorithm with rank-r flag means (dpb_flag_mean_*) as centres and r - a as the distance, on coefficients against the
+ *   whitened Gram Ghat [R][R] of all R = B k rows; X [B][k][N] fp32 as for dpb_flag_mean_*, 1 <= C <= B clusters, 1 <= r <= k.  The rank-r flag mean of a
+ *   cluster maximises the summed affinity of its members, so neither refitting the centres nor moving a member to the centre it holds best can raise
+ *   J = sum_i (r - a[i][label_i]).  The CALLER owns the rounds and runs the flag-mean solver per cluster (geometry.flag_kmeans is the loop):
+ *   init: Ghat (dpb_frechet_init's code), the seeds and the start labels.  seeds: a HOST list; n_seeds = C gives them all (distinct members), n_seeds = 1
+ *     gives seed 0 and each further seed is the member whose smallest D^2(i, s) = k - ||Ghat_is||_F^2 to the seeds so far is largest, the lowest index
+ *     on a tie, picked on the device.  Every member takes the nearest seed by D^2, the lowest cluster on a tie; a seed takes its own cluster.
+ *   gather: Gc [n_c k][n_c k] = Ghat[I_c][I_c], the members of cluster c ascending, contiguous (32-byte aligned): what dpb_flag_mean_init / _iterate /
+ *     _finish take as a caller's Ghat with B = n_c.  n_c must be the cluster's size as the block states it (otherwise nothing is written).
+ *   set_centre: files Ct_c [n_c k][r] of dpb_flag_mean_finish (Y_c = Ct_c^T Q[I_c], Ct_c^T Gc Ct_c = I) under its members' rows of Z [R][r].
+ *   assign: S[:, c-block] = sum_{j in c} Ghat[:, j-block] Z[j-rows] = Q Y_c^T for every cluster in ONE pass over Ghat on the fp64 matrix cores (a
+ *     workgroup per 32 rows and cluster; column block j meets the coefficients of j's own cluster only: 2 R^2 r flops), a[i][c] = ||S[i-rows, c-block]||_F^2,
+ *     J, and with apply != 0 the moves: member i goes to argmax_c a[i][c] (lowest c on a tie) if that exceeds a[i][label_i] by more than 1e-12 r; a
+ *     cluster none of whose members wants to stay keeps the one of largest affinity to it (lowest index on a tie), so a cluster never empties; then
+ *     the new labels, sizes, member lists and the clusters whose member set changed.  apply = 0: a and J of the labels as they stand.
+ *   finish: Y [C][r][N] fp32 from the coefficients on the rows as given (Z blockdiag(W), zero outside a centre's members) by the streaming pass of
+ *     dpb_flag_mean_finish: one pass over X when C r <= 64, otherwise one per cluster.
+ * Host part: the first dpb_flag_kmeans_host_bytes(...) bytes of scratch are {int32 moved, int32 kept, int32 degenerate members, int32 0, double J,
+ *   double 0}, then int32 sizes [C], changed [C], seeds [C], labels [B] (-1: degenerate) and degenerate flags [B]: the caller's one read per round.
+ *   dpb_flag_kmeans_affinity: the device address of a [B][C] fp64 inside the block (host arithmetic only; NULL with the error set when invalid).
+ * Degenerate member (the rule of dpb_subspace_angles): its flag is set, its label is -1, it joins no cluster and no sum, its row of a is NaN.
+ * Reproducibility: fp64, no atomics, every sum one fixed chain; the reduction range of the assignment pass is cut among the waves of a workgroup at
+ *   bounds that depend on the member list only and the partial tiles are added in wave order: bitwise the same run to run.
+ * Limits: 1 <= k <= 64, k <= N, 1 <= B <= 65535, B k <= 2^20, 1 <= C <= B, 1 <= r <= k.  Every call takes the same B, k, N, C, r and the same scratch:
+ *   256-byte aligned, dpb_flag_kmeans_scratch_bytes(B, k, N, C, r) bytes (8 R^2 of them Ghat, 8 R C r the products S).  init synchronises the stream
+ *   once (the seeds' copy); nothing else synchronises or allocates.  Errors via dpb_last_error. */
+size_t dpb_flag_affinity_scratch_bytes(int B, int k, int C, int r, int64_t N);   /* 0 when invalid */
+int dpb_flag_affinity(const float* A, const float* Y, int B, int k, int C, int r, int64_t N, double* aff /*[B][C]*/, void* scratch, size_t scratch_bytes,
+                      void* hip_stream);
+size_t dpb_flag_kmeans_scratch_bytes(int B, int k, int64_t N, int C, int r);     /* 0 when invalid */
+size_t dpb_flag_kmeans_host_bytes(int B, int k, int64_t N, int C, int r);        /* 0 when invalid */
+const double* dpb_flag_kmeans_affinity(int B, int k, int64_t N, int C, int r, const void* scratch);
+int dpb_flag_kmeans_init(const float* X, int B, int k, int64_t N, int C, int r, const int32_t* seeds /*host [n_seeds]*/, int n_seeds, void* scratch,
+                         size_t scratch_bytes, void* hip_stream);
+int dpb_flag_kmeans_gather(int c, int n_c, double* Gc /*[n_c k][n_c k]*/, int B, int k, int64_t N, int C, int r, void* scratch, size_t scratch_bytes,
+                           void* hip_stream);
+int dpb_flag_kmeans_set_centre(int c, int n_c, const double* Ct /*[n_c k][r]*/, int B, int k, int64_t N, int C, int r, void* scratch,
+                               size_t scratch_bytes, void* hip_stream);
+int dpb_flag_kmeans_assign(int apply, int B, int k, int64_t N, int C, int r, void* scratch, size_t scratch_bytes, void* hip_stream);
+int dpb_flag_kmeans_finish(const float* X, float* Y /*[C][r][N]*/, int B, int k, int64_t N, int C, int r, void* scratch, size_t scratch_bytes,
+                           void* hip_stream);
+
 /* ---- Grassmann geodesics: principal vectors, log and exp maps (additive to ABI version 1; engine-independent) --------------------------
  * Pairs (A_d, B_d), d < D, of bases of k rows in R^N, fp32, rows independent but not necessarily orthonormal (ROWS convention).  a_stride = k N:
  * A [D][k][N]; a_stride = 0: one A [k][N] paired with every B_d.  Everything between input and output is fp64 (csrc/geodesic.hip).
