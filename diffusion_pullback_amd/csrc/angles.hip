@@ -303,9 +303,9 @@ __global__ __launch_bounds__(NT) void angles_pair_kernel(const double* Wa, const
       lam[t] = l < 0.0 ? 0.0 : (l > 1.0 ? 1.0 : l);          // (a NaN stays a NaN and reaches the output)
     }
     __syncthreads();
-    if (t < k) {                                   // descending; ties by index (rank counting)
+    if (t < k) {                                   // descending, NaN first, ties by index: every slot of th is written for any lam (rank.h)
       const double mine = lam[t];
-      th[rank_desc<false>(lam, k, t)] = mine <= 0.5 ? asin(sqrt(mine)) : acos(sqrt(1.0 - mine));
+      th[rank_desc(lam, k, t)] = mine <= 0.5 ? asin(sqrt(mine)) : acos(sqrt(1.0 - mine));
     }
     __syncthreads();
     for (int e = t; e < k; e += NT) {

@@ -278,7 +278,7 @@ __global__ __launch_bounds__(NT) void fm_head_kernel(const double* part, double*
   jacobi_lds<KMAX, NT>(A, V, ws, m);
   if (t < m) lv[t] = A[t][t];
   __syncthreads();
-  if (t < m) { rk[t] = rank_desc<true>(lv, m, t); lam[rk[t]] = lv[t]; }
+  if (t < m) { rk[t] = rank_desc(lv, m, t); lam[rk[t]] = lv[t]; }
   __syncthreads();
   if (t == 0) { double l0 = lv[0]; for (int e = 1; e < m; ++e) l0 = lv[e] > l0 ? lv[e] : l0; ctl->lam0 = l0; }
   for (int e = t; e < m * m; e += NT) {                // A <- S: the eigenvectors as columns, descending
@@ -424,7 +424,7 @@ __global__ __launch_bounds__(NT) void fm_finish_head_kernel(const double* part, 
   jacobi_lds<KMAX, NT>(Nm, A, ws, m);                  // U into A
   if (t < m) lv[t] = Nm[t][t];
   __syncthreads();
-  if (t < m) rk[t] = rank_desc<true>(lv, m, t);
+  if (t < m) rk[t] = rank_desc(lv, m, t);
   for (int e = t; e < 64; e += NT) info[8 + e] = 0.0;
   __syncthreads();
   if (t < m) {
@@ -543,7 +543,7 @@ __global__ __launch_bounds__(NT) void fm_theta_kernel(const double* Mt, float* t
     thr[t] = th;
   }
   __syncthreads();
-  if (t < d) theta[i * d + rank_desc<true>(thr, d, t)] = (float)thr[t];
+  if (t < d) theta[i * d + rank_desc(thr, d, t)] = (float)thr[t];
 }
 
 // ------------------------------------------------------------------------------------------------------------ host side

@@ -184,7 +184,7 @@ __global__ __launch_bounds__(NT) void fr_basis_kernel(const double* Mt, double* 
     hv[t] = sn > 0.0 ? th * cs / sn : (sn == 0.0 ? 1.0 : sn);
   }
   __syncthreads();
-  if (t < k) ths[rank_desc<true>(thr, k, t)] = thr[t];       // descending; ties by index (rank counting)
+  if (t < k) ths[rank_desc(thr, k, t)] = thr[t];       // descending; ties by index (rank counting)
   __syncthreads();
   for (int e = t; e < k; e += NT) thetas[i * k + e] = ths[e];
   if (t == 0) {
@@ -379,7 +379,7 @@ __global__ __launch_bounds__(NT) void fr_finish_head_kernel(const double* Ps, co
   if (t < k) lam[t] = A[t][t];
   __syncthreads();
   if (t < k) {
-    const int rank = rank_desc<true>(lam, k, t);
+    const int rank = rank_desc(lam, k, t);
     weight[rank] = (float)lam[t];
     for (int c = 0; c < k; ++c) Rot[rank * k + c] = V[c][t];
   }

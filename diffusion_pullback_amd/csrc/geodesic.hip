@@ -158,7 +158,7 @@ __global__ __launch_bounds__(NT) void gd_pair_kernel(GdPairArgs a) {
     sgn[t] = V[best][t] < 0.0 ? -1.0 : 1.0;
   }
   __syncthreads();
-  if (t < k) ord[rank_desc<true>(val, k, t)] = t;  // descending; ties by index (rank counting)
+  if (t < k) ord[rank_desc(val, k, t)] = t;  // descending; ties by index (rank counting)
   __syncthreads();
   const bool refused = !ex && val[ord[0]] > GD_DOMAIN;         // (uniform)
   if (refused) {

@@ -2,29 +2,13 @@
 // eigen-solve, the fixed-order block sum, the guarded four-column row access, the row-group step of the fp64 MFMA streams and the descending rank order.
 #pragma once
 #include "kernels.h"
+#include "rank.h"      // sorts_before, rank_desc (one total order, NaN first, for every kernel that scatters by rank), max_nan
 
 namespace dpb {
 
 typedef double geom_d4 __attribute__((ext_vector_type(4)));
 
 __device__ inline double nan64() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-// the descending order of the rank counting: a NaN sorts before every number and ties go by index, so the ranks are a permutation whatever the values
-__device__ inline bool sorts_before(double other, double mine, bool other_first) {
-  const bool on = other != other, mn = mine != mine;
-  if (on || mn) return on && (!mn || other_first);
-  return other > mine || (other == mine && other_first);
-}
-
-// the rank of v[t] among v[0 .. k-1], descending, ties by index.  NAN_FIRST: the order of sorts_before; otherwise the plain comparison, under which a
-// NaN counts nothing and is counted by nothing (the eigen-solves of orth.hip and angles.hip, whose NaNs reach the output either way)
-template <bool NAN_FIRST>
-__device__ inline int rank_desc(const double* v, int k, int t) {
-  int rank = 0;
-  const double mine = v[t];
-  for (int e = 0; e < k; ++e) rank += (NAN_FIRST ? sorts_before(v[e], mine, e < t) : (v[e] > mine || (v[e] == mine && e < t))) ? 1 : 0;
-  return rank;
-}
 
 // ------------------------------------------------------------------------------------------------------------ the eigen-solve
 // A [k][k] symmetric in LDS -> diagonal; with eigenvectors, V <- V J for every rotation J (the caller starts it at the identity: A_in = V diag V^T).

@@ -22,6 +22,17 @@ struct OrthBatch { long w, v, s, conv, scratch; };
 constexpr int KMAX_REG = 56;          // largest rank of the register-tiled apply kernel (the reference's default pca_rank is 50)
 constexpr int KMAX_ALL = ORTH_MAX_RANK;   // largest supported rank, 128 (A [k][k+1] fp64 of the eigen-solve has to fit the 160 KB of LDS)
 
+// Non-finite input (include/dpb.h at dpb_orth).  A row of W holds a NaN or an inf exactly when its Gram diagonal sum w^2 is not finite (fp32 squares
+// cannot overflow the fp64 sums), so the eigen-solves test the k diagonal entries once, the same in every thread.
+template <int LD>
+__device__ inline bool gram_diag_bad(const double (*G)[LD], int k) {
+  bool bad = false;
+  for (int i = 0; i < k; ++i) bad |= !(fabs(G[i][i]) <= 1.79769313486231570815e308);
+  return bad;
+}
+// one element of Vprev - V for the two convergence figures: an inf (from Vprev) becomes a NaN, so that a non-finite Vprev reads conv = (NaN, NaN), never inf
+__device__ inline float finite_or_nan(float x) { return fabsf(x) <= 3.402823466e+38f ? x : __builtin_nanf(""); }
+
 // grid (nblk, k, ceil(k/16)): block (b, i, jt) accumulates G[i][jt*16..] and X[i][jt*16..] = W_i . Vprev_j over its slice of N and stores them as
 // partial b: Gp[b][0 | 1][k][k] (plain stores; eig_kernel adds the partials in block order -- no atomics, bitwise reproducible)
 __global__ __launch_bounds__(256) void gram_kernel(const float* W, const float* Vp, double* Gp, int k, long N, OrthBatch ob) {
@@ -90,6 +101,11 @@ __global__ __launch_bounds__(64) void eig_kernel(const double* Gp, int nbg, doub
     X[e] = x;
   }
   __syncthreads();
+  if (gram_diag_bad(Q, k)) {                     // a non-finite value in W (block-uniform): NaN out, no sweeps, no data-derived index
+    for (int e = r; e < k * k; e += 64) Cm[e] = nan64();
+    if (r < k) s_out[r] = __builtin_nanf("");
+    return;
+  }
   if (r < k)
     for (int j = 0; j < k; ++j) A[r][j] = 0.5 * (Q[r][j] + Q[j][r]);
   __syncthreads();
@@ -138,10 +154,10 @@ __global__ __launch_bounds__(64) void eig_kernel(const double* Gp, int nbg, doub
   __syncthreads();
   if (r < k) {
     const int i = r, e = order[i];
-    double lam = A[e][e] > 0 ? A[e][e] : 0.0;
+    double lam = !(A[e][e] <= 0) ? A[e][e] : 0.0; // (a NaN is not clamped to 0: it stays one in s and in the row of Cm)
     double sig = sqrt(lam);                       // singular value of W
     s_out[i] = (float)sqrt(sig);                  // reference returns s.sqrt() (utils.py:810)
-    double inv = sig > 1e-150 ? 1.0 / sig : 0.0;
+    double inv = !(sig <= 1e-150) ? 1.0 / sig : 0.0;
     double dot = 0;
     for (int j = 0; j < k; ++j) dot += Q[j][e] * inv * X[j * k + i];
     double sgn = dot < 0 ? -1.0 : 1.0;
@@ -185,6 +201,11 @@ __global__ __launch_bounds__(NT) void eig_par_kernel(double* Gp, int nbg, double
     Xg[e] = x;                                   // element e of partial 0 was read by this thread only: no other reader to race with
   }
   __syncthreads();
+  if (gram_diag_bad(A, k)) {                     // as eig_kernel: NaN out (block-uniform)
+    for (int e = t; e < k * k; e += NT) Cm[e] = nan64();
+    if (t < k) s_out[t] = __builtin_nanf("");
+    return;
+  }
   for (int e = t; e < k * k; e += NT) {          // A <- (G + G^T) / 2: the pair (i, j), (j, i) belongs to the thread that holds e = (i, j), i < j
     const int i = e / k, j = e % k;
     if (i < j) { const double v = 0.5 * (A[i][j] + A[j][i]); A[i][j] = v; A[j][i] = v; }
@@ -194,14 +215,14 @@ __global__ __launch_bounds__(NT) void eig_par_kernel(double* Gp, int nbg, double
   jacobi_round_robin<KMAX, NT>(A, Q, ws, k);
   if (t < k) lam[t] = A[t][t];
   __syncthreads();
-  if (t < k) order[rank_desc<false>(lam, k, t)] = t;       // descending eigenvalue; ties by index (rank counting instead of a serial sort)
+  if (t < k) order[rank_desc(lam, k, t)] = t;    // descending eigenvalue, NaN first, ties by index: a permutation of 0 .. k-1 for any lam (rank.h)
   __syncthreads();
   if (t < k) {
     const int i = t, e = order[i];
-    const double l = lam[e] > 0 ? lam[e] : 0.0;
+    const double l = !(lam[e] <= 0) ? lam[e] : 0.0;   // (a NaN is not clamped to 0, as eig_kernel)
     const double sig = sqrt(l);                   // singular value of W
     s_out[i] = (float)sqrt(sig);                  // reference returns s.sqrt() (utils.py:810)
-    const double inv = sig > 1e-150 ? 1.0 / sig : 0.0;
+    const double inv = !(sig <= 1e-150) ? 1.0 / sig : 0.0;
     double dot = 0;
     for (int j = 0; j < k; ++j) dot += Q.at(j, e) * inv * Xg[j * k + i];
     sgn[i] = (dot < 0 ? -1.0 : 1.0) * inv;
@@ -234,10 +255,10 @@ __global__ __launch_bounds__(256) void orth_apply_kernel(const float* W, const f
         for (int j = 0; j < KMAX; ++j)
           if (j < k) v += cm[i * k + j] * (double)w[j];
         float vf = (float)v;
-        float dlt = Vp[(long)i * N + n] - vf;
+        float dlt = finite_or_nan(Vp[(long)i * N + n] - vf);
         V[(long)i * N + n] = vf;
         d2 += (double)dlt * dlt;
-        viol = fmaxf(viol, fabsf(dlt) - 1e-5f * fabsf(vf));
+        viol = max_nan(viol, fabsf(dlt) - 1e-5f * fabsf(vf));
       }
     }
   }
@@ -247,13 +268,13 @@ __global__ __launch_bounds__(256) void orth_apply_kernel(const float* W, const f
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int o = 32; o > 0; o >>= 1) {
     d2 += __shfl_xor(d2, o, 64);
-    viol = fmaxf(viol, __shfl_xor(viol, o, 64));
+    viol = max_nan(viol, __shfl_xor(viol, o, 64));
   }
   if (lane == 0) { rd[wave] = d2; rv[wave] = viol; }
   __syncthreads();
   if (threadIdx.x == 0) {                        // this block's partial (finish kernel: block order)
     acc[2 * blockIdx.x] = ((rd[0] + rd[1]) + rd[2]) + rd[3];
-    acc[2 * blockIdx.x + 1] = (double)fmaxf(fmaxf(fmaxf(rv[0], rv[1]), fmaxf(rv[2], rv[3])), 0.f);
+    acc[2 * blockIdx.x + 1] = (double)max_nan(max_nan(max_nan(rv[0], rv[1]), max_nan(rv[2], rv[3])), 0.f);
   }
 }
 
@@ -284,10 +305,10 @@ __global__ __launch_bounds__(256) void orth_apply_tiled_kernel(const float* W, c
       for (int i = 0; i < IT; ++i) {
         if (i0 + i < k) {
           const float vf = (float)v[i];
-          const float dlt = Vp[(long)(i0 + i) * N + n] - vf;
+          const float dlt = finite_or_nan(Vp[(long)(i0 + i) * N + n] - vf);
           V[(long)(i0 + i) * N + n] = vf;
           d2 += (double)dlt * dlt;
-          viol = fmaxf(viol, fabsf(dlt) - 1e-5f * fabsf(vf));
+          viol = max_nan(viol, fabsf(dlt) - 1e-5f * fabsf(vf));
         }
       }
     }
@@ -297,13 +318,13 @@ __global__ __launch_bounds__(256) void orth_apply_tiled_kernel(const float* W, c
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   for (int o = 32; o > 0; o >>= 1) {
     d2 += __shfl_xor(d2, o, 64);
-    viol = fmaxf(viol, __shfl_xor(viol, o, 64));
+    viol = max_nan(viol, __shfl_xor(viol, o, 64));
   }
   if (lane == 0) { rd[wave] = d2; rv[wave] = viol; }
   __syncthreads();
   if (threadIdx.x == 0) {
     acc[2 * blockIdx.x] = ((rd[0] + rd[1]) + rd[2]) + rd[3];
-    acc[2 * blockIdx.x + 1] = (double)fmaxf(fmaxf(fmaxf(rv[0], rv[1]), fmaxf(rv[2], rv[3])), 0.f);
+    acc[2 * blockIdx.x + 1] = (double)max_nan(max_nan(max_nan(rv[0], rv[1]), max_nan(rv[2], rv[3])), 0.f);
   }
 }
 
@@ -316,7 +337,7 @@ __global__ void orth_finish_kernel(const double* acc, int nb, float* conv, OrthB
     for (int u = 0; u < 16; ++u) { const int b = min(b0 + u, nb - 1); t[u] = acc[2 * b]; v[u] = acc[2 * b + 1]; }
 #pragma unroll
     for (int u = 0; u < 16; ++u)
-      if (b0 + u < nb) { d2 += t[u]; m = fmax(m, v[u]); }
+      if (b0 + u < nb) { d2 += t[u]; m = max_nan(m, v[u]); }
   }
   conv[0] = (float)sqrt(d2);
   conv[1] = (float)m;

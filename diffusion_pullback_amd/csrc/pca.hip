@@ -154,7 +154,7 @@ __global__ void pca_svd_finish_kernel(const double* __restrict__ Cm, int q, floa
   if (i >= q) return;
   double n2 = 0.0;
   for (int j = 0; j < q; ++j) n2 += Cm[i * q + j] * Cm[i * q + j];
-  const double inv = n2 > 0.0 ? 1.0 / sqrt(n2) : 0.0;    // = sigma_i
+  const double inv = !(n2 <= 0.0) ? 1.0 / sqrt(n2) : 0.0;   // = sigma_i (NaN for the NaN row dpb_orth leaves on non-finite input: S is NaN, not 0)
   S[i] = (float)inv;
   for (int j = 0; j < q; ++j) UbT[i * q + j] = Cm[i * q + j] * inv;
 }

@@ -26,6 +26,7 @@ Deliberate differences:
 """
 from __future__ import annotations
 
+import math
 import time
 import types
 from typing import Optional, Tuple
@@ -55,6 +56,17 @@ def _t_shared(t, batch: int, what: str) -> float:
         raise ValueError(f"{what} takes one timestep for its batch, got {len(v)} with distinct values: per-sample timesteps are honoured by get_h, the "
                          "U-Net call, pullback_fixed, decoder_pullback_fixed, global_pca_zt and local_encoder_pullback_batch only")
     return _timesteps(t, batch)                            # (equal entries: one timestep, if there is one or one per sample)
+
+
+def _conv_finite(what: str, i: int, conv, batch: bool = False) -> None:
+    """The power iterations' guard: conv [B][2] as read back at iteration i (0-based) must be finite.  dpb_orth answers a NaN or an inf in W = J^T J V
+    (an fp16 tangent that overflowed) or in V_prev with conv = (NaN, NaN) and a NaN basis (include/dpb.h): that iteration is never counted as
+    converged -- the reference's svd raises on such input and its allclose is False on NaN."""
+    bad = [b for b, c in enumerate(conv) if not all(math.isfinite(float(a)) for a in c)]
+    if bad:
+        where = f" for sample(s) {bad} of the batch" if batch else ""
+        raise L.DpbError(f"{what}: the convergence figures of iteration {i} are not finite{where} (conv = {[list(conv[b]) for b in bad]}): W = J^T J V "
+                         "or V_prev holds a NaN or an inf, e.g. an fp16 tangent that overflowed; the basis of this iteration is NaN")
 
 
 class PullbackUNet:
@@ -222,6 +234,7 @@ class PullbackUNet:
             V, s, conv = eng.orth(W, V_prev)
             dist, viol = conv.tolist()                                            # the only host sync per iteration
             self.last_history.append(dist)
+            _conv_finite("local_encoder_pullback", i, [[dist, viol]])
             if self.verbose:
                 print(f"power method : {i}-th step convergence : ", dist)
             if viol <= thr and i > min_iter:
@@ -295,6 +308,7 @@ class PullbackUNet:
             V, U, s, conv = eng.iterate(key, V, 1)
             conv = conv.tolist()                               # the only host sync per iteration
             self.last_history.append([c[0] for c in conv])
+            _conv_finite("local_encoder_pullback_batch", i, conv, batch=True)
             if self.verbose:
                 print(f"power method : {i}-th step convergence : ", [c[0] for c in conv])
             for b in range(B):
@@ -370,9 +384,10 @@ class PullbackUNet:
             V, s, conv = eng.orth(W, V_prev)
             dist, viol = conv.tolist()                                            # the only host sync per iteration
             self.last_history.append(dist)
+            _conv_finite("local_decoder_pullback", i, [[dist, viol]])
             if self.verbose:
                 print(f"power method : {i}-th step convergence : ", dist)
-            if thr is not None and viol <= thr and i > min_iter:                 # the encoder's sign-aligned allclose rule (module docstring)
+            if thr is not None and viol <= thr and i > min_iter:                # the encoder's sign-aligned allclose rule (module docstring)
                 if self.verbose:
                     print("reach convergence threshold : ", dist)
                 break

@@ -152,6 +152,13 @@ int dpb_vjp(dpb_engine* e, int tap_buf, const float* U, int nt, float* W);
  * Domain: this is the Gram method (eigen-decomposition of W W^T in fp64), which squares the condition number: V and s have full fp32 accuracy up
  * to cond(W) ~ 1e4; beyond that the trailing vectors degrade (tests/test_gpu_orth.py).  Rows of W that are exactly orthogonal to all
  * others are not mixed; equal singular values among them come out in input order.
+ * Non-finite input (tests/test_gpu_orth.py):
+ *   - a NaN or an inf anywhere in W: every element of V and of s is NaN and conv = (NaN, NaN); the call returns 0.  The eigen-solve is skipped (the
+ *     Gram diagonal sum w^2 tells) and no index derived from data leaves [0, k): the eigenvalue ranking is a total order (NaN first).
+ *   - W finite, a NaN or an inf in Vprev: s is bitwise that of the call with a finite Vprev, every row of V is bitwise plus or minus that call's row
+ *     (only the sign alignment reads Vprev), and conv = (NaN, NaN).
+ *   - conv[0] and conv[1] both propagate a NaN through every reduction; neither is ever inf for a non-finite input.
+ *   The next call on the same scratch is unaffected (the scratch carries nothing from call to call).
  * Replaces: torch.linalg.svd + dist/allclose inputs, utils.py:799-806.  Engine-independent. */
 int dpb_orth(const float* W, const float* Vprev, float* V, float* s, float* conv, void* scratch, int k, int64_t N,
              void* hip_stream);
@@ -171,7 +178,8 @@ int dpb_orth_checked(const float* W, const float* Vprev, float* V, float* s, flo
  * descending).  The QR factorisations and svd(B) are dpb_orth (same spans); products on the f32-input MFMA, every reduction in a fixed
  * order (bitwise reproducible), 64-bit offsets (H may exceed 4 GiB).  1 <= q <= 128, q <= N - 1, q <= D, niter >= 0; scratch: device
  * memory of >= dpb_pca_scratch_bytes(q, N, D) bytes (any alignment).  No host synchronisation.  A rank-deficient centred H gives s = 0
- * in the missing directions (and zero rows of u).  Errors via dpb_last_error. */
+ * in the missing directions (and zero rows of u).  A NaN or an inf anywhere in H or R: every element of u and of s is NaN and the call returns 0
+ * (the rule of dpb_orth, which every factorisation goes through); the next call on the same scratch is unaffected.  Errors via dpb_last_error. */
 size_t dpb_pca_scratch_bytes(int q, int64_t N, int64_t D);   /* 0 when invalid */
 int dpb_pca_lowrank(const float* H, int64_t N, int64_t D, const float* R, int q, int niter, float* u, float* s, void* scratch,
                     size_t scratch_bytes, void* hip_stream);
@@ -501,6 +509,9 @@ int dpb_row_sumsq(const float* X, int64_t rows, int64_t N, double* ss /*[rows]*/
 /* n_iters full power iterations with no host synchronisation: V <- orth(J^T J V), U = J V_prev, for all B samples
  * of the last dpb_primal together (independent bases, one shared weight stream; B*k <= max_tangents).
  * V [B][k][N_in] in/out, U [B][k][N_h] out, s [B][k] out, conv [B][2] out (of the last iteration).
+ * Non-finite values follow the rule of dpb_orth per sample: a sample whose V or W = J^T J V holds a NaN or an inf (an fp16 tangent that overflowed)
+ * comes back with V and s all NaN and conv = (NaN, NaN), and stays so in the following iterations; no other sample's V, U, s or conv changes by a
+ * bit; the call returns 0.  A caller that reads conv for a stop rule must treat a non-finite conv as an error, never as converged.
  * Replaces: the loop body utils.py:756-808 (k <= 128), once per sample of the batch. */
 int dpb_pullback_iterate(dpb_engine* e, int tap_buf, float* V, float* U, float* s, float* conv, int k, int n_iters);
 

@@ -9,6 +9,11 @@ Cm = diag(sgn / sigma) E^T with the 1e-150 floor, V = Cm W rounded to fp32, the 
 that LAPACK's eigh does not share are restated explicitly, because the exact cases rest on them: an index whose off-diagonal Gram entries are all
 exactly zero is never rotated (its eigenvector stays the unit vector, its eigenvalue the diagonal entry, bit for bit), and equal eigenvalues keep
 their index order.
+
+Non-finite input has a rule of its own (include/dpb.h at dpb_orth), restated here too: a NaN or an inf in W gives V, s and conv all NaN; a non-finite
+Vprev leaves s and |V| alone and gives conv = (NaN, NaN); the eigenvalue ranking is a total order (rank_scatter) and conv[1] keeps a NaN (max_nan).
+The cases (NF_*), the poisons and the two assertions are shared by tests/test_gpu_orth.py and tests/test_orth_host.py, which also keeps the three
+traits the kernels had before the rule (MUTANTS) failing those assertions.
 """
 import functools
 
@@ -242,29 +247,131 @@ def _eig_jacobi_like(G):
     return lam, E
 
 
-def restate(W, Vprev, gram_dtype=np.float64, apply_dtype=np.float64):
+POISON = -1                      # what a slot of `order` holds before the rank scatter
+STALE = 1.0                      # what the restatement reads through a slot the scatter never wrote: a finite number, "whatever the memory held"
+MUTANTS = ("rank_plain", "clamp", "fmax")
+
+
+def rank_scatter(lam, total=True):
+    """order[rank(lam, t)] = t for every t into an array of POISON, as eig_par_kernel does it.  total: the order of sorts_before (csrc/rank.h) --
+    descending, NaN first, ties by index; otherwise the plain comparison lam[e] > lam[t] or (== and e < t), under which a NaN counts nothing and is
+    counted by nothing."""
+    k = len(lam)
+    order = np.full(k, POISON, dtype=np.int64)
+    for t in range(k):
+        mine, rank = lam[t], 0
+        for e in range(k):
+            if total and (np.isnan(lam[e]) or np.isnan(mine)):
+                rank += bool(np.isnan(lam[e]) and (not np.isnan(mine) or e < t))
+            else:
+                rank += bool(lam[e] > mine or (lam[e] == mine and e < t))
+        order[rank] = t
+    return order
+
+
+def max_nan(a, b):
+    """the kernels' maximum of the convergence figure: keeps a NaN operand (Python's max(0, nan) is 0, as fmaxf's)"""
+    return np.maximum(a, b)
+
+
+def restate(W, Vprev, gram_dtype=np.float64, apply_dtype=np.float64, mutant=None):
     """dpb_orth in numpy -> (V fp32 [k][N], s fp32 [k], conv fp32 [2]).  gram_dtype: the type W is multiplied and accumulated in for the Gram matrix
-    and the overlaps; apply_dtype: the same for V = Cm W.  float64 for both is the method; float32 for either is a mutant."""
-    Wg, Vg = W.astype(gram_dtype), Vprev.astype(gram_dtype)
-    G = (Wg @ Wg.T).astype(np.float64)
-    X = (Wg @ Vg.T).astype(np.float64)            # X[j][i] = W_j . Vprev_i
-    lam, E = _eig_jacobi_like(0.5 * (G + G.T))
-    order = np.argsort(-lam, kind="stable")       # descending, ties by index
-    lam, E = lam[order], E[:, order]
-    sig = np.sqrt(np.maximum(lam, 0.0))
-    inv = np.where(sig > MIN_SIGMA, 1.0 / np.where(sig > MIN_SIGMA, sig, 1.0), 0.0)
-    dot = np.einsum("ji,ji->i", E * inv[None, :], X)
-    Cm = (np.where(dot < 0, -1.0, 1.0) * inv)[:, None] * E.T
-    V = (Cm.astype(apply_dtype) @ W.astype(apply_dtype)).astype(np.float32)
-    d = Vprev.astype(np.float32) - V
-    conv0 = np.float32(np.sqrt((d.astype(np.float64) ** 2).sum()))
-    conv1 = np.float32(max(np.float32(0), (np.abs(d) - np.float32(1e-5) * np.abs(V)).max()))      # fp32, as the kernel is written
+    and the overlaps; apply_dtype: the same for V = Cm W.  float64 for both is the method; float32 for either is a mutant.
+
+    Non-finite input, the rule of include/dpb.h: a NaN or an inf in W (read off the Gram diagonal) gives V, s and conv all NaN without an eigen-solve;
+    a non-finite Vprev only reaches the sign alignment and conv, where an inf difference counts as NaN and both figures propagate it.
+    mutant (one of MUTANTS) restates the method WITHOUT that detection and with one of the three traits it had before the rule: "rank_plain" ranks
+    the eigenvalues by the plain comparison into a poisoned `order` and reads STALE through the unwritten slots, "clamp" takes lam > 0 ? lam : 0,
+    "fmax" takes the maximum of conv[1] with a NaN-dropping max."""
+    assert mutant is None or mutant in MUTANTS
+    k = len(W)
+    with np.errstate(all="ignore"):
+        Wg, Vg = W.astype(gram_dtype), Vprev.astype(gram_dtype)
+        G = (Wg @ Wg.T).astype(np.float64)
+        X = (Wg @ Vg.T).astype(np.float64)            # X[j][i] = W_j . Vprev_i
+        stale = np.zeros(k, dtype=bool)
+        if not np.isfinite(np.diag(G)).all():
+            if mutant is None:
+                return np.full(W.shape, np.nan, np.float32), np.full(k, np.nan, np.float32), np.full(2, np.nan, np.float32)
+            lam, E = np.full(k, np.nan), np.full((k, k), np.nan)        # what thirty Jacobi sweeps leave of a Gram matrix with one NaN
+        else:
+            lam, E = _eig_jacobi_like(0.5 * (G + G.T))
+        order = rank_scatter(lam, total=mutant != "rank_plain") if np.isnan(lam).any() else np.argsort(-lam, kind="stable")
+        stale = order == POISON
+        order = np.where(stale, 0, order)
+        lam, E = lam[order], E[:, order]
+        lam[stale], E[:, stale] = STALE, STALE
+        sig = np.sqrt(np.maximum(lam, 0.0) if mutant != "clamp" else np.where(lam > 0, lam, 0.0))      # np.maximum keeps a NaN
+        dead = sig <= MIN_SIGMA if mutant != "clamp" else ~(sig > MIN_SIGMA)
+        inv = np.where(dead, 0.0, 1.0 / np.where(dead, 1.0, sig))
+        dot = np.einsum("ji,ji->i", E * inv[None, :], X)
+        Cm = (np.where(dot < 0, -1.0, 1.0) * inv)[:, None] * E.T
+        V = (Cm.astype(apply_dtype) @ W.astype(apply_dtype)).astype(np.float32)
+        d = Vprev.astype(np.float32) - V
+        d = np.where(np.isfinite(d), d, np.float32(np.nan))             # an inf difference (from Vprev) counts as NaN: conv is never inf
+        conv0 = np.float32(np.sqrt((d.astype(np.float64) ** 2).sum()))
+        viol = np.abs(d) - np.float32(1e-5) * np.abs(V)                 # fp32, as the kernel is written
+        conv1 = np.float32(max_nan(np.float32(0), viol.max()) if mutant != "fmax" else max(np.float32(0), np.fmax.reduce(viol, axis=None)))
     return V, np.sqrt(sig).astype(np.float32), np.array([conv0, conv1], dtype=np.float32)
 
 
+# ----------------------------------------------------------------------------------------------------------- non-finite input: cases and assertions
+NF_K = [5, 6, 16, 17, 33, 57, 65, 97, 128]       # cyclic | round-robin 256 threads | <32> | <64> with apply<56> | tiled apply | <96> | eigenvectors in global memory
+NF_N = 300                                       # ragged against the 256-column slices: two blocks, the second 44 columns
+NF_SHAPES = [(k, NF_N) for k in NF_K] + [(128, 65795)]      # and the grid-stride route once
+NF_VALUES = {"nan": np.nan, "pinf": np.inf, "ninf": -np.inf}
+NF_POISONS = [f"{v}-{at}" for v in NF_VALUES for at in ("first", "tail")] + ["nan-row"]
+NF_VPREV_K = [5, 40, 100]
+
+
+def poisoned(A, how):
+    """a copy of A [k][N] with one of NF_POISONS put in: `value-first` at [0][0], `value-tail` at [k-1][N-1], `nan-row` the whole row k // 2"""
+    A = np.array(A, dtype=np.float32, copy=True)
+    v, at = how.split("-")
+    if at == "row":
+        A[len(A) // 2, :] = np.nan
+    else:
+        A[(0, 0) if at == "first" else (len(A) - 1, A.shape[1] - 1)] = NF_VALUES[v]
+    return A
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def assert_all_nan(V, s, conv, what):
+    """the rule for a non-finite W: every element of V, s and conv is NaN"""
+    V, s, conv = np.asarray(V), np.asarray(s), np.asarray(conv)
+    assert np.isnan(conv).all(), (what, "conv", conv)
+    assert np.isnan(s).all(), (what, "s", s)
+    assert np.isnan(V).all(), (what, "V", int(np.isnan(V).sum()), V.size)
+
+
+def assert_vprev_rule(got, clean, what):
+    """the rule for a finite W and a non-finite Vprev: s is bitwise the clean call's, |V| is bitwise the clean call's with one sign per row, conv is
+    (NaN, NaN)"""
+    (V, s, conv), (Vc, sc, _) = got, clean
+    assert np.array_equal(_bits(s), _bits(sc)), (what, "s")
+    assert np.array_equal(_bits(V) & 0x7FFFFFFF, _bits(Vc) & 0x7FFFFFFF), (what, "|V|")
+    flipped = (_bits(V) != _bits(Vc))
+    nz = (_bits(Vc) & 0x7FFFFFFF) != 0
+    for i in range(len(V)):
+        assert flipped[i][nz[i]].all() or not flipped[i][nz[i]].any(), (what, "row", i, "is neither the clean row nor its negative")
+    assert np.isnan(np.asarray(conv)).all(), (what, "conv", conv)
+
+
 # ----------------------------------------------------------------------------------------------------------- the kernel, called
-def gpu_orth(W, Vprev, inplace=False, device="cuda:0"):
-    """dpb_orth_checked on fp32 numpy (or device torch) inputs -> numpy (V, s, conv); inplace: V aliases Vprev"""
+def gpu_scratch(k, n, device="cuda:0"):
+    """a scratch tensor for gpu_orth calls of shape (k, n), for the tests that reuse one across calls"""
+    import torch
+
+    from diffusion_pullback_amd import lib as L
+    return torch.empty(int(L.load().dpb_orth_scratch_bytes(k, n)) // 8, dtype=torch.float64, device=device)
+
+
+def gpu_orth(W, Vprev, inplace=False, device="cuda:0", scratch=None):
+    """dpb_orth_checked on fp32 numpy (or device torch) inputs -> numpy (V, s, conv); inplace: V aliases Vprev; scratch: the caller's (gpu_scratch),
+    default a fresh one"""
     import ctypes as C
 
     import torch
@@ -278,7 +385,9 @@ def gpu_orth(W, Vprev, inplace=False, device="cuda:0"):
     V = Vpd if inplace else torch.empty_like(Wd)
     s = torch.empty(k, dtype=torch.float32, device=device)
     conv = torch.empty(2, dtype=torch.float32, device=device)
-    scratch = torch.empty(int(lib.dpb_orth_scratch_bytes(k, n)) // 8, dtype=torch.float64, device=device)
+    if scratch is None:
+        scratch = torch.empty(int(lib.dpb_orth_scratch_bytes(k, n)) // 8, dtype=torch.float64, device=device)
+    assert scratch.numel() * 8 >= int(lib.dpb_orth_scratch_bytes(k, n)) and scratch.dtype == torch.float64
     L.check(lib.dpb_orth_checked(Wd.data_ptr(), Vpd.data_ptr(), V.data_ptr(), s.data_ptr(), conv.data_ptr(), scratch.data_ptr(), scratch.numel() * 8,
                                  k, n, C.c_void_p(torch.cuda.current_stream(device).cuda_stream)))
     torch.cuda.synchronize(device)

@@ -31,6 +31,18 @@ Measured maxima on an MI355X per route (vec | on | s_ulps | conv0_ulps | conv1_e
     5 decades                                12.09 | 181.5 | 0.421 | 0.182 | 1.4e-09
     6 decades                                1126  | 9201  | 15.33 | 0.182 | 1.7e-09     (s_ulps of the leading half: < 1)
 Bitwise: two calls, the in-place call and the batched launch of dpb_pullback_iterate all return the bits of the single out-of-place call.
+
+Non-finite input (the rule of include/dpb.h, exact: NaN masks and bit equality, no tolerance):
+  * a NaN or an inf anywhere in W: every element of V and s is NaN, conv = (NaN, NaN), the call returns 0, and no index derived from data leaves
+    [0, k) -- the eigen-solve is skipped on a non-finite Gram diagonal and the eigenvalue ranking is a total order (NaN first; its index property is
+    proved on the CPU under ASan/UBSan, tests/test_rank_order_host.py).  The next clean call on the same scratch has the bits of a fresh one.
+  * W finite, Vprev non-finite: s has the clean call's bits, every row of V is bitwise plus or minus the clean row, conv = (NaN, NaN).
+  * batched launch: a bad sample changes no bit of any other sample's V, U, s or conv.
+  * the loops of pullback.py raise DpbError on a non-finite conv and never count it as converged (tests/test_stop_rule_host.py on a stub; here
+    on an fp16 engine whose cotangent overflows).
+Every k of every eigen-solve and apply route is covered at N = 300 (R.NF_SHAPES), the grid-stride route once, both DPB_EIG_PAR routes in their child.
+tests/test_orth_host.py holds the numpy restatement to the same assertions and keeps three mutants failing them: the plain-comparison ranking (slots
+of `order` unwritten, s finite through them), the lam > 0 ? lam : 0 clamp (s == 0 beside a NaN V) and the NaN-dropping maximum (conv[1] == 0).
 """
 import os
 import subprocess
@@ -151,10 +163,15 @@ def _linear_tape():
     return NR.build_tape([NR.linear("o", "x", "p", 24)], params, torch.float32, DEV, 40, 16)
 
 
+NAN_BATCH = [(3, 3), (3, 20), (2, 128)]          # cyclic | round-robin in LDS | eigenvectors in global memory
+
+
 @pytest.mark.parametrize("B,k", [(3, 3), (3, 12), (3, 20), (3, 60), (2, 128)])
 def test_batched_launch_equals_single_launches(B, k):
     """dpb_pullback_iterate re-orthonormalises all samples in one set of launches (OrthArgs::batch, the sample on a grid axis), in place: one
-    iteration must return the bits of Engine.orth on each sample's W = J^T J V0, and each sample meets the SVD bounds"""
+    iteration must return the bits of Engine.orth on each sample's W = J^T J V0, and each sample meets the SVD bounds.  For NAN_BATCH the iteration
+    is run once more with a row of sample 1's V0 set to NaN: sample 1 comes back all NaN in V and s with conv = (NaN, NaN), and V, U, s and conv of
+    every other sample keep the bits of the clean run"""
     N = 640
     e = NR.engine(_linear_tape(), B, B * k)
     g = torch.Generator().manual_seed(100 + k)
@@ -164,7 +181,7 @@ def test_batched_launch_equals_single_launches(B, k):
     V0 = torch.from_numpy(np.ascontiguousarray(V0, dtype=np.float32)).to(DEV)
     e.primal(NR.to_nchw(x), 1.0, None, "o")
     W = e.vjp("o", e.jvp("o", V0)).clone()
-    V, _, s, conv = e.iterate("o", V0.clone(), 1)
+    V, U, s, conv = e.iterate("o", V0.clone(), 1)
     torch.cuda.synchronize()
     for b in range(B):
         rows = slice(b * k, (b + 1) * k)
@@ -174,7 +191,81 @@ def test_batched_launch_equals_single_launches(B, k):
         print(f"B={B} k={k} sample {b}: singular values of W over {c.sqrtS[0] ** 2 / c.sqrtS[-1] ** 2:.1f}x")
         R.check(*single, c, k, N, 2, f"batch{B}-single{b}")
         assert _same_bits(single, batched), f"sample {b}: the batched launch differs from the single one"
+    if (B, k) in NAN_BATCH:
+        clean = [t.cpu().numpy() for t in (V.view(B, k, N), U.view(B, k, -1), s.view(B, k), conv)]
+        V0b = V0.clone()
+        V0b[k + k // 2] = float("nan")                             # one row of sample 1
+        got = e.iterate("o", V0b, 1)
+        torch.cuda.synchronize()
+        Vb, Ub, sb, cb = got[0].view(B, k, N).cpu().numpy(), got[1].view(B, k, -1).cpu().numpy(), got[2].view(B, k).cpu().numpy(), got[3].cpu().numpy()
+        R.assert_all_nan(Vb[1], sb[1], cb[1], f"B={B} k={k}: the poisoned sample")
+        for b in range(B):
+            if b != 1:
+                assert _same_bits((Vb[b], Ub[b], sb[b], cb[b]), (clean[0][b], clean[1][b], clean[2][b], clean[3][b])), \
+                    f"B={B} k={k}: sample {b} changed because sample 1 held a NaN"
     del e
+
+
+# ------------------------------------------------------------------------------------------------------------ (e2) non-finite input
+@pytest.mark.parametrize("k,N", R.NF_SHAPES)
+def test_non_finite_w_is_all_nan_and_leaves_no_state(k, N):
+    """a NaN, +inf or -inf at W[0][0] or at W[k-1][N-1], or a whole row of NaN: V, s and conv are entirely NaN (exact: NaN masks), and the next call
+    on clean data with the SAME scratch returns the bits of a clean call on a fresh scratch"""
+    W, Vp = R.inputs(k, N, 2)
+    Wd, Vpd = torch.tensor(W, device=DEV), torch.tensor(Vp, device=DEV)
+    clean = R.gpu_orth(Wd, Vpd)
+    assert all(np.isfinite(a).all() for a in clean)
+    scratch = R.gpu_scratch(k, N, DEV)
+    for how in R.NF_POISONS:
+        R.assert_all_nan(*R.gpu_orth(R.poisoned(W, how), Vpd, scratch=scratch), f"k={k} N={N} {how}")
+        assert _same_bits(clean, R.gpu_orth(Wd, Vpd, scratch=scratch)), f"k={k} N={N}: the clean call after {how} on the same scratch differs"
+
+
+@pytest.mark.parametrize("k", R.NF_VPREV_K)
+def test_non_finite_vprev_only_touches_signs_and_conv(k):
+    """W finite, Vprev poisoned: s keeps the clean call's bits, every row of V is bitwise plus or minus the clean row, conv = (NaN, NaN)"""
+    W, Vp = R.inputs(k, R.NF_N, 2)
+    Wd = torch.tensor(W, device=DEV)
+    clean = R.gpu_orth(Wd, Vp)
+    for how in R.NF_POISONS:
+        if how != "nan-row":
+            R.assert_vprev_rule(R.gpu_orth(Wd, R.poisoned(Vp, how)), clean, f"k={k} Vprev {how}")
+
+
+@pytest.mark.parametrize("k,how", [(5, "nan-tail"), (65, "pinf-first")])
+def test_non_finite_w_in_place(k, how):
+    W, Vp = R.inputs(k, R.NF_N, 2)
+    R.assert_all_nan(*R.gpu_orth(R.poisoned(W, how), Vp, inplace=True), f"k={k} {how} in place")
+
+
+def _fp16_overflow_net(B, k):
+    """the smallest real engine, one fp16 linear op 16 -> 24 on 40 rows with weights of the order 8000: J^T J V passes 65504 in the fp16 cotangent,
+    so dpb_orth is handed inf.  Returns a stand-in for the PullbackUNet the loops are methods of, around a real Engine."""
+    import types
+    g = torch.Generator().manual_seed(6)
+    params = {"p.weight": (8192.0 * torch.randn(24, 16, generator=g)).clamp(-60000.0, 60000.0), "p.bias": torch.zeros(24)}
+    tape = NR.build_tape([NR.linear("o", "x", "p", 24)], params, torch.float16, DEV, 40, 16)
+    eng = NR.engine(tape, B, B * k)
+    return types.SimpleNamespace(engine=eng, max_rank=B * k, device=DEV, verbose=False, k_shard_group=False, _tap=lambda op, block_idx: "o")
+
+
+def test_fp16_overflow_raises_in_the_power_iterations():
+    """the stop rule of pullback.py on a real engine: an fp16 tangent that overflows must end the loops with DpbError naming the iteration (and, in
+    the batch form, the samples), not with a "converged" NaN basis"""
+    from diffusion_pullback_amd import lib as L
+    from diffusion_pullback_amd.pullback import PullbackUNet
+    k = 3
+    g = torch.Generator().manual_seed(7)
+    V0 = torch.linalg.qr(torch.randn(640, k, generator=g))[0].T.contiguous()
+    x = 1e-3 * torch.randn(2, 16, 40, 1, generator=g)
+    net = _fp16_overflow_net(1, k)
+    with pytest.raises(L.DpbError, match=r"iteration 0 are not finite"):
+        PullbackUNet._pullback(net, x[:1], 1.0, None, None, None, k, 1, 1, 6, 1e-3, V0)
+    del net
+    net = _fp16_overflow_net(2, k)
+    with pytest.raises(L.DpbError, match=r"iteration 0 are not finite for sample\(s\) \[0, 1\]"):
+        PullbackUNet.local_encoder_pullback_batch(net, x, 1.0, None, None, None, pca_rank=k, min_iter=1, max_iter=6, convergence_threshold=1e-3, V0=V0)
+    del net
 
 
 # ------------------------------------------------------------------------------------------------------------ (f) the A/B solver routes
@@ -185,6 +276,8 @@ import _orth_ref as R
 for k in {ks!r}:
     c = R.case(k, 1000, 2)
     R.check(*R.gpu_orth(c.W, c.Vprev), c, k, 1000, 2, {route!r})
+    R.assert_all_nan(*R.gpu_orth(R.poisoned(c.W, "nan-tail"), c.Vprev), (k, {route!r}))
+    print("ORTH-NAN", k, {route!r})
 """
 
 
@@ -201,6 +294,7 @@ def test_solver_routes_behind_the_switch():
             pytest.fail(f"DPB_EIG_PAR={par}: the child died on signal {-r.returncode}; nothing more is started\n{r.stderr[-2000:]}", pytrace=False)
         assert r.returncode == 0, r.stderr[-3000:]
         assert r.stdout.count("ORTH-ERR") == len(ks)
+        assert r.stdout.count("ORTH-NAN") == len(ks)              # and a NaN in W is all NaN out on the route (module docstring, non-finite input)
 
 
 # ------------------------------------------------------------------------------------------------------------ (g) argument checks

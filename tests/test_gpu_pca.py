@@ -159,6 +159,46 @@ def test_pca_lowrank_bitwise_reproducible():
         assert torch.equal(u1, u2) and torch.equal(s1, s2)
 
 
+def _raw(H, R, q, niter, scratch):
+    """dpb_pca_lowrank itself with the caller's scratch -> (return value, u, s)"""
+    import ctypes as C
+
+    from diffusion_pullback_amd import lib as L
+    lib = L.load()
+    n, d = H.shape
+    u = torch.empty(q, d, dtype=torch.float32, device=DEV)
+    s = torch.empty(q, dtype=torch.float32, device=DEV)
+    r = lib.dpb_pca_lowrank(H.data_ptr(), n, d, R.data_ptr(), q, niter, u.data_ptr(), s.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                            C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    return r, u, s
+
+
+@pytest.mark.parametrize("q", [5, 50, 128])
+def test_pca_lowrank_non_finite_input_is_all_nan_and_leaves_no_state(q):
+    """include/dpb.h: one NaN or inf anywhere in H or R -> u and s all NaN, return 0 (every factorisation is dpb_orth, whose rule this is); the next
+    clean call on the same scratch returns the bits of a clean call on a fresh scratch.  Exact: NaN masks and bit equality."""
+    from diffusion_pullback_amd import lib as L
+    n, d, niter = 300, 4100, 2
+    H = _synthetic(n, d, rank=160, seed=q)
+    R = torch.randn(n, q, generator=torch.Generator().manual_seed(2000 + q)).to(DEV)
+    need = int(L.load().dpb_pca_scratch_bytes(q, n, d))
+    fresh = lambda: torch.empty(need, dtype=torch.uint8, device=DEV)
+    r0, u0, s0 = _raw(H, R, q, niter, fresh())
+    assert r0 == 0 and torch.isfinite(u0).all() and torch.isfinite(s0).all()
+    scratch = fresh()
+    for what, where, val in [("H", (n - 1, d - 1), float("nan")), ("H", (7, 1234), float("inf")), ("R", (n // 2, q - 1), float("nan"))]:
+        Hb, Rb = H.clone(), R.clone()
+        (Hb if what == "H" else Rb)[where] = val
+        r, u, s = _raw(Hb, Rb, q, niter, scratch)
+        assert r == 0, (what, val, L.load().dpb_last_error())
+        assert torch.isnan(s).all(), (what, val, "s", s[:4].tolist())
+        assert torch.isnan(u).all(), (what, val, "u", int(torch.isnan(u).sum()), u.numel())
+        r, u, s = _raw(H, R, q, niter, scratch)
+        assert r == 0 and torch.equal(u.view(torch.int32), u0.view(torch.int32)) and torch.equal(s.view(torch.int32), s0.view(torch.int32)), \
+            (what, val, "the clean call on the same scratch differs")
+
+
 def test_inv_jac_zt_2d_u_equals_per_column_calls():
     g = load_golden("pca_zt_tiny.pt")
     unet, _ = _bound(g, max_rank=3)

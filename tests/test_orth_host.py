@@ -1,7 +1,8 @@
 """CPU half of the dpb_orth pins (tests/test_gpu_orth.py): the float64 restatement of the method (tests/_orth_ref.py) must meet every bound the GPU
 tests hold the kernels to, on every accuracy case; each float32 mutant must miss the vec bound 16-fold -- the standing proof that the bars have
 teeth; the input conditions the bars rest on are asserted, so a seed change cannot silently void a check; and the exact cases' closed forms are
-checked against the restatement."""
+checked against the restatement.  Non-finite input: the restatement meets the rule of include/dpb.h on every case the GPU tests run, through the same
+two assertions, and the three traits the kernels had before the rule are kept as mutants that fail them."""
 import numpy as np
 import pytest
 
@@ -121,6 +122,66 @@ def test_restatement_near_rank_deficiency(k, N):
     V, s, conv = R.restate(c.W, c.Vprev)
     assert np.isfinite(V).all() and np.isfinite(s).all() and (s >= 0).all()
     R.check(V, s, conv, c, k, N, 2, "deficient")
+
+
+# ------------------------------------------------------------------------------------------------------------ non-finite input (include/dpb.h)
+@pytest.mark.parametrize("how", R.NF_POISONS)
+@pytest.mark.parametrize("k,N", R.NF_SHAPES)
+def test_restatement_non_finite_w_is_all_nan(k, N, how):
+    """every case of tests/test_gpu_orth.py::test_non_finite_w_is_all_nan_and_leaves_no_state, same assertion"""
+    W, Vp = R.inputs(k, N, 2)
+    Wb = R.poisoned(W, how)
+    assert (~np.isfinite(Wb)).sum() == (N if how == "nan-row" else 1)
+    R.assert_all_nan(*R.restate(Wb, Vp), f"k={k} N={N} {how}")
+
+
+@pytest.mark.parametrize("how", [h for h in R.NF_POISONS if h != "nan-row"])
+@pytest.mark.parametrize("k", R.NF_VPREV_K)
+def test_restatement_non_finite_vprev_only(k, how):
+    W, Vp = R.inputs(k, R.NF_N, 2)
+    R.assert_vprev_rule(R.restate(W, R.poisoned(Vp, how)), R.restate(W, Vp), f"k={k} Vprev {how}")
+
+
+@pytest.mark.parametrize("mutant,symptom", [("rank_plain", "s"), ("clamp", "s"), ("fmax", "conv")])
+@pytest.mark.parametrize("k", [5, 17, 128])
+def test_non_finite_mutants_fail_the_gpu_assertions(k, mutant, symptom):
+    """the method without the Gram-diagonal detection and with ONE of the three traits it had: each fails assert_all_nan, the assertion of the GPU
+    tests, in its own way -- the plain ranking leaves slots of `order` unwritten (not a permutation) and s comes back finite through them, the
+    lam > 0 ? lam : 0 clamp returns s == 0 beside a NaN V, the NaN-dropping maximum returns conv[1] == 0 beside a NaN V"""
+    W, Vp = R.inputs(k, R.NF_N, 2)
+    Wb = R.poisoned(W, "nan-first")
+    V, s, conv = R.restate(Wb, Vp, mutant=mutant)
+    print(f"k={k} {mutant}: s[:3] {s[:3]} conv {conv} NaN in V {int(np.isnan(V).sum())} / {V.size}")
+    with pytest.raises(AssertionError) as err:
+        R.assert_all_nan(V, s, conv, mutant)
+    assert f"'{symptom}'" in str(err.value), str(err.value)[:200]
+    lam = np.full(k, np.nan)
+    if mutant == "rank_plain":
+        order = R.rank_scatter(lam, total=False)
+        assert sorted(order) != list(range(k)) and (order == R.POISON).sum() == k - 1 and np.isfinite(s[1:]).all()
+    elif mutant == "clamp":
+        assert not s.any() and np.isnan(V).all()
+    else:
+        assert conv[1] == 0 and np.isnan(conv[0]) and np.isnan(V).all()
+    assert sorted(R.rank_scatter(lam)) == list(range(k))         # and the total order scatters a permutation: index order among NaNs
+    assert list(R.rank_scatter(lam)) == list(range(k))
+
+
+def test_rank_scatter_is_the_stable_descending_order_on_numbers_and_nan_first():
+    rng = np.random.default_rng(11)
+    for k in (1, 2, 5, 16, 33):
+        lam = rng.integers(0, 4, k).astype(np.float64)           # ties
+        assert list(R.rank_scatter(lam)) == list(np.argsort(-lam, kind="stable")) == list(R.rank_scatter(lam, total=False))
+        lam[rng.integers(0, k)] = np.nan
+        order = R.rank_scatter(lam)
+        assert sorted(order) == list(range(k)) and np.isnan(lam[order[0]])
+        rest = lam[order[1:]]
+        assert (np.diff(rest) <= 0).all()
+
+
+def test_max_nan_keeps_what_python_max_drops():
+    assert np.isnan(R.max_nan(np.float32(0), np.float32(np.nan))) and max(np.float32(0), np.float32(np.nan)) == 0
+    assert R.max_nan(np.float32(0), np.float32(2)) == 2
 
 
 # ------------------------------------------------------------------------------------------------------------ the measures themselves
