@@ -1675,6 +1675,36 @@ int dpb_flag_mean_finish(const float* X, const double* Ghat, float* Y, float* we
   return launch_flag_mean_finish(X, Ghat, B, k, N, r, max_iter, Y, weight, theta, Ct, info, scratch, scratch_bytes, (hipStream_t)stream);
 }
 
+// the weighted flag mean and the flag median (geometry.flag_mean(weights=) / flag_median): flagmean.hip
+size_t dpb_flag_median_scratch_bytes(int B, int k, int64_t N, int r, int max_iter) { return flag_median_scratch_bytes(B, k, N, r, max_iter, true); }
+size_t dpb_flag_median_solver_bytes(int B, int k, int r, int max_iter) { return flag_median_scratch_bytes(B, k, 0, r, max_iter, false); }
+
+int dpb_flag_median_init(const float* X, const double* Ghat, const double* member_weight, int B, int k, int64_t N, int r, uint64_t seed, int max_iter,
+                         void* scratch, size_t scratch_bytes, void* stream) {
+  if (!scratch || (X == nullptr) == (Ghat == nullptr)) return fail("dpb_flag_median_init: null scratch, or not exactly one of X and Ghat given");
+  return launch_flag_median_init(X, Ghat, member_weight, B, k, N, r, seed, max_iter, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int dpb_flag_median_iterate(int n_iter, double tol, const double* Ghat, int B, int k, int64_t N, int r, int max_iter, void* scratch, size_t scratch_bytes,
+                            void* stream) {
+  if (!scratch) return fail("dpb_flag_median_iterate: null argument");
+  return launch_flag_median_iterate(Ghat, B, k, N, r, max_iter, n_iter, tol, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int dpb_flag_median_round(double eps, double tol, int update, const double* Ghat, int B, int k, int64_t N, int r, int max_iter, void* scratch,
+                          size_t scratch_bytes, void* stream) {
+  if (!scratch) return fail("dpb_flag_median_round: null argument");
+  return launch_flag_median_round(Ghat, B, k, N, r, max_iter, eps, tol, update, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int dpb_flag_median_finish(const float* X, const double* Ghat, float* Y, float* weight, float* theta, double* Ct, double* member, double* info, int B, int k,
+                           int64_t N, int r, int max_iter, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!weight || !theta || !Ct || !member || !info || !scratch) return fail("dpb_flag_median_finish: null argument");
+  if ((X == nullptr) != (Y == nullptr) || (X == nullptr) == (Ghat == nullptr))
+    return fail("dpb_flag_median_finish: X and Y go together, and exactly one of X and Ghat is given");
+  return launch_flag_median_finish(X, Ghat, B, k, N, r, max_iter, Y, weight, theta, Ct, member, info, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
 // the chordal affinity of two stacks of subspaces, and flag k-means on it (geometry.flag_affinity / flag_kmeans): flagkmeans.hip
 size_t dpb_flag_affinity_scratch_bytes(int B, int k, int C, int r, int64_t N) { return flag_affinity_scratch_bytes(B, k, C, r, N); }
 

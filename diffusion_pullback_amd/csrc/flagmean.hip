@@ -684,4 +684,343 @@ int launch_flag_mean_finish(const float* X, const double* ghat, long B, int k, l
   return 0;
 }
 
+// ============================================================================================================ the weighted mean and the flag median
+// Weighted flag mean: P_w = (1/B) sum_i what_i Q_i^T Q_i, what of mean 1.  With D = diag(sqrt(what_i) (x) 1_k) the rows D Q have the Gram D Ghat D, so the
+// solver above runs unchanged on W = D Ghat D Z -- the scale meets the Z operand before its MFMAs and the output row as it is stored; no scaled copy of Ghat
+// exists -- and Y = C~ D Q: the coefficients on Q are C^T = D C~^T, C Ghat C^T = I.  The affinities of ALL members (weight 0 included) come from the
+// unweighted product M^T = Ghat C^T: a_i = ||M[i-rows]||_F^2.
+// Flag median (Mankovich et al., CVPR 2022): argmin_Y sum_i p_i d_i, d_i = sqrt(r - a_i), by iteratively reweighted flag means, w_i = p_i / max(d_i, eps)
+// normalised to mean 1; a round = the inner solve (warm-started: the block Z stays), the Rayleigh-Ritz step of finish, M, a, d, the smoothed objective
+// J = sum_i p_i phi(d_i) (phi(d) = d above eps, d^2 / (2 eps) + eps / 2 below: what the clamped weight descends) and the new table.
+struct FmedHead {         // the first 64 bytes of a median scratch block (documented in dpb.h: the caller's one read per round or chunk)
+  int round;              // objective evaluations so far
+  int done, iters;        // the inner solve's status (FmCtl), as of the last call
+  int n_degenerate;
+  int converged;          // J_prev - J <= tol J_prev was met: the table was not moved
+  int pad;
+  double J, Jprev, res;
+  double pad1, pad2;
+};
+static_assert(sizeof(FmedHead) == 64, "FmedHead is documented as 64 bytes");
+
+// fm_load's operands and the four table entries sw [R] = sqrt(what_{row / k}) of the lane's rows of Z, read through L2 beside them.  The loads stay as
+// fm_load issues them -- nothing waits on them where they are issued -- and the scale meets the Z operand in fmw_mma, just before the MFMAs that use it
+template <int KT>
+struct FmwOperands {
+  double a[2][4];
+  double b[4][KT];
+  double s[4];
+};
+
+template <int KT>
+__device__ __forceinline__ void fmw_load(FmwOperands<KT>& o, const double* __restrict__ G, const double* __restrict__ Z, const double* __restrict__ sw, int c,
+                                         int c_hi, int i0, int j, int g, int R, int m, bool vec) {
+  const int col = 16 * c + 4 * g;
+  const bool live = c < c_hi;
+#pragma unroll
+  for (int tl = 0; tl < 2; ++tl) {
+    const int row = i0 + 16 * tl + j;
+    const bool ok = live && row < R && col < R;
+    if (ok && vec) {
+      const geom_d4 v = *reinterpret_cast<const geom_d4*>(G + (long)row * R + col);
+      o.a[tl][0] = v[0]; o.a[tl][1] = v[1]; o.a[tl][2] = v[2]; o.a[tl][3] = v[3];
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) o.a[tl][e] = (ok && col + e < R) ? G[(long)row * R + col + e] : 0.0;
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int zr = col + e;
+    o.s[e] = (live && zr < R) ? sw[zr] : 0.0;
+#pragma unroll
+    for (int n = 0; n < KT; ++n) o.b[e][n] = (live && zr < R && 16 * n + j < m) ? Z[(long)zr * m + 16 * n + j] : 0.0;
+  }
+}
+
+template <int KT>
+__device__ __forceinline__ void fmw_mma(geom_d4 (&acc)[2][KT], const FmwOperands<KT>& o) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e)
+#pragma unroll
+    for (int n = 0; n < KT; ++n) {
+      const double b = o.b[e][n] * o.s[e];
+      acc[0][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a[0][e], b, acc[0][n], 0, 0, 0);
+      acc[1][n] = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a[1][e], b, acc[1][n], 0, 0, 0);
+    }
+}
+
+// Out = D Ghat D Z: fm_product_kernel's pass, cut points and wave-order sum, with the two scales (sw all ones: its bits)
+template <int KT, int NW>
+__global__ __launch_bounds__(NW * 64) void fmw_product_kernel(const double* __restrict__ G, const double* __restrict__ Z, const double* __restrict__ sw,
+                                                              double* __restrict__ Out, int R, int m, const FmCtl* ctl, int force) {
+  if (!force && ctl->done) return;
+  __shared__ double red[NW][2][KT][4][64];
+  static_assert(sizeof(double) * NW * 2 * KT * 4 * 64 <= 160 * 1024, "fmw_product_kernel exceeds the gfx950 LDS");
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, j = lane & 15, g = lane >> 4;
+  const int i0 = blockIdx.x * 32;
+  const int chunks = (R + 15) / 16, q = (chunks + NW - 1) / NW;
+  const int c_lo = wave * q, c_hi = c_lo + q < chunks ? c_lo + q : chunks;
+  const bool vec = (R & 3) == 0;
+  geom_d4 acc[2][KT];
+#pragma unroll
+  for (int tl = 0; tl < 2; ++tl)
+#pragma unroll
+    for (int n = 0; n < KT; ++n) acc[tl][n] = geom_d4{0.0, 0.0, 0.0, 0.0};
+  FmwOperands<KT> o0, o1;
+  fmw_load<KT>(o0, G, Z, sw, c_lo, c_hi, i0, j, g, R, m, vec);
+  for (int c = c_lo; c < c_hi; c += 2) {
+    fmw_load<KT>(o1, G, Z, sw, c + 1, c_hi, i0, j, g, R, m, vec);
+    fmw_mma<KT>(acc, o0);
+    fmw_load<KT>(o0, G, Z, sw, c + 2, c_hi, i0, j, g, R, m, vec);
+    fmw_mma<KT>(acc, o1);
+  }
+#pragma unroll
+  for (int tl = 0; tl < 2; ++tl)
+#pragma unroll
+    for (int n = 0; n < KT; ++n)
+#pragma unroll
+      for (int x = 0; x < 4; ++x) red[wave][tl][n][x][lane] = acc[tl][n][x];
+  __syncthreads();
+  for (int e = t; e < 2 * KT * 4 * 64; e += NW * 64) {
+    const int ln = e & 63, x = (e >> 6) & 3, n = (e >> 8) % KT, tl = (e >> 8) / KT;
+    double v = red[0][tl][n][x][ln];
+#pragma unroll
+    for (int w = 1; w < NW; ++w) v += red[w][tl][n][x][ln];
+    const int row = i0 + 16 * tl + (ln >> 4) + 4 * x, col = 16 * n + (ln & 15);
+    if (row < R && col < m) Out[(long)row * m + col] = v * sw[row];
+  }
+}
+
+// one workgroup: the prior p (given weights w [B] scaled to mean 1, the sum in index order; w == nullptr: all ones), what = p, the table and the head.
+// A negative or non-finite weight, or a zero sum, gives a NaN table: the solver then ends with the degenerate status
+__global__ __launch_bounds__(256) void fmed_init_kernel(const double* w, const double* G, double* prior, double* what, double* sw, FmedHead* head, int B, int k,
+                                                        long R) {
+  __shared__ double tot;
+  __shared__ int nd;
+  const int t = threadIdx.x;
+  if (t == 0) {
+    double s = 0.0;
+    int n = 0;
+    for (int i = 0; i < B; ++i) {
+      s += w ? w[i] : 1.0;
+      const double d = G[((long)i * k) * (R + 1)];
+      if (d != d) n += 1;
+    }
+    tot = s; nd = n;
+  }
+  __syncthreads();
+  for (int i = t; i < B; i += 256) {
+    const double wi = w ? w[i] : 1.0;
+    const double p = w ? ((wi >= 0.0 && tot > 0.0) ? wi * (double)B / tot : nan64()) : 1.0;
+    prior[i] = p; what[i] = p;
+  }
+  for (long e = t; e < R; e += 256) {
+    const double wi = w ? w[e / k] : 1.0;
+    const double p = w ? ((wi >= 0.0 && tot > 0.0) ? wi * (double)B / tot : nan64()) : 1.0;
+    sw[e] = sqrt(p);
+  }
+  if (t == 0) {
+    head->round = 0; head->done = 0; head->iters = 0; head->n_degenerate = nd; head->converged = 0; head->pad = 0;
+    head->J = 0.0; head->Jprev = 0.0; head->res = 0.0; head->pad1 = 0.0; head->pad2 = 0.0;
+  }
+}
+
+// the inner solve's status copied to the head (the caller's read)
+__global__ void fmed_sync_kernel(const FmCtl* ctl, FmedHead* head) {
+  head->done = ctl->done; head->iters = ctl->iters; head->res = ctl->res;
+}
+
+// Ct [R][r] rows scaled by the table: C^T = D C~^T
+__global__ __launch_bounds__(256) void fmed_scale_kernel(double* Ct, const double* sw, long R, int r) {
+  const long e = (long)blockIdx.x * 256 + threadIdx.x;
+  if (e < R * r) Ct[e] *= sw[e / r];
+}
+
+// block i (one wave): a_i = ||M[i-rows]||_F^2 -- lane-strided squares in element order, then the xor butterfly -- and d_i = sqrt(max(r - a_i, 0))
+__global__ __launch_bounds__(64) void fmed_affinity_kernel(const double* Mt, double* aff, double* dist, int k, int r) {
+  const int i = blockIdx.x, lane = threadIdx.x;
+  const double* Mb = Mt + (long)i * k * r;
+  double sq = 0.0;
+  for (int e = lane; e < k * r; e += 64) { const double v = Mb[e]; sq += v * v; }
+  for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o, 64);
+  if (lane == 0) {
+    const double x = (double)r - sq;
+    aff[i] = sq;
+    dist[i] = x != x ? nan64() : (x > 0.0 ? sqrt(x) : 0.0);
+  }
+}
+
+// one workgroup, the step of a round: J = sum_i p_i phi_eps(d_i) in index order; converged when round >= 1 and J_prev - J <= tol J_prev; otherwise, with
+// update, the new table what_i = w_i B / sum w, w_i = p_i / max(d_i, eps) (the sum in index order), and the inner solve's status cleared -- the block stays
+__global__ __launch_bounds__(256) void fmed_step_kernel(const double* prior, const double* dist, double* what, double* sw, FmedHead* head, FmCtl* ctl, int B, int k,
+                                                        long R, double eps, double tol, int update) {
+  __shared__ double tot;
+  __shared__ int move;
+  const int t = threadIdx.x;
+  if (t == 0) {
+    double J = 0.0, s = 0.0;
+    for (int i = 0; i < B; ++i) {
+      const double d = dist[i], p = prior[i];
+      J += p * (d >= eps ? d : d * d / (2.0 * eps) + 0.5 * eps);          // (a NaN distance: the else branch, a NaN)
+      s += p / (d > eps ? d : eps);
+    }
+    const double Jp = head->J;
+    const int conv = head->round >= 1 && (Jp - J <= tol * Jp) ? 1 : 0;
+    head->Jprev = head->round >= 1 ? Jp : J;
+    head->J = J;
+    head->round += 1;
+    head->converged = conv;
+    head->done = ctl->done; head->iters = ctl->iters; head->res = ctl->res;
+    move = (update && !conv && J == J && ctl->done != 2) ? 1 : 0;
+    tot = s;
+  }
+  __syncthreads();
+  if (!move) return;
+  for (int i = t; i < B; i += 256) { const double d = dist[i]; what[i] = prior[i] / (d > eps ? d : eps) * (double)B / tot; }
+  for (long e = t; e < R; e += 256) { const double d = dist[e / k]; sw[e] = sqrt(prior[e / k] / (d > eps ? d : eps) * (double)B / tot); }
+  if (t == 0) { ctl->done = 0; ctl->iters = 0; ctl->res = 0.0; }
+}
+
+// member [3][B] = affinity, distance, member weight
+__global__ __launch_bounds__(256) void fmed_member_kernel(const double* aff, const double* dist, const double* what, double* member, int B) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < B) { member[i] = aff[i]; member[B + i] = dist[i]; member[2 * (long)B + i] = what[i]; }
+}
+
+namespace {
+struct FmedLayout {
+  size_t head = 0, prior = 0, what = 0, aff = 0, dist = 0, sw = 0, wtmp = 0, itmp = 0, fm = 0, total = 0;
+  FmLayout l;
+};
+bool fmed_layout(long B, int k, long N, int r, long max_iter, bool own, FmedLayout& ml) {
+  if (!fm_layout(B, k, N, r, max_iter, own, ml.l)) return false;
+  ScratchCarver s;
+  const size_t bd = (size_t)B * sizeof(double);
+  ml.head = s.take(sizeof(FmedHead));
+  ml.prior = s.take(bd); ml.what = s.take(bd); ml.aff = s.take(bd); ml.dist = s.take(bd);
+  ml.sw = s.take((size_t)B * k * sizeof(double));
+  ml.wtmp = s.take(64 * sizeof(float));
+  ml.itmp = s.take((72 + (size_t)B) * sizeof(double));
+  ml.fm = s.off;
+  ml.total = s.off + ml.l.total;
+  return true;
+}
+struct FmedPtrs {
+  FmedHead* head; double *prior, *what, *aff, *dist, *sw, *itmp; float* wtmp;
+  FmPtrs p;
+};
+FmedPtrs fmed_ptrs(void* scratch, const FmedLayout& ml, const double* ghat) {
+  char* b = (char*)scratch;
+  FmedPtrs q;
+  q.head = (FmedHead*)(b + ml.head); q.prior = (double*)(b + ml.prior); q.what = (double*)(b + ml.what); q.aff = (double*)(b + ml.aff);
+  q.dist = (double*)(b + ml.dist); q.sw = (double*)(b + ml.sw); q.wtmp = (float*)(b + ml.wtmp); q.itmp = (double*)(b + ml.itmp);
+  q.p = fm_ptrs(b + ml.fm, ml.l, ghat);
+  return q;
+}
+int fmed_check(const char* who, long B, int k, long N, int r, long max_iter, const double* ghat, const void* scratch, size_t scratch_bytes, FmedLayout& ml) {
+  if (!fmed_layout(B, k, N, r, max_iter, ghat == nullptr, ml)) {
+    set_error("%s: B=%ld outside [1,65535], k=%d outside [1,%d], N=%ld < k, B k above 2^20, r=%d outside [1,min(%d,B k,N)] or max_iter=%ld outside [0,2^24]",
+              who, B, k, FRECHET_MAX_RANK, N, r, FLAG_MEAN_MAX_RANK, max_iter);
+    return -1;
+  }
+  if (ghat && (uintptr_t)ghat % 32) { set_error("%s: Ghat must be 32-byte aligned", who); return -1; }
+  return ghat ? check_scratch(who, scratch, scratch_bytes, ml.total, "dpb_flag_median_solver_bytes(%ld, %d, %d, %ld)", B, k, r, max_iter)
+              : check_scratch(who, scratch, scratch_bytes, ml.total, "dpb_flag_median_scratch_bytes(%ld, %d, %ld, %d, %ld)", B, k, N, r, max_iter);
+}
+
+void fmw_product(const FmedPtrs& q, const FmLayout& l, int R, int force, hipStream_t st) {
+  const dim3 grid((R + 31) / 32);
+  const FmPtrs& p = q.p;
+  if (g_fm_waves == 4) DPB_BY_TILES(l.m, DPB_LAUNCH((fmw_product_kernel<KT, 4>), grid, dim3(256), 0, st, p.G, p.Z, q.sw, p.Wb, R, l.m, p.ctl, force));
+  else DPB_BY_TILES(l.m, DPB_LAUNCH((fmw_product_kernel<KT, 8>), grid, dim3(512), 0, st, p.G, p.Z, q.sw, p.Wb, R, l.m, p.ctl, force));
+}
+
+// the Rayleigh-Ritz step of the block as it stands under the weighted projector (fm_finish_head_kernel on W = D Ghat D Z), C^T = D Z Sc into Ct [R][r],
+// M^T = Ghat C^T (the UNWEIGHTED product: a member of weight 0 keeps its affinity and angles) into Z1, then a and d of every member
+void fmed_ritz(const FmedPtrs& q, const FmLayout& l, int R, int r, int B, int k, double* Ct, float* weight, double* info, hipStream_t st) {
+  const FmPtrs& p = q.p;
+  const dim3 gc(l.nch), one(1), t256(256), grid((R + 31) / 32);
+  fmw_product(q, l, R, 1, st);
+  DPB_LAUNCH(fm_gram_kernel, gc, t256, 0, st, p.Z, p.Wb, p.part, R, l.m, 1, p.ctl, 1);
+  DPB_BY_RANK(l.m, DPB_LAUNCH((fm_finish_head_kernel<KM, NT>), one, dim3(NT), 0, st, p.part, p.G, p.S, weight, info, p.ctl, l.nch, l.m, r, B, k, (long)R));
+  DPB_LAUNCH(fm_rowmul_kernel, gc, t256, 0, st, p.Z, p.S, Ct, R, l.m, r, p.ctl, 1);
+  DPB_LAUNCH(fmed_scale_kernel, dim3((unsigned)(((long)R * r + 255) / 256)), t256, 0, st, Ct, q.sw, (long)R, r);
+  if (g_fm_waves == 4) DPB_BY_TILES(r, DPB_LAUNCH((fm_product_kernel<KT, 4>), grid, dim3(256), 0, st, p.G, Ct, p.Z1, R, r, p.ctl, 1));
+  else DPB_BY_TILES(r, DPB_LAUNCH((fm_product_kernel<KT, 8>), grid, dim3(512), 0, st, p.G, Ct, p.Z1, R, r, p.ctl, 1));
+  DPB_LAUNCH(fmed_affinity_kernel, dim3((unsigned)B), dim3(64), 0, st, p.Z1, q.aff, q.dist, k, r);
+}
+}  // namespace
+
+size_t flag_median_scratch_bytes(long B, int k, long N, int r, long max_iter, bool own) {
+  FmedLayout ml;
+  return fmed_layout(B, k, N, r, max_iter, own, ml) ? ml.total : 0;
+}
+
+int launch_flag_median_init(const float* X, const double* ghat, const double* member_weight, long B, int k, long N, int r, unsigned long long seed, long max_iter,
+                            void* scratch, size_t scratch_bytes, hipStream_t st) {
+  FmedLayout ml;
+  if (fmed_check("dpb_flag_median_init", B, k, N, r, max_iter, ghat, scratch, scratch_bytes, ml) != 0) return -1;
+  const FmedPtrs q = fmed_ptrs(scratch, ml, ghat);
+  // the flag mean's own init on the embedded block: Ghat (or the caller's), the start block, the status
+  if (launch_flag_mean_init(X, ghat, B, k, N, r, seed, max_iter, (char*)scratch + ml.fm, ml.l.total, st) != 0) return -1;
+  DPB_LAUNCH(fmed_init_kernel, dim3(1), dim3(256), 0, st, member_weight, q.p.G, q.prior, q.what, q.sw, q.head, (int)B, k, (long)(B * k));
+  DPB_CHECK(hipGetLastError());
+  return 0;
+}
+
+int launch_flag_median_iterate(const double* ghat, long B, int k, long N, int r, long max_iter, int n_iter, double tol, void* scratch, size_t scratch_bytes,
+                               hipStream_t st) {
+  FmedLayout ml;
+  if (fmed_check("dpb_flag_median_iterate", B, k, N, r, max_iter, ghat, scratch, scratch_bytes, ml) != 0) return -1;
+  if (n_iter < 0 || !(tol >= 0.0)) { set_error("dpb_flag_median_iterate: n_iter=%d < 0 or tol=%g < 0", n_iter, tol); return -1; }
+  const FmedPtrs q = fmed_ptrs(scratch, ml, ghat);
+  const FmPtrs& p = q.p;
+  const FmLayout& l = ml.l;
+  const int R = (int)(B * k);
+  const dim3 gc(l.nch), one(1), t256(256);
+  for (int it = 0; it < n_iter; ++it) {                   // launch_flag_mean_iterate's iteration with the weighted product
+    fmw_product(q, l, R, 0, st);
+    DPB_LAUNCH(fm_gram_kernel, gc, t256, 0, st, p.Z, p.Wb, p.part, R, l.m, 1, p.ctl, 0);
+    DPB_BY_RANK(l.m, DPB_LAUNCH((fm_head_kernel<KM, NT>), one, dim3(NT), 0, st, p.part, p.S, p.lam, p.A, p.ctl, l.nch, l.m, max_iter));
+    DPB_LAUNCH(fm_move_kernel, gc, t256, 0, st, p.Z, p.Wb, p.S, p.A, p.lam, p.Z1, p.respart, R, l.m, p.ctl);
+    fm_orth_pass(p, l, p.Z1, p.Z, R, r, tol, 1, st);
+  }
+  DPB_LAUNCH(fmed_sync_kernel, one, one, 0, st, p.ctl, q.head);
+  DPB_CHECK(hipGetLastError());
+  return 0;
+}
+
+int launch_flag_median_round(const double* ghat, long B, int k, long N, int r, long max_iter, double eps, double tol, int update, void* scratch,
+                             size_t scratch_bytes, hipStream_t st) {
+  FmedLayout ml;
+  if (fmed_check("dpb_flag_median_round", B, k, N, r, max_iter, ghat, scratch, scratch_bytes, ml) != 0) return -1;
+  if (r > k) { set_error("dpb_flag_median_round: r=%d outside [1,k=%d]: the distance sqrt(r - a) is defined for r <= k only", r, k); return -1; }
+  if (!(eps > 0.0) || !(tol >= 0.0)) { set_error("dpb_flag_median_round: eps=%g <= 0 or tol=%g < 0", eps, tol); return -1; }
+  const FmedPtrs q = fmed_ptrs(scratch, ml, ghat);
+  const int R = (int)(B * k);
+  fmed_ritz(q, ml.l, R, r, (int)B, k, q.p.Wb, q.wtmp, q.itmp, st);       // (Wb is free once the head has run: the coefficients take it)
+  DPB_LAUNCH(fmed_step_kernel, dim3(1), dim3(256), 0, st, q.prior, q.dist, q.what, q.sw, q.head, q.p.ctl, (int)B, k, (long)R, eps, tol, update ? 1 : 0);
+  DPB_CHECK(hipGetLastError());
+  return 0;
+}
+
+int launch_flag_median_finish(const float* X, const double* ghat, long B, int k, long N, int r, long max_iter, float* Y, float* weight, float* theta, double* Ct,
+                              double* member, double* info, void* scratch, size_t scratch_bytes, hipStream_t st) {
+  FmedLayout ml;
+  if (fmed_check("dpb_flag_median_finish", B, k, N, r, max_iter, ghat, scratch, scratch_bytes, ml) != 0) return -1;
+  const FmedPtrs q = fmed_ptrs(scratch, ml, ghat);
+  const FmPtrs& p = q.p;
+  const int R = (int)(B * k), nb = (int)B;
+  const dim3 gb((unsigned)B), one(1), t256(256);
+  fmed_ritz(q, ml.l, R, r, nb, k, Ct, weight, info, st);
+  DPB_LAUNCH(fmed_member_kernel, dim3((unsigned)((B + 255) / 256)), t256, 0, st, q.aff, q.dist, q.what, member, nb);
+  DPB_LAUNCH(fm_sign_kernel, one, t256, 0, st, Ct, p.sgn, (long)R, r);
+  DPB_LAUNCH(fm_coef_kernel, gb, t256, 0, st, Ct, p.Z1, p.sgn, X ? p.W : nullptr, p.G, p.Wb, k, r, (long)R);
+  { const int kr = k > r ? k : r; DPB_BY_RANK(kr, DPB_LAUNCH((fm_theta_kernel<KM, NT>), gb, dim3(NT), 0, st, p.Z1, theta, k, r)); }
+  if (X && launch_coef_stream(X, p.Wb, Y, R, r, N, st) != 0) return -1;
+  DPB_CHECK(hipGetLastError());
+  return 0;
+}
+
 }  // namespace dpb

@@ -426,6 +426,17 @@ int launch_flag_mean_iterate(const double* ghat, long B, int k, long N, int r, l
                              hipStream_t st);
 int launch_flag_mean_finish(const float* X, const double* ghat, long B, int k, long N, int r, long max_iter, float* Y, float* weight, float* theta, double* Ct,
                             double* info, void* scratch, size_t scratch_bytes, hipStream_t st);
+// the weighted flag mean (zero rounds) and the flag median by iteratively reweighted flag means (flagmean.hip): the same solver on D Ghat D, a round
+// per reweighting; member_weight [B] fp64 on the device or nullptr (uniform); member [3][B]: affinity, distance, member weight
+size_t flag_median_scratch_bytes(long B, int k, long N, int r, long max_iter, bool own);   // 0 when invalid
+int launch_flag_median_init(const float* X, const double* ghat, const double* member_weight, long B, int k, long N, int r, unsigned long long seed, long max_iter,
+                            void* scratch, size_t scratch_bytes, hipStream_t st);
+int launch_flag_median_iterate(const double* ghat, long B, int k, long N, int r, long max_iter, int n_iter, double tol, void* scratch, size_t scratch_bytes,
+                               hipStream_t st);
+int launch_flag_median_round(const double* ghat, long B, int k, long N, int r, long max_iter, double eps, double tol, int update, void* scratch,
+                             size_t scratch_bytes, hipStream_t st);
+int launch_flag_median_finish(const float* X, const double* ghat, long B, int k, long N, int r, long max_iter, float* Y, float* weight, float* theta, double* Ct,
+                              double* member, double* info, void* scratch, size_t scratch_bytes, hipStream_t st);
 
 // ---------------------------------------------------------------- flag k-means and the chordal affinity of two stacks (flagkmeans.hip): Lloyd's
 // algorithm with flag-mean centres on coefficients against the whitened Gram; the caller owns the rounds and runs the flag-mean solver per cluster

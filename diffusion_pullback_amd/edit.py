@@ -920,19 +920,24 @@ class EditUncondDiffusion(_EditBase):
         return self._edit_along_global_basis(idx, op, block_idx, vis_num, pcs, pca_rank, h_t, frechet_mean_space, local_projection, basis,
                                              basis if frechet_mean_space == "h" else None, dict(basis=basis, pcs=pcs, names=[], info=info))
 
-    def global_flag_mean_paths(self, op="mid", block_idx=0, pca_rank=50, num_local_basis=100, flag_mean_space="x", h_t=None, flag_rank=None):
+    def global_flag_mean_paths(self, op="mid", block_idx=0, pca_rank=50, num_local_basis=100, flag_mean_space="x", h_t=None, flag_rank=None,
+                               flag_mean_kind="mean"):
         """(basis file, info file) of the flag-mean global basis, laid out as global_frechet_mean_paths: u- (space h) or v- (space x) +
-        <h_t>T-<op>-block_<b>-seed_<seed>-num_local_basis_<n>-rank_<r>.pt holds [N, r] columns"""
+        <h_t>T-<op>-block_<b>-seed_<seed>-num_local_basis_<n>-rank_<r>.pt holds [N, r] columns; flag_mean_kind "median": the same names with -median
+        appended to the stem"""
+        if flag_mean_kind not in ("mean", "median"):
+            raise ValueError(f"flag_mean_kind must be 'mean' (geometry.flag_mean) or 'median' (geometry.flag_median), got {flag_mean_kind!r}")
         h_t = self.h_t if h_t is None else h_t
         r = pca_rank if not flag_rank else flag_rank
         save_dir = os.path.join(self.input_root, f"global_flag_mean_uncond-model_{self.model_name}-dataset_{self.dataset_name}-num_steps_{self.for_steps}-pca_rank_{pca_rank}")
-        name = f"{h_t}T-{op}-block_{block_idx}-seed_{self.seed}-num_local_basis_{num_local_basis}-rank_{r}"
+        name = f"{h_t}T-{op}-block_{block_idx}-seed_{self.seed}-num_local_basis_{num_local_basis}-rank_{r}" + ("-median" if flag_mean_kind == "median" else "")
         tag = "u" if flag_mean_space == "h" else "v"
         return os.path.join(save_dir, f"{tag}-{name}.pt"), os.path.join(save_dir, f"info-{tag}-{name}.pt")
 
     @torch.no_grad()
     def run_edit_global_flag_mean_zt(self, idx, op="mid", block_idx=0, vis_num=4, vis_num_pc=None, vis_pc_list=None, pca_rank=50, num_local_basis=100,
-                                     local_projection=True, flag_mean_space="x", h_t=None, flag_rank=None):
+                                     local_projection=True, flag_mean_space="x", h_t=None, flag_rank=None, flag_mean_kind="mean", flag_median_eps=1e-5,
+                                     flag_median_max_rounds=50):
         """Edit sample idx along the rows of the third GLOBAL basis: the flag (extrinsic) mean of num_local_basis local tangent spaces at h_t --
         the top flag_rank eigenvectors of their mean projector (geometry.flag_mean; flag_mean_space "x": the row spans of vT, "h": the column spans of
         u).  flag_rank None or 0: pca_rank; 1 <= flag_rank <= pca_rank.  Not in the reference: where the local spaces hold a few shared directions and
@@ -942,8 +947,15 @@ class EditUncondDiffusion(_EditBase):
         sampled together and saved there; the basis written as [N, r] columns under global_flag_mean_paths with an info- file (weight, eigenvalues,
         gap, theta, iterations, converged, space, names) beside it, an existing file loaded and column-normalised; the printed summary shows the
         spectrum around row r, so that a missing gap is seen; then the common tail _edit_along_global_basis (local_projection=False: space x only).
-        A pc >= flag_rank raises ValueError.  Returns a dict: basis [r, N] (rows), vk [P, N_x], pcs, names, info (None for a loaded basis)."""
+        A pc >= flag_rank raises ValueError.  Returns a dict: basis [r, N] (rows), vk [P, N_x], pcs, names, info (None for a loaded basis).
+
+        flag_mean_kind "median": the basis is the flag median of the same local bases (geometry.flag_median with flag_median_eps and
+        flag_median_max_rounds: the L1 counterpart, on which outlying local spaces pull with a bounded force), cached under the -median names of
+        global_flag_mean_paths; its info- file also holds member_weight, distance, objective and rounds, and the five members of lowest weight are
+        printed by name with their distances.  "mean" is the job as it was, file names included."""
         from . import geometry
+        if flag_mean_kind not in ("mean", "median"):
+            raise ValueError(f"flag_mean_kind must be 'mean' (geometry.flag_mean) or 'median' (geometry.flag_median), got {flag_mean_kind!r}")
         if flag_mean_space not in ("x", "h"):
             raise ValueError(f"flag_mean_space must be 'x' (the spans of vT) or 'h' (the spans of u), got {flag_mean_space!r}")
         if flag_mean_space == "h" and not local_projection:
@@ -964,7 +976,8 @@ class EditUncondDiffusion(_EditBase):
         h_t_idx = int((self.scheduler.timesteps - h_t * 1000).abs().argmin())
         load = lambda p: torch.load(p, map_location=self.device).to(torch.float32)
 
-        basis_path, info_path = self.global_flag_mean_paths(op, block_idx, pca_rank, num_local_basis, flag_mean_space, h_t, r)
+        median = flag_mean_kind == "median"
+        basis_path, info_path = self.global_flag_mean_paths(op, block_idx, pca_rank, num_local_basis, flag_mean_space, h_t, r, flag_mean_kind)
         os.makedirs(os.path.dirname(basis_path), exist_ok=True)
         info = None
         if os.path.exists(basis_path):
@@ -981,14 +994,28 @@ class EditUncondDiffusion(_EditBase):
                                             block_idx, pca_rank, 1e-4, local_dir, lambda *a: None)
             with T.phase("flag mean of the local bases"):
                 stack = torch.stack([load(p[3][2]) if flag_mean_space == "x" else load(p[3][0]).t() for p in pairs]).contiguous()
-                basis, info = geometry.flag_mean(stack, rank=r)
+                if median:
+                    basis, info = geometry.flag_median(stack, rank=r, eps=flag_median_eps, max_rounds=flag_median_max_rounds)
+                else:
+                    basis, info = geometry.flag_mean(stack, rank=r)
             eig = info["eigenvalues"]
             lo, hi = max(0, r - 3), min(len(eig), r + 3)
             around = " ".join(f"{v:.4f}" for v in eig[lo:r]) + " | " + " ".join(f"{v:.4f}" for v in eig[r:hi])
-            print(f"flag mean of {num_local_basis} local bases in {flag_mean_space}-space, rank {r}: {info['iterations']} iterations, residual "
-                  f"{info['residual']:.3e}" + ("" if info["converged"] else " -- NOT converged: row r sits inside the bulk of the spectrum")
+            if median:
+                head = (f"flag median of {num_local_basis} local bases in {flag_mean_space}-space, rank {r}: {info['rounds']} rounds, objective "
+                        f"{info['objective'][0]:.6f} -> {info['objective'][-1]:.6f}" + ("" if info["converged"] else " -- NOT converged")
+                        + ("" if info["monotone"] else " -- NOT monotone")
+                        + ("" if info["inner_converged"] else " -- an inner solve did NOT converge: row r sits inside the bulk of the spectrum"))
+            else:
+                head = (f"flag mean of {num_local_basis} local bases in {flag_mean_space}-space, rank {r}: {info['iterations']} iterations, residual "
+                        f"{info['residual']:.3e}" + ("" if info["converged"] else " -- NOT converged: row r sits inside the bulk of the spectrum"))
+            print(head
                   + f"; mean cos^2 of rows {lo} .. {hi - 1} (| after row {r - 1}): {around}"
                   + ("" if info["gap"] is None else f"; gap {info['gap']:.4f}"))
+            if median:
+                mw, dist = info["member_weight"].cpu(), info["distance"].cpu()
+                low = torch.argsort(mw, stable=True)[:5].tolist()
+                print("lowest member weights (the outlying local spaces): " + ", ".join(f"{pairs[i][2]} w={mw[i]:.3f} d={dist[i]:.3f}" for i in low))
             torch.save(basis.t().contiguous().cpu(), basis_path)
             info = {k: (v.cpu() if torch.is_tensor(v) else v) for k, v in info.items()}
             torch.save(dict(info, space=flag_mean_space, names=[p[2] for p in pairs]), info_path)

@@ -13,6 +13,10 @@ expressed in a target's basis and carried to the target's x-space, fp64 on the h
 the top eigenvectors of the mean projector, by block subspace iteration on the same whitened fp64 Gram; closed form, any rank, nested, and its
 spectrum says how many directions the local spaces share.
 
+``flag_mean(weights=)`` and ``flag_median`` are the weighted flag mean and the flag median (FlagIRLS) of the same bases -- the L1 counterpart, on which
+outlying members pull with a bounded force and whose final weights rank the members from typical to outlying: the same solver on the Gram scaled
+inside its one pass, a round per reweighting, warm-started.
+
 ``flag_affinity`` is the chordal affinity sum_j cos^2 theta_j = ||Q_Y Q_A^T||_F^2 between subspaces of different rank, and ``flag_kmeans`` clusters many
 bases into several families, each with a flag mean as its centre -- Lloyd's algorithm on that affinity (``csrc/flagkmeans.hip``), the analysis of
 ``run_tangent_space_clusters``: on the same whitened Gram, the flag-mean solver per cluster, one pass over the Gram per round for all clusters.
@@ -238,8 +242,80 @@ def _flag_info(raw: np.ndarray, b: int, r: int, weight, theta) -> dict:
             "gap": float(eig[r - 1] - eig[r]) if m > r else None, "theta": theta, "degenerate": np.nonzero(raw[72:72 + b] != 0)[0].tolist()}
 
 
+def _member_weights(weights, b: int, device) -> torch.Tensor:
+    """the caller's member weights as a [B] fp64 device tensor; ValueError naming the offending indices (the one host check, and its sync)"""
+    w = weights.detach().to("cpu", torch.float64).numpy() if torch.is_tensor(weights) else np.asarray(weights, dtype=np.float64)
+    if w.shape != (b,):
+        raise ValueError(f"weights must hold one value per basis, [B = {b}], got shape {tuple(w.shape)}")
+    bad = np.nonzero(~np.isfinite(w) | (w < 0))[0].tolist()
+    if bad:
+        raise ValueError(f"weights must be finite and >= 0: indices {bad}")
+    if not w.sum() > 0:
+        raise ValueError(f"weights must have a positive sum: all {b} are zero")
+    return torch.from_numpy(np.ascontiguousarray(w)).to(device)
+
+
+def _median_head(scratch: torch.Tensor) -> dict:
+    """the head of a dpb_flag_median_* block (include/dpb.h): one device read"""
+    raw = scratch[:64].cpu().numpy()
+    i, d = raw[:24].view(np.int32), raw[24:48].view(np.float64)
+    return {"round": int(i[0]), "done": int(i[1]), "iters": int(i[2]), "n_degenerate": int(i[3]), "converged": int(i[4]) != 0, "J": float(d[0]),
+            "J_prev": float(d[1]), "res": float(d[2])}
+
+
+def _median_run(lib, A: torch.Tensor, r: int, w_dev, do_rounds: bool, max_rounds: int, eps: float, tol: float, inner_iter: int, inner_tol: float,
+                check_every: int, seed: int, max_bytes: int, what: str):
+    """dpb_flag_median_*: init, then per round the chunked inner solve and (do_rounds) the round step, then finish.  do_rounds False is the weighted mean"""
+    b, k, n = A.shape
+    need = int(lib.dpb_flag_median_scratch_bytes(b, k, n, r, inner_iter))
+    if need == 0:
+        raise L.DpbError(f"dpb_flag_median does not take B = {b}, k = {k}, N = {n}, r = {r}, max_iter = {inner_iter}")
+    if need > max_bytes:
+        raise ValueError(f"{what} of B = {b} bases of k = {k} rows needs {need} bytes of device scratch (the fp64 Gram of all {b * k} rows), "
+                         f"max_bytes is {max_bytes}")
+    d = min(r, k)
+    objective, inner_its, inner_conv, converged = [], [], [], False
+    with torch.cuda.device(A.device):
+        st = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
+        dev = A.device
+        scratch = torch.empty(need, dtype=torch.uint8, device=dev)
+        Y = torch.empty(r, n, dtype=torch.float32, device=dev)
+        weight = torch.empty(r, dtype=torch.float32, device=dev)
+        theta = torch.empty(b, d, dtype=torch.float32, device=dev)
+        Ct = torch.empty(b * k, r, dtype=torch.float64, device=dev)
+        member = torch.empty(3, b, dtype=torch.float64, device=dev)
+        info_d = torch.empty(72 + b, dtype=torch.float64, device=dev)
+        sp = scratch.data_ptr()
+        L.check(lib.dpb_flag_median_init(A.data_ptr(), None, None if w_dev is None else w_dev.data_ptr(), b, k, n, r, seed, inner_iter, sp, need, st))
+        while True:
+            asked = 0
+            while asked < inner_iter:
+                steps = min(check_every, inner_iter - asked)
+                L.check(lib.dpb_flag_median_iterate(steps, float(inner_tol), None, b, k, n, r, inner_iter, sp, need, st))
+                asked += steps
+                if _median_head(scratch)["done"] != 0:                 # the one host read of the chunk
+                    break
+            if not do_rounds:
+                break
+            update = len(objective) < max_rounds
+            L.check(lib.dpb_flag_median_round(float(eps), float(tol), 1 if update else 0, None, b, k, n, r, inner_iter, sp, need, st))
+            head = _median_head(scratch)                                # the one host read of the round
+            objective.append(head["J"])
+            inner_its.append(head["iters"])
+            inner_conv.append(head["done"] == 1)
+            converged = head["converged"]
+            if converged or not update or head["done"] == 2 or head["J"] != head["J"]:
+                break
+        L.check(lib.dpb_flag_median_finish(A.data_ptr(), None, Y.data_ptr(), weight.data_ptr(), theta.data_ptr(), Ct.data_ptr(), member.data_ptr(),
+                                           info_d.data_ptr(), b, k, n, r, inner_iter, sp, need, st))
+        raw = info_d.cpu().numpy()
+    info = _flag_info(raw, b, r, weight, theta)
+    info.update({"affinity": member[0], "distance": member[1], "member_weight": member[2]})
+    return Y, info, objective, inner_its, inner_conv, converged
+
+
 def flag_mean(A: torch.Tensor, rank: Optional[int] = None, max_iter: int = 1000, tol: float = 1e-12, check_every: int = 16, seed: int = 0,
-              max_bytes: Optional[int] = None, check: bool = True) -> Tuple[torch.Tensor, dict]:
+              max_bytes: Optional[int] = None, check: bool = True, weights=None) -> Tuple[torch.Tensor, dict]:
     """The flag (extrinsic, chordal) mean of the row spans of A [B, k, N]: the top ``rank`` eigenvectors of the mean projector (1/B) sum_i Q_i^T Q_i
     over the orthonormalised members (Draper et al. 2014) -- closed form, no cut locus, defined for every rank in [1, min(64, B k, N)] (None: k), and
     nested: rows 0 .. j-1 are the rank-j mean (dpb_flag_mean_init / _iterate / _finish; see include/dpb.h for the method and the limits).  Rows need
@@ -254,7 +330,13 @@ def flag_mean(A: torch.Tensor, rank: Optional[int] = None, max_iter: int = 1000,
     Block subspace iteration with a Rayleigh-Ritz step per iteration on the whitened fp64 Gram of all B k rows, in chunks of check_every iterations
     with one status read per chunk.  Not converging within max_iter is not an error -- it is the answer when row ``rank`` sits inside the bulk of the
     spectrum: converged is False, Y is still orthonormal and weight its Rayleigh quotients.  The Gram must fit max_bytes (8 (B k)^2 bytes plus the
-    block).  check: raise ValueError naming the degenerate bases; False returns the NaNs.  Bitwise reproducible for a given seed (the start block)."""
+    block).  check: raise ValueError naming the degenerate bases; False returns the NaNs.  Bitwise reproducible for a given seed (the start block).
+
+    weights (None: the call above, untouched): a length-B tensor or sequence, finite, >= 0, with a positive sum -- the weighted flag mean, the top
+    eigenvectors of sum_i w_i Q_i^T Q_i / sum_i w_i (dpb_flag_median_* with no round: the same solver, the weights applied inside the pass over the Gram).
+    A member of weight 0 is excluded from the mean and still gets its row of ``theta``; ``weight`` and ``eigenvalues`` are those of the weighted
+    projector; info gains ``member_weight`` [B] (the weights scaled to mean 1) and ``affinity`` [B] (sum_j cos^2 of each member to span Y), fp64 on
+    the device.  Bad weights raise ValueError naming the indices (one host check).  Uniform weights return the unweighted call's bits."""
     lib = L.load()
     A = _stack(A, "A")
     b, k, n = A.shape
@@ -270,6 +352,13 @@ def flag_mean(A: torch.Tensor, rank: Optional[int] = None, max_iter: int = 1000,
     if max_iter < 0 or check_every < 1 or not tol >= 0 or seed < 0:
         raise ValueError(f"max_iter = {max_iter} must be >= 0, check_every = {check_every} >= 1, tol = {tol} >= 0 and seed = {seed} >= 0")
     max_bytes = DEFAULT_MAX_BYTES if max_bytes is None else int(max_bytes)
+    if weights is not None:
+        w_dev = _member_weights(weights, b, A.device)
+        Y, info, _, _, _, _ = _median_run(lib, A, r, w_dev, False, 0, 1.0, 0.0, max_iter, tol, check_every, seed, max_bytes, "the weighted flag mean")
+        info.pop("distance")
+        if check and info["degenerate"]:
+            raise ValueError(f"{DEGENERATE}: indices {info['degenerate']}")
+        return Y, info
     need = int(lib.dpb_flag_mean_scratch_bytes(b, k, n, r, max_iter))
     if need == 0:
         raise L.DpbError(f"dpb_flag_mean does not take B = {b}, k = {k}, N = {n}, r = {r}, max_iter = {max_iter}")
@@ -290,6 +379,56 @@ def flag_mean(A: torch.Tensor, rank: Optional[int] = None, max_iter: int = 1000,
                                          b, k, n, r, max_iter, scratch.data_ptr(), need, st))
         raw = info_d.cpu().numpy()
     info = _flag_info(raw, b, r, weight, theta)
+    if check and info["degenerate"]:
+        raise ValueError(f"{DEGENERATE}: indices {info['degenerate']}")
+    return Y, info
+
+
+def flag_median(A: torch.Tensor, rank: Optional[int] = None, eps: float = 1e-5, max_rounds: int = 50, tol: float = 1e-9, inner_iter: int = 200,
+                inner_tol: float = 1e-12, check_every: int = 16, seed: int = 0, weights=None, max_bytes: Optional[int] = None,
+                check: bool = True) -> Tuple[torch.Tensor, dict]:
+    """The flag median of the row spans of A [B, k, N] (Mankovich, King, Peterson, Kirby, CVPR 2022, FlagIRLS): the rank-``rank`` subspace (None: k;
+    1 <= rank <= k) minimising sum_i p_i d_i with d_i = sqrt(rank - a_i) the chordal distance -- not its square, which the flag mean minimises -- and
+    a_i = ||Q_i Y^T||_F^2, so that outlying members pull with a bounded force.  Iteratively reweighted flag means (dpb_flag_median_*; include/dpb.h):
+    round 0 is the flag mean under the prior weights p (``weights``; None: uniform), every further round the weighted flag mean under
+    w_i = p_i / max(d_i, eps), scaled to mean 1; the inner solve of a round (at most inner_iter iterations to inner_tol in chunks of check_every) is
+    warm-started at the previous round's block.  The objective is J = sum_i p_i phi(d_i), phi(d) = d for d >= eps and d^2 / (2 eps) + eps / 2 below
+    it: what IRLS with the clamped weight descends.  The run stops when J_prev - J <= tol J_prev (``converged``) or after max_rounds reweightings;
+    max_rounds = 0 is the (weighted) flag mean and its objective.
+
+    eps = 1e-5: the affinity's recorded worst error is 5.7e-12 (k = rank = 64), so sqrt(rank - a) has a floor near 2.4e-6; eps sits above that floor,
+    and a member lying in span Y gets a large, finite weight.
+
+    Returns Y [rank, N] fp32 (orthonormal rows, descending Rayleigh quotient) and info: ``rounds`` (reweightings taken), ``converged``, ``objective``
+    (fp64 numpy, one entry per round, the start included), ``monotone`` (no entry rose by more than 1e-12 J), ``member_weight`` [B] (the weights of
+    the last solve, mean 1: low for outlying members), ``distance`` [B] and ``affinity`` [B] (to the returned Y; fp64 on the device), ``weight``
+    [rank] (fp32: the Rayleigh quotients of the weighted mean projector of the last round), ``eigenvalues``, ``gap``, ``theta`` [B, rank] (as
+    flag_mean's), ``inner_iterations`` (per round), ``inner_converged`` (all of them) and ``degenerate``.  Not converging, an inner solve that does
+    not settle (row ``rank`` inside the bulk of the spectrum) and monotone = False are reported, not raised.  check: raise ValueError naming the
+    degenerate bases; False returns the NaNs.  One host read per round and one per chunk of the inner solves.  Bitwise reproducible."""
+    lib = L.load()
+    A = _stack(A, "A")
+    b, k, n = A.shape
+    if k > FRECHET_MAX_RANK:
+        raise ValueError(f"k = {k} rows per basis exceeds the rank {FRECHET_MAX_RANK} the flag median supports")
+    if k > n:
+        raise ValueError(f"k = {k} rows per basis exceeds their length N = {n}: they cannot be independent")
+    r = k if rank is None else int(rank)
+    if not 1 <= r <= k:
+        raise ValueError(f"rank = {r} outside [1, k = {k}]: the chordal distance sqrt(rank - a) is defined for rank <= k only")
+    max_rounds, inner_iter, check_every, seed = int(max_rounds), int(inner_iter), int(check_every), int(seed)
+    if not eps > 0 or max_rounds < 0 or inner_iter < 0 or check_every < 1 or not tol >= 0 or not inner_tol >= 0 or seed < 0:
+        raise ValueError(f"eps = {eps} must be > 0, max_rounds = {max_rounds} and inner_iter = {inner_iter} >= 0, check_every = {check_every} >= 1, "
+                         f"tol = {tol} and inner_tol = {inner_tol} >= 0 and seed = {seed} >= 0")
+    max_bytes = DEFAULT_MAX_BYTES if max_bytes is None else int(max_bytes)
+    w_dev = None if weights is None else _member_weights(weights, b, A.device)
+    Y, info, objective, inner_its, inner_conv, converged = _median_run(lib, A, r, w_dev, True, max_rounds, eps, tol, inner_iter, inner_tol, check_every,
+                                                                       seed, max_bytes, "the flag median")
+    objective = np.asarray(objective, dtype=np.float64)
+    info.pop("iterations"); info.pop("residual")
+    info.update({"rounds": len(objective) - 1, "converged": bool(converged), "objective": objective,
+                 "monotone": bool(np.all(objective[1:] <= objective[:-1] * (1.0 + 1e-12))), "inner_iterations": inner_its,
+                 "inner_converged": bool(all(inner_conv))})
     if check and info["degenerate"]:
         raise ValueError(f"{DEGENERATE}: indices {info['degenerate']}")
     return Y, info

@@ -118,6 +118,13 @@ SYMBOLS = {
     "dpb_flag_mean_init": (_I, [_P, _P, _I, _I, _L, _I, C.c_uint64, _I, _P, C.c_size_t, _P]),
     "dpb_flag_mean_iterate": (_I, [_I, C.c_double, _P, _I, _I, _L, _I, _I, _P, C.c_size_t, _P]),
     "dpb_flag_mean_finish": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _P, C.c_size_t, _P]),
+    # weighted flag mean and flag median (geometry.flag_mean(weights=) / flag_median): the flag-mean family plus a round per reweighting
+    "dpb_flag_median_scratch_bytes": (C.c_size_t, [_I, _I, _L, _I, _I]),
+    "dpb_flag_median_solver_bytes": (C.c_size_t, [_I, _I, _I, _I]),
+    "dpb_flag_median_init": (_I, [_P, _P, _P, _I, _I, _L, _I, C.c_uint64, _I, _P, C.c_size_t, _P]),
+    "dpb_flag_median_iterate": (_I, [_I, C.c_double, _P, _I, _I, _L, _I, _I, _P, C.c_size_t, _P]),
+    "dpb_flag_median_round": (_I, [C.c_double, C.c_double, _I, _P, _I, _I, _L, _I, _I, _P, C.c_size_t, _P]),
+    "dpb_flag_median_finish": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _L, _I, _I, _P, C.c_size_t, _P]),
     # chordal affinity of two stacks and flag k-means (geometry.flag_affinity / flag_kmeans): seeds is a host int32 array; the caller owns the rounds
     "dpb_flag_affinity_scratch_bytes": (C.c_size_t, [_I, _I, _I, _I, _L]),
     "dpb_flag_affinity": (_I, [_P, _P, _I, _I, _I, _I, _L, _P, _P, C.c_size_t, _P]),

@@ -36,6 +36,9 @@ sampling directory at --h_t (x: the spans of vT, h: the spans of u; missing ones
 ``--run_edit_global_flag_mean_zt True --flag_mean_space x|h --flag_rank r`` (new; unconditional nets only) edits --sample_idx along the rows of the
 flag (extrinsic) mean of the same local bases: the top r eigenvectors of their mean projector (geometry.flag_mean; --flag_rank 0, the default, means
 --pca_rank), cached as v- / u-...-rank_<r>.pt with an info- file that holds the spectrum.  It takes the Frechet job's other flags.
+--flag_mean_kind mean|median (new; default mean) makes that basis the flag median of the local bases instead (geometry.flag_median: the L1
+counterpart, by iteratively reweighted flag means; --flag_median_eps, the clamp of the weights, and --flag_median_max_rounds), cached under the same
+names with -median appended; its info- file also ranks the local bases from typical to outlying (member_weight, distance).
 ``--run_edit_global_hungarian_mean_zt True --hungarian_mean_space x|h`` (the reference's flags, define_argparser.py:121-122; unconditional nets only)
 edits --sample_idx along the other global basis: the Hungarian-matched mean of the same local bases -- the directions of every basis matched one to
 one and sign by sign to those of basis 0 and averaged (geometry.hungarian_mean; --hungarian_distance 1/cosine|cosine and --hungarian_max_sweeps are
@@ -98,6 +101,8 @@ _FLAGS = [  # (name, type, default) -- define_argparser.py:20-110, live path onl
     ("frechet_tol", float, 1e-6), ("local_projection", str2bool, True),
     # new: the start of the Karcher iteration (member: local basis 0; flag: the flag mean), and the flag-mean global-basis job (flag_rank 0: pca_rank)
     ("frechet_init", str, "member"), ("run_edit_global_flag_mean_zt", str2bool, False), ("flag_mean_space", str, "x"), ("flag_rank", int, 0),
+    # new: the flag-mean job's basis as the flag median (geometry.flag_median: iteratively reweighted flag means), its clamp and its round limit
+    ("flag_mean_kind", str, "mean"), ("flag_median_eps", float, 1e-5), ("flag_median_max_rounds", int, 50),
     # define_argparser.py:121-122: the other global-basis job (unconditional nets); hungarian_mean_space defaults to x, what the reference's method
     # does (its flag has no consumer); hungarian_distance / hungarian_max_sweeps are new (the reference passes distance='1/cosine')
     ("run_edit_global_hungarian_mean_zt", str2bool, False), ("hungarian_mean_space", str, "x"), ("hungarian_distance", str, "1/cosine"),
@@ -158,6 +163,13 @@ def parse_args(argv=None):
         p.error("--local_projection False is valid for --flag_mean_space x only")
     if args.run_edit_global_flag_mean_zt and not 0 <= args.flag_rank <= args.pca_rank:
         p.error("--flag_rank must lie in [1, --pca_rank] (0: --pca_rank)")
+    if args.flag_mean_kind != "mean" and "stable-diffusion" in args.model_name:
+        p.error("--flag_mean_kind belongs to --run_edit_global_flag_mean_zt, a job of the unconditional nets only: the reference has no Stable "
+                "Diffusion global basis")
+    if args.flag_mean_kind not in ("mean", "median"):
+        p.error("--flag_mean_kind must be mean (the flag mean of the local bases) or median (their flag median)")
+    if not args.flag_median_eps > 0 or args.flag_median_max_rounds < 0:
+        p.error("--flag_median_eps must be positive and --flag_median_max_rounds >= 0")
     if args.run_edit_global_hungarian_mean_zt and "stable-diffusion" in args.model_name:
         p.error("--run_edit_global_hungarian_mean_zt is a job of the unconditional nets only: the reference has no Stable Diffusion global Hungarian "
                 "basis (its run_edit_global_hungarian_mean_zt belongs to EditUncondDiffusion)")
@@ -401,7 +413,9 @@ def main(argv=None):
     if args.run_edit_global_flag_mean_zt:                                        # (not in the reference: the third global basis)
         edit.run_edit_global_flag_mean_zt(idx=args.sample_idx, op=args.op, block_idx=args.block_idx, vis_num=args.vis_num, vis_num_pc=args.vis_num_pc,
                                           pca_rank=args.pca_rank, num_local_basis=args.num_local_basis, local_projection=args.local_projection,
-                                          flag_mean_space=args.flag_mean_space, h_t=args.h_t, flag_rank=args.flag_rank)
+                                          flag_mean_space=args.flag_mean_space, h_t=args.h_t, flag_rank=args.flag_rank,
+                                          flag_mean_kind=args.flag_mean_kind, flag_median_eps=args.flag_median_eps,
+                                          flag_median_max_rounds=args.flag_median_max_rounds)
     if args.run_edit_global_hungarian_mean_zt:                                   # (the reference's main.py never calls it; its method's own defaults otherwise)
         edit.run_edit_global_hungarian_mean_zt(idx=args.sample_idx, op=args.op, block_idx=args.block_idx, vis_num=args.vis_num,
                                                vis_num_pc=args.vis_num_pc, pca_rank=args.pca_rank, num_local_basis=args.num_local_basis,

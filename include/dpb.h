@@ -371,6 +371,41 @@ int dpb_flag_mean_iterate(int n_iter, double tol, const double* Ghat, int B, int
 int dpb_flag_mean_finish(const float* X, const double* Ghat, float* Y, float* weight, float* theta, double* Ct, double* info, int B, int k, int64_t N,
                          int r, int max_iter, void* scratch, size_t scratch_bytes, void* hip_stream);
 
+/* ---- Weighted flag mean and flag median (FlagIRLS) of subspaces (additive to ABI version 1; engine-independent) --------------------------
+ * Weighted flag mean: the top-r eigenvectors of P_w = sum_i w_i Q_i^T Q_i / sum_i w_i.  Flag median (Mankovich, King, Peterson, Kirby, CVPR 2022): the
+ * rank-r subspace minimising sum_i p_i d_i, d_i = sqrt(r - a_i) the chordal distance (not its square), a_i = ||Q_i Y^T||_F^2, 1 <= r <= k, by iteratively
+ * reweighted flag means with w_i = p_i / max(d_i, eps); p the caller's weights (uniform when NULL).  A weighted mean is this family with zero rounds.
+ *
+ * Method (csrc/flagmean.hip).  what = w B / sum w (mean 1, the sum in index order) and D = diag(sqrt(what_i) (x) 1_k): the rows D Q have the Gram
+ * D Ghat D, and dpb_flag_mean_*'s solver runs on W = D Ghat D Z -- the same one pass over Ghat with the same cut points and wave-order sum, the scale
+ * applied to the Z operand before its MFMAs and to the output row as it is stored (a table of R square roots read through L2; no scaled copy of Ghat):
+ * uniform weights give dpb_flag_mean_*'s bits.  Y = C Q with C^T = D Z Sc, C Ghat C^T = I.  M^T = Ghat C^T is a second, UNWEIGHTED pass over Ghat: a
+ * member of weight 0 is excluded from the mean and still gets its affinity a_i = ||M[i-rows]||_F^2, distance and angles.
+ * dpb_flag_median_init: dpb_flag_mean_init's work (Ghat from X, or the caller's; the start block) and the table from member_weight [B] fp64 on the
+ *   DEVICE (NULL: uniform).  A negative or non-finite weight or a zero sum makes the table NaN: the solve then ends with status 2, it does not fault.
+ * dpb_flag_median_iterate: dpb_flag_mean_iterate on the weighted product (the inner solve), the status copied to the head.
+ * dpb_flag_median_round (r <= k): the Rayleigh-Ritz step of finish under the weighted projector, M, a_i, d_i = sqrt(max(r - a_i, 0)), the smoothed
+ *   objective J = sum_i p_i phi(d_i), phi(d) = d for d >= eps and d^2 / (2 eps) + eps / 2 below (what IRLS with the clamped weight descends), in index
+ *   order.  From the second round on, J_prev - J <= tol J_prev sets head.converged and moves nothing; otherwise, with update != 0, the new table
+ *   what_i = w_i B / sum w and the inner status cleared -- the block Z stays, so the next inner solve is warm-started.  update = 0: J only.
+ * dpb_flag_median_finish: dpb_flag_mean_finish's outputs under the table as it stands -- Y [r][N] fp32 (one pass over X), weight [r] fp32 (the Rayleigh
+ *   quotients of the WEIGHTED mean projector, in [0, 1]), theta [B][min(r,k)], Ct [R][r], info [72 + B] -- and member [3][B] fp64: affinity, distance,
+ *   member weight (what of the last round; the given ones, scaled to mean 1, for a weighted mean).
+ * Head: the first 64 bytes of scratch are {int32 round (objective evaluations), int32 done, int32 inner iterations (of the current inner solve),
+ *   int32 degenerate members, int32 converged, int32 0, double J, double previous J, double inner residual, 0, 0}: the caller's one read per round.
+ * Degenerate basis, reproducibility (fp64, no atomics, every sum one fixed chain), limits and the scratch contract: dpb_flag_mean_*'s, with
+ *   dpb_flag_median_scratch_bytes / _solver_bytes.  No device allocation, no host synchronisation.  Errors via dpb_last_error. */
+size_t dpb_flag_median_scratch_bytes(int B, int k, int64_t N, int r, int max_iter);   /* 0 when invalid */
+size_t dpb_flag_median_solver_bytes(int B, int k, int r, int max_iter);               /* 0 when invalid */
+int dpb_flag_median_init(const float* X, const double* Ghat, const double* member_weight /*device [B] or NULL*/, int B, int k, int64_t N, int r,
+                         uint64_t seed, int max_iter, void* scratch, size_t scratch_bytes, void* hip_stream);
+int dpb_flag_median_iterate(int n_iter, double tol, const double* Ghat, int B, int k, int64_t N, int r, int max_iter, void* scratch,
+                            size_t scratch_bytes, void* hip_stream);
+int dpb_flag_median_round(double eps, double tol, int update, const double* Ghat, int B, int k, int64_t N, int r, int max_iter, void* scratch,
+                          size_t scratch_bytes, void* hip_stream);
+int dpb_flag_median_finish(const float* X, const double* Ghat, float* Y, float* weight, float* theta, double* Ct, double* member /*[3][B]*/, double* info,
+                           int B, int k, int64_t N, int r, int max_iter, void* scratch, size_t scratch_bytes, void* hip_stream);
+
 /* ---- Chordal affinity of subspaces of unequal rank, and flag k-means (additive to ABI version 1; engine-independent) ---------------------
  * a(A, Y) = sum_j cos^2 theta_j(A, Y) = ||Q_Y Q_A^T||_F^2 in [0, min(r, k)] between a k-dimensional and an r-dimensional subspace of R^N (csrc/flagkmeans.hip).
  *
