@@ -1651,6 +1651,27 @@ int dpb_frechet_start(const double* Ct, int B, int k, int64_t N, int max_iter, v
   return launch_frechet_start(Ct, B, k, N, max_iter, scratch, scratch_bytes, (hipStream_t)stream);
 }
 
+// principal geodesic analysis of many local bases around a base point (geometry.grassmann_pga): pga.hip, on a Frechet scratch block after dpb_frechet_finish
+size_t dpb_pga_scratch_bytes(int B, int members, int k, int64_t N, int J) { return pga_scratch_bytes(B, members, k, N, J); }
+
+int dpb_pga_tangent_gram(int B, int members, int k, int64_t N, int max_iter, int J, void* frechet_scratch, size_t frechet_bytes, double* T, float* theta,
+                         int32_t* state, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!frechet_scratch || !T || !theta || !state || !scratch) return fail("dpb_pga_tangent_gram: null argument");
+  return launch_pga_tangent_gram(B, members, k, N, max_iter, J, frechet_scratch, frechet_bytes, T, theta, state, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int dpb_pga_eig(const double* T, int B, int members, int k, int64_t N, int J, int M, int center, double* Wt, double* out, void* scratch, size_t scratch_bytes,
+                void* stream) {
+  if (!T || !Wt || !out || !scratch) return fail("dpb_pga_eig: null argument");
+  return launch_pga_eig(T, B, members, k, N, J, M, center, Wt, out, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int dpb_pga_combine(const float* X, const double* Wt, int rows, float* out, int B, int members, int k, int64_t N, int max_iter, int J, void* frechet_scratch,
+                    size_t frechet_bytes, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!X || !Wt || !out || !frechet_scratch || !scratch) return fail("dpb_pga_combine: null argument");
+  return launch_pga_combine(X, Wt, B, members, k, N, max_iter, J, rows, frechet_scratch, frechet_bytes, out, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
 // the flag (extrinsic) mean of many local bases, the global basis of run_edit_global_flag_mean_zt: flagmean.hip
 size_t dpb_flag_mean_scratch_bytes(int B, int k, int64_t N, int r, int max_iter) { return flag_mean_scratch_bytes(B, k, N, r, max_iter, true); }
 size_t dpb_flag_mean_solver_bytes(int B, int k, int r, int max_iter) { return flag_mean_scratch_bytes(B, k, 0, r, max_iter, false); }
@@ -2042,6 +2063,7 @@ int dpb_debug_set(const char* key, int value) {
   else if (!strcmp(key, "cross_fold")) { g_cross_fold = value; return 0; }
   else if (!strcmp(key, "geglu_fwd")) { g_geglu_fwd = value; return 0; }
   else if (!strcmp(key, "iter_alias")) { g_iter_alias = value; return 0; }
+  else if (!strcmp(key, "pga_route")) { pga_debug_route(value); return 0; }
   else return fail("unknown debug key %s", key);
   gemm_debug_set(tile, splitk, kch);
   return 0;

@@ -596,6 +596,15 @@ const double* frechet_ghat(long B, int k, long N, long max_iter, const void* scr
   return fr_layout(B, k, N, max_iter, l) ? (const double*)((const char*)scratch + l.G) : nullptr;
 }
 
+// the parts of a Frechet scratch block that pga.hip reads after dpb_frechet_finish: Ghat, the whitenings, the flags, the base point's coefficients, the rotation
+bool frechet_view(long B, int k, long N, long max_iter, void* scratch, FrechetView& v) {
+  FrLayout l;
+  if (!scratch || !fr_layout(B, k, N, max_iter, l)) return false;
+  const FrPtrs p = fr_ptrs(scratch, l, B, k, max_iter);
+  v.G = p.G; v.W = p.W; v.Ct = p.Ct; v.Rot = p.Rot; v.flags = p.flags; v.total = l.total;
+  return true;
+}
+
 // the iteration restarted at the caller's point: C^T = Ct [R][k] (any full-rank coefficients on the whitened rows), whitened by the step's own
 // re-orthonormalisation -- the Cholesky factor of C Ghat C^T; the status cleared
 int launch_frechet_start(const double* Ct, long B, int k, long N, long max_iter, void* scratch, size_t scratch_bytes, hipStream_t st) {

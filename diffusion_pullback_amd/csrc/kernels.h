@@ -415,6 +415,21 @@ int launch_coef_stream(const float* X, const double* Zt, float* Y, int R, int k,
 const double* frechet_ghat(long B, int k, long N, long max_iter, const void* scratch);   // Ghat inside a Frechet scratch block; nullptr when invalid
 int launch_frechet_start(const double* Ct, long B, int k, long N, long max_iter, void* scratch, size_t scratch_bytes, hipStream_t st);
 
+struct FrechetView { const double *G, *W, *Ct, *Rot; const int* flags; size_t total; };
+bool frechet_view(long B, int k, long N, long max_iter, void* scratch, FrechetView& v);   // false when invalid
+
+// ---------------------------------------------------------------- principal geodesic analysis of B bases around a base point (pga.hip): the Gram of the log
+// maps at the current point of a Frechet scratch block from k x k algebra on Ghat, its (centred) eigen-problem, and the modes in one streaming pass;
+// n members = B, or B - 1 when the last basis of the block is the caller's base point; see include/dpb.h
+size_t pga_scratch_bytes(long B, long n, int k, long N, int J);   // 0 when invalid
+int launch_pga_tangent_gram(long B, long n, int k, long N, long max_iter, int J, void* fscratch, size_t fbytes, double* T, float* theta, int32_t* state,
+                            void* scratch, size_t scratch_bytes, hipStream_t st);
+int launch_pga_eig(const double* T, long B, long n, int k, long N, int J, int M, int center, double* Wt, double* out, void* scratch, size_t scratch_bytes,
+                   hipStream_t st);
+int launch_pga_combine(const float* X, const double* Wt, long B, long n, int k, long N, long max_iter, int J, int Jw, void* fscratch, size_t fbytes, float* out,
+                       void* scratch, size_t scratch_bytes, hipStream_t st);
+void pga_debug_route(int v);   // 0 by size, 1 the one-workgroup Jacobi, 2 the subspace iteration
+
 // ---------------------------------------------------------------- the flag (extrinsic) mean of B bases of k rows (flagmean.hip): the top-r eigenvectors
 // of the mean projector by block subspace iteration on the whitened Gram; ghat != nullptr: a caller's Ghat (the scratch then holds the solver only)
 constexpr int FLAG_MEAN_MAX_RANK = 64;   // the block of the subspace iteration is at most 64 columns wide: three 64 x 64 fp64 matrices of its head live in LDS

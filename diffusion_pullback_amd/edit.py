@@ -81,6 +81,32 @@ def save_distance_plot(dist: torch.Tensor, path: str, dpi=None) -> None:
     plt.close()
 
 
+def save_pga_plots(variance, scores: torch.Tensor, h_t, scree_path: str, scatter_path: str, dpi=None) -> None:
+    """The scree plot of a tangent-space PGA (variance per mode) and the scatter of its first two score columns coloured by h_t, next to its .pt file
+    (one column: the scores against the member index); skipped without matplotlib."""
+    try:
+        import matplotlib
+        matplotlib.use("Agg", force=False)
+        import matplotlib.pyplot as plt
+    except Exception:
+        return
+    kw = {"dpi": dpi} if dpi else {}
+    v = torch.as_tensor(variance).double().numpy()
+    plt.plot(range(1, len(v) + 1), v, "o-")
+    plt.xlabel("mode")
+    plt.ylabel("variance (rad^2)")
+    plt.savefig(scree_path, **kw)
+    plt.close()
+    s = scores.detach().double().cpu().numpy()
+    x, y = (s[:, 0], s[:, 1]) if s.shape[1] > 1 else (range(len(s)), s[:, 0])
+    plt.scatter(x, y, c=[float(h) for h in h_t], cmap="viridis")
+    plt.colorbar(label="h_t")
+    plt.xlabel("score 1" if s.shape[1] > 1 else "member")
+    plt.ylabel("score 2" if s.shape[1] > 1 else "score 1")
+    plt.savefig(scatter_path, **kw)
+    plt.close()
+
+
 def save_projection_plot(cu: Optional[torch.Tensor], cv: torch.Tensor, path: str) -> None:
     """The sorted magnitudes of a direction's coefficients in the local basis, 'u' (h-space; None: there is no h-space direction) and 'v' (x-space):
     projection_coeff-<EXP_NAME>.png of the global-basis job (edit.py:1168-1172); skipped without matplotlib."""
@@ -238,6 +264,53 @@ class _EditBase(object):
         torch.save(out, os.path.join(save_dir, self.EXP_NAME + ".pt"))
         order = torch.argsort(out["labels"], stable=True)
         save_distance_plot((r - out["affinity"])[order], os.path.join(save_dir, self.EXP_NAME + ".png"), dpi=80)
+        return out
+
+    @torch.no_grad()
+    def run_tangent_space_pga(self, h_t, op, block_idx, pca_rank=50, num_local_basis=10, space="x", pga_base="frechet", pga_modes=None, max_bytes=None,
+                              **naming):
+        """Principal geodesic analysis of the local tangent spaces run_sample_encoder_local_tangent_space_zt saved: how the (basis index, h_t) pairs
+        vary around a centre -- the modes that carry the spread, where every pair sits on them and, when the files span more than one h_t, how much
+        of the spread is a trend in the timestep (geometry.grassmann_pga with the h_t of each file as the covariate).  The files are listed, named and
+        refused as run_tangent_space_distance does (a missing one raises ValueError naming it; nothing is sampled); space "x": the row spans of vT,
+        "h": the column spans of u.  pga_base: "frechet" (the Karcher mean), "flag" (the flag mean) or a member's position in the list; pga_modes:
+        None for grassmann_pga's default.  Writes tangent_space_pga-<space>-<base>-M<M>-<EXP_NAME of the set>.pt -- a dict of names, idx, h_t, base
+        [k, N], modes [M, k, N], variance, explained, scores [P, M], residual, theta, mean_tangent_norm and, when fitted, slopes, intercept, r2,
+        slope_norm -- with a scree plot (-scree.png) and a scatter of the first two score columns coloured by h_t (-scores.png) next to it; prints
+        the spectrum and r2.  A mode is a tangent at the base: geometry.grassmann_exp(base, t * modes[m], 1.0) is a basis to edit with.  Returns
+        the dict."""
+        from . import geometry
+        if space not in ("x", "h"):
+            raise ValueError(f"space must be 'x' (vT) or 'h' (u), got {space!r}")
+        if not (pga_base in ("frechet", "flag") or (isinstance(pga_base, int) and not isinstance(pga_base, bool))):
+            raise ValueError(f"pga_base must be 'frechet', 'flag' or the position of a member, got {pga_base!r}")
+        save_dir, exp_name = self._tangent_space_naming(op, block_idx, pca_rank, **naming)
+        pairs = self._tangent_space_pairs(h_t, num_local_basis, save_dir, exp_name)
+        files = [paths[2] if space == "x" else paths[0] for _, _, _, paths in pairs]
+        missing = [os.path.basename(f) for f in files if not os.path.exists(f)]
+        if missing:
+            raise ValueError(f"{len(missing)} of {len(files)} tangent-space files are missing in {save_dir}: {missing}; run the sampling job "
+                             "(run_sample_encoder_local_tangent_space_zt) with the same arguments first")
+        hts = list(h_t) if isinstance(h_t, (list, tuple)) else [h_t]
+        member_ht = [float(h) for _, h, _, _ in pairs]
+        trend = len(set(member_ht)) > 1
+        with T.phase("tangent-space PGA (principal geodesic analysis)"):
+            bases = [torch.load(f, map_location=self.device).float() for f in files]
+            stack = torch.stack([b if space == "x" else b.T for b in bases]).contiguous()
+            base, modes, info = geometry.grassmann_pga(stack, base=pga_base, n_modes=None if not pga_modes else int(pga_modes),
+                                                       covariates=member_ht if trend else None, max_bytes=max_bytes)
+        m = modes.shape[0]
+        self.EXP_NAME = f"tangent_space_pga-{space}-{pga_base}-M{m}-" + exp_name(f"0to{num_local_basis - 1}", ",".join(str(h) for h in hts))
+        out = dict(names=[name for _, _, name, _ in pairs], idx=[int(i) for i, _, _, _ in pairs], h_t=member_ht, base=base.cpu(), modes=modes.cpu(),
+                   variance=torch.as_tensor(info["variance"]), explained=torch.as_tensor(info["explained"]), scores=info["scores"].cpu(),
+                   residual=info["residual"].cpu(), theta=info["theta"].cpu(), mean_tangent_norm=info["mean_tangent_norm"])
+        if trend:
+            out.update(slopes=info["slopes"].cpu(), intercept=info["intercept"].cpu(), r2=info["r2"], slope_norm=torch.as_tensor(info["slope_norm"]))
+        print(f"tangent-space PGA at the {pga_base} base, {len(pairs)} members: variance " + " ".join(f"{v:.3e}" for v in info["variance"])
+              + f"; explained {info['explained'][-1]:.3f} of {info['total_variance']:.3e}" + (f"; trend in h_t: r2 {info['r2']:.3f}" if trend else ""))
+        path = os.path.join(save_dir, self.EXP_NAME)
+        torch.save(out, path + ".pt")
+        save_pga_plots(out["variance"], out["scores"], member_ht, path + "-scree.png", path + "-scores.png", dpi=80)
         return out
 
     def _guidance_chains_together(self, z, vk, t, emb=None):

@@ -34,6 +34,11 @@ bases (``csrc/geodesic.hip``): which directions two tangent spaces share, the ta
 between them (interpolated or extrapolated) and the geodesic shot from a space along a tangent -- per pair from the exact fp64 Grams, then one
 streaming pass that holds both rotated tiles in registers and writes every output slice from them.
 
+``grassmann_pga`` is principal geodesic analysis of many such bases around a centre (``csrc/pga.hip``), the analysis of ``run_tangent_space_pga``: PCA of
+the log maps at the Frechet mean (or the flag mean, a member, any base) -- the modes that carry the spread, every member's scores on them, and the
+tangent-space regression on covariates such as the timestep -- from the Gram of the tangents, which closes in k x k algebra on the whitened Gram the
+mean has formed, then one streaming synthesis of the modes.
+
 There is no CPU fallback: inputs live on a HIP device.
 """
 from __future__ import annotations
@@ -454,8 +459,15 @@ def frechet_mean(A: torch.Tensor, init=0, max_iter: int = 1000, tol: float = 1e-
     init="flag" starts at the rank-k flag mean instead of a member (flag_mean: central, so no member is near pi/2 from it): the flag solver runs on the
     whitened Gram this call has already formed -- there is no second pass over the rows -- for at most 64 iterations (to a residual of 1e-10), and
     dpb_frechet_start takes its coefficients; info then holds ``flag_iterations`` and ``flag_converged``.  Any other string raises ValueError."""
-    lib = L.load()
     A = _stack(A, "A")
+    Y, info, _ = _frechet_run(A, init, max_iter, tol, step, check_every, max_bytes, check, 0)
+    return Y, info
+
+
+def _frechet_run(A: torch.Tensor, init, max_iter: int, tol: float, step: float, check_every: int, max_bytes: Optional[int], check: bool, extra_bytes: int):
+    """frechet_mean on a stacked fp32 A, its Frechet scratch block kept: (Y, info, (scratch, need, max_iter)).  extra_bytes: device memory the caller will
+    allocate next to it (counted against max_bytes)"""
+    lib = L.load()
     b, k, n = A.shape
     if k > FRECHET_MAX_RANK:
         raise ValueError(f"k = {k} rows per basis exceeds the rank {FRECHET_MAX_RANK} the Frechet mean supports")
@@ -473,8 +485,8 @@ def frechet_mean(A: torch.Tensor, init=0, max_iter: int = 1000, tol: float = 1e-
     need = int(lib.dpb_frechet_scratch_bytes(b, k, n, max_iter))
     if need == 0:
         raise L.DpbError(f"dpb_frechet does not take B = {b}, k = {k}, N = {n}, max_iter = {max_iter}")
-    if need > max_bytes:
-        raise ValueError(f"the Frechet mean of B = {b} bases of k = {k} rows needs {need} bytes of device scratch (the fp64 Gram of all {b * k} rows), "
+    if need + extra_bytes > max_bytes:
+        raise ValueError(f"the Frechet mean of B = {b} bases of k = {k} rows needs {need + extra_bytes} bytes of device scratch (the fp64 Gram of all {b * k} rows), "
                          f"max_bytes is {max_bytes}")
     with torch.cuda.device(A.device):
         st = C.c_void_p(torch.cuda.current_stream(A.device).cuda_stream)
@@ -491,7 +503,7 @@ def frechet_mean(A: torch.Tensor, init=0, max_iter: int = 1000, tol: float = 1e-
             ghat = lib.dpb_frechet_ghat(b, k, n, max_iter, scratch.data_ptr())
             if fneed == 0 or not ghat:
                 raise L.DpbError(f"dpb_flag_mean does not take B = {b}, k = {k}, r = {k} on the Frechet mean's Gram")
-            if need + fneed > max_bytes:
+            if need + extra_bytes + fneed > max_bytes:
                 raise ValueError(f"the flag start of the Frechet mean needs {fneed} more bytes of device scratch, max_bytes is {max_bytes}")
             fscratch = torch.empty(fneed, dtype=torch.uint8, device=A.device)
             fCt = torch.empty(b * k, k, dtype=torch.float64, device=A.device)
@@ -532,7 +544,7 @@ def frechet_mean(A: torch.Tensor, init=0, max_iter: int = 1000, tol: float = 1e-
     if len(worst):
         j = int(worst[0])
         raise L.DpbError(f"frechet_mean: the cost rose from {cost[j]!r} to {cost[j + 1]!r} at step {j + 1}: use a smaller step than {step}")
-    return Y, info
+    return Y, info, (scratch, need, max_iter)
 
 
 CUT_LOCUS = "pairs at the cut locus (largest principal angle above pi/2 - 1e-6: the geodesic is not unique there)"
@@ -635,6 +647,174 @@ def grassmann_exp(P: torch.Tensor, H: torch.Tensor, ts, check: bool = True, max_
     False returns their NaNs (dpb_grassmann_exp; see include/dpb.h).  No CPU fallback."""
     y, _, sigma = _grassmann_call(P, H, 3, ts, check, max_bytes, ("P", "H"))
     return y, sigma
+
+
+PGA_MAX_MODES = 64                   # the block of the subspace iteration is at most 64 columns wide
+PGA_MAX_COVARIATES = 8
+PGA_ROUTES = {1: "jacobi", 2: "subspace"}
+
+
+def _pga_covariates(covariates, b: int) -> np.ndarray:
+    x = covariates.detach().to("cpu", torch.float64).numpy() if torch.is_tensor(covariates) else np.asarray(covariates, dtype=np.float64)
+    if x.ndim == 1:
+        x = x[:, None]
+    if x.ndim != 2 or x.shape[0] != b or not 1 <= x.shape[1] <= PGA_MAX_COVARIATES:
+        raise ValueError(f"covariates must be [B = {b}] or [B = {b}, P <= {PGA_MAX_COVARIATES}], got shape {tuple(np.shape(covariates))}")
+    if not np.isfinite(x).all():
+        raise ValueError(f"covariates must be finite: members {np.nonzero(~np.isfinite(x).all(axis=1))[0].tolist()}")
+    return x
+
+
+def grassmann_pga(A: torch.Tensor, base="frechet", n_modes: Optional[int] = None, center: bool = True, covariates=None,
+                  max_bytes: Optional[int] = None, check: bool = True, **mean_kwargs) -> Tuple[torch.Tensor, torch.Tensor, dict]:
+    """Principal geodesic analysis (tangent PCA) of the row spans of A [B, k, N] around a base point: how the members vary around a centre.  With
+    L_i = Log_Y(span A_i) -- a [k, N] tangent in the convention of grassmann_log / grassmann_exp: row j is the image of row j of the returned Y and
+    L_i Y^T = 0 -- the analysis is ordinary PCA of the B vectors L_i under <L_a, L_b> = tr(L_a L_b^T), centred by their mean when ``center``
+    (dpb_pga_tangent_gram / _eig / _combine on the scratch block of the mean; see include/dpb.h for the method, the limits and the NaN rule).
+
+    base: "frechet" -- the Karcher mean; mean_kwargs are frechet_mean's init, max_iter, tol, step, check_every and Y is bitwise what
+    frechet_mean(A, ...) returns; "flag" -- the rank-k flag mean, as frechet_mean(init="flag") starts, with no Karcher step; an int -- that member; a
+    tensor [k, N] -- any independent rows, in the members' span or not (stacked as one more basis for the Gram, part of no statistic).
+
+    Returns (Y [k, N], modes [M, k, N], info).  Y: orthonormal rows in the canonical order of frechet_mean.  modes (fp32): mode m has unit Frobenius norm,
+    modes[m] Y^T = 0, descending variance; its sign makes its largest-magnitude score positive (magnitudes within 1e-9 relative tie; the lowest member wins).  A mode is a tangent at Y:
+    grassmann_exp(Y, t * modes[m], 1.0) walks along it.  n_modes (None: min(B - 1, 16) centred, min(B, 16) otherwise) in [1, min(64, B - 1 or B)].
+
+    info: ``variance`` [M] (fp64 numpy: the eigenvalues of the tangent covariance (1/B) sum_i vec(L_i - Lbar) vec(L_i - Lbar)^T, descending),
+    ``total_variance`` ((1/B) sum ||L_i - Lbar||^2), ``explained`` [M] (cumulative share; zeros when the total is 0), ``scores`` [B, M] (fp64 on the
+    device: <L_i - Lbar, modes[m]>), ``residual`` [B] (fp64: ||L_i - Lbar - sum_m scores[i, m] modes[m]||_F), ``mean_tangent_norm`` (||Lbar||_F: the
+    Karcher gradient norm when base="frechet"), ``mean_tangent`` [k, N] (fp32: Lbar itself, so that grassmann_exp(Y, mean_tangent + sum_m scores[i, m]
+    modes[m], 1.0) rebuilds member i up to its residual), ``theta`` [B, k] (fp32: principal angles of Y to every member, descending), ``tangent_gram`` [B, B]
+    (fp64 on the device, uncentred), ``degenerate`` and ``domain`` (member indices: degenerate, and beyond pi/2 - 1e-6 from the base), ``solver``
+    ("jacobi": one workgroup, B <= 128; "subspace": block subspace iteration with a Rayleigh-Ritz step, with ``subspace_iterations`` and
+    ``subspace_converged``), and the mean's own ``iterations`` and ``converged`` when a mean was computed.  An eigenvalue not above 1e-13 of the
+    largest, or below the rounding floor B k 2^-46 of the Gram, carries no mode: that mode, its variance and its scores are zero (B copies of one basis give zeros, not NaN).
+
+    covariates: [B] or [B, P] (tensor or sequence, P <= 8, finite) asks for the tangent-space least-squares fit L_i ~ L_0 + sum_p x_ip S_p; info gains
+    ``slopes`` [P, k, N] and ``intercept`` [k, N] (fp32 tangents at Y), ``r2`` (the share of the centred total variance the fit explains) and
+    ``slope_norm`` [P].  The basis predicted at covariate x is grassmann_exp(Y, intercept + sum_p x_p slopes[p], 1.0).  The coefficients of the slopes on
+    the L_i depend on the covariates alone and their norms on tangent_gram: the small solve runs on the host in float64.  A rank-deficient centred
+    design raises ValueError.
+
+    check: raise ValueError naming the degenerate members, or the members whose largest angle to the base exceeds pi/2 - 1e-6 (the cut locus of the
+    log map); False returns NaN in exactly those members' rows and columns of tangent_gram and rows of scores and residual, and forms every statistic
+    over the others (a degenerate member still makes Y and the modes NaN: that is frechet_mean's finish).  The fp64 Gram of all rows must fit
+    max_bytes.  One host read for the state and the spectrum, one for the covariate fit, plus the mean's own.  Bitwise reproducible.  No CPU fallback."""
+    lib = L.load()
+    A = _stack(A, "A")
+    b, k, n = A.shape
+    if k > FRECHET_MAX_RANK:
+        raise ValueError(f"k = {k} rows per basis exceeds the rank {FRECHET_MAX_RANK} the Frechet mean supports")
+    if k > n:
+        raise ValueError(f"k = {k} rows per basis exceeds their length N = {n}: they cannot be independent")
+    center = bool(center)
+    if center and b < 2:
+        raise ValueError(f"B = {b}: a centred analysis needs at least 2 members")
+    top = min(PGA_MAX_MODES, b - 1 if center else b)
+    m = min(top, 16) if n_modes is None else int(n_modes)
+    if not 1 <= m <= top:
+        raise ValueError(f"n_modes = {m} outside [1, min({PGA_MAX_MODES}, {'B - 1' if center else 'B'}) = {top}]")
+    x = None if covariates is None else _pga_covariates(covariates, b)
+    npar = 0 if x is None else x.shape[1]
+    rows = m + 1 + (npar + 1 if npar else 0)                  # the modes, the mean tangent, the slopes and the intercept
+    stacked, mean_args = A, None
+    if isinstance(base, str):
+        if base == "frechet":
+            bad = sorted(set(mean_kwargs) - {"init", "max_iter", "tol", "step", "check_every"})
+            if bad:
+                raise TypeError(f"grassmann_pga: unknown arguments {bad} (frechet_mean takes init, max_iter, tol, step, check_every)")
+            kw = {"init": 0, "max_iter": 1000, "tol": 1e-6, "step": 1.0, "check_every": 16, **mean_kwargs}
+            mean_args = (kw["init"], kw["max_iter"], kw["tol"], kw["step"], kw["check_every"])
+        elif base == "flag":
+            mean_args = ("flag", 0, 1e-6, 1.0, 16)
+        else:
+            raise ValueError(f"base must be 'frechet', 'flag', the index of a member or a [k, N] tensor, got {base!r}")
+    elif torch.is_tensor(base):
+        y0 = _device_f32(base, "base").to(A.device)
+        if tuple(y0.shape) != (k, n):
+            raise ValueError(f"base must be [k = {k}, N = {n}], got {tuple(y0.shape)}")
+        stacked = torch.cat([A, y0[None]])
+        mean_args = (b, 0, 1e-6, 1.0, 16)
+    else:
+        if not 0 <= int(base) < b:
+            raise ValueError(f"base = {base} outside [0, B = {b})")
+        mean_args = (int(base), 0, 1e-6, 1.0, 16)
+    if mean_kwargs and not (isinstance(base, str) and base == "frechet"):
+        raise TypeError(f"grassmann_pga: {sorted(mean_kwargs)} belong to base='frechet'")
+    bs = stacked.shape[0]
+    max_bytes = DEFAULT_MAX_BYTES if max_bytes is None else int(max_bytes)
+    pneed = int(lib.dpb_pga_scratch_bytes(bs, b, k, n, rows))
+    if pneed == 0:
+        raise L.DpbError(f"dpb_pga does not take B = {bs}, members = {b}, k = {k}, N = {n}, J = {rows}")
+    Y, minfo, (fscratch, fneed, cap) = _frechet_run(stacked, *mean_args, max_bytes, check, pneed)
+    dev = A.device
+    with torch.cuda.device(dev):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        scratch = torch.empty(pneed, dtype=torch.uint8, device=dev)
+        T = torch.empty(b, b, dtype=torch.float64, device=dev)
+        theta = torch.empty(b, k, dtype=torch.float32, device=dev)
+        state = torch.empty(b, dtype=torch.int32, device=dev)
+        Wt = torch.zeros(rows, b, dtype=torch.float64, device=dev)
+        out = torch.empty(72 + b * m + b, dtype=torch.float64, device=dev)
+        tangents = torch.empty(rows, k, n, dtype=torch.float32, device=dev)
+        L.check(lib.dpb_pga_tangent_gram(bs, b, k, n, cap, rows, fscratch.data_ptr(), fneed, T.data_ptr(), theta.data_ptr(), state.data_ptr(),
+                                         scratch.data_ptr(), pneed, st))
+        L.check(lib.dpb_pga_eig(T.data_ptr(), bs, b, k, n, rows, m, 1 if center else 0, Wt.data_ptr(), out.data_ptr(), scratch.data_ptr(), pneed, st))
+        raw = torch.cat([out[:72], state.to(torch.float64)]).cpu().numpy()          # the one host read: the header, the spectrum, the members' state
+        head, sta = raw[:72], raw[72:].astype(np.int64)
+        degenerate = np.nonzero(sta == 1)[0].tolist()
+        domain = np.nonzero(sta == 2)[0].tolist()
+        if check:
+            if degenerate or (sta == 4).any():
+                raise ValueError(f"{DEGENERATE}: indices {np.nonzero((sta == 1) | (sta == 4))[0].tolist()}")
+            if domain:
+                raise ValueError(f"basis {domain[0]} is outside the log map's domain at the base: its largest principal angle to the base exceeds "
+                                 f"pi/2 - 1e-6 (choose another base, or drop the basis): indices {domain}")
+        ok = sta == 0
+        nv = int(ok.sum())
+        fit = None
+        Wt[m] = torch.from_numpy(ok / max(nv, 1)).to(dev)                            # the mean tangent
+        if npar:
+            if nv < 2:
+                raise ValueError(f"the covariate fit needs at least 2 valid members, got {nv}")
+            xv = x[ok]
+            xbar = xv.mean(axis=0)
+            xc = xv - xbar
+            if np.linalg.matrix_rank(xc) < npar:
+                raise ValueError(f"covariates: the centred design matrix of the {nv} valid members has rank {np.linalg.matrix_rank(xc)} < P = {npar}")
+            xtx = xc.T @ xc
+            coef = np.zeros((npar, b))
+            coef[:, ok] = np.linalg.solve(xtx, xc.T)                                 # S_p = sum_i coef[p, i] L_i
+            icpt = np.zeros(b)
+            icpt[ok] = 1.0 / nv
+            icpt -= xbar @ coef
+            cd = torch.from_numpy(np.concatenate([coef, icpt[None]])).to(dev)
+            Wt[m + 1:] = cd
+            tz = torch.nan_to_num(T, nan=0.0)
+            okd = torch.from_numpy(ok).to(dev)
+            tz = tz * okd[:, None] * okd[None, :]
+            sg = cd[:npar] @ tz @ cd[:npar].t()
+            fit = torch.cat([sg.flatten(), tz.diagonal().sum()[None], tz.sum()[None]]).cpu().numpy()      # the covariate fit's host read
+        L.check(lib.dpb_pga_combine(A.data_ptr() if stacked is A else stacked.data_ptr(), Wt.data_ptr(), rows, tangents.data_ptr(), bs, b, k, n, cap, rows,
+                                    fscratch.data_ptr(), fneed, scratch.data_ptr(), pneed, st))
+    variance = head[8:8 + m].copy()
+    total = float(head[1])
+    info = {"variance": variance, "total_variance": total, "explained": np.cumsum(variance) / total if total > 0 else np.zeros(m),
+            "scores": out[72:72 + b * m].view(b, m), "residual": out[72 + b * m:], "mean_tangent_norm": float(head[2]), "theta": theta, "tangent_gram": T,
+            "mean_tangent": tangents[m], "degenerate": degenerate, "domain": domain, "solver": PGA_ROUTES[int(head[3])], "valid_members": nv}
+    if info["solver"] == "subspace":
+        info["subspace_iterations"], info["subspace_converged"] = int(head[4]), int(head[5]) == 1
+    if isinstance(base, str):
+        info["iterations"], info["converged"] = minfo["iterations"], minfo["converged"]
+        for key in ("flag_iterations", "flag_converged"):
+            if key in minfo:
+                info[key] = minfo[key]
+    if npar:
+        sg = fit[:npar * npar].reshape(npar, npar)
+        centred = float(fit[-2] - fit[-1] / nv)                                      # tr(H T H) over the valid members
+        info.update({"slopes": tangents[m + 1:m + 1 + npar], "intercept": tangents[m + 1 + npar], "slope_norm": np.sqrt(np.clip(np.diag(sg), 0.0, None)),
+                     "r2": float(np.trace(sg @ xtx) / centred) if centred > 0 else 0.0})
+    return Y, tangents[:m], info
 
 
 def linear_assignment(cost: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:

@@ -112,6 +112,11 @@ SYMBOLS = {
     "dpb_frechet_finish": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _I, _P, C.c_size_t, _P]),
     "dpb_frechet_ghat": (_P, [_I, _I, _L, _I, _P]),
     "dpb_frechet_start": (_I, [_P, _I, _I, _L, _I, _P, C.c_size_t, _P]),
+    # principal geodesic analysis around the point of a Frechet scratch block (geometry.grassmann_pga): tangent Gram, eigen-solve, synthesis
+    "dpb_pga_scratch_bytes": (C.c_size_t, [_I, _I, _I, _L, _I]),
+    "dpb_pga_tangent_gram": (_I, [_I, _I, _I, _L, _I, _I, _P, C.c_size_t, _P, _P, _P, _P, C.c_size_t, _P]),
+    "dpb_pga_eig": (_I, [_P, _I, _I, _I, _L, _I, _I, _I, _P, _P, _P, C.c_size_t, _P]),
+    "dpb_pga_combine": (_I, [_P, _P, _I, _P, _I, _I, _I, _L, _I, _I, _P, C.c_size_t, _P, C.c_size_t, _P]),
     # flag (extrinsic) mean of subspaces (geometry.flag_mean): init / iterate / finish on one scratch block, or on a caller's Ghat
     "dpb_flag_mean_scratch_bytes": (C.c_size_t, [_I, _I, _L, _I, _I]),
     "dpb_flag_mean_solver_bytes": (C.c_size_t, [_I, _I, _I, _I]),

@@ -21,6 +21,11 @@ one is an error: nothing is sampled silently) and writes tangent_space_distance-
 ``--run_tangent_space_clusters True --num_clusters C --cluster_rank r`` clusters the same files into C families by flag k-means, each with a rank-r flag
 mean as its centre (geometry.flag_kmeans; --cluster_rank 0, the default, means --pca_rank).  It takes --distance_space and the sampling job's flags as
 the distance job does, runs after the sampling job, and writes tangent_space_clusters-<space>-C<C>-r<r>-....pt (labels, centres, affinity, ...) and .png.
+``--run_tangent_space_pga True --pga_base frechet|flag --pga_modes M`` describes how the same files vary around their centre: principal geodesic
+analysis of their log maps at the Frechet (or flag) mean (geometry.grassmann_pga; --pga_modes 0, the default, means min(pairs - 1, 16)), and, when
+--h_t_list holds more than one timestep, the tangent-space regression on h_t (r2, slope_norm).  It takes --distance_space and the sampling job's flags as
+the distance job does, runs after the sampling job, and writes tangent_space_pga-<space>-<base>-M<M>-....pt (base, modes, variance, scores, ...), a scree
+plot and a scatter of the first two scores coloured by h_t.
 ``--run_edit_parallel_transport True --sample_idx_0 i --sample_idx_1 j`` (the reference's flags, define_argparser.py:117-119; unconditional nets only, with
 --is_stable_diffusion models it is an error) edits sample j along the principal directions of sample i carried over by parallel transport between their
 local tangent spaces at --h_t, and sample i along its own, at --edit_t; --sample_idx_1_list 1,2,3 (new) serves several targets in one call.  It honours
@@ -92,6 +97,8 @@ _FLAGS = [  # (name, type, default) -- define_argparser.py:20-110, live path onl
     ("run_tangent_space_distance", str2bool, False),
     # new: flag k-means of the sampled tangent spaces (geometry.flag_kmeans); cluster_rank 0: pca_rank
     ("run_tangent_space_clusters", str2bool, False), ("num_clusters", int, 2), ("cluster_rank", int, 0),
+    # new: principal geodesic analysis of the sampled tangent spaces (geometry.grassmann_pga); pga_modes 0: the default of grassmann_pga
+    ("run_tangent_space_pga", str2bool, False), ("pga_base", str, "frechet"), ("pga_modes", int, 0),
     # define_argparser.py:117-119: the parallel-transport edit job (unconditional nets); sample_idx_1_list is new: several targets in one call
     ("run_edit_parallel_transport", str2bool, False), ("sample_idx_0", int, 0), ("sample_idx_1", int, 0), ("sample_idx_1_list", str, ""),
     # define_argparser.py:112-114: the global-basis edit job (unconditional nets).  local_projection defaults to True here, the default of the method
@@ -187,6 +194,12 @@ def parse_args(argv=None):
             p.error(f"--num_clusters must lie in [1, {pairs}], the number of (basis, h_t) pairs of --num_local_basis and --h_t_list")
         if not 0 <= args.cluster_rank <= args.pca_rank:
             p.error("--cluster_rank must lie in [1, --pca_rank] (0: --pca_rank)")
+    if args.run_tangent_space_pga:
+        pairs = max(0, args.num_local_basis) * len(args.h_t_values)
+        if args.pga_base not in ("frechet", "flag"):
+            p.error("--pga_base must be frechet (the Karcher mean) or flag (the flag mean)")
+        if pairs < 2 or not 0 <= args.pga_modes <= min(64, pairs - 1):
+            p.error(f"--pga_modes must lie in [1, {min(64, pairs - 1)}] (0: the default), one less than the (basis, h_t) pairs of --num_local_basis and --h_t_list")
     if extra:
         print(f"note: ignoring flags of experiments outside the pullback path: {extra}")
     return args
@@ -400,6 +413,13 @@ def main(argv=None):
             edit.run_tangent_space_clusters(edit_prompt=args.edit_prompt, **kw)
         else:
             edit.run_tangent_space_clusters(fix_xt=args.fix_xt, fix_t=args.fix_t, **kw)
+    if args.run_tangent_space_pga:                                               # likewise after the sampling job
+        kw = dict(h_t=args.h_t_values if args.h_t_list else args.h_t, op=args.op, block_idx=args.block_idx, pca_rank=args.pca_rank,
+                  num_local_basis=args.num_local_basis, space=args.distance_space, pga_base=args.pga_base, pga_modes=args.pga_modes or None)
+        if args.is_stable_diffusion:
+            edit.run_tangent_space_pga(edit_prompt=args.edit_prompt, **kw)
+        else:
+            edit.run_tangent_space_pga(fix_xt=args.fix_xt, fix_t=args.fix_t, **kw)
     if args.run_edit_parallel_transport:                                         # main.py:36-40 (which fixes op='mid', block_idx=0, vis_num=4, vis_num_pc=2, pca_rank=50)
         edit.run_edit_parallel_transport(sample_idx_0=args.sample_idx_0,
                                          sample_idx_1=args.sample_idx_1_values if args.sample_idx_1_list else args.sample_idx_1, op=args.op,

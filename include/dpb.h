@@ -333,6 +333,48 @@ int dpb_frechet_finish(const float* X, float* Y, float* weight, float* theta, do
 const double* dpb_frechet_ghat(int B, int k, int64_t N, int max_iter, const void* scratch);
 int dpb_frechet_start(const double* Ct, int B, int k, int64_t N, int max_iter, void* scratch, size_t scratch_bytes, void* hip_stream);
 
+/* ---- Principal geodesic analysis of subspaces (additive to ABI version 1; engine-independent) ----------------------------------------------
+ * How the members of a set of local bases vary around a base point Y: PCA of their log maps L_i = Log_Y(span X_i) under <A, B> = tr(A B^T)
+ * (geometry.grassmann_pga, the analysis of run_tangent_space_pga).  The calls work on a Frechet scratch block whose point is Y, after
+ * dpb_frechet_finish (init alone: a member; init + start: a caller's coefficients; init + iterate: the Karcher mean); nothing of length N is touched
+ * before dpb_pga_combine.  `members` is B, or B - 1 when the last basis of the block is a base point stacked by the caller: it is then part of the
+ * Gram and of no statistic.  J: the most weight rows one dpb_pga_combine takes (modes + slopes + intercept), 1 <= J <= 80; the same (B, members, k,
+ * N, J) and the same pga scratch go to all three calls, in this order.
+ *
+ * Method.  With Q_i the whitened members, M_i = Y Q_i^T, I - M_i M_i^T = V sin^2(theta) V^T and F_i = V theta / (sin cos) V^T (the log map of
+ * dpb_frechet_iterate, the same cosine rule above pi/4), E_i = F_i M_i and K_i = F_i M_i M_i^T: L_i = E_i Q_i - K_i Y, and since Y Y^T = I and
+ * Q_a Y^T = M_a^T the inner product closes in k x k algebra, T_ab = tr(E_a Ghat_ab E_b^T) - tr(K_a K_b), T_aa = sum_j theta_aj^2: one pass over Ghat,
+ * a workgroup per pair a < b, mirrored (exactly symmetric).  Off the diagonal the two traces are of size k and their difference of size theta^2: an
+ * absolute error near k 2^-50, negligible for angles above 1e-4 rad.
+ *   dpb_pga_tangent_gram: T [members][members] fp64, theta [members][k] fp32 (descending), state [members] int32: 0 valid, 1 degenerate (the flag of
+ *     the whitening), 2 the largest angle to Y exceeds pi/2 - 1e-6 (outside the log map's domain), 4 otherwise not finite.
+ *   NaN rule: an invalid member has NaN in its whole row and column of T, the diagonal included, and nowhere else; the rows of a degenerate member are
+ *     left out of M = C Ghat, so the other members' entries do not see it.  (dpb_frechet_finish itself returns NaN for Y when a member is degenerate.)
+ *   dpb_pga_eig: the members whose diagonal entry is a number are the valid ones, nv of them.  Tc = H T H over them (center != 0; H = I - 1 1^T / nv) or
+ *     T, the rows and columns of the others zero.  Tc u = mu u by the round-robin Jacobi in one workgroup while members <= 128 (the matrix in LDS,
+ *     160 KiB), above that -- or when dpb_debug_set("pga_route", 2) forces it -- by the flag-mean solver (block subspace iteration with a Rayleigh-Ritz
+ *     step, 200 iterations at most, to a residual of 1e-13) on Tc as a Gram of one-row bases.  M <= min(64, members, J) modes in descending order.  Mode
+ *     m = sum_i Wt[m][i] L_i, Wt[m] = H u_m / sqrt(mu_m): unit Frobenius norm; sign: the largest-magnitude score is positive; magnitudes within 1e-9 relative of it tie, and the lowest member wins.
+ *     An eigenvalue that is not above 1e-13 of the largest, or not above members k 2^-46 (the rounding floor of T), carries no mode: zero weights,
+ *     variance and scores.
+ *     out fp64 [72 + members M + members]: [0] nv, [1] total variance tr(Tc) / nv, [2] ||mean tangent||_F = sqrt(1^T T 1) / nv, [3] the route (1 Jacobi,
+ *     2 subspace), [4] / [5] the subspace solver's iterations and status, [8 .. 8 + M) variance mu_m / nv, then scores [members][M] = sqrt(mu_m) u_mi
+ *     (NaN rows for invalid members), then residual [members], residual_i^2 = Tc_ii - sum_m scores_im^2 clamped at 0.
+ *   dpb_pga_combine: out fp32 [rows][k][N] = the tangents sum_i Wt[j][i] L_i for `rows` <= J weight rows Wt [rows][members] fp64 on the device (modes
+ *     from dpb_pga_eig, or any others: regression slopes, the intercept), invalid members left out.  Coefficients Zq = (blocks w_i E_i) - (sum_i w_i K_i) C
+ *     on the whitened rows in fp64, rotated by the rotation dpb_frechet_finish applied to Y -- row j of every output is the image of row j of that Y,
+ *     the convention of dpb_grassmann_pair mode 1 / dpb_grassmann_exp -- and composed with the whitenings; then all rows k outputs go through the
+ *     coefficient stream of dpb_frechet_finish, 64 output rows per pass over X, summed over the rows of X in index order in fp64, rounded once.
+ * Limits: those of dpb_frechet_* (k <= 64, k <= N, B <= 65535, B k <= 2^20).  Scratch: 256-byte aligned, >= dpb_pga_scratch_bytes (checked; 0 when the
+ * arguments are invalid).  No atomics, every sum a fixed chain: bitwise reproducible.  No host synchronisation in any call. */
+size_t dpb_pga_scratch_bytes(int B, int members, int k, int64_t N, int J);
+int dpb_pga_tangent_gram(int B, int members, int k, int64_t N, int max_iter, int J, void* frechet_scratch, size_t frechet_bytes, double* T, float* theta,
+                         int32_t* state, void* scratch, size_t scratch_bytes, void* hip_stream);
+int dpb_pga_eig(const double* T, int B, int members, int k, int64_t N, int J, int M, int center, double* Wt, double* out, void* scratch, size_t scratch_bytes,
+                void* hip_stream);
+int dpb_pga_combine(const float* X, const double* Wt, int rows, float* out, int B, int members, int k, int64_t N, int max_iter, int J, void* frechet_scratch,
+                    size_t frechet_bytes, void* scratch, size_t scratch_bytes, void* hip_stream);
+
 /* ---- Flag (extrinsic, chordal) mean of subspaces (additive to ABI version 1; engine-independent) -----------------------------------------
  * The global basis of run_edit_global_flag_mean_zt (Draper et al. 2014; Marrinan et al., CVPR 2014): the top-r eigenvectors of the mean projector
  * P = (1/B) sum_i Q_i^T Q_i over the orthonormalised bases Q_i = W_i X_i.  Closed form, no cut locus, defined for every rank r, nested (rows 0..j-1
