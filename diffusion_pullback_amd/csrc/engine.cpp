@@ -1850,6 +1850,112 @@ int dpb_local_pca_sample(dpb_engine* e, const float* x, float t, const float* ct
   return r;
 }
 
+// The parallel-h edit chain (reference src/modules/edit.py:1202-1229, :1470-1497): chain.hip between the engine's own passes
+size_t dpb_direction_step_scratch_bytes(int64_t n, int64_t N) { return direction_step_scratch_bytes(n, N); }
+
+int dpb_direction_step(const float* W, const float* x, float* x_out, float* vk, const float* step, float sega_sigma, int64_t n, int64_t N, double* stats,
+                       void* scratch, size_t scratch_bytes, void* stream) {
+  if (!W || !x || !x_out || !step || !stats || !scratch) return fail("dpb_direction_step: null argument");
+  return launch_direction_step(W, x, x_out, vk, step, sega_sigma, n, N, stats, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int dpb_shift_stats(const float* h, const float* h0, const float* u, int nu, const int32_t* dir, const float* sign, int64_t n, int64_t D, double* out,
+                    void* stream) {
+  if (!h || !h0 || !u || !dir || !sign || !out) return fail("dpb_shift_stats: null argument");
+  return launch_shift_stats(h, h0, u, nu, dir, sign, n, D, out, (hipStream_t)stream);
+}
+
+namespace {
+struct ChainScratch { size_t W = 0, cot = 0, h = 0, h0 = 0, part = 0, total = 0; long n_in = 0, n_h = 0; };
+bool chain_layout(const dpb_engine* e, int tap, int n, ChainScratch& l) {
+  if (!e || tap < 0 || tap >= (int)e->bufs.size() || n < 1) return false;
+  l.n_in = (long)e->bufs[e->x_buf].rows * e->x_channels;
+  l.n_h = (long)e->bufs[tap].rows * e->bufs[tap].Cv;
+  size_t off = 0;
+  auto take = [&](size_t b) { const size_t o = off; off += align_up(b); return o; };
+  l.W = take((size_t)n * l.n_in * sizeof(float));
+  l.cot = take((size_t)n * l.n_h * sizeof(float));
+  l.h = take((size_t)n * l.n_h * sizeof(float));
+  l.h0 = take((size_t)n * l.n_h * sizeof(float));
+  l.part = take(direction_step_scratch_bytes(n, l.n_in));
+  l.total = off;
+  return true;
+}
+}  // namespace
+
+size_t dpb_inv_jac_chain_scratch_bytes(const dpb_engine* e, int tap_buf, int n) {
+  ChainScratch l;
+  return chain_layout(e, tap_buf, n, l) ? l.total : 0;
+}
+
+int dpb_inv_jac_chain(dpb_engine* e, int tap_buf, const float* x, int n, const float* t, const float* ctx, const float* u, int nu, const int32_t* dir,
+                      const float* sign, const float* step, int steps, float sega_sigma, int final_shift, float* states, float* vk, double* stats,
+                      double* shift, void* scratch, size_t scratch_bytes) {
+  if (!e || !x || !t || !u || !dir || !sign || !step || !states || !stats || !shift || !scratch) return fail("dpb_inv_jac_chain: null argument");
+  e->cur_batch = 0;                                // as dpb_forward: whatever happens below, the primal state is gone
+  if (!e->ws) return fail("workspace not set (dpb_engine_set_workspace)");
+  const int cap = std::min(e->maxB, e->maxT);
+  if (n < 1 || n > cap) return fail("dpb_inv_jac_chain: n=%d chains outside [1,%d] (min of max_batch and max_tangents)", n, cap);
+  if (steps < 1) return fail("dpb_inv_jac_chain: steps=%d < 1", steps);
+  if (nu < 1) return fail("dpb_inv_jac_chain: nu=%d: at least one direction is needed", nu);
+  for (int b = 0; b < n; ++b) {
+    if (dir[b] < 0 || dir[b] >= nu) return fail("dpb_inv_jac_chain: dir[%d]=%d outside [0,%d)", b, dir[b], nu);
+    if (!isfinite(sign[b])) return fail("dpb_inv_jac_chain: sign[%d] is not finite", b);
+    if (!isfinite(step[b])) return fail("dpb_inv_jac_chain: step[%d] is not finite", b);
+  }
+  if (std::isnan(sega_sigma)) return fail("dpb_inv_jac_chain: sega_sigma is NaN");
+  const float* tv;
+  if (int r = check_timesteps(e, n, t, &tv)) return r;
+  if (tap_buf < 0 || tap_buf >= (int)e->bufs.size() || e->producer[tap_buf] < 0 || e->bufs[tap_buf].kind != DPB_BUF_ACT)
+    return fail("dpb_inv_jac_chain: invalid tap buffer %d (an activation produced by an op)", tap_buf);
+  if (e->bufs[tap_buf].is_const) return fail("dpb_inv_jac_chain: tap buffer %d does not depend on x", tap_buf);
+  if (e->ctx_buf >= 0 && !ctx) return fail("this network needs ctx (encoder_hidden_states)");
+  ChainScratch l;
+  chain_layout(e, tap_buf, n, l);
+  if ((uintptr_t)scratch % 256) return fail("dpb_inv_jac_chain: scratch must be 256-byte aligned");
+  if (scratch_bytes < l.total) return fail("dpb_inv_jac_chain: scratch of %zu bytes, dpb_inv_jac_chain_scratch_bytes = %zu", scratch_bytes, l.total);
+  char* sc = (char*)scratch;
+  float *Wb = (float*)(sc + l.W), *cot = (float*)(sc + l.cot), *hb = (float*)(sc + l.h), *h0 = (float*)(sc + l.h0);
+  const Buf& bt = e->bufs[tap_buf];
+  const size_t row = (size_t)n * l.n_in;
+  const long at = launch_count;                     // the sub-passes' LaunchSpans overwrite n_launch as they go: the assignment at the end is what counts
+  double fl = 0, gb = 0;
+  if (states != x) DPB_CHECK(hipMemcpyAsync(states, x, row * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+  // the tap activation of the pass just run, as fp32 NCHW, and its shift statistics against the copy kept from step 0
+  auto shift_of = [&](int j) -> int {
+    float* dst = j == 0 ? h0 : hb;
+    if (int r = launch_nhwc_to_nchw(e->dtype, e->P(tap_buf), dst, n, bt.Cv, bt.rows, bt.C, e->stream)) return r;
+    return launch_shift_stats(dst, h0, u, nu, dir, sign, n, l.n_h, shift + (size_t)j * n * 2, e->stream);
+  };
+  int r = 0;
+  for (int j = 0; j < steps && !r; ++j) {
+    const float* xj = states + (size_t)j * row;
+    Forward f;
+    f.temb_resident = j > 0;                        // same timesteps as the step before: their embeddings are still in P(temb_buf), no upload, no sync
+    r = primal_pass(e, xj, n, t[0], ctx, tap_buf, f, tv);
+    fl += e->flops; gb += e->gbytes;
+    if (!r) r = shift_of(j);
+    if (!r) r = launch_gather_cotangents(u, nu, dir, sign, n, l.n_h, cot, e->stream);
+    if (!r) r = vjp_pass(e, e->x_buf, tap_buf, cot, n, Wb);
+    fl += e->flops; gb += e->gbytes;
+    if (!r) r = launch_direction_step(Wb, xj, states + (size_t)(j + 1) * row, vk ? vk + (size_t)j * row : nullptr, step, sega_sigma, n, l.n_in,
+                                      stats + (size_t)j * n * 4, sc + l.part, l.total - l.part, e->stream);
+  }
+  if (!r && final_shift) {
+    Forward f;
+    f.stash = false; f.temb_resident = true;
+    r = primal_pass(e, states + (size_t)steps * row, n, t[0], ctx, tap_buf, f, tv);
+    fl += e->flops; gb += e->gbytes;
+    if (!r) r = shift_of(steps);
+  } else if (!r) {
+    DPB_CHECK(hipMemsetAsync(shift + (size_t)steps * n * 2, 0xff, (size_t)n * 2 * sizeof(double), e->stream));   // all bits set: a NaN
+  }
+  e->cur_batch = 0;                                // no primal state is left behind
+  e->primal_last = -1;
+  e->n_launch = launch_count - at; e->flops = fl; e->gbytes = gb;
+  return r;
+}
+
 static int g_iter_alias = getenv("DPB_ITER_ALIAS") ? atoi(getenv("DPB_ITER_ALIAS")) : 1;   // A/B switch: 0 = convert U out and back in every iteration
 static int g_orth_batch = getenv("DPB_ORTH_BATCH") ? atoi(getenv("DPB_ORTH_BATCH")) : 1;   // A/B switch: 0 = re-orthonormalise the samples of a batch one by one
 static int g_graph_iterate = 0;      // dpb_debug_set("graph_iterate", 1): replay the power iteration as a captured hipGraph (measurement option)

@@ -492,6 +492,19 @@ size_t perturb_scratch_bytes(int B, long n);             // 0 when invalid
 int launch_perturb_unit(const float* x, const float* noise, uint64_t seed, int64_t first, int B, long n, float norm, float* out, float* noise_out,
                         void* scratch, size_t scratch_bytes, hipStream_t st);
 
+// ---------------------------------------------------------------- the parallel-h edit chain (chain.hip): what lies between the U-Net passes of a step
+// direction step: W = J^T c [n][N] -> v = -W / ||W|| (fp64, rounded once), the SEGA mask (sega_sigma <= 0: off), x_out = x + step[b] v (x_out may alias
+// x; vk optional), stats [n][4] fp64 on the device = (sum w^2, std or 0, elements kept, flag); step: a HOST array; see include/dpb.h
+constexpr int CHAIN_MAX_ROWS = 256;       // rows per launch: the host lists (step; dir and sign) travel as kernel arguments
+size_t direction_step_scratch_bytes(long n, long N);     // 0 when invalid
+int launch_direction_step(const float* W, const float* x, float* x_out, float* vk, const float* step, float sega_sigma, long n, long N, double* stats,
+                          void* scratch, size_t scratch_bytes, hipStream_t st);
+// out [n][2] fp64 = (<h - h0, c> / ||c||, ||h - h0||^2), c = sign[b] u[dir[b]]; u [nu][D] on the device, dir / sign HOST arrays (validated here)
+int launch_shift_stats(const float* h, const float* h0, const float* u, int nu, const int32_t* dir, const float* sign, long n, long D, double* out,
+                       hipStream_t st);
+// cot[b] = sign[b] u[dir[b]]: the chain's cotangents, one per sample
+int launch_gather_cotangents(const float* u, int nu, const int32_t* dir, const float* sign, long n, long D, float* cot, hipStream_t st);
+
 // ---------------------------------------------------------------- DDIM
 // x_next = sqrt(a_next) * (x - e*sqrt(1-a_t))/sqrt(a_t) + sqrt(1-a_next) * e      (fp32, elementwise)
 int launch_ddim_step(const float* x, const float* e, float* out, float* x0, long n, float a_t, float a_next, hipStream_t st);

@@ -657,6 +657,12 @@ class EditUncondDiffusion(_EditBase):
         self.x_space_guidance_edit_step = args.x_space_guidance_edit_step
         self.x_space_guidance_scale = args.x_space_guidance_scale
         self.x_space_guidance_num_step = args.x_space_guidance_num_step
+        # "parallel-x": every chain of the global-basis jobs pushes along one x-space direction fixed at x_t (x-space guidance).  "parallel-h": the
+        # h-space direction is held fixed and the x-space direction is recomputed at every state (edit.py:1202-1229; _run_parallel_h_chains)
+        self.edit_xt = getattr(args, "edit_xt", "parallel-x")
+        self.x_edit_step_size = getattr(args, "x_edit_step_size", 0.0)
+        self.use_sega_reg = bool(getattr(args, "use_sega_reg", False))
+        self.sega_reg_sigma = getattr(args, "sega_reg_sigma", 1.0)
         self.result_folder, self.obs_folder = args.result_folder, args.obs_folder
         self.input_root = getattr(args, "input_root", "./inputs")
         self.EXP_NAME = "exp"
@@ -939,8 +945,10 @@ class EditUncondDiffusion(_EditBase):
         through geometry.transport_directions; local_projection=False uses v itself and is valid for space x only (for h the reference leaves vk
         undefined).  Then the x-space-guidance path of the driver's other jobs: chains named xt-<dataset>_<idx>-h_<h_t>T-edit_<edit_t>T-<op>-block_<b>-
         seed_<seed>-pc_<pc>_{pos,neg}, pictures x0_gen-<name>.png, projection_coeff-<name>.png in the obs folder; the job is skipped when the last
-        pc's _neg picture exists, an experiment when its own does.  trajectory_batch as in run_edit_parallel_transport.  The reference's parallel-h
-        and h_space_guidance branches are not built.  Returns a dict: basis [k, N] (rows), vk [P, N_x], pcs, names, info (None for a loaded basis).
+        pc's _neg picture exists, an experiment when its own does.  trajectory_batch as in run_edit_parallel_transport.
+        edit_xt "parallel-h" (space h only; local_projection=False allowed): the chains of _run_parallel_h_chains instead.
+        The reference's h_space_guidance branch is not built.
+        Returns a dict: basis [k, N] (rows), vk [P, N_x], pcs, names, info (None for a loaded basis).
         frechet_init "member" starts the iteration at local basis 0, "flag" at the flag mean of them all (geometry.frechet_mean(init="flag")); the
         info file of a "flag" run records it as ``init``."""
         from . import geometry
@@ -948,7 +956,8 @@ class EditUncondDiffusion(_EditBase):
             raise ValueError(f"frechet_init must be 'member' (start at local basis 0) or 'flag' (start at the flag mean), got {frechet_init!r}")
         if frechet_mean_space not in ("x", "h"):
             raise ValueError(f"frechet_mean_space must be 'x' (the spans of vT) or 'h' (the spans of u), got {frechet_mean_space!r}")
-        if frechet_mean_space == "h" and not local_projection:
+        self._check_parallel_h(frechet_mean_space)
+        if frechet_mean_space == "h" and not local_projection and self.edit_xt != "parallel-h":
             raise ValueError("local_projection=False is valid for frechet_mean_space 'x' only: an h-space direction reaches x-space through the sample's "
                              "own local basis (the reference leaves vk undefined there)")
         h_t = self.h_t if h_t is None else h_t
@@ -1031,7 +1040,8 @@ class EditUncondDiffusion(_EditBase):
             raise ValueError(f"flag_mean_kind must be 'mean' (geometry.flag_mean) or 'median' (geometry.flag_median), got {flag_mean_kind!r}")
         if flag_mean_space not in ("x", "h"):
             raise ValueError(f"flag_mean_space must be 'x' (the spans of vT) or 'h' (the spans of u), got {flag_mean_space!r}")
-        if flag_mean_space == "h" and not local_projection:
+        self._check_parallel_h(flag_mean_space)
+        if flag_mean_space == "h" and not local_projection and self.edit_xt != "parallel-h":
             raise ValueError("local_projection=False is valid for flag_mean_space 'x' only: an h-space direction reaches x-space through the sample's "
                              "own local basis")
         r = int(pca_rank if not flag_rank else flag_rank)
@@ -1101,7 +1111,10 @@ class EditUncondDiffusion(_EditBase):
         (space "x") or of h-space ("h").  The sample's own local basis (u, vT) at h_t is loaded or computed and saved; with local_projection
         vk = normalise(vT^T (vT v)) for x and normalise(vT^T (u^T u_k)) for h, both through geometry.transport_directions; without it (x only) v itself.
         Then the x-space-guidance chains xt-<dataset>_<idx>-h_<h_t>T-edit_<edit_t>T-<op>-block_<b>-seed_<seed>-pc_<pc>_{pos,neg}, an experiment skipped
-        when its picture exists, and projection_coeff-<name>.png (its u series from rows pcs of basis_h [k, N_h], when given).  Fills and returns out."""
+        when its picture exists, and projection_coeff-<name>.png (its u series from rows pcs of basis_h [k, N_h], when given).  edit_xt "parallel-h"
+        (space h): the same names, skip rule and order, but every chain follows its h-direction through _run_parallel_h_chains; with
+        local_projection the local basis and the plot are produced as above, without it no local-basis file is read or written.  Fills and returns
+        out (parallel-h adds "chains", the chain records)."""
         from . import geometry
         exp = lambda pc, tag: f"xt-{self.dataset_name}_{idx}-h_{h_t}T-edit_{self.edit_t}T-{op}-block_{block_idx}-seed_{self.seed}-pc_{pc:0=3d}_{tag}"
         picture = lambda name: os.path.exists(os.path.join(self.result_folder, f"x0_gen-{name}.png"))
@@ -1112,7 +1125,8 @@ class EditUncondDiffusion(_EditBase):
         xT = self._random_latent(idx) if self.dataset_name == "Random" else self.run_DDIMinversion(idx=idx)      # edit.py:1082-1085
         own_dir, own_name = self._tangent_space_naming(op, block_idx, pca_rank)
         files = self._basis_paths(own_dir, own_name(idx, h_t))
-        have = os.path.exists(files[0]) and os.path.exists(files[2])
+        parallel_h = self.edit_xt == "parallel-h"
+        have = os.path.exists(files[0]) and os.path.exists(files[2]) and (local_projection or not parallel_h)   # (parallel-h reads it for the plot only)
         if local_projection and not have:
             print("!!!SAMPLE LOCAL TANGENT SPACE!!!")
             at_h = self.DDIMforwardsteps(xT, t_start_idx=0, t_end_idx=h_t_idx)[:2]
@@ -1125,6 +1139,12 @@ class EditUncondDiffusion(_EditBase):
         original_xt = self.DDIMforwardsteps(xT, t_start_idx=0, t_end_idx=self.edit_t_idx)[0].detach()            # edit.py:1136-1137
         shape = original_xt.shape[1:]
         if not pcs:
+            return out
+        if parallel_h and not local_projection:             # edit.py:1202-1229 never reads vk: nothing of the local basis is needed
+            out["vk"] = None
+            chains = [(exp(pc, tag), original_xt, pc, sign) for pc in pcs for sign, tag in ((1, "pos"), (-1, "neg")) if not picture(exp(pc, tag))]
+            out["names"] = [c[0] for c in chains]
+            out["chains"] = self._run_parallel_h_chains(chains, basis, op, block_idx, vis_num, shape)
             return out
         if local_projection:
             with T.phase("projection of the global directions on the local basis"):
@@ -1146,8 +1166,66 @@ class EditUncondDiffusion(_EditBase):
                     save_projection_plot(None if uk is None else (u / u.norm(dim=0, keepdim=True)).t() @ uk,
                                          (vT / vT.norm(dim=1, keepdim=True)) @ (sign * vk[p]), os.path.join(self.obs_folder, f"projection_coeff-{exp(pc, tag)}.png"))
         out["names"] = [c[0] for c in chains]
+        if parallel_h:                                       # the projection above is the plot's only: the chain follows the h-direction itself
+            by_name = {exp(pc, tag): (pc, sign) for pc in pcs for sign, tag in ((1, "pos"), (-1, "neg"))}
+            out["chains"] = self._run_parallel_h_chains([(c[0], c[1], *by_name[c[0]]) for c in chains], basis, op, block_idx, vis_num, shape)
+            return out
         self._run_direction_chains(chains, vis_num, shape)
         return out
+
+    def _check_parallel_h(self, space):
+        """what --edit_xt asks of a global-basis job, checked before anything is computed"""
+        if self.edit_xt not in ("parallel-x", "parallel-h"):
+            raise ValueError(f"edit_xt must be 'parallel-x' or 'parallel-h', got {self.edit_xt!r}")
+        if self.edit_xt != "parallel-h":
+            return
+        if space != "h":
+            raise ValueError("edit_xt 'parallel-h' follows an h-space direction: it needs the h-space global basis (space 'h'); for space 'x' the "
+                             "reference leaves uk undefined")
+        if not (float(self.x_edit_step_size) > 0):
+            raise ValueError(f"edit_xt 'parallel-h' needs x_edit_step_size > 0, got {self.x_edit_step_size}")
+
+    def _run_parallel_h_chains(self, chains, basis_h, op, block_idx, vis_num, shape):
+        """The parallel-h branch (edit.py:1202-1229, :1470-1497).  chains: (EXP_NAME, start x_t [1, ...], pc, sign).  Each holds uk = sign *
+        basis_h[pc] / ||.|| fixed and takes vis_num steps x <- x + (x_edit_step_size / vis_num) * inv_jac_xt(x, t, uk) from its start at the timestep
+        timesteps[edit_t_idx] (the reference passes the INDEX edit_t_idx as t: not reproduced), with the SEGA rule when use_sega_reg; the states
+        xt[::int((vis_num + 1) / vis_num)] are decoded into x0_gen-<EXP_NAME>.png.  Each chain writes chain-<EXP_NAME>.pt into the obs folder (norm,
+        h_shift, h_dist, sega_std, sega_kept: one entry per step, the shifts one per state) and prints one line.  trajectory_batch > 1: all chains
+        through one unet.inv_jac_chain call and one decode batch; <= 1: one after another.  Returns the chain records, in order."""
+        if not chains:
+            return []
+        t = self.scheduler.timesteps[self.edit_t_idx]
+        uhat = (basis_h / basis_h.norm(dim=1, keepdim=True)).t().contiguous()                   # [N_h, k]: column pc is direction pc (edit.py:1152-1153)
+        sigma = float(self.sega_reg_sigma) if self.use_sega_reg else None
+        step = float(self.x_edit_step_size) / vis_num
+        stride = int((vis_num + 1) / vis_num)                                                   # edit.py:1218
+
+        def run(group):
+            self._phase = "parallel-h chain: one primal and one adjoint pass per step"
+            r = self.unet.inv_jac_chain(x=torch.cat([c[1] for c in group]).to(device=self.device, dtype=self.dtype), t=t, u=uhat,
+                                        dirs=[c[2] for c in group], signs=[float(c[3]) for c in group], steps=vis_num, step_size=step,
+                                        sega_sigma=sigma, op=op, block_idx=block_idx)
+            picked = r["states"][:, ::stride]
+            m = picked.size(1)
+            self._phase = "DDIM decode of the edited latents: U-Net forwards"
+            x0 = self.DDIMforwardsteps(picked.reshape(len(group) * m, *shape), t_start_idx=self.edit_t_idx, t_end_idx=-1, save_image_=False,
+                                       performance_boosting=True)
+            recs = []
+            for i, c in enumerate(group):
+                self.EXP_NAME = c[0]
+                save_image((x0[i * m:(i + 1) * m] / 2 + 0.5).clamp(0, 1), os.path.join(self.result_folder, f"x0_gen-{c[0]}.png"), nrow=m)
+                rec = {k: r[k][i].cpu() for k in ("norm", "h_shift", "h_dist", "sega_std", "sega_kept")}
+                torch.save(rec, os.path.join(self.obs_folder, f"chain-{c[0]}.pt"))
+                print(f"parallel-h chain {c[0]}: {vis_num} steps of {step:g}, ||J^T u|| {float(rec['norm'][0]):.4g} -> {float(rec['norm'][-1]):.4g}, "
+                      f"h shift along u {float(rec['h_shift'][-1]):.4g}, |h - h0| {float(rec['h_dist'][-1]):.4g}"
+                      + (f", SEGA kept {int(rec['sega_kept'][-1])} elements" if sigma else ""))
+                recs.append(rec)
+            return recs
+
+        groups = [chains] if self.trajectory_batch > 1 else [[c] for c in chains]
+        recs = [rec for g in groups for rec in run(g)]
+        self._phase = _EditBase._phase
+        return recs
 
     def global_hungarian_mean_paths(self, op="mid", block_idx=0, pca_rank=50, h_t=None):
         """{"u": (basis file, info file), "v": ...} of the two Hungarian global bases, in the reference's layout (edit.py:1270-1274; the directory
@@ -1176,12 +1254,14 @@ class EditUncondDiffusion(_EditBase):
         loaded as is).  The reference's v load branch reloads u (edit.py:1350-1352): not reproduced.
         Edit: the common tail of the global-basis jobs (_edit_along_global_basis).  hungarian_mean_space "x": vk = normalise(vT^T (vT vhat_pc)), the
         reference's live path; "h": vk = normalise(vT^T (u^T uhat_pc)), the route the Frechet job uses to bring an h-direction to x.
-        local_projection=False is valid for "x" only.  The reference's parallel-h and h_space_guidance branches are not built.
+        local_projection=False is valid for "x" only -- and for edit_xt "parallel-h" (space h only), whose chains are those of
+        _run_parallel_h_chains.  The reference's h_space_guidance branch is not built.
         Returns a dict: basis_u [k, N_h], basis_v [k, N_x] (rows), vk [P, N_x], pcs, names, info ({"u": ..., "v": ...}, None for a loaded basis)."""
         from . import geometry
         if hungarian_mean_space not in ("x", "h"):
             raise ValueError(f"hungarian_mean_space must be 'x' (the directions of vT) or 'h' (the directions of u), got {hungarian_mean_space!r}")
-        if hungarian_mean_space == "h" and not local_projection:
+        self._check_parallel_h(hungarian_mean_space)
+        if hungarian_mean_space == "h" and not local_projection and self.edit_xt != "parallel-h":
             raise ValueError("local_projection=False is valid for hungarian_mean_space 'x' only: an h-space direction reaches x-space through the "
                              "sample's own local basis")
         if hungarian_distance not in geometry.HUNGARIAN_DISTANCES:

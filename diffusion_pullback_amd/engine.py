@@ -333,6 +333,45 @@ class Engine:
                                                   count, _ptr(out), C.c_void_p(self._lp_scratch.data_ptr() + off), need))
         return out.view(count, d)
 
+    # ------------------------------------------------------------------ the parallel-h edit chain on the device
+    def inv_jac_chain(self, x: torch.Tensor, t, ctx: Optional[torch.Tensor], tap, u: torch.Tensor, dirs, signs, step, steps: int,
+                      sega_sigma: float = 0.0, final_shift: bool = True, return_vk: bool = False):
+        """dpb_inv_jac_chain: n = x.shape[0] chains advanced together for `steps` steps with no Python between the steps.  x [n, C, H, W], t a float
+        or n timesteps, ctx [n or 1, L, D] or None, u [nu, N_h] fp32 directions of `tap` (NCHW-flattened), dirs / signs / step: host sequences of n
+        entries (chain b follows signs[b] * u[dirs[b]] with step[b] per step; each step moves x along -J^T c / ||J^T c||).  Returns device tensors
+        (states [steps + 1, n, C, H, W], vk [steps, n, N_in] or None, stats [steps, n, 4] fp64 = (||J^T c||^2, SEGA std, elements kept, flag),
+        shift [steps + 1, n, 2] fp64 = (<h - h0, c> / ||c||, ||h - h0||^2)); no host sync beyond the one of the first primal pass.  Like forward(),
+        keeps no primal state."""
+        buf = self.tape.taps[tap]
+        steps = int(steps)
+        with torch.cuda.device(self.device):
+            self._set_stream()
+            x, n, ctx = self._inputs(x, ctx)
+            tl = timesteps(t, n)
+            tl = [tl] * n if isinstance(tl, float) else tl
+            dirs, signs, step = [int(d) for d in dirs], [float(s) for s in signs], [float(s) for s in step]
+            if not (len(dirs) == len(signs) == len(step) == n):
+                raise L.DpbError(f"dirs, signs and step have {len(dirs)}, {len(signs)} and {len(step)} entries for {n} chains: one of each per chain")
+            d = self.tap_numel(tap)
+            if u.numel() == 0 or u.numel() % d:
+                raise L.DpbError(f"u has {u.numel()} elements, not a whole number of directions of {d} (tap {tap})")
+            u = _f32(u, self.device).reshape(-1, d)
+            ns = max(steps, 1)
+            states = torch.empty(ns + 1, n, *x.shape[1:], dtype=torch.float32, device=self.device)
+            vk = torch.empty(ns, n, self.n_in, dtype=torch.float32, device=self.device) if return_vk else None
+            stats = torch.empty(ns, n, 4, dtype=torch.float64, device=self.device)
+            shift = torch.empty(ns + 1, n, 2, dtype=torch.float64, device=self.device)
+            need = int(self.lib.dpb_inv_jac_chain_scratch_bytes(self.h, buf, n))
+            if getattr(self, "_chain_scratch", None) is None or self._chain_scratch.numel() < need + 256:
+                self._chain_scratch = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+            off = (-self._chain_scratch.data_ptr()) % 256
+            self.batch = 0
+            L.check(self.lib.dpb_inv_jac_chain(self.h, buf, _ptr(x), n, (C.c_float * n)(*tl), _ptr(ctx), _ptr(u), u.shape[0], (C.c_int32 * n)(*dirs),
+                                               (C.c_float * n)(*signs), (C.c_float * n)(*step), steps, float(sega_sigma), int(bool(final_shift)),
+                                               _ptr(states), _ptr(vk), _ptr(stats), _ptr(shift),
+                                               C.c_void_p(self._chain_scratch.data_ptr() + off), need))
+        return states, vk, stats, shift
+
     def profile(self, enable: bool):
         L.check(self.lib.dpb_engine_profile(self.h, int(enable)))
 
@@ -402,3 +441,54 @@ def perturb_unit(x: torch.Tensor, B: int, noise: Optional[torch.Tensor] = None, 
         L.check(lib.dpb_perturb_unit(_ptr(x), _ptr(noise), C.c_uint64(int(seed) & (2 ** 64 - 1)), int(first), B, n, float(norm), _ptr(out), _ptr(g),
                                      _ptr(scratch), need, C.c_void_p(st)))
     return (out, g) if return_noise else out
+
+
+def direction_step(W: torch.Tensor, x: torch.Tensor, step, sega_sigma: float = 0.0, out: Optional[torch.Tensor] = None, return_vk: bool = True):
+    """dpb_direction_step (engine-independent): per row b of W [n, N] (the adjoint results J^T c) and x [n, N], fp32 on a HIP device,
+    v = -W_b / ||W_b||, the SEGA rule v <- where(|v| < sega_sigma * std(v), 0, v) when sega_sigma > 0, x_out = x + step[b] * v.  step: a float or a
+    host sequence of n.  out: the tensor x_out is written into (x itself for an in-place step), allocated here when None.  Returns (x_out, vk or
+    None, stats [n, 4] fp64 = (||W_b||^2, std or 0, elements kept, flag)); a zero or non-finite row has its flag set and NaN in its row of x_out
+    and vk.  No host sync (include/dpb.h states the arithmetic)."""
+    lib = L.load()
+    if not (W.is_cuda and W.dim() == 2 and W.dtype == torch.float32 and W.is_contiguous()):
+        raise L.DpbError("W must be a contiguous fp32 [n, N] tensor on a HIP device")
+    n, N = W.shape
+    if not (x.is_cuda and x.device == W.device and x.dtype == torch.float32 and x.is_contiguous() and x.numel() == n * N):
+        raise L.DpbError(f"x must be a contiguous fp32 tensor of {n * N} elements on {W.device}")
+    step = [float(step)] * n if not isinstance(step, (list, tuple)) and not torch.is_tensor(step) else [float(s) for s in step]
+    if len(step) != n:
+        raise L.DpbError(f"step has {len(step)} entries for {n} rows")
+    with torch.cuda.device(W.device):
+        st = torch.cuda.current_stream(W.device).cuda_stream
+        if out is None:
+            out = torch.empty_like(x)
+        elif not (out.is_cuda and out.device == W.device and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n * N):
+            raise L.DpbError(f"out must be a contiguous fp32 tensor of {n * N} elements on {W.device}")
+        vk = torch.empty_like(W) if return_vk else None
+        stats = torch.empty(max(n, 1), 4, dtype=torch.float64, device=W.device)
+        need = int(lib.dpb_direction_step_scratch_bytes(n, N))
+        scratch = torch.empty(max(need // 8, 1), dtype=torch.float64, device=W.device)
+        L.check(lib.dpb_direction_step(_ptr(W), _ptr(x), _ptr(out), _ptr(vk), (C.c_float * max(n, 1))(*step), float(sega_sigma), n, N, _ptr(stats),
+                                       _ptr(scratch), need, C.c_void_p(st)))
+    return out, vk, stats
+
+
+def shift_stats(h: torch.Tensor, h0: torch.Tensor, u: torch.Tensor, dirs, signs) -> torch.Tensor:
+    """dpb_shift_stats (engine-independent): h, h0 [n, D] and u [nu, D] fp32 on a HIP device, dirs / signs host sequences of n.  Returns [n, 2]
+    fp64 on the device: (<h - h0, c> / ||c||, ||h - h0||^2) with c = signs[b] * u[dirs[b]].  No host sync."""
+    lib = L.load()
+    for name, a in (("h", h), ("h0", h0), ("u", u)):
+        if not (a.is_cuda and a.dim() == 2 and a.dtype == torch.float32 and a.is_contiguous()):
+            raise L.DpbError(f"{name} must be a contiguous fp32 2-D tensor on a HIP device")
+    n, D = h.shape
+    if tuple(h0.shape) != (n, D) or u.shape[1] != D:
+        raise L.DpbError(f"h {tuple(h.shape)}, h0 {tuple(h0.shape)} and u {tuple(u.shape)} do not agree: [n, D], [n, D], [nu, D]")
+    dirs, signs = [int(d) for d in dirs], [float(s) for s in signs]
+    if len(dirs) != n or len(signs) != n:
+        raise L.DpbError(f"dirs and signs have {len(dirs)} and {len(signs)} entries for {n} rows")
+    with torch.cuda.device(h.device):
+        st = torch.cuda.current_stream(h.device).cuda_stream
+        out = torch.empty(max(n, 1), 2, dtype=torch.float64, device=h.device)
+        L.check(lib.dpb_shift_stats(_ptr(h), _ptr(h0), _ptr(u), u.shape[0], (C.c_int32 * max(n, 1))(*dirs), (C.c_float * max(n, 1))(*signs), n, D,
+                                    _ptr(out), C.c_void_p(st)))
+    return out

@@ -151,6 +151,13 @@ SYMBOLS = {
     "dpb_matched_mean_scratch_bytes": (C.c_size_t, [_I, _I, _L]),
     "dpb_matched_mean": (_I, [_P, _I, _I, _L, _P, _I, _I, _P, _P, _P, _P, _P, C.c_size_t, _P]),
     "dpb_row_sumsq": (_I, [_P, _L, _L, _P, _P]),
+    # the parallel-h edit chain (PullbackUNet.inv_jac_chain): step, dir and sign are host arrays
+    "dpb_direction_step_scratch_bytes": (C.c_size_t, [_L, _L]),
+    "dpb_direction_step": (_I, [_P, _P, _P, _P, C.POINTER(_F), _F, _L, _L, _P, _P, C.c_size_t, _P]),
+    "dpb_shift_stats": (_I, [_P, _P, _P, _I, C.POINTER(C.c_int32), C.POINTER(_F), _L, _L, _P, _P]),
+    "dpb_inv_jac_chain_scratch_bytes": (C.c_size_t, [_P, _I, _I]),
+    "dpb_inv_jac_chain": (_I, [_P, _I, _P, _I, C.POINTER(_F), _P, _P, _I, C.POINTER(C.c_int32), C.POINTER(_F), C.POINTER(_F), _I, _F, _I,
+                               _P, _P, _P, _P, _P, C.c_size_t]),
 }
 
 _lib = None

@@ -48,6 +48,14 @@ names with -median appended; its info- file also ranks the local bases from typi
 edits --sample_idx along the other global basis: the Hungarian-matched mean of the same local bases -- the directions of every basis matched one to
 one and sign by sign to those of basis 0 and averaged (geometry.hungarian_mean; --hungarian_distance 1/cosine|cosine and --hungarian_max_sweeps are
 new).  Both bases are computed and cached, u-....pt from the u's and v-....pt from the vT's, each with an info- file; x edits along v, h along u.
+``--edit_xt parallel-x|parallel-h`` (the reference's flag, define_argparser.py:52) says how the three global-basis jobs move x_t.  parallel-x, the
+default, is the x-space guidance above: one x-space direction computed at x_t, pushed along at every step.  parallel-h (space h only; unconditional
+nets only) holds the h-space direction u_pc fixed instead and recomputes the x-space direction at every state: --vis_num steps
+x <- x + (--x_edit_step_size / vis_num) * inv_jac_xt(x, t, u_pc), all chains advanced together on the device (PullbackUNet.inv_jac_chain), then the same
+decode into the same picture names; --use_sega_reg True --sega_reg_sigma s zeroes the elements of each direction below s standard deviations
+(edit.py:1212-1214).  --local_projection False is allowed there and needs no local basis at all.  Every chain leaves chain-<name>.pt in the obs
+folder: ||J^T u||, the h-space shift along u and |h - h0| per step.  Deviations: t is the timestep (the reference passes the index edit_t_idx);
+the reference's dynamic_thresholding / preserve_norm / preserve_contrast are methods it never defines and are not built.
 """
 from __future__ import annotations
 
@@ -114,6 +122,10 @@ _FLAGS = [  # (name, type, default) -- define_argparser.py:20-110, live path onl
     # does (its flag has no consumer); hungarian_distance / hungarian_max_sweeps are new (the reference passes distance='1/cosine')
     ("run_edit_global_hungarian_mean_zt", str2bool, False), ("hungarian_mean_space", str, "x"), ("hungarian_distance", str, "1/cosine"),
     ("hungarian_max_sweeps", int, 20),
+    # define_argparser.py:52, :84: how the global-basis jobs move x_t.  parallel-x (default): x-space guidance along one direction fixed at x_t;
+    # parallel-h: the h-space direction held fixed, the x-space direction recomputed at every one of vis_num steps of x_edit_step_size / vis_num
+    # (edit.py:1202-1229), with the SEGA rule of edit.py:1212-1214 under --use_sega_reg (sega_reg_sigma 1.0: the reference's commented default)
+    ("edit_xt", str, "parallel-x"), ("use_sega_reg", str2bool, False), ("sega_reg_sigma", float, 1.0),
     # new
     ("pca_rank", int, 2), ("op", str, "mid"), ("block_idx", int, 0), ("vis_num", int, 4), ("vis_num_pc", int, 2), ("weights", str, ""),
     ("net_scale", str, "full"), ("vae", str, "none"), ("text_encoder", str, "none"), ("tokenizer_dir", str, ""),
@@ -157,7 +169,7 @@ def parse_args(argv=None):
                 "(its run_edit_global_frechet_mean_zt belongs to EditUncondDiffusion)")
     if args.run_edit_global_frechet_mean_zt and args.frechet_mean_space not in ("x", "h"):
         p.error("--frechet_mean_space must be x (the spans of vT) or h (the spans of u)")
-    if args.run_edit_global_frechet_mean_zt and args.frechet_mean_space == "h" and not args.local_projection:
+    if args.run_edit_global_frechet_mean_zt and args.frechet_mean_space == "h" and not args.local_projection and args.edit_xt != "parallel-h":
         p.error("--local_projection False is valid for --frechet_mean_space x only")
     if args.frechet_init not in ("member", "flag"):
         p.error("--frechet_init must be member (start at local basis 0) or flag (start at the flag mean of the local bases)")
@@ -166,7 +178,7 @@ def parse_args(argv=None):
                 "(its global-basis jobs belong to EditUncondDiffusion)")
     if args.run_edit_global_flag_mean_zt and args.flag_mean_space not in ("x", "h"):
         p.error("--flag_mean_space must be x (the spans of vT) or h (the spans of u)")
-    if args.run_edit_global_flag_mean_zt and args.flag_mean_space == "h" and not args.local_projection:
+    if args.run_edit_global_flag_mean_zt and args.flag_mean_space == "h" and not args.local_projection and args.edit_xt != "parallel-h":
         p.error("--local_projection False is valid for --flag_mean_space x only")
     if args.run_edit_global_flag_mean_zt and not 0 <= args.flag_rank <= args.pca_rank:
         p.error("--flag_rank must lie in [1, --pca_rank] (0: --pca_rank)")
@@ -182,12 +194,19 @@ def parse_args(argv=None):
                 "basis (its run_edit_global_hungarian_mean_zt belongs to EditUncondDiffusion)")
     if args.run_edit_global_hungarian_mean_zt and args.hungarian_mean_space not in ("x", "h"):
         p.error("--hungarian_mean_space must be x (the directions of vT) or h (the directions of u)")
-    if args.run_edit_global_hungarian_mean_zt and args.hungarian_mean_space == "h" and not args.local_projection:
+    if args.run_edit_global_hungarian_mean_zt and args.hungarian_mean_space == "h" and not args.local_projection and args.edit_xt != "parallel-h":
         p.error("--local_projection False is valid for --hungarian_mean_space x only")
     if args.run_edit_global_hungarian_mean_zt and args.hungarian_distance not in ("1/cosine", "cosine"):
         p.error("--hungarian_distance must be 1/cosine (the reference's call) or cosine")
     if args.run_edit_global_hungarian_mean_zt and args.hungarian_max_sweeps < 1:
         p.error("--hungarian_max_sweeps must be >= 1")
+    if args.edit_xt not in ("parallel-x", "parallel-h"):
+        p.error("--edit_xt must be parallel-x (x-space guidance along a direction fixed at x_t) or parallel-h (the h-space direction held fixed)")
+    if args.edit_xt == "parallel-h" and not args.x_edit_step_size > 0:
+        p.error("--edit_xt parallel-h needs --x_edit_step_size > 0: the chain takes --vis_num steps of x_edit_step_size / vis_num")
+    if args.edit_xt == "parallel-h" and "stable-diffusion" in args.model_name:
+        p.error("--edit_xt parallel-h belongs to the global-basis jobs of the unconditional nets: the reference's Stable Diffusion driver has no such "
+                "branch")
     if args.run_tangent_space_clusters:
         pairs = max(0, args.num_local_basis) * len(args.h_t_values)
         if not 1 <= args.num_clusters <= pairs:
@@ -303,6 +322,8 @@ def build_unet(args) -> PullbackUNet:
         if getattr(args, "trajectory_batch", 0) > 1:
             n = 2 * args.vis_num_pc
             max_batch = max(max_batch, min(args.trajectory_batch, 2 * n), min(args.trajectory_batch, n * (args.vis_num + 1)))
+            if getattr(args, "edit_xt", "parallel-x") == "parallel-h":      # the chains of one inv_jac_chain call: a cotangent each (max_batch holds them already)
+                max_rank = max(max_rank, min(args.trajectory_batch, n))
     if args.is_stable_diffusion:
         cfg = cf.sd_config_for(args.model_name)           # SD-v1.x or SD-2(.1)-base; anything else raises
         if small:

@@ -616,6 +616,73 @@ class PullbackUNet:
         -> vT [k, N_in] (the vendored class takes 2-D u)."""
         return self.inv_jac_zt(x, t, None, op=op, block_idx=block_idx, u=u, perturb_h=perturb_h)
 
+    # ------------------------------------------------------------------ the parallel-h edit chain
+    def inv_jac_chain(self, x=None, t=None, u=None, dirs=None, signs=None, steps=1, step_size=1.0, sega_sigma=None, encoder_hidden_states=None,
+                      op=None, block_idx=None, return_vk=False, final_shift=True, check=True):
+        """The --edit_xt parallel-h branch of the reference's global-basis edits (src/modules/edit.py:1202-1229, :1470-1497) as one device loop:
+        chain b starts at x[b] and takes `steps` steps x <- x + step_size * v with v = inv_jac_xt(x, t, u_b) = -J^T c / ||J^T c|| recomputed at
+        every state, c = signs[b] * u[:, dirs[b]] held fixed (dpb_inv_jac_chain: one primal and one adjoint pass per step for all chains together,
+        no Python between the steps).  Sign: v is the reference's inv_jac_xt, so a chain with sign +1 moves h AGAINST c -- h_shift is negative at
+        first order, about -step_size * ||J^T c|| / ||c|| per step.
+        x [n, C, H, W]; t a float or n timesteps; u [D] or [D, k] as inv_jac_* take it (column i is direction i); dirs: n column indices (default:
+        0, or 0 .. n-1 when k == n > 1); signs: n floats (default +1); step_size: a float or n; sega_sigma: None or <= 0 off, else v <- where(|v| <
+        sega_sigma * std(v), 0, v) at every step (the reference's use_sega_reg).  More chains than the engine's max_batch (or max_rank) run in
+        groups; a chain is never split.  Returns a dict of tensors on x.device: states [n, steps + 1, C, H, W] (states[:, 0] = x), norm [n, steps]
+        = ||J^T c||, sega_std [n, steps] (0 when off), sega_kept [n, steps] (elements the rule kept; N_in when off), h_shift [n, steps + 1] =
+        <h - h0, c> / ||c|| and h_dist [n, steps + 1] = ||h - h0|| at every state (final_shift=False: the last column is NaN and the forward pass
+        at the last state is saved), vk [n, steps, N_in] when return_vk.  A chain whose J^T c is zero or not finite at some step has NaN from there
+        on: ValueError names the chain and the step, check=False returns the NaNs."""
+        key = self._tap(op, block_idx)
+        eng = self.engine
+        d = eng.tap_numel(key)
+        if x is None or x.dim() != 4:
+            raise ValueError("x must be [n, C, H, W]")
+        n, steps = x.shape[0], int(steps)
+        if steps < 1:
+            raise ValueError(f"steps={steps} < 1")
+        if u is None or u.numel() % d != 0 or (u.dim() == 1 and u.numel() != d):
+            raise ValueError(f"u must be [{d}] or [{d}, k] (features of the tap ({op}, {block_idx}))")
+        U = u.reshape(1, d) if u.dim() == 1 else u.reshape(d, -1).T
+        U = U.to(device=self.device, dtype=torch.float32).contiguous()
+        k = U.shape[0]
+        if dirs is None:
+            dirs = list(range(n)) if k == n and n > 1 else [0] * n
+        dirs = [int(a) for a in (dirs.tolist() if torch.is_tensor(dirs) else dirs)]
+        signs = [1.0] * n if signs is None else [float(a) for a in (signs.tolist() if torch.is_tensor(signs) else signs)]
+        step = step_size.tolist() if torch.is_tensor(step_size) else step_size
+        step = [float(a) for a in step] if isinstance(step, (list, tuple)) else [float(step)] * n
+        if not (len(dirs) == len(signs) == len(step) == n):
+            raise ValueError(f"dirs, signs and step_size need one entry per chain ({n}), got {len(dirs)}, {len(signs)}, {len(step)}")
+        if any(a < 0 or a >= k for a in dirs):
+            raise ValueError(f"dirs {dirs} outside [0, {k}): u has {k} direction(s)")
+        tl = _timesteps(t, n)
+        tl = [tl] * n if isinstance(tl, float) else tl
+        ctx = encoder_hidden_states
+        if ctx is not None and ctx.shape[0] not in (1, n):
+            raise ValueError(f"encoder_hidden_states has {ctx.shape[0]} rows for {n} chains: one, or one per chain")
+        sigma = 0.0 if sega_sigma is None else float(sega_sigma)
+        group = max(1, min(eng.max_batch, eng.max_tangents))
+        parts = []
+        for b0 in range(0, n, group):
+            sl = slice(b0, min(b0 + group, n))
+            cg = None if ctx is None else (ctx if ctx.shape[0] == 1 else ctx[sl])
+            parts.append(eng.inv_jac_chain(x[sl], tl[sl], cg, key, U, dirs[sl], signs[sl], step[sl], steps, sigma, final_shift, return_vk))
+        states = torch.cat([p[0] for p in parts], dim=1).transpose(0, 1).contiguous()
+        stats = torch.cat([p[2] for p in parts], dim=1).transpose(0, 1)
+        shift = torch.cat([p[3] for p in parts], dim=1).transpose(0, 1)
+        out = {"states": states.to(device=x.device, dtype=x.dtype),
+               "norm": stats[..., 0].sqrt().to(x.device), "sega_std": stats[..., 1].to(x.device), "sega_kept": stats[..., 2].to(x.device),
+               "h_shift": shift[..., 0].to(x.device), "h_dist": shift[..., 1].sqrt().to(x.device)}
+        if return_vk:
+            out["vk"] = torch.cat([p[1] for p in parts], dim=1).transpose(0, 1).contiguous().to(device=x.device, dtype=x.dtype)
+        if check:
+            flag = stats[..., 3].cpu()
+            if bool((flag != 0).any()):
+                b, j = [int(a) for a in (flag != 0).nonzero()[0]]
+                raise ValueError(f"inv_jac_chain: chain {b} has no direction at step {j}: ||J^T c||^2 = {float(stats[b, j, 0])} (zero or not finite); "
+                                 "check=False returns the NaN states")
+        return out
+
 
 def bind(unet, kind: str, cfg, dtype=torch.float32, device="cuda:0", **kw) -> PullbackUNet:
     """Attach the HIP-backed methods onto an existing U-Net module, like the reference's
@@ -631,6 +698,7 @@ def bind(unet, kind: str, cfg, dtype=torch.float32, device="cuda:0", **kw) -> Pu
     unet.get_h = types.MethodType(lambda self, *a, **k: self._dpb.get_h(*a, **k), unet)
     unet.get_h_to_e = types.MethodType(lambda self, *a, **k: self._dpb.get_h_to_e(*a, **k), unet)
     unet.local_encoder_pullback_batch = types.MethodType(lambda self, *a, **k: self._dpb.local_encoder_pullback_batch(*a, **k), unet)
+    unet.inv_jac_chain = types.MethodType(lambda self, *a, **k: self._dpb.inv_jac_chain(*a, **k), unet)
     if kind == "sd":
         unet.local_encoder_pullback_zt = types.MethodType(lambda self, *a, **k: self._dpb.local_encoder_pullback_zt(*a, **k), unet)
         unet.local_decoder_pullback_zt = types.MethodType(lambda self, *a, **k: self._dpb.local_decoder_pullback_zt(*a, **k), unet)

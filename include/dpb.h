@@ -640,6 +640,52 @@ int dpb_ddim_step(const float* x, const float* eps, float* out, float* x0, int64
 int dpb_lincomb(const float* x, const float* y, const float* z, float* out, int64_t n, float a, float b, float c,
                 void* hip_stream);
 
+/* ---- the parallel-h edit chain (additive to ABI version 1) --------------------------------------------------------------------------
+ * The --edit_xt parallel-h branch of the global-basis edit jobs (src/modules/edit.py:1202-1229, :1470-1497): the h-space direction c is held fixed and
+ * the x-space direction is recomputed at every state, v = -J^T c / ||J^T c|| (PullBackDDPM.inv_jac_xt, src/models/ddpm/diffusion.py:347-377),
+ * x <- x + step v, optionally with the SEGA rule v <- where(|v| < sega_sigma std(v), 0, v).  Sign: a chain with sign = +1 moves h AGAINST c,
+ * <h - h0, c> / ||c|| ~ -step ||J^T c|| / ||c|| at first order (the reference's convention, kept).
+ *
+ * dpb_direction_step (engine-independent): W [n][N] fp32 (the adjoint results J^T c), x [n][N], x_out [n][N] (may alias x: every element is read by
+ * the thread that overwrites it), vk [n][N] or NULL, step: a HOST array of n entries, stats [n][4] FP64 on the device.  Per row b:
+ *   S1 = sum w, S2 = sum w^2 in fp64 (fp32 widened on load; per-workgroup partial sums of slices of 4096 elements, added in slice order; no atomics:
+ *   the sums are a function of the row and N only); v_i = fl32(-w_i / sqrt(S2)), formed in fp64 and rounded once; when sega_sigma > 0 and N >= 2,
+ *   std = sqrt(max(0, 1 - S1^2 / (N S2)) / (N - 1)) -- torch's unbiased std of the unit-norm row, in the two sums -- and v_i <- 0 where
+ *   |v_i| < sega_sigma std, compared in fp64 (N = 1: v is left alone; the reference's std is NaN there and its where keeps the element);
+ *   x_out_i = fl32(x_i + step_b v_i), formed in fp64 and rounded once; stats[b] = (S2, std or 0, elements the rule kept (N when it is off), flag).
+ *   A row with S2 == 0 or S2 not finite: flag = 1, std = 0, kept = 0, and NaN in exactly that row of vk and x_out; no other row changes by a bit.
+ * Two launches per 256 rows (partial sums, apply: every apply workgroup re-adds the row's partials in index order); the kept count is a sum of
+ * integers below 2^53 and the one place an (fp64, exact) atomic is used.  A row's results are bitwise the same alone and at any position of a stack,
+ * whatever the alignment: rows start at b N floats, and each workgroup takes 16-byte accesses for an aligned row, 4-byte ones otherwise, with the
+ * same elements per thread.  scratch: 8-byte aligned device memory of >= dpb_direction_step_scratch_bytes(n, N) bytes.  Refused: a non-finite step[b],
+ * a NaN sega_sigma.  No host synchronisation.
+ * dpb_shift_stats (engine-independent): h [n][D], h0 [n][D], u [nu][D] fp32 on the device, dir [n] in [0, nu) and sign [n] HOST arrays;
+ * out [n][2] FP64 on the device = (<h - h0, c> / ||c||, ||h - h0||^2) with c = sign[b] u[dir[b]], fixed-order fp64 sums, no atomics.
+ *
+ * dpb_inv_jac_chain: n chains advanced together for `steps` steps, no host work between the steps.  x [n][N_in] fp32 NCHW, t: a HOST array of n
+ * timesteps (the rules of dpb_primal_t), ctx [n][L][Dc] or NULL, u [nu][N_h] fp32 NCHW-flattened directions of the tap, dir / sign / step HOST
+ * arrays of n entries: chain b follows c_b = sign[b] u[dir[b]] with step[b] per step.  states [steps + 1][n][N_in]: states[0] = x (states may
+ * start at x); step j runs dpb_primal_t at states[j] up to the tap, gathers the cotangents c_b on the device, runs the adjoint pass of dpb_vjp with
+ * one cotangent per sample, and dpb_direction_step into states[j + 1] (vk [steps][n][N_in] or NULL, stats [steps][n][4]).  shift [steps + 1][n][2]:
+ * dpb_shift_stats of the tap activation the primal pass of step j has just produced against the copy kept from step 0 (row 0 is (0, 0)); row
+ * `steps` takes one more forward pass to the tap when final_shift != 0, else it is NaN.
+ * Host synchronisation: ONE for the call -- the upload of the timestep embeddings in step 0; they stay resident in the engine for the other steps
+ * (as the chunks of dpb_local_pca_sample).  No device allocation: scratch is 256-byte aligned device memory of >=
+ * dpb_inv_jac_chain_scratch_bytes(e, tap_buf, n) bytes (0 when invalid).  The call leaves no primal state, as dpb_forward.
+ * Refused (dpb_last_error): n outside [1, min(max_batch, max_tangents)], steps < 1, nu < 1, a dir[b] outside [0, nu), a non-finite t[b], sign[b] or
+ * step[b], a tap that is not an x-dependent activation, a missing ctx, scratch too small or misaligned. */
+size_t dpb_direction_step_scratch_bytes(int64_t n, int64_t N);   /* 0 when invalid */
+int dpb_direction_step(const float* W, const float* x, float* x_out, float* vk /*or NULL*/, const float* step /*host [n]*/, float sega_sigma,
+                       int64_t n, int64_t N, double* stats /*dev [n][4]*/, void* scratch, size_t scratch_bytes, void* hip_stream);
+int dpb_shift_stats(const float* h, const float* h0, const float* u, int nu, const int32_t* dir /*host [n]*/, const float* sign /*host [n]*/,
+                    int64_t n, int64_t D, double* out /*dev [n][2]*/, void* hip_stream);
+size_t dpb_inv_jac_chain_scratch_bytes(const dpb_engine* e, int tap_buf, int n);
+int dpb_inv_jac_chain(dpb_engine* e, int tap_buf, const float* x /*dev [n][N_in]*/, int n, const float* t /*host [n]*/,
+                      const float* ctx /*dev [n][L][Dc] or NULL*/, const float* u /*dev [nu][N_h]*/, int nu, const int32_t* dir,
+                      const float* sign, const float* step /*host [n]*/, int steps, float sega_sigma, int final_shift,
+                      float* states /*dev [steps+1][n][N_in]*/, float* vk /*dev [steps][n][N_in] or NULL*/, double* stats /*dev [steps][n][4]*/,
+                      double* shift /*dev [steps+1][n][2]*/, void* scratch, size_t scratch_bytes);
+
 /* Token + position embedding lookup of the CLIP text encoder behind pipe._encode_prompt (src/modules/edit.py:505-522):
  * out[b][c][t] = tok_table[ids[b][t]][c] + pos_table[t][c], fp32 in the engine's NCHW boundary layout (H*W = tokens),
  * ready for dpb_primal of a text-encoder tape.  Tables are [vocab][channels] / [tokens][channels] in `dtype`. */
