@@ -152,6 +152,8 @@ struct Forward {
   // 0 .. producer[seed]; 1 < batch: the shared prefix, the rest of the tape runs on copies
   const float* u = nullptr; const int32_t* dir = nullptr; const float* scale = nullptr;
   int xbatch = 0;
+  // dpb_forward_shift_groups: the batch is `groups` copies of the xbatch samples, row g * xbatch + b is sample b in group g (0: dpb_forward_shift)
+  int groups = 0;
 };
 
 // Everything an op function may know about the pass it runs in.  Built on the stack by primal_pass / jvp_pass / vjp_pass.
@@ -1303,10 +1305,17 @@ int dpb_engine_set_workspace(dpb_engine* e, void* ws, size_t bytes) {
 // ops in (producer[f.seed], last] that were written at or before producer[f.seed] or are network inputs (ctx) -- the skips, the net-wide K/V
 // projection of the context.  SHARED buffers (time-embedding path, row biases) have one copy for any batch; the tap itself is written by shift_tap.
 // Nothing else crosses the seam: a primal normalisation op computes its statistics from its own input, it takes none from that input's producer.
+// dpb_forward_shift_groups with 1 < xb < batch: the tap becomes `groups` shifted copies of its xb rows, and the first xb samples of every such buffer
+// are copied as one block to each of the other groups (a buffer is [batch] contiguous samples, so the block of xb samples is one "row" of the copy).
 static int shift_seed(dpb_engine* e, const Forward& f, int batch, int xb, int last) {
   const int src = f.seed, ps = e->producer[src];
   const Buf& bs = e->bufs[src];
-  if (int r = launch_shift_tap(e->dtype, e->P(src), f.u, f.dir, f.scale, batch, xb < batch, bs.C, bs.Cv, bs.rows, e->stream)) return r;
+  const bool grouped = f.groups > 1 && xb > 1;
+  if (grouped) {
+    if (int r = launch_shift_tap_groups(e->dtype, e->P(src), f.u, f.dir, f.scale, xb, f.groups, bs.C, bs.Cv, bs.rows, e->stream)) return r;
+  } else {
+    if (int r = launch_shift_tap(e->dtype, e->P(src), f.u, f.dir, f.scale, batch, xb < batch, bs.C, bs.Cv, bs.rows, e->stream)) return r;
+  }
   if (xb == batch) return 0;
   std::vector<char> seen(e->bufs.size(), 0);
   std::vector<void*> ptr;
@@ -1316,9 +1325,9 @@ static int shift_seed(dpb_engine* e, const Forward& f, int batch, int xb, int la
       if (b == src || seen[b] || e->bufs[b].kind == DPB_BUF_SHARED || e->producer[b] > ps) continue;
       seen[b] = 1;
       ptr.push_back(e->P(b));
-      bytes.push_back((size_t)e->bufs[b].rows * e->bufs[b].C * e->es);
+      bytes.push_back((size_t)e->bufs[b].rows * e->bufs[b].C * e->es * (grouped ? xb : 1));
     }
-  return launch_replicate_rows(ptr.data(), bytes.data(), (int)ptr.size(), batch, e->stream);
+  return launch_replicate_rows(ptr.data(), bytes.data(), (int)ptr.size(), grouped ? f.groups : batch, e->stream);
 }
 
 // the sinusoidal timestep embedding, computed on the host in fp32 exactly as the reference frameworks do (diffusion.py:783-804 / diffusers
@@ -1467,6 +1476,31 @@ int dpb_forward_shift(dpb_engine* e, const float* x, int xbatch, int batch, floa
   Forward f;
   f.stash = false; f.seed = src_buf; f.u = u; f.dir = dir; f.scale = scale; f.xbatch = xbatch;
   return forward_pass(e, x, batch, t, ctx, dst_buf, channels, out, f);
+}
+
+// the checks dpb_forward_shift_groups and dpb_hguide_chain share: the shape of the grouped batch and its rows
+static int check_groups(dpb_engine* e, const char* who, int xbatch, int groups, int nu, const int32_t* dir, const float* scale) {
+  if (xbatch < 1) return fail("%s: xbatch=%d < 1", who, xbatch);
+  if (groups < 1) return fail("%s: groups=%d < 1", who, groups);
+  if (groups > SHIFT_MAX_ROWS) return fail("%s: groups=%d above %d", who, groups, SHIFT_MAX_ROWS);
+  if ((long)xbatch * groups > e->maxB) return fail("%s: xbatch * groups = %d * %d rows above max_batch=%d", who, xbatch, groups, e->maxB);
+  if (nu < 1) return fail("%s: nu=%d: at least one direction is needed", who, nu);
+  for (int r = 0; r < xbatch * groups; ++r) {
+    if (dir[r] < -1 || dir[r] >= nu) return fail("%s: dir[%d]=%d outside [-1,%d) (-1: no shift)", who, r, dir[r], nu);
+    if (!isfinite(scale[r])) return fail("%s: scale[%d] is not finite", who, r);
+  }
+  return 0;
+}
+
+int dpb_forward_shift_groups(dpb_engine* e, const float* x, int xbatch, int groups, float t, const float* ctx, int src_buf, const float* u, int nu,
+                             const int32_t* dir, const float* scale, int dst_buf, int channels, float* out) {
+  if (!e || !x || !out || !dir || !scale || !u) return fail("dpb_forward_shift_groups: null argument");
+  e->cur_batch = 0;                                // as dpb_forward: whatever happens below, the primal state is gone
+  if (int r = check_groups(e, "dpb_forward_shift_groups", xbatch, groups, nu, dir, scale)) return r;
+  if (int r = check_pair(e, src_buf, dst_buf, FOR_FORWARD)) return r;
+  Forward f;
+  f.stash = false; f.seed = src_buf; f.u = u; f.dir = dir; f.scale = scale; f.xbatch = xbatch; f.groups = groups;
+  return forward_pass(e, x, xbatch * groups, t, ctx, dst_buf, channels, out, f);
 }
 
 int dpb_read_buffer(dpb_engine* e, int buf, int channels, float* out) {
@@ -1949,6 +1983,105 @@ int dpb_inv_jac_chain(dpb_engine* e, int tap_buf, const float* x, int n, const f
     if (!r) r = shift_of(steps);
   } else if (!r) {
     DPB_CHECK(hipMemsetAsync(shift + (size_t)steps * n * 2, 0xff, (size_t)n * 2 * sizeof(double), e->stream));   // all bits set: a NaN
+  }
+  e->cur_batch = 0;                                // no primal state is left behind
+  e->primal_last = -1;
+  e->n_launch = launch_count - at; e->flops = fl; e->gbytes = gb;
+  return r;
+}
+
+// The h-space guidance edit (hguide.hip between the engine's grouped passes): dpb_ddim_step_asym and the device DDIM chain
+size_t dpb_ddim_step_asym_scratch_bytes(int64_t n, int64_t N) { return ddim_step_asym_scratch_bytes(n, N); }
+
+int dpb_ddim_step_asym(const float* x, const float* e, const float* e_s, float* out, float* x0, int64_t n, int64_t N, float alpha_t, float alpha_next,
+                       float gP, float gD, double* stats, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!x || !e || !e_s || !out || !stats || !scratch) return fail("dpb_ddim_step_asym: null argument");
+  return launch_ddim_step_asym(x, e, e_s, out, x0, n, N, alpha_t, alpha_next, gP, gD, stats, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+namespace {
+struct HguideScratch { size_t temb = 0, eps = 0, part = 0, total = 0; long n_in = 0, temb_c = 0; };
+bool hguide_layout(const dpb_engine* e, int n, int steps, HguideScratch& l) {
+  if (!e || n < 1 || steps < 1) return false;
+  l.n_in = (long)e->bufs[e->x_buf].rows * e->x_channels;
+  l.temb_c = e->temb_buf >= 0 ? e->bufs[e->temb_buf].C : 0;
+  size_t off = 0;
+  auto take = [&](size_t b) { const size_t o = off; off += align_up(b); return o; };
+  l.temb = take((size_t)steps * l.temb_c * sizeof(float));
+  l.eps = take((size_t)2 * n * l.n_in * sizeof(float));
+  l.part = take(ddim_step_asym_scratch_bytes(n, l.n_in));
+  l.total = off;
+  return true;
+}
+}  // namespace
+
+size_t dpb_hguide_chain_scratch_bytes(const dpb_engine* e, int n, int steps) {
+  HguideScratch l;
+  return hguide_layout(e, n, steps, l) ? l.total : 0;
+}
+
+int dpb_hguide_chain(dpb_engine* e, int tap_buf, int eps_buf, const float* x, int n, const float* t, const float* alpha_t, const float* alpha_next,
+                     const float* ctx, const float* u, int nu, const int32_t* dir, const float* scale, float gP, float gD, int steps, float* states,
+                     double* delta, void* scratch, size_t scratch_bytes) {
+  if (!e || !x || !t || !alpha_t || !alpha_next || !u || !dir || !scale || !states || !delta || !scratch) return fail("dpb_hguide_chain: null argument");
+  e->cur_batch = 0;                                // as dpb_forward: whatever happens below, the primal state is gone
+  if (!e->ws) return fail("workspace not set (dpb_engine_set_workspace)");
+  if (n < 1 || 2 * (long)n > e->maxB) return fail("dpb_hguide_chain: n=%d chains: a plain and a shifted row each, 2n outside [2,%d] (max_batch)", n, e->maxB);
+  if (steps < 1) return fail("dpb_hguide_chain: steps=%d < 1", steps);
+  if (nu < 1) return fail("dpb_hguide_chain: nu=%d: at least one direction is needed", nu);
+  for (int b = 0; b < n; ++b) {
+    if (dir[b] < 0 || dir[b] >= nu) return fail("dpb_hguide_chain: dir[%d]=%d outside [0,%d)", b, dir[b], nu);
+    if (!isfinite(scale[b])) return fail("dpb_hguide_chain: scale[%d] is not finite", b);
+  }
+  if (!isfinite(gP) || !isfinite(gD)) return fail("dpb_hguide_chain: gP=%g, gD=%g: not finite", gP, gD);
+  for (int j = 0; j < steps; ++j) {
+    if (!isfinite(t[j])) return fail("dpb_hguide_chain: t[%d] is not finite", j);
+    if (!(alpha_t[j] > 0.f && alpha_t[j] <= 1.f) || !(alpha_next[j] > 0.f && alpha_next[j] <= 1.f))
+      return fail("dpb_hguide_chain: step %d: alpha_t=%g and alpha_next=%g must lie in (0, 1]", j, alpha_t[j], alpha_next[j]);
+  }
+  if (tap_buf < 0 || tap_buf >= (int)e->bufs.size() || e->producer[tap_buf] < 0 || e->bufs[tap_buf].kind != DPB_BUF_ACT)
+    return fail("dpb_hguide_chain: invalid tap buffer %d (an activation produced by an op)", tap_buf);
+  if (e->bufs[tap_buf].is_const) return fail("dpb_hguide_chain: tap buffer %d does not depend on x", tap_buf);
+  if (int r = check_pair(e, tap_buf, eps_buf, FOR_FORWARD)) return r;
+  const Buf& be = e->bufs[eps_buf];
+  if (be.Cv != e->x_channels || be.rows != e->bufs[e->x_buf].rows)
+    return fail("dpb_hguide_chain: eps buffer %d is [%d][%d], the input is [%d][%d]: a DDIM step needs the two to agree", eps_buf, be.Cv, be.rows,
+                e->x_channels, e->bufs[e->x_buf].rows);
+  if (e->ctx_buf >= 0 && !ctx) return fail("this network needs ctx (encoder_hidden_states)");
+  HguideScratch l;
+  hguide_layout(e, n, steps, l);
+  if ((uintptr_t)scratch % 256) return fail("dpb_hguide_chain: scratch must be 256-byte aligned");
+  if (scratch_bytes < l.total) return fail("dpb_hguide_chain: scratch of %zu bytes, dpb_hguide_chain_scratch_bytes = %zu", scratch_bytes, l.total);
+  char* sc = (char*)scratch;
+  float *temb = (float*)(sc + l.temb), *eps = (float*)(sc + l.eps);
+  const size_t row = (size_t)n * l.n_in;
+  const long at = launch_count;                     // the sub-passes' LaunchSpans overwrite n_launch as they go: the assignment at the end is what counts
+  double fl = 0, gb = 0;
+  // rows 0 .. n-1: the plain net; rows n .. 2n-1: the chains' shifts
+  std::vector<int32_t> dirs(2 * n, -1);
+  std::vector<float> scales(2 * n, 0.f);
+  for (int b = 0; b < n; ++b) { dirs[n + b] = dir[b]; scales[n + b] = scale[b]; }
+  if (e->temb_buf >= 0) {
+    // the sinusoid rows of ALL the steps in one copy: the call's one host synchronisation (emb is a host temporary)
+    std::vector<float> emb((size_t)steps * l.temb_c, 0.f);
+    for (int j = 0; j < steps; ++j) temb_row(e, t[j], emb.data() + (size_t)j * l.temb_c);
+    DPB_CHECK(hipMemcpyAsync(temb, emb.data(), emb.size() * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    DPB_CHECK(hipStreamSynchronize(e->stream));
+  }
+  if (states != x) DPB_CHECK(hipMemcpyAsync(states, x, row * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+  int r = 0;
+  for (int j = 0; j < steps && !r; ++j) {
+    const float* xj = states + (size_t)j * row;
+    if (e->temb_buf >= 0)
+      r = launch_nchw_to_nhwc(e->dtype, temb + (size_t)j * l.temb_c, e->P(e->temb_buf), 1, (int)l.temb_c, 1, (int)l.temb_c, e->stream);
+    Forward f;
+    f.stash = false; f.temb_resident = true;       // step j's row was moved into P(temb_buf) on the device just now: no upload, no sync
+    f.seed = tap_buf; f.u = u; f.dir = dirs.data(); f.scale = scales.data(); f.xbatch = n; f.groups = 2;
+    if (!r) r = primal_pass(e, xj, 2 * n, t[j], ctx, eps_buf, f);
+    fl += e->flops; gb += e->gbytes;
+    if (!r) r = launch_nhwc_to_nchw(e->dtype, e->P(eps_buf), eps, 2 * n, be.Cv, be.rows, be.C, e->stream);
+    if (!r) r = launch_ddim_step_asym(xj, eps, eps + row, states + (size_t)(j + 1) * row, nullptr, n, l.n_in, alpha_t[j], alpha_next[j], gP, gD,
+                                      delta + (size_t)j * n * 2, sc + l.part, l.total - l.part, e->stream);
   }
   e->cur_batch = 0;                                // no primal state is left behind
   e->primal_last = -1;

@@ -505,6 +505,17 @@ int launch_shift_stats(const float* h, const float* h0, const float* u, int nu, 
 // cot[b] = sign[b] u[dir[b]]: the chain's cotangents, one per sample
 int launch_gather_cotangents(const float* u, int nu, const int32_t* dir, const float* sign, long n, long D, float* cot, hipStream_t st);
 
+// ---------------------------------------------------------------- the h-space guidance edit (hguide.hip)
+// the asymmetric DDIM step: d = e_s - e, eP = e + gP d, eD = e + gD d, out = sqrt(a_next) (x - eP sqrt(1-a_t)) / sqrt(a_t) + sqrt(1-a_next) eD in the
+// operation order of ddim_kernel (out may alias x; x0 optional: the predicted x0); stats [n][2] fp64 on the device = (sum d^2, flag); see include/dpb.h
+size_t ddim_step_asym_scratch_bytes(long n, long N);     // 0 when invalid
+int launch_ddim_step_asym(const float* x, const float* e, const float* es, float* out, float* x0, long n, long N, float a_t, float a_next, float gP,
+                          float gD, double* stats, void* scratch, size_t scratch_bytes, hipStream_t st);
+// the seam of dpb_forward_shift_groups: h [groups xb][HW][C] holds samples 0 .. xb-1; h[g xb + b] = h[b] + scale[g xb + b] * u[dir[g xb + b]] in place
+// (dir / scale: HOST arrays of groups * xb entries, dir in [-1, nu) checked by the caller); the arithmetic and the layouts of launch_shift_tap
+int launch_shift_tap_groups(int dtype, void* h, const float* u, const int* dir, const float* scale, int xb, int groups, int C, int Cv, long HW,
+                            hipStream_t st);
+
 // ---------------------------------------------------------------- DDIM
 // x_next = sqrt(a_next) * (x - e*sqrt(1-a_t))/sqrt(a_t) + sqrt(1-a_next) * e      (fp32, elementwise)
 int launch_ddim_step(const float* x, const float* e, float* out, float* x0, long n, float a_t, float a_next, hipStream_t st);

@@ -25,6 +25,7 @@ embeddings and save latents instead of decoded images (there are no weights offl
 """
 from __future__ import annotations
 
+import math
 import os
 import zlib
 from typing import Optional
@@ -663,6 +664,13 @@ class EditUncondDiffusion(_EditBase):
         self.x_edit_step_size = getattr(args, "x_edit_step_size", 0.0)
         self.use_sega_reg = bool(getattr(args, "use_sega_reg", False))
         self.sega_reg_sigma = getattr(args, "sega_reg_sigma", 1.0)
+        # "h_space_guidance" (with edit_xt at its default): the h-space direction is added at the tap at every DDIM step from edit_t down to
+        # no_edit_t, scaled up to h_edit_step_size (edit.py:1232-1245; _run_h_guidance_chains); h_guidance_mode: "asyrp" or "symmetric"
+        self.edit_ht = getattr(args, "edit_ht", "default")
+        self.h_edit_step_size = getattr(args, "h_edit_step_size", 0.0)
+        self.no_edit_t = getattr(args, "no_edit_t", 0.5)
+        self.no_edit_t_idx = int((self.scheduler.timesteps - self.no_edit_t * 1000).abs().argmin())
+        self.h_guidance_mode = getattr(args, "h_guidance_mode", "asyrp")
         self.result_folder, self.obs_folder = args.result_folder, args.obs_folder
         self.input_root = getattr(args, "input_root", "./inputs")
         self.EXP_NAME = "exp"
@@ -947,7 +955,7 @@ class EditUncondDiffusion(_EditBase):
         seed_<seed>-pc_<pc>_{pos,neg}, pictures x0_gen-<name>.png, projection_coeff-<name>.png in the obs folder; the job is skipped when the last
         pc's _neg picture exists, an experiment when its own does.  trajectory_batch as in run_edit_parallel_transport.
         edit_xt "parallel-h" (space h only; local_projection=False allowed): the chains of _run_parallel_h_chains instead.
-        The reference's h_space_guidance branch is not built.
+        edit_ht "h_space_guidance" (space h only; local_projection=False allowed): the device DDIM chains of _run_h_guidance_chains.
         Returns a dict: basis [k, N] (rows), vk [P, N_x], pcs, names, info (None for a loaded basis).
         frechet_init "member" starts the iteration at local basis 0, "flag" at the flag mean of them all (geometry.frechet_mean(init="flag")); the
         info file of a "flag" run records it as ``init``."""
@@ -957,7 +965,7 @@ class EditUncondDiffusion(_EditBase):
         if frechet_mean_space not in ("x", "h"):
             raise ValueError(f"frechet_mean_space must be 'x' (the spans of vT) or 'h' (the spans of u), got {frechet_mean_space!r}")
         self._check_parallel_h(frechet_mean_space)
-        if frechet_mean_space == "h" and not local_projection and self.edit_xt != "parallel-h":
+        if frechet_mean_space == "h" and not local_projection and self.edit_xt != "parallel-h" and self.edit_ht != "h_space_guidance":
             raise ValueError("local_projection=False is valid for frechet_mean_space 'x' only: an h-space direction reaches x-space through the sample's "
                              "own local basis (the reference leaves vk undefined there)")
         h_t = self.h_t if h_t is None else h_t
@@ -1041,7 +1049,7 @@ class EditUncondDiffusion(_EditBase):
         if flag_mean_space not in ("x", "h"):
             raise ValueError(f"flag_mean_space must be 'x' (the spans of vT) or 'h' (the spans of u), got {flag_mean_space!r}")
         self._check_parallel_h(flag_mean_space)
-        if flag_mean_space == "h" and not local_projection and self.edit_xt != "parallel-h":
+        if flag_mean_space == "h" and not local_projection and self.edit_xt != "parallel-h" and self.edit_ht != "h_space_guidance":
             raise ValueError("local_projection=False is valid for flag_mean_space 'x' only: an h-space direction reaches x-space through the sample's "
                              "own local basis")
         r = int(pca_rank if not flag_rank else flag_rank)
@@ -1113,8 +1121,9 @@ class EditUncondDiffusion(_EditBase):
         Then the x-space-guidance chains xt-<dataset>_<idx>-h_<h_t>T-edit_<edit_t>T-<op>-block_<b>-seed_<seed>-pc_<pc>_{pos,neg}, an experiment skipped
         when its picture exists, and projection_coeff-<name>.png (its u series from rows pcs of basis_h [k, N_h], when given).  edit_xt "parallel-h"
         (space h): the same names, skip rule and order, but every chain follows its h-direction through _run_parallel_h_chains; with
-        local_projection the local basis and the plot are produced as above, without it no local-basis file is read or written.  Fills and returns
-        out (parallel-h adds "chains", the chain records)."""
+        local_projection the local basis and the plot are produced as above, without it no local-basis file is read or written.  edit_ht
+        "h_space_guidance" (space h): as parallel-h, with the device DDIM chains of _run_h_guidance_chains.  Fills and returns out (parallel-h and
+        h_space_guidance add "chains", the chain records)."""
         from . import geometry
         exp = lambda pc, tag: f"xt-{self.dataset_name}_{idx}-h_{h_t}T-edit_{self.edit_t}T-{op}-block_{block_idx}-seed_{self.seed}-pc_{pc:0=3d}_{tag}"
         picture = lambda name: os.path.exists(os.path.join(self.result_folder, f"x0_gen-{name}.png"))
@@ -1125,7 +1134,8 @@ class EditUncondDiffusion(_EditBase):
         xT = self._random_latent(idx) if self.dataset_name == "Random" else self.run_DDIMinversion(idx=idx)      # edit.py:1082-1085
         own_dir, own_name = self._tangent_space_naming(op, block_idx, pca_rank)
         files = self._basis_paths(own_dir, own_name(idx, h_t))
-        parallel_h = self.edit_xt == "parallel-h"
+        h_guide = self.edit_ht == "h_space_guidance"
+        parallel_h = self.edit_xt == "parallel-h" or h_guide    # (both follow the h-direction itself: the local basis serves the plot only)
         have = os.path.exists(files[0]) and os.path.exists(files[2]) and (local_projection or not parallel_h)   # (parallel-h reads it for the plot only)
         if local_projection and not have:
             print("!!!SAMPLE LOCAL TANGENT SPACE!!!")
@@ -1144,7 +1154,10 @@ class EditUncondDiffusion(_EditBase):
             out["vk"] = None
             chains = [(exp(pc, tag), original_xt, pc, sign) for pc in pcs for sign, tag in ((1, "pos"), (-1, "neg")) if not picture(exp(pc, tag))]
             out["names"] = [c[0] for c in chains]
-            out["chains"] = self._run_parallel_h_chains(chains, basis, op, block_idx, vis_num, shape)
+            if h_guide:
+                out["chains"] = self._run_h_guidance_chains([(c[0], c[2], c[3]) for c in chains], original_xt, basis, op, block_idx, vis_num, shape)
+            else:
+                out["chains"] = self._run_parallel_h_chains(chains, basis, op, block_idx, vis_num, shape)
             return out
         if local_projection:
             with T.phase("projection of the global directions on the local basis"):
@@ -1168,6 +1181,9 @@ class EditUncondDiffusion(_EditBase):
         out["names"] = [c[0] for c in chains]
         if parallel_h:                                       # the projection above is the plot's only: the chain follows the h-direction itself
             by_name = {exp(pc, tag): (pc, sign) for pc in pcs for sign, tag in ((1, "pos"), (-1, "neg"))}
+            if h_guide:
+                out["chains"] = self._run_h_guidance_chains([(c[0], *by_name[c[0]]) for c in chains], original_xt, basis, op, block_idx, vis_num, shape)
+                return out
             out["chains"] = self._run_parallel_h_chains([(c[0], c[1], *by_name[c[0]]) for c in chains], basis, op, block_idx, vis_num, shape)
             return out
         self._run_direction_chains(chains, vis_num, shape)
@@ -1177,6 +1193,7 @@ class EditUncondDiffusion(_EditBase):
         """what --edit_xt asks of a global-basis job, checked before anything is computed"""
         if self.edit_xt not in ("parallel-x", "parallel-h"):
             raise ValueError(f"edit_xt must be 'parallel-x' or 'parallel-h', got {self.edit_xt!r}")
+        self._check_h_guidance(space)
         if self.edit_xt != "parallel-h":
             return
         if space != "h":
@@ -1184,6 +1201,72 @@ class EditUncondDiffusion(_EditBase):
                              "reference leaves uk undefined")
         if not (float(self.x_edit_step_size) > 0):
             raise ValueError(f"edit_xt 'parallel-h' needs x_edit_step_size > 0, got {self.x_edit_step_size}")
+
+    def _check_h_guidance(self, space):
+        """what --edit_ht asks of a global-basis job, checked before anything is computed"""
+        if self.edit_ht not in ("default", "h_space_guidance"):
+            raise ValueError(f"edit_ht must be 'default' or 'h_space_guidance', got {self.edit_ht!r}")
+        if self.edit_ht != "h_space_guidance":
+            return
+        if self.edit_xt == "parallel-h":
+            raise ValueError("edit_ht 'h_space_guidance' and edit_xt 'parallel-h' exclude each other: the reference takes the guidance branch with "
+                             "edit_xt at its default only")
+        if space != "h":
+            raise ValueError("edit_ht 'h_space_guidance' adds an h-space direction at the tap: it needs the h-space global basis (space 'h'), not 'x'")
+        if not (float(self.h_edit_step_size) != 0 and math.isfinite(float(self.h_edit_step_size))):
+            raise ValueError(f"edit_ht 'h_space_guidance' needs h_edit_step_size != 0 (the largest scale of the ladder), got {self.h_edit_step_size}")
+        if self.h_guidance_mode not in ("asyrp", "symmetric"):
+            raise ValueError(f"h_guidance_mode must be 'asyrp' or 'symmetric', got {self.h_guidance_mode!r}")
+        if not int(self.no_edit_t_idx) > int(self.edit_t_idx):
+            raise ValueError(f"edit_ht 'h_space_guidance' needs no_edit_t_idx > edit_t_idx (no_edit_t < edit_t on the table): got step {int(self.no_edit_t_idx)} "
+                             f"(no_edit_t {self.no_edit_t}) and step {int(self.edit_t_idx)} (edit_t {self.edit_t})")
+        if int(self.no_edit_t_idx) > int(self.performance_boosting_t_idx):
+            raise ValueError(f"edit_ht 'h_space_guidance': the guided interval (steps {int(self.edit_t_idx)} .. {int(self.no_edit_t_idx) - 1}) reaches "
+                             f"performance_boosting_t_idx = {int(self.performance_boosting_t_idx)}, where the decode takes eta = 1: the chain is eta = 0 only")
+
+    def _run_h_guidance_chains(self, exps, original_xt, basis_h, op, block_idx, vis_num, shape):
+        """The h_space_guidance branch (edit.py:1232-1245, :1500-1513, whose h_space_guidance method the reference never defines).  exps: (EXP_NAME,
+        pc, sign).  Every experiment runs vis_num chains from original_xt with the scales sign * linspace(0, h_edit_step_size, vis_num) along
+        basis_h[pc] / ||.|| (the ladder of the x-space sibling, edit.py:1188: row 0 is the unedited reconstruction; the reference repeats one uk over
+        identical rows): unet.h_space_guidance over the DDIM steps edit_t_idx .. no_edit_t_idx - 1 (t the timestep, not the index), then the plain
+        decode from no_edit_t_idx into x0_gen-<EXP_NAME>.png.  Each writes hguide-<EXP_NAME>.pt into the obs folder (delta_norm, dx_norm [vis_num,
+        steps], scales, timesteps, mode, states_end: the latents at no_edit_t) and prints one line.  trajectory_batch > 1: all pending chains
+        through calls of at most max_batch // 2 chains and one decode batch; <= 1: one experiment after another.  Returns the records, in order."""
+        if not exps:
+            return []
+        self.scheduler.set_timesteps(self.for_steps, device=self.device)
+        ts, al, an = self.scheduler.ddim_triples(int(self.edit_t_idx), int(self.no_edit_t_idx))
+        uhat = (basis_h / basis_h.norm(dim=1, keepdim=True)).t().contiguous()                   # [N_h, k]: column pc is direction pc
+        ladder = torch.linspace(0, float(self.h_edit_step_size), vis_num)
+
+        def run(group):
+            self._phase = "h-space guidance chain: one grouped pass (plain + shifted rows) per DDIM step"
+            n = len(group) * vis_num
+            r = self.unet.h_space_guidance(x=original_xt.expand(n, *shape).to(device=self.device, dtype=self.dtype), timesteps=ts, alphas=al,
+                                           alphas_next=an, u=uhat, dirs=[c[1] for c in group for _ in range(vis_num)],
+                                           scales=[float(c[2]) * float(a) for c in group for a in ladder], mode=self.h_guidance_mode, op=op,
+                                           block_idx=block_idx)
+            end = r["states"][:, -1]
+            self._phase = "DDIM decode of the edited latents: U-Net forwards"
+            x0 = self.DDIMforwardsteps(end, t_start_idx=int(self.no_edit_t_idx), t_end_idx=-1, save_image_=False, performance_boosting=True)
+            recs = []
+            for i, c in enumerate(group):
+                self.EXP_NAME = c[0]
+                sl = slice(i * vis_num, (i + 1) * vis_num)
+                save_image((x0[sl] / 2 + 0.5).clamp(0, 1), os.path.join(self.result_folder, f"x0_gen-{c[0]}.png"), nrow=vis_num)
+                rec = {"delta_norm": r["delta_norm"][sl].cpu(), "dx_norm": r["dx_norm"][sl].cpu(), "scales": float(c[2]) * ladder,
+                       "timesteps": torch.tensor(ts), "mode": self.h_guidance_mode, "states_end": end[sl].cpu()}
+                torch.save(rec, os.path.join(self.obs_folder, f"hguide-{c[0]}.pt"))
+                print(f"h-space guidance {c[0]} ({self.h_guidance_mode}): {len(ts)} steps t = {ts[0]:g} .. {ts[-1]:g}, scales up to "
+                      f"{float(rec['scales'][-1]):g}, ||e_s - e|| {float(rec['delta_norm'][-1, 0]):.4g} -> {float(rec['delta_norm'][-1, -1]):.4g}, "
+                      f"distance from the plain step, summed {float(rec['dx_norm'][-1].sum()):.4g}")
+                recs.append(rec)
+            return recs
+
+        groups = [exps] if self.trajectory_batch > 1 else [[c] for c in exps]
+        recs = [rec for g in groups for rec in run(g)]
+        self._phase = _EditBase._phase
+        return recs
 
     def _run_parallel_h_chains(self, chains, basis_h, op, block_idx, vis_num, shape):
         """The parallel-h branch (edit.py:1202-1229, :1470-1497).  chains: (EXP_NAME, start x_t [1, ...], pc, sign).  Each holds uk = sign *
@@ -1255,13 +1338,13 @@ class EditUncondDiffusion(_EditBase):
         Edit: the common tail of the global-basis jobs (_edit_along_global_basis).  hungarian_mean_space "x": vk = normalise(vT^T (vT vhat_pc)), the
         reference's live path; "h": vk = normalise(vT^T (u^T uhat_pc)), the route the Frechet job uses to bring an h-direction to x.
         local_projection=False is valid for "x" only -- and for edit_xt "parallel-h" (space h only), whose chains are those of
-        _run_parallel_h_chains.  The reference's h_space_guidance branch is not built.
+        _run_parallel_h_chains -- and for edit_ht "h_space_guidance" (space h only), the device DDIM chains of _run_h_guidance_chains.
         Returns a dict: basis_u [k, N_h], basis_v [k, N_x] (rows), vk [P, N_x], pcs, names, info ({"u": ..., "v": ...}, None for a loaded basis)."""
         from . import geometry
         if hungarian_mean_space not in ("x", "h"):
             raise ValueError(f"hungarian_mean_space must be 'x' (the directions of vT) or 'h' (the directions of u), got {hungarian_mean_space!r}")
         self._check_parallel_h(hungarian_mean_space)
-        if hungarian_mean_space == "h" and not local_projection and self.edit_xt != "parallel-h":
+        if hungarian_mean_space == "h" and not local_projection and self.edit_xt != "parallel-h" and self.edit_ht != "h_space_guidance":
             raise ValueError("local_projection=False is valid for hungarian_mean_space 'x' only: an h-space direction reaches x-space through the "
                              "sample's own local basis")
         if hungarian_distance not in geometry.HUNGARIAN_DISTANCES:

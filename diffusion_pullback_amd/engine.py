@@ -372,6 +372,67 @@ class Engine:
                                                C.c_void_p(self._chain_scratch.data_ptr() + off), need))
         return states, vk, stats, shift
 
+    # ------------------------------------------------------------------ the h-space guidance edit on the device
+    def forward_shift_groups(self, x: torch.Tensor, groups: int, t: float, ctx: Optional[torch.Tensor], src, u: torch.Tensor, dirs, scales,
+                             dst="eps") -> torch.Tensor:
+        """dpb_forward_shift_groups: forward_shift for `groups` shifted copies of the xb = x.shape[0] DIFFERENT samples of x.  Row g * xb + b of
+        the result is `dst` of sample b with scales[g * xb + b] * u[dirs[g * xb + b]] added at tap `src` (dirs = -1: unshifted); dirs / scales:
+        host sequences of xb * groups entries.  The part of the net up to the tap runs once at xb, the part after it at xb * groups.  Like
+        forward(), keeps no primal state."""
+        sbuf, dbuf = self.tape.taps[src], self.tape.taps[dst]
+        c, hh, ww = self.tape.tap_shape[dbuf]
+        dirs, scales, groups = [int(d) for d in dirs], [float(s) for s in scales], int(groups)
+        with torch.cuda.device(self.device):
+            self._set_stream()
+            x, xb, ctx = self._inputs(x, ctx)
+            b = xb * max(groups, 0)
+            if len(dirs) != b or len(scales) != b:
+                raise L.DpbError(f"dirs and scales have {len(dirs)} and {len(scales)} entries for {xb} samples x {groups} groups: one of each per row")
+            if u.numel() == 0 or u.numel() % self.tap_numel(src):
+                raise L.DpbError(f"u has {u.numel()} elements, not a whole number of directions of {self.tap_numel(src)} (tap {src})")
+            u = _f32(u, self.device).reshape(-1, self.tap_numel(src))
+            out = torch.empty(max(b, 1), c, hh, ww, dtype=torch.float32, device=self.device)
+            self.batch = 0
+            L.check(self.lib.dpb_forward_shift_groups(self.h, _ptr(x), xb, groups, float(t), _ptr(ctx), sbuf, _ptr(u), u.shape[0],
+                                                      (C.c_int32 * max(b, 1))(*dirs), (C.c_float * max(b, 1))(*scales), dbuf, c, _ptr(out)))
+        return out
+
+    def hguide_chain(self, x: torch.Tensor, t, alpha_t, alpha_next, ctx: Optional[torch.Tensor], tap, u: torch.Tensor, dirs, scales, gP: float = 1.0,
+                     gD: float = 0.0):
+        """dpb_hguide_chain: n = x.shape[0] chains advanced together through the S = len(t) DDIM steps (t[j], alpha_t[j]) -> alpha_next[j] with no
+        Python between the steps; chain b adds scales[b] * u[dirs[b]] at `tap` in the shifted row of every step.  t / alpha_t / alpha_next: host
+        sequences of S floats (the fp32 table entries), ctx [n or 1, L, D] or None, u [nu, N_h] fp32 (NCHW-flattened), dirs / scales: host
+        sequences of n.  2n rows run per step: n <= max_batch // 2.  Returns device tensors (states [S + 1, n, C, H, W] with states[0] = x,
+        delta [S, n, 2] fp64 = (||e_s - e||^2, flag)); one host sync for the call.  Like forward(), keeps no primal state."""
+        buf, ebuf = self.tape.taps[tap], self.tape.taps["eps"]
+        tl, al, an = [float(a) for a in t], [float(a) for a in alpha_t], [float(a) for a in alpha_next]
+        steps = len(tl)
+        if len(al) != steps or len(an) != steps:
+            raise L.DpbError(f"t, alpha_t and alpha_next have {steps}, {len(al)} and {len(an)} entries: one of each per step")
+        with torch.cuda.device(self.device):
+            self._set_stream()
+            x, n, ctx = self._inputs(x, ctx)
+            dirs, scales = [int(d) for d in dirs], [float(s) for s in scales]
+            if len(dirs) != n or len(scales) != n:
+                raise L.DpbError(f"dirs and scales have {len(dirs)} and {len(scales)} entries for {n} chains: one of each per chain")
+            d = self.tap_numel(tap)
+            if u.numel() == 0 or u.numel() % d:
+                raise L.DpbError(f"u has {u.numel()} elements, not a whole number of directions of {d} (tap {tap})")
+            u = _f32(u, self.device).reshape(-1, d)
+            ns = max(steps, 1)
+            states = torch.empty(ns + 1, n, *x.shape[1:], dtype=torch.float32, device=self.device)
+            delta = torch.empty(ns, n, 2, dtype=torch.float64, device=self.device)
+            need = int(self.lib.dpb_hguide_chain_scratch_bytes(self.h, n, ns))
+            if getattr(self, "_hguide_scratch", None) is None or self._hguide_scratch.numel() < need + 256:
+                self._hguide_scratch = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+            off = (-self._hguide_scratch.data_ptr()) % 256
+            self.batch = 0
+            fa = C.c_float * ns
+            L.check(self.lib.dpb_hguide_chain(self.h, buf, ebuf, _ptr(x), n, fa(*tl), fa(*al), fa(*an), _ptr(ctx), _ptr(u), u.shape[0],
+                                              (C.c_int32 * n)(*dirs), (C.c_float * n)(*scales), float(gP), float(gD), steps, _ptr(states), _ptr(delta),
+                                              C.c_void_p(self._hguide_scratch.data_ptr() + off), need))
+        return states, delta
+
     def profile(self, enable: bool):
         L.check(self.lib.dpb_engine_profile(self.h, int(enable)))
 
@@ -492,3 +553,31 @@ def shift_stats(h: torch.Tensor, h0: torch.Tensor, u: torch.Tensor, dirs, signs)
         L.check(lib.dpb_shift_stats(_ptr(h), _ptr(h0), _ptr(u), u.shape[0], (C.c_int32 * max(n, 1))(*dirs), (C.c_float * max(n, 1))(*signs), n, D,
                                     _ptr(out), C.c_void_p(st)))
     return out
+
+
+def ddim_step_asym(x: torch.Tensor, e: torch.Tensor, e_s: torch.Tensor, alpha_t: float, alpha_next: float, gP: float = 1.0, gD: float = 0.0,
+                   out: Optional[torch.Tensor] = None, return_x0: bool = True):
+    """dpb_ddim_step_asym (engine-independent): per row of x, e, e_s [n, N] (fp32 on a HIP device) the asymmetric DDIM step d = e_s - e,
+    eP = e + gP d, eD = e + gD d, P = (x - eP sqrt(1 - alpha_t)) / sqrt(alpha_t), out = sqrt(alpha_next) P + sqrt(1 - alpha_next) eD, fp32 in
+    dpb_ddim_step's operation order.  out: the tensor written into (x itself for an in-place step), allocated here when None.  Returns (out, P or
+    None, stats [n, 2] fp64 = (sum d^2, flag)); a row holding a non-finite value has its flag set and NaN in its row of out and P.  No host sync."""
+    lib = L.load()
+    if not (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and x.is_contiguous()):
+        raise L.DpbError("x must be a contiguous fp32 [n, N] tensor on a HIP device")
+    n, N = x.shape
+    for name, a in (("e", e), ("e_s", e_s)):
+        if not (a.is_cuda and a.device == x.device and a.dtype == torch.float32 and a.is_contiguous() and a.numel() == n * N):
+            raise L.DpbError(f"{name} must be a contiguous fp32 tensor of {n * N} elements on {x.device}")
+    with torch.cuda.device(x.device):
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        if out is None:
+            out = torch.empty_like(x)
+        elif not (out.is_cuda and out.device == x.device and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n * N):
+            raise L.DpbError(f"out must be a contiguous fp32 tensor of {n * N} elements on {x.device}")
+        x0 = torch.empty_like(x) if return_x0 else None
+        stats = torch.empty(max(n, 1), 2, dtype=torch.float64, device=x.device)
+        need = int(lib.dpb_ddim_step_asym_scratch_bytes(n, N))
+        scratch = torch.empty(max(need // 8, 1), dtype=torch.float64, device=x.device)
+        L.check(lib.dpb_ddim_step_asym(_ptr(x), _ptr(e), _ptr(e_s), _ptr(out), _ptr(x0), n, N, float(alpha_t), float(alpha_next), float(gP), float(gD),
+                                       _ptr(stats), _ptr(scratch), need, C.c_void_p(st)))
+    return out, x0, stats

@@ -158,6 +158,13 @@ SYMBOLS = {
     "dpb_inv_jac_chain_scratch_bytes": (C.c_size_t, [_P, _I, _I]),
     "dpb_inv_jac_chain": (_I, [_P, _I, _P, _I, C.POINTER(_F), _P, _P, _I, C.POINTER(C.c_int32), C.POINTER(_F), C.POINTER(_F), _I, _F, _I,
                                _P, _P, _P, _P, _P, C.c_size_t]),
+    # the h-space guidance edit (PullbackUNet.h_space_guidance): t, the alphas, dir and scale are host arrays
+    "dpb_ddim_step_asym_scratch_bytes": (C.c_size_t, [_L, _L]),
+    "dpb_ddim_step_asym": (_I, [_P, _P, _P, _P, _P, _L, _L, _F, _F, _F, _F, _P, _P, C.c_size_t, _P]),
+    "dpb_forward_shift_groups": (_I, [_P, _P, _I, _I, _F, _P, _I, _P, _I, _P, _P, _I, _I, _P]),
+    "dpb_hguide_chain_scratch_bytes": (C.c_size_t, [_P, _I, _I]),
+    "dpb_hguide_chain": (_I, [_P, _I, _I, _P, _I, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _P, _P, _I, C.POINTER(C.c_int32), C.POINTER(_F), _F, _F,
+                              _I, _P, _P, _P, C.c_size_t]),
 }
 
 _lib = None

@@ -56,6 +56,13 @@ decode into the same picture names; --use_sega_reg True --sega_reg_sigma s zeroe
 (edit.py:1212-1214).  --local_projection False is allowed there and needs no local basis at all.  Every chain leaves chain-<name>.pt in the obs
 folder: ||J^T u||, the h-space shift along u and |h - h0| per step.  Deviations: t is the timestep (the reference passes the index edit_t_idx);
 the reference's dynamic_thresholding / preserve_norm / preserve_contrast are methods it never defines and are not built.
+``--edit_ht default|h_space_guidance`` (the reference's flag, define_argparser.py:53) is the third way: with --edit_xt at its default and space h
+(unconditional nets only), every (pc, +-) experiment runs --vis_num chains from x_t whose h-space direction u_pc is ADDED at the tap at every DDIM step
+from --edit_t down to --no_edit_t (default 0.5), with the scales +-linspace(0, --h_edit_step_size, vis_num); --h_guidance_mode asyrp (default: the
+shift enters the predicted x0 only, Kwon et al.'s asymmetric process) or symmetric (the plain DDIM step of the shifted net).  The chains run on the
+device (PullbackUNet.h_space_guidance), then the plain decode from no_edit_t into the same picture names; --local_projection False is allowed as for
+parallel-h.  Every experiment leaves hguide-<name>.pt in the obs folder: ||e_s - e|| and the distance from the plain step per chain and step, the
+scales, the timesteps and the latents at no_edit_t.  The reference calls a h_space_guidance method it never defines; DESIGN.md states what is built.
 """
 from __future__ import annotations
 
@@ -126,6 +133,10 @@ _FLAGS = [  # (name, type, default) -- define_argparser.py:20-110, live path onl
     # parallel-h: the h-space direction held fixed, the x-space direction recomputed at every one of vis_num steps of x_edit_step_size / vis_num
     # (edit.py:1202-1229), with the SEGA rule of edit.py:1212-1214 under --use_sega_reg (sega_reg_sigma 1.0: the reference's commented default)
     ("edit_xt", str, "parallel-x"), ("use_sega_reg", str2bool, False), ("sega_reg_sigma", float, 1.0),
+    # define_argparser.py:53, :82-83: the third branch of the global-basis jobs.  h_space_guidance (with edit_xt at its default): the h-space direction
+    # is added at the tap at every DDIM step from edit_t down to no_edit_t (edit.py:1232-1245), with scales up to h_edit_step_size; h_guidance_mode
+    # is new: asyrp (the shift enters the predicted x0 only) or symmetric (the plain DDIM step of the shifted net)
+    ("edit_ht", str, "default"), ("h_edit_step_size", float, 0), ("no_edit_t", float, 0.5), ("h_guidance_mode", str, "asyrp"),
     # new
     ("pca_rank", int, 2), ("op", str, "mid"), ("block_idx", int, 0), ("vis_num", int, 4), ("vis_num_pc", int, 2), ("weights", str, ""),
     ("net_scale", str, "full"), ("vae", str, "none"), ("text_encoder", str, "none"), ("tokenizer_dir", str, ""),
@@ -169,7 +180,7 @@ def parse_args(argv=None):
                 "(its run_edit_global_frechet_mean_zt belongs to EditUncondDiffusion)")
     if args.run_edit_global_frechet_mean_zt and args.frechet_mean_space not in ("x", "h"):
         p.error("--frechet_mean_space must be x (the spans of vT) or h (the spans of u)")
-    if args.run_edit_global_frechet_mean_zt and args.frechet_mean_space == "h" and not args.local_projection and args.edit_xt != "parallel-h":
+    if args.run_edit_global_frechet_mean_zt and args.frechet_mean_space == "h" and not args.local_projection and args.edit_xt != "parallel-h" and args.edit_ht != "h_space_guidance":
         p.error("--local_projection False is valid for --frechet_mean_space x only")
     if args.frechet_init not in ("member", "flag"):
         p.error("--frechet_init must be member (start at local basis 0) or flag (start at the flag mean of the local bases)")
@@ -178,7 +189,7 @@ def parse_args(argv=None):
                 "(its global-basis jobs belong to EditUncondDiffusion)")
     if args.run_edit_global_flag_mean_zt and args.flag_mean_space not in ("x", "h"):
         p.error("--flag_mean_space must be x (the spans of vT) or h (the spans of u)")
-    if args.run_edit_global_flag_mean_zt and args.flag_mean_space == "h" and not args.local_projection and args.edit_xt != "parallel-h":
+    if args.run_edit_global_flag_mean_zt and args.flag_mean_space == "h" and not args.local_projection and args.edit_xt != "parallel-h" and args.edit_ht != "h_space_guidance":
         p.error("--local_projection False is valid for --flag_mean_space x only")
     if args.run_edit_global_flag_mean_zt and not 0 <= args.flag_rank <= args.pca_rank:
         p.error("--flag_rank must lie in [1, --pca_rank] (0: --pca_rank)")
@@ -194,7 +205,7 @@ def parse_args(argv=None):
                 "basis (its run_edit_global_hungarian_mean_zt belongs to EditUncondDiffusion)")
     if args.run_edit_global_hungarian_mean_zt and args.hungarian_mean_space not in ("x", "h"):
         p.error("--hungarian_mean_space must be x (the directions of vT) or h (the directions of u)")
-    if args.run_edit_global_hungarian_mean_zt and args.hungarian_mean_space == "h" and not args.local_projection and args.edit_xt != "parallel-h":
+    if args.run_edit_global_hungarian_mean_zt and args.hungarian_mean_space == "h" and not args.local_projection and args.edit_xt != "parallel-h" and args.edit_ht != "h_space_guidance":
         p.error("--local_projection False is valid for --hungarian_mean_space x only")
     if args.run_edit_global_hungarian_mean_zt and args.hungarian_distance not in ("1/cosine", "cosine"):
         p.error("--hungarian_distance must be 1/cosine (the reference's call) or cosine")
@@ -207,6 +218,27 @@ def parse_args(argv=None):
     if args.edit_xt == "parallel-h" and "stable-diffusion" in args.model_name:
         p.error("--edit_xt parallel-h belongs to the global-basis jobs of the unconditional nets: the reference's Stable Diffusion driver has no such "
                 "branch")
+    if args.edit_ht not in ("default", "h_space_guidance"):
+        p.error("--edit_ht must be default or h_space_guidance (the h-space direction added at the tap at every DDIM step from edit_t to no_edit_t)")
+    if args.h_guidance_mode not in ("asyrp", "symmetric"):
+        p.error("--h_guidance_mode must be asyrp (the shift enters the predicted x0 only) or symmetric (the plain DDIM step of the shifted net)")
+    if args.edit_ht == "h_space_guidance":
+        if "stable-diffusion" in args.model_name:
+            p.error("--edit_ht h_space_guidance belongs to the global-basis jobs of the unconditional nets: the reference's Stable Diffusion driver has "
+                    "no such branch")
+        if args.edit_xt == "parallel-h":
+            p.error("--edit_ht h_space_guidance and --edit_xt parallel-h exclude each other: the guidance branch runs with --edit_xt at its default")
+        if args.h_edit_step_size == 0:
+            p.error("--edit_ht h_space_guidance needs --h_edit_step_size != 0: the largest scale of the ladder of shifts")
+        if not args.no_edit_t < args.edit_t:
+            p.error("--edit_ht h_space_guidance needs --no_edit_t < --edit_t: the guided interval runs from edit_t down to no_edit_t")
+        if args.performance_boosting_t > 0 and args.no_edit_t < args.performance_boosting_t:
+            p.error("--edit_ht h_space_guidance: the guided interval must end at or above --performance_boosting_t (the decode takes eta = 1 below "
+                    "it, the chain is eta = 0 only)")
+        for job, space in (("run_edit_global_frechet_mean_zt", "frechet_mean_space"), ("run_edit_global_flag_mean_zt", "flag_mean_space"),
+                           ("run_edit_global_hungarian_mean_zt", "hungarian_mean_space")):
+            if getattr(args, job) and getattr(args, space) != "h":
+                p.error(f"--edit_ht h_space_guidance adds an h-space direction at the tap: --{space} must be h")
     if args.run_tangent_space_clusters:
         pairs = max(0, args.num_local_basis) * len(args.h_t_values)
         if not 1 <= args.num_clusters <= pairs:
@@ -324,6 +356,8 @@ def build_unet(args) -> PullbackUNet:
             max_batch = max(max_batch, min(args.trajectory_batch, 2 * n), min(args.trajectory_batch, n * (args.vis_num + 1)))
             if getattr(args, "edit_xt", "parallel-x") == "parallel-h":      # the chains of one inv_jac_chain call: a cotangent each (max_batch holds them already)
                 max_rank = max(max_rank, min(args.trajectory_batch, n))
+            if getattr(args, "edit_ht", "default") == "h_space_guidance":   # vis_num chains per experiment, a plain and a shifted row each per call
+                max_batch = max(max_batch, min(args.trajectory_batch, 2 * n * args.vis_num))
     if args.is_stable_diffusion:
         cfg = cf.sd_config_for(args.model_name)           # SD-v1.x or SD-2(.1)-base; anything else raises
         if small:

@@ -684,6 +684,80 @@ class PullbackUNet:
         return out
 
 
+    # ------------------------------------------------------------------ the h-space guidance edit
+    def h_space_guidance(self, x=None, timesteps=None, alphas=None, alphas_next=None, u=None, dirs=None, scales=None, mode="asyrp",
+                         encoder_hidden_states=None, op=None, block_idx=None, check=True):
+        """The edit_ht == 'h_space_guidance' branch of the reference's global-basis edits (src/modules/edit.py:1232-1245, :1500-1513, which call a
+        method the reference never defines) as Kwon et al. state it (Asyrp), one device loop (dpb_hguide_chain): chain b starts at x[b] and runs
+        the S DDIM steps (timesteps[j], alphas[j]) -> alphas_next[j]; at every step the net runs plain (e) and with scales[b] * u[:, dirs[b]] /
+        ||u[:, dirs[b]]|| added at the tap (op, block_idx) (e_s), and with d = e_s - e the step is
+            P = (x - (e + gP d) sqrt(1 - a)) / sqrt(a),   x' = sqrt(a_next) P + sqrt(1 - a_next) (e + gD d)                      (eta = 0).
+        mode: "asyrp" (gP, gD) = (1, 0), the asymmetric reverse process; "symmetric" (1, 1), the plain DDIM step of the shifted net; or a pair of
+        finite floats.  x [n, C, H, W]; timesteps / alphas / alphas_next: S floats each, shared by the chains (scheduler.ddim_triples gives them);
+        u [D] or [D, k] columns as the pullbacks and PCAs return them, normalised here as in h_traversal; dirs: n column indices (default: 0, or
+        0 .. n-1 when k == n > 1); scales: a float or n.  A step runs 2n rows: more chains than max_batch // 2 run in groups.  Returns a dict of
+        tensors on x.device: states [n, S + 1, C, H, W] (states[:, 0] = x), delta_norm [n, S] = ||d||, dx_norm [n, S] = |-sqrt(a_next)
+        sqrt(1 - a) / sqrt(a) gP + sqrt(1 - a_next) gD| ||d||, the distance from the plain DDIM step.  A chain that meets a non-finite value has NaN
+        from there on: ValueError names the chain and the step, check=False returns the NaNs.  Classifier-free guidance is not part of the chain:
+        SD takes the encoder_hidden_states rows it is given (one, or one per chain)."""
+        key = self._decoder_tap(op, block_idx)
+        eng = self.engine
+        d = eng.tap_numel(key)
+        if x is None or x.dim() != 4:
+            raise ValueError("x must be [n, C, H, W]")
+        n = x.shape[0]
+        if isinstance(mode, str):
+            if mode not in ("asyrp", "symmetric"):
+                raise ValueError(f"mode {mode!r}: 'asyrp', 'symmetric' or a pair (gP, gD)")
+            gP, gD = (1.0, 0.0) if mode == "asyrp" else (1.0, 1.0)
+        else:
+            gP, gD = (float(a) for a in mode)
+        if not (math.isfinite(gP) and math.isfinite(gD)):
+            raise ValueError(f"mode ({gP}, {gD}) is not finite")
+        as_list = lambda a: [float(v) for v in (a.reshape(-1).tolist() if torch.is_tensor(a) else a)]
+        tl, al, an = as_list(timesteps), as_list(alphas), as_list(alphas_next)
+        S = len(tl)
+        if S < 1 or len(al) != S or len(an) != S:
+            raise ValueError(f"timesteps, alphas and alphas_next need the same number (>= 1) of entries, got {S}, {len(al)}, {len(an)}")
+        if u is None or u.numel() == 0 or u.numel() % d != 0 or (u.dim() == 1 and u.numel() != d) or (u.dim() == 2 and u.shape[0] != d) or u.dim() > 2:
+            raise ValueError(f"u must be [{d}] or [{d}, k] (columns: directions at the tap ({op}, {block_idx}))")
+        U = u.detach().reshape(d, -1).to(device=self.device, dtype=torch.float32)
+        U = (U / U.norm(dim=0, keepdim=True)).T.contiguous()                     # [k, D] rows, unit norm (as h_traversal)
+        k = U.shape[0]
+        if dirs is None:
+            dirs = list(range(n)) if k == n and n > 1 else [0] * n
+        dirs = [int(a) for a in (dirs.tolist() if torch.is_tensor(dirs) else dirs)]
+        sc = scales.tolist() if torch.is_tensor(scales) else scales
+        sc = [float(a) for a in sc] if isinstance(sc, (list, tuple)) else [float(sc)] * n
+        if len(dirs) != n or len(sc) != n:
+            raise ValueError(f"dirs and scales need one entry per chain ({n}), got {len(dirs)}, {len(sc)}")
+        if any(a < 0 or a >= k for a in dirs):
+            raise ValueError(f"dirs {dirs} outside [0, {k}): u has {k} direction(s)")
+        ctx = encoder_hidden_states
+        if ctx is not None and ctx.shape[0] not in (1, n):
+            raise ValueError(f"encoder_hidden_states has {ctx.shape[0]} rows for {n} chains: one, or one per chain")
+        group = eng.max_batch // 2
+        if group < 1:
+            raise ValueError(f"h_space_guidance runs a plain and a shifted row per chain: the engine needs max_batch >= 2, has {eng.max_batch}")
+        parts = []
+        for b0 in range(0, n, group):
+            sl = slice(b0, min(b0 + group, n))
+            cg = None if ctx is None else (ctx if ctx.shape[0] == 1 else ctx[sl])
+            parts.append(eng.hguide_chain(x[sl], tl, al, an, cg, key, U, dirs[sl], sc[sl], gP, gD))
+        states = torch.cat([p[0] for p in parts], dim=1).transpose(0, 1).contiguous()
+        delta = torch.cat([p[1] for p in parts], dim=1).transpose(0, 1)          # [n, S, 2] fp64
+        a_t, a_n = torch.tensor(al, dtype=torch.float64), torch.tensor(an, dtype=torch.float64)
+        coef = (-a_n.sqrt() * (1 - a_t).sqrt() / a_t.sqrt() * gP + (1 - a_n).sqrt() * gD).abs()
+        dn = delta[..., 0].sqrt().to(x.device)
+        out = {"states": states.to(device=x.device, dtype=x.dtype), "delta_norm": dn, "dx_norm": dn * coef.to(x.device)}
+        if check:
+            flag = delta[..., 1].cpu()
+            if bool((flag != 0).any()):
+                b, j = [int(a) for a in (flag != 0).nonzero()[0]]
+                raise ValueError(f"h_space_guidance: chain {b} holds a non-finite value at step {j}; check=False returns the NaN states")
+        return out
+
+
 def bind(unet, kind: str, cfg, dtype=torch.float32, device="cuda:0", **kw) -> PullbackUNet:
     """Attach the HIP-backed methods onto an existing U-Net module, like the reference's
     ``types.MethodType`` injection (utils.py:103-104, :326-337).  ``unet.state_dict()`` uses diffusers' keys: ``UNet2DConditionModel`` for "sd"
@@ -699,6 +773,7 @@ def bind(unet, kind: str, cfg, dtype=torch.float32, device="cuda:0", **kw) -> Pu
     unet.get_h_to_e = types.MethodType(lambda self, *a, **k: self._dpb.get_h_to_e(*a, **k), unet)
     unet.local_encoder_pullback_batch = types.MethodType(lambda self, *a, **k: self._dpb.local_encoder_pullback_batch(*a, **k), unet)
     unet.inv_jac_chain = types.MethodType(lambda self, *a, **k: self._dpb.inv_jac_chain(*a, **k), unet)
+    unet.h_space_guidance = types.MethodType(lambda self, *a, **k: self._dpb.h_space_guidance(*a, **k), unet)
     if kind == "sd":
         unet.local_encoder_pullback_zt = types.MethodType(lambda self, *a, **k: self._dpb.local_encoder_pullback_zt(*a, **k), unet)
         unet.local_decoder_pullback_zt = types.MethodType(lambda self, *a, **k: self._dpb.local_decoder_pullback_zt(*a, **k), unet)

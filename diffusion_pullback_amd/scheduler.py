@@ -80,6 +80,23 @@ class YHCustomScheduler(object):
     def scale_model_input(self, sample, t=None):            # diffusers API used at edit.py:158 (identity for DDIM)
         return sample
 
+    def ddim_triples(self, t_start_idx: int, t_end_idx: int):
+        """The (t, alpha_t, alpha_next) of the steps with indices t_start_idx .. t_end_idx - 1 of the table set_timesteps built, as three lists of
+        Python floats holding the fp32 values: exactly what ``step`` looks up for each of them (the float timestep truncated by ``extract``), for
+        a device loop that takes its coefficients up front (PullbackUNet.h_space_guidance)."""
+        if self.timesteps is None:
+            raise ValueError("set_timesteps has not been called")
+        n = len(self.timesteps)
+        if not (0 <= t_start_idx < t_end_idx <= n):
+            raise ValueError(f"step indices [{t_start_idx}, {t_end_idx}) outside the {n} steps of the table")
+        ts, al, an = [], [], []
+        for i in range(t_start_idx, t_end_idx):
+            t, t_next = self.timesteps[i], self.timesteps_next[i]
+            ts.append(float(t))
+            al.append(float(extract(self.alphas_cumprod, t.reshape(()).cpu(), (1,)).item()))
+            an.append(float(extract(self.alphas_cumprod, t_next.reshape(()).cpu(), (1,)).item()))
+        return ts, al, an
+
     # utils.py:1197-1241 (= :288-315)
     def step(self, et, t, xt, eta=0.0, noise=None, **kwargs):
         assert et.shape == xt.shape, "et, xt shape should be same"

@@ -686,6 +686,56 @@ int dpb_inv_jac_chain(dpb_engine* e, int tap_buf, const float* x /*dev [n][N_in]
                       float* states /*dev [steps+1][n][N_in]*/, float* vk /*dev [steps][n][N_in] or NULL*/, double* stats /*dev [steps][n][4]*/,
                       double* shift /*dev [steps+1][n][2]*/, void* scratch, size_t scratch_bytes);
 
+/* ---- the h-space guidance edit (additive to ABI version 1) --------------------------------------------------------------------------
+ * The edit_ht == 'h_space_guidance' branch of the global-basis edit jobs (src/modules/edit.py:1232-1245, :1500-1513; the reference calls a
+ * h_space_guidance method it never defines), as Kwon et al. state it (Asyrp): a chain carries a state x, a direction c = u[dir] at the tap and a
+ * scale sigma; at every DDIM step of the guided interval
+ *   e = eps(x, t),  e_s = eps(x, t | h <- h + sigma c)  (a shifted row of dpb_forward_shift),  d = e_s - e,  eP = e + gP d,  eD = e + gD d,
+ *   P = (x - eP sqrt(1 - a)) / sqrt(a),   x' = sqrt(a_next) P + sqrt(1 - a_next) eD                                              (eta = 0).
+ * (gP, gD) = (1, 0): Asyrp's asymmetric process; (1, 1): the plain DDIM step of the shifted net; any finite pair is accepted.
+ *
+ * dpb_ddim_step_asym (engine-independent): x, e, e_s [n][N] fp32; out [n][N] (may alias x: every element is read by the thread that overwrites it);
+ * x0 [n][N] or NULL receives P; alpha_t, alpha_next, gP, gD host scalars; stats [n][2] FP64 on the device = (sum d^2, flag).  fp32 arithmetic in
+ * exactly the operation order of dpb_ddim_step (square roots in fp32 of the fp32 alphas); d, eP and eD are each formed first with one rounding
+ * (eP = fma(gP, d, e)), so a row with d == 0 or gP == gD == 0 equals dpb_ddim_step on (x, e) bit for bit.  sum d^2: the fp32 d widened to fp64,
+ * per-workgroup partial sums of slices of 4096 elements added in slice order, no atomics -- a function of the row and N only.  A row's results are
+ * bitwise the same alone and at any position of a stack, whatever the alignment: rows start at b N floats, and each workgroup takes 16-byte accesses
+ * for an aligned row, 4-byte ones otherwise, with the same elements per thread.  A row holding a non-finite value (in x, e or e_s): flag = 1 and NaN
+ * in exactly that row of out and x0; no other row changes by a bit.  Two launches per 32768 rows, no host synchronisation.  scratch: 8-byte aligned
+ * device memory of >= dpb_ddim_step_asym_scratch_bytes(n, N) bytes (0 when invalid).  Refused (dpb_last_error): null pointers, n < 1, N < 1,
+ * non-finite scalars, an alpha outside (0, 1], scratch too small or misaligned.
+ *
+ * dpb_forward_shift_groups: dpb_forward_shift for `groups` shifted copies of xbatch DIFFERENT samples.  x [xbatch], ctx [xbatch]; the batch has
+ * xbatch * groups rows, row r = g * xbatch + b is sample b in group g with its own dir[r] (-1: unshifted) and scale[r] (HOST arrays).  The ops up to
+ * the producer of src_buf run ONCE at xbatch; the tap is written as `groups` shifted copies of its xbatch rows; the first xbatch samples of every
+ * buffer the rest of the pass still reads (the set of dpb_forward_shift, derived from the tape) are copied as one block to each other group in one
+ * launch; the ops after the tap run at xbatch * groups.  groups = 1 is dpb_forward_shift(xbatch = batch) bit for bit, xbatch = 1 its shared-prefix
+ * call bit for bit (both take that call's own launches).  State rules and synchronisation of dpb_forward_shift.  Refused: xbatch < 1, groups < 1 or
+ * above 64, xbatch * groups > max_batch, nu < 1, a dir[r] outside [-1, nu), a non-finite scale[r], the (src_buf, dst_buf) rules of dpb_forward_shift.
+ *
+ * dpb_hguide_chain: n chains advanced together through `steps` DDIM steps, no host work between the steps.  x [n][N_in] fp32 NCHW; t, alpha_t,
+ * alpha_next: HOST arrays of `steps` entries (every chain shares a step's timestep); ctx [n][L][Dc] or NULL; u [nu][N_h] fp32 NCHW-flattened
+ * directions of tap_buf; dir [n] in [0, nu) and scale [n]: HOST arrays.  eps_buf: the network's output buffer (the shape of x).  states
+ * [steps + 1][n][N_in]: states[0] = x (states may start at x); step j is one dpb_forward_shift_groups pass with groups = 2 at states[j] and t[j] through
+ * to eps_buf -- group 0 unshifted (dir = -1), group 1 the chains' shifts -- and dpb_ddim_step_asym into states[j + 1]; delta [steps][n][2] FP64: its
+ * stats.  Host synchronisation: ONE for the call -- the sinusoid rows of ALL the steps are built on the host at entry and uploaded in one copy into
+ * scratch; each step moves its row into the time-embedding buffer on the device.  No device allocation: scratch is 256-byte aligned device memory
+ * of >= dpb_hguide_chain_scratch_bytes(e, n, steps) bytes (0 when invalid).  The call leaves no primal state, as dpb_forward.  Classifier-free
+ * guidance is not part of the chain.  Refused (dpb_last_error; the next call is unaffected): 2n > max_batch, n < 1, steps < 1, nu < 1, a dir[b]
+ * outside [0, nu), a non-finite t[j], scale[b], gP or gD, an alpha outside (0, 1], a tap that is not an x-dependent activation, eps_buf not
+ * downstream of it or not of the input's shape, a missing ctx, scratch too small or misaligned. */
+size_t dpb_ddim_step_asym_scratch_bytes(int64_t n, int64_t N);   /* 0 when invalid */
+int dpb_ddim_step_asym(const float* x, const float* e, const float* e_s, float* out, float* x0 /*or NULL*/, int64_t n, int64_t N, float alpha_t,
+                       float alpha_next, float gP, float gD, double* stats /*dev [n][2]*/, void* scratch, size_t scratch_bytes, void* hip_stream);
+int dpb_forward_shift_groups(dpb_engine* e, const float* x, int xbatch, int groups, float t, const float* ctx, int src_buf, const float* u, int nu,
+                             const int32_t* dir /*host [xbatch*groups]*/, const float* scale /*host [xbatch*groups]*/, int dst_buf, int channels,
+                             float* out);
+size_t dpb_hguide_chain_scratch_bytes(const dpb_engine* e, int n, int steps);
+int dpb_hguide_chain(dpb_engine* e, int tap_buf, int eps_buf, const float* x /*dev [n][N_in]*/, int n, const float* t /*host [steps]*/,
+                     const float* alpha_t /*host [steps]*/, const float* alpha_next /*host [steps]*/, const float* ctx /*dev [n][L][Dc] or NULL*/,
+                     const float* u /*dev [nu][N_h]*/, int nu, const int32_t* dir /*host [n]*/, const float* scale /*host [n]*/, float gP, float gD,
+                     int steps, float* states /*dev [steps+1][n][N_in]*/, double* delta /*dev [steps][n][2]*/, void* scratch, size_t scratch_bytes);
+
 /* Token + position embedding lookup of the CLIP text encoder behind pipe._encode_prompt (src/modules/edit.py:505-522):
  * out[b][c][t] = tok_table[ids[b][t]][c] + pos_table[t][c], fp32 in the engine's NCHW boundary layout (H*W = tokens),
  * ready for dpb_primal of a text-encoder tape.  Tables are [vocab][channels] / [tokens][channels] in `dtype`. */
