@@ -5,7 +5,7 @@
 //   shift statistics a = <h - h0, c> / ||c|| and q = ||h - h0||^2 per row, c = sign u[dir];
 //   cotangent gather cot[b] = sign[b] u[dir[b]].
 // fp32 in / fp32 out, every sum in fp64 in ONE fixed chain: thread t of a workgroup adds the elements of its groups of four in index order into its own
-// accumulator, the 256 accumulators meet in block_sum, and a row's slices of CH_SLICE elements are added in slice order by every workgroup that needs
+// accumulator, the 256 accumulators meet in block_sum, and a row's slices of ROW_SLICE elements are added in slice order by every workgroup that needs
 // the total.  No atomics in any floating-point sum: a row's results are a function of the row and N only -- not of n, of the row's position in the
 // stack or of the alignment of its pointers (the 16-byte and the 4-byte access paths give every thread the same elements in the same order).  The
 // count of kept elements is a sum of integers below 2^53, exact in fp64 in any order: the workgroups add theirs with one fp64 atomic each.
@@ -18,54 +18,29 @@ namespace dpb {
 
 namespace {
 
-constexpr int CH_NT = 256;                  // threads per workgroup
-constexpr int CH_GROUPS = 4;                // groups of four elements per thread and slice
-constexpr int CH_SLICE = CH_NT * 4 * CH_GROUPS;   // elements of a row per workgroup: 4096
-
 struct ChainSteps { float v[CHAIN_MAX_ROWS]; };               // host lists travel as kernel arguments, CHAIN_MAX_ROWS rows per launch
 struct ChainDirs { int dir[CHAIN_MAX_ROWS]; float sign[CHAIN_MAX_ROWS]; };
 
-__device__ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// elements j .. j+3 of a row of length N (j % 4 == 0, j < N), zeros past its end; al: the row pointer is 16-byte aligned
-__device__ inline float4 ch_load4(const float* row, long j, long N, bool al) {
-  if (al && j + 3 < N) return *reinterpret_cast<const float4*>(row + j);
-  float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-  v.x = row[j];
-  if (j + 1 < N) v.y = row[j + 1];
-  if (j + 2 < N) v.z = row[j + 2];
-  if (j + 3 < N) v.w = row[j + 3];
-  return v;
-}
-
-__device__ inline void ch_store4(float* row, long j, long N, bool al, float4 v) {
-  if (al && j + 3 < N) { *reinterpret_cast<float4*>(row + j) = v; return; }
-  row[j] = v.x;
-  if (j + 1 < N) row[j + 1] = v.y;
-  if (j + 2 < N) row[j + 2] = v.z;
-  if (j + 3 < N) row[j + 3] = v.w;
-}
-
 // part[b][slice] = (sum w, sum w^2) of the slice in fp64; the workgroup of slice 0 clears the row's kept count (stats[b][2]) for the apply kernel
-__global__ __launch_bounds__(CH_NT) void chain_partial_kernel(const float* W, long N, double* part, double* stats) {
-  __shared__ double red[CH_NT / 64];
+__global__ __launch_bounds__(ROW_NT) void chain_partial_kernel(const float* W, long N, double* part, double* stats) {
+  __shared__ double red[ROW_NT / 64];
   const int b = blockIdx.y, t = threadIdx.x;
   const long nsl = gridDim.x;
   const float* row = W + (long)b * N;
   const bool al = aligned16(row);
   double s1 = 0.0, s2 = 0.0;
 #pragma unroll
-  for (int i = 0; i < CH_GROUPS; ++i) {
-    const long j = (long)blockIdx.x * CH_SLICE + ((long)i * CH_NT + t) * 4;
+  for (int i = 0; i < ROW_GROUPS; ++i) {
+    const long j = (long)blockIdx.x * ROW_SLICE + ((long)i * ROW_NT + t) * 4;
     if (j < N) {
-      const float4 w = ch_load4(row, j, N, al);
+      const float4 w = row_load4(row, j, N, al);
       const double a0 = w.x, a1 = w.y, a2 = w.z, a3 = w.w;
       s1 += a0; s1 += a1; s1 += a2; s1 += a3;
       s2 += a0 * a0; s2 += a1 * a1; s2 += a2 * a2; s2 += a3 * a3;
     }
   }
-  s1 = block_sum<CH_NT>(s1, red);
-  s2 = block_sum<CH_NT>(s2, red);
+  s1 = block_sum<ROW_NT>(s1, red);
+  s2 = block_sum<ROW_NT>(s2, red);
   if (t == 0) {
     double* p = part + ((long)b * nsl + blockIdx.x) * 2;
     p[0] = s1; p[1] = s2;
@@ -74,20 +49,13 @@ __global__ __launch_bounds__(CH_NT) void chain_partial_kernel(const float* W, lo
 }
 
 // v = fl32(-w / sqrt(S2)), the SEGA mask, x_out = fl32(x + step v); the workgroup of slice 0 writes the row's (S2, std, . , flag)
-__global__ __launch_bounds__(CH_NT) void chain_apply_kernel(const float* W, const float* x, float* x_out, float* vk, long N, ChainSteps steps,
+__global__ __launch_bounds__(ROW_NT) void chain_apply_kernel(const float* W, const float* x, float* x_out, float* vk, long N, ChainSteps steps,
                                                             double sega_sigma, const double* part, double* stats) {
-  __shared__ double red[CH_NT / 64];
+  __shared__ double red[ROW_NT / 64];
   __shared__ double row_s[2];
   const int b = blockIdx.y, t = threadIdx.x;
   const long nsl = gridDim.x, off = (long)b * N;
-  if (t == 0) {
-    double s1 = 0.0, s2 = 0.0;
-    for (long s = 0; s < nsl; ++s) {                       // slices in index order, the same chain in every workgroup of the row
-      s1 += part[((long)b * nsl + s) * 2];
-      s2 += part[((long)b * nsl + s) * 2 + 1];
-    }
-    row_s[0] = s1; row_s[1] = s2;
-  }
+  if (t == 0) sum_slices<2>(part + (long)b * nsl * 2, nsl, row_s);
   __syncthreads();
   const double S1 = row_s[0], S2 = row_s[1];
   const bool bad = !(S2 > 0.0) || !(S2 < 1.7e308);          // zero, NaN or inf: the row has no direction
@@ -103,11 +71,11 @@ __global__ __launch_bounds__(CH_NT) void chain_apply_kernel(const float* W, cons
   const bool alw = aligned16(W + off), alx = aligned16(x + off), alo = aligned16(x_out + off), alv = vk && aligned16(vk + off);
   double kept = 0.0;
 #pragma unroll
-  for (int i = 0; i < CH_GROUPS; ++i) {
-    const long j = (long)blockIdx.x * CH_SLICE + ((long)i * CH_NT + t) * 4;
+  for (int i = 0; i < ROW_GROUPS; ++i) {
+    const long j = (long)blockIdx.x * ROW_SLICE + ((long)i * ROW_NT + t) * 4;
     if (j >= N) continue;
-    const float4 w = ch_load4(W + off, j, N, alw);
-    const float4 xv = ch_load4(x + off, j, N, alx);
+    const float4 w = row_load4(W + off, j, N, alw);
+    const float4 xv = row_load4(x + off, j, N, alx);
     const float wi[4] = {w.x, w.y, w.z, w.w}, xi[4] = {xv.x, xv.y, xv.z, xv.w};
     float vo[4], xo[4];
 #pragma unroll
@@ -119,10 +87,10 @@ __global__ __launch_bounds__(CH_NT) void chain_apply_kernel(const float* W, cons
       vo[c] = bad ? nanf_ : v;
       xo[c] = bad ? nanf_ : (float)((double)xi[c] + step * (double)v);
     }
-    ch_store4(x_out + off, j, N, alo, make_float4(xo[0], xo[1], xo[2], xo[3]));
-    if (vk) ch_store4(vk + off, j, N, alv, make_float4(vo[0], vo[1], vo[2], vo[3]));
+    row_store4(x_out + off, j, N, alo, make_float4(xo[0], xo[1], xo[2], xo[3]));
+    if (vk) row_store4(vk + off, j, N, alv, make_float4(vo[0], vo[1], vo[2], vo[3]));
   }
-  kept = block_sum<CH_NT>(bad ? 0.0 : kept, red);
+  kept = block_sum<ROW_NT>(bad ? 0.0 : kept, red);
   if (t == 0) {
     double* st = stats + (long)b * 4;
     if (kept != 0.0) atomicAdd(st + 2, kept);              // integers below 2^53: exact, the order of the workgroups does not matter
@@ -131,44 +99,37 @@ __global__ __launch_bounds__(CH_NT) void chain_apply_kernel(const float* W, cons
 }
 
 // out[b] = (a, q): a = <h - h0, c> / ||c||, q = ||h - h0||^2, c = sign[b] u[dir[b]]; one workgroup per row, the chain of rowsumsq_kernel
-__global__ __launch_bounds__(CH_NT) void chain_shift_kernel(const float* h, const float* h0, const float* u, long D, ChainDirs dirs, double* out) {
-  __shared__ double red[CH_NT / 64];
+__global__ __launch_bounds__(ROW_NT) void chain_shift_kernel(const float* h, const float* h0, const float* u, long D, ChainDirs dirs, double* out) {
+  __shared__ double red[ROW_NT / 64];
   const int b = blockIdx.x;
   const float *hr = h + (long)b * D, *gr = h0 + (long)b * D, *ur = u + (long)dirs.dir[b] * D;
   const bool alh = aligned16(hr), alg = aligned16(gr), alu = aligned16(ur);
   const double sg = (double)dirs.sign[b];
   double dc = 0.0, cc = 0.0, dd = 0.0;
-  for (long j = (long)threadIdx.x * 4; j < D; j += CH_NT * 4) {
-    const float4 a = ch_load4(hr, j, D, alh), g = ch_load4(gr, j, D, alg), c4 = ch_load4(ur, j, D, alu);
+  for (long j = (long)threadIdx.x * 4; j < D; j += ROW_NT * 4) {
+    const float4 a = row_load4(hr, j, D, alh), g = row_load4(gr, j, D, alg), c4 = row_load4(ur, j, D, alu);
     const double d[4] = {(double)a.x - (double)g.x, (double)a.y - (double)g.y, (double)a.z - (double)g.z, (double)a.w - (double)g.w};
     const double c[4] = {sg * (double)c4.x, sg * (double)c4.y, sg * (double)c4.z, sg * (double)c4.w};
 #pragma unroll
     for (int i = 0; i < 4; ++i) { dc += d[i] * c[i]; cc += c[i] * c[i]; dd += d[i] * d[i]; }
   }
-  dc = block_sum<CH_NT>(dc, red);
-  cc = block_sum<CH_NT>(cc, red);
-  dd = block_sum<CH_NT>(dd, red);
+  dc = block_sum<ROW_NT>(dc, red);
+  cc = block_sum<ROW_NT>(cc, red);
+  dd = block_sum<ROW_NT>(dd, red);
   if (threadIdx.x == 0) { out[(long)b * 2] = dc / sqrt(cc); out[(long)b * 2 + 1] = dd; }
 }
 
 // cot[b][j] = sign[b] * u[dir[b]][j] (one fp32 product: exact for sign = +-1)
-__global__ __launch_bounds__(CH_NT) void chain_gather_kernel(const float* u, long D, ChainDirs dirs, float* cot) {
+__global__ __launch_bounds__(ROW_NT) void chain_gather_kernel(const float* u, long D, ChainDirs dirs, float* cot) {
   const int b = blockIdx.y;
-  const long j = ((long)blockIdx.x * CH_NT + threadIdx.x) * 4;
+  const long j = ((long)blockIdx.x * ROW_NT + threadIdx.x) * 4;
   if (j >= D) return;
   const float* ur = u + (long)dirs.dir[b] * D;
   float* cr = cot + (long)b * D;
-  float4 v = ch_load4(ur, j, D, aligned16(ur));
+  float4 v = row_load4(ur, j, D, aligned16(ur));
   const float s = dirs.sign[b];
   v.x *= s; v.y *= s; v.z *= s; v.w *= s;
-  ch_store4(cr, j, D, aligned16(cr), v);
-}
-
-int check_rows(const char* who, long n, long N) {
-  if (n < 1 || n > 0x7fffffffL) { set_error("%s: n=%ld rows outside [1, 2^31)", who, n); return -1; }
-  if (N < 1) { set_error("%s: row length %ld < 1", who, N); return -1; }
-  if ((N + CH_SLICE - 1) / CH_SLICE > 0x7fffffffL) { set_error("%s: row length %ld too large", who, N); return -1; }
-  return 0;
+  row_store4(cr, j, D, aligned16(cr), v);
 }
 
 int fill_dirs(const char* who, ChainDirs& d, const int32_t* dir, const float* sign, long r0, int rows, int nu) {
@@ -182,10 +143,7 @@ int fill_dirs(const char* who, ChainDirs& d, const int32_t* dir, const float* si
 
 }  // namespace
 
-size_t direction_step_scratch_bytes(long n, long N) {
-  if (n < 1 || N < 1) return 0;
-  return (size_t)n * (size_t)((N + CH_SLICE - 1) / CH_SLICE) * 2 * sizeof(double);
-}
+size_t direction_step_scratch_bytes(long n, long N) { return row_partial_bytes(n, N); }
 
 int launch_direction_step(const float* W, const float* x, float* x_out, float* vk, const float* step, float sega_sigma, long n, long N, double* stats,
                           void* scratch, size_t scratch_bytes, hipStream_t st) {
@@ -198,13 +156,13 @@ int launch_direction_step(const float* W, const float* x, float* x_out, float* v
   if (std::isnan(sega_sigma)) { set_error("direction_step: sega_sigma is NaN"); return -1; }
   for (long b = 0; b < n; ++b)
     if (!std::isfinite(step[b])) { set_error("direction_step: step[%ld] is not finite", b); return -1; }
-  const long nsl = (N + CH_SLICE - 1) / CH_SLICE;
+  const long nsl = row_slices(N);
   double* part = (double*)scratch;
   for (long r0 = 0; r0 < n; r0 += CHAIN_MAX_ROWS) {
     const int rows = (int)std::min<long>(CHAIN_MAX_ROWS, n - r0);
     ChainSteps s;
     for (int i = 0; i < rows; ++i) s.v[i] = step[r0 + i];
-    const dim3 grid((unsigned)nsl, (unsigned)rows), block(CH_NT);
+    const dim3 grid((unsigned)nsl, (unsigned)rows), block(ROW_NT);
     const long o = r0 * N;
     DPB_LAUNCH(chain_partial_kernel, grid, block, 0, st, W + o, N, part + r0 * nsl * 2, stats + r0 * 4);
     DPB_LAUNCH(chain_apply_kernel, grid, block, 0, st, W + o, x + o, x_out + o, vk ? vk + o : nullptr, N, s, (double)sega_sigma,
@@ -223,7 +181,7 @@ int launch_shift_stats(const float* h, const float* h0, const float* u, int nu, 
     const int rows = (int)std::min<long>(CHAIN_MAX_ROWS, n - r0);
     ChainDirs d;
     if (fill_dirs("shift_stats", d, dir, sign, r0, rows, nu)) return -1;
-    DPB_LAUNCH(chain_shift_kernel, dim3((unsigned)rows), dim3(CH_NT), 0, st, h + r0 * D, h0 + r0 * D, u, D, d, out + r0 * 2);
+    DPB_LAUNCH(chain_shift_kernel, dim3((unsigned)rows), dim3(ROW_NT), 0, st, h + r0 * D, h0 + r0 * D, u, D, d, out + r0 * 2);
   }
   DPB_CHECK(hipGetLastError());
   return 0;
@@ -237,7 +195,7 @@ int launch_gather_cotangents(const float* u, int nu, const int32_t* dir, const f
     const int rows = (int)std::min<long>(CHAIN_MAX_ROWS, n - r0);
     ChainDirs d;
     if (fill_dirs("gather_cotangents", d, dir, sign, r0, rows, nu)) return -1;
-    DPB_LAUNCH(chain_gather_kernel, dim3((unsigned)((ng + CH_NT - 1) / CH_NT), (unsigned)rows), dim3(CH_NT), 0, st, u, D, d, cot + r0 * D);
+    DPB_LAUNCH(chain_gather_kernel, dim3((unsigned)((ng + ROW_NT - 1) / ROW_NT), (unsigned)rows), dim3(ROW_NT), 0, st, u, D, d, cot + r0 * D);
   }
   DPB_CHECK(hipGetLastError());
   return 0;

@@ -265,14 +265,18 @@ int launch_nhwc_to_nchw(int dtype, const void* src, float* dst, int n, int C, in
   return 0;
 }
 
-// h-space shift of a tap (dpb_forward_shift): P(src)[b] = P(src)[bcast ? 0 : b] + scale[b] * u[dir[b]] for the rows b0 .. b0 + nb - 1 of a batch.
-// h: the tap, NHWC [.][HW][C] in T (C - Cv pad channels, copied); u: fp32 [nu][Cv][HW], the NCHW-flattened layout of every tap at the boundary.
-// One block owns a tile of 32 pixels x 64 channels for ALL rows: every element of h is read and written by one thread only, so the in-place
-// broadcast of row 0 (read once into registers before any row is written) has no hazard.  u goes through LDS (read along pixels, written along
-// channels); the sum is formed in fp32 and rounded once by the store.  VEC: elements per access on the NHWC side (a 16-byte chunk, or 1).
+// h-space shift of a tap, the seam of dpb_forward_shift and dpb_forward_shift_groups: h holds the xb samples the prefix computed (rows 0 .. xb-1 of
+// [groups xb][HW][C]); row g xb + b becomes h[b] + scale u[dir] for every group g.  (xb, groups) = (1, batch): every row is a shifted copy of sample 0;
+// (batch, 1): every row is shifted in place.  h: the tap, NHWC in T (C - Cv pad channels, copied); u: fp32 [nu][Cv][HW], the NCHW-flattened layout of
+// every tap at the boundary.  One block owns a tile of 32 pixels x 64 channels for ALL rows: sample b's tile is read into registers before any of its
+// copies is written, and no other row is a source, so the in-place write of group 0 has no hazard.  u goes through LDS (read along pixels, written
+// along channels); the sum is formed in fp32 and rounded once by the store.  VEC: elements per access on the NHWC side (a 16-byte chunk, or 1).
+// rows: the (dir, scale) of samples b0 .. b0 + nb - 1 in groups g0 .. g0 + ng - 1, entry g nb + r for group g0 + g; a row of group 0 with dir < 0 is
+// its own source and is left alone, every other row is written.
 constexpr int SHIFT_TP = 32, SHIFT_TC = 64;
 template <typename T, int VEC>
-__global__ __launch_bounds__(256) void shift_tap_kernel(T* h, const float* u, ShiftRows rows, int b0, int nb, int bcast, int C, int Cv, long HW) {
+__global__ __launch_bounds__(256) void shift_tap_kernel(T* h, const float* u, ShiftRows rows, int b0, int nb, int g0, int ng, int xb, int C, int Cv,
+                                                        long HW) {
   constexpr int CPP = SHIFT_TC / VEC;                    // accesses per pixel of the tile
   constexpr int ITER = SHIFT_TP * CPP / 256;
   __shared__ float tile[SHIFT_TC][SHIFT_TP + 1];
@@ -280,73 +284,75 @@ __global__ __launch_bounds__(256) void shift_tap_kernel(T* h, const float* u, Sh
   const int c0 = blockIdx.y * SHIFT_TC;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   const long img = HW * (long)C;
-  float src[ITER][VEC];
   auto ld = [&](const T* p, float* o) {
     if constexpr (VEC == 1) o[0] = TT<T>::ld(p); else Vec<T>::load(p, o);
   };
   auto st = [&](T* p, const float* o) {
     if constexpr (VEC == 1) TT<T>::st(p, o[0]); else Vec<T>::store(p, o);
   };
-  if (bcast) {
+  for (int r = 0; r < nb; ++r) {
+    const int b = b0 + r;
+    float src[ITER][VEC];
 #pragma unroll
     for (int it = 0; it < ITER; ++it) {
       const int q = it * 256 + threadIdx.x, pl = q / CPP, c = c0 + (q % CPP) * VEC;
-      if (p0 + pl < HW && c < C) ld(h + (p0 + pl) * C + c, src[it]);
-    }
-  }
-  for (int r = 0; r < nb; ++r) {
-    const int b = b0 + r, dir = rows.dir[r];
-    const float sc = rows.scale[r];
-    if (dir < 0 && !(bcast && b > 0)) continue;          // unshifted row that is its own source: nothing to write (uniform over the block)
-    if (dir >= 0) {
-      __syncthreads();                                   // the tile of the row before has been read
-      const float* ub = u + (long)dir * Cv * HW;
-      for (int k = ty; k < SHIFT_TC; k += 8) {
-        const int c = c0 + k;
-        tile[k][tx] = (c < Cv && p0 + tx < HW) ? ub[(long)c * HW + p0 + tx] : 0.f;
-      }
-      __syncthreads();
-    }
-    T* hb = h + (long)b * img;
 #pragma unroll
-    for (int it = 0; it < ITER; ++it) {
-      const int q = it * 256 + threadIdx.x, pl = q / CPP, cl = (q % CPP) * VEC, c = c0 + cl;
-      if (p0 + pl >= HW || c >= C) continue;
-      T* p = hb + (p0 + pl) * C + c;
-      float v[VEC];
-      if (bcast) {
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) v[e] = src[it][e];
-      } else {
-        ld(p, v);
-      }
+      for (int el = 0; el < VEC; ++el) src[it][el] = 0.f;
+      if (p0 + pl < HW && c < C) ld(h + (long)b * img + (p0 + pl) * C + c, src[it]);
+    }
+    for (int g = 0; g < ng; ++g) {
+      const int dir = rows.dir[g * nb + r];
+      const float sc = rows.scale[g * nb + r];
+      if (dir < 0 && g0 + g == 0) continue;                // unshifted row that is its own source: nothing to write (uniform over the block)
       if (dir >= 0) {
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) v[e] += sc * tile[cl + e][pl];
+        __syncthreads();                                   // the tile of the row before has been read
+        const float* ub = u + (long)dir * Cv * HW;
+        for (int k = ty; k < SHIFT_TC; k += 8) {
+          const int c = c0 + k;
+          tile[k][tx] = (c < Cv && p0 + tx < HW) ? ub[(long)c * HW + p0 + tx] : 0.f;
+        }
+        __syncthreads();
       }
-      st(p, v);
+      T* hb = h + ((long)(g0 + g) * xb + b) * img;
+#pragma unroll
+      for (int it = 0; it < ITER; ++it) {
+        const int q = it * 256 + threadIdx.x, pl = q / CPP, cl = (q % CPP) * VEC, c = c0 + cl;
+        if (p0 + pl >= HW || c >= C) continue;
+        float v[VEC];
+#pragma unroll
+        for (int el = 0; el < VEC; ++el) v[el] = src[it][el];
+        if (dir >= 0) {
+#pragma unroll
+          for (int el = 0; el < VEC; ++el) v[el] += sc * tile[cl + el][pl];
+        }
+        st(hb + (p0 + pl) * C + c, v);
+      }
     }
   }
 }
 
 template <typename T>
-static int shift_tap_t(void* h, const float* u, const int* dir, const float* scale, int batch, int bcast, int C, int Cv, long HW, hipStream_t st) {
+static int shift_tap_t(void* h, const float* u, const int* dir, const float* scale, int xb, int groups, int C, int Cv, long HW, hipStream_t st) {
   const dim3 grid((unsigned)((HW + SHIFT_TP - 1) / SHIFT_TP), (unsigned)((C + SHIFT_TC - 1) / SHIFT_TC));
-  // rows travel as kernel arguments, SHIFT_MAX_ROWS per launch; the chunk holding row 0 -- the source of a broadcast -- goes last
-  for (int b0 = (batch - 1) / SHIFT_MAX_ROWS * SHIFT_MAX_ROWS; b0 >= 0; b0 -= SHIFT_MAX_ROWS) {
-    ShiftRows rows;
-    const int nb = std::min(SHIFT_MAX_ROWS, batch - b0);
-    for (int r = 0; r < nb; ++r) { rows.dir[r] = dir[b0 + r]; rows.scale[r] = scale[b0 + r]; }
-    if (C % TT<T>::CH == 0) DPB_LAUNCH((shift_tap_kernel<T, TT<T>::CH>), grid, dim3(256), 0, st, (T*)h, u, rows, b0, nb, bcast, C, Cv, HW);
-    else DPB_LAUNCH((shift_tap_kernel<T, 1>), grid, dim3(256), 0, st, (T*)h, u, rows, b0, nb, bcast, C, Cv, HW);
-    DPB_CHECK(hipGetLastError());
-  }
+  // rows travel as kernel arguments, SHIFT_MAX_ROWS per launch: every group of as many samples as fit, or -- more groups than that -- one sample's
+  // groups in chunks, the chunk holding group 0 (the source of the others) last
+  const int gper = std::min(groups, SHIFT_MAX_ROWS), per = SHIFT_MAX_ROWS / gper;
+  for (int g0 = (groups - 1) / gper * gper; g0 >= 0; g0 -= gper)
+    for (int b0 = 0; b0 < xb; b0 += per) {
+      ShiftRows rows;
+      const int ng = std::min(gper, groups - g0), nb = std::min(per, xb - b0);
+      for (int g = 0; g < ng; ++g)
+        for (int r = 0; r < nb; ++r) { rows.dir[g * nb + r] = dir[(g0 + g) * xb + b0 + r]; rows.scale[g * nb + r] = scale[(g0 + g) * xb + b0 + r]; }
+      if (C % TT<T>::CH == 0) DPB_LAUNCH((shift_tap_kernel<T, TT<T>::CH>), grid, dim3(256), 0, st, (T*)h, u, rows, b0, nb, g0, ng, xb, C, Cv, HW);
+      else DPB_LAUNCH((shift_tap_kernel<T, 1>), grid, dim3(256), 0, st, (T*)h, u, rows, b0, nb, g0, ng, xb, C, Cv, HW);
+      DPB_CHECK(hipGetLastError());
+    }
   return 0;
 }
-int launch_shift_tap(int dtype, void* h, const float* u, const int* dir, const float* scale, int batch, int bcast, int C, int Cv, long HW,
+int launch_shift_tap(int dtype, void* h, const float* u, const int* dir, const float* scale, int xb, int groups, int C, int Cv, long HW,
                      hipStream_t st) {
-  if (batch < 1 || C < 1 || Cv < 1 || Cv > C || HW < 1) { set_error("shift_tap: empty or inconsistent problem"); return -1; }
-  return DPB_DISPATCH_T(dtype, T, shift_tap_t<T>(h, u, dir, scale, batch, bcast, C, Cv, HW, st));
+  if (xb < 1 || groups < 1 || C < 1 || Cv < 1 || Cv > C || HW < 1) { set_error("shift_tap: empty or inconsistent problem"); return -1; }
+  return DPB_DISPATCH_T(dtype, T, shift_tap_t<T>(h, u, dir, scale, xb, groups, C, Cv, HW, st));
 }
 
 // sample 0 of every buffer of a descriptor table -> samples 1 .. batch-1, in place, 16-byte copies (blockIdx.y: the buffer)

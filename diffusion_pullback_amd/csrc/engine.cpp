@@ -148,12 +148,11 @@ struct Forward {
   bool temb_resident = false;       // P(temb_buf) already holds this t's embedding (dpb_local_pca_sample, chunks after the first): no upload, no sync
   int seed = -1;                    // buffer replaced after its producer has run (-1: none), by ...
   const float* h = nullptr;         // ... the caller's activation (dpb_forward_from), or
-  // ... P(seed)[b] <- P(seed)[b or 0] + scale[b] * u[dir[b]] (dpb_forward_shift).  xbatch: samples of x / ctx, i.e. the batch of ops
-  // 0 .. producer[seed]; 1 < batch: the shared prefix, the rest of the tape runs on copies
+  // ... P(seed)[g xbatch + b] <- P(seed)[b] + scale[.] * u[dir[.]] (dpb_forward_shift, dpb_forward_shift_groups): the batch is `groups` copies of
+  // the xbatch samples of x / ctx, row g * xbatch + b is sample b in group g.  xbatch is the batch of ops 0 .. producer[seed]; groups > 1: the
+  // shared prefix, the rest of the tape runs on copies
   const float* u = nullptr; const int32_t* dir = nullptr; const float* scale = nullptr;
-  int xbatch = 0;
-  // dpb_forward_shift_groups: the batch is `groups` copies of the xbatch samples, row g * xbatch + b is sample b in group g (0: dpb_forward_shift)
-  int groups = 0;
+  int xbatch = 0, groups = 0;
 };
 
 // Everything an op function may know about the pass it runs in.  Built on the stack by primal_pass / jvp_pass / vjp_pass.
@@ -1300,23 +1299,18 @@ int dpb_engine_set_workspace(dpb_engine* e, void* ws, size_t bytes) {
   return 0;
 }
 
-// dpb_forward_shift, right after op producer[f.seed]: the `batch` shifted copies of the tap, then (shared prefix, xb == 1 < batch) sample 0 of every
-// buffer the rest of the pass still reads broadcast to the other samples.  That set comes from the tape: the per-sample inputs (op_inputs) of the
-// ops in (producer[f.seed], last] that were written at or before producer[f.seed] or are network inputs (ctx) -- the skips, the net-wide K/V
-// projection of the context.  SHARED buffers (time-embedding path, row biases) have one copy for any batch; the tap itself is written by shift_tap.
-// Nothing else crosses the seam: a primal normalisation op computes its statistics from its own input, it takes none from that input's producer.
-// dpb_forward_shift_groups with 1 < xb < batch: the tap becomes `groups` shifted copies of its xb rows, and the first xb samples of every such buffer
-// are copied as one block to each of the other groups (a buffer is [batch] contiguous samples, so the block of xb samples is one "row" of the copy).
-static int shift_seed(dpb_engine* e, const Forward& f, int batch, int xb, int last) {
-  const int src = f.seed, ps = e->producer[src];
+// The shifted forwards, right after op producer[f.seed]: the tap becomes `groups` shifted copies of its xb rows, then (shared prefix, groups > 1) the
+// first xb samples of every buffer the rest of the pass still reads are copied as one block to each of the other groups (a buffer is [batch]
+// contiguous samples, so the block of xb samples is one "row" of the copy; xb == 1: sample 0 broadcast to the batch).  That set comes from the tape:
+// the per-sample inputs (op_inputs) of the ops in (producer[f.seed], last] that were written at or before producer[f.seed] or are network inputs
+// (ctx) -- the skips, the net-wide K/V projection of the context.  SHARED buffers (time-embedding path, row biases) have one copy for any batch; the
+// tap itself is written by shift_tap.  Nothing else crosses the seam: a primal normalisation op computes its statistics from its own input, it takes
+// none from that input's producer.
+static int shift_seed(dpb_engine* e, const Forward& f, int last) {
+  const int src = f.seed, ps = e->producer[src], xb = f.xbatch;
   const Buf& bs = e->bufs[src];
-  const bool grouped = f.groups > 1 && xb > 1;
-  if (grouped) {
-    if (int r = launch_shift_tap_groups(e->dtype, e->P(src), f.u, f.dir, f.scale, xb, f.groups, bs.C, bs.Cv, bs.rows, e->stream)) return r;
-  } else {
-    if (int r = launch_shift_tap(e->dtype, e->P(src), f.u, f.dir, f.scale, batch, xb < batch, bs.C, bs.Cv, bs.rows, e->stream)) return r;
-  }
-  if (xb == batch) return 0;
+  if (int r = launch_shift_tap(e->dtype, e->P(src), f.u, f.dir, f.scale, xb, f.groups, bs.C, bs.Cv, bs.rows, e->stream)) return r;
+  if (f.groups == 1) return 0;
   std::vector<char> seen(e->bufs.size(), 0);
   std::vector<void*> ptr;
   std::vector<size_t> bytes;
@@ -1325,9 +1319,9 @@ static int shift_seed(dpb_engine* e, const Forward& f, int batch, int xb, int la
       if (b == src || seen[b] || e->bufs[b].kind == DPB_BUF_SHARED || e->producer[b] > ps) continue;
       seen[b] = 1;
       ptr.push_back(e->P(b));
-      bytes.push_back((size_t)e->bufs[b].rows * e->bufs[b].C * e->es * (grouped ? xb : 1));
+      bytes.push_back((size_t)e->bufs[b].rows * e->bufs[b].C * e->es * xb);
     }
-  return launch_replicate_rows(ptr.data(), bytes.data(), (int)ptr.size(), grouped ? f.groups : batch, e->stream);
+  return launch_replicate_rows(ptr.data(), bytes.data(), (int)ptr.size(), f.groups, e->stream);
 }
 
 // the sinusoidal timestep embedding, computed on the host in fp32 exactly as the reference frameworks do (diffusion.py:783-804 / diffusers
@@ -1357,7 +1351,7 @@ static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const 
   ps.fwd = f;
   ps.per_sample_t = tv != nullptr;
   const Buf& bx = e->bufs[e->x_buf];
-  const int xb = f.u ? f.xbatch : batch;           // samples of x / ctx (dpb_forward_shift with a shared prefix: 1)
+  const int xb = f.u ? f.xbatch : batch;           // samples of x / ctx (a shifted forward with a shared prefix: batch / groups)
   if (int r = launch_nchw_to_nhwc(e->dtype, x, e->P(e->x_buf), xb, e->x_channels, bx.rows, bx.C, e->stream)) return r;
   if (e->ctx_buf >= 0) {
     if (!ctx) return fail("this network needs ctx (encoder_hidden_states)");
@@ -1392,8 +1386,8 @@ static int primal_pass(dpb_engine* e, const float* x, int batch, float t, const 
       if (int r = run_op(e, e->ops[i], ps, i <= seed_op ? xb : batch)) return r;
     ps.srow = 0;
     if (int r = fill_affine(e, i, ps, batch)) return r;
-    if (i == seed_op && f.u) {                     // dpb_forward_shift: the tap just computed, shifted per row (of sample 0 for every row when xb == 1)
-      if (int r = shift_seed(e, f, batch, xb, last)) return r;
+    if (i == seed_op && f.u) {                     // a shifted forward: the tap just computed becomes the shifted copies of its xb rows
+      if (int r = shift_seed(e, f, last)) return r;
     } else if (i == seed_op) {                     // dpb_forward_from: the caller's activation replaces the one just computed
       const Buf& bs = e->bufs[f.seed];
       if (int r = launch_nchw_to_nhwc(e->dtype, f.h, e->P(f.seed), batch, bs.Cv, bs.rows, bs.C, e->stream)) return r;
@@ -1474,23 +1468,67 @@ int dpb_forward_shift(dpb_engine* e, const float* x, int xbatch, int batch, floa
     if (dir[b] < -1 || dir[b] >= nu) return fail("dir[%d]=%d outside [-1,%d) (-1: no shift)", b, dir[b], nu);
   if (int r = check_pair(e, src_buf, dst_buf, FOR_FORWARD)) return r;
   Forward f;
-  f.stash = false; f.seed = src_buf; f.u = u; f.dir = dir; f.scale = scale; f.xbatch = xbatch;
+  f.stash = false; f.seed = src_buf; f.u = u; f.dir = dir; f.scale = scale; f.xbatch = xbatch; f.groups = batch / xbatch;
   return forward_pass(e, x, batch, t, ctx, dst_buf, channels, out, f);
 }
 
-// the checks dpb_forward_shift_groups and dpb_hguide_chain share: the shape of the grouped batch and its rows
+// The rows of a call that follows h-space directions: dir[r] in [lo, nu) (lo = -1: a row may go unshifted) and every per-row scalar finite
+struct RowScalars { const char* name; const float* v; };
+static int check_dirs(const char* who, int n, int nu, int lo, const int32_t* dir, std::initializer_list<RowScalars> scalars) {
+  if (nu < 1) return fail("%s: nu=%d: at least one direction is needed", who, nu);
+  for (int r = 0; r < n; ++r) {
+    if (dir[r] < lo || dir[r] >= nu) return fail("%s: dir[%d]=%d outside [%d,%d)%s", who, r, dir[r], lo, nu, lo < 0 ? " (-1: no shift)" : "");
+    for (const RowScalars& s : scalars)
+      if (!isfinite(s.v[r])) return fail("%s: %s[%d] is not finite", who, s.name, r);
+  }
+  return 0;
+}
+
+// the checks of dpb_forward_shift_groups: the shape of the grouped batch and its rows
 static int check_groups(dpb_engine* e, const char* who, int xbatch, int groups, int nu, const int32_t* dir, const float* scale) {
   if (xbatch < 1) return fail("%s: xbatch=%d < 1", who, xbatch);
   if (groups < 1) return fail("%s: groups=%d < 1", who, groups);
   if (groups > SHIFT_MAX_ROWS) return fail("%s: groups=%d above %d", who, groups, SHIFT_MAX_ROWS);
   if ((long)xbatch * groups > e->maxB) return fail("%s: xbatch * groups = %d * %d rows above max_batch=%d", who, xbatch, groups, e->maxB);
-  if (nu < 1) return fail("%s: nu=%d: at least one direction is needed", who, nu);
-  for (int r = 0; r < xbatch * groups; ++r) {
-    if (dir[r] < -1 || dir[r] >= nu) return fail("%s: dir[%d]=%d outside [-1,%d) (-1: no shift)", who, r, dir[r], nu);
-    if (!isfinite(scale[r])) return fail("%s: scale[%d] is not finite", who, r);
-  }
+  return check_dirs(who, xbatch * groups, nu, -1, dir, {{"scale", scale}});
+}
+
+// ---- the frame of the entry points that run several passes over a caller's scratch (dpb_local_pca_sample, dpb_inv_jac_chain, dpb_hguide_chain)
+// the scratch, carved into 256-byte aligned pieces: take() is the offset of the next one, off the total
+struct ScratchLayout {
+  size_t off = 0;
+  size_t take(size_t bytes) { const size_t o = off; off += align_up(bytes); return o; }
+};
+
+static int check_scratch(const char* who, const char* sizer, const void* scratch, size_t bytes, size_t need) {
+  if ((uintptr_t)scratch % 256) return fail("%s: scratch must be 256-byte aligned", who);
+  if (bytes < need) return fail("%s: scratch of %zu bytes, %s = %zu", who, bytes, sizer, need);
   return 0;
 }
+
+// a tap a chain can follow: an activation produced by an op that depends on x
+static int check_chain_tap(const dpb_engine* e, const char* who, int tap) {
+  if (tap < 0 || tap >= (int)e->bufs.size() || e->producer[tap] < 0 || e->bufs[tap].kind != DPB_BUF_ACT)
+    return fail("%s: invalid tap buffer %d (an activation produced by an op)", who, tap);
+  if (e->bufs[tap].is_const) return fail("%s: tap buffer %d does not depend on x", who, tap);
+  return 0;
+}
+
+// The statistics of a call made of several passes: opened before the first (the sub-passes' LaunchSpans overwrite n_launch as they go), add() after each
+// pass that counts flops and bytes, close() when the call ends: its totals, and no primal state is left behind.
+struct CallTotals {
+  dpb_engine* e;
+  const long at = launch_count;
+  double fl = 0, gb = 0;
+  explicit CallTotals(dpb_engine* e_) : e(e_) {}
+  void add() { fl += e->flops; gb += e->gbytes; }
+  int close(int r) {
+    e->cur_batch = 0;
+    e->primal_last = -1;
+    e->n_launch = launch_count - at; e->flops = fl; e->gbytes = gb;
+    return r;
+  }
+};
 
 int dpb_forward_shift_groups(dpb_engine* e, const float* x, int xbatch, int groups, float t, const float* ctx, int src_buf, const float* u, int nu,
                              const int32_t* dir, const float* scale, int dst_buf, int channels, float* out) {
@@ -1839,12 +1877,11 @@ struct LocalPcaScratch { size_t xb = 0, ctxb = 0, part = 0, total = 0; long n_in
 void local_pca_layout(const dpb_engine* e, LocalPcaScratch& l) {
   l.n_in = (long)e->bufs[e->x_buf].rows * e->x_channels;
   l.n_ctx = e->ctx_buf >= 0 ? (long)e->bufs[e->ctx_buf].rows * e->bufs[e->ctx_buf].Cv : 0;
-  size_t off = 0;
-  auto take = [&](size_t b) { const size_t o = off; off += (b + 255) / 256 * 256; return o; };
-  l.xb = take((size_t)e->maxB * l.n_in * sizeof(float));
-  l.ctxb = take((size_t)e->maxB * l.n_ctx * sizeof(float));
-  l.part = take(perturb_scratch_bytes(e->maxB, l.n_in));
-  l.total = off;
+  ScratchLayout s;
+  l.xb = s.take((size_t)e->maxB * l.n_in * sizeof(float));
+  l.ctxb = s.take((size_t)e->maxB * l.n_ctx * sizeof(float));
+  l.part = s.take(perturb_scratch_bytes(e->maxB, l.n_in));
+  l.total = s.off;
 }
 }  // namespace
 
@@ -1864,8 +1901,7 @@ int dpb_local_pca_sample(dpb_engine* e, const float* x, float t, const float* ct
   if (e->ctx_buf >= 0 && !ctx) return fail("this network needs ctx (encoder_hidden_states)");
   LocalPcaScratch l;
   local_pca_layout(e, l);
-  if ((uintptr_t)scratch % 256) return fail("dpb_local_pca_sample: scratch must be 256-byte aligned");
-  if (scratch_bytes < l.total) return fail("dpb_local_pca_sample: scratch of %zu bytes, dpb_local_pca_scratch_bytes = %zu", scratch_bytes, l.total);
+  if (int r = check_scratch("dpb_local_pca_sample", "dpb_local_pca_scratch_bytes", scratch, scratch_bytes, l.total)) return r;
   char* sc = (char*)scratch;
   float* xb = (float*)(sc + l.xb);
   float* cb = e->ctx_buf >= 0 ? (float*)(sc + l.ctxb) : nullptr;
@@ -1905,14 +1941,13 @@ bool chain_layout(const dpb_engine* e, int tap, int n, ChainScratch& l) {
   if (!e || tap < 0 || tap >= (int)e->bufs.size() || n < 1) return false;
   l.n_in = (long)e->bufs[e->x_buf].rows * e->x_channels;
   l.n_h = (long)e->bufs[tap].rows * e->bufs[tap].Cv;
-  size_t off = 0;
-  auto take = [&](size_t b) { const size_t o = off; off += align_up(b); return o; };
-  l.W = take((size_t)n * l.n_in * sizeof(float));
-  l.cot = take((size_t)n * l.n_h * sizeof(float));
-  l.h = take((size_t)n * l.n_h * sizeof(float));
-  l.h0 = take((size_t)n * l.n_h * sizeof(float));
-  l.part = take(direction_step_scratch_bytes(n, l.n_in));
-  l.total = off;
+  ScratchLayout s;
+  l.W = s.take((size_t)n * l.n_in * sizeof(float));
+  l.cot = s.take((size_t)n * l.n_h * sizeof(float));
+  l.h = s.take((size_t)n * l.n_h * sizeof(float));
+  l.h0 = s.take((size_t)n * l.n_h * sizeof(float));
+  l.part = s.take(direction_step_scratch_bytes(n, l.n_in));
+  l.total = s.off;
   return true;
 }
 }  // namespace
@@ -1931,29 +1966,20 @@ int dpb_inv_jac_chain(dpb_engine* e, int tap_buf, const float* x, int n, const f
   const int cap = std::min(e->maxB, e->maxT);
   if (n < 1 || n > cap) return fail("dpb_inv_jac_chain: n=%d chains outside [1,%d] (min of max_batch and max_tangents)", n, cap);
   if (steps < 1) return fail("dpb_inv_jac_chain: steps=%d < 1", steps);
-  if (nu < 1) return fail("dpb_inv_jac_chain: nu=%d: at least one direction is needed", nu);
-  for (int b = 0; b < n; ++b) {
-    if (dir[b] < 0 || dir[b] >= nu) return fail("dpb_inv_jac_chain: dir[%d]=%d outside [0,%d)", b, dir[b], nu);
-    if (!isfinite(sign[b])) return fail("dpb_inv_jac_chain: sign[%d] is not finite", b);
-    if (!isfinite(step[b])) return fail("dpb_inv_jac_chain: step[%d] is not finite", b);
-  }
+  if (int r = check_dirs("dpb_inv_jac_chain", n, nu, 0, dir, {{"sign", sign}, {"step", step}})) return r;
   if (std::isnan(sega_sigma)) return fail("dpb_inv_jac_chain: sega_sigma is NaN");
   const float* tv;
   if (int r = check_timesteps(e, n, t, &tv)) return r;
-  if (tap_buf < 0 || tap_buf >= (int)e->bufs.size() || e->producer[tap_buf] < 0 || e->bufs[tap_buf].kind != DPB_BUF_ACT)
-    return fail("dpb_inv_jac_chain: invalid tap buffer %d (an activation produced by an op)", tap_buf);
-  if (e->bufs[tap_buf].is_const) return fail("dpb_inv_jac_chain: tap buffer %d does not depend on x", tap_buf);
+  if (int r = check_chain_tap(e, "dpb_inv_jac_chain", tap_buf)) return r;
   if (e->ctx_buf >= 0 && !ctx) return fail("this network needs ctx (encoder_hidden_states)");
   ChainScratch l;
   chain_layout(e, tap_buf, n, l);
-  if ((uintptr_t)scratch % 256) return fail("dpb_inv_jac_chain: scratch must be 256-byte aligned");
-  if (scratch_bytes < l.total) return fail("dpb_inv_jac_chain: scratch of %zu bytes, dpb_inv_jac_chain_scratch_bytes = %zu", scratch_bytes, l.total);
+  if (int r = check_scratch("dpb_inv_jac_chain", "dpb_inv_jac_chain_scratch_bytes", scratch, scratch_bytes, l.total)) return r;
   char* sc = (char*)scratch;
   float *Wb = (float*)(sc + l.W), *cot = (float*)(sc + l.cot), *hb = (float*)(sc + l.h), *h0 = (float*)(sc + l.h0);
   const Buf& bt = e->bufs[tap_buf];
   const size_t row = (size_t)n * l.n_in;
-  const long at = launch_count;                     // the sub-passes' LaunchSpans overwrite n_launch as they go: the assignment at the end is what counts
-  double fl = 0, gb = 0;
+  CallTotals tot(e);
   if (states != x) DPB_CHECK(hipMemcpyAsync(states, x, row * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
   // the tap activation of the pass just run, as fp32 NCHW, and its shift statistics against the copy kept from step 0
   auto shift_of = [&](int j) -> int {
@@ -1967,11 +1993,11 @@ int dpb_inv_jac_chain(dpb_engine* e, int tap_buf, const float* x, int n, const f
     Forward f;
     f.temb_resident = j > 0;                        // same timesteps as the step before: their embeddings are still in P(temb_buf), no upload, no sync
     r = primal_pass(e, xj, n, t[0], ctx, tap_buf, f, tv);
-    fl += e->flops; gb += e->gbytes;
+    tot.add();
     if (!r) r = shift_of(j);
     if (!r) r = launch_gather_cotangents(u, nu, dir, sign, n, l.n_h, cot, e->stream);
     if (!r) r = vjp_pass(e, e->x_buf, tap_buf, cot, n, Wb);
-    fl += e->flops; gb += e->gbytes;
+    tot.add();
     if (!r) r = launch_direction_step(Wb, xj, states + (size_t)(j + 1) * row, vk ? vk + (size_t)j * row : nullptr, step, sega_sigma, n, l.n_in,
                                       stats + (size_t)j * n * 4, sc + l.part, l.total - l.part, e->stream);
   }
@@ -1979,15 +2005,12 @@ int dpb_inv_jac_chain(dpb_engine* e, int tap_buf, const float* x, int n, const f
     Forward f;
     f.stash = false; f.temb_resident = true;
     r = primal_pass(e, states + (size_t)steps * row, n, t[0], ctx, tap_buf, f, tv);
-    fl += e->flops; gb += e->gbytes;
+    tot.add();
     if (!r) r = shift_of(steps);
   } else if (!r) {
     DPB_CHECK(hipMemsetAsync(shift + (size_t)steps * n * 2, 0xff, (size_t)n * 2 * sizeof(double), e->stream));   // all bits set: a NaN
   }
-  e->cur_batch = 0;                                // no primal state is left behind
-  e->primal_last = -1;
-  e->n_launch = launch_count - at; e->flops = fl; e->gbytes = gb;
-  return r;
+  return tot.close(r);
 }
 
 // The h-space guidance edit (hguide.hip between the engine's grouped passes): dpb_ddim_step_asym and the device DDIM chain
@@ -2005,12 +2028,11 @@ bool hguide_layout(const dpb_engine* e, int n, int steps, HguideScratch& l) {
   if (!e || n < 1 || steps < 1) return false;
   l.n_in = (long)e->bufs[e->x_buf].rows * e->x_channels;
   l.temb_c = e->temb_buf >= 0 ? e->bufs[e->temb_buf].C : 0;
-  size_t off = 0;
-  auto take = [&](size_t b) { const size_t o = off; off += align_up(b); return o; };
-  l.temb = take((size_t)steps * l.temb_c * sizeof(float));
-  l.eps = take((size_t)2 * n * l.n_in * sizeof(float));
-  l.part = take(ddim_step_asym_scratch_bytes(n, l.n_in));
-  l.total = off;
+  ScratchLayout s;
+  l.temb = s.take((size_t)steps * l.temb_c * sizeof(float));
+  l.eps = s.take((size_t)2 * n * l.n_in * sizeof(float));
+  l.part = s.take(ddim_step_asym_scratch_bytes(n, l.n_in));
+  l.total = s.off;
   return true;
 }
 }  // namespace
@@ -2028,20 +2050,14 @@ int dpb_hguide_chain(dpb_engine* e, int tap_buf, int eps_buf, const float* x, in
   if (!e->ws) return fail("workspace not set (dpb_engine_set_workspace)");
   if (n < 1 || 2 * (long)n > e->maxB) return fail("dpb_hguide_chain: n=%d chains: a plain and a shifted row each, 2n outside [2,%d] (max_batch)", n, e->maxB);
   if (steps < 1) return fail("dpb_hguide_chain: steps=%d < 1", steps);
-  if (nu < 1) return fail("dpb_hguide_chain: nu=%d: at least one direction is needed", nu);
-  for (int b = 0; b < n; ++b) {
-    if (dir[b] < 0 || dir[b] >= nu) return fail("dpb_hguide_chain: dir[%d]=%d outside [0,%d)", b, dir[b], nu);
-    if (!isfinite(scale[b])) return fail("dpb_hguide_chain: scale[%d] is not finite", b);
-  }
+  if (int r = check_dirs("dpb_hguide_chain", n, nu, 0, dir, {{"scale", scale}})) return r;
   if (!isfinite(gP) || !isfinite(gD)) return fail("dpb_hguide_chain: gP=%g, gD=%g: not finite", gP, gD);
   for (int j = 0; j < steps; ++j) {
     if (!isfinite(t[j])) return fail("dpb_hguide_chain: t[%d] is not finite", j);
     if (!(alpha_t[j] > 0.f && alpha_t[j] <= 1.f) || !(alpha_next[j] > 0.f && alpha_next[j] <= 1.f))
       return fail("dpb_hguide_chain: step %d: alpha_t=%g and alpha_next=%g must lie in (0, 1]", j, alpha_t[j], alpha_next[j]);
   }
-  if (tap_buf < 0 || tap_buf >= (int)e->bufs.size() || e->producer[tap_buf] < 0 || e->bufs[tap_buf].kind != DPB_BUF_ACT)
-    return fail("dpb_hguide_chain: invalid tap buffer %d (an activation produced by an op)", tap_buf);
-  if (e->bufs[tap_buf].is_const) return fail("dpb_hguide_chain: tap buffer %d does not depend on x", tap_buf);
+  if (int r = check_chain_tap(e, "dpb_hguide_chain", tap_buf)) return r;
   if (int r = check_pair(e, tap_buf, eps_buf, FOR_FORWARD)) return r;
   const Buf& be = e->bufs[eps_buf];
   if (be.Cv != e->x_channels || be.rows != e->bufs[e->x_buf].rows)
@@ -2050,13 +2066,11 @@ int dpb_hguide_chain(dpb_engine* e, int tap_buf, int eps_buf, const float* x, in
   if (e->ctx_buf >= 0 && !ctx) return fail("this network needs ctx (encoder_hidden_states)");
   HguideScratch l;
   hguide_layout(e, n, steps, l);
-  if ((uintptr_t)scratch % 256) return fail("dpb_hguide_chain: scratch must be 256-byte aligned");
-  if (scratch_bytes < l.total) return fail("dpb_hguide_chain: scratch of %zu bytes, dpb_hguide_chain_scratch_bytes = %zu", scratch_bytes, l.total);
+  if (int r = check_scratch("dpb_hguide_chain", "dpb_hguide_chain_scratch_bytes", scratch, scratch_bytes, l.total)) return r;
   char* sc = (char*)scratch;
   float *temb = (float*)(sc + l.temb), *eps = (float*)(sc + l.eps);
   const size_t row = (size_t)n * l.n_in;
-  const long at = launch_count;                     // the sub-passes' LaunchSpans overwrite n_launch as they go: the assignment at the end is what counts
-  double fl = 0, gb = 0;
+  CallTotals tot(e);
   // rows 0 .. n-1: the plain net; rows n .. 2n-1: the chains' shifts
   std::vector<int32_t> dirs(2 * n, -1);
   std::vector<float> scales(2 * n, 0.f);
@@ -2078,15 +2092,12 @@ int dpb_hguide_chain(dpb_engine* e, int tap_buf, int eps_buf, const float* x, in
     f.stash = false; f.temb_resident = true;       // step j's row was moved into P(temb_buf) on the device just now: no upload, no sync
     f.seed = tap_buf; f.u = u; f.dir = dirs.data(); f.scale = scales.data(); f.xbatch = n; f.groups = 2;
     if (!r) r = primal_pass(e, xj, 2 * n, t[j], ctx, eps_buf, f);
-    fl += e->flops; gb += e->gbytes;
+    tot.add();
     if (!r) r = launch_nhwc_to_nchw(e->dtype, e->P(eps_buf), eps, 2 * n, be.Cv, be.rows, be.C, e->stream);
     if (!r) r = launch_ddim_step_asym(xj, eps, eps + row, states + (size_t)(j + 1) * row, nullptr, n, l.n_in, alpha_t[j], alpha_next[j], gP, gD,
                                       delta + (size_t)j * n * 2, sc + l.part, l.total - l.part, e->stream);
   }
-  e->cur_batch = 0;                                // no primal state is left behind
-  e->primal_last = -1;
-  e->n_launch = launch_count - at; e->flops = fl; e->gbytes = gb;
-  return r;
+  return tot.close(r);
 }
 
 static int g_iter_alias = getenv("DPB_ITER_ALIAS") ? atoi(getenv("DPB_ITER_ALIAS")) : 1;   // A/B switch: 0 = convert U out and back in every iteration

@@ -1,5 +1,6 @@
-// Device pieces shared by the geometry kernels (orth.hip, angles.hip, frechet.hip, flagmean.hip, geodesic.hip, transport.hip, hungarian.hip): the round-robin Jacobi
-// eigen-solve, the fixed-order block sum, the guarded four-column row access, the row-group step of the fp64 MFMA streams and the descending rank order.
+// Device pieces shared by the geometry kernels (orth.hip, angles.hip, frechet.hip, flagmean.hip, geodesic.hip, transport.hip, hungarian.hip) and the chain
+// kernels (chain.hip, hguide.hip): the round-robin Jacobi eigen-solve, the fixed-order block sum, the guarded four-column row access, rows cut into slices
+// with fixed-order fp64 sums, the row-group step of the fp64 MFMA streams and the descending rank order.
 #pragma once
 #include "kernels.h"
 #include "rank.h"      // sorts_before, rank_desc (one total order, NaN first, for every kernel that scatters by rank), max_nan
@@ -155,6 +156,46 @@ __device__ inline void store4(float* row, long n, long N, int vec, float4 v) {
       if (n + 3 < N) row[n + 3] = v.w;
     }
   }
+}
+
+// Rows cut into slices (chain.hip, hguide.hip): a workgroup of ROW_NT threads takes ROW_SLICE elements of a row, thread t the elements of its
+// ROW_GROUPS groups of four in index order; the per-slice fp64 partial sums of a row are then added in slice order.  (noise.hip is NOT one of these:
+// its workgroup sum is an LDS halving tree, not block_sum, and the local-PCA goldens pin its bits.)
+constexpr int ROW_NT = 256;                 // threads per workgroup
+constexpr int ROW_GROUPS = 4;               // groups of four elements per thread and slice
+constexpr int ROW_SLICE = ROW_NT * 4 * ROW_GROUPS;   // elements of a row per workgroup: 4096
+
+__device__ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// load4 / store4 for group j of a row (j % 4 == 0, j < N) that may start anywhere; al: the row pointer is 16-byte aligned
+__device__ inline float4 row_load4(const float* row, long j, long N, bool al) { return load4(row, j, N, al && j + 3 < N); }
+__device__ inline void row_store4(float* row, long j, long N, bool al, float4 v) { store4(row, j, N, al && j + 3 < N, v); }
+
+// tot[v] = the sum over a row's nsl slices of part[s][v], slices in index order: one thread's chain, the same in every workgroup of the row
+template <int NV>
+__device__ inline void sum_slices(const double* part, long nsl, double* tot) {
+  double s[NV] = {};
+  for (long i = 0; i < nsl; ++i)
+#pragma unroll
+    for (int v = 0; v < NV; ++v) s[v] += part[i * NV + v];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) tot[v] = s[v];
+}
+
+inline long row_slices(long N) { return (N + ROW_SLICE - 1) / ROW_SLICE; }
+
+// n rows of N elements fit a launch: the slices of a row and the rows are grid axes
+inline int check_rows(const char* who, long n, long N) {
+  if (n < 1 || n > 0x7fffffffL) { set_error("%s: n=%ld rows outside [1, 2^31)", who, n); return -1; }
+  if (N < 1) { set_error("%s: row length %ld < 1", who, N); return -1; }
+  if (row_slices(N) > 0x7fffffffL) { set_error("%s: row length %ld too large", who, N); return -1; }
+  return 0;
+}
+
+// bytes of the per-slice partial sums of n rows, two fp64 values per slice; 0 when invalid
+inline size_t row_partial_bytes(long n, long N) {
+  if (n < 1 || N < 1) return 0;
+  return (size_t)n * (size_t)row_slices(N) * 2 * sizeof(double);
 }
 
 // One row group of a stream on v_mfma_f64_16x16x4_f64: acc[m][e] += Z[16 m ..][rows r0 .. r0+3] x[rows][column e], Z kept transposed (Zt [rows][k]).

@@ -297,13 +297,15 @@ int launch_zero_cols(int dtype, void* dst, int ldd, int cd0, long rows, int ncol
 // fp32 NCHW [n][C][HW]  <->  T NHWC [n][HW][Cpad]
 int launch_nchw_to_nhwc(int dtype, const float* src, void* dst, int n, int C, int HW, int Cpad, hipStream_t st);
 int launch_nhwc_to_nchw(int dtype, const void* src, float* dst, int n, int C, int HW, int Cpad, hipStream_t st);
-// h-space shift of a tap (dpb_forward_shift): h[b] = h[bcast ? 0 : b] + scale[b] * u[dir[b]] for b < batch, in place.  h: NHWC [batch][HW][C] in
-// the engine dtype (Cv valid channels, the pad channels are copied); u: DEVICE fp32 [nu][Cv][HW] (NCHW-flattened); dir / scale: HOST arrays of
-// `batch` entries (dir[b] in [-1, nu), checked by the caller; -1 = no shift), passed as kernel arguments, SHIFT_MAX_ROWS rows per launch.
-// The sum is formed in fp32 and rounded once; 64-bit offsets; 16-byte accesses on the NHWC side when C is a multiple of the chunk.
+// h-space shift of a tap, the seam of dpb_forward_shift and dpb_forward_shift_groups: h [groups xb][HW][C] holds samples 0 .. xb-1, and
+// h[g xb + b] = h[b] + scale[g xb + b] * u[dir[g xb + b]] in place; (xb, groups) = (1, batch): shifted copies of sample 0, (batch, 1): every row
+// shifted where it is.  h: NHWC in the engine dtype (Cv valid channels, the pad channels are copied); u: DEVICE fp32 [nu][Cv][HW] (NCHW-flattened);
+// dir / scale: HOST arrays of groups * xb entries (dir in [-1, nu), checked by the caller; -1 = no shift: a copy, or nothing for a row of group 0),
+// passed as kernel arguments, SHIFT_MAX_ROWS rows per launch: ceil(xb / floor(SHIFT_MAX_ROWS / groups)) launches, or groups in chunks when there are
+// more of them than that.  The sum is formed in fp32 and rounded once; 64-bit offsets; 16-byte accesses on the NHWC side when C is a multiple of the chunk.
 constexpr int SHIFT_MAX_ROWS = 64;
 struct ShiftRows { int dir[SHIFT_MAX_ROWS]; float scale[SHIFT_MAX_ROWS]; };
-int launch_shift_tap(int dtype, void* h, const float* u, const int* dir, const float* scale, int batch, int bcast, int C, int Cv, long HW,
+int launch_shift_tap(int dtype, void* h, const float* u, const int* dir, const float* scale, int xb, int groups, int C, int Cv, long HW,
                      hipStream_t st);
 // sample 0 of each of `nbufs` buffers (sample_bytes[i] bytes per sample, a multiple of 16; 16-byte aligned) copied to samples 1 .. batch-1 in
 // place: one launch per REPL_MAX_BUFS buffers, the descriptor table in the kernel arguments, 16-byte copies
@@ -511,11 +513,6 @@ int launch_gather_cotangents(const float* u, int nu, const int32_t* dir, const f
 size_t ddim_step_asym_scratch_bytes(long n, long N);     // 0 when invalid
 int launch_ddim_step_asym(const float* x, const float* e, const float* es, float* out, float* x0, long n, long N, float a_t, float a_next, float gP,
                           float gD, double* stats, void* scratch, size_t scratch_bytes, hipStream_t st);
-// the seam of dpb_forward_shift_groups: h [groups xb][HW][C] holds samples 0 .. xb-1; h[g xb + b] = h[b] + scale[g xb + b] * u[dir[g xb + b]] in place
-// (dir / scale: HOST arrays of groups * xb entries, dir in [-1, nu) checked by the caller); the arithmetic and the layouts of launch_shift_tap
-int launch_shift_tap_groups(int dtype, void* h, const float* u, const int* dir, const float* scale, int xb, int groups, int C, int Cv, long HW,
-                            hipStream_t st);
-
 // ---------------------------------------------------------------- DDIM
 // x_next = sqrt(a_next) * (x - e*sqrt(1-a_t))/sqrt(a_t) + sqrt(1-a_next) * e      (fp32, elementwise)
 int launch_ddim_step(const float* x, const float* e, float* out, float* x0, long n, float a_t, float a_next, hipStream_t st);

@@ -101,6 +101,20 @@ class Engine:
         c, h, w = self.tape.tap_shape[self.tape.taps[tap]]
         return c * h * w
 
+    def _directions(self, u: torch.Tensor, tap, empty_ok: bool = False) -> torch.Tensor:
+        """u as fp32 [nu, N_tap] on the device: a whole number of NCHW-flattened directions of `tap` (empty_ok: nu = 0 is left to the library)"""
+        d = self.tap_numel(tap)
+        if (u.numel() == 0 and not empty_ok) or u.numel() % d:
+            raise L.DpbError(f"u has {u.numel()} elements, not a whole number of directions of {d} (tap {tap})")
+        return _f32(u, self.device).reshape(-1, d)
+
+    def _scratch(self, need: int):
+        """a 256-byte aligned pointer to `need` bytes of the engine's one grow-only device scratch; the calls that use it run on the engine's one
+        stream, one after the other"""
+        if getattr(self, "_scratch_buf", None) is None or self._scratch_buf.numel() < need + 256:
+            self._scratch_buf = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
+        return C.c_void_p(self._scratch_buf.data_ptr() + (-self._scratch_buf.data_ptr()) % 256)
+
     def _inputs(self, x: torch.Tensor, ctx: Optional[torch.Tensor]):
         x = _f32(x, self.device)
         b = x.shape[0]
@@ -239,22 +253,26 @@ class Engine:
         (dirs[b] = -1: unshifted).  u [nu, N_src] fp32 directions (NCHW-flattened; a device tensor is used where it lies), dirs / scales: host
         sequences of B entries.  x [B, ...] (ctx [B or 1, L, D]): one forward pass at B; x [1, ...] with B > 1: the shared prefix -- the part of
         the net up to the tap runs once, only the part after it at B.  Like forward(), keeps no primal state."""
-        sbuf, dbuf = self.tape.taps[src], self.tape.taps[dst]
-        c, hh, ww = self.tape.tap_shape[dbuf]
         dirs, scales = [int(d) for d in dirs], [float(s) for s in scales]
         b = len(dirs)
         if len(scales) != b:
             raise L.DpbError(f"dirs has {b} entries, scales {len(scales)}: one of each per output row")
+        return self._shifted(self.lib.dpb_forward_shift, b, lambda xb: b, True, x, t, ctx, src, u, dirs, scales, dst)
+
+    def _shifted(self, call, second, rows, empty_ok, x, t, ctx, src, u, dirs, scales, dst) -> torch.Tensor:
+        """forward_shift and forward_shift_groups behind their own checks: `call` is the entry point, `second` its argument after xbatch (the batch,
+        or the groups), rows(xb) the number of output rows, raising where dirs / scales do not fit it; empty_ok: see _directions"""
+        sbuf, dbuf = self.tape.taps[src], self.tape.taps[dst]
+        c, hh, ww = self.tape.tap_shape[dbuf]
         with torch.cuda.device(self.device):
             self._set_stream()
             x, xb, ctx = self._inputs(x, ctx)
-            if u.numel() % self.tap_numel(src):
-                raise L.DpbError(f"u has {u.numel()} elements, not a whole number of directions of {self.tap_numel(src)} (tap {src})")
-            u = _f32(u, self.device).reshape(-1, self.tap_numel(src))
+            b = rows(xb)
+            u = self._directions(u, src, empty_ok)
             out = torch.empty(max(b, 1), c, hh, ww, dtype=torch.float32, device=self.device)
             self.batch = 0
-            L.check(self.lib.dpb_forward_shift(self.h, _ptr(x), xb, b, float(t), _ptr(ctx), sbuf, _ptr(u), u.shape[0], (C.c_int32 * max(b, 1))(*dirs),
-                                               (C.c_float * max(b, 1))(*scales), dbuf, c, _ptr(out)))
+            L.check(call(self.h, _ptr(x), xb, second, float(t), _ptr(ctx), sbuf, _ptr(u), u.shape[0], (C.c_int32 * max(b, 1))(*dirs),
+                         (C.c_float * max(b, 1))(*scales), dbuf, c, _ptr(out)))
         return out
 
     def jvp_between(self, src, dst, V: torch.Tensor) -> torch.Tensor:
@@ -325,12 +343,9 @@ class Engine:
             elif not (out.is_cuda and out.device == x.device and out.dtype == torch.float32 and out.is_contiguous() and out.numel() == count * d):
                 raise L.DpbError(f"out must be a contiguous fp32 tensor of {count * d} elements on {x.device}")
             need = int(self.lib.dpb_local_pca_scratch_bytes(self.h))
-            if getattr(self, "_lp_scratch", None) is None or self._lp_scratch.numel() < need + 256:
-                self._lp_scratch = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-            off = (-self._lp_scratch.data_ptr()) % 256
             self.batch = 0
             L.check(self.lib.dpb_local_pca_sample(self.h, _ptr(x), float(t), _ptr(ctx), buf, c, _ptr(noise), C.c_uint64(int(seed) & (2 ** 64 - 1)), first,
-                                                  count, _ptr(out), C.c_void_p(self._lp_scratch.data_ptr() + off), need))
+                                                  count, _ptr(out), self._scratch(need), need))
         return out.view(count, d)
 
     # ------------------------------------------------------------------ the parallel-h edit chain on the device
@@ -352,24 +367,17 @@ class Engine:
             dirs, signs, step = [int(d) for d in dirs], [float(s) for s in signs], [float(s) for s in step]
             if not (len(dirs) == len(signs) == len(step) == n):
                 raise L.DpbError(f"dirs, signs and step have {len(dirs)}, {len(signs)} and {len(step)} entries for {n} chains: one of each per chain")
-            d = self.tap_numel(tap)
-            if u.numel() == 0 or u.numel() % d:
-                raise L.DpbError(f"u has {u.numel()} elements, not a whole number of directions of {d} (tap {tap})")
-            u = _f32(u, self.device).reshape(-1, d)
+            u = self._directions(u, tap)
             ns = max(steps, 1)
             states = torch.empty(ns + 1, n, *x.shape[1:], dtype=torch.float32, device=self.device)
             vk = torch.empty(ns, n, self.n_in, dtype=torch.float32, device=self.device) if return_vk else None
             stats = torch.empty(ns, n, 4, dtype=torch.float64, device=self.device)
             shift = torch.empty(ns + 1, n, 2, dtype=torch.float64, device=self.device)
             need = int(self.lib.dpb_inv_jac_chain_scratch_bytes(self.h, buf, n))
-            if getattr(self, "_chain_scratch", None) is None or self._chain_scratch.numel() < need + 256:
-                self._chain_scratch = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-            off = (-self._chain_scratch.data_ptr()) % 256
             self.batch = 0
             L.check(self.lib.dpb_inv_jac_chain(self.h, buf, _ptr(x), n, (C.c_float * n)(*tl), _ptr(ctx), _ptr(u), u.shape[0], (C.c_int32 * n)(*dirs),
                                                (C.c_float * n)(*signs), (C.c_float * n)(*step), steps, float(sega_sigma), int(bool(final_shift)),
-                                               _ptr(states), _ptr(vk), _ptr(stats), _ptr(shift),
-                                               C.c_void_p(self._chain_scratch.data_ptr() + off), need))
+                                               _ptr(states), _ptr(vk), _ptr(stats), _ptr(shift), self._scratch(need), need))
         return states, vk, stats, shift
 
     # ------------------------------------------------------------------ the h-space guidance edit on the device
@@ -379,23 +387,13 @@ class Engine:
         the result is `dst` of sample b with scales[g * xb + b] * u[dirs[g * xb + b]] added at tap `src` (dirs = -1: unshifted); dirs / scales:
         host sequences of xb * groups entries.  The part of the net up to the tap runs once at xb, the part after it at xb * groups.  Like
         forward(), keeps no primal state."""
-        sbuf, dbuf = self.tape.taps[src], self.tape.taps[dst]
-        c, hh, ww = self.tape.tap_shape[dbuf]
         dirs, scales, groups = [int(d) for d in dirs], [float(s) for s in scales], int(groups)
-        with torch.cuda.device(self.device):
-            self._set_stream()
-            x, xb, ctx = self._inputs(x, ctx)
-            b = xb * max(groups, 0)
-            if len(dirs) != b or len(scales) != b:
+
+        def rows(xb):
+            if len(dirs) != xb * max(groups, 0) or len(scales) != xb * max(groups, 0):
                 raise L.DpbError(f"dirs and scales have {len(dirs)} and {len(scales)} entries for {xb} samples x {groups} groups: one of each per row")
-            if u.numel() == 0 or u.numel() % self.tap_numel(src):
-                raise L.DpbError(f"u has {u.numel()} elements, not a whole number of directions of {self.tap_numel(src)} (tap {src})")
-            u = _f32(u, self.device).reshape(-1, self.tap_numel(src))
-            out = torch.empty(max(b, 1), c, hh, ww, dtype=torch.float32, device=self.device)
-            self.batch = 0
-            L.check(self.lib.dpb_forward_shift_groups(self.h, _ptr(x), xb, groups, float(t), _ptr(ctx), sbuf, _ptr(u), u.shape[0],
-                                                      (C.c_int32 * max(b, 1))(*dirs), (C.c_float * max(b, 1))(*scales), dbuf, c, _ptr(out)))
-        return out
+            return xb * max(groups, 0)
+        return self._shifted(self.lib.dpb_forward_shift_groups, groups, rows, False, x, t, ctx, src, u, dirs, scales, dst)
 
     def hguide_chain(self, x: torch.Tensor, t, alpha_t, alpha_next, ctx: Optional[torch.Tensor], tap, u: torch.Tensor, dirs, scales, gP: float = 1.0,
                      gD: float = 0.0):
@@ -415,22 +413,16 @@ class Engine:
             dirs, scales = [int(d) for d in dirs], [float(s) for s in scales]
             if len(dirs) != n or len(scales) != n:
                 raise L.DpbError(f"dirs and scales have {len(dirs)} and {len(scales)} entries for {n} chains: one of each per chain")
-            d = self.tap_numel(tap)
-            if u.numel() == 0 or u.numel() % d:
-                raise L.DpbError(f"u has {u.numel()} elements, not a whole number of directions of {d} (tap {tap})")
-            u = _f32(u, self.device).reshape(-1, d)
+            u = self._directions(u, tap)
             ns = max(steps, 1)
             states = torch.empty(ns + 1, n, *x.shape[1:], dtype=torch.float32, device=self.device)
             delta = torch.empty(ns, n, 2, dtype=torch.float64, device=self.device)
             need = int(self.lib.dpb_hguide_chain_scratch_bytes(self.h, n, ns))
-            if getattr(self, "_hguide_scratch", None) is None or self._hguide_scratch.numel() < need + 256:
-                self._hguide_scratch = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-            off = (-self._hguide_scratch.data_ptr()) % 256
             self.batch = 0
             fa = C.c_float * ns
             L.check(self.lib.dpb_hguide_chain(self.h, buf, ebuf, _ptr(x), n, fa(*tl), fa(*al), fa(*an), _ptr(ctx), _ptr(u), u.shape[0],
                                               (C.c_int32 * n)(*dirs), (C.c_float * n)(*scales), float(gP), float(gD), steps, _ptr(states), _ptr(delta),
-                                              C.c_void_p(self._hguide_scratch.data_ptr() + off), need))
+                                              self._scratch(need), need))
         return states, delta
 
     def profile(self, enable: bool):

@@ -163,6 +163,27 @@ def test_shared_prefix_flops_and_launches(kind):
         assert abs(fl - fE) <= 1e-9 * fE and n == nE + 1, (tap, n, nE, fl, fE)
 
 
+def test_shared_prefix_more_rows_than_one_launch_carries():
+    """xbatch = 1 and 66 rows on the small DDPM net (max_batch = 66): shift_tap carries 64 rows per launch, so the groups go in two chunks, rows
+    64 and 65 first and the chunk with row 0 -- the source of every row -- last.  Rows 0 and 64 are unshifted: row 0 is its own source and is left
+    alone, row 64 is a copy that has to be written.  Rows 0, 63, 64, 65 against the restatement, and one launch more than the 64-row call."""
+    kind, tap, B = "ddpm", ("mid", 0), 66
+    S = _setup(kind)
+    e = _net(kind, max_batch=B).engine
+    x1, t = S["x"][0:1], float(S["t"])
+    dirs = [b % 3 - 1 for b in range(B)]                                 # -1, 0, 1, ...: row 0 unshifted
+    scales = [0.25 * (b % 7 - 3) for b in range(B)]
+    dirs[63], scales[63], dirs[64], dirs[65], scales[65] = 0, 1.5, -1, 1, -2.0
+    e.forward_shift(x1, t, None, tap, S["u"][tap], dirs[:64], scales[:64])
+    n64 = e.stats()[0]
+    out = e.forward_shift(x1, t, None, tap, S["u"][tap], dirs, scales).cpu()
+    n66 = e.stats()[0]
+    errs = {b: rel(out[b:b + 1], _ref(kind, tap, 0, dirs[b], scales[b] if dirs[b] >= 0 else 0.0)) for b in (0, 63, 64, 65)}
+    print(errs, n64, n66)
+    assert out.shape[0] == B and all(v < 2e-4 for v in errs.values()), errs
+    assert n66 == n64 + 1, (n64, n66)
+
+
 # ------------------------------------------------------------------------------------------------ 5. 16-bit engines
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
 @pytest.mark.parametrize("kind", ["sd", "ddpm"])
