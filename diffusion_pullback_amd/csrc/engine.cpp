@@ -2100,6 +2100,115 @@ int dpb_hguide_chain(dpb_engine* e, int tap_buf, int eps_buf, const float* x, in
   return tot.close(r);
 }
 
+// Pullback geodesics between two latents (geodesic_chain.hip between the engine's own passes): the two kernels and the device energy chain
+size_t dpb_geodesic_cotangents_scratch_bytes(int64_t m, int64_t D) { return geodesic_cotangents_scratch_bytes(m, D); }
+
+int dpb_geodesic_cotangents(const float* h, float* cot, double* seg, double* csq, int64_t m, int64_t D, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!h || !cot || !seg || !scratch) return fail("dpb_geodesic_cotangents: null argument");
+  return launch_geodesic_cotangents(h, cot, seg, csq, m, D, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+size_t dpb_geodesic_update_scratch_bytes(int64_t m, int64_t N) { return geodesic_update_scratch_bytes(m, N); }
+
+int dpb_geodesic_update(const float* P, const float* W, float* P_out, float eta, float lambda, int64_t m, int64_t N, double* stats, double* xseg,
+                        void* scratch, size_t scratch_bytes, void* stream) {
+  if (!P || !W || !P_out || !stats || !xseg || !scratch) return fail("dpb_geodesic_update: null argument");
+  return launch_geodesic_update(P, W, P_out, eta, lambda, m, N, stats, xseg, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+namespace {
+struct GeodesicScratch { size_t h = 0, cot = 0, W = 0, x2 = 0, ctx2 = 0, part = 0, total = 0, part_bytes = 0; long n_in = 0, n_h = 0, n_ctx = 0; };
+bool geodesic_layout(const dpb_engine* e, int tap, int m, GeodesicScratch& l) {
+  if (!e || tap < 0 || tap >= (int)e->bufs.size() || m < 1) return false;
+  l.n_in = (long)e->bufs[e->x_buf].rows * e->x_channels;
+  l.n_h = (long)e->bufs[tap].rows * e->bufs[tap].Cv;
+  l.n_ctx = e->ctx_buf >= 0 ? (long)e->bufs[e->ctx_buf].rows * e->bufs[e->ctx_buf].Cv : 0;
+  l.part_bytes = std::max(geodesic_cotangents_scratch_bytes(m, l.n_h), geodesic_update_scratch_bytes(m, l.n_in));
+  ScratchLayout s;
+  l.h = s.take((size_t)(m + 2) * l.n_h * sizeof(float));
+  l.cot = s.take((size_t)m * l.n_h * sizeof(float));
+  l.W = s.take((size_t)m * l.n_in * sizeof(float));
+  l.x2 = s.take((size_t)2 * l.n_in * sizeof(float));
+  l.ctx2 = s.take((size_t)2 * l.n_ctx * sizeof(float));
+  l.part = s.take(l.part_bytes);
+  l.total = s.off;
+  return true;
+}
+}  // namespace
+
+size_t dpb_geodesic_chain_scratch_bytes(const dpb_engine* e, int tap_buf, int m) {
+  GeodesicScratch l;
+  return geodesic_layout(e, tap_buf, m, l) ? l.total : 0;
+}
+
+int dpb_geodesic_chain(dpb_engine* e, int tap_buf, const float* P, int m, float t, const float* ctx, float eta, float lambda, int iters, int final_energy,
+                       float* curves, double* seg_h, double* seg_x, double* stats, double* csq, void* scratch, size_t scratch_bytes) {
+  if (!e || !P || !curves || !seg_h || !seg_x || !stats || !scratch) return fail("dpb_geodesic_chain: null argument");
+  e->cur_batch = 0;                                // as dpb_forward: whatever happens below, the primal state is gone
+  if (!e->ws) return fail("workspace not set (dpb_engine_set_workspace)");
+  if (e->maxB < 2) return fail("dpb_geodesic_chain: max_batch=%d: the two end points run as one batch of 2", e->maxB);
+  const int cap = std::min(e->maxB, e->maxT);
+  if (m < 1 || m > cap) return fail("dpb_geodesic_chain: m=%d interior points outside [1,%d] (min of max_batch and max_tangents)", m, cap);
+  if (iters < 1) return fail("dpb_geodesic_chain: iters=%d < 1", iters);
+  if (!isfinite(t) || !isfinite(eta) || !isfinite(lambda) || lambda < 0.f)
+    return fail("dpb_geodesic_chain: t=%g, eta=%g and lambda=%g must be finite, lambda >= 0", t, eta, lambda);
+  if (int r = check_chain_tap(e, "dpb_geodesic_chain", tap_buf)) return r;
+  if (e->ctx_buf >= 0 && !ctx) return fail("this network needs ctx (encoder_hidden_states)");
+  GeodesicScratch l;
+  geodesic_layout(e, tap_buf, m, l);
+  if (int r = check_scratch("dpb_geodesic_chain", "dpb_geodesic_chain_scratch_bytes", scratch, scratch_bytes, l.total)) return r;
+  char* sc = (char*)scratch;
+  float *hb = (float*)(sc + l.h), *cot = (float*)(sc + l.cot), *Wb = (float*)(sc + l.W), *x2 = (float*)(sc + l.x2), *ctx2 = e->ctx_buf >= 0 ? (float*)(sc + l.ctx2) : nullptr;
+  const float* ctx_in = ctx2 ? ctx + l.n_ctx : nullptr;      // the conditioning of the interior rows
+  const Buf& bt = e->bufs[tap_buf];
+  const size_t row = (size_t)(m + 2) * l.n_in, last = (size_t)(m + 1) * l.n_in;
+  CallTotals tot(e);
+  if (curves != P) DPB_CHECK(hipMemcpyAsync(curves, P, row * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+  // The end points: one pass at batch 2 (it uploads the time embedding: the call's one host synchronisation), their tap activations kept as fp32 NCHW in
+  // rows 0 and m + 1 of the [m + 2][N_h] block for the whole call
+  DPB_CHECK(hipMemcpyAsync(x2, P, (size_t)l.n_in * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+  DPB_CHECK(hipMemcpyAsync(x2 + l.n_in, P + last, (size_t)l.n_in * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+  if (ctx2) {
+    DPB_CHECK(hipMemcpyAsync(ctx2, ctx, (size_t)l.n_ctx * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+    DPB_CHECK(hipMemcpyAsync(ctx2 + l.n_ctx, ctx + (size_t)(m + 1) * l.n_ctx, (size_t)l.n_ctx * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+  }
+  Forward f0;
+  f0.stash = false;
+  int r = primal_pass(e, x2, 2, t, ctx2, tap_buf, f0);
+  tot.add();
+  const size_t sample = (size_t)bt.rows * bt.C * e->es;      // bytes of one sample of the tap buffer
+  if (!r) r = launch_nhwc_to_nchw(e->dtype, e->P(tap_buf), hb, 1, bt.Cv, bt.rows, bt.C, e->stream);
+  if (!r) r = launch_nhwc_to_nchw(e->dtype, e->P(tap_buf) + sample, hb + (size_t)(m + 1) * l.n_h, 1, bt.Cv, bt.rows, bt.C, e->stream);
+  // the tap activations of the interior rows of `curve` into the middle of the block, then the cotangents and the h-segments of row j
+  auto energy_of = [&](const float* curve, int j, bool stash) -> int {
+    Forward f;
+    f.stash = stash; f.temb_resident = true;       // the end-point pass left this t's embedding in P(temb_buf): no upload, no sync
+    int q = primal_pass(e, curve + l.n_in, m, t, ctx_in, tap_buf, f);
+    tot.add();
+    if (!q) q = launch_nhwc_to_nchw(e->dtype, e->P(tap_buf), hb + l.n_h, m, bt.Cv, bt.rows, bt.C, e->stream);
+    if (!q) q = launch_geodesic_cotangents(hb, cot, seg_h + (size_t)j * (m + 1), csq && j < iters ? csq + (size_t)j * m : nullptr, m, l.n_h, sc + l.part,
+                                           l.part_bytes, e->stream);
+    return q;
+  };
+  for (int j = 0; j < iters && !r; ++j) {
+    const float* cj = curves + (size_t)j * row;
+    r = energy_of(cj, j, true);
+    if (!r) r = vjp_pass(e, e->x_buf, tap_buf, cot, m, Wb);
+    tot.add();
+    if (!r) r = launch_geodesic_update(cj, Wb, curves + (size_t)(j + 1) * row, eta, lambda, m, l.n_in, stats + (size_t)j * m * 4,
+                                       seg_x + (size_t)j * (m + 1), sc + l.part, l.part_bytes, e->stream);
+  }
+  if (!r && final_energy) {
+    r = energy_of(curves + (size_t)iters * row, iters, false);
+    // the x-segments of the last curve: the segment sums of the cotangent kernel (cot = null: nothing else), the chain of the update kernel's xseg
+    if (!r) r = launch_geodesic_cotangents(curves + (size_t)iters * row, nullptr, seg_x + (size_t)iters * (m + 1), nullptr, m, l.n_in, sc + l.part, l.part_bytes, e->stream);
+  } else if (!r) {
+    DPB_CHECK(hipMemsetAsync(seg_h + (size_t)iters * (m + 1), 0xff, (size_t)(m + 1) * sizeof(double), e->stream));   // all bits set: a NaN
+    DPB_CHECK(hipMemsetAsync(seg_x + (size_t)iters * (m + 1), 0xff, (size_t)(m + 1) * sizeof(double), e->stream));
+  }
+  return tot.close(r);
+}
+
 static int g_iter_alias = getenv("DPB_ITER_ALIAS") ? atoi(getenv("DPB_ITER_ALIAS")) : 1;   // A/B switch: 0 = convert U out and back in every iteration
 static int g_orth_batch = getenv("DPB_ORTH_BATCH") ? atoi(getenv("DPB_ORTH_BATCH")) : 1;   // A/B switch: 0 = re-orthonormalise the samples of a batch one by one
 static int g_graph_iterate = 0;      // dpb_debug_set("graph_iterate", 1): replay the power iteration as a captured hipGraph (measurement option)

@@ -513,6 +513,15 @@ int launch_gather_cotangents(const float* u, int nu, const int32_t* dir, const f
 size_t ddim_step_asym_scratch_bytes(long n, long N);     // 0 when invalid
 int launch_ddim_step_asym(const float* x, const float* e, const float* es, float* out, float* x0, long n, long N, float a_t, float a_next, float gP,
                           float gD, double* stats, void* scratch, size_t scratch_bytes, hipStream_t st);
+// ---------------------------------------------------------------- pullback geodesics between two latents (geodesic_chain.hip)
+// a curve of m + 2 rows, the end rows fixed.  cotangents: h [m+2][D] -> cot [m][D] = fl32(2 h_i - h_{i-1} - h_{i+1}), seg [m+1] fp64 =
+// ||h_{i+1} - h_i||^2, csq [m] fp64 (optional) = ||cot_i||^2.  update: P_out_i = fl32(P_i - eta (W_i + lambda (2 P_i - P_{i-1} - P_{i+1}))), end rows
+// copied (P_out must not overlap P), stats [m][4] fp64 = (sum W^2, sum g^2, sum (P_out - P)^2, flag), xseg [m+1] fp64 of the OLD curve; see include/dpb.h
+size_t geodesic_cotangents_scratch_bytes(long m, long D);   // 0 when invalid
+int launch_geodesic_cotangents(const float* h, float* cot, double* seg, double* csq, long m, long D, void* scratch, size_t scratch_bytes, hipStream_t st);
+size_t geodesic_update_scratch_bytes(long m, long N);       // 0 when invalid
+int launch_geodesic_update(const float* P, const float* W, float* P_out, float eta, float lambda, long m, long N, double* stats, double* xseg,
+                           void* scratch, size_t scratch_bytes, hipStream_t st);
 // ---------------------------------------------------------------- DDIM
 // x_next = sqrt(a_next) * (x - e*sqrt(1-a_t))/sqrt(a_t) + sqrt(1-a_next) * e      (fp32, elementwise)
 int launch_ddim_step(const float* x, const float* e, float* out, float* x0, long n, float a_t, float a_next, hipStream_t st);

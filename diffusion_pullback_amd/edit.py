@@ -314,6 +314,59 @@ class _EditBase(object):
         save_pga_plots(out["variance"], out["scores"], member_ht, path + "-scree.png", path + "-scores.png", dpi=80)
         return out
 
+    @torch.no_grad()
+    def run_geodesic_interpolation(self, sample_idx_0, sample_idx_1, op, block_idx, h_t=None, n_points=8, lam=0.0, max_iter=200, tol=1e-4,
+                                   check_every=4, max_halvings=8):
+        """The shortest path between two samples under the pullback metric of h = get_h(x, t) at the tap (op, block_idx), beside the two
+        interpolations a user has otherwise (the reference has no such job; its paper's metric is this one).  Both samples go to h_t (None: edit_t)
+        the way the tangent-space job takes its latents there: inversion or a Random latent, then DDIMforwardsteps.  The geodesic of n_points interior
+        points starts from the slerp curve (unet.pullback_geodesic: lam, max_iter, tol, check_every, max_halvings); lerp, slerp and geodesic are then
+        measured alike by unet.curve_energy and decoded together from h_t through DDIMforwardsteps(.., t_end_idx=-1) under the driver's batch bounds.
+        Files: x0_gen-Geodesic-<dataset>_<i>_<j>-<h_t>T-<op>-block_<b>-{lerp|slerp|geodesic}.png in the result folder, one row per curve, and
+        geodesic-Geodesic-<...>.pt in the obs folder: names, seed, h_t, t, the three curves at h_t, their statistics (energy, energy_h, energy_x,
+        length_h, length_x, uniformity, seg_h, seg_x) and the info of pullback_geodesic.  An existing .pt is loaded, not recomputed.  Prints one
+        line per curve; returns the record."""
+        from .pullback import geodesic_init
+        if int(sample_idx_0) == int(sample_idx_1):
+            raise ValueError(f"run_geodesic_interpolation joins two different samples, got sample_idx_0 = sample_idx_1 = {sample_idx_0}")
+        if int(n_points) < 1 or not (0 <= float(lam) < float("inf")):
+            raise ValueError(f"run_geodesic_interpolation: n_points={n_points} must be >= 1 and lam={lam} finite and >= 0")
+        h_t = self.edit_t if h_t is None else h_t
+        name = f"Geodesic-{self.dataset_name}_{sample_idx_0}_{sample_idx_1}-{h_t}T-{op}-block_{block_idx}"
+        self.EXP_NAME = name
+        kinds = ("lerp", "slerp", "geodesic")
+        line = lambda k, s: print(f"{name} {k}: energy {s['energy']:.6e}  h-length {s['length_h']:.6e}  uniformity {s['uniformity']:.6f}")
+        path = os.path.join(self.obs_folder, f"geodesic-{name}.pt")
+        if os.path.exists(path):
+            print("!!!ALREADY DONE!!!")
+            rec = torch.load(path)
+            for k in kinds:
+                line(k, rec["stats"][k])
+            return rec
+        self.scheduler.set_timesteps(self.for_steps, device=self.device)
+        h_t_idx = int((self.scheduler.timesteps - h_t * 1000).abs().argmin())
+        ends, t = [], self.scheduler.timesteps[h_t_idx]
+        for idx in (sample_idx_0, sample_idx_1):
+            xT = self._random_latent(idx) if self.dataset_name == "Random" else self.run_DDIMinversion(idx=idx)
+            ends.append(xT if h_t_idx == 0 else self.DDIMforwardsteps(xT, t_start_idx=0, t_end_idx=h_t_idx)[0])
+        xa, xb = (e.to(device=self.device, dtype=self.dtype) for e in ends)
+        ctx = self._geodesic_ctx()
+        with T.phase("pullback geodesic (device energy chain)"):
+            geo, info = self.unet.pullback_geodesic(xa, xb, t, n_points=int(n_points), op=op, block_idx=block_idx, encoder_hidden_states=ctx,
+                                                    init="slerp", lam=float(lam), max_iter=int(max_iter), tol=float(tol), check_every=int(check_every),
+                                                    max_halvings=int(max_halvings))
+            curves = {"lerp": geodesic_init(xa[0], xb[0], int(n_points), "linear"), "slerp": geodesic_init(xa[0], xb[0], int(n_points), "slerp"),
+                      "geodesic": geo.to(device=self.device, dtype=torch.float32)}
+            stats = {k: self.unet.curve_energy(curves[k], t, op=op, block_idx=block_idx, encoder_hidden_states=ctx, lam=float(lam)) for k in kinds}
+        for k in kinds:
+            line(k, stats[k])
+        self._geodesic_decode(torch.cat([curves[k] for k in kinds]).to(self.dtype), h_t_idx, [f"{name}-{k}" for k in kinds])
+        self.EXP_NAME = name
+        rec = dict(names=[f"{name}-{k}" for k in kinds], seed=self.seed, h_t=float(h_t), t=float(t), op=op, block_idx=block_idx, n_points=int(n_points),
+                   lam=float(lam), sample_idx=(int(sample_idx_0), int(sample_idx_1)), curves={k: curves[k].cpu() for k in kinds}, stats=stats, info=info)
+        torch.save(rec, path)
+        return rec
+
     def _guidance_chains_together(self, z, vk, t, emb=None):
         """n independent chains of x-space guidance (edit.py:484-502, :1716-1734) advanced together: chain i starts at z[i] and moves along vk[i],
         all at the timestep t.  Per step ONE U-Net call of 2 n rows, [z_1..z_n | z_1 + s v_1 .. z_n + s v_n], split only by the engine's batch limit
@@ -537,6 +590,16 @@ class EditStableDiffusion(_EditBase):
             save_image(x0, os.path.join(self.result_folder, f"x0_gen-{exp_name}.png"), nrow=x0.size(0))
         return latents
 
+    # run_geodesic_interpolation: the conditioning of get_h (the prompt the tangent-space job pulls back under) and the decode of the three curves
+    def _geodesic_ctx(self):
+        return self.edit_prompt_emb
+
+    def _geodesic_decode(self, latents, t_idx, names):
+        out = self.DDIMforwardsteps(latents, t_start_idx=t_idx, t_end_idx=-1, finish=False)
+        n = out.size(0) // len(names)
+        for i, name in enumerate(names):
+            self._finish_decode(out[i * n:(i + 1) * n], name)
+
     @torch.no_grad()
     def x_space_guidance(self, zt, t_idx, vk, single_edit_step, use_edit_prompt=False):
         t = self.scheduler.timesteps[t_idx]
@@ -754,6 +817,16 @@ class EditUncondDiffusion(_EditBase):
             xt, t, _ = self.DDIMforwardsteps(xT, t_start_idx=0, t_end_idx=h_t_idx)
             return xt, self.scheduler.timesteps[0] if fix_t else t                              # edit.py:1575-1576
         self._sample_tangent_spaces(pending, make_xt, None, op, block_idx, pca_rank, 1e-4, save_dir, lambda name, s, vT, lat_shape: setattr(self, "EXP_NAME", name))
+
+    # run_geodesic_interpolation: no conditioning, and the decode of the three curves as one batch (the eta = 1 tail of the other jobs' decodes)
+    def _geodesic_ctx(self):
+        return None
+
+    def _geodesic_decode(self, xt, t_idx, names):
+        x0 = self.DDIMforwardsteps(xt, t_start_idx=t_idx, t_end_idx=-1, save_image_=False, performance_boosting=True)
+        n = x0.size(0) // len(names)
+        for i, name in enumerate(names):
+            save_image((x0[i * n:(i + 1) * n] / 2 + 0.5).clamp(0, 1), os.path.join(self.result_folder, f"x0_gen-{name}.png"), nrow=n)
 
     @torch.no_grad()
     def x_space_guidance(self, xt, t_idx, vk, single_edit_step):

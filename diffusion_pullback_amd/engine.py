@@ -425,6 +425,33 @@ class Engine:
                                               self._scratch(need), need))
         return states, delta
 
+    # ------------------------------------------------------------------ pullback geodesics between two latents on the device
+    def geodesic_chain(self, P: torch.Tensor, t: float, ctx: Optional[torch.Tensor], tap, eta: float, lam: float, iters: int,
+                       final_energy: bool = True):
+        """dpb_geodesic_chain: `iters` Jacobi iterations P_i <- P_i - eta (J(P_i)^T (2 h_i - h_{i-1} - h_{i+1}) + lam (2 P_i - P_{i-1} - P_{i+1}))
+        of the m = P.shape[0] - 2 interior points of the curve P [m + 2, C, H, W] with no Python between them; the end rows stay.  One timestep t;
+        ctx [m + 2 or 1, L, D] or None.  Returns device tensors (curves [iters + 1, m + 2, C, H, W] with curves[0] = P, seg_h and seg_x
+        [iters + 1, m + 1] fp64 = ||h_{i+1} - h_i||^2 and ||P_{i+1} - P_i||^2 of every curve (the last row NaN unless final_energy, which takes one
+        more forward pass), stats [iters, m, 4] fp64 = (||J^T c||^2, ||g||^2, ||P_out - P||^2, flag), csq [iters, m] fp64 = ||c_i||^2); one host
+        sync for the call.  Like forward(), keeps no primal state."""
+        buf = self.tape.taps[tap]
+        iters = int(iters)
+        with torch.cuda.device(self.device):
+            self._set_stream()
+            P, n, ctx = self._inputs(P, ctx)
+            m = n - 2
+            ni, nm = max(iters, 1), max(m, 1)
+            curves = torch.empty(ni + 1, nm + 2, *P.shape[1:], dtype=torch.float32, device=self.device)
+            seg_h = torch.empty(ni + 1, nm + 1, dtype=torch.float64, device=self.device)
+            seg_x = torch.empty(ni + 1, nm + 1, dtype=torch.float64, device=self.device)
+            stats = torch.empty(ni, nm, 4, dtype=torch.float64, device=self.device)
+            csq = torch.empty(ni, nm, dtype=torch.float64, device=self.device)
+            need = int(self.lib.dpb_geodesic_chain_scratch_bytes(self.h, buf, m))
+            self.batch = 0
+            L.check(self.lib.dpb_geodesic_chain(self.h, buf, _ptr(P), m, float(t), _ptr(ctx), float(eta), float(lam), iters, int(bool(final_energy)),
+                                                _ptr(curves), _ptr(seg_h), _ptr(seg_x), _ptr(stats), _ptr(csq), self._scratch(need), need))
+        return curves, seg_h, seg_x, stats, csq
+
     def profile(self, enable: bool):
         L.check(self.lib.dpb_engine_profile(self.h, int(enable)))
 
@@ -545,6 +572,65 @@ def shift_stats(h: torch.Tensor, h0: torch.Tensor, u: torch.Tensor, dirs, signs)
         L.check(lib.dpb_shift_stats(_ptr(h), _ptr(h0), _ptr(u), u.shape[0], (C.c_int32 * max(n, 1))(*dirs), (C.c_float * max(n, 1))(*signs), n, D,
                                     _ptr(out), C.c_void_p(st)))
     return out
+
+
+def _curve_rows(name: str, a: torch.Tensor, rows: Optional[int] = None, device=None) -> None:
+    if not (a.is_cuda and a.dim() == 2 and a.dtype == torch.float32 and a.is_contiguous()):
+        raise L.DpbError(f"{name} must be a contiguous fp32 2-D tensor on a HIP device")
+    if rows is not None and (a.shape[0] != rows or a.device != device):
+        raise L.DpbError(f"{name} has {a.shape[0]} rows on {a.device}, expected {rows} on {device}")
+
+
+def geodesic_cotangents(h: torch.Tensor, cot: Optional[torch.Tensor] = None, return_csq: bool = True):
+    """dpb_geodesic_cotangents (engine-independent): h [m + 2, D] fp32 on a HIP device, the tap activations along a curve.  Returns (cot [m, D] fp32 =
+    2 h_i - h_{i-1} - h_{i+1} formed in fp64 and rounded once, seg [m + 1] fp64 = ||h_{i+1} - h_i||^2, csq [m] fp64 = ||cot_i||^2 or None).  cot: the
+    tensor written into, allocated here when None.  No host sync (include/dpb.h states the arithmetic)."""
+    lib = L.load()
+    _curve_rows("h", h)
+    n, D = h.shape
+    m = n - 2
+    with torch.cuda.device(h.device):
+        st = torch.cuda.current_stream(h.device).cuda_stream
+        if cot is None:
+            cot = torch.empty(max(m, 1), D, dtype=torch.float32, device=h.device)
+        else:
+            _curve_rows("cot", cot, max(m, 1), h.device)
+        seg = torch.empty(max(m, 1) + 1, dtype=torch.float64, device=h.device)
+        csq = torch.empty(max(m, 1), dtype=torch.float64, device=h.device) if return_csq else None
+        need = int(lib.dpb_geodesic_cotangents_scratch_bytes(m, D))
+        scratch = torch.empty(max(need // 8, 1), dtype=torch.float64, device=h.device)
+        L.check(lib.dpb_geodesic_cotangents(_ptr(h), _ptr(cot), _ptr(seg), _ptr(csq), m, D, _ptr(scratch), need, C.c_void_p(st)))
+    return cot, seg, csq
+
+
+def geodesic_update(P: torch.Tensor, W: torch.Tensor, eta: float, lam: float = 0.0, out: Optional[torch.Tensor] = None):
+    """dpb_geodesic_update (engine-independent): P [m + 2, N] (a curve) and W [m, N] (the adjoint results J^T c of its interior rows), fp32 on a HIP
+    device.  Returns (P_out [m + 2, N] with P_out_i = P_i - eta (W_i + lam (2 P_i - P_{i-1} - P_{i+1})) for the interior rows and the end rows
+    copied, stats [m, 4] fp64 = (||W_i||^2, ||g_i||^2, ||P_out_i - P_i||^2, flag), xseg [m + 1] fp64 = ||P_{i+1} - P_i||^2 of P).  out: the tensor
+    written into -- it must not overlap P -- allocated here when None.  A row that meets a non-finite value has its flag set and NaN in its row of
+    P_out.  No host sync."""
+    lib = L.load()
+    _curve_rows("P", P)
+    n, N = P.shape
+    m = n - 2
+    _curve_rows("W", W, max(m, 1), P.device)
+    if W.shape[1] != N:
+        raise L.DpbError(f"W {tuple(W.shape)} and P {tuple(P.shape)} do not agree: [m, N] and [m + 2, N]")
+    with torch.cuda.device(P.device):
+        st = torch.cuda.current_stream(P.device).cuda_stream
+        if out is None:
+            out = torch.empty_like(P)
+        else:
+            _curve_rows("out", out, n, P.device)
+            if out.shape[1] != N:
+                raise L.DpbError(f"out {tuple(out.shape)} and P {tuple(P.shape)} do not agree")
+        stats = torch.empty(max(m, 1), 4, dtype=torch.float64, device=P.device)
+        xseg = torch.empty(max(m, 1) + 1, dtype=torch.float64, device=P.device)
+        need = int(lib.dpb_geodesic_update_scratch_bytes(m, N))
+        scratch = torch.empty(max(need // 8, 1), dtype=torch.float64, device=P.device)
+        L.check(lib.dpb_geodesic_update(_ptr(P), _ptr(W), _ptr(out), float(eta), float(lam), m, N, _ptr(stats), _ptr(xseg), _ptr(scratch), need,
+                                        C.c_void_p(st)))
+    return out, stats, xseg
 
 
 def ddim_step_asym(x: torch.Tensor, e: torch.Tensor, e_s: torch.Tensor, alpha_t: float, alpha_next: float, gP: float = 1.0, gD: float = 0.0,

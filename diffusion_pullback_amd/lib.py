@@ -165,6 +165,13 @@ SYMBOLS = {
     "dpb_hguide_chain_scratch_bytes": (C.c_size_t, [_P, _I, _I]),
     "dpb_hguide_chain": (_I, [_P, _I, _I, _P, _I, C.POINTER(_F), C.POINTER(_F), C.POINTER(_F), _P, _P, _I, C.POINTER(C.c_int32), C.POINTER(_F), _F, _F,
                               _I, _P, _P, _P, C.c_size_t]),
+    # pullback geodesics between two latents (PullbackUNet.pullback_geodesic / curve_energy): eta, lambda and t are host scalars
+    "dpb_geodesic_cotangents_scratch_bytes": (C.c_size_t, [_L, _L]),
+    "dpb_geodesic_cotangents": (_I, [_P, _P, _P, _P, _L, _L, _P, C.c_size_t, _P]),
+    "dpb_geodesic_update_scratch_bytes": (C.c_size_t, [_L, _L]),
+    "dpb_geodesic_update": (_I, [_P, _P, _P, _F, _F, _L, _L, _P, _P, _P, C.c_size_t, _P]),
+    "dpb_geodesic_chain_scratch_bytes": (C.c_size_t, [_P, _I, _I]),
+    "dpb_geodesic_chain": (_I, [_P, _I, _P, _I, _F, _P, _F, _F, _I, _I, _P, _P, _P, _P, _P, _P, C.c_size_t]),
 }
 
 _lib = None

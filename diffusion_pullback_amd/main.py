@@ -63,6 +63,10 @@ shift enters the predicted x0 only, Kwon et al.'s asymmetric process) or symmetr
 device (PullbackUNet.h_space_guidance), then the plain decode from no_edit_t into the same picture names; --local_projection False is allowed as for
 parallel-h.  Every experiment leaves hguide-<name>.pt in the obs folder: ||e_s - e|| and the distance from the plain step per chain and step, the
 scales, the timesteps and the latents at no_edit_t.  The reference calls a h_space_guidance method it never defines; DESIGN.md states what is built.
+``--run_geodesic_interpolation True --sample_idx_0 i --sample_idx_1 j --geodesic_points m --geodesic_lambda l --geodesic_max_iter n --geodesic_tol tol``
+(both drivers; with --h_t --op --block_idx) joins the latents of two samples at h_t by the shortest path under the pullback metric of get_h
+(PullbackUNet.pullback_geodesic, m interior points, started from slerp), measures lerp, slerp and the geodesic alike (energy, h-length, uniformity) and
+decodes the three curves: x0_gen-Geodesic-<dataset>_<i>_<j>-<h_t>T-<op>-block_<b>-{lerp|slerp|geodesic}.png and geodesic-Geodesic-<...>.pt.
 """
 from __future__ import annotations
 
@@ -137,6 +141,9 @@ _FLAGS = [  # (name, type, default) -- define_argparser.py:20-110, live path onl
     # is added at the tap at every DDIM step from edit_t down to no_edit_t (edit.py:1232-1245), with scales up to h_edit_step_size; h_guidance_mode
     # is new: asyrp (the shift enters the predicted x0 only) or symmetric (the plain DDIM step of the shifted net)
     ("edit_ht", str, "default"), ("h_edit_step_size", float, 0), ("no_edit_t", float, 0.5), ("h_guidance_mode", str, "asyrp"),
+    # new: the pullback geodesic between the latents of --sample_idx_0 and --sample_idx_1 at --h_t (PullbackUNet.pullback_geodesic), against lerp and slerp
+    ("run_geodesic_interpolation", str2bool, False), ("geodesic_points", int, 8), ("geodesic_lambda", float, 0.0), ("geodesic_max_iter", int, 200),
+    ("geodesic_tol", float, 1e-4),
     # new
     ("pca_rank", int, 2), ("op", str, "mid"), ("block_idx", int, 0), ("vis_num", int, 4), ("vis_num_pc", int, 2), ("weights", str, ""),
     ("net_scale", str, "full"), ("vae", str, "none"), ("text_encoder", str, "none"), ("tokenizer_dir", str, ""),
@@ -251,6 +258,15 @@ def parse_args(argv=None):
             p.error("--pga_base must be frechet (the Karcher mean) or flag (the flag mean)")
         if pairs < 2 or not 0 <= args.pga_modes <= min(64, pairs - 1):
             p.error(f"--pga_modes must lie in [1, {min(64, pairs - 1)}] (0: the default), one less than the (basis, h_t) pairs of --num_local_basis and --h_t_list")
+    if args.run_geodesic_interpolation:
+        if args.geodesic_points < 1:
+            p.error("--geodesic_points must be >= 1: the points of the curve between its two ends")
+        if not (0 <= args.geodesic_lambda < float("inf")):
+            p.error("--geodesic_lambda must be finite and >= 0 (0: the pullback energy alone)")
+        if args.geodesic_max_iter < 1 or not (0 <= args.geodesic_tol < float("inf")):
+            p.error("--geodesic_max_iter must be >= 1 and --geodesic_tol finite and >= 0")
+        if args.sample_idx_0 == args.sample_idx_1:
+            p.error("--run_geodesic_interpolation joins two different samples: --sample_idx_0 and --sample_idx_1 are equal")
     if extra:
         print(f"note: ignoring flags of experiments outside the pullback path: {extra}")
     return args
@@ -358,6 +374,9 @@ def build_unet(args) -> PullbackUNet:
                 max_rank = max(max_rank, min(args.trajectory_batch, n))
             if getattr(args, "edit_ht", "default") == "h_space_guidance":   # vis_num chains per experiment, a plain and a shifted row each per call
                 max_batch = max(max_batch, min(args.trajectory_batch, 2 * n * args.vis_num))
+    if getattr(args, "run_geodesic_interpolation", False):                     # the curve is one batch: its two ends and a cotangent per interior point
+        max_batch = max(max_batch, args.geodesic_points + 2)
+        max_rank = max(max_rank, args.geodesic_points)
     if args.is_stable_diffusion:
         cfg = cf.sd_config_for(args.model_name)           # SD-v1.x or SD-2(.1)-base; anything else raises
         if small:
@@ -480,6 +499,10 @@ def main(argv=None):
                                          sample_idx_1=args.sample_idx_1_values if args.sample_idx_1_list else args.sample_idx_1, op=args.op,
                                          block_idx=args.block_idx, vis_num=args.vis_num, vis_num_pc=args.vis_num_pc, pca_rank=args.pca_rank,
                                          h_t=args.h_t)
+    if args.run_geodesic_interpolation:                                          # (not in the reference: the shortest path under its paper's metric)
+        edit.run_geodesic_interpolation(sample_idx_0=args.sample_idx_0, sample_idx_1=args.sample_idx_1, op=args.op, block_idx=args.block_idx,
+                                        h_t=args.h_t, n_points=args.geodesic_points, lam=args.geodesic_lambda, max_iter=args.geodesic_max_iter,
+                                        tol=args.geodesic_tol)
     if args.run_edit_global_frechet_mean_zt:                                     # (the reference's main.py never calls it; its method's own defaults otherwise)
         edit.run_edit_global_frechet_mean_zt(idx=args.sample_idx, op=args.op, block_idx=args.block_idx, vis_num=args.vis_num, vis_num_pc=args.vis_num_pc,
                                              pca_rank=args.pca_rank, num_local_basis=args.num_local_basis, local_projection=args.local_projection,

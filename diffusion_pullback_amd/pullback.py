@@ -757,6 +757,199 @@ class PullbackUNet:
                 raise ValueError(f"h_space_guidance: chain {b} holds a non-finite value at step {j}; check=False returns the NaN states")
         return out
 
+    # ------------------------------------------------------------------ pullback geodesics between two latents
+    def _curve_args(self, what, curve, t, op, block_idx, encoder_hidden_states, lam):
+        """the checks pullback_geodesic and curve_energy share, made before anything runs: (tap key, m, t, ctx, lam)"""
+        key = self._tap(op, block_idx)
+        eng = self.engine
+        if curve is None or curve.dim() != 4 or tuple(curve.shape[1:]) != tuple(self.in_shape):
+            raise ValueError(f"{what}: the curve must be [m + 2, {', '.join(str(a) for a in self.in_shape)}]")
+        m = curve.shape[0] - 2
+        if m < 1:
+            raise ValueError(f"{what}: n_points={m} < 1: a curve has two end points and at least one point between them")
+        if m + 2 > eng.max_batch:
+            raise ValueError(f"{what}: a curve of {m + 2} points is longer than the engine's max_batch={eng.max_batch}: its points are coupled and "
+                             "run as one batch (a longer curve is not split)")
+        if m > eng.max_tangents:
+            raise ValueError(f"{what}: n_points={m} above the engine's max_rank={eng.max_tangents}: the adjoint pass carries one cotangent per point")
+        lam = float(lam)
+        if not math.isfinite(lam) or lam < 0:
+            raise ValueError(f"{what}: lam={lam} must be finite and >= 0")
+        ctx = encoder_hidden_states
+        if ctx is not None and ctx.shape[0] not in (1, m + 2):
+            raise ValueError(f"{what}: encoder_hidden_states has {ctx.shape[0]} rows for a curve of {m + 2} points: one, or one per point")
+        if ctx is not None and ctx.shape[0] == 1:
+            ctx = ctx.expand(m + 2, *ctx.shape[1:])
+        return key, m, _t_shared(t, m + 2, what), ctx, lam
+
+    def curve_energy(self, curve=None, t=None, op=None, block_idx=None, encoder_hidden_states=None, lam=0.0):
+        """The ruler of pullback_geodesic, without optimisation: curve [m + 2, C, H, W] at ONE timestep t -> a dict with seg_h, seg_x [m + 1] fp64
+        (||h_{i+1} - h_i||^2 at the tap (op, block_idx) and ||P_{i+1} - P_i||^2), energy_h = 1/2 sum seg_h, energy_x = 1/2 sum seg_x, energy =
+        energy_h + lam energy_x, length_h = sum sqrt(seg_h), length_x, and uniformity = length_h^2 / ((m + 1) sum seg_h) (1 when the h-segments are
+        equal: a discrete geodesic has constant speed).  No chain: get_h of the two end points as one batch and of the m interior points as another
+        -- the two batches dpb_geodesic_chain runs, so the figures of a chain's last row are these bit for bit -- then dpb_geodesic_cotangents on
+        the activations and on the curve itself.  Lets lerp, slerp and the geodesic be measured alike.  A curve longer than max_batch is refused."""
+        from .engine import geodesic_cotangents
+        key, m, t, ctx, lam = self._curve_args("curve_energy", curve, t, op, block_idx, encoder_hidden_states, lam)
+        eng = self.engine
+        P = curve.detach().to(device=self.device, dtype=torch.float32).contiguous()
+        ends = torch.stack([P[0], P[m + 1]])
+        h = torch.empty(m + 2, eng.tap_numel(key), dtype=torch.float32, device=self.device)
+        he = eng.forward(ends, t, None if ctx is None else torch.stack([ctx[0], ctx[m + 1]]), key).flatten(1)
+        h[0], h[m + 1] = he[0], he[1]
+        eng.forward(P[1:m + 1], t, None if ctx is None else ctx[1:m + 1], key, out=h[1:m + 1])
+        seg_h = geodesic_cotangents(h, return_csq=False)[1]
+        seg_x = geodesic_cotangents(P.flatten(1), return_csq=False)[1]
+        return _curve_stats(seg_h.cpu(), seg_x.cpu(), lam)
+
+    def pullback_geodesic(self, x_a=None, x_b=None, t=None, n_points=8, op=None, block_idx=None, encoder_hidden_states=None, init="slerp", lam=0.0,
+                          step_size=None, max_iter=200, tol=1e-4, check_every=4, max_halvings=8, check=True):
+        """The shortest path from x_a to x_b [1, C, H, W] or [C, H, W] at ONE timestep t under the pullback metric G = J^T J of h = get_h(x, t) at
+        the tap (op, block_idx), as a discrete curve of m = n_points interior points between the fixed ends: gradient descent on
+            E = 1/2 sum_i ||h_{i+1} - h_i||^2 + 1/2 lam sum_i ||P_{i+1} - P_i||^2,    g_i = J(P_i)^T (2 h_i - h_{i-1} - h_{i+1}) + lam (2 P_i - P_{i-1} - P_{i+1}),
+        by Jacobi steps P_i <- P_i - eta g_i on the device (dpb_geodesic_chain: per iteration one primal and one adjoint pass of the m points, no
+        Python between the iterations of a block).  lam = 0 (default) is well posed: g_i lies in the row space of J, what J does not see of the
+        start curve is kept.  init: "slerp", "linear", or a tensor [m + 2, C, H, W] whose end rows equal x_a and x_b.  encoder_hidden_states (SD):
+        one row for the whole curve, or m + 2.
+        The driver (host): blocks of check_every iterations at one eta, each read back once.  A block whose end energy is not finite or above its
+        start energy is discarded and eta <- eta / 2 -- after max_halvings such halvings in a row the descent stops, converged=False; an accepted
+        block ends the descent with converged=True when E_start - E_end <= tol E_start.  max_iter bounds the iterations run, discarded ones
+        included.  step_size=None: eta_0 = 1/4 sum_i ||c_i||^2 / sum_i ||g_i||^2 from a one-iteration probe block with eta = 0 (the csq output of
+        dpb_geodesic_cotangents and the ||g||^2 of dpb_geodesic_update).
+        Returns (curve [m + 2, C, H, W] on x_a.device, info): info holds energy (a list: E at every accepted block boundary, the start included),
+        energy_h, energy_x, length_h, length_x, uniformity, seg_h, seg_x (the final curve's, as curve_energy gives them), grad_norm [m] (||g_i|| at
+        the last iteration taken), step_size (the final eta), iterations (accepted), attempted (all), halvings, decisions (a bool per block),
+        converged, monotone (the energies of `energy` never rise: what the block rule guarantees), rises (the iterations INSIDE accepted blocks at
+        which E rose -- a Jacobi chain at one eta may rise and come back within a block; check_every=1 sees every one) and start = {energy, length_h,
+        uniformity} of the initial curve.
+        A point that meets a non-finite value at the first iteration of a block (the curve itself, or its adjoint): ValueError names the point and
+        the iteration; check=False returns the curve after that iteration, with NaN in the rows it reached -- the point's own and its two
+        neighbours', whose cotangents read its activation -- and every other row as the clean step leaves it.  A curve longer than max_batch is
+        refused."""
+        if x_a is None or x_b is None:
+            raise ValueError("pullback_geodesic: x_a and x_b are needed")
+        shape = tuple(self.in_shape)
+        xa, xb = (x.detach().unsqueeze(0) if x.dim() == 3 else x.detach() for x in (x_a, x_b))
+        if tuple(xa.shape) != (1, *shape) or tuple(xb.shape) != (1, *shape):
+            raise ValueError(f"pullback_geodesic: x_a and x_b must be one sample of shape {shape} each, got {tuple(x_a.shape)} and {tuple(x_b.shape)}")
+        m, max_iter, check_every, max_halvings = int(n_points), int(max_iter), int(check_every), int(max_halvings)
+        if m < 1:
+            raise ValueError(f"pullback_geodesic: n_points={m} < 1")
+        if max_iter < 1 or check_every < 1 or max_halvings < 0:
+            raise ValueError(f"pullback_geodesic: max_iter={max_iter} and check_every={check_every} must be >= 1, max_halvings={max_halvings} >= 0")
+        tol = float(tol)
+        if not math.isfinite(tol) or tol < 0:
+            raise ValueError(f"pullback_geodesic: tol={tol} must be finite and >= 0")
+        if step_size is not None and not (math.isfinite(float(step_size)) and float(step_size) > 0):
+            raise ValueError(f"pullback_geodesic: step_size={step_size} must be finite and > 0 (None: the step rule)")
+        P0 = geodesic_init(xa[0], xb[0], m, init)
+        key, m, t, ctx, lam = self._curve_args("pullback_geodesic", P0, t, op, block_idx, encoder_hidden_states, lam)
+        eng = self.engine
+
+        def block(P, eta, iters, final=True):
+            curves, seg_h, seg_x, stats, csq = eng.geodesic_chain(P, t, ctx, key, eta, lam, iters, final)
+            return curves, seg_h.cpu(), seg_x.cpu(), stats.cpu(), csq.cpu()
+        curve, info = geodesic_descent(block, P0.to(self.device), lam, None if step_size is None else float(step_size), max_iter, tol, check_every,
+                                       max_halvings, check)
+        return curve.to(device=x_a.device, dtype=x_a.dtype), info
+
+
+def geodesic_init(xa: torch.Tensor, xb: torch.Tensor, m: int, init="slerp") -> torch.Tensor:
+    """the start curve [m + 2, C, H, W] fp32 between xa and xb [C, H, W]: "linear" x_a + s (x_b - x_a), "slerp" sin((1 - s) w) / sin w x_a + sin(s w)
+    / sin w x_b with w the angle between the two (linear when sin w < 1e-6), s = i / (m + 1), formed in float64; or a tensor of that shape whose end
+    rows equal xa and xb.  The end rows are xa and xb themselves, bit for bit."""
+    a, b = xa.detach().to(torch.float32), xb.detach().to(torch.float32)
+    if torch.is_tensor(init):
+        P = init.detach().to(device=a.device, dtype=torch.float32)
+        if tuple(P.shape) != (m + 2, *a.shape):
+            raise ValueError(f"pullback_geodesic: init has shape {tuple(P.shape)}, expected {(m + 2, *a.shape)} (n_points + 2 rows)")
+        if not (torch.equal(P[0], a) and torch.equal(P[-1], b)):
+            raise ValueError("pullback_geodesic: the end rows of init must equal x_a and x_b")
+        return P.contiguous()
+    if init not in ("slerp", "linear"):
+        raise ValueError(f"pullback_geodesic: init {init!r}: 'slerp', 'linear' or a tensor [n_points + 2, C, H, W]")
+    a64, b64 = a.double().cpu(), b.double().cpu()
+    s = (torch.arange(m + 2, dtype=torch.float64) / (m + 1)).view(-1, *([1] * a.dim()))
+    wa, wb = 1 - s, s
+    if init == "slerp":
+        c = float((a64 * b64).sum() / (a64.norm() * b64.norm()).clamp_min(1e-300))
+        w = math.acos(max(-1.0, min(1.0, c)))
+        if math.sin(w) >= 1e-6:
+            wa, wb = torch.sin((1 - s) * w) / math.sin(w), torch.sin(s * w) / math.sin(w)
+    P = (wa * a64 + wb * b64).to(torch.float32).to(a.device)
+    P[0], P[-1] = a, b
+    return P.contiguous()
+
+
+def _curve_stats(seg_h: torch.Tensor, seg_x: torch.Tensor, lam: float) -> dict:
+    """the statistics of one curve from its segment sums (fp64, on the host)"""
+    seg_h, seg_x = seg_h.double(), seg_x.double()
+    eh, ex = 0.5 * float(seg_h.sum()), 0.5 * float(seg_x.sum())
+    lh = float(seg_h.sqrt().sum())
+    return {"energy": eh + lam * ex, "energy_h": eh, "energy_x": ex, "length_h": lh, "length_x": float(seg_x.sqrt().sum()),
+            "uniformity": lh * lh / (seg_h.numel() * float(seg_h.sum())) if float(seg_h.sum()) > 0 else float("nan"), "seg_h": seg_h, "seg_x": seg_x}
+
+
+def geodesic_descent(block, P0, lam, step_size, max_iter, tol, check_every, max_halvings, check=True):
+    """The host driver of pullback_geodesic.  block(P, eta, iters, final) -> (curves [iters + 1, m + 2, ...] on the device, and on the host seg_h,
+    seg_x [iters + 1, m + 1], stats [iters, m, 4], csq [iters, m]) is one dpb_geodesic_chain call.  Returns (curve, info); the rules are those of
+    PullbackUNet.pullback_geodesic."""
+    E = lambda sh, sx: 0.5 * float(sh.double().sum()) + lam * 0.5 * float(sx.double().sum())
+
+    def flagged(stats, j):
+        bad = (stats[j, :, 3] != 0).nonzero()
+        return None if bad.numel() == 0 else int(bad[0]) + 1
+
+    curve, attempted, row, energy, last = P0, 0, 0, [], None       # last: (seg_h, seg_x, stats row) of the curve held
+    info = {"halvings": 0, "decisions": [], "converged": False, "rises": 0, "iterations": 0}
+    if step_size is None:                            # the probe: one iteration at eta = 0 moves nothing and yields ||c||^2 and ||g||^2
+        _, _, _, st, csq = block(curve, 0.0, 1, False)
+        c2, g2 = float(csq[0].double().sum()), float(st[0, :, 1].double().sum())
+        # (a stationary curve, g = 0, or a non-finite one: any eta -- the first block accepts the one and reports the other)
+        eta = 0.25 * c2 / g2 if g2 > 0 and math.isfinite(c2 / g2) and c2 > 0 else 1.0
+    else:
+        eta = step_size
+    while attempted < max_iter:
+        n = min(check_every, max_iter - attempted)
+        curves, sh, sx, st, _ = block(curve, eta, n, True)
+        attempted += n
+        if not energy:
+            energy.append(E(sh[0], sx[0]))
+            info["start"] = {k: _curve_stats(sh[0], sx[0], lam)[k] for k in ("energy", "length_h", "uniformity")}
+            last = (sh[0], sx[0], st[0])
+        bad = flagged(st, 0)
+        if bad is not None:
+            if check:
+                # a point that is not finite itself flags its two neighbours as well (they read its activation): name the point, not the neighbours
+                own = (~torch.isfinite(curves[0]).flatten(1).all(1)).nonzero().flatten().tolist()
+                bad = own[0] if own else bad
+                raise ValueError(f"pullback_geodesic: point {bad} of the curve " + ("is not finite" if own else "meets a non-finite activation or "
+                                 f"adjoint J^T c") + f" at iteration {info['iterations']}; check=False returns the NaN rows")
+            curve, last = curves[1], (sh[1], sx[1], st[0])
+            break
+        e0, e1 = E(sh[0], sx[0]), E(sh[n], sx[n])
+        ok = math.isfinite(e1) and e1 <= e0
+        info["decisions"].append(ok)
+        if not ok:
+            eta, row = eta / 2, row + 1
+            info["halvings"] += 1
+            if row >= max_halvings:
+                break
+            continue
+        row = 0
+        es = [E(sh[j], sx[j]) for j in range(n + 1)]
+        info["rises"] += sum(es[j + 1] > es[j] for j in range(n))
+        curve, last = curves[n], (sh[n], sx[n], st[n - 1])
+        info["iterations"] += n
+        energy.append(e1)
+        if e0 - e1 <= tol * e0:
+            info["converged"] = True
+            break
+    info.update(_curve_stats(last[0], last[1], lam))
+    info.update(energy=energy, monotone=all(b <= a for a, b in zip(energy, energy[1:])), grad_norm=last[2][:, 1].double().sqrt(), step_size=eta,
+                attempted=attempted)
+    return curve, info
+
 
 def bind(unet, kind: str, cfg, dtype=torch.float32, device="cuda:0", **kw) -> PullbackUNet:
     """Attach the HIP-backed methods onto an existing U-Net module, like the reference's
@@ -774,6 +967,8 @@ def bind(unet, kind: str, cfg, dtype=torch.float32, device="cuda:0", **kw) -> Pu
     unet.local_encoder_pullback_batch = types.MethodType(lambda self, *a, **k: self._dpb.local_encoder_pullback_batch(*a, **k), unet)
     unet.inv_jac_chain = types.MethodType(lambda self, *a, **k: self._dpb.inv_jac_chain(*a, **k), unet)
     unet.h_space_guidance = types.MethodType(lambda self, *a, **k: self._dpb.h_space_guidance(*a, **k), unet)
+    unet.pullback_geodesic = types.MethodType(lambda self, *a, **k: self._dpb.pullback_geodesic(*a, **k), unet)
+    unet.curve_energy = types.MethodType(lambda self, *a, **k: self._dpb.curve_energy(*a, **k), unet)
     if kind == "sd":
         unet.local_encoder_pullback_zt = types.MethodType(lambda self, *a, **k: self._dpb.local_encoder_pullback_zt(*a, **k), unet)
         unet.local_decoder_pullback_zt = types.MethodType(lambda self, *a, **k: self._dpb.local_decoder_pullback_zt(*a, **k), unet)

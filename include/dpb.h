@@ -736,6 +736,57 @@ int dpb_hguide_chain(dpb_engine* e, int tap_buf, int eps_buf, const float* x /*d
                      const float* u /*dev [nu][N_h]*/, int nu, const int32_t* dir /*host [n]*/, const float* scale /*host [n]*/, float gP, float gD,
                      int steps, float* states /*dev [steps+1][n][N_in]*/, double* delta /*dev [steps][n][2]*/, void* scratch, size_t scratch_bytes);
 
+/* ---- pullback geodesics between two latents (additive to ABI version 1) ---------------------------------------------------------------
+ * The shortest path between two latents under the pullback metric G(x) = J(x)^T J(x) of h = get_h(x, t), as a discrete curve
+ * P_0 = x_a, P_1 .. P_m, P_{m+1} = x_b at ONE timestep: the m interior points move, the end points are fixed.  With h_i the tap activation of P_i,
+ *   E = 1/2 sum_{i=0..m} ||h_{i+1} - h_i||^2 + 1/2 lambda sum_{i=0..m} ||P_{i+1} - P_i||^2                                   (lambda >= 0)
+ *   g_i = J(P_i)^T c_i + lambda d_i,   c_i = 2 h_i - h_{i-1} - h_{i+1},   d_i = 2 P_i - P_{i-1} - P_{i+1}                   (i = 1 .. m)
+ * and one iteration is the Jacobi step P_i <- P_i - eta g_i, every g_i taken from the same old curve.  lambda = 0 is well posed for this descent:
+ * g_i lies in the row space of J, so what J does not see of the start curve is kept.  (The reference has no such job; its paper's metric is this G.)
+ *
+ * dpb_geodesic_cotangents (engine-independent): h [m+2][D] fp32, cot [m][D] fp32, seg [m+1] FP64, csq [m] FP64 or NULL, all on the device.
+ *   cot_i = fl32((2 h_i - h_{i-1}) - h_{i+1}) (row i - 1 of cot), formed in fp64 and rounded once; seg_i = sum (h_{i+1} - h_i)^2 in fp64 (fp32 widened
+ *   on load, the difference, its square and the sum each rounded once; per-workgroup partial sums of slices of 4096 elements, added in slice order);
+ *   csq_i = sum cot_i^2 of the ROUNDED cotangent, the same chain (row i - 1 of csq): the ||c_i||^2 of the step rule eta_0 = 1/4 sum ||c_i||^2 /
+ *   sum ||g_i||^2.  No atomics: cot_i, csq_i and seg_i are a function of rows i-1 .. i+1 and D only -- bitwise the same in any longer curve and at any
+ *   alignment (16-byte accesses for an aligned row, 4-byte ones otherwise, the same elements per thread).  Two launches, no host synchronisation.
+ * dpb_geodesic_update (engine-independent): P [m+2][N], W [m][N] (the adjoint results J^T c), P_out [m+2][N] fp32; eta, lambda host scalars;
+ *   stats [m][4] FP64, xseg [m+1] FP64 on the device.  Interior rows: g = W_i + lambda ((2 P_i - P_{i-1}) - P_{i+1}) and P_out_i = fl32(P_i - eta g),
+ *   in fp64, every operation rounded once and one rounding to fp32; the end rows are copied.  eta == 0 hands P through bit for bit.  P_out must not
+ *   overlap P (a row reads its neighbours' OLD values): refused.  stats[i - 1] = (sum W_i^2, sum g_i^2, sum (P_out_i - P_i)^2, flag) and xseg_i =
+ *   sum (P_{i+1} - P_i)^2 of the OLD curve, the fixed-order fp64 slice sums of above.  A row whose W_i, P_i or neighbours P_{i-1}, P_{i+1} hold a
+ *   non-finite value: flag = 1 and NaN in exactly that row of P_out (its sums are those of its elements as they are); no other row changes by a bit.
+ *   Two launches, no host synchronisation.
+ * Either: scratch is 8-byte aligned device memory of >= its *_scratch_bytes(m, D or N) bytes (0 when invalid).  Refused (dpb_last_error), the outputs
+ * untouched: null pointers (csq may be NULL), m < 1 or m + 2 > 32768, a row length < 1, a non-finite eta or lambda, lambda < 0, scratch too small or
+ * misaligned.
+ *
+ * dpb_geodesic_chain: `iters` Jacobi iterations with no host work between them.  P [m+2][N_in] fp32 NCHW, one timestep t, ctx [m+2][L][Dc] or NULL.
+ * curves [iters + 1][m+2][N_in]: curves[0] = P (curves may start at P).  At entry the two END POINTS run once to the tap as one batch of 2; their
+ * activations stay in scratch as fp32 NCHW for the whole call.  Iteration j: one primal pass of the m interior rows of curves[j] up to the tap, its
+ * activations converted into the middle of the [m+2][N_h] block, dpb_geodesic_cotangents (seg_h[j]), the adjoint pass of dpb_vjp with one cotangent
+ * per sample, dpb_geodesic_update into curves[j + 1] (stats[j], seg_x[j]).  seg_h, seg_x [iters + 1][m+1], stats [iters][m][4] FP64; csq [iters][m]
+ * FP64 or NULL: the csq of the cotangent kernel at every iteration (||c_i||^2 is no function of the segment sums, and the step rule needs it).  Row `iters` of
+ * seg_h / seg_x takes one more forward pass of the interior rows when final_energy != 0, else it is NaN.  So E of curves[j] is
+ * 1/2 sum seg_h[j] + 1/2 lambda sum seg_x[j].
+ * Host synchronisation: ONE for the call -- the upload of the timestep embedding in the end-point pass; it stays resident in the engine for every
+ * other pass.  No device allocation: scratch is 256-byte aligned device memory of >= dpb_geodesic_chain_scratch_bytes(e, tap_buf, m) bytes (0 when
+ * invalid).  The call leaves no primal state, as dpb_forward.  Refused (dpb_last_error; the next call is unaffected): m outside
+ * [1, min(max_batch, max_tangents)], max_batch < 2, iters < 1, a non-finite t, eta or lambda, lambda < 0, a tap that is not an x-dependent
+ * activation, a missing ctx, scratch too small or misaligned. */
+size_t dpb_geodesic_cotangents_scratch_bytes(int64_t m, int64_t D);   /* 0 when invalid */
+int dpb_geodesic_cotangents(const float* h /*dev [m+2][D]*/, float* cot /*dev [m][D]*/, double* seg /*dev [m+1]*/, double* csq /*dev [m] or NULL*/,
+                            int64_t m, int64_t D, void* scratch, size_t scratch_bytes, void* hip_stream);
+size_t dpb_geodesic_update_scratch_bytes(int64_t m, int64_t N);       /* 0 when invalid */
+int dpb_geodesic_update(const float* P /*dev [m+2][N]*/, const float* W /*dev [m][N]*/, float* P_out /*dev [m+2][N]*/, float eta, float lambda,
+                        int64_t m, int64_t N, double* stats /*dev [m][4]*/, double* xseg /*dev [m+1]*/, void* scratch, size_t scratch_bytes,
+                        void* hip_stream);
+size_t dpb_geodesic_chain_scratch_bytes(const dpb_engine* e, int tap_buf, int m);
+int dpb_geodesic_chain(dpb_engine* e, int tap_buf, const float* P /*dev [m+2][N_in]*/, int m, float t, const float* ctx /*dev [m+2][L][Dc] or NULL*/,
+                       float eta, float lambda, int iters, int final_energy, float* curves /*dev [iters+1][m+2][N_in]*/,
+                       double* seg_h /*dev [iters+1][m+1]*/, double* seg_x /*dev [iters+1][m+1]*/, double* stats /*dev [iters][m][4]*/,
+                       double* csq /*dev [iters][m] or NULL*/, void* scratch, size_t scratch_bytes);
+
 /* Token + position embedding lookup of the CLIP text encoder behind pipe._encode_prompt (src/modules/edit.py:505-522):
  * out[b][c][t] = tok_table[ids[b][t]][c] + pos_table[t][c], fp32 in the engine's NCHW boundary layout (H*W = tokens),
  * ready for dpb_primal of a text-encoder tape.  Tables are [vocab][channels] / [tokens][channels] in `dtype`. */
