@@ -2013,6 +2013,196 @@ int dpb_inv_jac_chain(dpb_engine* e, int tap_buf, const float* x, int n, const f
   return tot.close(r);
 }
 
+// The least-squares inverse of the Jacobian and the newton-h chain: cgls.hip between the engine's tangent and adjoint passes
+size_t dpb_cgls_init_scratch_bytes(int64_t R, int64_t N, int64_t D) { return cgls_scratch_bytes(R, N, D); }
+size_t dpb_cgls_h_step_scratch_bytes(int64_t R, int64_t N, int64_t D) { return cgls_scratch_bytes(R, N, D); }
+size_t dpb_cgls_x_step_scratch_bytes(int64_t R, int64_t N, int64_t D) { return cgls_scratch_bytes(R, N, D); }
+
+int dpb_cgls_init(const float* c, const float* w0, float* delta, float* r, float* p, double* state, double* hist, double mu_abs, double mu_rel,
+                  double tol, int64_t R, int64_t N, int64_t D, void* scratch, size_t scratch_bytes, void* stream) {
+  if (!c || !w0 || !delta || !r || !p || !state || !hist || !scratch) return fail("dpb_cgls_init: null argument");
+  return launch_cgls_init(c, w0, delta, r, p, state, hist, mu_abs, mu_rel, tol, R, N, D, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int dpb_cgls_h_step(const float* q, float* delta, float* r, float* p, double* state, double* hist, int64_t R, int64_t N, int64_t D, void* scratch,
+                    size_t scratch_bytes, void* stream) {
+  if (!q || !delta || !r || !p || !state || !hist || !scratch) return fail("dpb_cgls_h_step: null argument");
+  return launch_cgls_h_step(q, delta, r, p, state, hist, R, N, D, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int dpb_cgls_x_step(const float* w, float* delta, float* r, float* p, double* state, double* hist, double tol, int64_t R, int64_t N, int64_t D,
+                    void* scratch, size_t scratch_bytes, void* stream) {
+  if (!w || !delta || !r || !p || !state || !hist || !scratch) return fail("dpb_cgls_x_step: null argument");
+  return launch_cgls_x_step(w, delta, r, p, state, hist, tol, R, N, D, scratch, scratch_bytes, (hipStream_t)stream);
+}
+
+int dpb_newton_residual(const float* h0, const float* h, const float* u, int nu, const int32_t* dir, const float* sign, const float* scale, double frac,
+                        int64_t n, int64_t D, float* res, void* stream) {
+  if (!h0 || !h || !u || !dir || !sign || !scale || !res) return fail("dpb_newton_residual: null argument");
+  return launch_newton_residual(h0, h, u, nu, dir, sign, scale, frac, n, D, res, (hipStream_t)stream);
+}
+
+int dpb_newton_update(const float* x, const float* delta, const double* state, double radius, float* x_out, double* step_stats, int64_t n, int64_t N,
+                      void* stream) {
+  if (!x || !delta || !state || !x_out || !step_stats) return fail("dpb_newton_update: null argument");
+  return launch_newton_update(x, delta, state, radius, x_out, step_stats, n, N, (hipStream_t)stream);
+}
+
+namespace {
+// the solver's working set for nt rows: w = J^T r, q = J p, the residual r, the search direction p, the per-row state and the slice sums
+struct LstsqScratch { size_t w = 0, q = 0, r = 0, p = 0, state = 0, part = 0, part_bytes = 0, total = 0; long n_in = 0, n_h = 0; };
+void lstsq_take(const dpb_engine* e, int tap, int nt, ScratchLayout& s, LstsqScratch& l) {
+  l.n_in = (long)e->bufs[e->x_buf].rows * e->x_channels;
+  l.n_h = (long)e->bufs[tap].rows * e->bufs[tap].Cv;
+  l.w = s.take((size_t)nt * l.n_in * sizeof(float));
+  l.q = s.take((size_t)nt * l.n_h * sizeof(float));
+  l.r = s.take((size_t)nt * l.n_h * sizeof(float));
+  l.p = s.take((size_t)nt * l.n_in * sizeof(float));
+  l.state = s.take((size_t)nt * 8 * sizeof(double));
+  l.part_bytes = cgls_scratch_bytes(nt, l.n_in, l.n_h);
+  l.part = s.take(l.part_bytes);
+  l.total = s.off;
+}
+bool lstsq_layout(const dpb_engine* e, int tap, int nt, LstsqScratch& l) {
+  if (!e || tap < 0 || tap >= (int)e->bufs.size() || nt < 1) return false;
+  ScratchLayout s;
+  lstsq_take(e, tap, nt, s, l);
+  return true;
+}
+
+int check_solver_scalars(const char* who, double mu_abs, double mu_rel, double tol, int iters) {
+  if (!(mu_abs >= 0.0) || !std::isfinite(mu_abs)) return fail("%s: mu_abs=%g must be finite and not negative", who, mu_abs);
+  if (!(mu_rel >= 0.0) || !std::isfinite(mu_rel)) return fail("%s: mu_rel=%g must be finite and not negative", who, mu_rel);
+  if (!(tol >= 0.0) || !std::isfinite(tol)) return fail("%s: tol=%g must be finite and not negative", who, tol);
+  if (iters < 0) return fail("%s: iters=%d < 0", who, iters);
+  return 0;
+}
+
+// The inner solve on the primal state of the last pass: one adjoint pass for w0 = J^T c, then iters rounds of tangent pass, h-step, adjoint pass,
+// x-step; nothing between them touches the host.  r: the residual rows (the caller's or the scratch's); fl / gb: the passes' flops and bytes.
+int lstsq_solve(dpb_engine* e, int tap, const float* c, int nt, double mu_abs, double mu_rel, double tol, int iters, float* delta, float* r, double* hist,
+                char* sc, const LstsqScratch& l, double& fl, double& gb) {
+  float *w = (float*)(sc + l.w), *q = (float*)(sc + l.q), *p = (float*)(sc + l.p);
+  double* state = (double*)(sc + l.state);
+  void* part = sc + l.part;
+  if (int rc = vjp_pass(e, e->x_buf, tap, c, nt, w)) return rc;
+  fl += e->flops; gb += e->gbytes;
+  if (int rc = launch_cgls_init(c, w, delta, r, p, state, hist, mu_abs, mu_rel, tol, nt, l.n_in, l.n_h, part, l.part_bytes, e->stream)) return rc;
+  for (int i = 1; i <= iters; ++i) {
+    double* hi = hist + (size_t)i * nt * 4;
+    if (int rc = jvp_pass(e, e->x_buf, tap, p, nt, q)) return rc;
+    fl += e->flops; gb += e->gbytes;
+    if (int rc = launch_cgls_h_step(q, delta, r, p, state, hi, nt, l.n_in, l.n_h, part, l.part_bytes, e->stream)) return rc;
+    if (int rc = vjp_pass(e, e->x_buf, tap, r, nt, w)) return rc;
+    fl += e->flops; gb += e->gbytes;
+    if (int rc = launch_cgls_x_step(w, delta, r, p, state, hi, tol, nt, l.n_in, l.n_h, part, l.part_bytes, e->stream)) return rc;
+  }
+  return 0;
+}
+}  // namespace
+
+size_t dpb_jac_lstsq_scratch_bytes(const dpb_engine* e, int tap_buf, int nt) {
+  LstsqScratch l;
+  return lstsq_layout(e, tap_buf, nt, l) ? l.total : 0;
+}
+
+int dpb_jac_lstsq(dpb_engine* e, int tap_buf, const float* c, int nt, double mu_abs, double mu_rel, double tol, int iters, float* delta, float* resid,
+                  double* hist, void* scratch, size_t scratch_bytes) {
+  if (!e || !c || !delta || !hist || !scratch) return fail("dpb_jac_lstsq: null argument");
+  if (int r = check_solver_scalars("dpb_jac_lstsq", mu_abs, mu_rel, tol, iters)) return r;
+  if (int r = check_pass(e, e->x_buf, tap_buf, nt)) return r;
+  if ((uintptr_t)hist & 7) return fail("dpb_jac_lstsq: hist must be 8-byte aligned");
+  LstsqScratch l;
+  lstsq_layout(e, tap_buf, nt, l);
+  if (int r = check_scratch("dpb_jac_lstsq", "dpb_jac_lstsq_scratch_bytes", scratch, scratch_bytes, l.total)) return r;
+  const long at = launch_count;                     // the sub-passes' LaunchSpans overwrite n_launch as they go: the assignment at the end is what counts
+  double fl = 0, gb = 0;
+  char* sc = (char*)scratch;
+  const int r = lstsq_solve(e, tap_buf, c, nt, mu_abs, mu_rel, tol, iters, delta, resid ? resid : (float*)(sc + l.r), hist, sc, l, fl, gb);
+  e->n_launch = launch_count - at; e->flops = fl; e->gbytes = gb;
+  return r;
+}
+
+namespace {
+struct NewtonScratch { size_t h = 0, h0 = 0, res = 0, delta = 0, total = 0; LstsqScratch ls; };
+bool newton_layout(const dpb_engine* e, int tap, int n, NewtonScratch& l) {
+  if (!e || tap < 0 || tap >= (int)e->bufs.size() || n < 1) return false;
+  ScratchLayout s;
+  lstsq_take(e, tap, n, s, l.ls);
+  l.h = s.take((size_t)n * l.ls.n_h * sizeof(float));
+  l.h0 = s.take((size_t)n * l.ls.n_h * sizeof(float));
+  l.res = s.take((size_t)n * l.ls.n_h * sizeof(float));
+  l.delta = s.take((size_t)n * l.ls.n_in * sizeof(float));
+  l.total = s.off;
+  return true;
+}
+}  // namespace
+
+size_t dpb_newton_h_chain_scratch_bytes(const dpb_engine* e, int tap_buf, int n) {
+  NewtonScratch l;
+  return newton_layout(e, tap_buf, n, l) ? l.total : 0;
+}
+
+int dpb_newton_h_chain(dpb_engine* e, int tap_buf, const float* x, int n, const float* t, const float* ctx, const float* u, int nu, const int32_t* dir,
+                       const float* sign, const float* scale, int steps, int iters, double mu_abs, double mu_rel, double tol, double radius,
+                       int final_shift, float* states, double* hist, double* step_stats, double* shift, void* scratch, size_t scratch_bytes) {
+  if (!e || !x || !t || !u || !dir || !sign || !scale || !states || !hist || !step_stats || !shift || !scratch)
+    return fail("dpb_newton_h_chain: null argument");
+  e->cur_batch = 0;                                // as dpb_forward: whatever happens below, the primal state is gone
+  if (!e->ws) return fail("workspace not set (dpb_engine_set_workspace)");
+  const int cap = std::min(e->maxB, e->maxT);
+  if (n < 1 || n > cap) return fail("dpb_newton_h_chain: n=%d chains outside [1,%d] (min of max_batch and max_tangents)", n, cap);
+  if (steps < 1) return fail("dpb_newton_h_chain: steps=%d < 1", steps);
+  if (int r = check_dirs("dpb_newton_h_chain", n, nu, 0, dir, {{"sign", sign}, {"scale", scale}})) return r;
+  if (int r = check_solver_scalars("dpb_newton_h_chain", mu_abs, mu_rel, tol, iters)) return r;
+  if (!(radius >= 0.0) || !std::isfinite(radius)) return fail("dpb_newton_h_chain: radius=%g must be finite and not negative (0: no clamp)", radius);
+  const float* tv;
+  if (int r = check_timesteps(e, n, t, &tv)) return r;
+  if (int r = check_chain_tap(e, "dpb_newton_h_chain", tap_buf)) return r;
+  if (e->ctx_buf >= 0 && !ctx) return fail("this network needs ctx (encoder_hidden_states)");
+  if ((uintptr_t)hist & 7 || (uintptr_t)step_stats & 7 || (uintptr_t)shift & 7) return fail("dpb_newton_h_chain: hist, step_stats and shift must be 8-byte aligned");
+  NewtonScratch l;
+  newton_layout(e, tap_buf, n, l);
+  if (int r = check_scratch("dpb_newton_h_chain", "dpb_newton_h_chain_scratch_bytes", scratch, scratch_bytes, l.total)) return r;
+  char* sc = (char*)scratch;
+  float *hb = (float*)(sc + l.h), *h0 = (float*)(sc + l.h0), *res = (float*)(sc + l.res), *delta = (float*)(sc + l.delta);
+  const Buf& bt = e->bufs[tap_buf];
+  const long n_in = l.ls.n_in, n_h = l.ls.n_h;
+  const size_t row = (size_t)n * n_in;
+  CallTotals tot(e);
+  if (states != x) DPB_CHECK(hipMemcpyAsync(states, x, row * sizeof(float), hipMemcpyDeviceToDevice, e->stream));
+  // the tap activation of the pass just run, as fp32 NCHW, and its shift statistics against the copy kept from step 0
+  auto shift_of = [&](int j) -> int {
+    float* dst = j == 0 ? h0 : hb;
+    if (int r = launch_nhwc_to_nchw(e->dtype, e->P(tap_buf), dst, n, bt.Cv, bt.rows, bt.C, e->stream)) return r;
+    return launch_shift_stats(dst, h0, u, nu, dir, sign, n, n_h, shift + (size_t)j * n * 2, e->stream);
+  };
+  int r = 0;
+  for (int j = 0; j < steps && !r; ++j) {
+    const float* xj = states + (size_t)j * row;
+    Forward f;
+    f.temb_resident = j > 0;                        // same timesteps as the step before: their embeddings are still in P(temb_buf), no upload, no sync
+    r = primal_pass(e, xj, n, t[0], ctx, tap_buf, f, tv);
+    tot.add();
+    if (!r) r = shift_of(j);
+    if (!r) r = launch_newton_residual(h0, j == 0 ? h0 : hb, u, nu, dir, sign, scale, (double)(j + 1) / (double)steps, n, n_h, res, e->stream);
+    if (!r) r = lstsq_solve(e, tap_buf, res, n, mu_abs, mu_rel, tol, iters, delta, (float*)(sc + l.ls.r), hist + (size_t)j * (iters + 1) * n * 4, sc, l.ls,
+                            tot.fl, tot.gb);
+    if (!r) r = launch_newton_update(xj, delta, (const double*)(sc + l.ls.state), radius, states + (size_t)(j + 1) * row, step_stats + (size_t)j * n * 4, n,
+                                     n_in, e->stream);
+  }
+  if (!r && final_shift) {
+    Forward f;
+    f.stash = false; f.temb_resident = true;
+    r = primal_pass(e, states + (size_t)steps * row, n, t[0], ctx, tap_buf, f, tv);
+    tot.add();
+    if (!r) r = shift_of(steps);
+  } else if (!r) {
+    DPB_CHECK(hipMemsetAsync(shift + (size_t)steps * n * 2, 0xff, (size_t)n * 2 * sizeof(double), e->stream));   // all bits set: a NaN
+  }
+  return tot.close(r);
+}
+
 // The h-space guidance edit (hguide.hip between the engine's grouped passes): dpb_ddim_step_asym and the device DDIM chain
 size_t dpb_ddim_step_asym_scratch_bytes(int64_t n, int64_t N) { return ddim_step_asym_scratch_bytes(n, N); }
 

@@ -522,8 +522,24 @@ int launch_geodesic_cotangents(const float* h, float* cot, double* seg, double* 
 size_t geodesic_update_scratch_bytes(long m, long N);       // 0 when invalid
 int launch_geodesic_update(const float* P, const float* W, float* P_out, float eta, float lambda, long m, long N, double* stats, double* xseg,
                            void* scratch, size_t scratch_bytes, hipStream_t st);
+// ---------------------------------------------------------------- the least-squares inverse of the Jacobian (cgls.hip): CGLS between the passes
+// R independent rows of min ||J d - c||^2 + mu ||d||^2; d, p, w [R][N], r, q, c [R][D] fp32; state [R][8] and hist [R][4] fp64 on the device;
+// d, r and p are updated in place; one scratch size for the three steps; see include/dpb.h
+size_t cgls_scratch_bytes(long R, long N, long D);          // 0 when invalid
+int launch_cgls_init(const float* c, const float* w0, float* delta, float* r, float* p, double* state, double* hist, double mu_abs, double mu_rel,
+                     double tol, long R, long N, long D, void* scratch, size_t scratch_bytes, hipStream_t st);
+int launch_cgls_h_step(const float* q, float* delta, float* r, float* p, double* state, double* hist, long R, long N, long D, void* scratch,
+                       size_t scratch_bytes, hipStream_t st);
+int launch_cgls_x_step(const float* w, float* delta, float* r, float* p, double* state, double* hist, double tol, long R, long N, long D, void* scratch,
+                       size_t scratch_bytes, hipStream_t st);
+// the newton-h chain around an inner solve: res = fl32(h0 + frac scale[b] sign[b] u[dir[b]] - h) (dir / sign / scale HOST arrays), and
+// x_out = fl32(x + kappa d), kappa = min(1, radius / ||d||) with ||d||^2 from the solver's state, step_stats [n][4] = (||res||^2, ||d||^2, kappa, flag)
+int launch_newton_residual(const float* h0, const float* h, const float* u, int nu, const int32_t* dir, const float* sign, const float* scale,
+                           double frac, long n, long D, float* res, hipStream_t st);
+int launch_newton_update(const float* x, const float* delta, const double* state, double radius, float* x_out, double* step_stats, long n, long N,
+                         hipStream_t st);
 // ---------------------------------------------------------------- DDIM
-// x_next = sqrt(a_next) * (x - e*sqrt(1-a_t))/sqrt(a_t) + sqrt(1-a_next) * e      (fp32, elementwise)
+// x_next =sqrt(a_next) * (x - e*sqrt(1-a_t))/sqrt(a_t) + sqrt(1-a_next) * e      (fp32, elementwise)
 int launch_ddim_step(const float* x, const float* e, float* out, float* x0, long n, float a_t, float a_next, hipStream_t st);
 // out = a*x + b*y + c*z (z may be null)
 int launch_lincomb(const float* x, const float* y, const float* z, float* out, long n, float a, float b, float c, hipStream_t st);

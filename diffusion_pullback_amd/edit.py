@@ -724,6 +724,10 @@ class EditUncondDiffusion(_EditBase):
         # "parallel-x": every chain of the global-basis jobs pushes along one x-space direction fixed at x_t (x-space guidance).  "parallel-h": the
         # h-space direction is held fixed and the x-space direction is recomputed at every state (edit.py:1202-1229; _run_parallel_h_chains)
         self.edit_xt = getattr(args, "edit_xt", "parallel-x")
+        # "newton-h": every chain aims at the h-space shift h_edit_step_size along its direction by damped Gauss-Newton steps (_run_newton_h_chains)
+        self.newton_iters = getattr(args, "newton_iters", 8)
+        self.newton_damping = getattr(args, "newton_damping", 0.1)
+        self.newton_radius = getattr(args, "newton_radius", 0.0)
         self.x_edit_step_size = getattr(args, "x_edit_step_size", 0.0)
         self.use_sega_reg = bool(getattr(args, "use_sega_reg", False))
         self.sega_reg_sigma = getattr(args, "sega_reg_sigma", 1.0)
@@ -1038,7 +1042,7 @@ class EditUncondDiffusion(_EditBase):
         if frechet_mean_space not in ("x", "h"):
             raise ValueError(f"frechet_mean_space must be 'x' (the spans of vT) or 'h' (the spans of u), got {frechet_mean_space!r}")
         self._check_parallel_h(frechet_mean_space)
-        if frechet_mean_space == "h" and not local_projection and self.edit_xt != "parallel-h" and self.edit_ht != "h_space_guidance":
+        if frechet_mean_space == "h" and not local_projection and self.edit_xt not in ("parallel-h", "newton-h") and self.edit_ht != "h_space_guidance":
             raise ValueError("local_projection=False is valid for frechet_mean_space 'x' only: an h-space direction reaches x-space through the sample's "
                              "own local basis (the reference leaves vk undefined there)")
         h_t = self.h_t if h_t is None else h_t
@@ -1122,7 +1126,7 @@ class EditUncondDiffusion(_EditBase):
         if flag_mean_space not in ("x", "h"):
             raise ValueError(f"flag_mean_space must be 'x' (the spans of vT) or 'h' (the spans of u), got {flag_mean_space!r}")
         self._check_parallel_h(flag_mean_space)
-        if flag_mean_space == "h" and not local_projection and self.edit_xt != "parallel-h" and self.edit_ht != "h_space_guidance":
+        if flag_mean_space == "h" and not local_projection and self.edit_xt not in ("parallel-h", "newton-h") and self.edit_ht != "h_space_guidance":
             raise ValueError("local_projection=False is valid for flag_mean_space 'x' only: an h-space direction reaches x-space through the sample's "
                              "own local basis")
         r = int(pca_rank if not flag_rank else flag_rank)
@@ -1208,7 +1212,8 @@ class EditUncondDiffusion(_EditBase):
         own_dir, own_name = self._tangent_space_naming(op, block_idx, pca_rank)
         files = self._basis_paths(own_dir, own_name(idx, h_t))
         h_guide = self.edit_ht == "h_space_guidance"
-        parallel_h = self.edit_xt == "parallel-h" or h_guide    # (both follow the h-direction itself: the local basis serves the plot only)
+        run_h_chains = self._run_newton_h_chains if self.edit_xt == "newton-h" else self._run_parallel_h_chains
+        parallel_h = self.edit_xt in ("parallel-h", "newton-h") or h_guide    # (all follow the h-direction itself: the local basis serves the plot only)
         have = os.path.exists(files[0]) and os.path.exists(files[2]) and (local_projection or not parallel_h)   # (parallel-h reads it for the plot only)
         if local_projection and not have:
             print("!!!SAMPLE LOCAL TANGENT SPACE!!!")
@@ -1230,7 +1235,7 @@ class EditUncondDiffusion(_EditBase):
             if h_guide:
                 out["chains"] = self._run_h_guidance_chains([(c[0], c[2], c[3]) for c in chains], original_xt, basis, op, block_idx, vis_num, shape)
             else:
-                out["chains"] = self._run_parallel_h_chains(chains, basis, op, block_idx, vis_num, shape)
+                out["chains"] = run_h_chains(chains, basis, op, block_idx, vis_num, shape)
             return out
         if local_projection:
             with T.phase("projection of the global directions on the local basis"):
@@ -1257,16 +1262,25 @@ class EditUncondDiffusion(_EditBase):
             if h_guide:
                 out["chains"] = self._run_h_guidance_chains([(c[0], *by_name[c[0]]) for c in chains], original_xt, basis, op, block_idx, vis_num, shape)
                 return out
-            out["chains"] = self._run_parallel_h_chains([(c[0], c[1], *by_name[c[0]]) for c in chains], basis, op, block_idx, vis_num, shape)
+            out["chains"] = run_h_chains([(c[0], c[1], *by_name[c[0]]) for c in chains], basis, op, block_idx, vis_num, shape)
             return out
         self._run_direction_chains(chains, vis_num, shape)
         return out
 
     def _check_parallel_h(self, space):
         """what --edit_xt asks of a global-basis job, checked before anything is computed"""
-        if self.edit_xt not in ("parallel-x", "parallel-h"):
-            raise ValueError(f"edit_xt must be 'parallel-x' or 'parallel-h', got {self.edit_xt!r}")
+        if self.edit_xt not in ("parallel-x", "parallel-h", "newton-h"):
+            raise ValueError(f"edit_xt must be 'parallel-x', 'parallel-h' or 'newton-h', got {self.edit_xt!r}")
         self._check_h_guidance(space)
+        if self.edit_xt == "newton-h":
+            if space != "h":
+                raise ValueError("edit_xt 'newton-h' aims at an h-space shift: it needs the h-space global basis (space 'h'), not 'x'")
+            if not (float(self.h_edit_step_size) != 0 and math.isfinite(float(self.h_edit_step_size))):
+                raise ValueError(f"edit_xt 'newton-h' needs h_edit_step_size != 0 (the h-space shift the chain aims at), got {self.h_edit_step_size}")
+            if int(self.newton_iters) < 0 or not float(self.newton_damping) >= 0 or not float(self.newton_radius) >= 0:
+                raise ValueError(f"edit_xt 'newton-h' needs newton_iters, newton_damping and newton_radius >= 0, got {self.newton_iters}, "
+                                 f"{self.newton_damping}, {self.newton_radius}")
+            return
         if self.edit_xt != "parallel-h":
             return
         if space != "h":
@@ -1281,8 +1295,8 @@ class EditUncondDiffusion(_EditBase):
             raise ValueError(f"edit_ht must be 'default' or 'h_space_guidance', got {self.edit_ht!r}")
         if self.edit_ht != "h_space_guidance":
             return
-        if self.edit_xt == "parallel-h":
-            raise ValueError("edit_ht 'h_space_guidance' and edit_xt 'parallel-h' exclude each other: the reference takes the guidance branch with "
+        if self.edit_xt in ("parallel-h", "newton-h"):
+            raise ValueError(f"edit_ht 'h_space_guidance' and edit_xt {self.edit_xt!r} exclude each other: the reference takes the guidance branch with "
                              "edit_xt at its default only")
         if space != "h":
             raise ValueError("edit_ht 'h_space_guidance' adds an h-space direction at the tap: it needs the h-space global basis (space 'h'), not 'x'")
@@ -1383,6 +1397,50 @@ class EditUncondDiffusion(_EditBase):
         self._phase = _EditBase._phase
         return recs
 
+    def _run_newton_h_chains(self, chains, basis_h, op, block_idx, vis_num, shape):
+        """The newton-h branch, beside _run_parallel_h_chains.  chains: (EXP_NAME, start x_t [1, ...], pc, sign).  Each aims at the h-space shift
+        h_edit_step_size along uk = sign * basis_h[pc] / ||.|| in vis_num damped Gauss-Newton steps from its start, at the timestep
+        timesteps[edit_t_idx] (unet.newton_h_chain: newton_iters CGLS iterations per step with newton_damping, a step's length in x clamped to
+        newton_radius when that is > 0); the states picked as the sibling picks them are decoded into x0_gen-<EXP_NAME>.png.  A pos chain moves h
+        ALONG uk, where parallel-h moves against it.  Each chain writes newton-<EXP_NAME>.pt into the obs folder (h_shift, h_dist, h_off: one entry
+        per state; resid_norm, delta_norm, clip, inner_iterations: one per step; scale) and prints one line.  trajectory_batch > 1: all chains
+        through one unet.newton_h_chain call and one decode batch; <= 1: one after another.  Returns the chain records, in order."""
+        if not chains:
+            return []
+        t = self.scheduler.timesteps[self.edit_t_idx]
+        uhat = (basis_h / basis_h.norm(dim=1, keepdim=True)).t().contiguous()                   # [N_h, k]: column pc is direction pc
+        scale = float(self.h_edit_step_size)
+        stride = int((vis_num + 1) / vis_num)
+        keys = ("h_shift", "h_dist", "h_off", "resid_norm", "delta_norm", "clip", "inner_iterations")
+
+        def run(group):
+            self._phase = "newton-h chain: one primal pass and the inner solve's tangent and adjoint passes per step"
+            r = self.unet.newton_h_chain(x=torch.cat([c[1] for c in group]).to(device=self.device, dtype=self.dtype), t=t, u=uhat,
+                                         dirs=[c[2] for c in group], signs=[float(c[3]) for c in group], scale=scale, steps=vis_num,
+                                         iters=int(self.newton_iters), damping=float(self.newton_damping),
+                                         radius=float(self.newton_radius) or None, op=op, block_idx=block_idx)
+            picked = r["states"][:, ::stride]
+            m = picked.size(1)
+            self._phase = "DDIM decode of the edited latents: U-Net forwards"
+            x0 = self.DDIMforwardsteps(picked.reshape(len(group) * m, *shape), t_start_idx=self.edit_t_idx, t_end_idx=-1, save_image_=False,
+                                       performance_boosting=True)
+            recs = []
+            for i, c in enumerate(group):
+                self.EXP_NAME = c[0]
+                save_image((x0[i * m:(i + 1) * m] / 2 + 0.5).clamp(0, 1), os.path.join(self.result_folder, f"x0_gen-{c[0]}.png"), nrow=m)
+                rec = {k: r[k][i].cpu() for k in keys}
+                rec["scale"] = scale
+                torch.save(rec, os.path.join(self.obs_folder, f"newton-{c[0]}.pt"))
+                print(f"newton-h chain {c[0]}: {vis_num} steps of {int(self.newton_iters)} iterations, h shift along u {float(rec['h_shift'][-1]):.4g} "
+                      f"of {scale:g} asked, off-axis {float(rec['h_off'][-1]):.4g}, inner iterations {[int(a) for a in rec['inner_iterations']]}")
+                recs.append(rec)
+            return recs
+
+        groups = [chains] if self.trajectory_batch > 1 else [[c] for c in chains]
+        recs = [rec for g in groups for rec in run(g)]
+        self._phase = _EditBase._phase
+        return recs
+
     def global_hungarian_mean_paths(self, op="mid", block_idx=0, pca_rank=50, h_t=None):
         """{"u": (basis file, info file), "v": ...} of the two Hungarian global bases, in the reference's layout (edit.py:1270-1274; the directory
         without the scheduler_name the reference never defines): {u,v}-<h_t>T-<op>-block_<b>-seed_<seed>.pt holds [N, k] columns.  The reference's
@@ -1417,7 +1475,7 @@ class EditUncondDiffusion(_EditBase):
         if hungarian_mean_space not in ("x", "h"):
             raise ValueError(f"hungarian_mean_space must be 'x' (the directions of vT) or 'h' (the directions of u), got {hungarian_mean_space!r}")
         self._check_parallel_h(hungarian_mean_space)
-        if hungarian_mean_space == "h" and not local_projection and self.edit_xt != "parallel-h" and self.edit_ht != "h_space_guidance":
+        if hungarian_mean_space == "h" and not local_projection and self.edit_xt not in ("parallel-h", "newton-h") and self.edit_ht != "h_space_guidance":
             raise ValueError("local_projection=False is valid for hungarian_mean_space 'x' only: an h-space direction reaches x-space through the "
                              "sample's own local basis")
         if hungarian_distance not in geometry.HUNGARIAN_DISTANCES:

@@ -380,6 +380,58 @@ class Engine:
                                                _ptr(states), _ptr(vk), _ptr(stats), _ptr(shift), self._scratch(need), need))
         return states, vk, stats, shift
 
+    # ------------------------------------------------------------------ the least-squares inverse of the Jacobian and the newton-h chain
+    def jac_lstsq(self, tap, c: torch.Tensor, mu_abs: float = 0.0, mu_rel: float = 0.1, tol: float = 1e-5, iters: int = 16,
+                  return_resid: bool = False):
+        """dpb_jac_lstsq on the state primal() left: CGLS on min ||J d - c||^2 + mu ||d||^2 from d = 0, per row, mu = mu_abs + mu_rel ||J^T c||^2 /
+        ||c||^2.  c [nt, N_h] (NCHW-flattened), with jvp()'s row convention: row j belongs to sample j // (nt // batch).  Returns device tensors
+        (delta [nt, N_in], resid [nt, N_h] or None, hist [iters + 1, nt, 4] fp64 = (gamma, ||r||^2, ||d||^2, flag)); no host sync; the primal state
+        stays usable (include/dpb.h states the recurrence and the flags)."""
+        buf = self.tape.taps[tap]
+        iters = int(iters)
+        with torch.cuda.device(self.device):
+            self._set_stream()
+            c = _f32(c, self.device).reshape(-1, self.tap_numel(tap))
+            nt = c.shape[0]
+            delta = torch.empty(nt, self.n_in, dtype=torch.float32, device=self.device)
+            resid = torch.empty_like(c) if return_resid else None
+            hist = torch.empty(max(iters, 0) + 1, nt, 4, dtype=torch.float64, device=self.device)
+            need = int(self.lib.dpb_jac_lstsq_scratch_bytes(self.h, buf, nt))
+            L.check(self.lib.dpb_jac_lstsq(self.h, buf, _ptr(c), nt, float(mu_abs), float(mu_rel), float(tol), iters, _ptr(delta), _ptr(resid),
+                                           _ptr(hist), self._scratch(need), need))
+        return delta, resid, hist
+
+    def newton_h_chain(self, x: torch.Tensor, t, ctx: Optional[torch.Tensor], tap, u: torch.Tensor, dirs, signs, scale, steps: int, iters: int,
+                       mu_abs: float = 0.0, mu_rel: float = 0.1, tol: float = 1e-5, radius: float = 0.0, final_shift: bool = True):
+        """dpb_newton_h_chain: n = x.shape[0] damped Gauss-Newton chains advanced together, chain b towards h0_b + scale[b] * signs[b] * u[dirs[b]]
+        in `steps` outer steps of `iters` CGLS iterations each, with no Python between them.  A chain with sign +1 moves h ALONG its direction (the
+        opposite of inv_jac_chain).  Returns device tensors (states [steps + 1, n, C, H, W], hist [steps, iters + 1, n, 4] fp64, step_stats
+        [steps, n, 4] fp64 = (||res||^2, ||delta||^2, kappa, flag), shift [steps + 1, n, 2] fp64 as inv_jac_chain's).  Like forward(), keeps no
+        primal state."""
+        buf = self.tape.taps[tap]
+        steps, iters = int(steps), int(iters)
+        with torch.cuda.device(self.device):
+            self._set_stream()
+            x, n, ctx = self._inputs(x, ctx)
+            tl = timesteps(t, n)
+            tl = [tl] * n if isinstance(tl, float) else tl
+            dirs, signs, scale = [int(d) for d in dirs], [float(s) for s in signs], [float(s) for s in scale]
+            if not (len(dirs) == len(signs) == len(scale) == n):
+                raise L.DpbError(f"dirs, signs and scale have {len(dirs)}, {len(signs)} and {len(scale)} entries for {n} chains: one of each per chain")
+            u = self._directions(u, tap)
+            ns, ni = max(steps, 1), max(iters, 0)
+            states = torch.empty(ns + 1, n, *x.shape[1:], dtype=torch.float32, device=self.device)
+            hist = torch.empty(ns, ni + 1, n, 4, dtype=torch.float64, device=self.device)
+            step_stats = torch.empty(ns, n, 4, dtype=torch.float64, device=self.device)
+            shift = torch.empty(ns + 1, n, 2, dtype=torch.float64, device=self.device)
+            need = int(self.lib.dpb_newton_h_chain_scratch_bytes(self.h, buf, n))
+            self.batch = 0
+            L.check(self.lib.dpb_newton_h_chain(self.h, buf, _ptr(x), n, (C.c_float * n)(*tl), _ptr(ctx), _ptr(u), u.shape[0], (C.c_int32 * n)(*dirs),
+                                                (C.c_float * n)(*signs), (C.c_float * n)(*scale), steps, iters, float(mu_abs), float(mu_rel), float(tol),
+                                                float(radius), int(bool(final_shift)), _ptr(states), _ptr(hist), _ptr(step_stats), _ptr(shift),
+                                                self._scratch(need), need))
+        return states, hist, step_stats, shift
+
     # ------------------------------------------------------------------ the h-space guidance edit on the device
     def forward_shift_groups(self, x: torch.Tensor, groups: int, t: float, ctx: Optional[torch.Tensor], src, u: torch.Tensor, dirs, scales,
                              dst="eps") -> torch.Tensor:
@@ -572,6 +624,110 @@ def shift_stats(h: torch.Tensor, h0: torch.Tensor, u: torch.Tensor, dirs, signs)
         L.check(lib.dpb_shift_stats(_ptr(h), _ptr(h0), _ptr(u), u.shape[0], (C.c_int32 * max(n, 1))(*dirs), (C.c_float * max(n, 1))(*signs), n, D,
                                     _ptr(out), C.c_void_p(st)))
     return out
+
+
+def _rows32(name: str, a: torch.Tensor, shape=None, device=None) -> None:
+    if not (a.is_cuda and a.dim() == 2 and a.dtype == torch.float32 and a.is_contiguous()) or (device is not None and a.device != device) \
+            or (shape is not None and tuple(a.shape) != tuple(shape)):
+        raise L.DpbError(f"{name} must be a contiguous fp32 2-D tensor on a HIP device" + (f" of shape {tuple(shape)}" if shape is not None else ""))
+
+
+class CglsState:
+    """The device side of a CGLS solve of R rows (include/dpb.h "The least-squares inverse"): delta, p [R, N] and r [R, D] fp32, updated in place by
+    the steps, state [R, 8] fp64 = (gamma, gamma0, mu, ||r||^2, ||delta||^2, flag, ||c||^2, x-steps taken) and the solver's scratch."""
+
+    def __init__(self, R: int, N: int, D: int, device):
+        lib = L.load()
+        self.R, self.N, self.D = R, N, D
+        self.delta = torch.empty(R, N, dtype=torch.float32, device=device)
+        self.p = torch.empty(R, N, dtype=torch.float32, device=device)
+        self.r = torch.empty(R, D, dtype=torch.float32, device=device)
+        self.state = torch.empty(R, 8, dtype=torch.float64, device=device)
+        self.need = int(lib.dpb_cgls_init_scratch_bytes(R, N, D))
+        self.scratch = torch.empty(max(self.need // 8, 1), dtype=torch.float64, device=device)
+
+
+def cgls_init(c: torch.Tensor, w0: torch.Tensor, mu_abs: float = 0.0, mu_rel: float = 0.0, tol: float = 0.0, into: Optional[CglsState] = None):
+    """dpb_cgls_init (engine-independent): c [R, D] and w0 = J^T c [R, N], fp32 on a HIP device.  Returns (CglsState, hist [R, 4] fp64 = (gamma,
+    ||r||^2, ||delta||^2, flag)).  into: a CglsState of the same shape to reuse.  No host sync."""
+    lib = L.load()
+    _rows32("c", c)
+    R, D = c.shape
+    _rows32("w0", w0, device=c.device)
+    if w0.shape[0] != R:
+        raise L.DpbError(f"c has {R} rows, w0 {w0.shape[0]}")
+    N = w0.shape[1]
+    s = into if into is not None else CglsState(R, N, D, c.device)
+    if (s.R, s.N, s.D) != (R, N, D):
+        raise L.DpbError(f"the CglsState is for {(s.R, s.N, s.D)}, the call for {(R, N, D)}")
+    with torch.cuda.device(c.device):
+        st = torch.cuda.current_stream(c.device).cuda_stream
+        hist = torch.empty(R, 4, dtype=torch.float64, device=c.device)
+        L.check(lib.dpb_cgls_init(_ptr(c), _ptr(w0), _ptr(s.delta), _ptr(s.r), _ptr(s.p), _ptr(s.state), _ptr(hist), float(mu_abs), float(mu_rel),
+                                  float(tol), R, N, D, _ptr(s.scratch), s.need, C.c_void_p(st)))
+    return s, hist
+
+
+def cgls_h_step(s: CglsState, q: torch.Tensor) -> torch.Tensor:
+    """dpb_cgls_h_step: q = J p [R, D]; updates s.delta and s.r in place and returns the history row [R, 4] fp64.  No host sync."""
+    lib = L.load()
+    _rows32("q", q, (s.R, s.D), s.delta.device)
+    with torch.cuda.device(q.device):
+        st = torch.cuda.current_stream(q.device).cuda_stream
+        hist = torch.empty(s.R, 4, dtype=torch.float64, device=q.device)
+        L.check(lib.dpb_cgls_h_step(_ptr(q), _ptr(s.delta), _ptr(s.r), _ptr(s.p), _ptr(s.state), _ptr(hist), s.R, s.N, s.D, _ptr(s.scratch), s.need,
+                                    C.c_void_p(st)))
+    return hist
+
+
+def cgls_x_step(s: CglsState, w: torch.Tensor, tol: float = 0.0) -> torch.Tensor:
+    """dpb_cgls_x_step: w = J^T r [R, N]; updates s.p in place and returns the history row [R, 4] fp64.  No host sync."""
+    lib = L.load()
+    _rows32("w", w, (s.R, s.N), s.delta.device)
+    with torch.cuda.device(w.device):
+        st = torch.cuda.current_stream(w.device).cuda_stream
+        hist = torch.empty(s.R, 4, dtype=torch.float64, device=w.device)
+        L.check(lib.dpb_cgls_x_step(_ptr(w), _ptr(s.delta), _ptr(s.r), _ptr(s.p), _ptr(s.state), _ptr(hist), float(tol), s.R, s.N, s.D,
+                                    _ptr(s.scratch), s.need, C.c_void_p(st)))
+    return hist
+
+
+def newton_residual(h0: torch.Tensor, h: torch.Tensor, u: torch.Tensor, dirs, signs, scale, frac: float) -> torch.Tensor:
+    """dpb_newton_residual (engine-independent): res[b] = h0[b] + frac * scale[b] * signs[b] * u[dirs[b]] - h[b], formed in fp64 and rounded once;
+    h0, h [n, D] and u [nu, D] fp32 on a HIP device, dirs / signs / scale host sequences of n.  No host sync."""
+    lib = L.load()
+    _rows32("h0", h0)
+    n, D = h0.shape
+    _rows32("h", h, (n, D), h0.device)
+    _rows32("u", u, device=h0.device)
+    if u.shape[1] != D:
+        raise L.DpbError(f"u {tuple(u.shape)} does not hold directions of {D} elements")
+    dirs, signs, scale = [int(d) for d in dirs], [float(s) for s in signs], [float(s) for s in scale]
+    if not (len(dirs) == len(signs) == len(scale) == n):
+        raise L.DpbError(f"dirs, signs and scale have {len(dirs)}, {len(signs)} and {len(scale)} entries for {n} rows")
+    with torch.cuda.device(h0.device):
+        st = torch.cuda.current_stream(h0.device).cuda_stream
+        res = torch.empty_like(h0)
+        L.check(lib.dpb_newton_residual(_ptr(h0), _ptr(h), _ptr(u), u.shape[0], (C.c_int32 * n)(*dirs), (C.c_float * n)(*signs), (C.c_float * n)(*scale),
+                                        float(frac), n, D, _ptr(res), C.c_void_p(st)))
+    return res
+
+
+def newton_update(x: torch.Tensor, delta: torch.Tensor, state: torch.Tensor, radius: float = 0.0):
+    """dpb_newton_update (engine-independent): x_out[b] = x[b] + kappa_b * delta[b], kappa_b = min(1, radius / ||delta_b||) (radius = 0: no clamp) with
+    ||delta_b||^2 from the solver's state [n, 8] fp64.  Returns (x_out, step_stats [n, 4] fp64 = (||res||^2, ||delta||^2, kappa, flag)).  No host sync."""
+    lib = L.load()
+    _rows32("x", x)
+    n, N = x.shape
+    _rows32("delta", delta, (n, N), x.device)
+    if not (state.is_cuda and state.device == x.device and state.dtype == torch.float64 and state.is_contiguous() and tuple(state.shape) == (n, 8)):
+        raise L.DpbError(f"state must be a contiguous fp64 [{n}, 8] tensor on {x.device}")
+    with torch.cuda.device(x.device):
+        st = torch.cuda.current_stream(x.device).cuda_stream
+        out = torch.empty_like(x)
+        stats = torch.empty(n, 4, dtype=torch.float64, device=x.device)
+        L.check(lib.dpb_newton_update(_ptr(x), _ptr(delta), _ptr(state), float(radius), _ptr(out), _ptr(stats), n, N, C.c_void_p(st)))
+    return out, stats
 
 
 def _curve_rows(name: str, a: torch.Tensor, rows: Optional[int] = None, device=None) -> None:

@@ -158,6 +158,20 @@ SYMBOLS = {
     "dpb_inv_jac_chain_scratch_bytes": (C.c_size_t, [_P, _I, _I]),
     "dpb_inv_jac_chain": (_I, [_P, _I, _P, _I, C.POINTER(_F), _P, _P, _I, C.POINTER(C.c_int32), C.POINTER(_F), C.POINTER(_F), _I, _F, _I,
                                _P, _P, _P, _P, _P, C.c_size_t]),
+    # the least-squares inverse of the Jacobian and the newton-h chain (PullbackUNet.jac_lstsq / newton_h_chain): dir, sign and scale are host arrays
+    "dpb_cgls_init_scratch_bytes": (C.c_size_t, [_L, _L, _L]),
+    "dpb_cgls_init": (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, _L, _L, _L, _P, C.c_size_t, _P]),
+    "dpb_cgls_h_step_scratch_bytes": (C.c_size_t, [_L, _L, _L]),
+    "dpb_cgls_h_step": (_I, [_P, _P, _P, _P, _P, _P, _L, _L, _L, _P, C.c_size_t, _P]),
+    "dpb_cgls_x_step_scratch_bytes": (C.c_size_t, [_L, _L, _L]),
+    "dpb_cgls_x_step": (_I, [_P, _P, _P, _P, _P, _P, C.c_double, _L, _L, _L, _P, C.c_size_t, _P]),
+    "dpb_newton_residual": (_I, [_P, _P, _P, _I, C.POINTER(C.c_int32), C.POINTER(_F), C.POINTER(_F), C.c_double, _L, _L, _P, _P]),
+    "dpb_newton_update": (_I, [_P, _P, _P, C.c_double, _P, _P, _L, _L, _P]),
+    "dpb_jac_lstsq_scratch_bytes": (C.c_size_t, [_P, _I, _I]),
+    "dpb_jac_lstsq": (_I, [_P, _I, _P, _I, C.c_double, C.c_double, C.c_double, _I, _P, _P, _P, _P, C.c_size_t]),
+    "dpb_newton_h_chain_scratch_bytes": (C.c_size_t, [_P, _I, _I]),
+    "dpb_newton_h_chain": (_I, [_P, _I, _P, _I, C.POINTER(_F), _P, _P, _I, C.POINTER(C.c_int32), C.POINTER(_F), C.POINTER(_F), _I, _I,
+                                C.c_double, C.c_double, C.c_double, C.c_double, _I, _P, _P, _P, _P, _P, C.c_size_t]),
     # the h-space guidance edit (PullbackUNet.h_space_guidance): t, the alphas, dir and scale are host arrays
     "dpb_ddim_step_asym_scratch_bytes": (C.c_size_t, [_L, _L]),
     "dpb_ddim_step_asym": (_I, [_P, _P, _P, _P, _P, _L, _L, _F, _F, _F, _F, _P, _P, C.c_size_t, _P]),

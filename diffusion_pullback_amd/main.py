@@ -56,6 +56,11 @@ decode into the same picture names; --use_sega_reg True --sega_reg_sigma s zeroe
 (edit.py:1212-1214).  --local_projection False is allowed there and needs no local basis at all.  Every chain leaves chain-<name>.pt in the obs
 folder: ||J^T u||, the h-space shift along u and |h - h0| per step.  Deviations: t is the timestep (the reference passes the index edit_t_idx);
 the reference's dynamic_thresholding / preserve_norm / preserve_contrast are methods it never defines and are not built.
+``--edit_xt newton-h`` (new; space h only; unconditional nets only) is the third value: every (pc, +-) chain starts at x_t and aims at the h-space
+shift --h_edit_step_size along +-u_pc in --vis_num damped Gauss-Newton steps, each the least-squares inverse of the Jacobian applied to the remaining
+residual by --newton_iters CGLS iterations (PullbackUNet.newton_h_chain; --newton_damping, the relative Tikhonov term, and --newton_radius, the clamp
+of a step's length in x, 0 = off), where parallel-h takes the steepest-descent direction.  Same picture names, skip rule and --local_projection False
+allowance as parallel-h; a pos chain moves h ALONG u_pc (parallel-h: against).  Every chain leaves newton-<name>.pt in the obs folder.
 ``--edit_ht default|h_space_guidance`` (the reference's flag, define_argparser.py:53) is the third way: with --edit_xt at its default and space h
 (unconditional nets only), every (pc, +-) experiment runs --vis_num chains from x_t whose h-space direction u_pc is ADDED at the tap at every DDIM step
 from --edit_t down to --no_edit_t (default 0.5), with the scales +-linspace(0, --h_edit_step_size, vis_num); --h_guidance_mode asyrp (default: the
@@ -137,6 +142,10 @@ _FLAGS = [  # (name, type, default) -- define_argparser.py:20-110, live path onl
     # parallel-h: the h-space direction held fixed, the x-space direction recomputed at every one of vis_num steps of x_edit_step_size / vis_num
     # (edit.py:1202-1229), with the SEGA rule of edit.py:1212-1214 under --use_sega_reg (sega_reg_sigma 1.0: the reference's commented default)
     ("edit_xt", str, "parallel-x"), ("use_sega_reg", str2bool, False), ("sega_reg_sigma", float, 1.0),
+    # new: --edit_xt newton-h, the third value: every chain aims at the h-space shift h_edit_step_size along u_pc in vis_num damped Gauss-Newton steps
+    # of newton_iters CGLS iterations each (PullbackUNet.newton_h_chain); newton_damping: the relative Tikhonov term; newton_radius: the clamp of a
+    # step's length in x (0: off)
+    ("newton_iters", int, 8), ("newton_damping", float, 0.1), ("newton_radius", float, 0.0),
     # define_argparser.py:53, :82-83: the third branch of the global-basis jobs.  h_space_guidance (with edit_xt at its default): the h-space direction
     # is added at the tap at every DDIM step from edit_t down to no_edit_t (edit.py:1232-1245), with scales up to h_edit_step_size; h_guidance_mode
     # is new: asyrp (the shift enters the predicted x0 only) or symmetric (the plain DDIM step of the shifted net)
@@ -187,7 +196,7 @@ def parse_args(argv=None):
                 "(its run_edit_global_frechet_mean_zt belongs to EditUncondDiffusion)")
     if args.run_edit_global_frechet_mean_zt and args.frechet_mean_space not in ("x", "h"):
         p.error("--frechet_mean_space must be x (the spans of vT) or h (the spans of u)")
-    if args.run_edit_global_frechet_mean_zt and args.frechet_mean_space == "h" and not args.local_projection and args.edit_xt != "parallel-h" and args.edit_ht != "h_space_guidance":
+    if args.run_edit_global_frechet_mean_zt and args.frechet_mean_space == "h" and not args.local_projection and args.edit_xt not in ("parallel-h", "newton-h") and args.edit_ht != "h_space_guidance":
         p.error("--local_projection False is valid for --frechet_mean_space x only")
     if args.frechet_init not in ("member", "flag"):
         p.error("--frechet_init must be member (start at local basis 0) or flag (start at the flag mean of the local bases)")
@@ -196,7 +205,7 @@ def parse_args(argv=None):
                 "(its global-basis jobs belong to EditUncondDiffusion)")
     if args.run_edit_global_flag_mean_zt and args.flag_mean_space not in ("x", "h"):
         p.error("--flag_mean_space must be x (the spans of vT) or h (the spans of u)")
-    if args.run_edit_global_flag_mean_zt and args.flag_mean_space == "h" and not args.local_projection and args.edit_xt != "parallel-h" and args.edit_ht != "h_space_guidance":
+    if args.run_edit_global_flag_mean_zt and args.flag_mean_space == "h" and not args.local_projection and args.edit_xt not in ("parallel-h", "newton-h") and args.edit_ht != "h_space_guidance":
         p.error("--local_projection False is valid for --flag_mean_space x only")
     if args.run_edit_global_flag_mean_zt and not 0 <= args.flag_rank <= args.pca_rank:
         p.error("--flag_rank must lie in [1, --pca_rank] (0: --pca_rank)")
@@ -212,19 +221,34 @@ def parse_args(argv=None):
                 "basis (its run_edit_global_hungarian_mean_zt belongs to EditUncondDiffusion)")
     if args.run_edit_global_hungarian_mean_zt and args.hungarian_mean_space not in ("x", "h"):
         p.error("--hungarian_mean_space must be x (the directions of vT) or h (the directions of u)")
-    if args.run_edit_global_hungarian_mean_zt and args.hungarian_mean_space == "h" and not args.local_projection and args.edit_xt != "parallel-h" and args.edit_ht != "h_space_guidance":
+    if args.run_edit_global_hungarian_mean_zt and args.hungarian_mean_space == "h" and not args.local_projection and args.edit_xt not in ("parallel-h", "newton-h") and args.edit_ht != "h_space_guidance":
         p.error("--local_projection False is valid for --hungarian_mean_space x only")
     if args.run_edit_global_hungarian_mean_zt and args.hungarian_distance not in ("1/cosine", "cosine"):
         p.error("--hungarian_distance must be 1/cosine (the reference's call) or cosine")
     if args.run_edit_global_hungarian_mean_zt and args.hungarian_max_sweeps < 1:
         p.error("--hungarian_max_sweeps must be >= 1")
-    if args.edit_xt not in ("parallel-x", "parallel-h"):
-        p.error("--edit_xt must be parallel-x (x-space guidance along a direction fixed at x_t) or parallel-h (the h-space direction held fixed)")
+    if args.edit_xt not in ("parallel-x", "parallel-h", "newton-h"):
+        p.error("--edit_xt must be parallel-x (x-space guidance along a direction fixed at x_t), parallel-h (the h-space direction held fixed) or "
+                "newton-h (damped Gauss-Newton steps towards an h-space shift)")
     if args.edit_xt == "parallel-h" and not args.x_edit_step_size > 0:
         p.error("--edit_xt parallel-h needs --x_edit_step_size > 0: the chain takes --vis_num steps of x_edit_step_size / vis_num")
     if args.edit_xt == "parallel-h" and "stable-diffusion" in args.model_name:
         p.error("--edit_xt parallel-h belongs to the global-basis jobs of the unconditional nets: the reference's Stable Diffusion driver has no such "
                 "branch")
+    if args.edit_xt == "newton-h":
+        if "stable-diffusion" in args.model_name:
+            p.error("--edit_xt newton-h belongs to the global-basis jobs of the unconditional nets, as parallel-h: the Stable Diffusion driver has no "
+                    "such branch")
+        if args.h_edit_step_size == 0:
+            p.error("--edit_xt newton-h needs --h_edit_step_size != 0: the h-space shift the chain aims at")
+        if args.edit_ht == "h_space_guidance":
+            p.error("--edit_xt newton-h and --edit_ht h_space_guidance exclude each other: the guidance branch runs with --edit_xt at its default")
+        if args.newton_iters < 0 or not args.newton_damping >= 0 or not args.newton_radius >= 0:
+            p.error("--newton_iters, --newton_damping and --newton_radius must not be negative (--newton_radius 0: no clamp)")
+        for job, space in (("run_edit_global_frechet_mean_zt", "frechet_mean_space"), ("run_edit_global_flag_mean_zt", "flag_mean_space"),
+                           ("run_edit_global_hungarian_mean_zt", "hungarian_mean_space")):
+            if getattr(args, job) and getattr(args, space) != "h":
+                p.error(f"--edit_xt newton-h aims at an h-space shift: --{space} must be h")
     if args.edit_ht not in ("default", "h_space_guidance"):
         p.error("--edit_ht must be default or h_space_guidance (the h-space direction added at the tap at every DDIM step from edit_t to no_edit_t)")
     if args.h_guidance_mode not in ("asyrp", "symmetric"):
@@ -370,7 +394,7 @@ def build_unet(args) -> PullbackUNet:
         if getattr(args, "trajectory_batch", 0) > 1:
             n = 2 * args.vis_num_pc
             max_batch = max(max_batch, min(args.trajectory_batch, 2 * n), min(args.trajectory_batch, n * (args.vis_num + 1)))
-            if getattr(args, "edit_xt", "parallel-x") == "parallel-h":      # the chains of one inv_jac_chain call: a cotangent each (max_batch holds them already)
+            if getattr(args, "edit_xt", "parallel-x") in ("parallel-h", "newton-h"):      # the chains of one inv_jac_chain call: a cotangent each (max_batch holds them already)
                 max_rank = max(max_rank, min(args.trajectory_batch, n))
             if getattr(args, "edit_ht", "default") == "h_space_guidance":   # vis_num chains per experiment, a plain and a shifted row each per call
                 max_batch = max(max_batch, min(args.trajectory_batch, 2 * n * args.vis_num))

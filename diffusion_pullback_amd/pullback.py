@@ -515,7 +515,8 @@ class PullbackUNet:
         """Reference: utils.inv_jac_zt, src/utils/utils.py:1117-1160: the x-space direction of the h-space direction u at one sample.  The
         reference differentiates ||h + perturb_h u - get_h(x)|| at x, whose gradient is -J^T u / ||u||; so vT = -J^T u / ||J^T u|| (one primal,
         one adjoint pass; perturb_h drops out).  u [D] -> vT [1, N_in].  Extension: u [D, k] (the reference raises NotImplementedError, the
-        code after its raise states the result) -> vT [k, N_in], row i from column i, each row normalised; the adjoints run in chunks of max_rank."""
+        code after its raise states the result) -> vT [k, N_in], row i from column i, each row normalised; the adjoints run in chunks of max_rank.
+        This is one gradient of the objective, not its minimiser: jac_lstsq solves the least-squares problem (with the opposite sign)."""
         sample = x if sample is None else sample
         timestep = t if timestep is None else timestep
         key = self._tap(op, block_idx)
@@ -613,7 +614,8 @@ class PullbackUNet:
 
     def inv_jac_xt(self, x=None, t=None, op=None, block_idx=None, u=None, perturb_h=1e-1):
         """Reference: PullBackDDPM.inv_jac_xt, src/models/ddpm/diffusion.py:347-377: inv_jac_zt without conditioning; u [D] -> vT [1, N_in], u [D, k]
-        -> vT [k, N_in] (the vendored class takes 2-D u)."""
+        -> vT [k, N_in] (the vendored class takes 2-D u).  One gradient of the objective, not its minimiser: jac_lstsq solves the least-squares
+        problem (with the opposite sign)."""
         return self.inv_jac_zt(x, t, None, op=op, block_idx=block_idx, u=u, perturb_h=perturb_h)
 
     # ------------------------------------------------------------------ the parallel-h edit chain
@@ -682,6 +684,147 @@ class PullbackUNet:
                 raise ValueError(f"inv_jac_chain: chain {b} has no direction at step {j}: ||J^T c||^2 = {float(stats[b, j, 0])} (zero or not finite); "
                                  "check=False returns the NaN states")
         return out
+
+    # ------------------------------------------------------------------ the least-squares inverse of the Jacobian and the newton-h chain
+    def _h_directions(self, what, u, key, op, block_idx):
+        d = self.engine.tap_numel(key)
+        if u is None or u.numel() % d != 0 or (u.dim() == 1 and u.numel() != d):
+            raise ValueError(f"{what}: u must be [{d}] or [{d}, k] (features of the tap ({op}, {block_idx}))")
+        U = u.reshape(1, d) if u.dim() == 1 else u.reshape(d, -1).T
+        return U.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def jac_lstsq(self, x=None, t=None, u=None, damping=0.1, mu=0.0, iters=16, tol=1e-5, encoder_hidden_states=None, op=None, block_idx=None,
+                  check=True, sample=None, timestep=None):
+        """The x-space step that realises an h-space step: delta = argmin_d ||J d - u||^2 + mu_b ||d||^2 by CGLS from d = 0 (dpb_jac_lstsq: one
+        adjoint pass, then `iters` rounds of one tangent and one adjoint pass, no Python between them), where inv_jac_zt / inv_jac_xt give the
+        steepest-descent direction -J^T u / ||J^T u|| of the same objective.  With a +u on the right-hand side, h moves ALONG u at first order: the
+        opposite sign to inv_jac_* and inv_jac_chain, which keep the reference's.
+        One sample x [1, C, H, W] with u [D] or u [D, k] as inv_jac_* take it (column i is right-hand side i), or n samples x [n, C, H, W] with
+        u [D, n] (column b belongs to sample b; t a float or n timesteps).  mu_b = mu + damping * ||J^T u_b||^2 / ||u_b||^2: `mu` is the absolute
+        Tikhonov term (mu_abs), `damping` the relative one (mu_rel), in units of the squared gain of J along u_b.  For a pure left singular direction
+        of J the step shrinks by 1 / (1 + damping); components that J sees `damping` times more weakly (sigma_i^2 = damping * sigma^2) are halved, and
+        weaker ones are suppressed in proportion.  tol: a row stops (and freezes) once ||J^T r - mu d|| <= tol * ||J^T u||.
+        Returns (delta [k, N_in], info): info["gamma"], ["resid_norm"], ["delta_norm"] are [k, iters + 1] (||J^T r - mu d||^2, ||u - J d||,
+        ||d|| after init and after every round), ["iterations"] [k] the rounds a row took, ["converged"] [k] bool (flag 1), ["flag"] [k] and ["mu"]
+        [k] = mu_b.  check=True: ValueError names a row with a non-finite input (flag 3); rows that converged (1) or met a zero denominator (2) are
+        reported in info, not raised."""
+        x = sample if x is None else x
+        t = timestep if t is None else t
+        key = self._tap(op, block_idx)
+        eng = self.engine
+        if x is None or x.dim() != 4:
+            raise ValueError("jac_lstsq: x must be [n, C, H, W]")
+        U = self._h_directions("jac_lstsq", u, key, op, block_idx)
+        n, k, iters = x.shape[0], U.shape[0], int(iters)
+        if n > 1 and k != n:
+            raise ValueError(f"jac_lstsq: {n} samples need u [D, {n}] (one right-hand side per sample), got {k} column(s)")
+        if iters < 0:
+            raise ValueError(f"jac_lstsq: iters={iters} < 0")
+        for name, v in (("damping", damping), ("mu", mu), ("tol", tol)):
+            if not (math.isfinite(float(v)) and float(v) >= 0.0):
+                raise ValueError(f"jac_lstsq: {name}={v} must be finite and not negative")
+        ctx = encoder_hidden_states
+        if ctx is not None and ctx.shape[0] not in (1, n):
+            raise ValueError(f"encoder_hidden_states has {ctx.shape[0]} rows for {n} samples: one, or one per sample")
+        tl = _timesteps(t, n)
+        tl = [tl] * n if isinstance(tl, float) else tl
+        parts = []
+        if n == 1:
+            eng.primal(x, tl, ctx, key)
+            for Ui in U.split(max(1, eng.max_tangents)):
+                parts.append(eng.jac_lstsq(key, Ui, float(mu), float(damping), float(tol), iters))
+        else:
+            group = max(1, min(eng.max_batch, eng.max_tangents))
+            for b0 in range(0, n, group):
+                sl = slice(b0, min(b0 + group, n))
+                eng.primal(x[sl], tl[sl], None if ctx is None else (ctx if ctx.shape[0] == 1 else ctx[sl]), key)
+                parts.append(eng.jac_lstsq(key, U[sl], float(mu), float(damping), float(tol), iters))
+        delta = torch.cat([p[0] for p in parts], dim=0)
+        hist = torch.cat([p[2] for p in parts], dim=1).transpose(0, 1)           # [k, iters + 1, 4]
+        return delta.to(device=x.device, dtype=x.dtype), self._lstsq_info("jac_lstsq", hist, U, float(mu), float(damping), x.device, check)
+
+    @staticmethod
+    def _lstsq_info(what, hist, U, mu, damping, device, check):
+        """hist [k, iters + 1, 4] fp64 on the engine's device -> the info dict of jac_lstsq"""
+        flag = hist[..., 3]
+        last = flag[:, -1]
+        if check and bool((last == 3).any()):
+            b = int((last == 3).nonzero()[0])
+            j = int((flag[b] == 3).nonzero()[0])
+            raise ValueError(f"{what}: row {b} met a non-finite input at " + ("the start" if j == 0 else f"iteration {j}") +
+                             "; check=False returns the NaN row")
+        live = (flag == 0).sum(dim=1)                                             # rows of hist written while the row was live
+        gamma0 = hist[:, 0, 0]
+        info = {"gamma": hist[..., 0], "resid_norm": hist[..., 1].sqrt(), "delta_norm": hist[..., 2].sqrt(),
+                "iterations": torch.clamp(live, max=hist.shape[1] - 1).to(torch.int64), "converged": last == 1, "flag": last.to(torch.int64)}
+        cc = (U.double() ** 2).sum(dim=1)
+        info["mu"] = mu + damping * torch.where(cc > 0, gamma0 / cc, torch.zeros_like(cc))      # mu_b as the solver forms it (0 / 0: mu alone)
+        return {k_: v.to(device) for k_, v in info.items()}
+
+    def newton_h_chain(self, x=None, t=None, u=None, dirs=None, signs=None, scale=1.0, steps=4, iters=8, damping=0.1, mu=0.0, tol=1e-5, radius=None,
+                       encoder_hidden_states=None, op=None, block_idx=None, final_shift=True, check=True):
+        """A damped Gauss-Newton chain towards an h-space target, as one device loop (dpb_newton_h_chain): chain b starts at x[b] and aims at
+        h0_b + scale_b * c_b, c_b = signs[b] * u[:, dirs[b]].  Outer step j of `steps`: one primal pass at the state, the residual
+        res = h0 + ((j + 1) / steps) * scale_b * c_b - h, the inner solve of jac_lstsq on it (`iters` CGLS rounds with `damping`, `mu`, `tol`), and
+        x <- x + kappa * delta with kappa = min(1, radius / ||delta||) (radius None or 0: no clamp).  Where inv_jac_chain follows the steepest-descent
+        direction -J^T c / ||J^T c|| and drifts towards what J amplifies most, this chain takes the least-squares step, so its off-axis distance h_off
+        stays smaller at the same shift.  Sign: a chain with sign +1 moves h ALONG c (h_shift > 0) -- the opposite of inv_jac_chain, which keeps the
+        reference's sign.  `scale` is in h units (the shift asked for), a float or n floats.
+        x [n, C, H, W]; t a float or n timesteps; u, dirs, signs as inv_jac_chain takes them.  More chains than min(max_batch, max_rank) run in
+        groups; a chain is never split.  Returns a dict of tensors on x.device: states [n, steps + 1, C, H, W]; h_shift, h_dist [n, steps + 1] as
+        inv_jac_chain's (final_shift=False: the last column is NaN); h_off = sqrt(max(0, h_dist^2 - h_shift^2)); resid_norm [n, steps] = ||res|| at
+        the start of each step; delta_norm [n, steps] = ||delta|| before the clamp; clip [n, steps] = kappa; inner_iterations [n, steps]; gamma
+        [n, steps, iters + 1]; flag [n, steps].  check=True: ValueError names a chain and step with a non-finite input (flag 3)."""
+        key = self._tap(op, block_idx)
+        eng = self.engine
+        if x is None or x.dim() != 4:
+            raise ValueError("newton_h_chain: x must be [n, C, H, W]")
+        n, steps, iters = x.shape[0], int(steps), int(iters)
+        if steps < 1:
+            raise ValueError(f"newton_h_chain: steps={steps} < 1")
+        if iters < 0:
+            raise ValueError(f"newton_h_chain: iters={iters} < 0")
+        U = self._h_directions("newton_h_chain", u, key, op, block_idx)
+        k = U.shape[0]
+        if dirs is None:
+            dirs = list(range(n)) if k == n and n > 1 else [0] * n
+        dirs = [int(a) for a in (dirs.tolist() if torch.is_tensor(dirs) else dirs)]
+        signs = [1.0] * n if signs is None else [float(a) for a in (signs.tolist() if torch.is_tensor(signs) else signs)]
+        sc = scale.tolist() if torch.is_tensor(scale) else scale
+        sc = [float(a) for a in sc] if isinstance(sc, (list, tuple)) else [float(sc)] * n
+        if not (len(dirs) == len(signs) == len(sc) == n):
+            raise ValueError(f"newton_h_chain: dirs, signs and scale need one entry per chain ({n}), got {len(dirs)}, {len(signs)}, {len(sc)}")
+        if any(a < 0 or a >= k for a in dirs):
+            raise ValueError(f"newton_h_chain: dirs {dirs} outside [0, {k}): u has {k} direction(s)")
+        radius = 0.0 if radius is None else float(radius)
+        for name, v in (("damping", damping), ("mu", mu), ("tol", tol), ("radius", radius)):
+            if not (math.isfinite(float(v)) and float(v) >= 0.0):
+                raise ValueError(f"newton_h_chain: {name}={v} must be finite and not negative")
+        tl = _timesteps(t, n)
+        tl = [tl] * n if isinstance(tl, float) else tl
+        ctx = encoder_hidden_states
+        if ctx is not None and ctx.shape[0] not in (1, n):
+            raise ValueError(f"encoder_hidden_states has {ctx.shape[0]} rows for {n} chains: one, or one per chain")
+        group = max(1, min(eng.max_batch, eng.max_tangents))
+        parts = []
+        for b0 in range(0, n, group):
+            sl = slice(b0, min(b0 + group, n))
+            cg = None if ctx is None else (ctx if ctx.shape[0] == 1 else ctx[sl])
+            parts.append(eng.newton_h_chain(x[sl], tl[sl], cg, key, U, dirs[sl], signs[sl], sc[sl], steps, iters, float(mu), float(damping), float(tol),
+                                            radius, final_shift))
+        states = torch.cat([p[0] for p in parts], dim=1).transpose(0, 1).contiguous()
+        hist = torch.cat([p[1] for p in parts], dim=2).permute(2, 0, 1, 3)        # [n, steps, iters + 1, 4]
+        stats = torch.cat([p[2] for p in parts], dim=1).transpose(0, 1)           # [n, steps, 4]
+        shift = torch.cat([p[3] for p in parts], dim=1).transpose(0, 1)
+        if check and bool((stats[..., 3] == 3).any()):
+            b, j = [int(a) for a in (stats[..., 3] == 3).nonzero()[0]]
+            raise ValueError(f"newton_h_chain: chain {b} met a non-finite value in outer step {j}; check=False returns the NaN states")
+        a, q = shift[..., 0], shift[..., 1]
+        live = (hist[..., 3] == 0).sum(dim=2)
+        out = {"states": states.to(device=x.device, dtype=x.dtype), "h_shift": a, "h_dist": q.sqrt(), "h_off": torch.clamp(q - a * a, min=0.0).sqrt(),
+               "resid_norm": stats[..., 0].sqrt(), "delta_norm": stats[..., 1].sqrt(), "clip": stats[..., 2],
+               "inner_iterations": torch.clamp(live, max=iters).to(torch.int64), "gamma": hist[..., 0], "flag": stats[..., 3].to(torch.int64)}
+        return {k_: v.to(x.device) for k_, v in out.items()}
 
 
     # ------------------------------------------------------------------ the h-space guidance edit
@@ -966,6 +1109,8 @@ def bind(unet, kind: str, cfg, dtype=torch.float32, device="cuda:0", **kw) -> Pu
     unet.get_h_to_e = types.MethodType(lambda self, *a, **k: self._dpb.get_h_to_e(*a, **k), unet)
     unet.local_encoder_pullback_batch = types.MethodType(lambda self, *a, **k: self._dpb.local_encoder_pullback_batch(*a, **k), unet)
     unet.inv_jac_chain = types.MethodType(lambda self, *a, **k: self._dpb.inv_jac_chain(*a, **k), unet)
+    unet.jac_lstsq = types.MethodType(lambda self, *a, **k: self._dpb.jac_lstsq(*a, **k), unet)
+    unet.newton_h_chain = types.MethodType(lambda self, *a, **k: self._dpb.newton_h_chain(*a, **k), unet)
     unet.h_space_guidance = types.MethodType(lambda self, *a, **k: self._dpb.h_space_guidance(*a, **k), unet)
     unet.pullback_geodesic = types.MethodType(lambda self, *a, **k: self._dpb.pullback_geodesic(*a, **k), unet)
     unet.curve_energy = types.MethodType(lambda self, *a, **k: self._dpb.curve_energy(*a, **k), unet)

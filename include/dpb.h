@@ -686,6 +686,75 @@ int dpb_inv_jac_chain(dpb_engine* e, int tap_buf, const float* x /*dev [n][N_in]
                       float* states /*dev [steps+1][n][N_in]*/, float* vk /*dev [steps][n][N_in] or NULL*/, double* stats /*dev [steps][n][4]*/,
                       double* shift /*dev [steps+1][n][2]*/, void* scratch, size_t scratch_bytes);
 
+/* ---- the least-squares inverse of the Jacobian and the newton-h chain (additive to ABI version 1) ---------------------------------------
+ * The reference's inv_jac_xt aims at argmin_v ||perturbed_h - f(xt + v)|| (src/models/ddpm/diffusion.py:369) and takes ONE gradient of that norm:
+ * the steepest-descent direction -J^T c / ||J^T c||, which the parallel-h chain above follows.  This section is the minimiser itself: CGLS on
+ *   min_d ||J d - c||^2 + mu ||d||^2   from d = 0   (at mu = 0 and enough iterations: the minimum-norm solution J^+ c),
+ * with the tangent and adjoint passes of the engine for the products with J and J^T, and a damped Gauss-Newton chain built on it.
+ *
+ * The solver kernels (engine-independent), R independent rows per call.  Row b carries d_b, p_b [N], r_b [D] fp32 and state[b][8] FP64 on the device =
+ * (gamma, gamma0, mu_b, ||r||^2, ||d||^2, flag, ||c||^2, x-steps taken); alpha and beta never leave the device.
+ *   dpb_cgls_init    c [R][D], w0 [R][N] (= J^T c, supplied): d = 0, r = c, p = w0, gamma = gamma0 = ||w0||^2, mu_b = mu_abs + mu_rel gamma0 / ||c||^2
+ *   dpb_cgls_h_step  q [R][D] (= J p):        alpha = gamma / (||q||^2 + mu_b ||p||^2), d <- fl32(d + alpha p), r <- fl32(r - alpha q)
+ *   dpb_cgls_x_step  w [R][N] (= J^T r):      s = w - mu_b d (fp64, not stored), gamma' = ||s||^2, beta = gamma' / gamma, p <- fl32(s + beta p),
+ *                                             gamma <- gamma'
+ * d, r and p are updated in place.  Every sum is in fp64 over fp32 operands widened on load: per-workgroup sums of slices of 4096 elements, added in
+ * slice order by every workgroup that needs the total; no floating-point atomics.  Every new element is formed in fp64 and rounded once.  A row
+ * takes 16-byte accesses when it is aligned and 4-byte ones otherwise, with the same elements per thread: a row's bits depend on that row, N and D
+ * only -- the same alone, anywhere in a stack and at any alignment.  Three launches per 256 rows and call (slice sums, apply, one thread per row for
+ * the scalars).  Each call writes one history row hist[b] = (gamma, ||r||^2, ||d||^2, flag) FP64 on the device.  Flags:
+ *   1  gamma <= tol^2 gamma0 (gamma0 = 0 included), set by init and by the x-step: converged.  The row FREEZES: every later step leaves its d, r, p
+ *      and state as they are, bit for bit, and reads none of its inputs (in fp32 a row iterated past its floor moves away from the solution again);
+ *   2  a zero or non-finite denominator (||q||^2 + mu_b ||p||^2 in the h-step; ||c||^2 = 0 with w0 != 0, or a non-finite mu_b, at init): frozen too;
+ *   3  a non-finite input (c or w0; q or p; w): NaN in d, r, p and in the scalars of exactly that row, frozen.
+ * scratch: 8-byte aligned device memory of >= dpb_cgls_*_scratch_bytes(R, N, D) bytes (the three sizes are equal: one block serves a whole
+ * solve).  Refused (dpb_last_error): a null argument, R < 1, N < 1, D < 1, a negative or non-finite mu_abs /
+ * mu_rel / tol, scratch too small, scratch / state / hist not 8-byte aligned.  No host synchronisation.
+ *
+ * dpb_newton_residual (engine-independent): res[b] = fl32(h0[b] + (frac scale[b]) (sign[b] u[dir[b]]) - h[b]), formed in fp64 and rounded once;
+ * h0, h, res [n][D], u [nu][D] fp32 on the device, dir / sign / scale HOST arrays.  dpb_newton_update (engine-independent): x_out[b] =
+ * fl32(x[b] + kappa_b d[b]) with kappa_b = min(1, radius / ||d_b||) (radius = 0: no clamp), ||d_b||^2 read from the solver's state;
+ * step_stats[b] = (||res||^2, ||d||^2, kappa, flag) FP64 on the device, the first and the last from the state as well.
+ *
+ * dpb_jac_lstsq: the solve on the primal state dpb_primal / dpb_primal_t left, with dpb_jvp's row convention -- row j belongs to sample
+ * j / (nt / batch), so one sample with k right-hand sides and n samples with one each are the same call.  One adjoint pass for w0, dpb_cgls_init, then
+ * `iters` rounds of tangent pass, h-step, adjoint pass, x-step; no host work or synchronisation between them.  The passes run for frozen rows too
+ * (the batch shape never changes).  c [nt][N_h], delta [nt][N_in], resid [nt][N_h] or NULL (c - J delta, as the recurrence carries it),
+ * hist [iters + 1][nt][4]: row 0 from init, row i from round i.  p goes into the tangent pass as it is (||p|| ~ ||J^T c||): on a 16-bit engine a
+ * right-hand side large enough to overflow the tangent activations ends as flag 3; the problem is linear, scale c down and delta up.  The primal state stays usable, as after dpb_jvp.  scratch: 256-byte aligned device
+ * memory of >= dpb_jac_lstsq_scratch_bytes(e, tap_buf, nt) bytes (0 when invalid).  Refused: what dpb_jvp refuses, iters < 0, and the solver's.
+ *
+ * dpb_newton_h_chain: n chains advanced together; chain b aims at h0_b + scale[b] c_b, c_b = sign[b] u[dir[b]].  Sign: a chain with sign = +1 moves
+ * h ALONG c -- the opposite of dpb_inv_jac_chain, which keeps the reference's sign.  Outer step j of `steps`: dpb_primal_t at states[j] up to the
+ * tap and dpb_shift_stats against the h0 kept from step 0 (shift[j]); res = dpb_newton_residual at frac = (j + 1) / steps; the solve of dpb_jac_lstsq
+ * on it (hist [steps][iters + 1][n][4]); states[j + 1] = dpb_newton_update (step_stats [steps][n][4]).  shift[steps]: one more forward pass when
+ * final_shift != 0, else NaN.  Host synchronisation: ONE for the call, the upload of the timestep embeddings in step 0.  No device allocation:
+ * scratch is 256-byte aligned device memory of >= dpb_newton_h_chain_scratch_bytes(e, tap_buf, n) bytes (0 when invalid).  The call leaves no primal
+ * state, as dpb_forward.  Refused: what dpb_inv_jac_chain refuses (scale in the place of step), a negative or non-finite radius, and the solver's. */
+size_t dpb_cgls_init_scratch_bytes(int64_t R, int64_t N, int64_t D);     /* 0 when invalid */
+int dpb_cgls_init(const float* c, const float* w0, float* delta, float* r, float* p, double* state /*dev [R][8]*/, double* hist /*dev [R][4]*/,
+                  double mu_abs, double mu_rel, double tol, int64_t R, int64_t N, int64_t D, void* scratch, size_t scratch_bytes, void* hip_stream);
+size_t dpb_cgls_h_step_scratch_bytes(int64_t R, int64_t N, int64_t D);
+int dpb_cgls_h_step(const float* q, float* delta, float* r, float* p, double* state, double* hist, int64_t R, int64_t N, int64_t D, void* scratch,
+                    size_t scratch_bytes, void* hip_stream);
+size_t dpb_cgls_x_step_scratch_bytes(int64_t R, int64_t N, int64_t D);
+int dpb_cgls_x_step(const float* w, float* delta, float* r, float* p, double* state, double* hist, double tol, int64_t R, int64_t N, int64_t D,
+                    void* scratch, size_t scratch_bytes, void* hip_stream);
+int dpb_newton_residual(const float* h0, const float* h, const float* u, int nu, const int32_t* dir /*host [n]*/, const float* sign /*host [n]*/,
+                        const float* scale /*host [n]*/, double frac, int64_t n, int64_t D, float* res, void* hip_stream);
+int dpb_newton_update(const float* x, const float* delta, const double* state /*dev [n][8]*/, double radius, float* x_out,
+                      double* step_stats /*dev [n][4]*/, int64_t n, int64_t N, void* hip_stream);
+size_t dpb_jac_lstsq_scratch_bytes(const dpb_engine* e, int tap_buf, int nt);
+int dpb_jac_lstsq(dpb_engine* e, int tap_buf, const float* c /*dev [nt][N_h]*/, int nt, double mu_abs, double mu_rel, double tol, int iters,
+                  float* delta /*dev [nt][N_in]*/, float* resid /*dev [nt][N_h] or NULL*/, double* hist /*dev [iters+1][nt][4]*/, void* scratch,
+                  size_t scratch_bytes);
+size_t dpb_newton_h_chain_scratch_bytes(const dpb_engine* e, int tap_buf, int n);
+int dpb_newton_h_chain(dpb_engine* e, int tap_buf, const float* x /*dev [n][N_in]*/, int n, const float* t /*host [n]*/,
+                       const float* ctx /*dev [n][L][Dc] or NULL*/, const float* u /*dev [nu][N_h]*/, int nu, const int32_t* dir,
+                       const float* sign, const float* scale /*host [n]*/, int steps, int iters, double mu_abs, double mu_rel, double tol,
+                       double radius, int final_shift, float* states /*dev [steps+1][n][N_in]*/, double* hist /*dev [steps][iters+1][n][4]*/,
+                       double* step_stats /*dev [steps][n][4]*/, double* shift /*dev [steps+1][n][2]*/, void* scratch, size_t scratch_bytes);
+
 /* ---- the h-space guidance edit (additive to ABI version 1) --------------------------------------------------------------------------
  * The edit_ht == 'h_space_guidance' branch of the global-basis edit jobs (src/modules/edit.py:1232-1245, :1500-1513; the reference calls a
  * h_space_guidance method it never defines), as Kwon et al. state it (Asyrp): a chain carries a state x, a direction c = u[dir] at the tap and a
